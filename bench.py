@@ -20,7 +20,9 @@ N > 1: one process per GPU, utterances sharded by rank (weak scaling: 32 per GPU
 only exchange is ONE fixed-capacity RCCL all-gather of the generated mels + lengths at the end of
 each step; per-rank step times and the shard imbalance are reported beside the max-over-ranks time.
 
-Output: ONE JSON line on rank 0 with the whole-job mel-frames/s, plus
+Output: ONE JSON line on rank 0 with the whole-job mel-frames/s and `ms_per_step`.  A plain run sets up, warms up, times
+the K steps and prints that line, nothing else; `--dump-outputs DIR` also writes what the last timed step returned (mel,
+mel_lens, and on one GPU the vocoder waveform and prosody codes of the full path) as DIR/<name>.npy, and `--full` adds
   roofline      - the GEMM/conv engine (dominant kernel family) against the f32-EQUIVALENT ceiling of the matrix
                   pipe form that executes most of its FLOPs (x3h: 2500 TF/s / 3 products = 833.3; the fractions of the
                   x6 ceiling 416.7, of the launch-mix ceiling and of the f32-MFMA peak 157.3 are reported beside it):
@@ -30,7 +32,10 @@ Output: ONE JSON line on rank 0 with the whole-job mel-frames/s, plus
   cpu_baseline  - the oracle (a port of the reference's path; dense primitives on ATen, the kernels the
                   reference dispatches to) timed on this box's host cores on a bounded sample of the
                   same workload (rank 0, N = 1 only) three ways - 16 threads, every core in one process,
-                  and a process pool of cores/16 workers x 16 threads; `value` is the highest of them.
+                  and a process pool of cores/16 workers x 16 threads; `value` is the highest of them;
+  workloads     - default C3 run on one GPU: the other BASELINE configurations (C2 / C1 / C5, the C4 anchor on one
+                  rank), three batches in flight and the path with the ADM's own durations, each timed on its own.
+The `--no-roofline` / `--no-cpu-baseline` / `--no-sub-workloads` switches drop single parts of a `--full` run.
 """
 from __future__ import annotations
 
@@ -61,6 +66,28 @@ STAGES_FULL = ["vqpe", "mrte", "adm", "plm", "decoder", "vocoder"]
 # step from the committed per-kernel PMC passes (FETCH_SIZE x 2, gfx950 correction): profiles/r05_c1_per_kernel_pmc.md
 C1_HBM_GB_PER_STEP = 28.1
 HBM_ACHIEVABLE_GBS = 6300.0       # MI355X_MICROARCH.md: what a streaming kernel reaches of the 8 TB/s spec
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000 - 64 * 1024     # --dump-outputs: at most 64 MB of .npy files, headers included
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: array} as outdir/<name>.npy, float64 for integer data and float32 otherwise.  When the whole set is
+    larger than DUMP_BUDGET_BYTES the largest arrays are replaced by a fixed, seeded sample of their elements (flattened,
+    in index order; the same indices on every run), so that two builds can still be compared element for element."""
+    os.makedirs(outdir, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype.kind in "biu" or v.dtype == np.float64 else np.float32)
+           for k, v in arrays.items()}
+    total = sum(v.nbytes for v in out.values())
+    for k in sorted(out, key=lambda k_: -out[k_].nbytes):
+        if total <= DUMP_BUDGET_BYTES:
+            break
+        v = out[k]
+        keep = max(1, (v.nbytes - (total - DUMP_BUDGET_BYTES)) // v.itemsize)
+        idx = np.sort(np.random.Generator(np.random.PCG64(1234)).choice(v.size, keep, replace=False))
+        out[k] = v.reshape(-1)[idx]
+        total -= v.nbytes - out[k].nbytes
+        print(f"--dump-outputs: {k} {v.shape} written as a seeded sample of {keep} elements", file=sys.stderr)
+    for k, v in out.items():
+        np.save(os.path.join(outdir, f"{k}.npy"), v)
 
 
 def mfma_peak_of(model):
@@ -350,10 +377,15 @@ def main() -> None:
     ap.add_argument("--jitter", type=float, default=None,
                     help="utterance lengths scaled by U(1 - jitter, 1): ragged batches (default 0 for weak, 0.3 for strong, "
                          "where it is what makes the shard balance `slowest_over_mean` mean something)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline (one profiled and one traced step, "
+                         "clock probes), the CPU baseline and, on the default C3 run, the other workloads (`workloads`)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-sub-workloads", action="store_true",
-                    help="default C3 run only: skip the C2 / C1 / C5 sub-results (`workloads` in the JSON line)")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="--full, default C3 run only: skip the C2 / C1 / C5 sub-results (`workloads` in the JSON line)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline")
     ap.add_argument("--inflight", type=int, default=1,
                     help="batches in flight: step i runs on handle i %% N and HIP stream i %% N (N model handles, each with its "
                          "own weights and workspace); a step is still one batch, the timed region still ends with a device-wide "
@@ -376,6 +408,8 @@ def main() -> None:
                     help="test hook: exercise the launch / sharding / all-gather / reporting logic of this script on "
                          "CPU (gloo) with a stand-in engine - measures nothing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -504,11 +538,13 @@ def main() -> None:
                 ev[1].record()
         into = exchange.mel_view(B) if (exchange is not None and do_exchange and B) else None
         out = model.synthesize_batch(phone, pl, mel_in, ml, forced_dur=dur, forced_codes=codes, run_plm=full,
-                                     vocoder=full, tm_cap=shape.Tm, skip_adm=args.skip_adm, prompt_vqpe=side, mel_out=into)
+                                     vocoder=full, tm_cap=shape.Tm, skip_adm=args.skip_adm, prompt_vqpe=side, mel_out=into,
+                                     return_aux=not dry)
         mel, lens = out[0], out[1]
+        aux = out[2] if len(out) > 2 else None    # device tensors the call fills anyway (durations, codes, waveform)
         if world > 1 and do_exchange:   # the path's only exchange: ONE fixed-capacity RCCL all-gather over xGMI, lengths stay on the device
             mel, lens = gather_mels(mel, lens, host_lens=False, exchange=exchange)
-        return mel, lens
+        return mel, lens, aux
 
     if args.ab and not dry and world == 1:
         b_opts = [kv.split("=") for kv in args.ab.split(",")]
@@ -540,7 +576,7 @@ def main() -> None:
     sync()
     t0 = time.perf_counter()
     for i_ in range(args.steps):
-        step(i=i_)
+        last = step(i=i_)
     sync()
     local_elapsed = time.perf_counter() - t0          # this rank's own step loop (before waiting for the others)
     if world > 1:
@@ -563,6 +599,23 @@ def main() -> None:
         total_frames = float(frames_per_step)
     ms_per_step = elapsed / args.steps * 1e3
     value = total_frames * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the timed path received in its last step, padding past each utterance's length zeroed
+        mel_o, lens_o, aux = last
+        lens_h = np.asarray(lens_o.cpu() if hasattr(lens_o, "cpu") else lens_o).astype(np.int64)
+        mel_h = mel_o.cpu().numpy().copy()
+        for b_, n_ in enumerate(lens_h):
+            mel_h[b_, n_:] = 0.0
+        dump = {"mel": mel_h, "mel_lens": lens_h}
+        if aux is not None and world == 1 and full:
+            codes_h = aux["codes"].cpu().numpy().copy()
+            wav_h = aux["wav"].cpu().numpy().copy()
+            pad_ = int(getattr(h, "inference_padding", 0))
+            for b_, n_ in enumerate(lens_h):
+                codes_h[b_, -(-n_ // g.vqpe.stride):] = 0
+                wav_h[b_, (n_ + 2 * pad_) * h.hop:] = 0.0
+            dump.update({"codes": codes_h, "wav": wav_h})
+        dump_outputs(args.dump_outputs, dump)
 
     result = {
         "metric": "mel-frames/sec (whole node)", "value": round(value, 1), "unit": "mel-frames/s",
@@ -595,7 +648,7 @@ def main() -> None:
 
     if dry:
         result["data"] = "DRY RUN on CPU with a stand-in engine: not a measurement"
-    if rank == 0 and not args.no_roofline and not dry:
+    if rank == 0 and args.full and not args.no_roofline and not dry:
         # (1) one PROFILED step (events at the stage boundaries only - no per-launch instrumentation)
         # (rank 0 only: these extra steps must not enter the collective the other ranks have already left)
         model.set_profiling(True)
@@ -711,7 +764,7 @@ def main() -> None:
                             "tflops": round(r["flops"] / max(r["ms"], 1e-9) / 1e9, 2)} for r in tr],
         }
 
-    if rank == 0 and world == 1 and not dry and not args.no_roofline and "roofline" in result:
+    if rank == 0 and world == 1 and not dry and args.full and not args.no_roofline and "roofline" in result:
         # sustained shader clock under the dominant kernel, measured live: one wave of gemm_x6_ldr_kernel reads s_memtime
         # (shader cycles) and s_memrealtime (constant rate) around its K loop; the bf16 pipe's ceiling scales with it
         from megatts2_amd import runtime as rt
@@ -737,8 +790,8 @@ def main() -> None:
                                          "shorter than the power manager's reaction time stay near 1.9-2.2 GHz"}
             rf["peak_at_sustained_clock"] = round(rf["peak"] * clk / 2.4, 1)
             rf["frac_of_peak_at_sustained_clock"] = round(rf["achieved"] / (rf["peak"] * clk / 2.4), 4)
-    if (rank == 0 and world == 1 and not dry and args.workload == "C3" and not args.no_sub_workloads and not args.batch
-            and not args.skip_adm and not args.opt):
+    if (rank == 0 and world == 1 and not dry and args.full and args.workload == "C3" and not args.no_sub_workloads
+            and not args.batch and not args.skip_adm and not args.opt):
         subs = {}
         # what else this repo publishes, timed by the same command: the throughput mode with three
         # batches in flight (FIRST: its two extra handles need ~6 GB each, before the big sub-workloads grow this handle's
@@ -756,7 +809,7 @@ def main() -> None:
             except Exception as e:
                 subs[nm] = {"error": str(e)[:200]}
         result["workloads"] = subs
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not dry:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not dry:
         # the oracle (a port of the reference path; dense primitives on ATen = the kernels the reference itself
         # dispatches to) on the utterances of the same workload for up to ~25 s, in its own process with a hard limit.
         # kind "port", not "reference": /root/reference does not exist on the GPU box (the port is pinned to it by

@@ -392,9 +392,51 @@ def make_vq_near_ties() -> None:
               int((ora != idx).sum()), "rows", np.nonzero(ora != idx)[0][:10])
 
 
+def make_host_tables() -> None:
+    """Host-side fixtures, so that the CPU tests need no reference tree: the model hyper-parameters of each
+    configs/*.yaml (numbers and names only: the `init_args` values of model.G / model.plm / model.adm, every
+    `class_path` dropped), the key order and shapes of the reference modules' state_dict(), and what the reference's
+    SymbolTable makes of a seeded random k2 table and of a table that lists <eps> with a non-zero id."""
+    import json
+
+    import yaml
+    root = ref_shim.REFERENCE_ROOT
+
+    def hparams(node):
+        if isinstance(node, dict):
+            return {k: hparams(v) for k, v in node.items() if k != "class_path"}
+        return node
+    for name, key in (("gan", "G"), ("plm", "plm"), ("adm", "adm")):
+        with open(os.path.join(root, "configs", f"config_{name}.yaml")) as f:
+            tree = yaml.safe_load(f)
+        with open(os.path.join(GOLDEN, f"hparams_{name}.yaml"), "w") as f:
+            yaml.safe_dump({"model": {key: hparams(tree["model"][key])}}, f, sort_keys=False)
+    ref = ref_shim.load()
+    from utils.utils import instantiate_class
+    G = ref.MegaG.from_hparams(f"{root}/configs/config_gan.yaml")
+    plm = instantiate_class((), yaml.safe_load(open(f"{root}/configs/config_plm.yaml"))["model"]["plm"])
+    adm = instantiate_class((), yaml.safe_load(open(f"{root}/configs/config_adm.yaml"))["model"]["adm"])
+    shapes = {nm: [[k, list(v.shape)] for k, v in mod.state_dict().items()] for nm, mod in (("G", G), ("plm", plm), ("adm", adm))}
+    with open(os.path.join(GOLDEN, "ref_state_dict_shapes.json"), "w") as f:
+        json.dump(shapes, f)
+    from utils.symbol_table import SymbolTable as Ref
+    rng = np.random.default_rng(5)
+    syms = sorted({"".join(chr(int(c)) for c in rng.integers(48, 123, rng.integers(1, 5))) for _ in range(200)})
+    ids = rng.permutation(np.arange(1, len(syms) + 1))
+    table = "".join(f"{s} {i}\n" for s, i in zip(syms, ids))
+    moved = Ref.from_str("<eps> 4\na 1\nb 2\n")
+    out = {"table": table, "symbols": Ref.from_str(table.strip()).symbols,      # what Ref.from_file reads
+           "moved": {"eps_id": moved["<eps>"], "id0": moved[0], "symbols": moved.symbols}}
+    with open(os.path.join(GOLDEN, "symbols_random_ref.json"), "w", encoding="utf-8") as f:
+        json.dump(out, f, ensure_ascii=False)
+
+
 def main() -> None:
     os.makedirs(GOLDEN, exist_ok=True)
     torch.manual_seed(0)
+    if "--extra-host" in sys.argv:
+        make_host_tables()
+        return
     if "--extra-vq" in sys.argv:
         make_vq_near_ties()
         return

@@ -14,7 +14,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with `pytest -m gpu` on the GPU box)")
-    config.addinivalue_line("markers", "reference: needs the reference tree at /root/reference (build container only)")
 
 
 def _cfgs(kind):

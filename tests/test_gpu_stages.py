@@ -634,7 +634,7 @@ def test_prod_strong_scaling_shard_geometry_b96_ragged():
 
 
 def test_prod_strong_scaling_the_exact_256_utterance_call():
-    """What `bench.py --gpus 1 --scaling strong` (and the default line's `workloads.C4_strong_n1`) TIMES: the 256 ragged
+    """What `bench.py --gpus 1 --scaling strong` (and `bench.py --full`'s `workloads.C4_strong_n1`) TIMES: the 256 ragged
     utterances of BASELINE configs[3] (C4 geometry, lengths U(0.7, 1), seed 1004) in ONE synthesize_batch call with the prompt's
     VQ-PE and the vocoder, exactly as the bench issues it (that call was parity-checked at B = 96 only).
     The longest, the shortest and a middle utterance against the oracle run alone: the ADM's own durations, the free-running
@@ -680,7 +680,7 @@ def test_prod_strong_scaling_the_exact_256_utterance_call():
 
 
 def test_prod_three_batches_in_flight_equal_three_sequential_calls():
-    """`bench.py --inflight 3` (the default line's `workloads.C3_inflight3`) at production size: three handles, each with its
+    """`bench.py --inflight 3` (`bench.py --full`'s `workloads.C3_inflight3`) at production size: three handles, each with its
     own weights and arena, three HIP streams, three DIFFERENT C3 batches enqueued back to back without a host synchronisation -
     mels, waveforms, prosody codes, durations and prompt VQ-PE codes bit-identical to the same three batches run one after
     the other on one handle (exercised on the tiny model only)."""

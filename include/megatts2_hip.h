@@ -140,6 +140,28 @@ int mt2_plm_infer_prompted(mt2_model* m, void* stream, const float* cond, const 
                            int B, const int64_t* prefix_codes, int P, int max_steps, int64_t* codes,
                            float* last_logits);
 
+/* ---- seeded sampling of the PLM's prosody codes (no reference counterpart: the reference decodes greedily,
+ * models/megatts2.py:165-181; greedy stays the default and the parity path).  Per step and utterance, over the vq_bins
+ * logits z: rank order = value descending, index ascending; K = the first top_k (all when 0); w = exp((z - max z) /
+ * temperature) on K; R = the shortest rank-order prefix of K holding top_p of sum_K w; the code is the first index of R,
+ * walked in ascending index order, whose running sum of w exceeds u * sum_R w (the last index of R when rounding leaves
+ * none).  u = (x0 >> 8) * 2^-24, x0 = the first word of Philox4x32-10 with key = the utterance's seed (lo, hi) and counter
+ * = (target position, 0, 0, 0) - position 0 is the first code after the BOS and after any prompt prefix.  A code depends on
+ * (seed, position, logits) only: batch, slot, stream groups and a repeated call do not change it.  top_k = 1 (or a tiny
+ * top_p) is the greedy argmax exactly.  Invalid parameters (temperature <= 0 or not finite, top_k outside [0, vq_bins],
+ * top_p outside (0, 1], reserved != 0, seeds == NULL) are an error before anything is launched. */
+typedef struct mt2_sampling {
+    float temperature;        /* > 0 */
+    int32_t top_k;            /* 0 = all vq_bins */
+    float top_p;              /* (0, 1]; 1 = off */
+    int32_t reserved;         /* must be 0 */
+    const uint64_t* seeds;    /* HOST, one per utterance of the call */
+} mt2_sampling;
+/* mt2_plm_infer_prompted with sampling (NULL: greedy, identical to mt2_plm_infer_prompted) */
+int mt2_plm_infer_sampled(mt2_model* m, void* stream, const float* cond, const int32_t* lens /*host*/, int Tq_max, int B,
+                          const int64_t* prefix_codes, int P, int max_steps, int64_t* codes, float* last_logits,
+                          const mt2_sampling* sampling);
+
 /* ---- generator.vqpe.vq.decode(codes) (modules/quantization/vq.py:109-113)
  * codes int64 [n_q=1, B, Tq_max] -> out f32 [B, vq_dim, Tq_max]. */
 int mt2_vq_decode(mt2_model* m, void* stream, const int64_t* codes, int B, int Tq_max, float* out);
@@ -220,6 +242,21 @@ int mt2_synthesize_prompt_conditioned(mt2_model* m, void* stream, const int64_t*
                                       const int32_t* prompt_dur /*host*/, const int32_t* forced_dur /*host*/, int Tq_cap, int flags,
                                       float* mel, int Tm_cap, int32_t* mel_lens /*host*/, int32_t* dur_out, int64_t* codes_out,
                                       float* wav, int64_t* prompt_codes);
+/* the two synthesis calls with the PLM's codes sampled (mt2_sampling; seeds[b] for utterance b).  NULL: greedy, identical to
+ * the call without the suffix.  mt2_workspace_query bounds the arena of these calls too. */
+int mt2_synthesize_batch_sampled(mt2_model* m, void* stream, const int64_t* phone, const int32_t* phone_lens /*host*/,
+                                 int Np_max, const float* prompt_mel, const int32_t* prompt_lens /*host*/, int Tp_max,
+                                 int B, const int32_t* forced_dur /*host*/, const int64_t* forced_codes, int Tq_cap,
+                                 int flags, float* mel, int Tm_cap, int32_t* mel_lens /*host*/, int32_t* dur_out,
+                                 int64_t* codes_out, float* wav, int64_t* prompt_codes, const mt2_sampling* sampling);
+int mt2_synthesize_prompt_conditioned_sampled(mt2_model* m, void* stream, const int64_t* phone,
+                                              const int32_t* phone_lens /*host*/, int Np_max, const float* prompt_mel,
+                                              const int32_t* prompt_lens /*host*/, int Tp_max, int B,
+                                              const int64_t* prompt_phone, const int32_t* prompt_phone_lens /*host*/,
+                                              int Npp_max, const int32_t* prompt_dur /*host*/,
+                                              const int32_t* forced_dur /*host*/, int Tq_cap, int flags, float* mel,
+                                              int Tm_cap, int32_t* mel_lens /*host*/, int32_t* dur_out, int64_t* codes_out,
+                                              float* wav, int64_t* prompt_codes, const mt2_sampling* sampling);
 
 /* ---- tuning.  Every switch lives in the handle (no process-global state): two handles do not see each other's settings.  None
  * changes results beyond f32 summation order.  The 30 names of round 6 (default in parentheses; the options the A/B records closed
@@ -315,6 +352,11 @@ int mt2_op_gemm_tm_pairs(void* stream, const float* X, int ldx, int Rx, int a_mu
                          const float* ln_gamma, const float* ln_beta, float ln_eps, float* stat_out, const float* ln_stat, int ln_nt);
 int mt2_op_layernorm(void* stream, const float* x, int ldx, const float* gamma, const float* beta, const float* R1,
                      int ldr1, const int32_t* valid, float* out, int ldo, int M, int C, float eps, int act);
+/* The PLM's sampling draw on A rows of N <= 1024 logits (row stride ld): out[j] (int64, device) = the code of row j under the
+ * rule of mt2_sampling with Philox key seeds_dev[j] (uint64, device) and counter positions_dev[j] (int32, device).
+ * s->seeds is not read here (may be NULL); the other fields are checked as for the _sampled calls. */
+int mt2_op_sample_rows(void* stream, const float* logits, int ld, int N, int A, const mt2_sampling* s, const uint64_t* seeds_dev,
+                       const int32_t* positions_dev, int64_t* out);
 int mt2_op_attention(void* stream, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv,
                      float* O, int ldo, const int32_t* q_start, const int32_t* q_len, const int32_t* kv_start,
                      const int32_t* kv_len, int B, int H, int D, int max_qlen, float scale);

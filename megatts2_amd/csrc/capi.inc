@@ -33,6 +33,15 @@ static void require_ready(mt2_model* m, int need = 0) {
     MT2_REQUIRE(!(need & NEED_PLM) || m->has_plm, "PLM (plm.*) weights were not loaded into this handle");
     MT2_REQUIRE(!(need & NEED_VOC) || m->has_vocoder, "HiFi-GAN (hifigan.*) weights were not loaded");
 }
+// the parameters of a sampled call (include/megatts2_hip.h, mt2_sampling), checked before anything is launched
+static void check_sampling(const mt2_sampling& s, int bins, bool host_seeds) {
+    MT2_REQUIRE(std::isfinite(s.temperature) && s.temperature > 0.0f, "sampling temperature must be finite and > 0");
+    MT2_REQUIRE(s.top_k >= 0 && s.top_k <= bins, "sampling top_k must be in [0, vq_bins]");
+    MT2_REQUIRE(s.top_p > 0.0f && s.top_p <= 1.0f, "sampling top_p must be in (0, 1]");
+    MT2_REQUIRE(s.reserved == 0, "mt2_sampling.reserved must be 0");
+    MT2_REQUIRE(!host_seeds || s.seeds != nullptr, "sampling needs one seed per utterance (seeds is NULL)");
+    MT2_REQUIRE(bins <= 1024, "the sampling kernel serves at most 1024 bins");
+}
 static std::vector<int> iota_rows(int B, int stride) {
     std::vector<int> v(B);
     for (int b = 0; b < B; ++b) v[b] = b * stride;
@@ -254,7 +263,7 @@ int mt2_workspace_query(const mt2_model* m, int B, int Np_max, int Tp_max, int T
     if (flags & MT2_RUN_PLM) {
         const long long d = cfg.plm_vq_dim + cfg.plm_tc_dim, ff = 4 * d, M = (long long)B * Tq;
         const int G = std::max(1, std::min(m->plm_groups > 0 ? m->plm_groups : m->ar_groups, B));
-        f += 2ll * B * (Tq + 1) + 2ll * B * Tq + 8ll * B + (long long)B * cfg.plm_bins;
+        f += 2ll * B * (Tq + 1) + 2ll * B * Tq + 8ll * B + (long long)B * cfg.plm_bins + 2ll * B;   // + seeds of a sampled call
         f += M * d + 3 * M * d + (long long)B * d + G * enc(0, d, ff) + enc(M + 2ll * B * G, d, ff) - enc(0, d, ff);
     }
     f += DR * cfg.dec_hidden * 5 + DR * cfg.mel_bins;
@@ -455,11 +464,13 @@ int mt2_max_pool_ceil(mt2_model* m, void* stream, const float* x, const int32_t*
     MT2_API_END
 }
 
-int mt2_plm_infer_prompted(mt2_model* m, void* stream, const float* cond, const int32_t* lens, int Tq_max, int B,
-                           const int64_t* prefix_codes, int P, int max_steps, int64_t* codes, float* last_logits) {
+int mt2_plm_infer_sampled(mt2_model* m, void* stream, const float* cond, const int32_t* lens, int Tq_max, int B,
+                          const int64_t* prefix_codes, int P, int max_steps, int64_t* codes, float* last_logits,
+                          const mt2_sampling* sampling) {
     MT2_API_BEGIN
     require_ready(m, NEED_PLM);
     MT2_REQUIRE(B >= 1 && P >= 0 && max_steps >= 0 && (P == 0 || prefix_codes != nullptr), "bad arguments");
+    if (sampling) check_sampling(*sampling, m->cfg.plm_bins, true);
     std::vector<int> total(B);
     for (int b = 0; b < B; ++b) {
         MT2_REQUIRE(lens[b] >= 1 && lens[b] <= Tq_max, "length out of range");
@@ -471,9 +482,14 @@ int mt2_plm_infer_prompted(mt2_model* m, void* stream, const float* cond, const 
     MT2_HIP(hipMemsetAsync(codes, 0, sizeof(int64_t) * (size_t)B * Tq_max, c.s));
     ArPrefix pre;
     pre.P = P; pre.data = prefix_codes; pre.max_steps = max_steps;
-    plm_run(c, cond, m->cfg.plm_tc_dim, iota_rows(B, P + Tq_max), total.data(), B, codes, Tq_max, last_logits, Tq_max, pre);
+    plm_run(c, cond, m->cfg.plm_tc_dim, iota_rows(B, P + Tq_max), total.data(), B, codes, Tq_max, last_logits, Tq_max, pre,
+            sampling);
     ids_verdict(c);
     MT2_API_END
+}
+int mt2_plm_infer_prompted(mt2_model* m, void* stream, const float* cond, const int32_t* lens, int Tq_max, int B,
+                           const int64_t* prefix_codes, int P, int max_steps, int64_t* codes, float* last_logits) {
+    return mt2_plm_infer_sampled(m, stream, cond, lens, Tq_max, B, prefix_codes, P, max_steps, codes, last_logits, nullptr);
 }
 int mt2_plm_infer(mt2_model* m, void* stream, const float* cond, const int32_t* lens, int Tq_max, int B,
                   int64_t* codes, float* last_logits) {
@@ -677,14 +693,15 @@ static void prompt_vqpe_side(const Ctx& c, const float* prompt_mel, const int32_
 
 // ---------------------------------------------------------------------------------------------------
 // Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) on a batch
-int mt2_synthesize_batch(mt2_model* m, void* stream, const int64_t* phone, const int32_t* phone_lens, int Np_max,
-                         const float* prompt_mel, const int32_t* prompt_lens, int Tp_max, int B,
-                         const int32_t* forced_dur, const int64_t* forced_codes, int Tq_cap, int flags, float* mel,
-                         int Tm_cap, int32_t* mel_lens, int32_t* dur_out, int64_t* codes_out, float* wav,
-                         int64_t* prompt_codes) {
+int mt2_synthesize_batch_sampled(mt2_model* m, void* stream, const int64_t* phone, const int32_t* phone_lens, int Np_max,
+                                 const float* prompt_mel, const int32_t* prompt_lens, int Tp_max, int B,
+                                 const int32_t* forced_dur, const int64_t* forced_codes, int Tq_cap, int flags, float* mel,
+                                 int Tm_cap, int32_t* mel_lens, int32_t* dur_out, int64_t* codes_out, float* wav,
+                                 int64_t* prompt_codes, const mt2_sampling* sampling) {
     MT2_API_BEGIN
     require_ready(m, NEED_G);
     MT2_REQUIRE(B >= 1, "empty batch");
+    if (sampling) check_sampling(*sampling, m->cfg.plm_bins, true);
     MT2_CALL(m, stream);
     const mt2_config& cfg = m->cfg;
     const int H = cfg.mrte_hidden, Dq = cfg.vq_dim;
@@ -757,7 +774,7 @@ int mt2_synthesize_batch(mt2_model* m, void* stream, const int64_t* phone, const
         MT2_REQUIRE(flags & MT2_RUN_PLM, "neither forced codes nor MT2_RUN_PLM given");
         int64_t* cdev = codes_out ? codes_out : c.ws.get<int64_t>((size_t)B * Tq_cap);
         MT2_HIP(hipMemsetAsync(cdev, 0, sizeof(int64_t) * (size_t)B * Tq_cap, c.s));
-        plm_run(c, cond, H, fp.q_row0, fp.tq.data(), B, cdev, Tq_cap, nullptr, 0);
+        plm_run(c, cond, H, fp.q_row0, fp.tq.data(), B, cdev, Tq_cap, nullptr, 0, ArPrefix(), sampling);
         codes = cdev;
     } else if (codes_out && codes_out != forced_codes) {
         MT2_HIP(hipMemcpyAsync(codes_out, forced_codes, sizeof(int64_t) * (size_t)B * Tq_cap,
@@ -780,6 +797,15 @@ int mt2_synthesize_batch(mt2_model* m, void* stream, const int64_t* phone, const
     }
     MT2_API_END
 }
+int mt2_synthesize_batch(mt2_model* m, void* stream, const int64_t* phone, const int32_t* phone_lens, int Np_max,
+                         const float* prompt_mel, const int32_t* prompt_lens, int Tp_max, int B,
+                         const int32_t* forced_dur, const int64_t* forced_codes, int Tq_cap, int flags, float* mel,
+                         int Tm_cap, int32_t* mel_lens, int32_t* dur_out, int64_t* codes_out, float* wav,
+                         int64_t* prompt_codes) {
+    return mt2_synthesize_batch_sampled(m, stream, phone, phone_lens, Np_max, prompt_mel, prompt_lens, Tp_max, B, forced_dur,
+                                        forced_codes, Tq_cap, flags, mel, Tm_cap, mel_lens, dur_out, codes_out, wav,
+                                        prompt_codes, nullptr);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Prompt-conditioned synthesis as ONE call (SURVEY 8f row f1): the layout the PLM is trained on (modules/datamodule.py:161-177,
@@ -788,15 +814,16 @@ int mt2_synthesize_batch(mt2_model* m, void* stream, const int64_t* phone, const
 // the prompt's and the target's tc_latent (the mel context is shared; only the phone branch differs: both phone sets run
 // through the phone encoder as one batch of 2 B sequences); the prompt's VQ-PE runs on the handle's side stream beside the
 // ADM; nothing leaves the device between the stages except the durations (one D2H, as in the reference).
-int mt2_synthesize_prompt_conditioned(mt2_model* m, void* stream, const int64_t* phone, const int32_t* phone_lens, int Np_max,
-                                      const float* prompt_mel, const int32_t* prompt_lens, int Tp_max, int B,
-                                      const int64_t* prompt_phone, const int32_t* prompt_phone_lens, int Npp_max,
-                                      const int32_t* prompt_dur, const int32_t* forced_dur, int Tq_cap, int flags, float* mel,
-                                      int Tm_cap, int32_t* mel_lens, int32_t* dur_out, int64_t* codes_out, float* wav,
-                                      int64_t* prompt_codes) {
+int mt2_synthesize_prompt_conditioned_sampled(mt2_model* m, void* stream, const int64_t* phone, const int32_t* phone_lens,
+                                              int Np_max, const float* prompt_mel, const int32_t* prompt_lens, int Tp_max, int B,
+                                              const int64_t* prompt_phone, const int32_t* prompt_phone_lens, int Npp_max,
+                                              const int32_t* prompt_dur, const int32_t* forced_dur, int Tq_cap, int flags,
+                                              float* mel, int Tm_cap, int32_t* mel_lens, int32_t* dur_out, int64_t* codes_out,
+                                              float* wav, int64_t* prompt_codes, const mt2_sampling* sampling) {
     MT2_API_BEGIN
     require_ready(m, NEED_G | NEED_ADM | NEED_PLM);
     MT2_REQUIRE(B >= 1 && prompt_phone && prompt_phone_lens && prompt_dur && prompt_codes, "bad arguments");
+    if (sampling) check_sampling(*sampling, m->cfg.plm_bins, true);
     MT2_CALL(m, stream);
     const mt2_config& cfg = m->cfg;
     const int H = cfg.mrte_hidden, Dq = cfg.vq_dim, pool = cfg.vq_stride;
@@ -879,11 +906,22 @@ int mt2_synthesize_prompt_conditioned(mt2_model* m, void* stream, const int64_t*
     MT2_HIP(hipMemsetAsync(cdev, 0, sizeof(int64_t) * (size_t)B * Tq_cap, c.s));
     ArPrefix pre;
     pre.P = P; pre.data = prompt_codes; pre.stride = (Tp_max + pool - 1) / pool;
-    plm_run(c, cond, H, q0, total.data(), B, cdev, Tq_cap, nullptr, 0, pre);
+    plm_run(c, cond, H, q0, total.data(), B, cdev, Tq_cap, nullptr, 0, pre, sampling);
     st.mark("plm");
     decode_and_vocode(c, st, xdec, fp, ip, cdev, flags, mel, Tm_cap, wav, B);
     st.finish();
     MT2_API_END
+}
+int mt2_synthesize_prompt_conditioned(mt2_model* m, void* stream, const int64_t* phone, const int32_t* phone_lens, int Np_max,
+                                      const float* prompt_mel, const int32_t* prompt_lens, int Tp_max, int B,
+                                      const int64_t* prompt_phone, const int32_t* prompt_phone_lens, int Npp_max,
+                                      const int32_t* prompt_dur, const int32_t* forced_dur, int Tq_cap, int flags, float* mel,
+                                      int Tm_cap, int32_t* mel_lens, int32_t* dur_out, int64_t* codes_out, float* wav,
+                                      int64_t* prompt_codes) {
+    return mt2_synthesize_prompt_conditioned_sampled(m, stream, phone, phone_lens, Np_max, prompt_mel, prompt_lens, Tp_max, B,
+                                                     prompt_phone, prompt_phone_lens, Npp_max, prompt_dur, forced_dur, Tq_cap,
+                                                     flags, mel, Tm_cap, mel_lens, dur_out, codes_out, wav, prompt_codes,
+                                                     nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1072,6 +1110,16 @@ int mt2_op_layernorm(void* stream, const float* x, int ldx, const float* gamma, 
     p.out = out; p.ldo = ldo; p.M = M; p.C = C; p.eps = eps; p.act = act >= 100 ? act - 100 : act;
     p.out_planes = act >= 100 ? 1 : 0;        // tests: act + 100 = the output as fp16 planes (LnP::out_planes)
     MT2_HIP(launch_layernorm(p, (hipStream_t)stream));
+    MT2_API_END
+}
+
+int mt2_op_sample_rows(void* stream, const float* logits, int ld, int N, int A, const mt2_sampling* s, const uint64_t* seeds_dev,
+                       const int32_t* positions_dev, int64_t* out) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(logits && s && seeds_dev && positions_dev && out && A >= 0 && N >= 1 && ld >= N, "bad arguments");
+    check_sampling(*s, N, false);
+    MT2_HIP(launch_sample_rows(logits, ld, N, out, 1, 0, A, s->temperature, s->top_k, s->top_p,
+                               reinterpret_cast<const uint32_t*>(seeds_dev), nullptr, positions_dev, 0, (hipStream_t)stream));
     MT2_API_END
 }
 

@@ -1086,9 +1086,11 @@ static void adm_run(const Ctx& c, const float* tc, int ld_tc, int tc_rows, const
 
 // MegaPLM.infer (models/megatts2.py:165-181).  cond rows buffer (ld), utterance b's first row row0[b]; lens[b] =
 // ALL positions of the sequence (prompt prefix + target); codes_out / last_logits receive the target positions.
+// smp (validated by the caller; nullptr = greedy): each step's code is drawn by launch_sample_rows instead of the argmax -
+// the same launch count, utterance b's seed smp->seeds[b], counter = the target position t - P.
 static void plm_run(const Ctx& c, const float* cond, int ld_c, const std::vector<int>& row0, const int* lens, int B,
                     int64_t* codes_out, int ostride, float* last_logits, int logit_tmax,
-                    const ArPrefix& pre = ArPrefix()) {
+                    const ArPrefix& pre = ArPrefix(), const mt2_sampling* smp = nullptr) {
     mt2_model& m = c.m;
     const mt2_config& cfg = m.cfg;
     const OptGuard pairs_guard(m.opts.ln_pairs, 0);      // the hand-off pays in the ADM only (profiles/r05_opts_ab.txt)
@@ -1118,6 +1120,15 @@ static void plm_run(const Ctx& c, const float* cond, int ld_c, const std::vector
         q.nmax = q.len[0];
         q.A = q.B;
         q.o_crow = ip.add(crow); q.o_len = ip.add(q.len); q.o_slot = ip.add(q.slot);
+    }
+    int o_seed = -1;
+    if (smp) {      // (lo, hi) words of every utterance's seed, uploaded once per call with the plan
+        std::vector<int> sd(2 * (size_t)B);
+        for (int b = 0; b < B; ++b) {
+            sd[2 * b] = (int)(uint32_t)smp->seeds[b];
+            sd[2 * b + 1] = (int)(uint32_t)(smp->seeds[b] >> 32);
+        }
+        o_seed = ip.add(sd);
     }
     ip.upload(c.ws, c.m.pinned(), c.s);
 
@@ -1153,7 +1164,12 @@ static void plm_run(const Ctx& c, const float* cond, int ld_c, const std::vector
         p.X = y; p.ldx = d; p.Rx = q.A; p.Cin = d; p.W = m.plm_wpred;
         p.C = q.logits; p.ldc = NB; p.M = q.A; p.N = NB;
         gemm(cg, p);
-        MT2_HIP(launch_argmax_rows(q.logits, NB, NB, q.codes, cstride, n, q.A, cg.s));
+        if (smp)
+            MT2_HIP(launch_sample_rows(q.logits, NB, NB, q.codes, cstride, n, q.A, smp->temperature, smp->top_k, smp->top_p,
+                                       reinterpret_cast<const uint32_t*>(ip.dev(o_seed)), ip.dev(q.o_slot), nullptr, t - pre.P,
+                                       cg.s));
+        else
+            MT2_HIP(launch_argmax_rows(q.logits, NB, NB, q.codes, cstride, n, q.A, cg.s));
         if (last_logits && t - pre.P < logit_tmax)
             for (int j = 0; j < q.A; ++j)
                 MT2_HIP(hipMemcpyAsync(last_logits + ((size_t)q.slot[j] * logit_tmax + (t - pre.P)) * NB,

@@ -299,6 +299,11 @@ hipError_t launch_unpack_wav(const float* src, const long long* start, const lon
 // row arg-max with lowest-index ties (torch.argmax): out[j*ostride + ooff] = argmax_n x[j, 0:N]
 hipError_t launch_argmax_rows(const float* x, int ldx, int N, int64_t* out, int ostride, int ooff, int A,
                               hipStream_t s);
+// seeded temperature / top-k / top-p draw (sampling.hip; N <= 1024): out[j*ostride + ooff] = the code of row j under the rule
+// of sampling.hip with Philox key = seeds[2b], seeds[2b+1] (lo, hi) of utterance b = slot ? slot[j] : j and counter
+// = pos ? pos[j] : pos0.  top_k = 1 is launch_argmax_rows.  hipErrorInvalidValue for parameters outside the rule.
+hipError_t launch_sample_rows(const float* x, int ldx, int N, int64_t* out, int ostride, int ooff, int A, float tau, int top_k,
+                              float top_p, const uint32_t* seeds, const int* slot, const int* pos, int pos0, hipStream_t s);
 // EuclideanCodebook.quantize (core_vq.py:175-183) given xe = x @ E^T:
 //   idx[m] = argmax_j -((|x_m|^2 - 2*xe[m,j]) + ee[j]), lowest index on ties
 hipError_t launch_vq_argmin(const float* x, int ldx, int D, const float* xe, int ldxe, const float* ee, int N,

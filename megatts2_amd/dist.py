@@ -176,11 +176,14 @@ def gather_mels(mel, lens, b_cap: int = 0, t_cap: int = 0, host_lens: bool = Tru
     return _unpack_gathered(_all_gather_flat(buf), world, b_cap, t_cap, Cc, host_lens)
 
 
-def synthesize_sharded(tts, utterances, vocoder: bool = False):
+def synthesize_sharded(tts, utterances, vocoder: bool = False, sampling=None, seeds=None):
     """Shard a list of `synth.Utterance`-like objects (phone, prompt_mel, optional durations / p_codes)
     over the process group, synthesize the local shard with `tts.synthesize`, all-gather the mels and
     return them in the ORIGINAL utterance order on every rank: (list of [Tm_i, C] tensors).  Fewer
-    utterances than ranks is fine: a rank with an empty shard contributes zero rows to the exchange."""
+    utterances than ranks is fine: a rank with an empty shard contributes zero rows to the exchange.
+    `sampling` (sampling.PLMSampling; None = greedy): each utterance keeps its OWN seed wherever it lands - its record's
+    `.seed`, otherwise `seeds[i]` (or s + i for an int s; default s = 0) by its index i in `utterances` - so the
+    result does not depend on the world size."""
     import torch
     import torch.distributed as dist
 
@@ -193,8 +196,16 @@ def synthesize_sharded(tts, utterances, vocoder: bool = False):
              for u in utterances]
     shards = shard_utterances(costs, world)
     mine = shards[rank]
+    kw = {}
+    if sampling is not None:      # passed only when sampling: a synthesize_list without these keywords keeps working
+        from .sampling import seed_array
+        sd = seed_array(seeds, len(utterances))
+        own = [int(u.seed) if getattr(u, "seed", None) is not None else int(sd[i]) for i, u in enumerate(utterances)]
+        kw = dict(sampling=sampling, seeds=np.asarray([own[i] & 0xFFFFFFFFFFFFFFFF for i in mine], np.uint64))
+    elif seeds is not None:
+        raise ValueError("seeds given without sampling")
     if mine:
-        mel, lens = tts.synthesize_list([utterances[i] for i in mine], vocoder=vocoder)
+        mel, lens = tts.synthesize_list([utterances[i] for i in mine], vocoder=vocoder, **kw)
     else:   # nothing to do on this rank - it still has to take part in the collective
         dev = getattr(getattr(tts, "native", None), "device", None) or torch.device("cpu")
         mel, lens = torch.zeros(0, 1, utterances[0].prompt_mel.shape[1], device=dev), np.zeros(0, np.int32)

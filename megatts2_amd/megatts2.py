@@ -22,6 +22,7 @@ from . import config as cfgmod
 from . import weights
 from .config import HIFIGAN_HOP_LENGTH, HIFIGAN_SR
 from .runtime import NativeError, NativeModel
+from .sampling import PLMSampling, seed_array
 
 
 def _np_sd(sd) -> Dict[str, np.ndarray]:
@@ -193,21 +194,29 @@ class MegaPLM:
             self._native = NativeModel(plm_cfg=self.cfg, sd_plm=self.state)
         return self._native
 
-    def infer(self, tc_latent, lens=None, prompt_tc_latent=None, prompt_codes=None):
+    def infer(self, tc_latent, lens=None, prompt_tc_latent=None, prompt_codes=None, temperature=None, top_k: int = 0,
+              top_p: float = 1.0, seed=None):
         """models/megatts2.py:165-181.  Optional prompt conditioning, in the layout the PLM is
         TRAINED on (modules/datamodule.py:201-212): `prompt_tc_latent` [B, P, tc] = the prompt utterance's
         length-regulated, max-pooled tc_latents, `prompt_codes` int64 [B, P] = its VQ-PE prosody codes
         (`generator.vqpe(prompt_mel)[3][0]`); both are put in front of the target's and decoding continues
-        after them.  Returns the target's codes [B, Tq]."""
+        after them.  Returns the target's codes [B, Tq].
+        `temperature` (None = the reference's greedy decoding): draw every code with temperature / top_k / top_p, seeded per
+        utterance by `seed` (an int s - utterance b gets s + b - or one per utterance; sampling.PLMSampling)."""
         if (prompt_tc_latent is None) != (prompt_codes is None):
             raise ValueError("prompt_tc_latent and prompt_codes go together")
+        kw = {}
+        if temperature is not None:
+            kw = dict(sampling=PLMSampling(temperature, top_k, top_p), seeds=seed)
+        elif seed is not None or top_k or top_p != 1.0:
+            raise ValueError("top_k / top_p / seed need a temperature (temperature=None is greedy decoding)")
         if prompt_codes is None:
-            return self.native.plm_infer(tc_latent, lens)
+            return self.native.plm_infer(tc_latent, lens, **kw)
         import torch
         if prompt_tc_latent.shape[1] != prompt_codes.shape[-1]:
             raise ValueError("prompt_tc_latent and prompt_codes must have the same length")   # datamodule.py:207 assert
         cond = torch.cat([prompt_tc_latent.to(tc_latent.device, torch.float32), tc_latent.to(torch.float32)], dim=1)
-        return self.native.plm_infer(cond, lens, prefix_codes=prompt_codes.to(tc_latent.device))
+        return self.native.plm_infer(cond, lens, prefix_codes=prompt_codes.to(tc_latent.device), **kw)
 
     def eval(self):
         return self
@@ -337,15 +346,17 @@ class Megatts:
 
     # -- batched tensor-level pipeline (the measured hot path)
     def synthesize(self, phone_tokens, mels, phone_lens=None, mel_lens=None, forced_durations=None,
-                   forced_codes=None, vocoder: bool = False, return_aux: bool = False):
+                   forced_codes=None, vocoder: bool = False, return_aux: bool = False, sampling=None, seeds=None):
         """phone_tokens int64 [B, Np], mels f32 [B, Tp, 80] -> (mel [B, Tm, 80], mel_lens) - the
-        no_grad block of Megatts.forward (models/megatts2.py:353-368) for every utterance of the batch."""
+        no_grad block of Megatts.forward (models/megatts2.py:353-368) for every utterance of the batch.
+        `sampling` (sampling.PLMSampling; None = greedy) / `seeds` (int64 [B] or one int s -> s + b): sampled PLM codes."""
         return self.native.synthesize_batch(phone_tokens, phone_lens, mels, mel_lens, forced_durations, forced_codes,
-                                            run_plm=forced_codes is None, vocoder=vocoder, return_aux=return_aux)
+                                            run_plm=forced_codes is None, vocoder=vocoder, return_aux=return_aux,
+                                            sampling=sampling, seeds=seeds)
 
     def synthesize_prompt_conditioned(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations, phone_lens=None,
                                       mel_lens=None, prompt_phone_lens=None, forced_durations=None, vocoder: bool = False,
-                                      return_aux: bool = False):
+                                      return_aux: bool = False, sampling=None, seeds=None):
         """Synthesis with the PLM conditioned on the prompt's prosody - the layout the PLM is trained
         on (reference modules/datamodule.py:161-177,196-212) at inference: the prompt's length-regulated, max-pooled
         tc_latents in front of the target's, the prompt's VQ-PE codes behind the BOS, greedy decoding from there.
@@ -356,7 +367,7 @@ class Megatts:
         calls (round 3's form; kept as the cross-check of the fused entry point)."""
         out = self.native.synthesize_prompt_conditioned(phone_tokens, phone_lens, mels, mel_lens, prompt_phone_tokens,
                                                         prompt_phone_lens, prompt_durations, forced_dur=forced_durations,
-                                                        vocoder=vocoder)
+                                                        vocoder=vocoder, sampling=sampling, seeds=seeds)
         return out if return_aux else (out[0], out[1])
 
     def synthesize_prompt_conditioned_staged(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations, phone_lens=None,
@@ -400,10 +411,12 @@ class Megatts:
         aux["dur"], aux["prompt_codes"] = dur, codes_p[:, :P]
         return (out[0], out[1], aux) if return_aux else (out[0], out[1])
 
-    def synthesize_list(self, utterances: Sequence, vocoder: bool = False):
+    def synthesize_list(self, utterances: Sequence, vocoder: bool = False, sampling=None, seeds=None):
         """List of utterance records (`.phone` int64 [Np], `.prompt_mel` f32 [Tp, 80], optional
         `.durations`, `.p_codes`) -> (mel [B, Tm_max, 80] device tensor, lens); pads to the batch
-        maxima and forwards per-utterance lengths, so every utterance is computed as if alone."""
+        maxima and forwards per-utterance lengths, so every utterance is computed as if alone.
+        `sampling` (sampling.PLMSampling): the PLM's codes are drawn, utterance i seeded by its record's `.seed` when it has
+        one, otherwise by `seeds` (one per record, or an int s -> s + i; default s = 0)."""
         import torch
         B = len(utterances)
         Np = max(u.phone.size for u in utterances)
@@ -425,10 +438,19 @@ class Megatts:
             if have_c:
                 codes[i, :u.p_codes.size] = u.p_codes
         dev = self.native.device
+        kw = {}
+        if sampling is not None:
+            sd = seed_array(seeds, B)
+            for i, u in enumerate(utterances):
+                if getattr(u, "seed", None) is not None:
+                    sd[i] = np.uint64(int(u.seed) & 0xFFFFFFFFFFFFFFFF)
+            kw = dict(sampling=sampling, seeds=sd)
+        elif seeds is not None:
+            raise ValueError("seeds given without sampling")
         out = self.native.synthesize_batch(torch.from_numpy(phone).to(dev), pl, torch.from_numpy(mel).to(dev), ml,
                                            forced_dur=dur,
                                            forced_codes=torch.from_numpy(codes).to(dev) if have_c else None,
-                                           run_plm=not have_c, vocoder=vocoder)
+                                           run_plm=not have_c, vocoder=vocoder, **kw)
         return out[0], out[1]
 
     # -- the reference's entry point (models/megatts2.py:325-375).  Prompt audio: every *.wav of the directory

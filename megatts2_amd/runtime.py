@@ -15,6 +15,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import config as cfgmod
+from . import sampling as sampmod
 
 _LIB = None
 MAX_POSITIONS = 8192       # rows of the sine tables (the reference builds 4000 and extends on demand)
@@ -332,10 +333,24 @@ class NativeModel:
         _check(self.lib.mt2_max_pool_ceil(self.h, _stream(), _ptr(x), _iptr(ln), T, D, B, k, _ptr(out), Tq))
         return out
 
-    def plm_infer(self, cond, lens=None, return_logits=False, prefix_codes=None, max_steps: int = 0):
+    @staticmethod
+    def _sampling(sampling, seeds, B: int):
+        """(mt2_sampling struct, its seed array) of a sampled call, or (None, None) for greedy decoding."""
+        sampling = sampmod.as_sampling(sampling)
+        if sampling is None:
+            if seeds is not None:
+                raise ValueError("seeds given without sampling")
+            return None, None
+        sd = sampmod.seed_array(seeds, B)
+        return sampling.to_c(sd), sd
+
+    def plm_infer(self, cond, lens=None, return_logits=False, prefix_codes=None, max_steps: int = 0, sampling=None,
+                  seeds=None):
         """MegaPLM.infer.  With `prefix_codes` int64 [B, P] the first P rows of `cond` [B, P + Tq, tc] are the
         prompt's pooled tc_latents and decoding is conditioned on the prompt's prosody codes (training layout of
-        reference modules/datamodule.py:201-212); `lens` are the TARGET lengths, the result covers the target."""
+        reference modules/datamodule.py:201-212); `lens` are the TARGET lengths, the result covers the target.
+        `sampling` (a sampling.PLMSampling; None = greedy) draws every code instead of the argmax, with `seeds` = an int64
+        array [B] or one int s (utterance b gets s + b): mt2_plm_infer_sampled."""
         import torch
         B = cond.shape[0]
         cond = self._f32(cond)
@@ -348,8 +363,13 @@ class NativeModel:
         ln = self._lens(lens, B, Tq)
         codes = torch.empty(B, Tq, device=cond.device, dtype=torch.int64)
         logits = torch.zeros(B, Tq, self.plm_cfg.vq_bins, device=cond.device, dtype=torch.float32) if return_logits else None
-        self._guarded(lambda: self.lib.mt2_plm_infer_prompted(self.h, _stream(), _ptr(cond), _iptr(ln), Tq, B, _ptr(prefix_codes), P,
-                                               int(max_steps), _ptr(codes), _ptr(logits)))
+        smp, _sd = self._sampling(sampling, seeds, B)
+        if smp is None:
+            self._guarded(lambda: self.lib.mt2_plm_infer_prompted(self.h, _stream(), _ptr(cond), _iptr(ln), Tq, B, _ptr(prefix_codes),
+                                                                  P, int(max_steps), _ptr(codes), _ptr(logits)))
+        else:       # counter-based draws: the range guard's repeat of the call draws the same u
+            self._guarded(lambda: self.lib.mt2_plm_infer_sampled(self.h, _stream(), _ptr(cond), _iptr(ln), Tq, B, _ptr(prefix_codes),
+                                                                 P, int(max_steps), _ptr(codes), _ptr(logits), C.byref(smp)))
         return (codes, logits) if return_logits else codes
 
     def vq_decode(self, codes):
@@ -404,10 +424,11 @@ class NativeModel:
 
     def synthesize_batch(self, phone, phone_lens, prompt_mel, prompt_lens, forced_dur=None, forced_codes=None,
                          run_plm=True, vocoder=False, skip_adm=False, tm_cap: Optional[int] = None,
-                         return_aux=False, prompt_vqpe=False, mel_out=None, check_range=True):
+                         return_aux=False, prompt_vqpe=False, mel_out=None, check_range=True, sampling=None, seeds=None):
         """Megatts.forward's no_grad block for a batch; returns (mel [B, Tm_cap, 80], mel_lens[, aux]).
         `mel_out`: a caller-owned contiguous f32 [B, tm_cap, mel_bins] device tensor the mels are written into (the native call
-        zero-fills it first) - e.g. `dist.MelExchange.mel_view(B)`, so that a multi-GPU step gathers without a copy."""
+        zero-fills it first) - e.g. `dist.MelExchange.mel_view(B)`, so that a multi-GPU step gathers without a copy.
+        `sampling` / `seeds`: the PLM's codes drawn instead of decoded greedily (as plm_infer; mt2_synthesize_batch_sampled)."""
         import torch
         B, Np = phone.shape
         Tp = prompt_mel.shape[1]
@@ -447,18 +468,28 @@ class NativeModel:
         flags = ((MT2_RUN_PLM if run_plm else 0) | (MT2_RUN_VOCODER if vocoder else 0) | (MT2_SKIP_ADM if skip_adm else 0)
                  | (MT2_PROMPT_VQPE if prompt_vqpe else 0))
         pcodes = torch.empty(B, -(-Tp // st), device=dev, dtype=torch.int64) if prompt_vqpe else None
-        self._guarded(lambda: self.lib.mt2_synthesize_batch(
-            self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _iptr(fd), _ptr(forced_codes), tq_cap,
-            flags, _ptr(mel), tm_cap, _iptr(mel_lens), _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes)), check_range)
+        smp, _sd = self._sampling(sampling, seeds, B)
+        if smp is None:
+            self._guarded(lambda: self.lib.mt2_synthesize_batch(
+                self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _iptr(fd), _ptr(forced_codes),
+                tq_cap, flags, _ptr(mel), tm_cap, _iptr(mel_lens), _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes)),
+                check_range)
+        else:
+            self._guarded(lambda: self.lib.mt2_synthesize_batch_sampled(
+                self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _iptr(fd), _ptr(forced_codes),
+                tq_cap, flags, _ptr(mel), tm_cap, _iptr(mel_lens), _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes),
+                C.byref(smp)), check_range)
         if return_aux:
             return mel, mel_lens, {"dur": dur_out, "codes": codes_out, "wav": wav, "prompt_codes": pcodes}
         return mel, mel_lens
 
     def synthesize_prompt_conditioned(self, phone, phone_lens, prompt_mel, prompt_lens, prompt_phone, prompt_phone_lens,
-                                      prompt_dur, forced_dur=None, vocoder=False, tm_cap: Optional[int] = None, check_range=True):
+                                      prompt_dur, forced_dur=None, vocoder=False, tm_cap: Optional[int] = None, check_range=True,
+                                      sampling=None, seeds=None):
         """mt2_synthesize_prompt_conditioned: prompt-conditioned synthesis (the PLM continued from the prompt's prosody codes,
         modules/datamodule.py:161-177,196-212) as ONE native call -> (mel, mel_lens, aux) with aux["dur"] the ADM's own
-        durations, aux["codes"] the decoded target codes, aux["prompt_codes"] [B, P] the prompt's VQ-PE codes."""
+        durations, aux["codes"] the decoded target codes, aux["prompt_codes"] [B, P] the prompt's VQ-PE codes.
+        `sampling` / `seeds`: the target's codes drawn instead of decoded greedily (mt2_synthesize_prompt_conditioned_sampled)."""
         import torch
         B, Np = phone.shape
         Tp, Npp = prompt_mel.shape[1], prompt_phone.shape[1]
@@ -488,10 +519,17 @@ class NativeModel:
         pad = int(getattr(self.hg_cfg, "inference_padding", 0))
         wav = torch.empty(B, self.hg_cfg.hop * (tm_cap + 2 * pad), device=dev, dtype=torch.float32) if vocoder else None
         pcodes = torch.empty(B, -(-Tp // st), device=dev, dtype=torch.int64)
-        self._guarded(lambda: self.lib.mt2_synthesize_prompt_conditioned(
-            self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _ptr(prompt_phone), _iptr(ppl), Npp,
-            _iptr(pd), _iptr(fd), tq_cap, MT2_RUN_VOCODER if vocoder else 0, _ptr(mel), tm_cap, _iptr(mel_lens), _ptr(dur_out),
-            _ptr(codes_out), _ptr(wav), _ptr(pcodes)), check_range)
+        smp, _sd = self._sampling(sampling, seeds, B)
+        if smp is None:
+            self._guarded(lambda: self.lib.mt2_synthesize_prompt_conditioned(
+                self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _ptr(prompt_phone), _iptr(ppl),
+                Npp, _iptr(pd), _iptr(fd), tq_cap, MT2_RUN_VOCODER if vocoder else 0, _ptr(mel), tm_cap, _iptr(mel_lens),
+                _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes)), check_range)
+        else:
+            self._guarded(lambda: self.lib.mt2_synthesize_prompt_conditioned_sampled(
+                self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _ptr(prompt_phone), _iptr(ppl),
+                Npp, _iptr(pd), _iptr(fd), tq_cap, MT2_RUN_VOCODER if vocoder else 0, _ptr(mel), tm_cap, _iptr(mel_lens),
+                _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes), C.byref(smp)), check_range)
         P = -(-int(ml[0]) // st)
         return mel, mel_lens, {"dur": dur_out, "codes": codes_out, "wav": wav, "prompt_codes": pcodes[:, :P]}
 
@@ -791,6 +829,24 @@ def op_gemm_x6_ln(X, W, bias=None, R=None, M=None, a_mul=1, shift0=0, epi_act=AC
                                      C.byref(nt), C.byref(pw), _ptr(ln_stat), ln_nt, int(ln_w), _ptr(ln_s), C.c_float(eps)))
     if want_stats:
         return out, stat.view(-1)[:M * nt.value * 2].reshape(M, nt.value, 2).clone(), pw.value      # dense [M][nt][2]
+    return out
+
+
+def op_sample_rows(logits, sampling, seeds, positions):
+    """mt2_op_sample_rows: the PLM's sampling draw on every row of `logits` f32 [A, N] (device) with per-row seeds (int64 /
+    uint64 values [A], device tensor) and target positions (int32 [A], device) -> int64 [A]."""
+    import torch
+    lib = load_library()
+    A, N = logits.shape
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.stride(1) == 1
+    seeds = seeds.contiguous().to(torch.int64)
+    positions = positions.contiguous().to(torch.int32)
+    assert seeds.shape == (A,) and positions.shape == (A,)
+    out = torch.empty(A, device=logits.device, dtype=torch.int64)
+    s = sampmod.as_sampling(sampling).to_c(np.zeros(1, np.uint64))
+    s.seeds = C.cast(C.c_void_p(0), C.POINTER(C.c_uint64))      # the op reads seeds_dev only
+    _check(lib.mt2_op_sample_rows(_stream(), _ptr(logits), logits.stride(0), N, A, C.byref(s), _ptr(seeds), _ptr(positions),
+                                  _ptr(out)))
     return out
 
 

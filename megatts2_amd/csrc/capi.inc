@@ -245,6 +245,12 @@ int mt2_workspace_query(const mt2_model* m, int B, int Np_max, int Tp_max, int T
     auto enc = [&](long long M, long long d, long long ff) {
         return M * (5 * d + ff + 128) + std::max(256ll * 32 * 64 + 16ll * 32 * d, 8 * M * d) + 7 * 64;
     };
+    // an AR run over B sequences of up to L positions: step rows, layer-0 QKV cache, last rows, encoder scratch per stream group
+    auto ar = [&](long long d, long long ff, long long L, int stage_groups) {
+        const long long M = (long long)B * L;
+        const int G = std::max(1, std::min(stage_groups > 0 ? stage_groups : m->ar_groups, B));
+        return M * d + 3 * M * d + (long long)B * d + G * enc(0, d, ff) + enc(M + 2ll * B * G, d, ff) - enc(0, d, ff);
+    };
     const long long H = cfg.mrte_hidden, st = cfg.mrte_stride;
     const long long FR = rows(Tp_max, (int)std::max<long long>(st / 2, 2)), XR = rows((Tp_max - 1) / st + 1, 2), PR = rows(Np_max, 2);
     long long f = 0;                                                              // floats (ints counted as floats)
@@ -253,18 +259,15 @@ int mt2_workspace_query(const mt2_model* m, int B, int Np_max, int Tp_max, int T
     f += 4 * XR * H * cfg.mrte_n_layer + 2 * XR * H;
     f += PR * H + enc(PR, H, cfg.content_ff_dim) + 2 * XR * H + 2 * PR * H;
     if (!(flags & MT2_SKIP_ADM)) {
-        const long long d = cfg.adm_emb_dim + cfg.adm_tc_emb_dim, ff = 4ll * cfg.adm_emb_dim, M = (long long)B * Np_max;
-        const int G = std::max(1, std::min(m->adm_groups > 0 ? m->adm_groups : m->ar_groups, B));
         f += PR * cfg.adm_tc_emb_dim + (long long)B * (Np_max + 1) + 8ll * B;
-        f += M * d + 3 * M * d + (long long)B * d + G * enc(0, d, ff) + enc(M + 2ll * B * G, d, ff) - enc(0, d, ff);
+        f += ar(cfg.adm_emb_dim + cfg.adm_tc_emb_dim, 4ll * cfg.adm_emb_dim, Np_max, m->adm_groups);
     }
     const long long DR = rows(Tm_cap, 2), DIN = H + cfg.vq_dim, Tq = (Tm_cap + cfg.vq_stride - 1) / cfg.vq_stride;
     f += 8 * DR + 4ll * B * Tq + DR * DIN + (long long)B * Tq * H + (long long)B * Np_max;
     if (flags & MT2_RUN_PLM) {
-        const long long d = cfg.plm_vq_dim + cfg.plm_tc_dim, ff = 4 * d, M = (long long)B * Tq;
-        const int G = std::max(1, std::min(m->plm_groups > 0 ? m->plm_groups : m->ar_groups, B));
+        const long long d = cfg.plm_vq_dim + cfg.plm_tc_dim;
         f += 2ll * B * (Tq + 1) + 2ll * B * Tq + 8ll * B + (long long)B * cfg.plm_bins + 2ll * B;   // + seeds of a sampled call
-        f += M * d + 3 * M * d + (long long)B * d + G * enc(0, d, ff) + enc(M + 2ll * B * G, d, ff) - enc(0, d, ff);
+        f += ar(d, 4 * d, Tq, m->plm_groups);
     }
     f += DR * cfg.dec_hidden * 5 + DR * cfg.mel_bins;
     if (flags & MT2_PROMPT_VQPE) {      // vqpe_rows on the prompt mel
@@ -573,7 +576,30 @@ int mt2_mel_decoder(mt2_model* m, void* stream, const float* x, const int32_t* l
     MT2_API_END
 }
 
-static void hifigan_to_wav(const Ctx& c, const float* wavrows, const RowSet& M0, int hop, float* wav, int T_cap) {
+// Vocoder rows of B utterances: every utterance's mel frames with `hg_inference_padding` replicated frames on both sides, a gap of
+// zero rows between utterances.  d_src[r] = source row of vocoder row r, utterance b's frames starting at first[b] (-1: gap row).
+struct VocRows { RowSet M0; const int* d_src; };
+static VocRows vocoder_rows(const Ctx& c, const std::vector<int>& first, const int* lens, int B) {
+    const mt2_config& cfg = c.m.cfg;
+    const int pad = cfg.hg_inference_padding;
+    std::vector<int> plen(B);
+    for (int b = 0; b < B; ++b) plen[b] = lens[b] + 2 * pad;
+    IntPlan ip;
+    VocRows v;
+    // gap rows between utterances at the mel level: 4 cover the zero-padded dilated convs (x hop per stage); the reflect
+    // edge mode (speechbrain) keeps TWO halos in every gap (conv_pre k7: 2 x 3 mel rows; stage 1: 2 x 25 of 64 rows)
+    v.M0 = make_rows(plen.data(), B, cfg.hg_reflect_pad ? 8 : 4);
+    const RowPlanOffsets o = plan_rows(ip, v.M0);
+    const int o_src = ip.add(padded_src(v.M0, first, lens, pad));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    bind_rows(ip, o, v.M0);
+    v.d_src = ip.dev(o_src);
+    return v;
+}
+// waveform rows (hifigan_rows: hop samples per vocoder row) -> wav [B, hop * T_cap], zero behind every utterance
+static void hifigan_to_wav(const Ctx& c, const float* wavrows, const RowSet& M0, float* wav, int T_cap) {
+    int hop = 1;
+    for (int i = 0; i < c.m.cfg.hg_n_up; ++i) hop *= c.m.cfg.hg_up_rates[i];
     const size_t n = 2 * (size_t)M0.B;
     long long* st = static_cast<long long*>(c.m.pinned().alloc(n * sizeof(long long)));   // handle-owned staging
     long long mx = 0;
@@ -593,26 +619,12 @@ int mt2_hifigan(mt2_model* m, void* stream, const float* mel, const int32_t* len
     require_ready(m, NEED_VOC);
     MT2_REQUIRE(B >= 1, "empty batch");
     MT2_CALL(m, stream);
-    const int NM = m->cfg.hg_in_dim, pad = m->cfg.hg_inference_padding;
-    std::vector<int> plen(B);
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= T_max, "length out of range");
-        plen[b] = lens[b] + 2 * pad;
-    }
-    IntPlan ip;
-    // gap rows between utterances at the mel level: 4 cover the zero-padded dilated convs (x hop per stage); the reflect
-    // edge mode (speechbrain) keeps TWO halos in every gap (conv_pre k7: 2 x 3 mel rows; stage 1: 2 x 25 of 64 rows)
-    RowSet M0 = make_rows(plen.data(), B, m->cfg.hg_reflect_pad ? 8 : 4);
-    RowPlanOffsets o = plan_rows(ip, M0);
-    const int o_map = ip.add(padded_src(M0, iota_rows(B, T_max), lens, pad));     // rowmap[r] = b*T_max + t
-    ip.upload(c.ws, c.m.pinned(), c.s);
-    bind_rows(ip, o, M0);
-    float* xrows = c.ws.get<float>((size_t)M0.R * NM);
-    MT2_HIP(launch_pack_rows(mel, NM, T_max, 1, ip.dev(o_map), xrows, NM, M0.R, c.s));
-    float* wr = hifigan_rows(c, xrows, M0);
-    int hop = 1;
-    for (int i = 0; i < m->cfg.hg_n_up; ++i) hop *= m->cfg.hg_up_rates[i];
-    hifigan_to_wav(c, wr, M0, hop, wav, T_max + 2 * pad);
+    const int NM = m->cfg.hg_in_dim;
+    for (int b = 0; b < B; ++b) MT2_REQUIRE(lens[b] >= 1 && lens[b] <= T_max, "length out of range");
+    const VocRows v = vocoder_rows(c, iota_rows(B, T_max), lens, B);      // d_src[r] = b*T_max + t
+    float* xrows = c.ws.get<float>((size_t)v.M0.R * NM);
+    MT2_HIP(launch_pack_rows(mel, NM, T_max, 1, v.d_src, xrows, NM, v.M0.R, c.s));
+    hifigan_to_wav(c, hifigan_rows(c, xrows, v.M0), v.M0, wav, T_max + 2 * m->cfg.hg_inference_padding);
     MT2_API_END
 }
 
@@ -642,23 +654,52 @@ static void decode_and_vocode(const Ctx& c, Stages& st, float* xdec, const Frame
     if (flags & MT2_RUN_VOCODER) {   // :370  hifi_gan.decode_batch(x)
         MT2_REQUIRE(m->has_vocoder && wav != nullptr, "vocoder requested but not available");
         MT2_REQUIRE(cfg.hg_in_dim == NM, "vocoder input width differs from the mel width");
-        const int pad = cfg.hg_inference_padding;
-        IntPlan ip2;
-        std::vector<int> plen(B);
-        for (int b = 0; b < B; ++b) plen[b] = fp.D.len[b] + 2 * pad;
-        RowSet M0 = make_rows(plen.data(), B, cfg.hg_reflect_pad ? 8 : 4);
-        RowPlanOffsets o = plan_rows(ip2, M0);
-        const int o_src = ip2.add(padded_src(M0, fp.D.off, fp.D.len.data(), pad));
-        ip2.upload(c.ws, c.m.pinned(), c.s);
-        bind_rows(ip2, o, M0);
-        float* xm = c.ws.get<float>((size_t)M0.R * NM);
-        MT2_HIP(launch_gather_rows(mrows, NM, ip2.dev(o_src), xm, NM, NM, M0.R, c.s));
-        float* wr = hifigan_rows(c, xm, M0);
-        int hop = 1;
-        for (int i = 0; i < cfg.hg_n_up; ++i) hop *= cfg.hg_up_rates[i];
-        hifigan_to_wav(c, wr, M0, hop, wav, Tm_cap + 2 * pad);
+        const VocRows v = vocoder_rows(c, fp.D.off, fp.D.len.data(), B);
+        float* xm = c.ws.get<float>((size_t)v.M0.R * NM);
+        MT2_HIP(launch_gather_rows(mrows, NM, v.d_src, xm, NM, NM, v.M0.R, c.s));
+        hifigan_to_wav(c, hifigan_rows(c, xm, v.M0), v.M0, wav, Tm_cap + 2 * cfg.hg_inference_padding);
         st.mark("vocoder");
     }
+}
+
+// :355  dt = adm.infer(tc_latent) on the first B row ranges of tc.P -> device durations [B, Np_max] (dur_out, or arena rows) ->
+// the HOST durations everything behind the ADM is planned on: forced_dur where given, otherwise read back - the output length
+// depends on them: one D2H + sync, as the reference (mrte.py:53).  The one seam between the ADM and the frame plan.
+static const int32_t* adm_durations(const Ctx& c, Stages& st, const TcResult& tc, const int32_t* phone_lens, int Np_max, int B,
+                                    bool run_adm, const int32_t* forced_dur, int32_t* dur_out, std::vector<int32_t>& dur_host) {
+    int32_t* dur_dev = dur_out ? dur_out : c.ws.get<int32_t>((size_t)B * Np_max);
+    if (run_adm) {
+        MT2_HIP(hipMemsetAsync(dur_dev, 0, sizeof(int32_t) * (size_t)B * Np_max, c.s));
+        adm_run(c, tc.rows, c.m.cfg.mrte_hidden, tc.P.R, tc.P.off, phone_lens, B, dur_dev, nullptr, Np_max);
+    } else {
+        MT2_REQUIRE(forced_dur != nullptr, "MT2_SKIP_ADM needs forced durations");
+    }
+    st.mark("adm");
+    if (forced_dur) return forced_dur;
+    dur_host.resize((size_t)B * Np_max);
+    MT2_HIP(hipMemcpyAsync(dur_host.data(), dur_dev, dur_host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    MT2_HIP(hipStreamSynchronize(c.s));
+    return dur_host.data();
+}
+// the frame plan of the target utterances against the caller's capacities; publishes the mel lengths
+static void check_frames(const FramePlan& fp, int B, int Tm_cap, int Tq_cap, int32_t* mel_lens) {
+    MT2_REQUIRE(fp.D.maxlen <= Tm_cap, "Tm_cap smaller than the longest utterance");
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(fp.tq[b] <= Tq_cap, "Tq_cap smaller than the longest prosody sequence");
+        MT2_REQUIRE(fp.D.len[b] >= 1, "utterance with zero frames");
+        if (mel_lens) mel_lens[b] = fp.D.len[b];
+    }
+}
+// where the PLM's codes go: the caller's codes_out [B, Tq_cap] or arena rows, zeroed
+static int64_t* codes_buffer(const Ctx& c, int64_t* codes_out, int B, int Tq_cap) {
+    int64_t* cdev = codes_out ? codes_out : c.ws.get<int64_t>((size_t)B * Tq_cap);
+    MT2_HIP(hipMemsetAsync(cdev, 0, sizeof(int64_t) * (size_t)B * Tq_cap, c.s));
+    return cdev;
+}
+// the caller's stream waits for the prompt VQ-PE of prompt_vqpe_side
+static void join_vqpe_side(const Ctx& c) {
+    MT2_HIP(hipStreamWaitEvent(c.s, c.m.ev_vq_join, 0));
+    c.m.vq_forked = false;
 }
 
 // the optional VQProsodyEncoder.forward on the PROMPT mel on the handle's own stream (MT2_PROMPT_VQPE and the prompt-conditioned
@@ -727,33 +768,12 @@ int mt2_synthesize_batch_sampled(mt2_model* m, void* stream, const int64_t* phon
     // ADM's latency-bound step launches leave idle, and joins back before the call ends.
     const bool vq_side = (flags & MT2_PROMPT_VQPE) != 0;
     if (vq_side) prompt_vqpe_side(c, prompt_mel, prompt_lens, Tp_max, B, prompt_codes);
-    // :355  dt = adm.infer(tc_latent)
-    int32_t* dur_dev = dur_out ? dur_out : c.ws.get<int32_t>((size_t)B * Np_max);
     std::vector<int32_t> dur_host;
-    if (!(flags & MT2_SKIP_ADM)) {
-        MT2_HIP(hipMemsetAsync(dur_dev, 0, sizeof(int32_t) * (size_t)B * Np_max, c.s));
-        adm_run(c, tc.rows, H, tc.P.R, tc.P.off, phone_lens, B, dur_dev, nullptr, Np_max);
-    } else {
-        MT2_REQUIRE(forced_dur != nullptr, "MT2_SKIP_ADM needs forced durations");
-    }
-    st.mark("adm");
-    const int32_t* dur = forced_dur;
-    if (!dur) {   // the output length depends on the durations: one D2H + sync, as the reference (mrte.py:53)
-        dur_host.resize((size_t)B * Np_max);
-        MT2_HIP(hipMemcpyAsync(dur_host.data(), dur_dev, dur_host.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
-                               c.s));
-        MT2_HIP(hipStreamSynchronize(c.s));
-        dur = dur_host.data();
-    }
+    const int32_t* dur = adm_durations(c, st, tc, phone_lens, Np_max, B, !(flags & MT2_SKIP_ADM), forced_dur, dur_out, dur_host);
     // :356-358  length regulation (gather) and max_pool1d(8, ceil) conditioning
     IntPlan ip;
     FramePlan fp = plan_frames(ip, dur, Np_max, phone_lens, B, tc.P.off, cfg.vq_stride, Tq_cap, Tm_cap);
-    MT2_REQUIRE(fp.D.maxlen <= Tm_cap, "Tm_cap smaller than the longest utterance");
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(fp.tq[b] <= Tq_cap, "Tq_cap smaller than the longest prosody sequence");
-        MT2_REQUIRE(fp.D.len[b] >= 1, "utterance with zero frames");
-        if (mel_lens) mel_lens[b] = fp.D.len[b];
-    }
+    check_frames(fp, B, Tm_cap, Tq_cap, mel_lens);
     ip.upload(c.ws, c.m.pinned(), c.s);
     bind_rows(ip, fp.oD, fp.D);
     if (forced_codes) {      // only the positions the decoder will read: q < ceil(frames / 8) of each utterance
@@ -772,8 +792,7 @@ int mt2_synthesize_batch_sampled(mt2_model* m, void* stream, const int64_t* phon
     const int64_t* codes = forced_codes;
     if (!codes) {
         MT2_REQUIRE(flags & MT2_RUN_PLM, "neither forced codes nor MT2_RUN_PLM given");
-        int64_t* cdev = codes_out ? codes_out : c.ws.get<int64_t>((size_t)B * Tq_cap);
-        MT2_HIP(hipMemsetAsync(cdev, 0, sizeof(int64_t) * (size_t)B * Tq_cap, c.s));
+        int64_t* cdev = codes_buffer(c, codes_out, B, Tq_cap);
         plm_run(c, cond, H, fp.q_row0, fp.tq.data(), B, cdev, Tq_cap, nullptr, 0, ArPrefix(), sampling);
         codes = cdev;
     } else if (codes_out && codes_out != forced_codes) {
@@ -782,10 +801,7 @@ int mt2_synthesize_batch_sampled(mt2_model* m, void* stream, const int64_t* phon
     }
     st.mark("plm");
     decode_and_vocode(c, st, xdec, fp, ip, codes, flags, mel, Tm_cap, wav, B);
-    if (vq_side) {                                                        // the side stream joins before the call ends
-        MT2_HIP(hipStreamWaitEvent(c.s, m->ev_vq_join, 0));
-        m->vq_forked = false;
-    }
+    if (vq_side) join_vqpe_side(c);                                       // the side stream joins before the call ends
     st.finish();
     ids_verdict(c);
     if (vq_side && m->profiling) {      // its own (overlapped) duration on the side stream
@@ -846,33 +862,19 @@ int mt2_synthesize_prompt_conditioned_sampled(mt2_model* m, void* stream, const 
                                  prompt_mel, prompt_lens, Tp_max, B);
     st.mark("mrte");
     prompt_vqpe_side(c, prompt_mel, prompt_lens, Tp_max, B, prompt_codes);      // side stream, beside the ADM
-    // :355  dt = adm.infer(tc_latent)  (the target sequences are the first B row ranges of tc.P)
-    int32_t* dur_dev = dur_out ? dur_out : c.ws.get<int32_t>((size_t)B * Np_max);
-    MT2_HIP(hipMemsetAsync(dur_dev, 0, sizeof(int32_t) * (size_t)B * Np_max, c.s));
-    adm_run(c, tc.rows, H, tc.P.R, tc.P.off, phone_lens, B, dur_dev, nullptr, Np_max);
-    st.mark("adm");
-    std::vector<int32_t> dur_host;
-    const int32_t* dur = forced_dur;
-    if (!dur) {
-        dur_host.resize((size_t)B * Np_max);
-        MT2_HIP(hipMemcpyAsync(dur_host.data(), dur_dev, dur_host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        MT2_HIP(hipStreamSynchronize(c.s));
-        dur = dur_host.data();
-    }
+    std::vector<int32_t> dur_host;      // (the target sequences are the first B row ranges of tc.P)
+    const int32_t* dur = adm_durations(c, st, tc, phone_lens, Np_max, B, true, forced_dur, dur_out, dur_host);
     // :356-358 for both sides: length regulation (gather) into ONE row buffer [prompt frames | target frames], then ONE
     // ceil-mode max-pool launch that writes the PLM conditioning of utterance b as [P prompt rows | tq[b] target rows]
     IntPlan ip;
     FramePlan fp = plan_frames(ip, dur, Np_max, phone_lens, B, tc.P.off, pool, Tq_cap, Tm_cap);
     std::vector<int> prow0(tc.P.off.begin() + B, tc.P.off.end());
     FramePlan pp = plan_frames(ip, prompt_dur, Npp_max, prompt_phone_lens, B, prow0, pool, 0, 0);
-    MT2_REQUIRE(fp.D.maxlen <= Tm_cap, "Tm_cap smaller than the longest utterance");
+    check_frames(fp, B, Tm_cap, Tq_cap, mel_lens);
     std::vector<int> total(B), q0(B);
     int qr = 0;
     for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(fp.tq[b] <= Tq_cap, "Tq_cap smaller than the longest prosody sequence");
-        MT2_REQUIRE(fp.D.len[b] >= 1, "utterance with zero frames");
         MT2_REQUIRE(pp.tq[b] == P, "prompt alignment does not pool to the prefix length");
-        if (mel_lens) mel_lens[b] = fp.D.len[b];
         q0[b] = qr;
         total[b] = P + fp.tq[b];
         qr += total[b];
@@ -900,10 +902,8 @@ int mt2_synthesize_prompt_conditioned_sampled(mt2_model* m, void* stream, const 
     MT2_HIP(launch_pool_max(rows, DIN, ip.dev(o_first), ip.dev(o_cnt), cond, H, H, qr, c.s));
     st.mark("regulate");
     // :359  p_codes = plm.infer(...) continued from the prompt's codes: they come from the side stream
-    MT2_HIP(hipStreamWaitEvent(c.s, m->ev_vq_join, 0));
-    m->vq_forked = false;
-    int64_t* cdev = codes_out ? codes_out : c.ws.get<int64_t>((size_t)B * Tq_cap);
-    MT2_HIP(hipMemsetAsync(cdev, 0, sizeof(int64_t) * (size_t)B * Tq_cap, c.s));
+    join_vqpe_side(c);
+    int64_t* cdev = codes_buffer(c, codes_out, B, Tq_cap);
     ArPrefix pre;
     pre.P = P; pre.data = prompt_codes; pre.stride = (Tp_max + pool - 1) / pool;
     plm_run(c, cond, H, q0, total.data(), B, cdev, Tq_cap, nullptr, 0, pre, sampling);

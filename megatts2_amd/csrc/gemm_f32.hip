@@ -1852,7 +1852,7 @@ bool gemm_writes_planes(const GemmP& p_in, const EngineOpts& o) {
     if (p.a_mul == 0) p.a_mul = 1;
     p.K = p.taps * p.Cin;
     if (p.ldw == 0) p.ldw = p.K;
-    if (!(o.x3h & 1) || o.force_cfg >= 0 || !o.epi_t4 || p.M <= 64) return false;
+    if (!(o.x3h & 1) || o.force_cfg >= 0 || p.M <= 64) return false;
     int idx = -1;
     const TileCfg* c = choose_cfg(p, o, &idx);
     return c_planes_ok(p, c);
@@ -1873,7 +1873,7 @@ hipError_t launch_gemm(const GemmP& p_in, hipStream_t s, EngineOpts* opts) {
     // a handful of rows: the weight-streaming kernel (gemm_skinny.hip) instead of a tile configuration
     const bool sk_forced = o.force_cfg == kSkinny32 || o.force_cfg == kSkinny64;
     const bool tm_forced = o.force_cfg == kSkinnyTm32 || o.force_cfg == kSkinnyTm64;
-    if (tm_forced || (!p.a_planes && o.skinny_tm && o.skinny_rows > 0 && o.force_cfg < 0 && p.groups >= o.skinny_groups &&
+    if (tm_forced || (!p.a_planes && o.skinny_tm && o.skinny_rows > 0 && o.force_cfg < 0 &&
                       gemm_skinny_tm_eligible(p, o.skinny_rows))) {
         if (!gemm_skinny_tm_eligible(p, 64)) return hipErrorInvalidValue;
         p.sk_nw = o.skinny_nw;
@@ -1899,7 +1899,7 @@ hipError_t launch_gemm(const GemmP& p_in, hipStream_t s, EngineOpts* opts) {
         }
         return launch_gemm_skinny_tm(p, s);
     }
-    if (sk_forced || (o.skinny_rows > 0 && o.force_cfg < 0 && p.groups >= o.skinny_groups && gemm_skinny_eligible(p, o.skinny_rows))) {
+    if (sk_forced || (o.skinny_rows > 0 && o.force_cfg < 0 && gemm_skinny_eligible(p, o.skinny_rows))) {
         if (!gemm_skinny_eligible(p, 64)) return hipErrorInvalidValue;
         const int sidx = p.M <= 32 ? kSkinny32 : kSkinny64;
         if (opts) opts->last_cfg = kCfgs[sidx].name;
@@ -1943,7 +1943,7 @@ hipError_t launch_gemm(const GemmP& p_in, hipStream_t s, EngineOpts* opts) {
     if (p.a_planes && (c->x3h < 0 || c->win_qs || p.pro_act != ACT_NONE || p.stat_out || (p.Cin % BK) != 0 || (p.ldx % BK) != 0 ||
                        (p.groups > 1 && (p.strideX % BK) != 0) || p.a_mul != 1 || p.rowbase || (((unsigned long long)p.X) & 127)))
         return hipErrorNotSupported;
-    if (p.c_planes && !(c_planes_ok(p, c) && o.epi_t4)) return hipErrorNotSupported;
+    if (p.c_planes && !c_planes_ok(p, c)) return hipErrorNotSupported;
     const int fi = p.a_planes ? PRO_APL : ((p.pro_act == PRO_LNX || p.stat_out) ? PRO_LNX : p.pro_act);
     // LayerNorm as a prologue of the f32 tiles (pro_act 3 / 4: rounds 1-2, measured slower than LayerNorm + GEMM) is retired: callers
     // fall back on NotSupported; the <= 64-row weight-streaming kernel (above) keeps its own LayerNorm prologue
@@ -1977,7 +1977,7 @@ hipError_t launch_gemm(const GemmP& p_in, hipStream_t s, EngineOpts* opts) {
     }
     if (opts) { opts->last_stat_nt = p.stat_nt; opts->last_stat_w = p.stat_w; }
     const int tiles = ((p.M + c->bm - 1) / c->bm) * ((p.N + c->bn - 1) / c->bn);
-    p.epi_t4 = o.epi_t4 ? 1 : 0;
+    p.epi_t4 = 1;
     p.ldr_prio = o.ldr_prio;
     p.ldr64 = o.ldr64 ? 1 : 0;
     dim3 grid(tiles, 1, p.groups), block(c->threads);

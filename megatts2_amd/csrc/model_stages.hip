@@ -200,8 +200,8 @@ static void ln_linear(const Ctx& c, const float* x, int ldx, int Rx, int a_mul, 
         }
         attach_tm(c.m, q);
         if (q.Wtm && gemm_skinny_tm_eligible(q, c.m.opts.skinny_rows)) {
-            // launch_gemm routes to the tile-major kernel only when its own conditions hold too (skinny_groups); with another
-            // routing the LayerNorm-prologue form may not exist for the tile it picks: fall through like the branches below
+            // launch_gemm routes to the tile-major kernel only when its own conditions hold too; with another routing the
+            // LayerNorm-prologue form may not exist for the tile it picks: fall through like the branches below
             const hipError_t e = launch_gemm(q, c.s, &c.m.opts);
             if (e == hipSuccess) return;
             if (e != hipErrorNotSupported) MT2_HIP(e);
@@ -336,19 +336,25 @@ static EncScratch enc_scratch(const Ctx& c, const EncW& e, int M) {
     s.stat = c.ws.get<float>((size_t)M * 128);     // row statistics handed from GEMM to GEMM: <= 64 (mean, M2) pairs per row
     return s;
 }
-static void attention_self(const Ctx& c, const EncW& e, const AttnGeom& g, const float* qkv, float* att, bool o_planes = false) {
+// the attention launch parameters that come from the engine options and the head geometry (H heads of width D): the one place
+// where they are set - callers add their row ranges and pointers
+static AttnP attn_params(const Ctx& c, int H, int D) {
     AttnP a{};
-    a.o_planes = o_planes ? 1 : 0; a.x3h_flag = c.m.opts.x3h_flag;
-    const int d = e.d, D = d / e.heads;
+    a.H = H; a.D = D; a.scale = 1.0f / std::sqrt((float)D);
+    a.lds_min_qlen = c.m.opts.attn_lds_min; a.x6_min_qlen = c.m.opts.attn_x6_min;
+    a.x3h = (c.m.opts.x3h & 8) ? 1 : 0; a.x3h_flag = c.m.opts.x3h_flag;
+    return a;
+}
+static AttnP attn_params(const Ctx& c, const EncW& e) { return attn_params(c, e.heads, e.d / e.heads); }
+static void attention_self(const Ctx& c, const EncW& e, const AttnGeom& g, const float* qkv, float* att, bool o_planes = false) {
+    AttnP a = attn_params(c, e);
+    a.o_planes = o_planes ? 1 : 0;
+    const int d = e.d;
     a.Q = qkv; a.ldq = 3 * d; a.K = qkv + d; a.ldk = 3 * d; a.V = qkv + 2 * d; a.ldv = 3 * d;
     a.O = att; a.ldo = d;
     a.q_start = g.start; a.q_len = g.len; a.kv_start = g.start; a.kv_len = g.len;
     a.u_qstride = g.u_stride; a.u_qlen = g.u_len; a.u_kvstride = g.u_stride; a.u_kvlen = g.u_len;
-    a.B = g.B; a.H = e.heads; a.D = D; a.max_qlen = g.max_len; a.max_kvlen = g.max_len;
-    a.scale = 1.0f / std::sqrt((float)D);
-    a.lds_min_qlen = c.m.opts.attn_lds_min; a.lds_waves = c.m.opts.attn_lds_waves; a.x6_min_qlen = c.m.opts.attn_x6_min;
-    a.x3h = (c.m.opts.x3h & 8) ? 1 : 0; a.x3h_flag = c.m.opts.x3h_flag;
-    a.ds_short = c.m.opts.attn_ds;
+    a.B = g.B; a.max_qlen = g.max_len; a.max_kvlen = g.max_len;
     MT2_HIP(launch_attention(a, c.s));
 }
 static void encoder_layer(const Ctx& c, const EncW& e, const EncLayerW& w, float* x, int M, const AttnGeom& g,
@@ -398,7 +404,7 @@ static int choose_split(const Ctx& c, int M, int N, int K) {
     // (N = 768 / 1024: 6 / 8 column tiles); K slices as GEMM groups bring them to >= t_x6_128 tiles, and the reduction
     // rides on the next LayerNorm as before (profiles/r02_gemm_sweep_x6.txt: ff.3 at M = 864 does 85 TF/s on the f32
     // K-split tile; four x6 slices of K = 1024 have the shape of ff.0, 125 TF/s)
-    if (c.m.opts.x6_gemm && c.m.opts.x6_splitk && (N & 127) == 0 && (K & 31) == 0) {
+    if (c.m.opts.x6_gemm && (N & 127) == 0 && (K & 31) == 0) {
         const long long t128 = (long long)((M + 127) / 128) * (N / 128);
         if (t128 < c.m.opts.t_x6_128) {
             int S = 1;
@@ -551,11 +557,11 @@ static Pending encoder_layer_ar(const Ctx& c, const EncW& e, const EncLayerW& w,
 static void encoder_layer_last(const Ctx& c, const EncW& e, const EncLayerW& w, float* x, int n, int A,
                                const EncScratch& s, float* y, const Pending& in) {
     MT2_REQUIRE(!e.conv_ff, "AR step layers use the Linear feed-forward");
-    const int d = e.d, M = A * n, D = d / e.heads;
+    const int d = e.d, M = A * n;
     float* kv = s.qkv;                                   // [M, 2d]: K | V
     float* q = s.att;                                    // [A, d]
     float* att = s.att + (size_t)A * d;                  // [A, d]
-    AttnP a{};
+    AttnP a = attn_params(c, e);
     if (c.m.opts.skinny_tm && M <= c.m.opts.skinny_rows && M <= 64 && c.m.opts.force_cfg < 0) {
         // a handful of rows (one utterance's steps): Q | K | V of ALL rows in ONE weight-streaming launch - the Q rows that
         // are not the last of their sequence cost nothing measurable at M <= 64, a second launch costs ~8 us
@@ -585,11 +591,7 @@ static void encoder_layer_last(const Ctx& c, const EncW& e, const EncLayerW& w, 
         a.u_qstride = 1;
     }
     a.O = att; a.ldo = d;
-    a.u_qlen = 1; a.u_kvstride = n; a.u_kvlen = n; a.B = A; a.H = e.heads; a.D = D; a.max_qlen = 1;
-    a.scale = 1.0f / std::sqrt((float)D);
-    a.lds_min_qlen = c.m.opts.attn_lds_min; a.lds_waves = c.m.opts.attn_lds_waves; a.x6_min_qlen = c.m.opts.attn_x6_min;
-    a.x3h = (c.m.opts.x3h & 8) ? 1 : 0; a.x3h_flag = c.m.opts.x3h_flag;
-    a.ds_short = c.m.opts.attn_ds;
+    a.u_qlen = 1; a.u_kvstride = n; a.u_kvlen = n; a.B = A; a.max_qlen = 1;
     MT2_HIP(launch_attention(a, c.s));
     // y = x[last rows] + out_proj(att): the residual rows sit n*d floats apart starting at row n-1
     const Pending py = linear_residual(c, att, d, A, w.wo, w.bo, d, d, y, s.stat, x + (size_t)(n - 1) * d, n * d);
@@ -604,7 +606,7 @@ static void encoder_layer_last(const Ctx& c, const EncW& e, const EncLayerW& w, 
 static Pending encoder_layer_first_cached(const Ctx& c, const EncW& e, const EncLayerW& w, float* x, int n, int A,
                                           float* qkv_cache, int cs, const EncScratch& s, bool fill_all) {
     MT2_REQUIRE(!e.conv_ff, "AR step layers use the Linear feed-forward");
-    const int d = e.d, M = A * n, D = d / e.heads;
+    const int d = e.d, M = A * n;
     if (fill_all && n > 1) {
         // first step of a run that starts from a forced history (prompt prefix, teacher-forced tests): the cache
         // has no rows yet - LN1 -> QKV of ALL n rows, compact, then one strided copy into the cache layout
@@ -615,16 +617,13 @@ static Pending encoder_layer_first_cached(const Ctx& c, const EncW& e, const Enc
         // LN1 -> QKV of the newest row of every active sequence, written into the cache at row stride cs
         ln_linear(c, x, d, M, n, n - 1, A, ln1_qkv(w, d), 3 * d, d, qkv_cache + (size_t)(n - 1) * 3 * d, cs * 3 * d, s.h);
     }
-    AttnP a{};
+    AttnP a = attn_params(c, e);
     a.Q = qkv_cache; a.ldq = 3 * d; a.K = qkv_cache + d; a.ldk = 3 * d; a.V = qkv_cache + 2 * d; a.ldv = 3 * d;
     a.O = s.att; a.ldo = d;
     a.u_qstride = cs; a.u_qlen = n; a.u_kvstride = cs; a.u_kvlen = n; a.u_ostride = n;
-    a.B = A; a.H = e.heads; a.D = D; a.max_qlen = n; a.scale = 1.0f / std::sqrt((float)D);
-    a.lds_min_qlen = c.m.opts.attn_lds_min; a.lds_waves = c.m.opts.attn_lds_waves; a.x6_min_qlen = c.m.opts.attn_x6_min;
-    a.x3h = (c.m.opts.x3h & 8) ? 1 : 0; a.x3h_flag = c.m.opts.x3h_flag;
-    a.ds_short = c.m.opts.attn_ds;
+    a.B = A; a.max_qlen = n;
     const bool opl = ar_outproj_takes_planes(c, e, w, x, M, s.att, s);
-    a.o_planes = opl ? 1 : 0; a.x3h_flag = c.m.opts.x3h_flag;
+    a.o_planes = opl ? 1 : 0;
     MT2_HIP(launch_attention(a, c.s));
     return ar_layer_tail(c, e, w, x, M, s.att, s, opl);
 }
@@ -918,14 +917,11 @@ static TcResult tc_latent_rows(const Ctx& c, const std::vector<PhoneSet>& sets, 
     MT2_HIP(hipStreamWaitEvent(c.s, m.ev_join[0], 0));
     float* kv = c.ws.get<float>((size_t)mp.X.R * 2 * H);
     linear(c, ctx, H, mp.X.R, m.x_wkv, m.x_bkv, 2 * H, H, kv, 2 * H);
-    AttnP a{};
+    AttnP a = attn_params(c, 1, H);
     a.Q = q; a.ldq = H; a.K = kv; a.ldk = 2 * H; a.V = kv + H; a.ldv = 2 * H; a.O = sc.att; a.ldo = H;
     a.q_start = P.d_start; a.q_len = P.d_len;
     a.kv_start = S > 1 ? ip2.dev(o_kvs) : mp.X.d_start; a.kv_len = S > 1 ? ip2.dev(o_kvl) : mp.X.d_len;
-    a.B = BS; a.H = 1; a.D = H; a.max_qlen = P.maxlen; a.max_kvlen = mp.X.maxlen; a.scale = 1.0f / std::sqrt((float)H);
-    a.lds_min_qlen = c.m.opts.attn_lds_min; a.lds_waves = c.m.opts.attn_lds_waves; a.x6_min_qlen = c.m.opts.attn_x6_min;
-    a.x3h = (c.m.opts.x3h & 8) ? 1 : 0; a.x3h_flag = c.m.opts.x3h_flag;
-    a.ds_short = c.m.opts.attn_ds;
+    a.B = BS; a.max_qlen = P.maxlen; a.max_kvlen = mp.X.maxlen;
     MT2_HIP(launch_attention(a, c.s));
     float* o = c.ws.get<float>((size_t)P.R * H);
     linear(c, sc.att, H, P.R, m.x_wo, m.x_bo, H, H, o, H);
@@ -1009,53 +1005,51 @@ struct ArPrefix {
     int stride = 0;               // PLM: row stride of `data` in elements (0: P)
 };
 
-// MegaADM.infer (models/megatts2.py:257-275).  tc: rows buffer (ld), utterance b's first row row0[b].
-static void adm_run(const Ctx& c, const float* tc, int ld_tc, int tc_rows, const std::vector<int>& row0,
-                    const int* lens, int B, int32_t* dur_out, float* flt_out, int dstride,
-                    const ArPrefix& pre = ArPrefix()) {
+// ---- one driver for both AR models.  ar_run owns what they share: the length order, the stream groups with their integer
+// plan (first input row, length, utterance of every sequence), history-independent scratch, fork / join and the step loop;
+// a stage (AdmStage / PlmStage below, resolved at compile time - nothing is type-erased or allocated per step) supplies
+//   plan(ip)                  its own integers of the call's plan, before the upload
+//   begin(c, hstride, B)      what runs in front of the groups on the caller's stream; the history buffer [B, hstride]
+//   init_hist(c, ip, q)       the history rows of group q (and the group's stage-specific scratch)
+//   step_input(cg, ip, q, n)  x rows of the A active sequences at n positions
+//   head(cg, ip, q, y, n, t)  position n of the history from the last-position rows y [A, d]
+//   finalize(ip, q, s)        the group's results into the caller's buffers
+struct ArGrp {
+    int g = 0, first = 0;                   // group index; sequences in the groups before it (row of the run's history buffer)
+    int B = 0, nmax = 0, A = 0;             // sequences, positions of the longest, sequences still active
+    int o_row = 0, o_len = 0, o_slot = 0;   // plan offsets
+    std::vector<int> len, slot;
+    float *x = nullptr, *ylast = nullptr, *qkv0 = nullptr; EncScratch sc{};
+};
+template <class Stage>
+static void ar_run(const Ctx& c, const EncW& e, const std::vector<int>& row0, const int* lens, int B, int stage_groups,
+                   const ArPrefix& pre, Stage& st) {
     mt2_model& m = c.m;
-    const mt2_config& cfg = m.cfg;
-    const OptGuard pairs_guard(m.opts.ln_pairs, m.opts.ln_pairs_adm);
-    const EncW& e = m.adm_enc;
-    const int d = e.d, Dc = cfg.adm_tc_emb_dim, De = cfg.adm_emb_dim;
-    ArOrder ord = ar_order(lens, B);
-    MT2_REQUIRE(ord.nmax <= cfg.max_positions, "ADM sequence longer than the positional table");
-    for (int b = 0; b < B; ++b) MT2_REQUIRE(lens[b] > pre.P, "forced history is not shorter than the sequence");
-    ArGroups grp = ar_groups(m, c.s, ord, B, m.adm_groups);
-    struct Grp {
-        int B, nmax, A; int o_tcrow, o_len, o_slot;
-        std::vector<int> len;
-        float *p, *x, *ylast, *qkv0; EncScratch sc;
-    };
-    std::vector<Grp> gs(grp.G);
+    const int d = e.d;
+    const ArOrder ord = ar_order(lens, B);
+    const ArGroups grp = ar_groups(m, c.s, ord, B, stage_groups);
+    std::vector<ArGrp> gs(grp.G);
     IntPlan ip;
-    for (int g = 0; g < grp.G; ++g) {
-        Grp& q = gs[g];
-        q.B = (int)grp.slots[g].size();
-        std::vector<int> tcrow, slot;
+    for (int g = 0, first = 0; g < grp.G; ++g) {
+        ArGrp& q = gs[g];
+        q.g = g; q.first = first;
+        std::vector<int> row;
         for (int j : grp.slots[g]) {
-            tcrow.push_back(row0[ord.slot_b[j]]);
+            row.push_back(row0[ord.slot_b[j]]);
             q.len.push_back(ord.len[j]);
-            slot.push_back(ord.slot_b[j]);
+            q.slot.push_back(ord.slot_b[j]);
         }
+        q.B = q.A = (int)q.len.size();
         q.nmax = q.len[0];
-        q.A = q.B;
-        q.o_tcrow = ip.add(tcrow); q.o_len = ip.add(q.len); q.o_slot = ip.add(slot);
+        first += q.B;
+        q.o_row = ip.add(row); q.o_len = ip.add(q.len); q.o_slot = ip.add(q.slot);
     }
+    st.plan(ip);
     ip.upload(c.ws, c.m.pinned(), c.s);
-
-    float* tcemb = c.ws.get<float>((size_t)tc_rows * Dc);
-    linear(c, tc, ld_tc, tc_rows, m.adm_wtc, nullptr, Dc, cfg.adm_tc_dim, tcemb, Dc);   // tc_linear_emb (no bias)
-    const int pstride = ord.nmax + 1;
-    float* p_all = c.ws.get<float>((size_t)B * pstride);
-    int pofs = 0;
-    for (Grp& q : gs) {
+    st.begin(c, ord.nmax + 1, B);
+    for (ArGrp& q : gs) {
         const int Mmax = q.B * q.nmax;
-        q.p = p_all + (size_t)pofs * pstride;
-        pofs += q.B;
-        // p_code starts at 0.0 (:262), followed by the forced history if any
-        MT2_HIP(launch_adm_init_hist(q.p, pstride, static_cast<const float*>(pre.data), pre.P, ip.dev(q.o_slot), q.B,
-                                     c.s));
+        st.init_hist(c, ip, q);
         q.x = c.ws.get<float>((size_t)Mmax * d);
         q.sc = enc_scratch(c, e, std::max(Mmax, 2 * q.B));   // last layer: q | att rows of A sequences
         q.ylast = c.ws.get<float>((size_t)q.B * d);
@@ -1063,128 +1057,130 @@ static void adm_run(const Ctx& c, const float* tc, int ld_tc, int tc_rows, const
     }
     ar_fork(m, grp);
     const int t_end = pre.max_steps > 0 ? std::min(ord.nmax, pre.P + pre.max_steps) : ord.nmax;
-    auto step = [&](int g, int t) {
-        const int n = t + 1;
-        Grp& q = gs[g];
-        while (q.A > 0 && q.len[q.A - 1] <= t) --q.A;
-        if (q.A == 0) return;
-        Ctx cg{m, grp.stream[g], c.ws};
-        MT2_HIP(launch_adm_step_input(tcemb, Dc, ip.dev(q.o_tcrow), m.adm_wdt, q.p, pstride, m.pe_adm, q.x, Dc, De,
-                                      n, q.A, cg.s));
-        const float* y = ar_step_layers(cg, e, q.x, n, q.A, q.qkv0, q.nmax, q.sc, q.ylast, t == pre.P && pre.P > 0);
-        MT2_HIP(launch_adm_predict(y, d, m.adm_wpred, q.p, pstride, n, 1, q.A, cg.s));
-    };
-    for (int t = pre.P; t < t_end; ++t)        // interleaved: both chains' queues are fed step by step
-        for (int g = 0; g < grp.G; ++g) step(g, t);
-    for (int g = 0; g < grp.G; ++g) {
-        Grp& q = gs[g];
-        MT2_HIP(launch_adm_finalize(q.p, pstride, ip.dev(q.o_len), ip.dev(q.o_slot), dur_out, flt_out, dstride, q.B,
-                                    dstride < q.nmax ? dstride : q.nmax, grp.stream[g]));
-    }
+    for (int t = pre.P; t < t_end; ++t)        // interleaved: all chains' queues are fed step by step
+        for (int g = 0; g < grp.G; ++g) {
+            ArGrp& q = gs[g];
+            while (q.A > 0 && q.len[q.A - 1] <= t) --q.A;
+            if (q.A == 0) continue;
+            const int n = t + 1;
+            const Ctx cg{m, grp.stream[g], c.ws};
+            st.step_input(cg, ip, q, n);
+            const float* y = ar_step_layers(cg, e, q.x, n, q.A, q.qkv0, q.nmax, q.sc, q.ylast, t == pre.P && pre.P > 0);
+            st.head(cg, ip, q, y, n, t);
+        }
+    for (int g = 0; g < grp.G; ++g) st.finalize(ip, gs[g], grp.stream[g]);
     ar_join(m, grp);
+}
+static int longest(const int* lens, int B) { return B > 0 ? *std::max_element(lens, lens + B) : 0; }
+
+// MegaADM.infer (models/megatts2.py:257-275).  tc: rows buffer (ld), utterance b's first row row0[b].
+struct AdmStage {
+    mt2_model& m; const float* tc; int ld_tc, tc_rows; const ArPrefix& pre;
+    int32_t* dur_out; float* flt_out; int dstride;
+    float *tcemb = nullptr, *p_all = nullptr; int pstride = 0;
+    float* p(const ArGrp& q) const { return p_all + (size_t)q.first * pstride; }
+    void plan(IntPlan&) {}
+    void begin(const Ctx& c, int hstride, int B) {
+        const int Dc = m.cfg.adm_tc_emb_dim;
+        tcemb = c.ws.get<float>((size_t)tc_rows * Dc);
+        linear(c, tc, ld_tc, tc_rows, m.adm_wtc, nullptr, Dc, m.cfg.adm_tc_dim, tcemb, Dc);   // tc_linear_emb (no bias)
+        pstride = hstride;
+        p_all = c.ws.get<float>((size_t)B * pstride);
+    }
+    void init_hist(const Ctx& c, const IntPlan& ip, const ArGrp& q) {      // p_code starts at 0.0 (:262), followed by the forced history if any
+        MT2_HIP(launch_adm_init_hist(p(q), pstride, static_cast<const float*>(pre.data), pre.P, ip.dev(q.o_slot), q.B, c.s));
+    }
+    void step_input(const Ctx& cg, const IntPlan& ip, const ArGrp& q, int n) {
+        MT2_HIP(launch_adm_step_input(tcemb, m.cfg.adm_tc_emb_dim, ip.dev(q.o_row), m.adm_wdt, p(q), pstride, m.pe_adm, q.x,
+                                      m.cfg.adm_tc_emb_dim, m.cfg.adm_emb_dim, n, q.A, cg.s));
+    }
+    void head(const Ctx& cg, const IntPlan&, const ArGrp& q, const float* y, int n, int) {
+        MT2_HIP(launch_adm_predict(y, m.adm_enc.d, m.adm_wpred, p(q), pstride, n, 1, q.A, cg.s));
+    }
+    void finalize(const IntPlan& ip, const ArGrp& q, hipStream_t s) {
+        MT2_HIP(launch_adm_finalize(p(q), pstride, ip.dev(q.o_len), ip.dev(q.o_slot), dur_out, flt_out, dstride, q.B,
+                                    dstride < q.nmax ? dstride : q.nmax, s));
+    }
+};
+static void adm_run(const Ctx& c, const float* tc, int ld_tc, int tc_rows, const std::vector<int>& row0,
+                    const int* lens, int B, int32_t* dur_out, float* flt_out, int dstride,
+                    const ArPrefix& pre = ArPrefix()) {
+    mt2_model& m = c.m;
+    const OptGuard pairs_guard(m.opts.ln_pairs, m.opts.ln_pairs_adm);
+    MT2_REQUIRE(longest(lens, B) <= m.cfg.max_positions, "ADM sequence longer than the positional table");
+    for (int b = 0; b < B; ++b) MT2_REQUIRE(lens[b] > pre.P, "forced history is not shorter than the sequence");
+    AdmStage st{m, tc, ld_tc, tc_rows, pre, dur_out, flt_out, dstride};
+    ar_run(c, m.adm_enc, row0, lens, B, m.adm_groups, pre, st);
 }
 
 // MegaPLM.infer (models/megatts2.py:165-181).  cond rows buffer (ld), utterance b's first row row0[b]; lens[b] =
 // ALL positions of the sequence (prompt prefix + target); codes_out / last_logits receive the target positions.
 // smp (validated by the caller; nullptr = greedy): each step's code is drawn by launch_sample_rows instead of the argmax -
 // the same launch count, utterance b's seed smp->seeds[b], counter = the target position t - P.
-static void plm_run(const Ctx& c, const float* cond, int ld_c, const std::vector<int>& row0, const int* lens, int B,
-                    int64_t* codes_out, int ostride, float* last_logits, int logit_tmax,
-                    const ArPrefix& pre = ArPrefix(), const mt2_sampling* smp = nullptr) {
-    mt2_model& m = c.m;
-    const mt2_config& cfg = m.cfg;
-    const OptGuard pairs_guard(m.opts.ln_pairs, 0);      // the hand-off pays in the ADM only (profiles/r05_opts_ab.txt)
-    const EncW& e = m.plm_enc;
-    const int d = e.d, Dc = cfg.plm_tc_dim, De = cfg.plm_vq_dim, NB = cfg.plm_bins;
-    ArOrder ord = ar_order(lens, B);
-    MT2_REQUIRE(ord.nmax <= cfg.max_positions, "PLM sequence longer than the positional table");
-    MT2_REQUIRE(1024 < cfg.plm_bins + 2, "pc_embedding too small for the BOS id 1024");
-    for (int b = 0; b < B; ++b) MT2_REQUIRE(lens[b] > pre.P, "prompt prefix is not shorter than the sequence");
-    ArGroups grp = ar_groups(m, c.s, ord, B, m.plm_groups);
-    struct Grp {
-        int B, nmax, A; int o_crow, o_len, o_slot;
-        std::vector<int> len, slot;
-        int64_t* codes; float *x, *ylast, *qkv0, *logits; EncScratch sc;
-    };
-    std::vector<Grp> gs(grp.G);
-    IntPlan ip;
-    for (int g = 0; g < grp.G; ++g) {
-        Grp& q = gs[g];
-        q.B = (int)grp.slots[g].size();
-        std::vector<int> crow;
-        for (int j : grp.slots[g]) {
-            crow.push_back(row0[ord.slot_b[j]]);
-            q.len.push_back(ord.len[j]);
-            q.slot.push_back(ord.slot_b[j]);
-        }
-        q.nmax = q.len[0];
-        q.A = q.B;
-        q.o_crow = ip.add(crow); q.o_len = ip.add(q.len); q.o_slot = ip.add(q.slot);
-    }
-    int o_seed = -1;
-    if (smp) {      // (lo, hi) words of every utterance's seed, uploaded once per call with the plan
-        std::vector<int> sd(2 * (size_t)B);
-        for (int b = 0; b < B; ++b) {
+struct PlmStage {
+    mt2_model& m; const float* cond; int ld_c; int nseq; const ArPrefix& pre; const mt2_sampling* smp;
+    int64_t* codes_out; int ostride; float* last_logits; int logit_tmax;
+    int64_t* codes_all = nullptr; int cstride = 0, o_seed = -1;
+    std::vector<float*> logits;      // per group: [B, bins]
+    int64_t* codes(const ArGrp& q) const { return codes_all + (size_t)q.first * cstride; }
+    void plan(IntPlan& ip) {
+        if (!smp) return;       // (lo, hi) words of every utterance's seed, uploaded once per call with the plan
+        std::vector<int> sd(2 * (size_t)nseq);
+        for (int b = 0; b < nseq; ++b) {
             sd[2 * b] = (int)(uint32_t)smp->seeds[b];
             sd[2 * b + 1] = (int)(uint32_t)(smp->seeds[b] >> 32);
         }
         o_seed = ip.add(sd);
     }
-    ip.upload(c.ws, c.m.pinned(), c.s);
-
-    const int cstride = ord.nmax + 1;
-    int64_t* codes_all = c.ws.get<int64_t>((size_t)B * cstride);
-    int cofs = 0;
-    for (Grp& q : gs) {
-        const int Mmax = q.B * q.nmax;
-        q.codes = codes_all + (size_t)cofs * cstride;
-        cofs += q.B;
-        // BOS literal 1024 (models/megatts2.py:170), then the prompt's codes if any - on the device, no host staging
-        MT2_HIP(launch_plm_init_hist(q.codes, cstride, 1024, static_cast<const int64_t*>(pre.data), pre.P,
-                                     pre.stride > 0 ? pre.stride : pre.P, ip.dev(q.o_slot), q.B, c.s));
-        q.x = c.ws.get<float>((size_t)Mmax * d);
-        q.logits = c.ws.get<float>((size_t)q.B * NB);
-        q.sc = enc_scratch(c, e, std::max(Mmax, 2 * q.B));   // last layer: q | att rows of A sequences
-        q.ylast = c.ws.get<float>((size_t)q.B * d);
-        q.qkv0 = e.layers.size() >= 2 ? c.ws.get<float>((size_t)Mmax * 3 * d) : nullptr;   // layer-0 QKV cache
+    void begin(const Ctx& c, int hstride, int B) {
+        cstride = hstride;
+        codes_all = c.ws.get<int64_t>((size_t)B * cstride);
     }
-    ar_fork(m, grp);
-    const int t_end = pre.max_steps > 0 ? std::min(ord.nmax, pre.P + pre.max_steps) : ord.nmax;
-    auto step = [&](int g, int t) {
-        const int n = t + 1;
-        Grp& q = gs[g];
-        while (q.A > 0 && q.len[q.A - 1] <= t) --q.A;
-        if (q.A == 0) return;
-        Ctx cg{m, grp.stream[g], c.ws};
-        MT2_HIP(launch_plm_step_input(cond, ld_c, ip.dev(q.o_crow), m.plm_emb, q.codes, cstride, m.pe_plm, q.x, Dc,
-                                      De, n, q.A, NB + 2, cg.s));
-        const float* y = ar_step_layers(cg, e, q.x, n, q.A, q.qkv0, q.nmax, q.sc, q.ylast, t == pre.P && pre.P > 0);
-        // predict_layer on the last position of each sequence only (:178 takes [:, -1:]), then argmax
+    void init_hist(const Ctx& c, const IntPlan& ip, const ArGrp& q) {
+        // BOS literal 1024 (models/megatts2.py:170), then the prompt's codes if any - on the device, no host staging
+        MT2_HIP(launch_plm_init_hist(codes(q), cstride, 1024, static_cast<const int64_t*>(pre.data), pre.P,
+                                     pre.stride > 0 ? pre.stride : pre.P, ip.dev(q.o_slot), q.B, c.s));
+        logits.push_back(c.ws.get<float>((size_t)q.B * m.cfg.plm_bins));
+    }
+    void step_input(const Ctx& cg, const IntPlan& ip, const ArGrp& q, int n) {
+        MT2_HIP(launch_plm_step_input(cond, ld_c, ip.dev(q.o_row), m.plm_emb, codes(q), cstride, m.pe_plm, q.x, m.cfg.plm_tc_dim,
+                                      m.cfg.plm_vq_dim, n, q.A, m.cfg.plm_bins + 2, cg.s));
+    }
+    void head(const Ctx& cg, const IntPlan& ip, const ArGrp& q, const float* y, int n, int t) {
+        // predict_layer on the last position of each sequence only (:178 takes [:, -1:]), then argmax (or the seeded draw)
+        const int d = m.plm_enc.d, NB = m.cfg.plm_bins;
+        float* lg = logits[q.g];
         GemmP p{};
         p.X = y; p.ldx = d; p.Rx = q.A; p.Cin = d; p.W = m.plm_wpred;
-        p.C = q.logits; p.ldc = NB; p.M = q.A; p.N = NB;
+        p.C = lg; p.ldc = NB; p.M = q.A; p.N = NB;
         gemm(cg, p);
         if (smp)
-            MT2_HIP(launch_sample_rows(q.logits, NB, NB, q.codes, cstride, n, q.A, smp->temperature, smp->top_k, smp->top_p,
+            MT2_HIP(launch_sample_rows(lg, NB, NB, codes(q), cstride, n, q.A, smp->temperature, smp->top_k, smp->top_p,
                                        reinterpret_cast<const uint32_t*>(ip.dev(o_seed)), ip.dev(q.o_slot), nullptr, t - pre.P,
                                        cg.s));
         else
-            MT2_HIP(launch_argmax_rows(q.logits, NB, NB, q.codes, cstride, n, q.A, cg.s));
+            MT2_HIP(launch_argmax_rows(lg, NB, NB, codes(q), cstride, n, q.A, cg.s));
         if (last_logits && t - pre.P < logit_tmax)
             for (int j = 0; j < q.A; ++j)
-                MT2_HIP(hipMemcpyAsync(last_logits + ((size_t)q.slot[j] * logit_tmax + (t - pre.P)) * NB,
-                                       q.logits + (size_t)j * NB, sizeof(float) * NB, hipMemcpyDeviceToDevice,
-                                       cg.s));
-    };
-    for (int t = pre.P; t < t_end; ++t)
-        for (int g = 0; g < grp.G; ++g) step(g, t);
-    for (int g = 0; g < grp.G; ++g) {
-        Grp& q = gs[g];
-        const int nt = q.nmax - pre.P;
-        MT2_HIP(launch_plm_finalize(q.codes, cstride, ip.dev(q.o_len), ip.dev(q.o_slot), codes_out, ostride, q.B,
-                                    ostride < nt ? ostride : nt, pre.P, grp.stream[g]));
+                MT2_HIP(hipMemcpyAsync(last_logits + ((size_t)q.slot[j] * logit_tmax + (t - pre.P)) * NB, lg + (size_t)j * NB,
+                                       sizeof(float) * NB, hipMemcpyDeviceToDevice, cg.s));
     }
-    ar_join(m, grp);
+    void finalize(const IntPlan& ip, const ArGrp& q, hipStream_t s) {
+        const int nt = q.nmax - pre.P;
+        MT2_HIP(launch_plm_finalize(codes(q), cstride, ip.dev(q.o_len), ip.dev(q.o_slot), codes_out, ostride, q.B,
+                                    ostride < nt ? ostride : nt, pre.P, s));
+    }
+};
+static void plm_run(const Ctx& c, const float* cond, int ld_c, const std::vector<int>& row0, const int* lens, int B,
+                    int64_t* codes_out, int ostride, float* last_logits, int logit_tmax,
+                    const ArPrefix& pre = ArPrefix(), const mt2_sampling* smp = nullptr) {
+    mt2_model& m = c.m;
+    const OptGuard pairs_guard(m.opts.ln_pairs, 0);      // the hand-off pays in the ADM only (profiles/r05_opts_ab.txt)
+    MT2_REQUIRE(longest(lens, B) <= m.cfg.max_positions, "PLM sequence longer than the positional table");
+    MT2_REQUIRE(1024 < m.cfg.plm_bins + 2, "pc_embedding too small for the BOS id 1024");
+    for (int b = 0; b < B; ++b) MT2_REQUIRE(lens[b] > pre.P, "prompt prefix is not shorter than the sequence");
+    PlmStage st{m, cond, ld_c, B, pre, smp, codes_out, ostride, last_logits, logit_tmax};
+    ar_run(c, m.plm_enc, row0, lens, B, m.plm_groups, pre, st);
 }
 
 // ---------------------------------------------------------------------------------------------------

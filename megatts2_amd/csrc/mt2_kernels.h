@@ -46,7 +46,7 @@ struct GemmP {
     const int* rowbase; int a_mul; int shift0; int taps; int dil; int Cin;
     const float* W; long long strideW; int ldw;
     unsigned long long* dbg = nullptr;   // MT2_PHASE_TIMING builds only: per-phase cycle sums of one wave (tools/x6_phase_timing.py)
-    int epi_t4 = 1;             // 16-byte-store epilogue where the layout allows it (set by launch_gemm from EngineOpts::epi_t4)
+    int epi_t4 = 1;             // 16-byte-store epilogue where the layout allows it (always on: launch_gemm sets it)
     int sk_nw = 8;              // gemm_skinny_tm_kernel: waves per workgroup that split K (8; 16 = option skinny_nw, set by launch_gemm)
     int a_planes = 0;           // 1: X holds fp16 planes ([32 hi | 32 lo] per 32 k of a row, x3h_planes.h's block layout without a row scale)
                                 // written by a producer kernel (LnP::out_planes): x3h loader / K-split tiles only, no prologue, Cin % 32 = 0
@@ -107,7 +107,6 @@ struct EngineOpts {
     bool win_conv = true;        // window-convolution kernel for narrow square convs (Cin = Cout in {32, 64, 128})
     bool x6_conv = true;         // ... on the bf16 matrix pipe, f32-equivalent 3-way split (6 products), where W3 planes exist
     bool x6_gemm = true;         // the implicit GEMMs likewise (loader-wave and K-split tiles)
-    bool x6_splitk = true;       // K slices (through the next LayerNorm) to give the N = d AR GEMMs enough x6 tiles
     int x3h = 15;                // f32-equivalent THREE-product form on the fp16 pipe (gemm_x3h.hip) wherever an x6 tile has one and the
                                  // weights come with fp16 planes (GemmP::Wh); bits: 1 the 128x128 loader tile, 2 the K-split tiles of the
                                  // AR steps, 4 the window convolutions, 8 the long-sequence attention kernel (AttnP::x3h: C5 -3.3 %,
@@ -119,7 +118,6 @@ struct EngineOpts {
                                  // 1, 3: the 32x64 k4 and 64x64 k2/k4 tiles (84, 85); 2, 4: + the 32x32 k8 tile (86); 5: the
                                  // 64x64 tile only.  Default 4: isolated launches +10..50 %
                                  // (profiles/r03_gemm_sweep_x6k.txt), C3 step -1.6 % (profiles/r03_ab_interleaved_v1.txt)
-    bool epi_t4 = true;          // DPP-transposed 16-byte-store epilogue for wave tiles without epilogue prefetch
     int a_planes = 3;            // producers of fp16 planes for x3h GEMMs that take their A operand as planes (GemmP::a_planes; wherever
                                  // gemm_takes_planes() says so).  Bit 0: LayerNorm -> Linear pairs of the AR layers and LayerNorm -> Conv1d inside
                                  // the conv stacks (LnP::out_planes); bit 1: ff.0's epilogue stores relu(..) as planes for ff.3 (GemmP::c_planes);
@@ -131,10 +129,7 @@ struct EngineOpts {
     int attn_lds_min = 640;      // attention: from this many queries per sequence on the LDS-tiled kernel (AttnP::lds_min_qlen; 0 never)
     int attn_x6_min = 192;       // attention on the bf16 pipe (f32-equivalent, AttnP::x6_min_qlen) from this many queries on; 0: never
                                  // (C5 step 5525 -> 5314 ms at 192, 5376 at 448: profiles/r03_opts_ab.txt)
-    int attn_lds_waves = 0;      // ... its query tiles per workgroup (AttnP::lds_waves)
-    int attn_ds = 1;             // short sequences on the AR heads: head dim split over the waves as well (AttnP::ds_short)
     bool skinny_tm = true;       // ... on the tile-major weight copy where one exists (gemm_skinny_tm_kernel; LayerNorm prologue included)
-    int skinny_groups = 1;       // ... only for launches with at least this many GemmP groups (split-K slabs)
     int skinny_pairs = 1;        // launches of at most skinny_rows rows: the residual GEMM's epilogue leaves (mean, M2) pairs per 16-column block
                                  // and the LayerNorm prologue of the consuming launch merges them instead of re-reading all M x K rows
     int skinny_nw = 16;          // waves of the tile-major weight-streaming kernel that split K (8; 16: four per SIMD - twelve for K = 768 -
@@ -310,9 +305,6 @@ hipError_t launch_vq_argmin(const float* x, int ldx, int D, const float* xe, int
                             const int* valid, int64_t* idx, int M, hipStream_t s);
 // ee[j] = sum_d E[j,d]^2
 hipError_t launch_row_sqnorm(const float* E, int D, float* ee, int N, hipStream_t s);
-// decoder input (models/megatts2.py:361-366): out[r] = [tc[tcmap[r]], E[codes[codemap[r]]]]
-hipError_t launch_decoder_input(const float* tc, int ld_tc, const int* tcmap, const float* E, const int64_t* codes,
-                                const int* codemap, float* out, int Dc, int Dq, int R, int bins, hipStream_t s);
 // zq rows (modules/vqpe.py:59-61): out[r] = E[codes[codemap[r]]]
 hipError_t launch_codebook_rows(const float* E, const int64_t* codes, const int* codemap, float* out, int ldo,
                                 int Dq, int R, int bins, hipStream_t s);
@@ -320,7 +312,6 @@ hipError_t launch_codebook_rows(const float* E, const int64_t* codes, const int*
 hipError_t launch_reflect_pad_blocks(const float* wav, long long wstride, const int* blk_b, const int* blk_t,
                                      const int* len, int hop, int pad, float* out, int R, hipStream_t s);
 hipError_t launch_magnitude(const float* spec, int lds_, int F, float* out, int ldo, int M, hipStream_t s);
-hipError_t launch_tanh_col(const float* x, int ldx, float* out, long long n, hipStream_t s);
 // reflect halo rows of every utterance (rows start[b]*scale .. +len[b]*scale) in front of a "same" convolution
 hipError_t launch_fill_reflect(float* x, int ld, int C, const int* start, const int* len, int B, long long scale, int G,
                                hipStream_t s);

@@ -850,30 +850,6 @@ hipError_t launch_row_sqnorm(const float* E, int D, float* ee, int N, hipStream_
     return hipGetLastError();
 }
 
-// decoder input rows (models/megatts2.py:361-366): [tc_latent_expand (gather), zq (codebook row, x8 repeat)]
-__global__ void decoder_input_kernel(const float* tc, int ld_tc, const int* tcmap, const float* E,
-                                     const int64_t* codes, const int* codemap, float* out, int Dc, int Dq, int R,
-                                     int bins) {
-    const int D = Dc + Dq, c4n = D >> 2;
-    MT2_ROW_LOOP(R, D) {
-        const int r = (int)(i_ / c4n), c = (int)(i_ % c4n) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        const int tr = tcmap[r];
-        if (tr >= 0) {
-            if (c < Dc) v = *reinterpret_cast<const float4*>(tc + (long long)tr * ld_tc + c);
-            else v = *reinterpret_cast<const float4*>(E + clamp_id(codes[codemap[r]], bins) * Dq + (c - Dc));
-        }
-        *reinterpret_cast<float4*>(out + (long long)r * D + c) = v;
-    }
-}
-hipError_t launch_decoder_input(const float* tc, int ld_tc, const int* tcmap, const float* E, const int64_t* codes,
-                                const int* codemap, float* out, int Dc, int Dq, int R, int bins, hipStream_t s) {
-    if (R <= 0) return hipSuccess;
-    hipLaunchKernelGGL(decoder_input_kernel, row_grid((long long)R * ((Dc + Dq) >> 2)), dim3(256), 0, s, tc, ld_tc,
-                       tcmap, E, codes, codemap, out, Dc, Dq, R, bins);
-    return hipGetLastError();
-}
-
 // EuclideanCodebook.dequantize (core_vq.py:188-190) + the x8 repeat of vqpe.py:59-61 via codemap
 __global__ void codebook_rows_kernel(const float* E, const int64_t* codes, const int* codemap, float* out, int ldo,
                                      int Dq, int R, int bins) {
@@ -891,17 +867,6 @@ hipError_t launch_codebook_rows(const float* E, const int64_t* codes, const int*
     if (R <= 0) return hipSuccess;
     hipLaunchKernelGGL(codebook_rows_kernel, row_grid((long long)R * (Dq >> 2)), dim3(256), 0, s, E, codes, codemap,
                        out, ldo, Dq, R, bins);
-    return hipGetLastError();
-}
-
-__global__ void tanh_col_kernel(const float* x, int ldx, float* out, long long n) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x)
-        out[i] = tanhf(x[i * ldx]);
-}
-hipError_t launch_tanh_col(const float* x, int ldx, float* out, long long n, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(tanh_col_kernel, row_grid(n), dim3(256), 0, s, x, ldx, out, n);
     return hipGetLastError();
 }
 

@@ -335,14 +335,15 @@ class NativeModel:
 
     @staticmethod
     def _sampling(sampling, seeds, B: int):
-        """(mt2_sampling struct, its seed array) of a sampled call, or (None, None) for greedy decoding."""
+        """(pointer to the mt2_sampling struct, its seed array) of a sampled call, or (None, None) - the NULL the `_sampled` entry
+        points take for greedy decoding (the greedy C symbols forward to them with NULL themselves)."""
         sampling = sampmod.as_sampling(sampling)
         if sampling is None:
             if seeds is not None:
                 raise ValueError("seeds given without sampling")
             return None, None
         sd = sampmod.seed_array(seeds, B)
-        return sampling.to_c(sd), sd
+        return C.byref(sampling.to_c(sd)), sd
 
     def plm_infer(self, cond, lens=None, return_logits=False, prefix_codes=None, max_steps: int = 0, sampling=None,
                   seeds=None):
@@ -363,13 +364,9 @@ class NativeModel:
         ln = self._lens(lens, B, Tq)
         codes = torch.empty(B, Tq, device=cond.device, dtype=torch.int64)
         logits = torch.zeros(B, Tq, self.plm_cfg.vq_bins, device=cond.device, dtype=torch.float32) if return_logits else None
-        smp, _sd = self._sampling(sampling, seeds, B)
-        if smp is None:
-            self._guarded(lambda: self.lib.mt2_plm_infer_prompted(self.h, _stream(), _ptr(cond), _iptr(ln), Tq, B, _ptr(prefix_codes),
-                                                                  P, int(max_steps), _ptr(codes), _ptr(logits)))
-        else:       # counter-based draws: the range guard's repeat of the call draws the same u
-            self._guarded(lambda: self.lib.mt2_plm_infer_sampled(self.h, _stream(), _ptr(cond), _iptr(ln), Tq, B, _ptr(prefix_codes),
-                                                                 P, int(max_steps), _ptr(codes), _ptr(logits), C.byref(smp)))
+        smp, _sd = self._sampling(sampling, seeds, B)      # counter-based draws: the range guard's repeat of the call draws the same u
+        self._guarded(lambda: self.lib.mt2_plm_infer_sampled(self.h, _stream(), _ptr(cond), _iptr(ln), Tq, B, _ptr(prefix_codes),
+                                                             P, int(max_steps), _ptr(codes), _ptr(logits), smp))
         return (codes, logits) if return_logits else codes
 
     def vq_decode(self, codes):
@@ -422,6 +419,33 @@ class NativeModel:
         self._guarded(lambda: self.lib.mt2_hifigan(self.h, _stream(), _ptr(mel), _iptr(ln), T, B, _ptr(wav)))
         return wav
 
+    def _synth_buffers(self, forced_dur, pl, Np: int, tm_cap: Optional[int], vocoder: bool, dev, mel_out=None):
+        """The part the synthesis methods share: forced durations on the host (or None), the frame / code capacities they imply
+        and the output tensors -> (fd, tm_cap, tq_cap, mel, mel_lens, dur_out, codes_out, wav)."""
+        import torch
+        B = len(pl)
+        fd = None
+        if forced_dur is not None:
+            fd = _i32(forced_dur.detach().cpu().numpy() if hasattr(forced_dur, "detach") else forced_dur).reshape(B, Np)
+            tm_cap = max(tm_cap or 0, int(max(int(fd[b, :pl[b]].sum()) for b in range(B))))
+        if tm_cap is None:
+            tm_cap = 128 * Np          # clamp(1, 128) bounds every duration (models/megatts2.py:275)
+        tq_cap = -(-tm_cap // self.g_cfg.vqpe.stride)
+        nm = self.g_cfg.mrte.mel_bins
+        if mel_out is not None:
+            if (tuple(mel_out.shape) != (B, tm_cap, nm) or mel_out.dtype != torch.float32
+                    or not mel_out.is_contiguous() or mel_out.device != dev):
+                raise ValueError(f"mel_out must be a contiguous f32 [{B}, {tm_cap}, {nm}] tensor on {dev}")
+            mel = mel_out
+        else:
+            mel = torch.empty(B, tm_cap, nm, device=dev, dtype=torch.float32)
+        mel_lens = np.zeros(B, np.int32)
+        dur_out = torch.empty(B, Np, device=dev, dtype=torch.int32)
+        codes_out = torch.empty(B, tq_cap, device=dev, dtype=torch.int64)
+        pad = int(getattr(self.hg_cfg, "inference_padding", 0))
+        wav = torch.empty(B, self.hg_cfg.hop * (tm_cap + 2 * pad), device=dev, dtype=torch.float32) if vocoder else None
+        return fd, tm_cap, tq_cap, mel, mel_lens, dur_out, codes_out, wav
+
     def synthesize_batch(self, phone, phone_lens, prompt_mel, prompt_lens, forced_dur=None, forced_codes=None,
                          run_plm=True, vocoder=False, skip_adm=False, tm_cap: Optional[int] = None,
                          return_aux=False, prompt_vqpe=False, mel_out=None, check_range=True, sampling=None, seeds=None):
@@ -435,15 +459,9 @@ class NativeModel:
         phone = phone.contiguous().to(torch.int64)
         prompt_mel = self._f32(prompt_mel)
         pl, ml = self._lens(phone_lens, B, Np), self._lens(prompt_lens, B, Tp)
-        fd = None
-        if forced_dur is not None:
-            fd = _i32(forced_dur.detach().cpu().numpy() if hasattr(forced_dur, "detach") else forced_dur).reshape(B, Np)
-            need = int(max(int(fd[b, :pl[b]].sum()) for b in range(B)))
-            tm_cap = max(tm_cap or 0, need)
-        if tm_cap is None:
-            tm_cap = 128 * Np          # clamp(1, 128) bounds every duration (models/megatts2.py:275)
-        st = self.g_cfg.vqpe.stride
-        tq_cap = -(-tm_cap // st)
+        dev = prompt_mel.device
+        fd, tm_cap, tq_cap, mel, mel_lens, dur_out, codes_out, wav = self._synth_buffers(forced_dur, pl, Np, tm_cap, vocoder, dev,
+                                                                                        mel_out)
         if forced_codes is not None:
             forced_codes = forced_codes.contiguous().to(torch.int64)
             assert forced_codes.shape[0] == B
@@ -452,33 +470,14 @@ class NativeModel:
                 n = min(tq_cap, forced_codes.shape[1])
                 fc[:, :n] = forced_codes[:, :n]
                 forced_codes = fc
-        dev = prompt_mel.device
-        if mel_out is not None:
-            if (tuple(mel_out.shape) != (B, tm_cap, self.g_cfg.mrte.mel_bins) or mel_out.dtype != torch.float32
-                    or not mel_out.is_contiguous() or mel_out.device != dev):
-                raise ValueError(f"mel_out must be a contiguous f32 [{B}, {tm_cap}, {self.g_cfg.mrte.mel_bins}] tensor on {dev}")
-            mel = mel_out
-        else:
-            mel = torch.empty(B, tm_cap, self.g_cfg.mrte.mel_bins, device=dev, dtype=torch.float32)
-        mel_lens = np.zeros(B, np.int32)
-        dur_out = torch.empty(B, Np, device=dev, dtype=torch.int32)
-        codes_out = torch.empty(B, tq_cap, device=dev, dtype=torch.int64)
-        pad = int(getattr(self.hg_cfg, "inference_padding", 0))
-        wav = torch.empty(B, self.hg_cfg.hop * (tm_cap + 2 * pad), device=dev, dtype=torch.float32) if vocoder else None
         flags = ((MT2_RUN_PLM if run_plm else 0) | (MT2_RUN_VOCODER if vocoder else 0) | (MT2_SKIP_ADM if skip_adm else 0)
                  | (MT2_PROMPT_VQPE if prompt_vqpe else 0))
-        pcodes = torch.empty(B, -(-Tp // st), device=dev, dtype=torch.int64) if prompt_vqpe else None
+        pcodes = torch.empty(B, -(-Tp // self.g_cfg.vqpe.stride), device=dev, dtype=torch.int64) if prompt_vqpe else None
         smp, _sd = self._sampling(sampling, seeds, B)
-        if smp is None:
-            self._guarded(lambda: self.lib.mt2_synthesize_batch(
-                self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _iptr(fd), _ptr(forced_codes),
-                tq_cap, flags, _ptr(mel), tm_cap, _iptr(mel_lens), _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes)),
-                check_range)
-        else:
-            self._guarded(lambda: self.lib.mt2_synthesize_batch_sampled(
-                self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _iptr(fd), _ptr(forced_codes),
-                tq_cap, flags, _ptr(mel), tm_cap, _iptr(mel_lens), _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes),
-                C.byref(smp)), check_range)
+        self._guarded(lambda: self.lib.mt2_synthesize_batch_sampled(
+            self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _iptr(fd), _ptr(forced_codes),
+            tq_cap, flags, _ptr(mel), tm_cap, _iptr(mel_lens), _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes), smp),
+            check_range)
         if return_aux:
             return mel, mel_lens, {"dur": dur_out, "codes": codes_out, "wav": wav, "prompt_codes": pcodes}
         return mel, mel_lens
@@ -504,32 +503,14 @@ class NativeModel:
         st = self.g_cfg.vqpe.stride
         if len({-(-int(v) // st) for v in ml}) != 1:
             raise ValueError("prompt-conditioned batches need prompts of one pooled length (pad-free prefix layout)")
-        fd = None
-        if forced_dur is not None:
-            fd = _i32(forced_dur.detach().cpu().numpy() if hasattr(forced_dur, "detach") else forced_dur).reshape(B, Np)
-            tm_cap = max(tm_cap or 0, int(max(int(fd[b, :pl[b]].sum()) for b in range(B))))
-        if tm_cap is None:
-            tm_cap = 128 * Np          # clamp(1, 128) bounds every duration (models/megatts2.py:275)
-        tq_cap = -(-tm_cap // st)
         dev = prompt_mel.device
-        mel = torch.empty(B, tm_cap, self.g_cfg.mrte.mel_bins, device=dev, dtype=torch.float32)
-        mel_lens = np.zeros(B, np.int32)
-        dur_out = torch.empty(B, Np, device=dev, dtype=torch.int32)
-        codes_out = torch.empty(B, tq_cap, device=dev, dtype=torch.int64)
-        pad = int(getattr(self.hg_cfg, "inference_padding", 0))
-        wav = torch.empty(B, self.hg_cfg.hop * (tm_cap + 2 * pad), device=dev, dtype=torch.float32) if vocoder else None
+        fd, tm_cap, tq_cap, mel, mel_lens, dur_out, codes_out, wav = self._synth_buffers(forced_dur, pl, Np, tm_cap, vocoder, dev)
         pcodes = torch.empty(B, -(-Tp // st), device=dev, dtype=torch.int64)
         smp, _sd = self._sampling(sampling, seeds, B)
-        if smp is None:
-            self._guarded(lambda: self.lib.mt2_synthesize_prompt_conditioned(
-                self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _ptr(prompt_phone), _iptr(ppl),
-                Npp, _iptr(pd), _iptr(fd), tq_cap, MT2_RUN_VOCODER if vocoder else 0, _ptr(mel), tm_cap, _iptr(mel_lens),
-                _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes)), check_range)
-        else:
-            self._guarded(lambda: self.lib.mt2_synthesize_prompt_conditioned_sampled(
-                self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _ptr(prompt_phone), _iptr(ppl),
-                Npp, _iptr(pd), _iptr(fd), tq_cap, MT2_RUN_VOCODER if vocoder else 0, _ptr(mel), tm_cap, _iptr(mel_lens),
-                _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes), C.byref(smp)), check_range)
+        self._guarded(lambda: self.lib.mt2_synthesize_prompt_conditioned_sampled(
+            self.h, _stream(), _ptr(phone), _iptr(pl), Np, _ptr(prompt_mel), _iptr(ml), Tp, B, _ptr(prompt_phone), _iptr(ppl),
+            Npp, _iptr(pd), _iptr(fd), tq_cap, MT2_RUN_VOCODER if vocoder else 0, _ptr(mel), tm_cap, _iptr(mel_lens),
+            _ptr(dur_out), _ptr(codes_out), _ptr(wav), _ptr(pcodes), smp), check_range)
         P = -(-int(ml[0]) // st)
         return mel, mel_lens, {"dur": dur_out, "codes": codes_out, "wav": wav, "prompt_codes": pcodes[:, :P]}
 

@@ -352,6 +352,27 @@ int mt2_op_gemm_tm_pairs(void* stream, const float* X, int ldx, int Rx, int a_mu
                          const float* ln_gamma, const float* ln_beta, float ln_eps, float* stat_out, const float* ln_stat, int ln_nt);
 int mt2_op_layernorm(void* stream, const float* x, int ldx, const float* gamma, const float* beta, const float* R1,
                      int ldr1, const int32_t* valid, float* out, int ldo, int M, int C, float eps, int act);
+/* Test-only entries into the row kernels (csrc/rowops.hip; tests/test_gpu_rowops.py).  Every pointer is device memory.
+ * mt2_op_layernorm_ex: one LayerNorm launch with every field of its parameter block -
+ *   out[m] = mask * (act(LN(x[m]) * gamma[g] + beta[g]) + R1[m % r1_rows] + R2[m]),  g = m / rows_per_group, mask = valid[m % valid_rows]
+ *   (rows_per_group / r1_rows / valid_rows = 0: one gamma / beta, R1 row m, valid[m]; R1, R2, valid, x3h_flag may be NULL);
+ *   out_planes = 1 stores fp16 planes as mt2_op_layernorm's act + 100 does. */
+int mt2_op_layernorm_ex(void* stream, const float* x, int ldx, const float* gamma, const float* beta, int rows_per_group,
+                        const float* R1, int ldr1, int r1_rows, const float* R2, int ldr2, const int32_t* valid, int valid_rows,
+                        float* out, int ldo, int M, int C, float eps, int act, int out_planes, int32_t* x3h_flag);
+/* mt2_op_ln_reduce: the split-K consumer, xout = ((sum_{g < S} parts[g * pstride + m * C ..], g ascending) + bias) + R (bias, R and
+ *   xout may be NULL; xout may alias R), hout = LN(xout) * gamma + beta (fp16 planes when h_planes = 1: M <= 4096 only).  The launcher
+ *   picks one workgroup per row up to M = 4096 and one wave per row beyond. */
+int mt2_op_ln_reduce(void* stream, const float* parts, long long pstride, int S, const float* bias, const float* R, int ldr,
+                     const float* gamma, const float* beta, float* xout, int ldx, float* hout, int ldh, int M, int C, float eps,
+                     int h_planes, int32_t* x3h_flag);
+/* mt2_op_row: one row utility by name (embed_pe, gather_rows, pool_max, sum_groups, avg3, conv_post, fill_reflect, pack_rows,
+ *   unpack_rows, adm_step_input, plm_step_input, adm_predict, adm_finalize, plm_finalize, adm_init_hist, plm_init_hist, check_ids,
+ *   copy_2d, scatter_i64, expand_mask, unpack_wav, argmax_rows, vq_argmin, row_sqnorm, codebook_rows, reflect_pad_blocks, magnitude).
+ *   The arguments are those of launch_<op> (csrc/mt2_kernels.h) in its order, split by kind: pointers -> ptrs, integers -> ints,
+ *   floats -> flts.  An unknown name or a wrong count of any kind is an error (mt2_last_error) and launches nothing. */
+int mt2_op_row(void* stream, const char* op, void* const* ptrs, int nptrs, const long long* ints, int nints, const float* flts,
+               int nflts);
 /* The PLM's sampling draw on A rows of N <= 1024 logits (row stride ld): out[j] (int64, device) = the code of row j under the
  * rule of mt2_sampling with Philox key seeds_dev[j] (uint64, device) and counter positions_dev[j] (int32, device).
  * s->seeds is not read here (may be NULL); the other fields are checked as for the _sampled calls. */

@@ -1,6 +1,8 @@
 // extern "C" surface of libmegatts2_hip (declared in include/megatts2_hip.h).  Included at the end of
 // model_stages.hip so that the stage drivers stay file-local.  Nothing throws across the boundary.
 
+#include <climits>
+
 namespace mt2 {
 extern thread_local std::string g_last_error;
 void finalize_model(mt2_model& m);
@@ -1110,6 +1112,108 @@ int mt2_op_layernorm(void* stream, const float* x, int ldx, const float* gamma, 
     p.out = out; p.ldo = ldo; p.M = M; p.C = C; p.eps = eps; p.act = act >= 100 ? act - 100 : act;
     p.out_planes = act >= 100 ? 1 : 0;        // tests: act + 100 = the output as fp16 planes (LnP::out_planes)
     MT2_HIP(launch_layernorm(p, (hipStream_t)stream));
+    MT2_API_END
+}
+
+// ---- test-only entries into the row kernels (rowops.hip): every field of the parameter block, nothing defaulted
+int mt2_op_layernorm_ex(void* stream, const float* x, int ldx, const float* gamma, const float* beta, int rows_per_group,
+                        const float* R1, int ldr1, int r1_rows, const float* R2, int ldr2, const int32_t* valid, int valid_rows,
+                        float* out, int ldo, int M, int C, float eps, int act, int out_planes, int32_t* x3h_flag) {
+    MT2_API_BEGIN
+    LnP p{};
+    p.x = x; p.ldx = ldx; p.gamma = gamma; p.beta = beta; p.rows_per_group = rows_per_group;
+    p.R1 = R1; p.ldr1 = ldr1; p.r1_rows = r1_rows; p.R2 = R2; p.ldr2 = ldr2; p.valid = valid; p.valid_rows = valid_rows;
+    p.out = out; p.ldo = ldo; p.M = M; p.C = C; p.eps = eps; p.act = act; p.out_planes = out_planes; p.x3h_flag = x3h_flag;
+    MT2_HIP(launch_layernorm(p, (hipStream_t)stream));
+    MT2_API_END
+}
+
+int mt2_op_ln_reduce(void* stream, const float* parts, long long pstride, int S, const float* bias, const float* R, int ldr,
+                     const float* gamma, const float* beta, float* xout, int ldx, float* hout, int ldh, int M, int C, float eps,
+                     int h_planes, int32_t* x3h_flag) {
+    MT2_API_BEGIN
+    LnReduceP p{};
+    p.parts = parts; p.pstride = pstride; p.S = S; p.bias = bias; p.R = R; p.ldr = ldr; p.gamma = gamma; p.beta = beta;
+    p.xout = xout; p.ldx = ldx; p.hout = hout; p.ldh = ldh; p.M = M; p.C = C; p.eps = eps; p.h_planes = h_planes;
+    p.x3h_flag = x3h_flag;
+    MT2_HIP(launch_ln_reduce(p, (hipStream_t)stream));      // the launcher's own choice between its two kernels (M = 4096)
+    MT2_API_END
+}
+
+// an integer argument of mt2_op_row that the launcher takes as int
+static int row_int(long long v) {
+    MT2_REQUIRE(v >= INT_MIN && v <= INT_MAX, "mt2_op_row: integer argument does not fit the launcher's int parameter");
+    return (int)v;
+}
+// One dispatcher for the launch_* row utilities of mt2_kernels.h: `op` is the launcher's name without "launch_"; its arguments arrive
+// in the launcher's order, split by kind - pointers in ptrs, integers in ints, floats in flts.  The counts are checked against the
+// table BEFORE anything is unpacked: a wrong count or an unknown name is an error, never a launch.
+int mt2_op_row(void* stream, const char* op, void* const* ptrs, int nptrs, const long long* ints, int nints, const float* flts,
+               int nflts) {
+    MT2_API_BEGIN
+    // one line per op: its name, how many pointers / integers / floats it takes, and the call that unpacks them
+    struct RowOp { const char* name; int np, ni, nf; hipError_t (*run)(void* const*, const long long*, const float*, hipStream_t); };
+#define ROW_ARGS void* const* ptrs, const long long* ints, const float* flts, hipStream_t s
+#define ROW_PF(i) static_cast<const float*>(ptrs[i])
+#define ROW_PFW(i) static_cast<float*>(ptrs[i])
+#define ROW_PI(i) static_cast<const int*>(ptrs[i])
+#define ROW_PIW(i) static_cast<int*>(ptrs[i])
+#define ROW_PL(i) static_cast<const int64_t*>(ptrs[i])
+#define ROW_PLW(i) static_cast<int64_t*>(ptrs[i])
+#define ROW_PLL(i) static_cast<const long long*>(ptrs[i])
+#define ROW_INT(i) row_int(ints[i])
+#define ROW_LONG(i) (ints[i])
+    static const RowOp kOps[] = {
+        {"embed_pe", 6, 4, 0, [](ROW_ARGS) { return launch_embed_pe(ROW_PF(0), ROW_INT(0), ROW_PL(1), ROW_PI(2), ROW_PI(3), ROW_PF(4), ROW_PFW(5), ROW_INT(1), ROW_INT(2), ROW_INT(3), s); }},
+        {"gather_rows", 3, 4, 0, [](ROW_ARGS) { return launch_gather_rows(ROW_PF(0), ROW_INT(0), ROW_PI(1), ROW_PFW(2), ROW_INT(1), ROW_INT(2), ROW_INT(3), s); }},
+        {"pool_max", 4, 4, 0, [](ROW_ARGS) { return launch_pool_max(ROW_PF(0), ROW_INT(0), ROW_PI(1), ROW_PI(2), ROW_PFW(3), ROW_INT(1), ROW_INT(2), ROW_INT(3), s); }},
+        {"sum_groups", 2, 6, 0, [](ROW_ARGS) { return launch_sum_groups(ROW_PF(0), ROW_LONG(0), ROW_INT(1), ROW_INT(2), ROW_PFW(1), ROW_INT(3), ROW_INT(4), ROW_INT(5), s); }},
+        {"avg3", 4, 1, 1, [](ROW_ARGS) { return launch_avg3(ROW_PF(0), ROW_PF(1), ROW_PF(2), flts[0], ROW_PFW(3), ROW_LONG(0), s); }},
+        {"conv_post", 7, 3, 2, [](ROW_ARGS) { return launch_conv_post(ROW_PF(0), ROW_PF(1), ROW_PF(2), flts[0], ROW_LONG(0), ROW_INT(1), ROW_INT(2), ROW_PF(3), ROW_PF(4), flts[1], ROW_PI(5), ROW_PFW(6), s); }},
+        {"fill_reflect", 3, 5, 0, [](ROW_ARGS) { return launch_fill_reflect(ROW_PFW(0), ROW_INT(0), ROW_INT(1), ROW_PI(1), ROW_PI(2), ROW_INT(2), ROW_LONG(3), ROW_INT(4), s); }},
+        {"pack_rows", 3, 5, 0, [](ROW_ARGS) { return launch_pack_rows(ROW_PF(0), ROW_INT(0), ROW_INT(1), ROW_INT(2), ROW_PI(1), ROW_PFW(2), ROW_INT(3), ROW_INT(4), s); }},
+        {"unpack_rows", 3, 5, 0, [](ROW_ARGS) { return launch_unpack_rows(ROW_PF(0), ROW_INT(0), ROW_INT(1), ROW_INT(2), ROW_INT(3), ROW_PI(1), ROW_PFW(2), ROW_INT(4), s); }},
+        {"adm_step_input", 6, 6, 0, [](ROW_ARGS) { return launch_adm_step_input(ROW_PF(0), ROW_INT(0), ROW_PI(1), ROW_PF(2), ROW_PF(3), ROW_INT(1), ROW_PF(4), ROW_PFW(5), ROW_INT(2), ROW_INT(3), ROW_INT(4), ROW_INT(5), s); }},
+        {"plm_step_input", 6, 7, 0, [](ROW_ARGS) { return launch_plm_step_input(ROW_PF(0), ROW_INT(0), ROW_PI(1), ROW_PF(2), ROW_PL(3), ROW_INT(1), ROW_PF(4), ROW_PFW(5), ROW_INT(2), ROW_INT(3), ROW_INT(4), ROW_INT(5), ROW_INT(6), s); }},
+        {"adm_predict", 3, 5, 0, [](ROW_ARGS) { return launch_adm_predict(ROW_PF(0), ROW_INT(0), ROW_PF(1), ROW_PFW(2), ROW_INT(1), ROW_INT(2), ROW_INT(3), ROW_INT(4), s); }},
+        {"adm_finalize", 5, 4, 0, [](ROW_ARGS) { return launch_adm_finalize(ROW_PF(0), ROW_INT(0), ROW_PI(1), ROW_PI(2), static_cast<int32_t*>(ptrs[3]), ROW_PFW(4), ROW_INT(1), ROW_INT(2), ROW_INT(3), s); }},
+        {"plm_finalize", 4, 5, 0, [](ROW_ARGS) { return launch_plm_finalize(ROW_PL(0), ROW_INT(0), ROW_PI(1), ROW_PI(2), ROW_PLW(3), ROW_INT(1), ROW_INT(2), ROW_INT(3), ROW_INT(4), s); }},
+        {"adm_init_hist", 3, 3, 0, [](ROW_ARGS) { return launch_adm_init_hist(ROW_PFW(0), ROW_INT(0), ROW_PF(1), ROW_INT(1), ROW_PI(2), ROW_INT(2), s); }},
+        {"plm_init_hist", 3, 5, 0, [](ROW_ARGS) { return launch_plm_init_hist(ROW_PLW(0), ROW_INT(0), (int64_t)ROW_LONG(1), ROW_PL(1), ROW_INT(2), ROW_INT(3), ROW_PI(2), ROW_INT(4), s); }},
+        {"check_ids", 3, 3, 0, [](ROW_ARGS) { return launch_check_ids(ROW_PL(0), ROW_PI(1), ROW_INT(0), ROW_LONG(1), ROW_PIW(2), ROW_INT(2), s); }},
+        {"copy_2d", 2, 4, 0, [](ROW_ARGS) { return launch_copy_2d(ROW_PF(0), ROW_LONG(0), ROW_PFW(1), ROW_LONG(1), ROW_LONG(2), ROW_INT(3), s); }},
+        {"scatter_i64", 3, 1, 0, [](ROW_ARGS) { return launch_scatter_i64(ROW_PL(0), ROW_PI(1), ROW_PLW(2), ROW_INT(0), s); }},
+        {"expand_mask", 2, 2, 0, [](ROW_ARGS) { return launch_expand_mask(ROW_PI(0), ROW_INT(0), ROW_PIW(1), ROW_LONG(1), s); }},
+        {"unpack_wav", 4, 3, 0, [](ROW_ARGS) { return launch_unpack_wav(ROW_PF(0), ROW_PLL(1), ROW_PLL(2), ROW_PFW(3), ROW_LONG(0), ROW_LONG(1), ROW_INT(2), s); }},
+        {"argmax_rows", 2, 5, 0, [](ROW_ARGS) { return launch_argmax_rows(ROW_PF(0), ROW_INT(0), ROW_INT(1), ROW_PLW(1), ROW_INT(2), ROW_INT(3), ROW_INT(4), s); }},
+        {"vq_argmin", 5, 5, 0, [](ROW_ARGS) { return launch_vq_argmin(ROW_PF(0), ROW_INT(0), ROW_INT(1), ROW_PF(1), ROW_INT(2), ROW_PF(2), ROW_INT(3), ROW_PI(3), ROW_PLW(4), ROW_INT(4), s); }},
+        {"row_sqnorm", 2, 2, 0, [](ROW_ARGS) { return launch_row_sqnorm(ROW_PF(0), ROW_INT(0), ROW_PFW(1), ROW_INT(1), s); }},
+        {"codebook_rows", 4, 4, 0, [](ROW_ARGS) { return launch_codebook_rows(ROW_PF(0), ROW_PL(1), ROW_PI(2), ROW_PFW(3), ROW_INT(0), ROW_INT(1), ROW_INT(2), ROW_INT(3), s); }},
+        {"reflect_pad_blocks", 5, 4, 0, [](ROW_ARGS) { return launch_reflect_pad_blocks(ROW_PF(0), ROW_LONG(0), ROW_PI(1), ROW_PI(2), ROW_PI(3), ROW_INT(1), ROW_INT(2), ROW_PFW(4), ROW_INT(3), s); }},
+        {"magnitude", 2, 4, 0, [](ROW_ARGS) { return launch_magnitude(ROW_PF(0), ROW_INT(0), ROW_INT(1), ROW_PFW(1), ROW_INT(2), ROW_INT(3), s); }},
+    };
+#undef ROW_ARGS
+#undef ROW_PF
+#undef ROW_PFW
+#undef ROW_PI
+#undef ROW_PIW
+#undef ROW_PL
+#undef ROW_PLW
+#undef ROW_PLL
+#undef ROW_INT
+#undef ROW_LONG
+    MT2_REQUIRE(op != nullptr, "mt2_op_row: null op name");
+    const std::string name(op);
+    int id = -1;
+    for (size_t i = 0; i < sizeof(kOps) / sizeof(kOps[0]); ++i)
+        if (name == kOps[i].name) id = (int)i;
+    MT2_REQUIRE(id >= 0, "mt2_op_row: unknown op '" + name + "'");
+    MT2_REQUIRE(nptrs == kOps[id].np && nints == kOps[id].ni && nflts == kOps[id].nf,
+                "mt2_op_row: wrong argument count for '" + name + "' (wants " + std::to_string(kOps[id].np) + " pointers, " +
+                    std::to_string(kOps[id].ni) + " integers, " + std::to_string(kOps[id].nf) + " floats)");
+    MT2_REQUIRE((nptrs == 0 || ptrs) && (nints == 0 || ints) && (nflts == 0 || flts), "mt2_op_row: null argument array");
+    const hipError_t e = kOps[id].run(ptrs, ints, flts, (hipStream_t)stream);
+    if (e != hipSuccess) throw Error("mt2_op_row(" + name + "): " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
     MT2_API_END
 }
 

@@ -296,7 +296,8 @@ hipError_t launch_argmax_rows(const float* x, int ldx, int N, int64_t* out, int 
                               hipStream_t s);
 // seeded temperature / top-k / top-p draw (sampling.hip; N <= 1024): out[j*ostride + ooff] = the code of row j under the rule
 // of sampling.hip with Philox key = seeds[2b], seeds[2b+1] (lo, hi) of utterance b = slot ? slot[j] : j and counter
-// = pos ? pos[j] : pos0.  top_k = 1 is launch_argmax_rows.  hipErrorInvalidValue for parameters outside the rule.
+// = pos ? pos[j] : pos0.  top_k = 1 is launch_argmax_rows on rows without NaN (the rule orders finite and infinite logits only; a NaN
+// row is launch_argmax_rows' alone to define).  hipErrorInvalidValue for parameters outside the rule.
 hipError_t launch_sample_rows(const float* x, int ldx, int N, int64_t* out, int ostride, int ooff, int A, float tau, int top_k,
                               float top_p, const uint32_t* seeds, const int* slot, const int* pos, int pos0, hipStream_t s);
 // EuclideanCodebook.quantize (core_vq.py:175-183) given xe = x @ E^T:

@@ -98,6 +98,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnP p) {
 // xout = x_new (the residual stream), hout = LayerNorm(x_new).  The GEMM that produced `parts` ran as S
 // independent K slices (GemmP groups) and skipped its epilogue; the kernel boundary is the only
 // synchronisation, the reduction is deterministic, and no launch is added: this IS the layer's LayerNorm.
+// (This wave-per-row form serves M > 4096 only: choose_split never splits K for that many rows, so no stage reaches it -
+// tests/test_gpu_rowops.py does, through mt2_op_ln_reduce, on both sides of the launcher's switch.)
 __global__ __launch_bounds__(256) void ln_reduce_kernel(LnReduceP p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = blockIdx.x * 4 + wave;
@@ -754,9 +756,12 @@ hipError_t launch_unpack_wav(const float* src, const long long* start, const lon
     return hipGetLastError();
 }
 
-// torch.argmax semantics: first index of the maximum.  One wave per row, (value, index) reduction.
+// torch.argmax semantics: first index of the maximum, and NaN is the greatest value (a row with NaNs answers the index of its
+// first NaN, as torch.argmax / Tensor.max(-1).indices do - never the untouched 0x7fffffff of a row where no ordered comparison
+// holds).  Rows without NaN take the same decisions as the plain ordered rule.  One wave per row, (value, index) reduction.
 __device__ __forceinline__ void argmax_combine(float& bv, int& bi, float ov, int oi) {
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    const bool on = ov != ov, bn = bv != bv;
+    if (on ? (!bn || oi < bi) : (!bn && (ov > bv || (ov == bv && oi < bi)))) { bv = ov; bi = oi; }
 }
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* x, int ldx, int N, int64_t* out,
                                                           int ostride, int ooff, int A) {

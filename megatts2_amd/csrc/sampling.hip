@@ -10,7 +10,8 @@
 //               R when rounding leaves none).
 // u = (x0 >> 8) * 2^-24 with x0 the first word of Philox4x32-10 (key = the utterance's 64-bit seed, counter = (target
 // position, 0, 0, 0)): a code depends on (seed, position, logits) only - not on the batch, the slot, the stream groups or
-// a repeated call.  top_k = 1 (or a tiny top_p) is exactly the argmax with lowest-index ties.
+// a repeated call.  top_k = 1 (or a tiny top_p) is exactly the argmax with lowest-index ties on rows without NaN; the rule does not
+// order NaN logits (argmax_rows_kernel's NaN-is-greatest rule is the greedy path's alone).
 //
 // One wave64 per row, four rows per 256-thread block (as argmax_rows_kernel); lane l owns logits [16 l, 16 l + 16), so an
 // index-order prefix sum is a per-lane partial sum plus a wave scan.  The top-k cut is a bisection over order-preserving

@@ -841,6 +841,68 @@ def op_layernorm(x, gamma, beta, R1=None, valid=None, eps=1e-5, act=ACT_NONE):
     return out
 
 
+# ---- test-only entries into the row kernels (csrc/rowops.hip).  The caller owns every buffer, outputs included (a test pre-fills
+# them with a sentinel), and passes the launcher's arguments in the launcher's order (csrc/mt2_kernels.h).
+
+def op_layernorm_ex(x, ldx, gamma, beta, rows_per_group, R1, ldr1, r1_rows, R2, ldr2, valid, valid_rows, out, ldo, M, Cc, eps=1e-5,
+                    act=ACT_NONE, out_planes=0, x3h_flag=None):
+    """mt2_op_layernorm_ex: one LayerNorm launch with every field of LnP."""
+    _check(load_library().mt2_op_layernorm_ex(_stream(), _ptr(x), ldx, _ptr(gamma), _ptr(beta), rows_per_group, _ptr(R1), ldr1,
+                                              r1_rows, _ptr(R2), ldr2, _ptr(valid), valid_rows, _ptr(out), ldo, M, Cc,
+                                              C.c_float(eps), act, out_planes, _ptr(x3h_flag)))
+
+
+def op_ln_reduce(parts, pstride, S, bias, R, ldr, gamma, beta, xout, ldx, hout, ldh, M, Cc, eps=1e-5, h_planes=0, x3h_flag=None):
+    """mt2_op_ln_reduce: the split-K consumer with every field of LnReduceP, through the launcher's own kernel choice."""
+    _check(load_library().mt2_op_ln_reduce(_stream(), _ptr(parts), C.c_longlong(pstride), S, _ptr(bias), _ptr(R), ldr, _ptr(gamma),
+                                           _ptr(beta), _ptr(xout), ldx, _ptr(hout), ldh, M, Cc, C.c_float(eps), h_planes,
+                                           _ptr(x3h_flag)))
+
+
+def op_row(op, *args, stream=None):
+    """mt2_op_row: launch_<op> with `args` in the launcher's order.  Marshalling is by kind: a tensor (or None = NULL) is a pointer,
+    an int an integer, a float a float."""
+    ptrs, ints, flts = [], [], []
+    for a in args:
+        if isinstance(a, float):
+            flts.append(a)
+        elif isinstance(a, (int, np.integer)) and not isinstance(a, bool):
+            ints.append(int(a))
+        else:
+            ptrs.append(a.data_ptr() if a is not None else 0)
+    _check(load_library().mt2_op_row(stream if stream is not None else _stream(), op.encode(), (C.c_void_p * len(ptrs))(*ptrs), len(ptrs),
+                                     (C.c_longlong * len(ints))(*ints), len(ints), (C.c_float * len(flts))(*flts), len(flts)))
+
+
+def op_embed_pe(table, Cc, ids, idmap, pos, pe, out, ldo, R, vocab): op_row("embed_pe", table, Cc, ids, idmap, pos, pe, out, ldo, R, vocab)
+def op_gather_rows(src, lds_, map_, out, ldo, Cc, R): op_row("gather_rows", src, lds_, map_, out, ldo, Cc, R)
+def op_pool_max(src, lds_, first, cnt, out, ldo, Cc, R): op_row("pool_max", src, lds_, first, cnt, out, ldo, Cc, R)
+def op_sum_groups(x, strideG, groups, ld, out, ldo, Cc, R): op_row("sum_groups", x, strideG, groups, ld, out, ldo, Cc, R)
+def op_avg3(a, b, d, scale, out, n): op_row("avg3", a, b, d, float(scale), out, n)
+def op_conv_post(x0, x1, x2, scale, R, ch, k, w, bias, slope, valid, out): op_row("conv_post", x0, x1, x2, float(scale), R, ch, k, w, bias, float(slope), valid, out)
+def op_fill_reflect(x, ld, Cc, start, len_, B, scale, G): op_row("fill_reflect", x, ld, Cc, start, len_, B, scale, G)
+def op_pack_rows(src, Cc, Tmax, cmajor, rowmap, dst, ldd, R): op_row("pack_rows", src, Cc, Tmax, cmajor, rowmap, dst, ldd, R)
+def op_unpack_rows(src, lds_, Cc, Tmax, cmajor, rowmap, dst, R): op_row("unpack_rows", src, lds_, Cc, Tmax, cmajor, rowmap, dst, R)
+def op_adm_step_input(tc_emb, ld_tc, tc_row, w_dt, p, pstride, pe, x, Dc, De, n, A): op_row("adm_step_input", tc_emb, ld_tc, tc_row, w_dt, p, pstride, pe, x, Dc, De, n, A)
+def op_plm_step_input(cond, ld_c, cond_row, emb, codes, cstride, pe, x, Dc, De, n, A, emb_rows): op_row("plm_step_input", cond, ld_c, cond_row, emb, codes, cstride, pe, x, Dc, De, n, A, emb_rows)
+def op_adm_predict(x, D, w, p, pstride, n, xn, A): op_row("adm_predict", x, D, w, p, pstride, n, xn, A)
+def op_adm_finalize(p, pstride, lens, slot_b, dur, flt, dstride, A, nmax): op_row("adm_finalize", p, pstride, lens, slot_b, dur, flt, dstride, A, nmax)
+def op_plm_finalize(codes, cstride, lens, slot_b, out, ostride, A, nmax, skip): op_row("plm_finalize", codes, cstride, lens, slot_b, out, ostride, A, nmax, skip)
+def op_adm_init_hist(p, pstride, prefix, P, slot_b, A): op_row("adm_init_hist", p, pstride, prefix, P, slot_b, A)
+def op_plm_init_hist(codes, cstride, bos, prefix, P, pstride, slot_b, A): op_row("plm_init_hist", codes, cstride, bos, prefix, P, pstride, slot_b, A)
+def op_check_ids(ids, map_, R, hi, flag, bit): op_row("check_ids", ids, map_, R, hi, flag, bit)
+def op_copy_2d(src, spitch, dst, dpitch, width, rows): op_row("copy_2d", src, spitch, dst, dpitch, width, rows)
+def op_scatter_i64(src, map_, out, R): op_row("scatter_i64", src, map_, out, R)
+def op_expand_mask(in_, factor, out, n): op_row("expand_mask", in_, factor, out, n)
+def op_unpack_wav(src, start, len_, out, out_stride, max_len, B): op_row("unpack_wav", src, start, len_, out, out_stride, max_len, B)
+def op_argmax_rows(x, ldx, N, out, ostride, ooff, A): op_row("argmax_rows", x, ldx, N, out, ostride, ooff, A)
+def op_vq_argmin(x, ldx, D, xe, ldxe, ee, N, valid, idx, M): op_row("vq_argmin", x, ldx, D, xe, ldxe, ee, N, valid, idx, M)
+def op_row_sqnorm(E, D, ee, N): op_row("row_sqnorm", E, D, ee, N)
+def op_codebook_rows(E, codes, codemap, out, ldo, Dq, R, bins): op_row("codebook_rows", E, codes, codemap, out, ldo, Dq, R, bins)
+def op_reflect_pad_blocks(wav, wstride, blk_b, blk_t, len_, hop, pad, out, R): op_row("reflect_pad_blocks", wav, wstride, blk_b, blk_t, len_, hop, pad, out, R)
+def op_magnitude(spec, lds_, F, out, ldo, M): op_row("magnitude", spec, lds_, F, out, ldo, M)
+
+
 def op_attention(Q, K, V, q_start, q_len, kv_start, kv_len, H, D, scale, lds_min_qlen=-1, lds_waves=0, out=None, x6_min_qlen=-1):
     """mt2_op_attention_tuned: one attention launch with the kernel choice exposed.  lds_waves: 0 / 4 / 8 query tiles per workgroup of
     the LDS-tiled and matrix-pipe kernels; + 32 = the register kernel instead of the head-dim-split one; + 64 = the output rows as fp16

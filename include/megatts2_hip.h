@@ -412,6 +412,14 @@ int mt2_gemm_trace_end(mt2_model* m, int cap, const char** names, int64_t* launc
 int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top);
 int mt2_gemm_config_count(void);
 const char* mt2_gemm_config_name(int idx);
+/* test hook, no device needed: what the GEMM front door (gemm_dispatch.hip) would do with the dense launch M x N x K (taps, dilation,
+ * groups, prologue pro_act) - err: the hipError_t it would return before launching (0: it launches), cfg: the configuration index (-1:
+ * none chosen), variant: the kernel variant of that tile, lds: dynamic LDS bytes, planes: bit 0 the launch could take its A operand as
+ * fp16 planes, bit 1 it could write C as planes.  operands: which optional operands exist - 1 W3, 2 Wh + wh_inv, 4 Wtm, 8 stat_out,
+ * 16 ln_stat, 32 R, 64 rowbase, 128 a_planes, 256 c_planes; all on 128 bytes except those named in `misaligned` (same bits; 512 X,
+ * 1024 C).  force_cfg / x3h: the options of the same names.  Returns 0. */
+int mt2_gemm_route(int M, int N, int K, int taps, int dil, int groups, int pro_act, int operands, int misaligned, int force_cfg,
+                   int x3h, int* err, int* cfg, int* variant, long long* lds, int* planes);
 /* time `iters` back-to-back launches of one GEMM / conv (taps, dilation) with HIP events on `stream`, cycling
  * through `w_copies` copies of the weight matrix (> 1: weights are not L2-resident from the previous launch);
  * flags bit0: leaky-ReLU prologue, bit1: bias + residual + row-mask epilogue, bit2: clock probe - one wave of the

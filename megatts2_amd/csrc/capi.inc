@@ -951,6 +951,43 @@ int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top) {
 int mt2_gemm_config_count(void) { return gemm_num_configs(); }
 const char* mt2_gemm_config_name(int idx) { return gemm_config_name(idx); }
 
+// What launch_gemm would do with a launch, without making it (gemm_route; no device needed - the routing tests).  The launch is the
+// dense one of mt2_bench_gemm: Cin = K / taps, ldx = Cin, ldw = K, ldc = ldr = N, Rx = M + taps * dil, groups laid out back to back.
+// `operands`: which optional operands exist (dummy pointers, never dereferenced) - 1 W3, 2 Wh + wh_inv, 4 Wtm, 8 stat_out, 16 ln_stat
+// (with ln_g / ln_b and pairs of 64 columns), 32 R, 64 rowbase, 128 a_planes, 256 c_planes.  Every pointer sits on 128 bytes except
+// those whose bit is set in `misaligned` (same bits; 512: X, 1024: C), which sit 4 bytes further.  variant: GemmVariant; planes: bit 0
+// gemm_takes_planes, bit 1 gemm_writes_planes for the same launch.
+int mt2_gemm_route(int M, int N, int K, int taps, int dil, int groups, int pro_act, int operands, int misaligned, int force_cfg,
+                   int x3h, int* err, int* cfg, int* variant, long long* lds, int* planes) {
+    alignas(128) static char dummy[12 * 128];
+    const auto ptr = [&](int slot, int bit) { return (void*)(dummy + 128 * slot + ((misaligned & bit) ? 4 : 0)); };
+    GemmP p{};
+    const int Cin = taps > 0 ? K / taps : K;
+    p.X = (const float*)ptr(0, 512); p.ldx = Cin; p.Rx = M + taps * dil; p.a_mul = 1; p.taps = taps; p.dil = dil; p.Cin = Cin;
+    p.W = (const float*)ptr(1, 0); p.ldw = K; p.C = (float*)ptr(2, 1024); p.ldc = N; p.M = M; p.N = N; p.K = K; p.groups = groups;
+    p.strideX = (long long)p.Rx * Cin; p.strideW = (long long)N * K; p.strideC = (long long)M * N; p.strideB = N; p.strideR = (long long)M * N;
+    p.pro_act = pro_act; p.out_scale = 1.0f;
+    if (operands & 1) p.W3 = ptr(3, 1);
+    if (operands & 2) { p.Wh = ptr(4, 2); p.wh_inv = (const float*)ptr(5, 0); }
+    if (operands & 4) { p.Wtm = (const float*)ptr(6, 4); p.tm_kb = K / 64; }
+    if (operands & 8) p.stat_out = (float*)ptr(7, 8);
+    if (operands & 16) { p.ln_stat = (const float*)ptr(8, 16); p.ln_g = p.ln_b = (const float*)ptr(9, 0); p.ln_w = 64; p.ln_nt = K / 64; }
+    if (operands & 32) { p.R = (const float*)ptr(10, 32); p.ldr = N; }
+    if (operands & 64) p.rowbase = (const int*)ptr(11, 64);
+    p.a_planes = (operands & 128) ? 1 : 0;
+    p.c_planes = (operands & 256) ? 1 : 0;
+    EngineOpts o;
+    o.force_cfg = force_cfg;
+    o.x3h = x3h;
+    const GemmRoute r = gemm_route(p, o);
+    if (err) *err = (int)r.err;
+    if (cfg) *cfg = r.cfg;
+    if (variant) *variant = r.variant;
+    if (lds) *lds = (long long)r.lds;
+    if (planes) *planes = (gemm_takes_planes(p, o) ? 1 : 0) | (gemm_writes_planes(p, o) ? 2 : 0);
+    return 0;
+}
+
 int mt2_op_gemm(void* stream, const float* X, int ldx, int Rx, const int32_t* rowbase, int a_mul, int shift0,
                 int taps, int dil, int Cin, const float* W, int ldw, const float* bias, const float* R, int ldr,
                 const int32_t* valid, float* C, int ldc, int M, int N, int pro_act, float pro_slope, int epi_act,

@@ -1,8 +1,8 @@
-// Device-side pieces shared by the GEMM translation units (gemm_f32.hip: the f32-MFMA and bf16-pipe "x6" kernels and the tile
-// table; gemm_x3h.hip: the fp16-pipe "x3h" kernels): activation helpers, the fused epilogues (plain, prefetched, 16-byte stores,
+// Device-side pieces shared by the GEMM kernel units (gemm_f32.hip: the f32-MFMA and bf16-pipe "x6" kernels; gemm_x3h.hip: the
+// fp16-pipe "x3h" kernels; each with the table rows of its tiles, gemm_tiles.h): activation helpers, the fused epilogues (plain, prefetched, 16-byte stores,
 // row-statistics pairs), the LayerNorm pair merge, LDS read / counted-wait / loader-priority primitives.
 #pragma once
-#include "mt2_kernels.h"
+#include "gemm_tiles.h"
 #include "planes_store.h"
 #include <type_traits>
 #include <utility>
@@ -396,11 +396,10 @@ __device__ __forceinline__ void epilogue_t4(const GemmP& p, f32x16 (&acc)[TM][TN
     }
 }
 
-constexpr int BK = 32;   // K chunk (floats)
-constexpr int PRO_LN = 3;   // prologue kind: LayerNorm of the A rows (value of GemmP::pro_act; the <= 64-row weight-streaming kernel only)
-constexpr int PRO_APL = 3;  // variant index of the x3h tiles whose A operand ARRIVES as fp16 planes (GemmP::a_planes; no prologue)
-constexpr int PRO_LNA = 4;  // LayerNorm of the A rows, ALGEBRAIC form: statistics in the prologue, correction in the epilogue
-constexpr int PRO_LNX = 5;  // ... ALGEBRAIC form on PAIR statistics written by the producer GEMM's epilogue (GemmP::ln_stat): no pass over K
+// template argument of the x3h kernels whose A operand ARRIVES as fp16 planes (GemmP::a_planes; no prologue).  A kernel-side value,
+// beside the Act / PRO_LNX arguments of the other instantiations: never a value of GemmP::pro_act, never a slot of TileCfg::fn
+// (that is V_APLANES)
+constexpr int PRO_APL = 3;
 
 __device__ __forceinline__ f32x4 lds_read_b128(unsigned byte_addr) {
     f32x4 v;

@@ -14,7 +14,7 @@
 // Two kernels share the epilogue and the tile map:
 //   gemm_f32_kernel      (v1, tile configurations 0-7) stages operands through registers into a padded,
 //                        double-buffered LDS tile.  Kept as the simple reference implementation for A/B
-//                        runs and kernel tests; never chosen by choose_cfg.
+//                        runs and kernel tests; never chosen by choose_cfg (gemm_dispatch.hip).
 //   gemm_f32_dma_kernel  (v2, configurations 8+, what the model runs) moves operands global -> LDS with
 //                        LDS-DMA into a swizzled ring, optionally splits K over wave groups of the
 //                        workgroup, and prefetches the epilogue operands (description at the kernel).
@@ -1429,574 +1429,81 @@ __global__ __launch_bounds__((WGM * WGN * KS + NL) * 64) void gemm_x6_ks_kernel(
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------------
-// host side: tile-configuration choice and launch
+// host side: the table rows of this unit's tiles (gemm_tiles.h; gemm_dispatch.hip places them and routes launches)
 
-struct TileCfg {
-    int bm, bn, threads;
-    size_t lds;               // window configurations: the ring part only (the window depends on taps and dilation)
-    const char* name;
-    void (*fn[6])(GemmP);     // indexed by the prologue: none / relu / leaky relu / LayerNorm / algebraic LayerNorm / none + pair statistics
-                              // (PRO_LNX: pair-fed algebraic LayerNorm and the row-statistics epilogue) - nullptr: no variant
-    int win_qs = 0;           // > 0: window convolution for Cin = Cout = 32 * win_qs
-    bool x6 = false;          // window convolution on the bf16 pipe (3-way split, 6 products): needs GemmP::W3
-    int x6_ks = 0;            // > 0: x6 K-split tile (gemm_x6_ks_kernel): linear layers with K a multiple of 32 * x6_ks
-    int stat_w = 0;           // > 0: the tile has the row-statistics epilogue (GemmP::stat_out: one pair per stat_w columns) and
-                              // the pair-fed algebraic-LayerNorm form (pro_act == PRO_LNX)
-    int x3h = -1;             // >= 0: the tile runs on the fp16 pipe (3 products, gemm_x3h.hip): needs GemmP::Wh / wh_inv; the kernels
-                              // come from x3h_kernel(x3h, variant), fn[] only says which variants exist
-};
-
-// A configuration that was measured, documented (profiles/) and is no longer built: the index keeps its
-// meaning in the profiles of earlier rounds, launch_gemm answers hipErrorNotSupported
-#define MT2_RETIRED(NAME_) { 0, 0, 0, 0, "retired:" NAME_, { nullptr, nullptr, nullptr, nullptr, nullptr } }
-#define MT2_CFG(BM_, BN_, WM_, WN_)                                                                    \
-    { BM_, BN_, WM_* WN_ * 64, 2ull * (BM_ + BN_) * LS * sizeof(float), #BM_ "x" #BN_ "_" #WM_ "x" #WN_, \
-      { gemm_f32_kernel<BM_, BN_, WM_, WN_>, gemm_f32_kernel<BM_, BN_, WM_, WN_>,                        \
-        gemm_f32_kernel<BM_, BN_, WM_, WN_>, nullptr, nullptr } }
-#define MT2_DMA(BM_, BN_, WM_, WN_, NST_)                                              \
-    { BM_, BN_, WM_* WN_ * 64, (size_t)NST_ * (BM_ + BN_) * BK * sizeof(float),          \
-      "dma" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_s" #NST_,                                   \
-      { gemm_f32_dma_kernel<BM_, BN_, WM_, WN_, 1, NST_, ACT_NONE>, gemm_f32_dma_kernel<BM_, BN_, WM_, WN_, 1, NST_, ACT_RELU>, \
-        gemm_f32_dma_kernel<BM_, BN_, WM_, WN_, 1, NST_, ACT_LRELU>, nullptr, nullptr } }
-#define MT2_DMAK(BM_, BN_, WM_, WN_, KS_, NST_)                                                        \
-    { BM_, BN_, WM_* WN_ * KS_ * 64, (size_t)KS_ * NST_ * (BM_ + BN_) * BK * sizeof(float),              \
-      "dma" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_k" #KS_ "_s" #NST_,                                        \
-      { gemm_f32_dma_kernel<BM_, BN_, WM_, WN_, KS_, NST_, ACT_NONE>, gemm_f32_dma_kernel<BM_, BN_, WM_, WN_, KS_, NST_, ACT_RELU>, \
-        gemm_f32_dma_kernel<BM_, BN_, WM_, WN_, KS_, NST_, ACT_LRELU>, nullptr, nullptr } }
-// 2-deep ring, one 32x32 tile per wave
-#define MT2_DMAL(BM_, BN_, WM_, WN_, KS_)                                                               \
-    { BM_, BN_, WM_* WN_ * KS_ * 64, (size_t)KS_ * 2 * (BM_ + BN_) * BK * sizeof(float),                 \
-      "dma" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_k" #KS_ "_s2",                                             \
-      { gemm_f32_dma_kernel<BM_, BN_, WM_, WN_, KS_, 2, ACT_NONE>, gemm_f32_dma_kernel<BM_, BN_, WM_, WN_, KS_, 2, ACT_RELU>, \
-        gemm_f32_dma_kernel<BM_, BN_, WM_, WN_, KS_, 2, ACT_LRELU>, nullptr, nullptr } }
-
-#define MT2_WIN(QS_, BM_, BN_, WM_, WN_, NST_)                                                               \
-    { BM_, BN_, WM_* WN_ * 64, (size_t)NST_ * (((BN_ / 8 + WM_ * WN_ - 1) / (WM_ * WN_)) * WM_ * WN_ * 256) * sizeof(float), \
-      "win" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_s" #NST_,                                                       \
-      { conv_win_f32_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_NONE>, conv_win_f32_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_RELU>, \
-        conv_win_f32_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_LRELU>, nullptr, nullptr }, QS_ }
-
-#define MT2_GX6L(BM_, BN_, WM_, WN_, NL_, NST_)                                                                \
-    { BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * ((size_t)BM_ * BK * 4 + (size_t)(3 * BN_ / 16) * 1024),       \
-      "x6ldr" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_,                                                  \
-      { gemm_x6_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_NONE>, gemm_x6_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_RELU>, \
-        gemm_x6_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_LRELU>, nullptr, nullptr }, 0, true }
+#define MT2_ACTS(K_, ...) { K_<__VA_ARGS__, ACT_NONE>, K_<__VA_ARGS__, ACT_RELU>, K_<__VA_ARGS__, ACT_LRELU> }
+#define MT2_ACTS_LNX(K_, ...) { K_<__VA_ARGS__, ACT_NONE>, K_<__VA_ARGS__, ACT_RELU>, K_<__VA_ARGS__, ACT_LRELU>, nullptr, K_<__VA_ARGS__, PRO_LNX> }
+// v1: register-staged double buffer
+#define MT2_CFG(IDX_, BM_, BN_, WM_, WN_)                                                                     \
+    { IDX_, BM_, BN_, WM_* WN_ * 64, 2ull * (BM_ + BN_) * LS * sizeof(float), #BM_ "x" #BN_ "_" #WM_ "x" #WN_, \
+      { gemm_f32_kernel<BM_, BN_, WM_, WN_>, gemm_f32_kernel<BM_, BN_, WM_, WN_>, gemm_f32_kernel<BM_, BN_, WM_, WN_> } }
+// v2: LDS-DMA ring
+#define MT2_DMA(IDX_, BM_, BN_, WM_, WN_, NST_)                                              \
+    { IDX_, BM_, BN_, WM_* WN_ * 64, (size_t)NST_ * (BM_ + BN_) * BK * sizeof(float),          \
+      "dma" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_s" #NST_, MT2_ACTS(gemm_f32_dma_kernel, BM_, BN_, WM_, WN_, 1, NST_) }
+// ... + in-workgroup K split: 2-deep ring, one 32x32 tile per wave
+#define MT2_DMAL(IDX_, BM_, BN_, WM_, WN_, KS_)                                                          \
+    { IDX_, BM_, BN_, WM_* WN_ * KS_ * 64, (size_t)KS_ * 2 * (BM_ + BN_) * BK * sizeof(float),            \
+      "dma" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_k" #KS_ "_s2", MT2_ACTS(gemm_f32_dma_kernel, BM_, BN_, WM_, WN_, KS_, 2) }
+#define MT2_WIN(IDX_, QS_, BM_, BN_, WM_, WN_, NST_)                                                          \
+    { IDX_, BM_, BN_, WM_* WN_ * 64, (size_t)NST_ * (((BN_ / 8 + WM_ * WN_ - 1) / (WM_ * WN_)) * WM_ * WN_ * 256) * sizeof(float), \
+      "win" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_s" #NST_, MT2_ACTS(conv_win_f32_kernel, QS_, BM_, BN_, WM_, WN_, NST_), PIPE_F32, QS_ }
+// x6 loader-wave tiles: stage = BM x 128 B (A, f32) + 3 x BN x 64 B (B planes)
+#define MT2_GX6L(IDX_, BM_, BN_, WM_, WN_, NL_, NST_)                                                          \
+    { IDX_, BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * ((size_t)BM_ * BK * 4 + (size_t)(3 * BN_ / 16) * 1024), \
+      "x6ldr" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_, MT2_ACTS(gemm_x6_ldr_kernel, BM_, BN_, WM_, WN_, NL_, NST_), PIPE_X6 }
 // ... with the PRO_LNX variant (LayerNorm statistics handed from GEMM to GEMM): the production AR tiles only
-#define MT2_GX6L_S(BM_, BN_, WM_, WN_, NL_, NST_)                                                              \
-    { BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * ((size_t)BM_ * BK * 4 + (size_t)(3 * BN_ / 16) * 1024),       \
-      "x6ldr" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_,                                                  \
-      { gemm_x6_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_NONE>, gemm_x6_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_RELU>, \
-        gemm_x6_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_LRELU>, nullptr, nullptr,                               \
-        gemm_x6_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, PRO_LNX> }, 0, true, 0, (BN_) / (WN_) }
-#define MT2_GX6K_S(BM_, BN_, WM_, WN_, KS_, NL_, NST_)                                                         \
-    { BM_, BN_, (WM_* WN_ * KS_ + NL_) * 64, (size_t)KS_ * NST_ * ((size_t)BM_ * BK * 4 + (size_t)(3 * BN_ / 16) * 1024), \
+#define MT2_GX6L_S(IDX_, BM_, BN_, WM_, WN_, NL_, NST_)                                                        \
+    { IDX_, BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * ((size_t)BM_ * BK * 4 + (size_t)(3 * BN_ / 16) * 1024), \
+      "x6ldr" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_, MT2_ACTS_LNX(gemm_x6_ldr_kernel, BM_, BN_, WM_, WN_, NL_, NST_), \
+      PIPE_X6, 0, 0, (BN_) / (WN_) }
+#define MT2_GX6K_S(IDX_, BM_, BN_, WM_, WN_, KS_, NL_, NST_)                                                   \
+    { IDX_, BM_, BN_, (WM_* WN_ * KS_ + NL_) * 64, (size_t)KS_ * NST_ * ((size_t)BM_ * BK * 4 + (size_t)(3 * BN_ / 16) * 1024), \
       "x6ks" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_k" #KS_ "+" #NL_ "_s" #NST_,                                         \
-      { gemm_x6_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_NONE>, gemm_x6_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_RELU>, \
-        gemm_x6_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_LRELU>, nullptr, nullptr,                           \
-        gemm_x6_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_LNX> }, 0, true, KS_, 32 }
-#define MT2_WX6L(QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                         \
-    { BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * (((3 * BN_ / 16 + NL_ - 1) / NL_) * NL_ * 1024),                 \
+      MT2_ACTS_LNX(gemm_x6_ks_kernel, BM_, BN_, WM_, WN_, KS_, NL_, NST_), PIPE_X6, 0, KS_, 32 }
+// x6 window convolutions; ring stage = 3 planes x BN x 64 B
+#define MT2_WX6L(IDX_, QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                   \
+    { IDX_, BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * (((3 * BN_ / 16 + NL_ - 1) / NL_) * NL_ * 1024),           \
       "x6winl" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_,                                           \
       { conv_win_x6_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_NONE, NL_>, conv_win_x6_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_RELU, NL_>, \
-        conv_win_x6_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_LRELU, NL_>, nullptr, nullptr }, QS_, true }
-#define MT2_WX6(QS_, BM_, BN_, WM_, WN_, NST_)                                                               \
-    { BM_, BN_, WM_* WN_ * 64, (size_t)NST_ * (((3 * BN_ / 16 + WM_ * WN_ - 1) / (WM_ * WN_)) * WM_ * WN_ * 1024),   \
-      "x6win" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_s" #NST_,                                                     \
-      { conv_win_x6_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_NONE>, conv_win_x6_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_RELU>, \
-        conv_win_x6_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_LRELU>, nullptr, nullptr }, QS_, true }
+        conv_win_x6_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_LRELU, NL_> }, PIPE_X6, QS_ }
+#define MT2_WX6(IDX_, QS_, BM_, BN_, WM_, WN_, NST_)                                                         \
+    { IDX_, BM_, BN_, WM_* WN_ * 64, (size_t)NST_ * (((3 * BN_ / 16 + WM_ * WN_ - 1) / (WM_ * WN_)) * WM_ * WN_ * 1024),   \
+      "x6win" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_s" #NST_, MT2_ACTS(conv_win_x6_kernel, QS_, BM_, BN_, WM_, WN_, NST_), PIPE_X6, QS_ }
 
-// x3h loader-wave tiles (gemm_x3h.hip): stage = BM x 128 B (A, f32) + 2 x BN x 64 B (fp16 planes); HAS_LNX_: the PRO_LNX variant exists
-static void x3h_variant_exists(GemmP) {}
-#define MT2_X3HL(ID_, BM_, BN_, WM_, WN_, NL_, NST_, HAS_LNX_)                                                     \
-    { BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * ((size_t)BM_ * BK * 4 + (size_t)(2 * BN_ / 16) * 1024),       \
-      "x3hldr" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_ "xc",                                            \
-      { x3h_variant_exists, x3h_variant_exists, x3h_variant_exists, x3h_variant_exists, nullptr,                    \
-        (HAS_LNX_) ? x3h_variant_exists : nullptr }, 0, true, 0, (HAS_LNX_) ? (BN_) / (WN_) : 0, ID_ }
-
-#define MT2_X3HK(ID_, BM_, BN_, WM_, WN_, KS_, NL_, NST_)                                                           \
-    { BM_, BN_, (WM_* WN_ * KS_ + NL_) * 64, (size_t)KS_ * NST_ * ((size_t)BM_ * BK * 4 + (size_t)(2 * BN_ / 16) * 1024), \
-      "x3hks" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_k" #KS_ "+" #NL_ "_s" #NST_,                                        \
-      { x3h_variant_exists, x3h_variant_exists, x3h_variant_exists, x3h_variant_exists, nullptr, x3h_variant_exists }, 0, true, KS_, 32, ID_ }
-
-#define MT2_X3HW(ID_, QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                           \
-    { BM_, BN_, (WM_* WN_ + NL_) * 64,                                                                               \
-      (size_t)NST_ * (((2 * BN_ / 16 + ((NL_) > 0 ? (NL_) : WM_ * WN_) - 1) / ((NL_) > 0 ? (NL_) : WM_ * WN_)) * ((NL_) > 0 ? (NL_) : WM_ * WN_) * 1024), \
-      "x3hwin" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_,                                                  \
-      { x3h_variant_exists, x3h_variant_exists, x3h_variant_exists, nullptr, nullptr, nullptr }, QS_, true, 0, 0, ID_ }
-
-static const TileCfg kCfgs[] = {
+static const TileCfg kF32Rows[] = {
     // v1: register-staged double buffer (kept for A/B runs and as the reference implementation)
-    MT2_RETIRED("128x128_2x2"),                             // 0
-    MT2_RETIRED("64x128_2x2"),                              // 1
-    MT2_RETIRED("128x64_2x2"),                              // 2
-    MT2_CFG(64, 64, 2, 2),     // 3
-    MT2_RETIRED("32x128_1x4"),                              // 4
-    MT2_RETIRED("32x64_1x2"),                               // 5
-    MT2_RETIRED("128x32_4x1"),                              // 6
-    MT2_RETIRED("64x32_2x1"),                               // 7
+    MT2_CFG(CFG_64x64, 64, 64, 2, 2),
     // v2: LDS-DMA ring
-    MT2_RETIRED("dma128x128_2x2_s3"),                       // 8
-    MT2_RETIRED("dma128x128_2x2_s4"),                       // 9
-    MT2_RETIRED("dma64x128_2x2_s4"),                        // 10
-    MT2_RETIRED("dma64x64_2x2_s4"),                         // 11
-    MT2_DMA(64, 64, 2, 2, 3),     // 12
-    MT2_RETIRED("dma32x128_1x4_s4"),                        // 13
-    MT2_RETIRED("dma32x64_1x2_s4"),                         // 14
-    MT2_DMA(128, 32, 4, 1, 4),    // 15
-    MT2_DMA(256, 128, 4, 2, 3),   // 16: 8 waves (2 per SIMD), 64x64 per wave, 43 FLOP per operand byte
-    MT2_DMA(128, 128, 4, 2, 4),   // 17: 8 waves, 32x64 per wave
+    MT2_DMA(CFG_DMA64x64_S3, 64, 64, 2, 2, 3),
+    MT2_DMA(CFG_DMA128x32_S4, 128, 32, 4, 1, 4),
+    MT2_DMA(CFG_DMA256x128_S3, 256, 128, 4, 2, 3),   // 8 waves (2 per SIMD), 64x64 per wave, 43 FLOP per operand byte
+    MT2_DMA(CFG_DMA128x128_S4, 128, 128, 4, 2, 4),   // 8 waves, 32x64 per wave
     // v2 + in-workgroup K split (one 32x32 tile per wave, KS waves per SIMD)
-    MT2_DMAL(64, 64, 2, 2, 2),      // 18:  8 waves,  64 KiB LDS (2 workgroups per CU)
-    MT2_RETIRED("dma64x64_2x2_k2_s4"),                      // 19:  8 waves, 128 KiB
-    MT2_DMAL(64, 64, 2, 2, 4),      // 20: 16 waves, 128 KiB
-    MT2_RETIRED("dma32x64_1x2_k4_s3"),                      // 21:  8 waves, 144 KiB, 32-row tiles for the first AR steps
-    MT2_DMAL(32, 64, 1, 2, 4),      // 22:  8 waves,  96 KiB
+    MT2_DMAL(CFG_DMA64x64_K2, 64, 64, 2, 2, 2),      //  8 waves,  64 KiB LDS (2 workgroups per CU)
+    MT2_DMAL(CFG_DMA64x64_K4, 64, 64, 2, 2, 4),      // 16 waves, 128 KiB
+    MT2_DMAL(CFG_DMA32x64_K4, 32, 64, 1, 2, 4),      //  8 waves,  96 KiB
     // 64-wide outputs (HiFi-GAN stage 3): a 128-wide tile would idle half of its MFMAs
-    MT2_DMA(256, 64, 4, 2, 3),      // 23: 8 waves, 64x32 per wave, 120 KiB
-    MT2_RETIRED("dma128x64_4x2_s4"),                        // 24: 8 waves, 32x32 per wave,  96 KiB
-    MT2_RETIRED("dma128x64_4x2_s2"),                        // 25: the same with a 2-deep ring: 48 KiB -> 3 workgroups per CU
-    MT2_RETIRED("dma64x64_2x2_k1_s2"),                      // 26: 4 waves, 2-deep ring: 32 KiB -> 5 workgroups per CU
-    MT2_RETIRED("dma128x64_4x2_k2_s2"),                     // 27: 16 waves (2 K groups of 4x2), 96 KiB
-    MT2_DMAL(32, 32, 1, 1, 8),      // 28: 8 waves = 8 K groups of one wave, 128 KiB: the shortest K chain (M*N <= 256 tiles)
-    MT2_RETIRED("dma32x32_1x1_k4_s3"),                      // 29: 4 waves, 96 KiB
+    MT2_DMA(CFG_DMA256x64_S3, 256, 64, 4, 2, 3),     // 8 waves, 64x32 per wave, 120 KiB
+    MT2_DMAL(CFG_DMA32x32_K8, 32, 32, 1, 1, 8),      // 8 waves = 8 K groups of one wave, 128 KiB: the shortest K chain (M*N <= 256 tiles)
     // v3: window convolutions (Cin = Cout in {32, 64, 128}); ring = 3 stages of max(BN / 8, waves) KiB
-    MT2_WIN(1, 256, 32, 8, 1, 3),    // 30: 8 waves, one 32x32 tile each; 24 + 40 KiB -> 2 workgroups per CU
-    MT2_WIN(2, 256, 64, 8, 1, 3),    // 31: 8 waves, 32x64 each; 24 + 80 KiB
-    MT2_WIN(4, 128, 128, 4, 2, 3),   // 32: 8 waves, 32x64 each; 48 + 92 KiB
-    MT2_RETIRED("win128x64_4x2_s3"),                        // 33: 8 waves, 32x32 each; 24 + 46 KiB -> 2 workgroups per CU
-    // v3b: window convolutions on the bf16 pipe, f32-equivalent (6 products); ring stage = 3 planes x BN x 64 B
-    MT2_WX6(1, 256, 32, 8, 1, 3),    // 34: 8 waves, 32x32 each; 24 + 40 KiB
-    MT2_RETIRED("x6win256x64_8x1_s3"),                      // 35: 8 waves, 32x64 each; 48 + 80 KiB
-    MT2_RETIRED("x6win128x128_4x2_s2"),                     // 36: 8 waves, 32x64 each; 48 + 92 KiB
-    // v2b: implicit GEMM on the bf16 pipe, f32-equivalent; stage = BM x 128 B (A, f32) + 3 x BN x 64 B (B planes)
-    MT2_RETIRED("x6dma256x128_4x2_s2"),                     // 37: 8 waves, 64x64 each; 2 x 56 KiB
-    MT2_RETIRED("x6dma128x128_4x2_s3"),                     // 38: 8 waves, 32x64 each; 3 x 40 KiB
-    MT2_RETIRED("x6dma128x128_4x2_s2"),                     // 39: the same with a 2-deep ring: 80 KiB (LDS would admit two workgroups per CU, its 197 VGPRs one)
-    MT2_RETIRED("x6dma128x256_2x4_s2"),      // 40: 8 waves, 64x64 each; 2 x 64 KiB (wide N: the AR feed-forward / QKV)
-    MT2_RETIRED("x6dma256x128_8x2_s2"),      // 41: 16 waves, 32x64 each; 2 x 56 KiB (4 waves per SIMD)
-    MT2_RETIRED("x6dma256x128_8x1_s2"),      // 42: 8 waves, 32x128 each: every A fragment is split ONCE per workgroup, 24 MFMAs per split
-    MT2_RETIRED("x6dma128x128_4x1_s2"),      // 43: 4 waves, 32x128 each; 80 KiB -> 2 workgroups per CU
-    MT2_RETIRED("x6dma128x256_4x1_s2"),      // 44: 4 waves, 32x256 each (48 MFMAs per split); 2 x 64 KiB
-    // v2c: x6 with the A operand through registers (plain vector loads), weight planes through the ring
-    MT2_RETIRED("x6areg256x128_8x1_s3"),     // 45: 8 waves, 32x128 each; ring 3 x 24 KiB
-    MT2_RETIRED("x6areg256x128_4x2_s3"),     // 46: 8 waves, 64x64 each
-    MT2_RETIRED("x6areg128x128_4x2_s3"),     // 47: 8 waves, 32x64 each; 72 KiB -> 2 workgroups per CU
-    MT2_RETIRED("x6areg128x128_4x1_s3"),     // 48: 4 waves, 32x128 each
-    MT2_RETIRED("x6areg64x128_2x2_s3"),      // 49: 4 waves, 32x64 each; 72 KiB -> 2 workgroups per CU: mid-size AR launches
-    MT2_RETIRED("x6areg128x256_4x2_s2"),     // 50: 8 waves, 32x128 each; ring 2 x 48 KiB
+    MT2_WIN(CFG_WIN256x32, 1, 256, 32, 8, 1, 3),     // 8 waves, one 32x32 tile each; 24 + 40 KiB -> 2 workgroups per CU
+    MT2_WIN(CFG_WIN256x64, 2, 256, 64, 8, 1, 3),     // 8 waves, 32x64 each; 24 + 80 KiB
+    MT2_WIN(CFG_WIN128x128, 4, 128, 128, 4, 2, 3),   // 8 waves, 32x64 each; 48 + 92 KiB
+    // v3b: window convolutions on the bf16 pipe, f32-equivalent (6 products)
+    MT2_WX6(CFG_X6WIN256x32, 1, 256, 32, 8, 1, 3),   // 8 waves, 32x32 each; 24 + 40 KiB
     // v2d: x6 with loader waves (the compute waves issue no vector-memory instruction inside the K loop)
-    MT2_GX6L(256, 128, 4, 2, 4, 2),  // 51: 8 compute + 4 loader waves
-    MT2_RETIRED("x6ldr256x128_4x2+2_s2"),                   // 52: 8 + 2
-    MT2_RETIRED("x6ldr128x128_4x2+4_s2"),  // 53: 8 + 4
-    MT2_RETIRED("x6ldr128x128_4x2+2_s2"),  // 54: 8 + 2
-    MT2_GX6L_S(128, 128, 4, 2, 4, 3),  // 55: 8 + 4, 3-deep ring (120 KiB); + the PRO_LNX variant
-    MT2_RETIRED("x6ldrx128x128_4x2+4_s3"),    // 56: the same with cross-chunk prefetch of the first fragments
-    MT2_RETIRED("x6ldrx128x128_4x2+2_s3"),    // 57: 8 + 2 loader waves
+    MT2_GX6L(CFG_X6LDR256x128, 256, 128, 4, 2, 4, 2),    // 8 compute + 4 loader waves
+    MT2_GX6L_S(CFG_X6LDR128x128, 128, 128, 4, 2, 4, 3),  // 8 + 4, 3-deep ring (120 KiB); + the PRO_LNX variant
     // v3c: x6 window convolutions with loader waves
-    MT2_WX6L(2, 256, 64, 8, 1, 3, 4),   // 58: 8 compute + 4 loader waves
-    MT2_WX6L(4, 128, 128, 4, 2, 2, 4),  // 59
-    MT2_RETIRED("x6winl128x128_4x2+2_s2"),  // 60: 8 + 2
-    MT2_RETIRED("x6winl256x64_8x1+2_s3"),   // 61: 8 + 2
-    // v2e: loader waves + de-phased compute groups
-    MT2_RETIRED("x6ldrd128x128_4x2+4_s3"),       // 62
-    // v2d, small tiles for launches that cannot fill the chip with 128x128 tiles (the AR steps' mid-size GEMMs): one
-    // 32x32 tile per compute wave, 3-deep ring
-    MT2_RETIRED("x6ldr64x128_2x4+4_s3"),                    // 63: 8 + 4 waves, 96 KiB
-    MT2_RETIRED("x6ldr128x64_4x2+4_s3"),                    // 64: 8 + 4 waves, 84 KiB (less operand ingest per FLOP than 63: the A panel is the cheap one)
-    MT2_RETIRED("x6ldr64x128_2x4+2_s3"),      // 65: 8 + 2 waves
-    MT2_RETIRED("x6ldr128x64_4x2+2_s3"),      // 66: 8 + 2 waves
-    // v2f: loader waves + mid-chunk barrier (MP): fragment fetch and split never wait with an empty matrix pipe
-    MT2_RETIRED("x6ldm128x128_4x2+4_s3"),                   // 67: the 55 tile
-    MT2_RETIRED("x6ldm256x128_4x2+4_s2"),                   // 68: the 51 tile
-    MT2_RETIRED("x6ldm128x64_4x2+4_s3"),     // 69: the 64 tile
-    MT2_RETIRED("x6ldm64x128_2x4+4_s3"),     // 70: the 63 tile
-    MT2_RETIRED("x6ldm128x128_4x2+4_s2"),    // 71: 128x128 with a 2-deep ring (80 KiB)
-    // ONE compute wave per SIMD (64x64 per wave) + 4 loader waves: two barrier-synchronised waves on a SIMD run one after
-    // the other (the matrix pipe's arbiter serves the older wave first, profiles/r03_ubench_x6_issue_v2.txt), each at a
-    // lone wave's efficiency and each with its own exposed head; one wave with twice the tile has the same MFMA count per
-    // SIMD, 37 % less LDS traffic, half the splits per MFMA, and 256 registers for the MP pipeline
-    MT2_RETIRED("x6ldm128x128_2x2+4_s3"),                   // 72: 4 + 4 waves, 120 KiB
-    MT2_RETIRED("x6ldm128x128_2x2+2_s3"),    // 73: 4 + 2 waves
-    MT2_RETIRED("x6ldr128x128_2x2+4_s3"),     // 74: the same tile without the MP pipeline (A/B)
-    // v2g: loader waves + FREE-RUNNING compute waves (LDS counters instead of s_barrier in the K loop)
-    MT2_RETIRED("x6ldf128x128_4x2+4_s3"),                   // 75: the 55 tile
-    MT2_RETIRED("x6ldf256x128_4x2+4_s2"),    // 76: the 51 tile
-    MT2_RETIRED("x6ldf128x64_4x2+4_s3"),     // 77: the 64 tile
-    MT2_RETIRED("x6ldf128x128_4x2+2_s3"),    // 78: 55 with 2 loader waves
-    // v2h: x6 arithmetic on the K-split tiles of the AR steps, loader waves own the refill
-    MT2_RETIRED("x6ks32x64_1x2_k4+4_s2"),                   // 79: 8 compute (4 K groups of 1x2) + 4 loader waves, 128 KiB: the 22 tile
-    MT2_RETIRED("x6ks64x64_2x2_k2+4_s3"),                   // 80: 8 compute (2 K groups of 2x2) + 4 loader waves, 120 KiB: the 18 / 20 tile
-    MT2_RETIRED("x6ks32x64_1x2_k4+2_s2"),    // 81: 79 with 2 loader waves
-    MT2_RETIRED("x6ks32x32_1x1_k8+4_s2"),                   // 82: 8 K groups of one wave + 4 loader waves, 112 KiB: the 28 tile
-    MT2_RETIRED("x6ks64x64_2x2_k2+4_s2"),    // 83: 80 with a 2-deep ring (80 KiB)
-    MT2_GX6K_S(32, 64, 1, 2, 4, 8, 2),  // 84 (+ PRO_LNX): 79 with EIGHT loader waves (16 waves: a round's 64 pieces are 8 per loader)
-    MT2_GX6K_S(64, 64, 2, 2, 2, 8, 3),  // 85 (+ PRO_LNX): 80 with eight loader waves (5 pieces per loader and round)
-    MT2_GX6K_S(32, 32, 1, 1, 8, 8, 2),  // 86 (+ PRO_LNX): 82 with eight loader waves
-    // names only: the weight-streaming kernel for M <= 64 rows lives in gemm_skinny.hip (launch_gemm routes to it)
-    { 32, 32, 512, 0, "skinny32_f32", { nullptr, nullptr, nullptr, nullptr, nullptr } },    // 87
-    { 64, 32, 512, 0, "skinny64_f32", { nullptr, nullptr, nullptr, nullptr, nullptr } },    // 88
-    { 32, 32, 512, 0, "skinnytm32_f32", { nullptr, nullptr, nullptr, nullptr, nullptr } },  // 89: the same on tile-major weights
-    { 64, 32, 512, 0, "skinnytm64_f32", { nullptr, nullptr, nullptr, nullptr, nullptr } },  // 90   (+ LayerNorm prologue)
-    // v4: the loader-wave tiles on the fp16 pipe, f32-equivalent THREE-product form (gemm_x3h.hip)
-    MT2_RETIRED("x3hldr128x128_4x2+4_s3"),                  // 91: the 55 tile, one-barrier-per-chunk loop, 3 x 32 KiB (-> 103)
-    MT2_RETIRED("x3hldr128x128_4x2+4_s4"),                  // 92: ... with a 4-deep ring (128 KiB)
-    MT2_RETIRED("x3hldr128x128_2x2+4_s3"),                  // 93: one compute wave per SIMD (64x64 per wave) + 4 loaders
-    MT2_RETIRED("x3hldr128x128_2x2+4_s4"),                  // 94: ... with a 4-deep ring
-    // ... and the K-split tiles of the AR steps (gemm_x3h_ks_kernel; + PRO_LNX)
-    MT2_X3HK(X3H_KS_32x64_K4, 32, 64, 1, 2, 4, 8, 2),             // 95: the 84 tile, 96 KiB
-    MT2_X3HK(X3H_KS_64x64_K2, 64, 64, 2, 2, 2, 8, 3),             // 96: the 85 tile, 96 KiB
-    MT2_X3HK(X3H_KS_32x32_K8, 32, 32, 1, 1, 8, 8, 2),             // 97: the 86 tile, 128 KiB
-    // ... and the window convolutions of the vocoder's resblocks (conv_win_x3h_kernel)
-    MT2_X3HW(X3H_WIN_256x32, 1, 256, 32, 8, 1, 4, 4),             // 98: the 34 tile (32 channels)
-    MT2_X3HW(X3H_WIN_256x64, 2, 256, 64, 8, 1, 4, 4),             // 99: the 58 tile
-    MT2_X3HW(X3H_WIN_128x128, 4, 128, 128, 4, 2, 3, 4),           // 100: the 59 tile
-    // ... the loader tiles with ONE barrier per 64-deep super-chunk (4 stages = 2 super-stages, 128 KiB): +1 % isolated, +2.4 % SLOWER
-    // in the model (profiles/r06_experiment_x3h_superchunk.patch)
-    MT2_RETIRED("x3hldr128x128_4x2+4_s4c2"),                // 101: the 91 tile
-    MT2_RETIRED("x3hldr128x128_2x2+4_s4c2"),                // 102: the 94 tile
-    // ... the loader tile with the fragment pipeline running across the chunk boundary (gemm_x3h_ldr_kernel; "xc" in the name)
-    MT2_X3HL(X3H_LDR_128x128, 128, 128, 4, 2, 4, 4, true),  // 103: the 55 tile (+ PRO_LNX), 4 x 32 KiB: THE x3h loader tile
-    MT2_RETIRED("x3hldr128x128_4x2+4_s3xc"),                // 104: ... 3 x 32 KiB (one chunk-time of DMA latency: slower)
-    MT2_RETIRED("x3hldr128x128_2x2+4_s4xc"),                // 105: the 94 tile in this form (slower than 103 on every shape)
+    MT2_WX6L(CFG_X6WINL256x64, 2, 256, 64, 8, 1, 3, 4),  // 8 compute + 4 loader waves
+    MT2_WX6L(CFG_X6WINL128x128, 4, 128, 128, 4, 2, 2, 4),
+    // v2h: x6 arithmetic on the K-split tiles of the AR steps (+ PRO_LNX), EIGHT loader waves own the refill
+    MT2_GX6K_S(CFG_X6KS32x64_K4, 32, 64, 1, 2, 4, 8, 2),     // the dma32x64 k4 tile; 16 waves: a round's 64 pieces are 8 per loader
+    MT2_GX6K_S(CFG_X6KS64x64_K2, 64, 64, 2, 2, 2, 8, 3),     // the dma64x64 k2 / k4 tile; 5 pieces per loader and round
+    MT2_GX6K_S(CFG_X6KS32x32_K8, 32, 32, 1, 1, 8, 8, 2),     // the dma32x32 k8 tile
 };
-constexpr int kSkinny32 = 87, kSkinny64 = 88, kSkinnyTm32 = 89, kSkinnyTm64 = 90;
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-
-int gemm_trace_shapes(EngineOpts& o, char* buf, int cap, int top) {
-    struct Agg { int cfg, M, N, K, g; long long n; double ms, fl; };
-    std::vector<Agg> v;
-    for (auto& r : o.trace) {
-        float dt = 0.f;
-        if (hipEventSynchronize(r.e1) != hipSuccess || hipEventElapsedTime(&dt, r.e0, r.e1) != hipSuccess) return -1;
-        bool found = false;
-        for (auto& a : v)
-            if (a.cfg == r.cfg && a.M == r.M && a.N == r.N && a.K == r.K && a.g == r.groups) {
-                ++a.n; a.ms += dt; a.fl += r.flops; found = true;
-                break;
-            }
-        if (!found) v.push_back({r.cfg, r.M, r.N, r.K, r.groups, 1, (double)dt, r.flops});
-    }
-    std::sort(v.begin(), v.end(), [](const Agg& a, const Agg& b) { return a.ms > b.ms; });
-    int off = 0;
-    for (int i = 0; i < (int)v.size() && i < top; ++i) {
-        const Agg& a = v[i];
-        const int w = snprintf(buf + off, cap - off, "%s %d %d %d %d %lld %.3f %.2f\n", kCfgs[a.cfg].name, a.M, a.N, a.K, a.g,
-                               a.n, a.ms, a.fl / (a.ms > 0 ? a.ms : 1e-9) / 1e9);
-        if (w < 0 || w >= cap - off) break;
-        off += w;
-    }
-    return off;
-}
-
-int gemm_num_configs() { return kNumCfgs; }
-const char* gemm_config_name(int idx) { return idx >= 0 && idx < kNumCfgs ? kCfgs[idx].name : ""; }
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per-DEVICE state of the code object: a "done" mask per (configuration,
-// prologue) with one bit per device only saves the call; the benign race (two threads setting the same value) is harmless.
-static std::atomic<unsigned long long> g_attr_done[kNumCfgs][6];   // bit per device (dyn_lds_once)
-
-// ---- launch trace (measurement only): HIP events around every GEMM launch, on the launch stream; the records
-// live in the EngineOpts of whoever asked for the trace (the model handle).
-// Per tile configuration: launches, executed FLOPs (2*M*N*K*groups) and summed kernel time (ms).  When the
-// launches ran on several streams (AR stream groups) their intervals overlap; a last pseudo-entry named
-// "union" carries the length of the UNION of all launch intervals (= time during which at least one engine
-// kernel was running), the right denominator for a whole-engine throughput.
-int gemm_trace_collect(EngineOpts& o, int cap, const char** names, int64_t* launches, double* flops, double* ms) {
-    o.trace_on = false;
-    auto& tr = o.trace;
-    int n = 0;
-    std::vector<std::pair<double, double>> iv;
-    double fl_all = 0.0;
-    bool ok = true;
-    for (int i = 0; i < kNumCfgs && n < cap && ok; ++i) {
-        int64_t cnt = 0;
-        double fl = 0.0, t = 0.0;
-        for (auto& r : tr) {
-            if (r.cfg != i) continue;
-            float dt = 0.f, t0 = 0.f;
-            if (hipEventSynchronize(r.e1) != hipSuccess || hipEventElapsedTime(&dt, r.e0, r.e1) != hipSuccess ||
-                hipEventElapsedTime(&t0, tr.front().e0, r.e0) != hipSuccess) { ok = false; break; }
-            iv.emplace_back((double)t0, (double)t0 + dt);
-            ++cnt; fl += r.flops; t += dt;
-        }
-        if (cnt == 0) continue;
-        names[n] = kCfgs[i].name; launches[n] = cnt; flops[n] = fl; ms[n] = t;
-        fl_all += fl;
-        ++n;
-    }
-    if (ok && n < cap && !iv.empty()) {
-        std::sort(iv.begin(), iv.end());
-        double uni = 0.0, lo = iv[0].first, hi = iv[0].second;
-        for (auto& x : iv) {
-            if (x.first > hi) { uni += hi - lo; lo = x.first; hi = x.second; }
-            else if (x.second > hi) hi = x.second;
-        }
-        uni += hi - lo;
-        names[n] = "union"; launches[n] = (int64_t)iv.size(); flops[n] = fl_all; ms[n] = uni;
-        ++n;
-    }
-    for (auto& r : tr) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-    tr.clear();
-    return ok ? n : -1;
-}
-
-// Tile choice, from tools/gemm_sweep.py on MI355X (profiles/r01_gemm_sweep_v3.txt).  Two regimes:
-//   * operand ingest: a CU sustains ~20 GB/s of global->LDS DMA however many workgroups it hosts, so a
-//     tile costs about (bm + bn) * K * 4 B / 20 GB/s; 64x64 tiles (16 FLOP per operand byte) are ingest-bound
-//     at ~85 TFLOP/s but fill the chip earliest - they win for every GEMM of the autoregressive steps
-//     (M <= ~2200 rows);
-//   * matrix issue: big tiles (32-43 FLOP/B) need >= 2 waves per SIMD to keep the MFMA pipe busy across the
-//     per-chunk barrier: the 8-wave 256x128 / 128x128 tiles reach 95-106 TFLOP/s once there are enough of
-//     them to load every CU (conv stacks, vocoder).
-//   * chain / fill (AR steps): a launch with fewer 64x64 tiles than the chip has CUs leaves one workgroup per
-//     CU at best, and a 4-wave tile then runs at the pace of ONE wave per SIMD: serial chain K/2 x 64 cycles
-//     plus an exposed barrier + DMA-issue + ds_read bubble per chunk (measured ~1 us per 32-wide chunk vs
-//     0.43 us of MFMA).  The K-split tiles put 2-4 waves on each SIMD of the same CU instead.
-// (the thresholds, in tiles, are EngineOpts::t_ks4 / t_ks2 / t32 / t32x32)
-
-// A CU retires one 64x64 tile of K=768 in ~12 us whatever the launch looks like, so for the AR-step shapes the
-// choice is about how many CUs get a tile and how many tiles the busiest CU gets (profiles/r01_gemm_sweep_ar_*):
-//   32x64 K-split tiles while they fit one per CU; 64x64 K-split tiles while THEY fit one (k4) / two (k2) per CU;
-//   a big 8-wave tile when its tile count just fills the chip once (200..256); otherwise plain 64x64 tiles
-//   (three workgroups per CU, de-phased) and the 8-wave tiles for the conv stacks and the vocoder.
-// window convolution: plain "same" conv over contiguous rows, square, narrow (see conv_win_f32_kernel)
-static bool win_eligible(const GemmP& p) {
-    return p.taps >= 2 && !p.rowbase && p.a_mul == 1 && p.groups == 1 && p.N == p.Cin &&
-           (p.Cin == 32 || p.Cin == 64 || p.Cin == 128) && (p.taps - 1) * p.dil <= 64 && p.pro_act < PRO_LN;
-}
-static const TileCfg* choose_cfg(const GemmP& p, const EngineOpts& o, int* idx_out) {
-    int bi = 12;                                                        // dma64x64_2x2_s3
-    const bool x3h_ok = p.Wh && p.wh_inv;
-    if (o.win_conv && win_eligible(p) && !(o.force_cfg >= 0 && o.force_cfg < kNumCfgs)) {
-        bi = p.Cin == 32 ? 30 : (p.Cin == 64 ? 31 : 32);
-        if (o.x6_conv && p.W3) {
-            // the bf16-pipe forms: 34 (32 channels), and with loader waves 58 / 59 (64 / 128 channels: +5..14 % / +2..6 % over the
-            // self-refilling forms 35 / 36, retired in round 6)
-            bi = bi == 30 ? 34 : (bi == 31 ? 58 : 59);
-            // the fp16-pipe forms of the 64- and 128-channel tiles (profiles/r06_gemm_sweep_x3hwin_v1.txt: +19..37 % and +35..40 %, and
-            // +11..18 % more with the cross-chunk pipeline, _v3_cross_chunk.txt, +10..35 % more with the window converted to fp16
-            // planes once per tile, _v4_planes_in_lds.txt).  The 32-channel convolutions too since then: 94 vs 72 TF/s with 3 taps,
-            // 221 vs 123 with 11 (the first x3h build of that tile was 3..19 % SLOWER than x6)
-            if ((o.x3h & 4) && x3h_ok) bi = bi == 58 ? 99 : (bi == 59 ? 100 : (bi == 34 ? 98 : bi));
-        }
-        *idx_out = bi;
-        return &kCfgs[bi];
-    }
-    const long long t32 = (long long)((p.M + 31) / 32) * ((p.N + 63) / 64) * p.groups;
-    const long long t32x32 = (long long)((p.M + 31) / 32) * ((p.N + 31) / 32) * p.groups;
-    const long long t64 = (long long)((p.M + 63) / 64) * ((p.N + 63) / 64) * p.groups;
-    const long long t128 = (long long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.groups;
-    const long long t256 = (long long)((p.M + 255) / 256) * ((p.N + 127) / 128) * p.groups;
-    if (p.N <= 32) bi = 15;                                             // dma128x32_4x1_s4
-    else if (p.N <= 64 && t128 >= 400) bi = 23;                         // dma256x64_4x2_s3
-    else if (p.N <= 256 && t128 >= 400) bi = 17;                        // two n-tiles: 128x128 beats 256x128 (vocoder)
-    else if (t256 >= 400 || (t256 >= 200 && t256 <= 256)) bi = 16;      // dma256x128_4x2_s3
-    else if (t128 >= 400 || (t128 >= 200 && t128 <= 256)) bi = 17;      // dma128x128_4x2_s4
-    else if (t32x32 <= o.t32x32 && p.K >= 512) bi = 28;                 // dma32x32_1x1_k8_s2
-    else if (t32 <= o.t32) bi = 22;                                     // dma32x64_1x2_k4_s2
-    else if (t64 <= o.t_ks4) bi = 20;                                   // dma64x64_2x2_k4_s2
-    else if (t64 <= o.t_ks2) bi = 18;                                   // dma64x64_2x2_k2_s2
-    // Launches whose weights come with planes leave the f32 MFMA for the 16-bit matrix pipe in an f32-equivalent form: the
-    // loader-wave tiles (256x128 from t_x6_256 tiles on, 128x128 from t_x6_128 / t_x3h_128 on - conv stacks, vocoder stage 1, the
-    // PLM / ADM QKV and ff.0 at full batch) and, below that, the K-split tiles of the AR steps (out-projection, ff.3, early steps).
-    if (o.x6_gemm && p.W3 && (p.K & 7) == 0 && (p.ldw & 7) == 0 && (p.pro_act < PRO_LN || p.pro_act == PRO_LNX) && p.N > 64) {
-        const bool h1 = (o.x3h & 1) && x3h_ok;      // the 128x128 tile will run in its x3h form: its own crossover against the K-split tiles
-        if (t256 >= o.t_x6_256) bi = 51;
-        else if (t128 >= (h1 ? o.t_x3h_128 : o.t_x6_128)) bi = 55;
-        // K-split tiles on the bf16 pipe, eight loader waves (x6_ks: 0 off; 1, 3: the 32x64 k4 and 64x64 k2 tiles; 2, 4: + the 32x32
-        // k8 tile; 5: the 64x64 tile only)
-        if (o.x6_ks && p.taps == 1) {
-            if (bi == 22 && p.K % (BK * 4) == 0 && o.x6_ks != 5) bi = 84;
-            else if ((bi == 20 || bi == 18) && p.K % (BK * 2) == 0) bi = 85;
-            else if ((o.x6_ks == 2 || o.x6_ks == 4) && bi == 28 && p.K % (BK * 8) == 0) bi = 86;
-        }
-    }
-    // the fp16-pipe form of the tile (three products instead of six) where one exists and the weights come with fp16 planes
-    // (profiles/r06_gemm_sweep_x3h_v1_gate.txt: the 128x128 x3h tile beats BOTH x6 loader tiles on every shape of the model - 199 vs
-    // 146 TF/s at 864x4096x1024, 245 vs 188 at 4096^3 on the first build; 243 and 297 with the cross-chunk pipeline and the loaders
-    // on buffer loads, profiles/r06_gemm_sweep_x3hxc_v2_buffer_loads.txt)
-    if ((o.x3h & 1) && x3h_ok && (bi == 55 || bi == 51)) bi = 103;
-    // K-split tiles 84 / 85 / 86 -> 95 / 96 / 97 (profiles/r06_gemm_sweep_x3hk_v1.txt: +13..20 %, +25..50 %, +20..30 % per launch)
-    if ((o.x3h & 2) && x3h_ok && bi >= 84 && bi <= 86) bi += 11;
-    if (o.force_cfg >= 0 && o.force_cfg < kNumCfgs) bi = o.force_cfg;
-    *idx_out = bi;
-    return &kCfgs[bi];
-}
-
-bool gemm_takes_planes(const GemmP& p_in, const EngineOpts& o) {
-    GemmP p = p_in;
-    if (p.taps <= 0) p.taps = 1;
-    if (p.groups <= 0) p.groups = 1;
-    if (p.a_mul == 0) p.a_mul = 1;
-    p.K = p.taps * p.Cin;
-    if (p.ldw == 0) p.ldw = p.K;
-    if (!(o.x3h & 3) || o.force_cfg >= 0 || p.M <= 64 || p.pro_act != ACT_NONE || p.stat_out || (p.Cin % BK) != 0 || (p.ldx % BK) != 0 ||
-        (p.groups > 1 && (p.strideX % BK) != 0) || p.a_mul != 1 || p.rowbase || !p.Wh || !p.wh_inv || (((unsigned long long)p.X) & 127))
-        return false;
-    int idx = -1;
-    const TileCfg* c = choose_cfg(p, o, &idx);
-    return c && c->x3h >= 0 && !c->win_qs && c->fn[PRO_APL] != nullptr;
-}
-
-// C as fp16 planes (GemmP::c_planes): the x3h loader tile's 16-byte-store epilogue, whole 128-byte blocks per row, one group
-static bool c_planes_ok(const GemmP& p, const TileCfg* c) {
-    return c && c->x3h >= 0 && !c->x6_ks && !c->win_qs && p.groups == 1 && !p.R && !p.stat_out && (p.N & 31) == 0 && (p.ldc & 31) == 0 &&
-           (((unsigned long long)p.C) & 127) == 0 && (((unsigned long long)p.bias) & 15) == 0 && ((p.strideC | p.strideB) & 3) == 0 && p.Wh && p.wh_inv && p.M > 64;
-}
-bool gemm_writes_planes(const GemmP& p_in, const EngineOpts& o) {
-    GemmP p = p_in;
-    if (p.taps <= 0) p.taps = 1;
-    if (p.groups <= 0) p.groups = 1;
-    if (p.a_mul == 0) p.a_mul = 1;
-    p.K = p.taps * p.Cin;
-    if (p.ldw == 0) p.ldw = p.K;
-    if (!(o.x3h & 1) || o.force_cfg >= 0 || p.M <= 64) return false;
-    int idx = -1;
-    const TileCfg* c = choose_cfg(p, o, &idx);
-    return c_planes_ok(p, c);
-}
-
-hipError_t launch_gemm(const GemmP& p_in, hipStream_t s, EngineOpts* opts) {
-    static const EngineOpts kDefaults;
-    const EngineOpts& o = opts ? *opts : kDefaults;
-    GemmP p = p_in;
-    if (p.M <= 0 || p.N <= 0 || p.groups <= 0) return hipSuccess;
-    if ((p.Cin & 3) || (p.ldx & 3) || (p.ldw & 3) || p.K != p.taps * p.Cin) return hipErrorInvalidValue;
-    if (p.pro_act < 0 || p.pro_act > PRO_LNX) return hipErrorInvalidValue;
-    if (opts) opts->last_stat_nt = opts->last_stat_w = 0;
-    if (p.c_planes && p.M <= 64) return hipErrorNotSupported;      // (the <= 64-row kernels write f32)
-    if (p.pro_act == PRO_LNX && (p.taps != 1 || p.groups != 1 || !p.ln_g || !p.ln_stat || p.ln_nt < 2 || p.ln_nt > 32 ||
-                                 (p.ln_nt & 1) || p.ln_w <= 0 || p.ln_nt * p.ln_w != p.K || (((unsigned long long)p.ln_stat) & 15)))
-        return hipErrorInvalidValue;
-    // a handful of rows: the weight-streaming kernel (gemm_skinny.hip) instead of a tile configuration
-    const bool sk_forced = o.force_cfg == kSkinny32 || o.force_cfg == kSkinny64;
-    const bool tm_forced = o.force_cfg == kSkinnyTm32 || o.force_cfg == kSkinnyTm64;
-    if (tm_forced || (!p.a_planes && o.skinny_tm && o.skinny_rows > 0 && o.force_cfg < 0 &&
-                      gemm_skinny_tm_eligible(p, o.skinny_rows))) {
-        if (!gemm_skinny_tm_eligible(p, 64)) return hipErrorInvalidValue;
-        p.sk_nw = o.skinny_nw;
-        if (p.stat_out) {       // row statistics as pairs per 16-column block (gemm_skinny_tm_kernel's epilogue): N / 16 <= 64 pairs per row
-            const int nt = p.N / 16;
-            if (p.groups == 1 && (nt & 1) == 0 && nt <= 64 && ((((unsigned long long)p.stat_out) & 15) == 0)) { p.stat_nt = nt; p.stat_w = 16; }
-            else { p.stat_out = nullptr; p.stat_nt = p.stat_w = 0; }
-        }
-        if (opts) { opts->last_stat_nt = p.stat_nt; opts->last_stat_w = p.stat_w; }
-        const int sidx = p.M <= 32 ? kSkinnyTm32 : kSkinnyTm64;
-        if (opts) opts->last_cfg = kCfgs[sidx].name;
-        if (opts && opts->trace_on) {
-            TraceRec r;
-            r.cfg = sidx;
-            r.flops = 2.0 * p.M * p.N * p.K * p.groups;
-            r.M = p.M; r.N = p.N; r.K = p.K; r.groups = p.groups;
-            if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return hipErrorUnknown;
-            (void)hipEventRecord(r.e0, s);
-            const hipError_t e = launch_gemm_skinny_tm(p, s);
-            (void)hipEventRecord(r.e1, s);
-            opts->trace.push_back(r);
-            return e;
-        }
-        return launch_gemm_skinny_tm(p, s);
-    }
-    if (sk_forced || (o.skinny_rows > 0 && o.force_cfg < 0 && gemm_skinny_eligible(p, o.skinny_rows))) {
-        if (!gemm_skinny_eligible(p, 64)) return hipErrorInvalidValue;
-        const int sidx = p.M <= 32 ? kSkinny32 : kSkinny64;
-        if (opts) opts->last_cfg = kCfgs[sidx].name;
-        if (opts && opts->trace_on) {
-            TraceRec r;
-            r.cfg = sidx;
-            r.flops = 2.0 * p.M * p.N * p.K * p.groups;
-            r.M = p.M; r.N = p.N; r.K = p.K; r.groups = p.groups;
-            if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return hipErrorUnknown;
-            (void)hipEventRecord(r.e0, s);
-            const hipError_t e = launch_gemm_skinny(p, s);
-            (void)hipEventRecord(r.e1, s);
-            opts->trace.push_back(r);
-            return e;
-        }
-        return launch_gemm_skinny(p, s);
-    }
-    int idx = 0;
-    const TileCfg* c = choose_cfg(p, o, &idx);
-    if (p.pro_act == PRO_LNX && !(c->stat_w && c->fn[PRO_LNX])) return hipErrorNotSupported;      // callers fall back to LayerNorm + GEMM
-    // the x3h loader tile writes through the 16-byte-store epilogue only in its pair-statistics variant: columns in fours, 16-byte bases
-    if (c->x3h >= 0 && !c->x6_ks && !c->win_qs && (p.pro_act == PRO_LNX || p.stat_out)) {
-        const bool t4 = ((p.N | p.ldc | (p.R ? p.ldr : 0)) & 3) == 0 && ((p.strideC | p.strideR | p.strideB) & 3) == 0 &&
-                        (((unsigned long long)p.C | (unsigned long long)p.R | (unsigned long long)p.bias) & 15) == 0;
-        if (!t4) {
-            if (p.pro_act == PRO_LNX) return hipErrorNotSupported;
-            p.stat_out = nullptr;
-        }
-    }
-    if (p.stat_out) {       // row-statistics epilogue where the chosen tile has one; otherwise the launch simply writes none
-        const int nt = c->stat_w ? p.N / c->stat_w : 0;
-        if (c->stat_w && c->fn[PRO_LNX] && (p.pro_act == ACT_NONE || p.pro_act == PRO_LNX) && p.groups == 1 &&
-            p.N % c->stat_w == 0 && nt >= 2 && nt <= 32 && (nt & 1) == 0 && ((((unsigned long long)p.stat_out) & 15) == 0)) {
-            p.stat_w = c->stat_w; p.stat_nt = nt;
-        } else {
-            p.stat_out = nullptr; p.stat_w = p.stat_nt = 0;
-        }
-    }
-    // variant index: pair statistics (consumer and / or producer side) run the PRO_LNX instantiation - the K loop of ACT_NONE
-    // ... an A operand that arrives as fp16 planes (a_planes) runs the PRO_APL instantiation: x3h loader / K-split tiles only
-    if (p.a_planes && (c->x3h < 0 || c->win_qs || p.pro_act != ACT_NONE || p.stat_out || (p.Cin % BK) != 0 || (p.ldx % BK) != 0 ||
-                       (p.groups > 1 && (p.strideX % BK) != 0) || p.a_mul != 1 || p.rowbase || (((unsigned long long)p.X) & 127)))
-        return hipErrorNotSupported;
-    if (p.c_planes && !c_planes_ok(p, c)) return hipErrorNotSupported;
-    const int fi = p.a_planes ? PRO_APL : ((p.pro_act == PRO_LNX || p.stat_out) ? PRO_LNX : p.pro_act);
-    // LayerNorm as a prologue of the f32 tiles (pro_act 3 / 4: rounds 1-2, measured slower than LayerNorm + GEMM) is retired: callers
-    // fall back on NotSupported; the <= 64-row weight-streaming kernel (above) keeps its own LayerNorm prologue
-    if (p.pro_act == PRO_LN || p.pro_act == PRO_LNA) return hipErrorNotSupported;
-    size_t lds = c->lds, lds_attr = 0;
-    // pair-fed LayerNorm on the loader-wave tiles: + row statistics [BM][2] behind the ring.  The PRO_LNX instantiation also serves
-    // stat_out-only producers: the same size for both, so that the cached MaxDynamicSharedMemorySize attribute covers either use
-    if (fi == PRO_LNX && !c->x6_ks) lds = c->lds + (size_t)c->bm * 2 * sizeof(float);
-    if (c->x3h >= 0) {
-        if (!p.Wh || !p.wh_inv || (p.K & 7) || (p.ldw & 7) || (p.pro_act >= PRO_LN && p.pro_act != PRO_LNX)) return hipErrorInvalidValue;
-        if (p.wh_ldb == 0) p.wh_ldb = 4ll * ((p.ldw + 31) / 32 * 32);      // chunk-interleaved rows, K padded to whole chunks
-        if (p.groups > 1 && p.wh_gstride == 0) p.wh_gstride = p.strideW * 4;   // (exact for whole-chunk rows; attach_planes sets it otherwise)
-        if ((((unsigned long long)p.Wh) & 127) || (p.wh_ldb & 127) || (p.wh_gstride & 127)) return hipErrorInvalidValue;
-        p.x3h_flag = o.x3h_flag;
-    } else
-    if (c->x6 && (!p.W3 || (p.K & 7) || (p.ldw & 7) || (p.pro_act >= PRO_LN && p.pro_act != PRO_LNX))) return hipErrorInvalidValue;
-    if (c->x6_ks && (p.taps != 1 || p.K % (BK * c->x6_ks) != 0)) return hipErrorInvalidValue;
-    if (c->x6 && c->x3h < 0 && p.w3_plane == 0) p.w3_plane = (long long)p.N * p.ldw;
-    if (c->win_qs) {
-        if (!win_eligible(p) || p.Cin != 32 * c->win_qs) return hipErrorInvalidValue;
-        const int wrp = (c->bm + (p.taps - 1) * p.dil + 7) & ~7;
-        lds = c->lds + (size_t)c->win_qs * wrp * BK * sizeof(float);
-    }
-    void (*fn)(GemmP) = c->fn[fi];
-    if (fn && c->x3h >= 0) fn = x3h_kernel(c->x3h, fi);
-    if (!fn) return hipErrorNotSupported;           // retired configuration / no variant for this prologue
-    {
-        if (c->win_qs) lds_attr = c->lds + (size_t)c->win_qs * ((c->bm + 64 + 7) & ~7) * BK * sizeof(float);
-        hipError_t e = dyn_lds_once(g_attr_done[idx][fi], reinterpret_cast<const void*>(fn), c->win_qs ? lds_attr : lds);
-        if (e != hipSuccess) return e;
-    }
-    if (opts) { opts->last_stat_nt = p.stat_nt; opts->last_stat_w = p.stat_w; }
-    const int tiles = ((p.M + c->bm - 1) / c->bm) * ((p.N + c->bn - 1) / c->bn);
-    p.epi_t4 = 1;
-    p.ldr_prio = o.ldr_prio;
-    p.ldr64 = o.ldr64 ? 1 : 0;
-    dim3 grid(tiles, 1, p.groups), block(c->threads);
-    if (opts) opts->last_cfg = c->name;
-    if (opts && opts->trace_on) {
-        TraceRec r;
-        r.cfg = idx;
-        r.flops = 2.0 * p.M * p.N * p.K * p.groups;
-        r.M = p.M; r.N = p.N; r.K = p.K; r.groups = p.groups;
-        if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return hipErrorUnknown;
-        (void)hipEventRecord(r.e0, s);
-        hipLaunchKernelGGL(fn, grid, block, lds, s, p);
-        (void)hipEventRecord(r.e1, s);
-        opts->trace.push_back(r);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(fn, grid, block, lds, s, p);
-    return hipGetLastError();
-}
-
+TileRows gemm_f32_tile_rows() { return {kF32Rows, (int)(sizeof(kF32Rows) / sizeof(kF32Rows[0]))}; }
 
 }  // namespace mt2

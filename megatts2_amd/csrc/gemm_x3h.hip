@@ -1189,37 +1189,44 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_win_x3h_kernel(Gem
 }
 
 // ---------------------------------------------------------------------------------------------------
-// host side: the kernels of this unit by tile id and prologue (the tile table lives in gemm_f32.hip)
-#define MT2_X3H_LDR(BM_, BN_, WM_, WN_, NL_, NST_)                                                                          \
-    { gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_NONE>, gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_RELU>, \
-      gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_LRELU>, gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, PRO_APL>, nullptr, \
-      gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, PRO_LNX> }
-#define MT2_X3H_KS(BM_, BN_, WM_, WN_, KS_, NL_, NST_)                                                                          \
-    { gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_NONE>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_RELU>, \
-      gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_LRELU>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_APL>, nullptr, \
-      gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_LNX> }
+// host side: the table rows of this unit's tiles (gemm_tiles.h; gemm_dispatch.hip places them and routes launches)
 
-#define MT2_X3H_WIN(QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                                         \
-    { conv_win_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_NONE, NL_>, conv_win_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_RELU, NL_>, \
-      conv_win_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_LRELU, NL_>, nullptr, nullptr, nullptr }
+// loader-wave tile: stage = BM x 128 B (A, f32) + 2 x BN x 64 B (fp16 planes); pair statistics per wave tile of BN / WN columns
+#define MT2_X3H_LDR(IDX_, BM_, BN_, WM_, WN_, NL_, NST_)                                                                    \
+    { IDX_, BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * ((size_t)BM_ * BK * 4 + (size_t)(2 * BN_ / 16) * 1024),         \
+      "x3hldr" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_ "xc",                                                    \
+      { gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_NONE>, gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_RELU>, \
+        gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, ACT_LRELU>, gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, PRO_APL>, \
+        gemm_x3h_ldr_kernel<BM_, BN_, WM_, WN_, NL_, NST_, PRO_LNX> }, PIPE_X3H, 0, 0, (BN_) / (WN_) }
+#define MT2_X3H_KS(IDX_, BM_, BN_, WM_, WN_, KS_, NL_, NST_)                                                                \
+    { IDX_, BM_, BN_, (WM_* WN_ * KS_ + NL_) * 64, (size_t)KS_ * NST_ * ((size_t)BM_ * BK * 4 + (size_t)(2 * BN_ / 16) * 1024), \
+      "x3hks" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_k" #KS_ "+" #NL_ "_s" #NST_,                                                \
+      { gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_NONE>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_RELU>, \
+        gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_LRELU>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_APL>, \
+        gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_LNX> }, PIPE_X3H, 0, KS_, 32 }
+// window convolution: ring stage = 2 planes x BN x 64 B, in whole KiB per loader wave
+#define MT2_X3H_WIN(IDX_, QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                               \
+    { IDX_, BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * (((2 * BN_ / 16 + NL_ - 1) / NL_) * NL_ * 1024),                  \
+      "x3hwin" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_,                                                          \
+      { conv_win_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_NONE, NL_>, conv_win_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_RELU, NL_>, \
+        conv_win_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_LRELU, NL_> }, PIPE_X3H, QS_ }
 
-X3hKernel x3h_kernel(int tile, int variant) {
-    static void (*const kTable[kX3hTiles][6])(GemmP) = {
-        // X3H_LDR_128x128: 8 compute + 4 loader waves, 4 x 32 KiB (+ PRO_LNX).  Retired beside it in round 6, each measured slower on
-        // every shape of the model (profiles/r06_gemm_sweep_x3hxc_v2_buffer_loads.txt): the one-barrier-per-chunk loop of the same
-        // tile (3 x 32 KiB), the cross-chunk form with a 3-deep ring (one chunk-time of DMA latency), and the 64x64-per-wave forms
-        // (one compute wave per SIMD + 4 loaders, 211..227 registers) in both loops
-        MT2_X3H_LDR(128, 128, 4, 2, 4, 4),
-        MT2_X3H_KS(32, 64, 1, 2, 4, 8, 2),          // X3H_KS_32x64_K4: the 84 tile (8 compute + 8 loader waves)
-        MT2_X3H_KS(64, 64, 2, 2, 2, 8, 3),          // X3H_KS_64x64_K2: the 85 tile
-        MT2_X3H_KS(32, 32, 1, 1, 8, 8, 2),          // X3H_KS_32x32_K8: the 86 tile
-        MT2_X3H_WIN(2, 256, 64, 8, 1, 4, 4),        // X3H_WIN_256x64: the 58 tile (8 compute + 4 loader waves), cross-chunk form: one more stage
-        MT2_X3H_WIN(4, 128, 128, 4, 2, 3, 4),       // X3H_WIN_128x128: the 59 tile
-        MT2_X3H_WIN(1, 256, 32, 8, 1, 4, 4),        // X3H_WIN_256x32: the 34 tile with loader waves
-        // (measured and not kept, round 6: the 32-channel window convolution - 3..19 % slower than its x6 form)
-    };
-    if (tile < 0 || tile >= kX3hTiles || variant < 0 || variant >= 6) return nullptr;
-    return kTable[tile][variant];
-}
+static const TileCfg kX3hRows[] = {
+    // the K-split tiles of the AR steps (+ V_APLANES, + PRO_LNX): 8 compute + 8 loader waves
+    MT2_X3H_KS(CFG_X3HKS32x64_K4, 32, 64, 1, 2, 4, 8, 2),           // the x6ks32x64 k4 tile, 96 KiB
+    MT2_X3H_KS(CFG_X3HKS64x64_K2, 64, 64, 2, 2, 2, 8, 3),           // the x6ks64x64 k2 tile, 96 KiB
+    MT2_X3H_KS(CFG_X3HKS32x32_K8, 32, 32, 1, 1, 8, 8, 2),           // the x6ks32x32 k8 tile, 128 KiB
+    // the window convolutions of the vocoder's resblocks: 8 compute + 4 loader waves, cross-chunk form (one more stage than x6)
+    MT2_X3H_WIN(CFG_X3HWIN256x32, 1, 256, 32, 8, 1, 4, 4),          // the x6win256x32 tile with loader waves (32 channels)
+    MT2_X3H_WIN(CFG_X3HWIN256x64, 2, 256, 64, 8, 1, 4, 4),          // the x6winl256x64 tile
+    MT2_X3H_WIN(CFG_X3HWIN128x128, 4, 128, 128, 4, 2, 3, 4),        // the x6winl128x128 tile
+    // THE x3h loader tile, the fragment pipeline running across the chunk boundary ("xc" in the name): 8 compute + 4 loader waves,
+    // 4 x 32 KiB (+ V_APLANES, + PRO_LNX); the x6ldr128x128 tile.  Retired beside it in round 6, each measured slower on every shape of
+    // the model (profiles/r06_gemm_sweep_x3hxc_v2_buffer_loads.txt): the one-barrier-per-chunk loop of the same tile (3 x 32 KiB), the
+    // cross-chunk form with a 3-deep ring (one chunk-time of DMA latency), and the 64x64-per-wave forms (one compute wave per SIMD + 4
+    // loaders, 211..227 registers) in both loops
+    MT2_X3H_LDR(CFG_X3HLDR128x128, 128, 128, 4, 2, 4, 4),
+};
+TileRows gemm_x3h_tile_rows() { return {kX3hRows, (int)(sizeof(kX3hRows) / sizeof(kX3hRows[0]))}; }
 
 }  // namespace mt2

@@ -152,16 +152,17 @@ struct EngineOpts {
                                  // (no pair-fed form) and a LayerNorm launch is no longer a latency item (C5: 5342 vs 5210 ms without a cap,
                                  // +0.46 % for the ADM alone at 2048, +0.1 % at 1280)
 };
+// gemm_dispatch.hip: the front door of the engine.  gemm_route decides, without a HIP call, what launch_gemm does with a launch:
+// the error it returns (hipSuccess: it launches), the configuration index (gemm_config_name; 87..90: the <= 64-row kernels of
+// gemm_skinny.hip; -1: nothing to launch or rejected before a choice), the variant of that tile's kernel (GemmVariant, gemm_tiles.h),
+// the dynamic LDS bytes, and the row-statistics layout it writes (0: none - a stat_out the chosen kernel cannot serve is dropped)
+struct GemmRoute { hipError_t err; int cfg; int variant; size_t lds; int stat_nt, stat_w; };
+GemmRoute gemm_route(const GemmP& p, const EngineOpts& o);
 hipError_t launch_gemm(const GemmP& p, hipStream_t s, EngineOpts* o = nullptr);
 // would launch_gemm run this launch (planes attached, no prologue) on an x3h tile that takes its A operand as fp16 planes (a_planes)?
 bool gemm_takes_planes(const GemmP& p, const EngineOpts& o);
 // would launch_gemm run this launch on an x3h loader tile whose epilogue can store C as fp16 planes (GemmP::c_planes)?
 bool gemm_writes_planes(const GemmP& p, const EngineOpts& o);
-// gemm_x3h.hip: the kernels of the fp16-pipe form by tile id and variant (prologue none / relu / leaky relu / - / - / pair statistics);
-// nullptr: no such variant
-enum X3hTile : int { X3H_LDR_128x128 = 0, X3H_KS_32x64_K4, X3H_KS_64x64_K2, X3H_KS_32x32_K8, X3H_WIN_256x64, X3H_WIN_128x128, X3H_WIN_256x32, kX3hTiles };
-typedef void (*X3hKernel)(GemmP);
-X3hKernel x3h_kernel(int tile, int variant);
 // gemm_skinny.hip: weight-streaming linear layer for M <= 64 rows (taps = 1, no rowbase, K a multiple of 32)
 bool gemm_skinny_eligible(const GemmP& p, int max_rows);
 hipError_t launch_gemm_skinny(const GemmP& p, hipStream_t s);
@@ -171,7 +172,7 @@ hipError_t launch_gemm_skinny_tm(const GemmP& p, hipStream_t s);
 hipError_t launch_tile_major(const float* W, int N, int K, float* out, hipStream_t s);   // row-major [N, K] -> tile-major blocks
 int gemm_num_configs();
 const char* gemm_config_name(int idx);
-// per tile configuration: launches, executed FLOPs, summed ms; last entry "union" (see gemm_f32.hip); -1 on error
+// per tile configuration: launches, executed FLOPs, summed ms; last entry "union" (see gemm_dispatch.hip); -1 on error
 int gemm_trace_collect(EngineOpts& o, int cap, const char** names, int64_t* launches, double* flops, double* ms);
 // text table "config M N K groups launches ms tflops" of the traced launches grouped by shape, slowest first (call
 // BEFORE gemm_trace_collect, which frees the records); returns the number of bytes written (< cap)

@@ -930,6 +930,13 @@ def op_attention_x3h(Q, K, V, q_start, q_len, kv_start, kv_len, H, D, scale, lds
     return O, int(flag[0].item())
 
 
+def op_gemm_route(M, N, K, taps=1, dil=1, groups=1, pro_act=ACT_NONE, operands=0, misaligned=0, force_cfg=-1, x3h=15):
+    """mt2_gemm_route (no device needed) -> (hipError_t, config index, variant, LDS bytes, planes bits) of the launch launch_gemm would make."""
+    out = [C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_int(0)]
+    _check(load_library().mt2_gemm_route(M, N, K, taps, dil, groups, pro_act, operands, misaligned, force_cfg, x3h, *map(C.byref, out)))
+    return tuple(v.value for v in out)
+
+
 def bench_gemm(M, N, K, taps=1, force_cfg=-1, iters=20, w_copies=1, dil=1, flags=0):
     lib = load_library()
     ms = C.c_float(0)

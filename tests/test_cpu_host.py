@@ -24,7 +24,7 @@ def test_library_builds_and_exports_every_declared_symbol():
 
 
 def test_tile_configuration_table_matches_the_indices_the_chooser_uses():
-    """choose_cfg (gemm_f32.hip) and the kernel tests address tile configurations by table index: pin index -> name, so
+    """choose_cfg (gemm_dispatch.hip) and the kernel tests address tile configurations by table index: pin index -> name, so
     that inserting a configuration in the middle of the table cannot silently re-route launches (no GPU needed)."""
     from megatts2_amd.build import build
     lib = ctypes.CDLL(build(verbose=False))
@@ -45,6 +45,114 @@ def test_tile_configuration_table_matches_the_indices_the_chooser_uses():
             103: "x3hldr128x128_4x2+4_s4xc", 104: "retired:x3hldr128x128_4x2+4_s3xc", 105: "retired:x3hldr128x128_2x2+4_s4xc"}
     for i, name in want.items():
         assert names[i] == name, (i, names[i], name)
+
+
+HIP_INVALID_VALUE, HIP_NOT_SUPPORTED = 1, 801
+# mt2_gemm_route operand bits
+OP_W3, OP_WH, OP_WTM, OP_STAT, OP_LNSTAT, OP_R, OP_ROWBASE, OP_APLANES, OP_CPLANES, MIS_X, MIS_C = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024
+V_NONE, V_RELU, V_LRELU, V_APLANES, V_LNX = range(5)
+
+
+def test_gemm_route_reproduces_the_recorded_routing_table():
+    """tests/gemm_routes.json was recorded by running the routing code as it was BEFORE gemm_dispatch.hip existed (choose_cfg, the
+    skinny eligibility tests, gemm_takes_planes / gemm_writes_planes and launch_gemm's validation, on the CPU) over the grid
+    M x N x Cin x taps x groups x operands x pro_act x x3h: mt2_gemm_route gives the same configuration, the same two planes answers
+    and the same accept / reject for each of its 107 520 launches, and the grid reaches every live configuration but 3 (forced only)."""
+    import json
+    from megatts2_amd.runtime import op_gemm_route
+    with open(os.path.join(ROOT, "tests", "gemm_routes.json")) as f:
+        tab = json.load(f)
+    Ms, outcomes, seen, bad = tab["M"], tab["outcomes"], set(), []
+    assert len(tab["rows"]) * len(Ms) == 107520
+    for N, Cin, taps, groups, operands, pro_act, x3h, oc in tab["rows"]:
+        for M, want in zip(Ms, outcomes[oc]):
+            err, cfg, _, _, planes = op_gemm_route(M, N, taps * Cin, taps, 1, groups, pro_act, operands, 0, -1, x3h)
+            got = cfg * 8 + planes * 2 + (1 if err in (HIP_INVALID_VALUE, HIP_NOT_SUPPORTED) else 0)
+            seen.add(want >> 3)
+            if got != want and len(bad) < 10:
+                bad.append(((M, N, Cin, taps, groups, operands, pro_act, x3h), want, got, err))
+    assert not bad, bad
+    lib = ctypes.CDLL(__import__("megatts2_amd.build", fromlist=["build"]).build(verbose=False))
+    lib.mt2_gemm_config_name.restype = ctypes.c_char_p
+    live = {i for i in range(lib.mt2_gemm_config_count()) if not lib.mt2_gemm_config_name(i).startswith(b"retired:")}
+    assert len(live) == 32 and live - seen == {3}
+
+
+def test_gemm_route_forced_configurations_and_rejections():
+    """The forced and the rejected launches, as launch_gemm's source answered them before the refactor (no GPU needed)."""
+    from megatts2_amd.build import build
+    from megatts2_amd.runtime import op_gemm_route
+    lib = ctypes.CDLL(build(verbose=False))
+    lib.mt2_gemm_config_name.restype = ctypes.c_char_p
+    retired = [i for i in range(lib.mt2_gemm_config_count()) if lib.mt2_gemm_config_name(i).startswith(b"retired:")]
+    assert len(retired) == 74
+    full = OP_W3 | OP_WH
+    for i in retired:       # with and without planes, big and small launches
+        for M, ops in ((864, 0), (864, full), (32, full | OP_WTM), (864, full | OP_STAT)):
+            err, cfg = op_gemm_route(M, 768, 768, operands=ops, force_cfg=i)[:2]
+            assert (err, cfg) == (HIP_NOT_SUPPORTED, i), (i, M, ops, err, cfg)
+    # the <= 64-row kernels forced onto launches they cannot run: too many rows, taps, K not in whole blocks, no tile-major copy
+    for cfg in (87, 88, 89, 90):
+        assert op_gemm_route(65, 768, 768, operands=OP_WTM, force_cfg=cfg)[0] == HIP_INVALID_VALUE
+        assert op_gemm_route(32, 768, 3 * 256, taps=3, operands=OP_WTM, force_cfg=cfg)[0] == HIP_INVALID_VALUE
+        assert op_gemm_route(32, 768, 100, operands=OP_WTM, force_cfg=cfg)[0] == HIP_INVALID_VALUE
+    assert op_gemm_route(32, 768, 768, operands=0, force_cfg=89)[0] == HIP_INVALID_VALUE
+    assert op_gemm_route(32, 768, 768, operands=OP_WTM, force_cfg=89)[:2] == (0, 89)
+    assert op_gemm_route(64, 768, 768, operands=OP_WTM, force_cfg=89)[:2] == (0, 90)      # the row count picks 32 / 64 within the family
+    assert op_gemm_route(64, 768, 768, operands=0, force_cfg=87)[:2] == (0, 88)
+    # C as planes: the x3h loader tile only, more than 64 rows
+    assert op_gemm_route(864, 768, 768, operands=full | OP_CPLANES, force_cfg=103)[:3] == (0, 103, V_NONE)
+    assert op_gemm_route(864, 768, 768, operands=full | OP_CPLANES, force_cfg=96)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(864, 768, 768, operands=full | OP_CPLANES, force_cfg=55)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(64, 768, 768, operands=full | OP_CPLANES, force_cfg=103)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(64, 768, 768, operands=full | OP_CPLANES | OP_WTM)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(864, 768, 768, operands=full | OP_CPLANES | OP_R, force_cfg=103)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(864, 768, 768, operands=full | OP_CPLANES, misaligned=MIS_C, force_cfg=103)[0] == HIP_NOT_SUPPORTED
+    # A as planes: x3h loader / K-split tiles, no prologue, X on 128 bytes
+    for cfg in (103, 95, 96, 97):
+        assert op_gemm_route(864, 768, 768, operands=full | OP_APLANES, force_cfg=cfg)[:3] == (0, cfg, V_APLANES)
+    for cfg in (55, 85, 12, 3):
+        assert op_gemm_route(864, 768, 768, operands=full | OP_APLANES, force_cfg=cfg)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(2200, 64, 3 * 64, taps=3, operands=full | OP_APLANES, force_cfg=99)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(864, 768, 768, pro_act=1, operands=full | OP_APLANES, force_cfg=103)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(864, 768, 768, operands=full | OP_APLANES, misaligned=MIS_X, force_cfg=103)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(864, 768, 776, operands=full | OP_APLANES, force_cfg=103)[0] == HIP_NOT_SUPPORTED      # Cin % 32
+    # pair-fed LayerNorm (pro_act 5): the tiles with the pair-statistics variant only; LDS + [BM][2] statistics on the loader tiles
+    for cfg, lds in ((55, 3 * 40960 + 1024), (103, 4 * 32768 + 1024), (84, 131072), (85, 122880), (86, 163840), (95, 98304), (96, 98304), (97, 131072)):
+        assert op_gemm_route(864, 768, 768, pro_act=5, operands=full | OP_LNSTAT, force_cfg=cfg)[:4] == (0, cfg, V_LNX, lds), cfg
+    for cfg in (51, 12, 16, 3, 20):
+        assert op_gemm_route(864, 768, 768, pro_act=5, operands=full | OP_LNSTAT, force_cfg=cfg)[0] == HIP_NOT_SUPPORTED
+    assert op_gemm_route(864, 768, 768, pro_act=5, operands=full, force_cfg=103)[0] == HIP_INVALID_VALUE       # no ln_stat
+    assert op_gemm_route(864, 768, 768, pro_act=5, operands=full | OP_LNSTAT, misaligned=OP_LNSTAT, force_cfg=103)[0] == HIP_INVALID_VALUE
+    assert op_gemm_route(864, 768, 768, pro_act=5, operands=full | OP_LNSTAT, misaligned=MIS_C, force_cfg=103)[0] == HIP_NOT_SUPPORTED
+    # LayerNorm prologues 3 / 4 exist on the tile-major <= 64-row kernel alone
+    for pro in (3, 4):
+        for cfg in (-1, 12, 20, 55, 103):
+            assert op_gemm_route(864, 768, 768, pro_act=pro, operands=full | OP_LNSTAT, force_cfg=cfg)[0] == HIP_NOT_SUPPORTED, (pro, cfg)
+    assert op_gemm_route(864, 768, 768, pro_act=6)[0] == HIP_INVALID_VALUE
+    # row statistics: written where the tile can (pairs per wave tile), silently dropped elsewhere - the launch still succeeds
+    assert op_gemm_route(864, 768, 768, operands=full | OP_STAT, force_cfg=103)[:3] == (0, 103, V_LNX)
+    assert op_gemm_route(864, 768, 768, operands=full | OP_STAT, misaligned=OP_STAT, force_cfg=103)[:3] == (0, 103, V_NONE)
+    assert op_gemm_route(864, 768, 768, operands=full | OP_STAT, misaligned=MIS_C, force_cfg=103)[:3] == (0, 103, V_NONE)
+    assert op_gemm_route(864, 768, 768, operands=full | OP_STAT, force_cfg=51)[:3] == (0, 51, V_NONE)
+    assert op_gemm_route(864, 768, 768, pro_act=2, operands=full | OP_STAT, force_cfg=103)[:3] == (0, 103, V_LRELU)
+    # window configurations: forced onto a launch that is no window convolution, or one of another width
+    for cfg in (30, 31, 32, 34, 58, 59, 98, 99, 100):
+        assert op_gemm_route(864, 768, 768, operands=full, force_cfg=cfg)[0] == HIP_INVALID_VALUE, cfg
+        assert op_gemm_route(2200, 256, 3 * 256, taps=3, operands=full, force_cfg=cfg)[0] == HIP_INVALID_VALUE, cfg
+    assert op_gemm_route(2200, 64, 3 * 64, taps=3, operands=full, force_cfg=98)[0] == HIP_INVALID_VALUE
+    assert op_gemm_route(2200, 64, 3 * 64, taps=3, dil=33, operands=full)[1] != 99        # span > 64 rows: an implicit GEMM
+    # window LDS: the ring + QS chunks of (BM + span rounded to 8) rows of 128 bytes
+    assert op_gemm_route(2200, 64, 3 * 64, taps=3, dil=5, operands=full)[:4] == (0, 99, V_NONE, 4 * 8192 + 2 * ((256 + 10 + 7) & ~7) * 128)
+    assert op_gemm_route(2200, 64, 3 * 64, taps=3, pro_act=2, operands=full, x3h=0)[:3] == (0, 58, V_LRELU)
+    # pipes without their operands, K-split tiles on a K they cannot split
+    assert op_gemm_route(864, 768, 768, operands=OP_W3, force_cfg=103)[0] == HIP_INVALID_VALUE
+    assert op_gemm_route(864, 768, 768, operands=full, misaligned=OP_WH, force_cfg=103)[0] == HIP_INVALID_VALUE
+    assert op_gemm_route(864, 768, 768, operands=OP_WH, force_cfg=55)[0] == HIP_INVALID_VALUE
+    assert op_gemm_route(864, 768, 800, operands=full, force_cfg=95)[0] == HIP_INVALID_VALUE
+    assert op_gemm_route(864, 768, 3 * 256, taps=3, operands=full, force_cfg=85)[0] == HIP_INVALID_VALUE
+    assert op_gemm_route(864, 768, 770, operands=full)[0] == HIP_INVALID_VALUE             # Cin % 4
+    assert op_gemm_route(0, 768, 768)[:2] == (0, -1)                                       # nothing to launch
 
 
 def test_product_path_fails_loudly_without_gpu():

@@ -162,6 +162,28 @@ int mt2_plm_infer_sampled(mt2_model* m, void* stream, const float* cond, const i
                           const int64_t* prefix_codes, int P, int max_steps, int64_t* codes, float* last_logits,
                           const mt2_sampling* sampling);
 
+/* ---- prosody interpolation (Mega-TTS 2, section 3.3; no reference counterpart): the PLM decoded against TWO prosody prompts
+ * at once - context A (the target speaker's) and context B (a second, "rhythmic" speaker's).  Per step and utterance, over the
+ * two rows of vq_bins logits zA, zB, with gamma in [0, 1] and the temperature / top_k / top_p / u of mt2_sampling:
+ *   wA_i = exp((zA_i - max zA) / temperature), SA = sum wA (same for B);
+ *   m_i  = (1 - gamma) * wA_i / SA + gamma * wB_i / SB            (the mixture; sum m = 1 up to rounding);
+ *   rank order = m descending, index ascending; K = the first top_k (all when 0); R = the shortest rank-order prefix of K
+ *   with sum_R m >= top_p * sum_K m; the code is the first index of R, walked in ascending index order, whose running sum of m
+ *   exceeds u * sum_R m (the last index of R when rounding leaves none).
+ * Unlike the single-row rule, the rank order is decided on the COMPUTED f32 m, not on the logits (two logit rows have no
+ * common order).  u is the same Philox4x32-10 draw: key = the utterance's seed, counter = (target position, 0, 0, 0); a code
+ * depends on (seed, position, the two logit rows, gamma) only - not on the batch, the slot, the stream groups or a repeated
+ * call.  The code is fed back to BOTH contexts.  gamma = 0 decodes context A alone, gamma = 1 context B alone.  sampling ==
+ * NULL is greedy on the mixture: temperature 1, the arg-max of m with the lowest index on ties.
+ * cond f32 [2, B, P + Tq_max, tc_dim] (context A, then context B: P prompt rows, then the target rows), prefix_codes int64
+ * [2, B, P] (device; NULL when P = 0), gamma HOST f32 [B], lens = TARGET lengths; codes int64 [B, Tq_max] (0 in padding);
+ * last_logits optional f32 [2, B, Tq_max, bins].  Invalid parameters (gamma NULL, NaN or outside [0, 1]; P > 0 without
+ * prefix_codes; the mt2_sampling errors) are an error before anything is launched; prefix codes are range-checked like those of
+ * mt2_plm_infer_prompted. */
+int mt2_plm_infer_interpolated(mt2_model* m, void* stream, const float* cond, const int32_t* lens /*host*/, int Tq_max, int B,
+                               const int64_t* prefix_codes, int P, const float* gamma /*host*/, int max_steps, int64_t* codes,
+                               float* last_logits, const mt2_sampling* sampling);
+
 /* ---- generator.vqpe.vq.decode(codes) (modules/quantization/vq.py:109-113)
  * codes int64 [n_q=1, B, Tq_max] -> out f32 [B, vq_dim, Tq_max]. */
 int mt2_vq_decode(mt2_model* m, void* stream, const int64_t* codes, int B, int Tq_max, float* out);
@@ -378,6 +400,11 @@ int mt2_op_row(void* stream, const char* op, void* const* ptrs, int nptrs, const
  * s->seeds is not read here (may be NULL); the other fields are checked as for the _sampled calls. */
 int mt2_op_sample_rows(void* stream, const float* logits, int ld, int N, int A, const mt2_sampling* s, const uint64_t* seeds_dev,
                        const int32_t* positions_dev, int64_t* out);
+/* The interpolated draw on A PAIRS of rows (pair j = rows 2j, 2j + 1 of logits: context A, context B) with gamma_dev[j] (f32,
+ * device): out (int64 [2 A], device) receives the code of pair j at 2j AND 2j + 1, as both histories do.  s NULL = greedy on the
+ * mixture (seeds_dev / positions_dev are then not read). */
+int mt2_op_sample_mix_rows(void* stream, const float* logits, int ld, int N, int A, const mt2_sampling* s,
+                           const uint64_t* seeds_dev, const int32_t* positions_dev, const float* gamma_dev, int64_t* out);
 int mt2_op_attention(void* stream, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv,
                      float* O, int ldo, const int32_t* q_start, const int32_t* q_len, const int32_t* kv_start,
                      const int32_t* kv_len, int B, int H, int D, int max_qlen, float scale);

@@ -492,6 +492,34 @@ int mt2_plm_infer_sampled(mt2_model* m, void* stream, const float* cond, const i
     ids_verdict(c);
     MT2_API_END
 }
+// prosody interpolation: two contexts per utterance decoded in lock step on the mixture of their next-code distributions
+int mt2_plm_infer_interpolated(mt2_model* m, void* stream, const float* cond, const int32_t* lens, int Tq_max, int B,
+                               const int64_t* prefix_codes, int P, const float* gamma, int max_steps, int64_t* codes,
+                               float* last_logits, const mt2_sampling* sampling) {
+    MT2_API_BEGIN
+    require_ready(m, NEED_PLM);
+    MT2_REQUIRE(B >= 1 && P >= 0 && max_steps >= 0, "bad arguments");
+    MT2_REQUIRE(P == 0 || prefix_codes != nullptr, "prefix_codes is NULL with P > 0");
+    MT2_REQUIRE(gamma != nullptr, "gamma is NULL (one interpolation weight per utterance)");
+    for (int b = 0; b < B; ++b) MT2_REQUIRE(gamma[b] >= 0.0f && gamma[b] <= 1.0f, "gamma must be in [0, 1]");      // (false for NaN)
+    if (sampling) check_sampling(*sampling, m->cfg.plm_bins, true);
+    MT2_REQUIRE(m->cfg.plm_bins <= 1024, "the mixture kernel serves at most 1024 bins");
+    std::vector<int> total(B);
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= Tq_max, "length out of range");
+        total[b] = P + lens[b];
+    }
+    MT2_CALL(m, stream);
+    if (P > 0)     // both contexts' prompt codes index pc_embedding [bins + 2, vq_dim]
+        ids_check(c, prefix_codes, nullptr, 2ll * B * P, m->cfg.plm_bins + 2, ID_PREFIX);
+    MT2_HIP(hipMemsetAsync(codes, 0, sizeof(int64_t) * (size_t)B * Tq_max, c.s));
+    ArPrefix pre;
+    pre.P = P; pre.data = prefix_codes; pre.max_steps = max_steps;
+    plm_run(c, cond, m->cfg.plm_tc_dim, iota_rows(2 * B, P + Tq_max), total.data(), B, codes, Tq_max, last_logits, Tq_max, pre,
+            sampling, gamma);
+    ids_verdict(c);
+    MT2_API_END
+}
 int mt2_plm_infer_prompted(mt2_model* m, void* stream, const float* cond, const int32_t* lens, int Tq_max, int B,
                            const int64_t* prefix_codes, int P, int max_steps, int64_t* codes, float* last_logits) {
     return mt2_plm_infer_sampled(m, stream, cond, lens, Tq_max, B, prefix_codes, P, max_steps, codes, last_logits, nullptr);
@@ -1261,6 +1289,19 @@ int mt2_op_sample_rows(void* stream, const float* logits, int ld, int N, int A, 
     check_sampling(*s, N, false);
     MT2_HIP(launch_sample_rows(logits, ld, N, out, 1, 0, A, s->temperature, s->top_k, s->top_p,
                                reinterpret_cast<const uint32_t*>(seeds_dev), nullptr, positions_dev, 0, (hipStream_t)stream));
+    MT2_API_END
+}
+
+int mt2_op_sample_mix_rows(void* stream, const float* logits, int ld, int N, int A, const mt2_sampling* s,
+                           const uint64_t* seeds_dev, const int32_t* positions_dev, const float* gamma_dev, int64_t* out) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(logits && gamma_dev && out && A >= 0 && N >= 1 && ld >= N, "bad arguments");
+    MT2_REQUIRE(!s || (seeds_dev && positions_dev), "bad arguments: a sampled draw needs seeds_dev and positions_dev");
+    if (s) check_sampling(*s, N, false);
+    MT2_REQUIRE(N <= 1024, "the mixture kernel serves at most 1024 bins");
+    MT2_HIP(launch_sample_mix_rows(logits, ld, N, out, 1, 0, A, s == nullptr, s ? s->temperature : 1.0f, s ? s->top_k : 0,
+                                   s ? s->top_p : 1.0f, reinterpret_cast<const uint32_t*>(seeds_dev), nullptr, positions_dev, 0,
+                                   gamma_dev, (hipStream_t)stream));
     MT2_API_END
 }
 

@@ -1014,16 +1014,22 @@ struct ArPrefix {
 //   step_input(cg, ip, q, n)  x rows of the A active sequences at n positions
 //   head(cg, ip, q, y, n, t)  position n of the history from the last-position rows y [A, d]
 //   finalize(ip, q, s)        the group's results into the caller's buffers
+// Pair mode (per = 2: prosody interpolation, PlmStage): every utterance contributes TWO sequences of its length, decoded in lock
+// step - context A then context B, adjacent in their group at rows 2j and 2j + 1 of everything a step touches.  lens / the
+// length order / the deal into groups stay per UTTERANCE and are then expanded, so a pair is never split across chains and the
+// active set shrinks by whole pairs; row0 has per * B entries and sequence s of utterance b is id s * B + b (its row0, its slot
+// in q.slot: prefix row, logits row).  per = 1 is every other call: the same plan, launches and arguments as before.
 struct ArGrp {
     int g = 0, first = 0;                   // group index; sequences in the groups before it (row of the run's history buffer)
     int B = 0, nmax = 0, A = 0;             // sequences, positions of the longest, sequences still active
     int o_row = 0, o_len = 0, o_slot = 0;   // plan offsets
+    int o_ulen = -1, o_uslot = -1;          // pair mode: length and utterance of every PAIR of the group
     std::vector<int> len, slot;
     float *x = nullptr, *ylast = nullptr, *qkv0 = nullptr; EncScratch sc{};
 };
 template <class Stage>
 static void ar_run(const Ctx& c, const EncW& e, const std::vector<int>& row0, const int* lens, int B, int stage_groups,
-                   const ArPrefix& pre, Stage& st) {
+                   const ArPrefix& pre, Stage& st, int per = 1) {
     mt2_model& m = c.m;
     const int d = e.d;
     const ArOrder ord = ar_order(lens, B);
@@ -1033,20 +1039,25 @@ static void ar_run(const Ctx& c, const EncW& e, const std::vector<int>& row0, co
     for (int g = 0, first = 0; g < grp.G; ++g) {
         ArGrp& q = gs[g];
         q.g = g; q.first = first;
-        std::vector<int> row;
-        for (int j : grp.slots[g]) {
-            row.push_back(row0[ord.slot_b[j]]);
-            q.len.push_back(ord.len[j]);
-            q.slot.push_back(ord.slot_b[j]);
-        }
+        std::vector<int> row, ulen, uslot;
+        for (int j : grp.slots[g])
+            for (int sq = 0; sq < per; ++sq) {
+                row.push_back(row0[sq * B + ord.slot_b[j]]);
+                q.len.push_back(ord.len[j]);
+                q.slot.push_back(sq * B + ord.slot_b[j]);
+            }
         q.B = q.A = (int)q.len.size();
         q.nmax = q.len[0];
         first += q.B;
         q.o_row = ip.add(row); q.o_len = ip.add(q.len); q.o_slot = ip.add(q.slot);
+        if (per > 1) {
+            for (int j : grp.slots[g]) { ulen.push_back(ord.len[j]); uslot.push_back(ord.slot_b[j]); }
+            q.o_ulen = ip.add(ulen); q.o_uslot = ip.add(uslot);
+        }
     }
     st.plan(ip);
     ip.upload(c.ws, c.m.pinned(), c.s);
-    st.begin(c, ord.nmax + 1, B);
+    st.begin(c, ord.nmax + 1, per * B);
     for (ArGrp& q : gs) {
         const int Mmax = q.B * q.nmax;
         st.init_hist(c, ip, q);
@@ -1117,13 +1128,21 @@ static void adm_run(const Ctx& c, const float* tc, int ld_tc, int tc_rows, const
 // ALL positions of the sequence (prompt prefix + target); codes_out / last_logits receive the target positions.
 // smp (validated by the caller; nullptr = greedy): each step's code is drawn by launch_sample_rows instead of the argmax -
 // the same launch count, utterance b's seed smp->seeds[b], counter = the target position t - P.
+// gamma (host f32 [nseq], validated by the caller; nullptr = one sequence per utterance): ar_run's pair mode.  The head's GEMM
+// covers the 2A rows of the A active pairs and ONE launch_sample_mix_rows (greedy on the mixture without smp) replaces the sampler /
+// arg-max: the code of pair j goes to both histories.  gamma travels with the plan, bit-cast, as the seeds do.
 struct PlmStage {
     mt2_model& m; const float* cond; int ld_c; int nseq; const ArPrefix& pre; const mt2_sampling* smp;
-    int64_t* codes_out; int ostride; float* last_logits; int logit_tmax;
-    int64_t* codes_all = nullptr; int cstride = 0, o_seed = -1;
+    int64_t* codes_out; int ostride; float* last_logits; int logit_tmax; const float* gamma = nullptr;
+    int64_t* codes_all = nullptr; int cstride = 0, o_seed = -1, o_gamma = -1;
     std::vector<float*> logits;      // per group: [B, bins]
     int64_t* codes(const ArGrp& q) const { return codes_all + (size_t)q.first * cstride; }
     void plan(IntPlan& ip) {
+        if (gamma) {
+            std::vector<int> gm(nseq);
+            std::memcpy(gm.data(), gamma, sizeof(float) * (size_t)nseq);
+            o_gamma = ip.add(gm);
+        }
         if (!smp) return;       // (lo, hi) words of every utterance's seed, uploaded once per call with the plan
         std::vector<int> sd(2 * (size_t)nseq);
         for (int b = 0; b < nseq; ++b) {
@@ -1154,7 +1173,12 @@ struct PlmStage {
         p.X = y; p.ldx = d; p.Rx = q.A; p.Cin = d; p.W = m.plm_wpred;
         p.C = lg; p.ldc = NB; p.M = q.A; p.N = NB;
         gemm(cg, p);
-        if (smp)
+        if (gamma)
+            MT2_HIP(launch_sample_mix_rows(lg, NB, NB, codes(q), cstride, n, q.A / 2, !smp, smp ? smp->temperature : 1.0f,
+                                           smp ? smp->top_k : 0, smp ? smp->top_p : 1.0f,
+                                           smp ? reinterpret_cast<const uint32_t*>(ip.dev(o_seed)) : nullptr, ip.dev(q.o_uslot),
+                                           nullptr, t - pre.P, reinterpret_cast<const float*>(ip.dev(o_gamma)), cg.s));
+        else if (smp)
             MT2_HIP(launch_sample_rows(lg, NB, NB, codes(q), cstride, n, q.A, smp->temperature, smp->top_k, smp->top_p,
                                        reinterpret_cast<const uint32_t*>(ip.dev(o_seed)), ip.dev(q.o_slot), nullptr, t - pre.P,
                                        cg.s));
@@ -1167,20 +1191,25 @@ struct PlmStage {
     }
     void finalize(const IntPlan& ip, const ArGrp& q, hipStream_t s) {
         const int nt = q.nmax - pre.P;
+        if (gamma) {      // context A's history (every second row): the generated parts of a pair are identical
+            MT2_HIP(launch_plm_finalize(codes(q), 2 * cstride, ip.dev(q.o_ulen), ip.dev(q.o_uslot), codes_out, ostride, q.B / 2,
+                                        ostride < nt ? ostride : nt, pre.P, s));
+            return;
+        }
         MT2_HIP(launch_plm_finalize(codes(q), cstride, ip.dev(q.o_len), ip.dev(q.o_slot), codes_out, ostride, q.B,
                                     ostride < nt ? ostride : nt, pre.P, s));
     }
 };
 static void plm_run(const Ctx& c, const float* cond, int ld_c, const std::vector<int>& row0, const int* lens, int B,
                     int64_t* codes_out, int ostride, float* last_logits, int logit_tmax,
-                    const ArPrefix& pre = ArPrefix(), const mt2_sampling* smp = nullptr) {
+                    const ArPrefix& pre = ArPrefix(), const mt2_sampling* smp = nullptr, const float* gamma = nullptr) {
     mt2_model& m = c.m;
     const OptGuard pairs_guard(m.opts.ln_pairs, 0);      // the hand-off pays in the ADM only (profiles/r05_opts_ab.txt)
     MT2_REQUIRE(longest(lens, B) <= m.cfg.max_positions, "PLM sequence longer than the positional table");
     MT2_REQUIRE(1024 < m.cfg.plm_bins + 2, "pc_embedding too small for the BOS id 1024");
     for (int b = 0; b < B; ++b) MT2_REQUIRE(lens[b] > pre.P, "prompt prefix is not shorter than the sequence");
-    PlmStage st{m, cond, ld_c, B, pre, smp, codes_out, ostride, last_logits, logit_tmax};
-    ar_run(c, m.plm_enc, row0, lens, B, m.plm_groups, pre, st);
+    PlmStage st{m, cond, ld_c, B, pre, smp, codes_out, ostride, last_logits, logit_tmax, gamma};
+    ar_run(c, m.plm_enc, row0, lens, B, m.plm_groups, pre, st, gamma ? 2 : 1);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -301,6 +301,12 @@ hipError_t launch_argmax_rows(const float* x, int ldx, int N, int64_t* out, int 
 // row is launch_argmax_rows' alone to define).  hipErrorInvalidValue for parameters outside the rule.
 hipError_t launch_sample_rows(const float* x, int ldx, int N, int64_t* out, int ostride, int ooff, int A, float tau, int top_k,
                               float top_p, const uint32_t* seeds, const int* slot, const int* pos, int pos0, hipStream_t s);
+// the same draw on the MIXTURE of two rows (prosody interpolation; rule in sampling.hip): pair j = rows 2j, 2j + 1 of x, utterance
+// b = slot ? slot[j] : j gives the seed and gamma[b] in [0, 1] (device f32); the code goes to out[(2j)*ostride + ooff] AND
+// out[(2j+1)*ostride + ooff].  greedy: arg-max of the mixture at temperature 1 (tau / top_k / top_p / seeds / pos unused).
+hipError_t launch_sample_mix_rows(const float* x, int ldx, int N, int64_t* out, int ostride, int ooff, int A, bool greedy, float tau,
+                                  int top_k, float top_p, const uint32_t* seeds, const int* slot, const int* pos, int pos0,
+                                  const float* gamma, hipStream_t s);
 // EuclideanCodebook.quantize (core_vq.py:175-183) given xe = x @ E^T:
 //   idx[m] = argmax_j -((|x_m|^2 - 2*xe[m,j]) + ee[j]), lowest index on ties
 hipError_t launch_vq_argmin(const float* x, int ldx, int D, const float* xe, int ldxe, const float* ee, int N,

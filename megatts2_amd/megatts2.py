@@ -218,6 +218,29 @@ class MegaPLM:
         cond = torch.cat([prompt_tc_latent.to(tc_latent.device, torch.float32), tc_latent.to(torch.float32)], dim=1)
         return self.native.plm_infer(cond, lens, prefix_codes=prompt_codes.to(tc_latent.device), **kw)
 
+    def infer_interpolated(self, tc_latent, prompt_a, prompt_b, gamma, lens=None, temperature=None, top_k: int = 0,
+                           top_p: float = 1.0, seed=None):
+        """Prosody interpolation (Mega-TTS 2, section 3.3): decode against two prosody prompts at once.  `prompt_a` / `prompt_b`
+        are `(prompt_tc_latent [B, P, tc], prompt_codes int64 [B, P])` pairs as `infer` takes them, of one length P; at every step
+        the two contexts' next-code distributions are mixed as (1 - gamma) * pA + gamma * pB (`gamma` one float or one per
+        utterance in [0, 1]), and the code chosen on the mixture - greedy, or drawn with `temperature` / `top_k` / `top_p` /
+        `seed` as in `infer` - is fed back to both.  Returns the target's codes [B, Tq]."""
+        import torch
+        kw = {}
+        if temperature is not None:
+            kw = dict(sampling=PLMSampling(temperature, top_k, top_p), seeds=seed)
+        elif seed is not None or top_k or top_p != 1.0:
+            raise ValueError("top_k / top_p / seed need a temperature (temperature=None is greedy decoding)")
+        conds, prefixes = [], []
+        for tc_p, codes_p in (prompt_a, prompt_b):
+            if tc_p.shape[1] != codes_p.shape[-1]:
+                raise ValueError("prompt_tc_latent and prompt_codes must have the same length")
+            conds.append(torch.cat([tc_p.to(tc_latent.device, torch.float32), tc_latent.to(torch.float32)], dim=1))
+            prefixes.append(codes_p.to(tc_latent.device))
+        if conds[0].shape != conds[1].shape:
+            raise ValueError("both prompts must have one pooled length P")
+        return self.native.plm_infer_interpolated(conds[0], conds[1], lens, gamma, prefix_a=prefixes[0], prefix_b=prefixes[1], **kw)
+
     def eval(self):
         return self
 
@@ -409,6 +432,58 @@ class Megatts:
                                    vocoder=vocoder, return_aux=True)
         aux = out[2]
         aux["dur"], aux["prompt_codes"] = dur, codes_p[:, :P]
+        return (out[0], out[1], aux) if return_aux else (out[0], out[1])
+
+    def synthesize_prosody_interpolated(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations, rhythm_mels,
+                                        rhythm_phone_tokens, rhythm_durations, gamma, phone_lens=None, mel_lens=None,
+                                        prompt_phone_lens=None, rhythm_mel_lens=None, rhythm_phone_lens=None,
+                                        forced_durations=None, vocoder: bool = False, return_aux: bool = False, sampling=None,
+                                        seeds=None):
+        """Synthesis with the prosody interpolated between two prompts (Mega-TTS 2, section 3.3): the timbre prompt `mels` (with its
+        own phones `prompt_phone_tokens` and alignment `prompt_durations`, as `synthesize_prompt_conditioned` takes them) and a
+        rhythm prompt `rhythm_mels` / `rhythm_phone_tokens` / `rhythm_durations`.  The PLM runs two contexts in lock step
+        (`plm_infer_interpolated`): both see the target's pooled tc_latents under the TIMBRE prompt; context A's prefix is the
+        timbre prompt's pooled tc_latents and VQ-PE codes, context B's the rhythm prompt's (its phones and alignment through MRTE
+        with its own mel, its own VQ-PE codes).  gamma = 0 is `synthesize_prompt_conditioned`; the timbre comes from `mels` at every
+        gamma.  Composed from stage calls like `synthesize_prompt_conditioned_staged`; all prompts of the call must have one pooled
+        length P (ValueError otherwise)."""
+        import torch
+        nat = self.native
+        B = phone_tokens.shape[0]
+        st = self.generator.cfg.vqpe.stride
+
+        def prompt_side(pm, pm_lens, pp, pp_lens, pdur):
+            pm_lens = nat._lens(pm_lens, B, pm.shape[1])
+            pd = np.asarray(pdur.detach().cpu().numpy() if hasattr(pdur, "detach") else pdur, np.int32).reshape(B, -1)
+            ppl = nat._lens(pp_lens, B, pp.shape[1])
+            for b in range(B):
+                if int(pd[b, :ppl[b]].sum()) != int(pm_lens[b]):
+                    raise ValueError("prompt durations must sum to the prompt's mel frames")      # datamodule.py:198 assert
+            tc_p = nat.tc_latent(pp, pm, ppl, pm_lens)
+            cond_p = nat.max_pool_ceil(nat.length_regulate(tc_p, pd, ppl), st, pm_lens)
+            codes_p = nat.vqpe_forward(pm, pm_lens)[1][0]
+            return cond_p, codes_p, -(-pm_lens // st), pm_lens
+
+        cond_a, codes_a, q_a, mel_lens = prompt_side(mels, mel_lens, prompt_phone_tokens, prompt_phone_lens, prompt_durations)
+        cond_b, codes_b, q_b, _ = prompt_side(rhythm_mels, rhythm_mel_lens, rhythm_phone_tokens, rhythm_phone_lens, rhythm_durations)
+        P = int(q_a[0])
+        if (q_a != P).any() or (q_b != P).any():
+            raise ValueError("prosody interpolation needs prompts of one pooled length (pad-free prefix layout)")
+        # target side: ADM, regulation, pooling - under the timbre prompt
+        pl = nat._lens(phone_lens, B, phone_tokens.shape[1])
+        tc = nat.tc_latent(phone_tokens, mels, pl, mel_lens)
+        dur = nat.adm_infer(tc, pl)
+        use = np.asarray(dur.cpu().numpy() if forced_durations is None else forced_durations, np.int32).reshape(B, -1)
+        len_t = np.asarray([int(use[b, :pl[b]].sum()) for b in range(B)], np.int32)
+        cond_t = nat.max_pool_ceil(nat.length_regulate(tc, use, pl), st, len_t)
+        q_t = -(-len_t // st)
+        codes = nat.plm_infer_interpolated(torch.cat([cond_a[:, :P], cond_t], dim=1), torch.cat([cond_b[:, :P], cond_t], dim=1),
+                                           q_t, gamma, prefix_a=codes_a[:, :P], prefix_b=codes_b[:, :P], sampling=sampling,
+                                           seeds=seeds)
+        out = nat.synthesize_batch(phone_tokens, pl, mels, mel_lens, forced_dur=use, forced_codes=codes, run_plm=False,
+                                   vocoder=vocoder, return_aux=True)
+        aux = out[2]
+        aux["dur"], aux["prompt_codes"], aux["rhythm_codes"] = dur, codes_a[:, :P], codes_b[:, :P]
         return (out[0], out[1], aux) if return_aux else (out[0], out[1])
 
     def synthesize_list(self, utterances: Sequence, vocoder: bool = False, sampling=None, seeds=None):

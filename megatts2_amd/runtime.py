@@ -369,6 +369,38 @@ class NativeModel:
                                                              P, int(max_steps), _ptr(codes), _ptr(logits), smp))
         return (codes, logits) if return_logits else codes
 
+    def plm_infer_interpolated(self, cond_a, cond_b, lens, gamma, prefix_a=None, prefix_b=None, return_logits=False,
+                               max_steps: int = 0, sampling=None, seeds=None):
+        """Prosody interpolation (mt2_plm_infer_interpolated): the PLM decoded against two contexts in lock step, every code drawn
+        from the mixture (1 - gamma) * pA + gamma * pB of their next-code distributions and fed back to both.  cond_a / cond_b f32
+        [B, P + Tq, tc] (P prompt rows, then the target rows), prefix_a / prefix_b int64 [B, P] (both or neither), `gamma` one
+        float or one per utterance in [0, 1], `lens` the TARGET lengths.  `sampling` None = greedy on the mixture.  Returns the
+        codes [B, Tq] (and, with return_logits, the logits of both contexts f32 [2, B, Tq, bins])."""
+        import torch
+        if (prefix_a is None) != (prefix_b is None):
+            raise ValueError("prefix_a and prefix_b go together")
+        if cond_a.shape != cond_b.shape:
+            raise ValueError("cond_a and cond_b must have one shape")
+        B = cond_a.shape[0]
+        cond = torch.stack([self._f32(cond_a), self._f32(cond_b)])
+        P, prefix = 0, None
+        if prefix_a is not None:
+            prefix_a, prefix_b = (p.contiguous().to(torch.int64).reshape(B, -1) for p in (prefix_a, prefix_b))
+            if prefix_a.shape != prefix_b.shape:
+                raise ValueError("prefix_a and prefix_b must have one length")
+            P = prefix_a.shape[1]
+            prefix = torch.stack([prefix_a, prefix_b]) if P else None
+        Tq = cond.shape[2] - P
+        assert Tq >= 1, "cond must hold the prompt rows followed by at least one target row"
+        ln = self._lens(lens, B, Tq)
+        gm = sampmod.gamma_array(gamma, B)
+        codes = torch.empty(B, Tq, device=cond.device, dtype=torch.int64)
+        logits = torch.zeros(2, B, Tq, self.plm_cfg.vq_bins, device=cond.device, dtype=torch.float32) if return_logits else None
+        smp, _sd = self._sampling(sampling, seeds, B)      # counter-based draws: the range guard's repeat draws the same codes
+        self._guarded(lambda: self.lib.mt2_plm_infer_interpolated(self.h, _stream(), _ptr(cond), _iptr(ln), Tq, B, _ptr(prefix), P,
+                                                                  _iptr(gm), int(max_steps), _ptr(codes), _ptr(logits), smp))
+        return (codes, logits) if return_logits else codes
+
     def vq_decode(self, codes):
         import torch
         nq, B, Tq = codes.shape
@@ -828,6 +860,31 @@ def op_sample_rows(logits, sampling, seeds, positions):
     s.seeds = C.cast(C.c_void_p(0), C.POINTER(C.c_uint64))      # the op reads seeds_dev only
     _check(lib.mt2_op_sample_rows(_stream(), _ptr(logits), logits.stride(0), N, A, C.byref(s), _ptr(seeds), _ptr(positions),
                                   _ptr(out)))
+    return out
+
+
+def op_sample_mix_rows(logits, sampling, seeds, positions, gamma):
+    """mt2_op_sample_mix_rows: the interpolated draw on the A row pairs of `logits` f32 [2 A, N] (device; pair j = rows 2j,
+    2j + 1) with per-pair seeds (int64 / uint64 values [A]), target positions (int32 [A]) and gamma (f32 [A]), all device tensors
+    -> int64 [2 A] (the pair's code at 2j and 2j + 1).  `sampling` None = greedy on the mixture (seeds / positions may be None)."""
+    import torch
+    lib = load_library()
+    A, N = logits.shape[0] // 2, logits.shape[1]
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == 2 * A
+    gamma = gamma.contiguous().to(torch.float32)
+    assert gamma.shape == (A,)
+    s = None
+    if sampling is not None:
+        seeds = seeds.contiguous().to(torch.int64)
+        positions = positions.contiguous().to(torch.int32)
+        assert seeds.shape == (A,) and positions.shape == (A,)
+        s = sampmod.as_sampling(sampling).to_c(np.zeros(1, np.uint64))
+        s.seeds = C.cast(C.c_void_p(0), C.POINTER(C.c_uint64))      # the op reads seeds_dev only
+    else:
+        seeds = positions = None
+    out = torch.empty(2 * A, device=logits.device, dtype=torch.int64)
+    _check(lib.mt2_op_sample_mix_rows(_stream(), _ptr(logits), logits.stride(0), N, A, C.byref(s) if s is not None else None,
+                                      _ptr(seeds), _ptr(positions), _ptr(gamma), _ptr(out)))
     return out
 
 

@@ -69,6 +69,22 @@ def seed_array(seeds: Union[None, int, Sequence[int], np.ndarray], B: int) -> np
     return np.ascontiguousarray([int(v) & 0xFFFFFFFFFFFFFFFF for v in a.tolist()], np.uint64)
 
 
+def gamma_array(gamma, B: int) -> np.ndarray:
+    """float32 [B] interpolation weights of `plm_infer_interpolated`: one float for every utterance or one per utterance, each
+    in [0, 1] (0 = context A's prosody alone, 1 = context B's)."""
+    if hasattr(gamma, "detach"):
+        gamma = gamma.detach().cpu().numpy()
+    a = np.asarray(gamma, np.float64)
+    if a.ndim == 0:
+        a = np.full(B, float(a))
+    a = a.reshape(-1)
+    if a.size != B:
+        raise ValueError(f"{a.size} gamma values for {B} utterances")
+    if not bool(np.all((a >= 0.0) & (a <= 1.0))):       # (False for NaN)
+        raise ValueError(f"gamma must be in [0, 1], got {a.tolist()!r}")
+    return np.ascontiguousarray(a, np.float32)
+
+
 def philox4x32_10(ctr: Sequence[int], key: Sequence[int]):
     """Philox4x32-10 (Salmon et al., SC'11) on one counter block: 4 x u32 counter, 2 x u32 key -> 4 x u32."""
     c0, c1, c2, c3 = (int(v) & _MASK32 for v in ctr)

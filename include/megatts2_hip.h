@@ -337,6 +337,42 @@ int mt2_op_gemm_x3h(void* stream, const float* X, int ldx, int Rx, int shift0, i
  * [rows][2 * ceil32(row_len)] uint16 (fp16 bit patterns; per row and 32-k chunk 32 hi values, then 32 lo values; K zero-padded to a
  * multiple of 32), inv [rows] */
 int mt2_x3h_split(const float* W, long long rows, long long row_len, uint16_t* planes, float* inv);
+/* host helper (no device): how a launch with `groups` groups, weight pointer `w_off` elements into a buffer that was split as
+ * [rows][row_len] (mt2_x3h_split), row stride ldw and group stride strideW walks that buffer's fp16 planes - the rule the model
+ * applies to every launch (csrc/x3h_planes.h, x3h_group_planes).  *form = 0: the launch cannot use the planes (the other outputs are
+ * 0); 1 "whole": the groups step through whole matrices, rows and scales move together; 2 "slices": the groups are K slices of the
+ * same rows and share their scales.  *wh_off: byte offset of Wh in the plane buffer, *wh_ldb: bytes per plane row, *wh_gstride:
+ * bytes between groups, *inv_off: element offset of wh_inv, *wh_inv_stride: scales between groups. */
+int mt2_x3h_group_planes(long long row_len, long long w_off, long long ldw, long long strideW, long long groups, int32_t* form,
+                         long long* wh_off, long long* wh_ldb, long long* wh_gstride, long long* inv_off, long long* wh_inv_stride);
+/* Kernel tests of GROUPED launches (grid.z = groups; tests/test_gpu_gemm_groups.py): one launch of the engine with every operand,
+ * stride and leading dimension of its parameter block (csrc/mt2_kernels.h, GemmP) given explicitly - nothing is defaulted and
+ * force_cfg carries no offsets.  K = taps * Cin.  Group g reads X + g * strideX, W + g * strideW (W3 likewise, in bf16 elements, its
+ * three planes w3_plane elements apart), Wh + g * wh_gstride BYTES, wh_inv + g * wh_inv_stride, bias + g * strideB, R + g * strideR
+ * and writes C + g * strideC; a stride of 0 shares the operand.  One group of a grouped launch is the same descriptor with
+ * groups = 1 and the pointers moved by the strides.  W3 / Wh / wh_inv / rowbase / bias / R / valid / range_flag may be NULL;
+ * a_planes = 1: X holds fp16 planes.  range_flag: device int32, |= 1 when an fp16-pipe launch converted an activation with
+ * |a| >= 65504.  cfg_out (host, may be NULL): the configuration index the routing chose (-1: rejected before a choice).
+ * struct_bytes = sizeof(mt2_gemm_desc) as the caller sees it: a mirror of the struct laid out differently is an error, not a launch. */
+typedef struct mt2_gemm_desc {
+    int32_t struct_bytes;
+    const float* X; long long strideX; int32_t ldx, Rx;
+    const int32_t* rowbase; int32_t a_mul, shift0, taps, dil, Cin;
+    const float* W; long long strideW; int32_t ldw;
+    const void* W3; long long w3_plane;
+    const void* Wh; const float* wh_inv; long long wh_ldb, wh_gstride, wh_inv_stride;
+    int32_t a_planes;
+    const float* bias; long long strideB;
+    const float* R; long long strideR; int32_t ldr;
+    const int32_t* valid;
+    float* C; long long strideC; int32_t ldc;
+    int32_t M, N, groups;
+    int32_t pro_act; float pro_slope; int32_t epi_act; float out_scale;
+    int32_t force_cfg;
+    int32_t* range_flag;
+    int32_t* cfg_out;
+} mt2_gemm_desc;
+int mt2_op_gemm_grouped(void* stream, const mt2_gemm_desc* d);
 /* Range guard of the fp16-pipe kernels inside a model handle (option "x3h", default 15): waits for the handle's last call, then
  * *tripped = 1 (and the guard is re-armed) when that call converted an activation outside the fp16 range - its outputs are then
  * to be discarded and the call repeated with mt2_set_option(m, "x3h", 0) (the bf16 six-product form has f32's exponent range). */

@@ -1078,6 +1078,44 @@ int mt2_x3h_split(const float* W, long long rows, long long row_len, uint16_t* p
     x3h_split_rows(W, (size_t)rows, (size_t)row_len, planes, inv);
     MT2_API_END
 }
+// host helper: the plane-stride rule of the model's launches (x3h_planes.h, x3h_group_planes; model_stages.hip attach_planes calls the same function)
+int mt2_x3h_group_planes(long long row_len, long long w_off, long long ldw, long long strideW, long long groups, int32_t* form,
+                         long long* wh_off, long long* wh_ldb, long long* wh_gstride, long long* inv_off, long long* wh_inv_stride) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(row_len > 0 && w_off >= 0 && groups >= 1 && form && wh_off && wh_ldb && wh_gstride && inv_off && wh_inv_stride,
+                "bad arguments");
+    const X3hGroupPlanes g = x3h_group_planes(row_len, w_off, ldw, strideW, groups);
+    *form = g.form; *wh_off = g.wh_off; *wh_ldb = g.wh_ldb; *wh_gstride = g.wh_gstride; *inv_off = g.inv_off;
+    *wh_inv_stride = g.wh_inv_stride;
+    MT2_API_END
+}
+
+// Kernel tests of grouped launches: every field of GemmP a caller of the model sets, given explicitly (no defaults, no offsets on
+// force_cfg).  The per-call EngineOpts of mt2_op_gemm.
+int mt2_op_gemm_grouped(void* stream, const mt2_gemm_desc* d) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(d != nullptr, "null descriptor");
+    MT2_REQUIRE(d->struct_bytes == (int32_t)sizeof(mt2_gemm_desc), "descriptor size mismatch");
+    if (d->cfg_out) *d->cfg_out = -1;
+    GemmP p{};
+    p.X = d->X; p.strideX = d->strideX; p.ldx = d->ldx; p.Rx = d->Rx;
+    p.rowbase = d->rowbase; p.a_mul = d->a_mul; p.shift0 = d->shift0; p.taps = d->taps; p.dil = d->dil; p.Cin = d->Cin;
+    p.W = d->W; p.strideW = d->strideW; p.ldw = d->ldw;
+    p.W3 = d->W3; p.w3_plane = d->w3_plane;
+    p.Wh = d->Wh; p.wh_inv = d->wh_inv; p.wh_ldb = d->wh_ldb; p.wh_gstride = d->wh_gstride; p.wh_inv_stride = d->wh_inv_stride;
+    p.a_planes = d->a_planes;
+    p.bias = d->bias; p.strideB = d->strideB; p.R = d->R; p.strideR = d->strideR; p.ldr = d->ldr; p.valid = d->valid;
+    p.C = d->C; p.strideC = d->strideC; p.ldc = d->ldc;
+    p.M = d->M; p.N = d->N; p.K = d->taps * d->Cin; p.groups = d->groups;
+    p.pro_act = d->pro_act; p.pro_slope = d->pro_slope; p.epi_act = d->epi_act; p.out_scale = d->out_scale;
+    MT2_REQUIRE(p.X && p.W && p.C && p.taps >= 1 && p.dil >= 1 && p.a_mul >= 1 && p.groups >= 1, "bad arguments");
+    EngineOpts o;            // per call: no state is shared with any handle or thread
+    o.force_cfg = d->force_cfg;
+    o.x3h_flag = d->range_flag;
+    if (d->cfg_out) *d->cfg_out = gemm_route(p, o).cfg;
+    MT2_HIP(launch_gemm(p, (hipStream_t)stream, &o));
+    MT2_API_END
+}
 
 // Kernel tests of the GEMM -> GEMM LayerNorm hand-off (round 5; GemmP::stat_out / ln_stat): ONE linear launch on an x6 tile.
 // stat_out != nullptr: the epilogue also writes (mean, M2) pairs of the final C rows ([M][*stat_nt][2]; *stat_nt = 0 when the

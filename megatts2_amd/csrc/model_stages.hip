@@ -78,20 +78,16 @@ static void attach_planes(const mt2_model& m, GemmP& p) {
         p.W3 = it->p3 + (p.W - it->base);
         p.w3_plane = (long long)it->n;
         // the fp16 planes carry one scale per weight row: usable when this launch walks the buffer with the rows it was split by
-        // (K slices of a row - split-K - share the row's scale)
+        // (K slices of a row - split-K - share the row's scale): the rule is x3h_group_planes (x3h_planes.h), which the kernel tests
+        // run as well
         const int ldw = p.ldw ? p.ldw : (p.taps > 0 ? p.taps : 1) * p.Cin;
-        const long long rl = (long long)it->row_len, groups = p.groups > 0 ? p.groups : 1;
-        const long long row0 = (long long)((size_t)(p.W - it->base) / it->row_len), col0 = (long long)((size_t)(p.W - it->base) % it->row_len);
-        const long long ldb = 4ll * (long long)x3h_padded_k(it->row_len);      // bytes per chunk-interleaved row (x3h_planes.h)
-        // groups either step through whole matrices (the parallel branches of a conv stack: strideW a multiple of the row length)
-        // or through K slices of the SAME rows (split-K: every slice inside one row, shared scales); a launch starts on a chunk
-        const bool whole = p.strideW % rl == 0, slices = !whole && col0 + p.strideW * groups <= rl && p.strideW % 32 == 0;
-        if (it->ph && ldw == (int)it->row_len && col0 % 32 == 0 && (whole || slices || groups == 1)) {
-            p.Wh = reinterpret_cast<const char*>(it->ph) + row0 * ldb + (col0 / 32) * 128;
-            p.wh_ldb = ldb;
-            p.wh_gstride = whole ? (p.strideW / rl) * ldb : (p.strideW / 32) * 128;
-            p.wh_inv = it->inv + row0;
-            p.wh_inv_stride = whole ? p.strideW / rl : 0;
+        const X3hGroupPlanes g = x3h_group_planes((long long)it->row_len, (long long)(p.W - it->base), ldw, p.strideW, p.groups);
+        if (it->ph && g.form != X3H_NO_PLANES) {
+            p.Wh = reinterpret_cast<const char*>(it->ph) + g.wh_off;
+            p.wh_ldb = g.wh_ldb;
+            p.wh_gstride = g.wh_gstride;
+            p.wh_inv = it->inv + g.inv_off;
+            p.wh_inv_stride = g.wh_inv_stride;
         }
     }
 }

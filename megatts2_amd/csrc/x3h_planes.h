@@ -85,4 +85,39 @@ inline void x3h_split_rows(const float* w, size_t rows, size_t row_len, uint16_t
     }
 }
 
+// How a GEMM launch (GemmP: W, ldw, strideW, groups) walks the planes of the buffer its W points into.  The planes carry ONE scale per
+// row of the matrix they were split by ([rows][row_len]), so they serve a launch that walks the buffer with those rows, starting on a
+// 32-k chunk: `w_off` = element offset of W in the buffer (row0 = w_off / row_len, col0 = w_off % row_len), ldw == row_len,
+// col0 % 32 == 0, and the groups either
+//   WHOLE  - step through whole matrices (the parallel branches of a conv stack): strideW a multiple of the row length (0 included:
+//            shared weights) - rows and scales move by strideW / row_len per group; or
+//   SLICES - step through K slices of the SAME rows (split-K): every slice inside one row, strideW % 32 == 0 - the planes move by
+//            strideW / 32 blocks of 128 bytes, the slices share the row's scale (wh_inv_stride = 0);
+// a single group needs neither.  form == X3H_NO_PLANES: the launch cannot use the fp16 planes (the other fields are 0).
+enum X3hPlaneForm : int { X3H_NO_PLANES = 0, X3H_WHOLE = 1, X3H_SLICES = 2 };
+struct X3hGroupPlanes {
+    int form;
+    long long wh_off;         // BYTE offset of GemmP::Wh in the plane buffer
+    long long wh_ldb;         // bytes per chunk-interleaved row
+    long long wh_gstride;     // bytes between groups
+    long long inv_off;        // element offset of GemmP::wh_inv in the scale vector (= row0)
+    long long wh_inv_stride;  // scales between groups
+};
+inline X3hGroupPlanes x3h_group_planes(long long row_len, long long w_off, long long ldw, long long strideW, long long groups) {
+    X3hGroupPlanes r{X3H_NO_PLANES, 0, 0, 0, 0, 0};
+    if (row_len <= 0 || w_off < 0) return r;
+    if (groups < 1) groups = 1;
+    const long long row0 = w_off / row_len, col0 = w_off % row_len;
+    const long long ldb = 4ll * (long long)x3h_padded_k((size_t)row_len);
+    const bool whole = strideW % row_len == 0, slices = !whole && col0 + strideW * groups <= row_len && strideW % 32 == 0;
+    if (ldw != row_len || col0 % 32 != 0 || !(whole || slices || groups == 1)) return r;
+    r.form = whole ? X3H_WHOLE : X3H_SLICES;
+    r.wh_off = row0 * ldb + (col0 / 32) * 128;
+    r.wh_ldb = ldb;
+    r.wh_gstride = whole ? (strideW / row_len) * ldb : (strideW / 32) * 128;
+    r.inv_off = row0;
+    r.wh_inv_stride = whole ? strideW / row_len : 0;
+    return r;
+}
+
 }  // namespace mt2

@@ -22,6 +22,7 @@ MAX_POSITIONS = 8192       # rows of the sine tables (the reference builds 4000 
 
 MT2_RUN_PLM, MT2_RUN_VOCODER, MT2_SKIP_ADM, MT2_PROMPT_VQPE = 1, 2, 4, 8
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
+ACT_LOGCLAMP = 4          # epilogue only: log(max(v, pro_slope))
 
 
 class NativeError(RuntimeError):
@@ -958,6 +959,102 @@ def op_row_sqnorm(E, D, ee, N): op_row("row_sqnorm", E, D, ee, N)
 def op_codebook_rows(E, codes, codemap, out, ldo, Dq, R, bins): op_row("codebook_rows", E, codes, codemap, out, ldo, Dq, R, bins)
 def op_reflect_pad_blocks(wav, wstride, blk_b, blk_t, len_, hop, pad, out, R): op_row("reflect_pad_blocks", wav, wstride, blk_b, blk_t, len_, hop, pad, out, R)
 def op_magnitude(spec, lds_, F, out, ldo, M): op_row("magnitude", spec, lds_, F, out, ldo, M)
+
+
+# ---- test-only entry into GROUPED launches of the GEMM engine (tests/test_gpu_gemm_groups.py, tests/test_gemm_groups_host.py): the
+# descriptor mirror, the model's plane-stride rule, a weight buffer in every operand form, and the launch itself
+
+class MT2GemmDesc(C.Structure):
+    """ctypes mirror of mt2_gemm_desc (include/megatts2_hip.h): one engine launch with every operand and stride explicit."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("X", C.c_void_p), ("strideX", C.c_longlong), ("ldx", C.c_int32), ("Rx", C.c_int32),
+        ("rowbase", C.c_void_p), ("a_mul", C.c_int32), ("shift0", C.c_int32), ("taps", C.c_int32), ("dil", C.c_int32),
+        ("Cin", C.c_int32),
+        ("W", C.c_void_p), ("strideW", C.c_longlong), ("ldw", C.c_int32),
+        ("W3", C.c_void_p), ("w3_plane", C.c_longlong),
+        ("Wh", C.c_void_p), ("wh_inv", C.c_void_p), ("wh_ldb", C.c_longlong), ("wh_gstride", C.c_longlong),
+        ("wh_inv_stride", C.c_longlong),
+        ("a_planes", C.c_int32),
+        ("bias", C.c_void_p), ("strideB", C.c_longlong),
+        ("R", C.c_void_p), ("strideR", C.c_longlong), ("ldr", C.c_int32),
+        ("valid", C.c_void_p),
+        ("C", C.c_void_p), ("strideC", C.c_longlong), ("ldc", C.c_int32),
+        ("M", C.c_int32), ("N", C.c_int32), ("groups", C.c_int32),
+        ("pro_act", C.c_int32), ("pro_slope", C.c_float), ("epi_act", C.c_int32), ("out_scale", C.c_float),
+        ("force_cfg", C.c_int32),
+        ("range_flag", C.c_void_p),
+        ("cfg_out", C.POINTER(C.c_int32)),
+    ]
+
+
+def x3h_group_planes(row_len, w_off, ldw, strideW, groups):
+    """mt2_x3h_group_planes (host only): how a launch walks the fp16 planes of a buffer split as [rows][row_len] - the rule the model
+    applies to its own launches.  -> None (no planes) or a dict: form ("whole" / "slices"), wh_off (bytes), wh_ldb, wh_gstride (bytes),
+    inv_off (elements), wh_inv_stride."""
+    lib = load_library()
+    form = C.c_int32(0)
+    v = [C.c_longlong(0) for _ in range(5)]
+    _check(lib.mt2_x3h_group_planes(C.c_longlong(row_len), C.c_longlong(w_off), C.c_longlong(ldw), C.c_longlong(strideW),
+                                    C.c_longlong(groups), C.byref(form), *[C.byref(x) for x in v]))
+    if form.value == 0:
+        return None
+    return {"form": {1: "whole", 2: "slices"}[form.value], "wh_off": v[0].value, "wh_ldb": v[1].value, "wh_gstride": v[2].value,
+            "inv_off": v[3].value, "wh_inv_stride": v[4].value}
+
+
+class GemmWeights:
+    """Test helper: a weight buffer [rows, row_len] on the device in every operand form of the engine, as the model loader keeps it: f32, three
+    bf16 planes (plane stride = the whole buffer) and two fp16 planes with one scale per row."""
+
+    def __init__(self, W, device="cuda"):
+        W = W.detach().to("cpu").contiguous()
+        assert W.dim() == 2
+        self.rows, self.row_len = W.shape
+        self.f32 = W.to(device)
+        self.w3 = split_bf16x3(W).to(device)
+        ph, inv = split_f16x2_rows(W)
+        self.ph, self.inv = ph.to(device), inv.to(device)
+
+
+def op_gemm_grouped(X, wts, out, *, M, N, Cin, ldx, Rx, ldw, ldc, groups=1, strideX=0, strideW=0, strideC=0, w_off=0, taps=1, dil=1,
+                    a_mul=1, shift0=0, rowbase=None, bias=None, strideB=0, R=None, strideR=0, ldr=0, valid=None, pro_act=ACT_NONE,
+                    pro_slope=0.0, epi_act=ACT_NONE, out_scale=1.0, force_cfg=-1, x6=True, x3h=True, a_planes=0, wh_gstride=None,
+                    flag=None):
+    """mt2_op_gemm_grouped: one launch of the engine with `groups` groups.  X / out / bias / R: device tensors whose data pointer is
+    the operand of group 0 (a view into a larger buffer moves it); wts: GemmWeights, the launch's W starts w_off elements into it.
+    x6 / x3h: attach the bf16 / fp16 planes - the fp16 strides come from x3h_group_planes, i.e. from the model's own rule (no planes
+    when it says so); wh_gstride overrides its group stride (rejection tests).  flag: device int32 range-guard word.  Writes `out`
+    in place and returns the configuration index the routing chose."""
+    lib = load_library()
+    d = MT2GemmDesc()
+    d.struct_bytes = C.sizeof(MT2GemmDesc)
+    d.X, d.strideX, d.ldx, d.Rx = X.data_ptr(), strideX, ldx, Rx
+    d.rowbase = rowbase.data_ptr() if rowbase is not None else None
+    d.a_mul, d.shift0, d.taps, d.dil, d.Cin = a_mul, shift0, taps, dil, Cin
+    d.W, d.strideW, d.ldw = wts.f32.data_ptr() + 4 * w_off, strideW, ldw
+    if x6:
+        d.W3, d.w3_plane = wts.w3.data_ptr() + 2 * w_off, wts.rows * wts.row_len
+    if x3h:
+        g = x3h_group_planes(wts.row_len, w_off, ldw, strideW, groups)
+        if g is not None:
+            d.Wh, d.wh_inv = wts.ph.data_ptr() + g["wh_off"], wts.inv.data_ptr() + 4 * g["inv_off"]
+            d.wh_ldb, d.wh_gstride, d.wh_inv_stride = g["wh_ldb"], g["wh_gstride"], g["wh_inv_stride"]
+            if wh_gstride is not None:
+                d.wh_gstride = wh_gstride
+    d.a_planes = a_planes
+    d.bias, d.strideB = (bias.data_ptr() if bias is not None else None), strideB
+    d.R, d.strideR, d.ldr = (R.data_ptr() if R is not None else None), strideR, ldr
+    d.valid = valid.data_ptr() if valid is not None else None
+    d.C, d.strideC, d.ldc = out.data_ptr(), strideC, ldc
+    d.M, d.N, d.groups = M, N, groups
+    d.pro_act, d.pro_slope, d.epi_act, d.out_scale = pro_act, pro_slope, epi_act, out_scale
+    d.force_cfg = force_cfg
+    d.range_flag = flag.data_ptr() if flag is not None else None
+    cfg = C.c_int32(-1)
+    d.cfg_out = C.pointer(cfg)
+    _check(lib.mt2_op_gemm_grouped(_stream(), C.byref(d)))
+    return cfg.value
 
 
 def op_attention(Q, K, V, q_start, q_len, kv_start, kv_len, H, D, scale, lds_min_qlen=-1, lds_waves=0, out=None, x6_min_qlen=-1):

@@ -23,7 +23,7 @@ def main() -> None:
         ap.add_argument(f"--{k}-ckpt")
         ap.add_argument(f"--{k}-config")
     ap.add_argument("--symbol-table")
-    ap.add_argument("--wavs-dir", required=True)
+    ap.add_argument("--wavs-dir", required=True, help="prompt *.wav files, any sample rate (resampled to 16 kHz on the GPU)")
     ap.add_argument("--text")
     ap.add_argument("--phones", help="comma separated phone token ids (bypasses the G2P)")
     ap.add_argument("--out", default="test.wav")

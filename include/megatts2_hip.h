@@ -223,6 +223,34 @@ typedef struct mt2_audio_config {
 int mt2_mel_spectrogram(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* wav,
                         const int32_t* lens /*host*/, int L_max, int B, float* mel, int T_max);
 
+/* ---- prompt audio at any sample rate (models/megatts2.py:335-336: `librosa.load(wav, sr=16000)`, `librosa.util.normalize`).
+ * librosa's soxr resampler is not reproduced (parity unpinned); the rule is the Kaiser-windowed-sinc polyphase filter in the form
+ * torchaudio documents for resample(..., resampling_method="sinc_interp_kaiser") with its "kaiser_best" constants (lpw = 64 zero
+ * crossings, rolloff = 0.9475937167399596, beta = 14.769656459379492), table arithmetic in double, rounded once to f32:
+ *   g = gcd(sr_in, sr_out), o = sr_in / g, n = sr_out / g, base = min(o, n) * rolloff, width = ceil(lpw * o / base), taps = 2 width + o
+ *   t[p][k] = clamp((-p / n + (k - width) / o) * base, -lpw, +lpw)
+ *   h[p][k] = sinc(pi t) * I0(beta * sqrt(1 - (t / lpw)^2)) / I0(beta) * (base / o)
+ *   y[i * n + p] = sum_{k < taps} h[p][k] * x[i * o - width + k]   (x = 0 outside [0, L); one f32 fma chain, k ascending)
+ *   L_out = ceil(n * L / o)
+ * so a sample depends on its utterance and the ratio alone, never on the batch around it.  Refused (error, never a clamp):
+ * sr_in <= 0 or sr_out <= 0; sr_in == sr_out (nothing to do: do not call); a reduced ratio whose table n * taps * 4 bytes exceeds
+ * 8 MiB (16001 -> 16000 would need about 8 GB) or whose taps exceed the kernel's 64 KiB window of on-chip memory; lens[b] < 1 or
+ * > L_max; Lout_max < max_b L_out_b.  A refused call launches nothing and leaves `out` untouched. */
+#define MT2_RESAMPLE_NORMALIZE 1 /* models/megatts2.py:336: y / max |y| per utterance in f32 (unchanged while the peak is below FLT_MIN) */
+/* models/megatts2.py:335  the rule's integers for one pair of rates and one length; host only, no HIP call (outputs may be NULL) */
+int mt2_resample_query(int sr_in, int sr_out, long long L, long long* L_out, int* o, int* n, int* taps);
+/* models/megatts2.py:335  the f32 filter the device applies; host only, no HIP call */
+int mt2_resample_table(int sr_in, int sr_out, float* table /*host, [n][taps] phase-major*/);
+/* models/megatts2.py:335-336  wav f32 [B, L_max] (device) at sr_in -> out f32 [B, Lout_max] (device) at sr_out, zeros in
+ * [L_out_b, Lout_max); samples beyond lens[b] are never read.  The filter table of a ratio is built and uploaded on the first call
+ * that uses it (a synchronous copy) and kept in the handle; `m` may be a bare handle (no weights), as for mt2_mel_spectrogram. */
+int mt2_resample(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                 int sr_in, int sr_out, int flags, float* out /*[B, Lout_max]*/, int Lout_max, int32_t* out_lens /*host, may be NULL*/);
+/* models/megatts2.py:336  the normalisation alone, for audio that already has the model's rate: out[b, j] = wav[b, j] / max_j |wav[b, j]|
+ * for j < lens[b] (same rule as MT2_RESAMPLE_NORMALIZE, same kernels), zeros in [lens[b], L_max).  out f32 [B, L_max] may be wav. */
+int mt2_peak_normalize(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                       float* out);
+
 /* ---- the whole of Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) for a batch,
  * activations staying in the packed internal layout between stages.
  *   forced_dur   (host, optional) int32 [B, Np_max]: replaces the ADM's integer durations AFTER the ADM

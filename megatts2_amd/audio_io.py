@@ -2,9 +2,11 @@
 
 * WAV in:  what `Megatts.forward` does with librosa (reference models/megatts2.py:333-336:
   `librosa.load(wav, sr=16000)` -> mono float32, then `librosa.util.normalize`), without librosa:
-  RIFF PCM 8/16/24/32-bit and IEEE float32, channels averaged, peak-normalised.  A file at another
-  sample rate is rejected unless `resample=True` (polyphase; librosa's soxr resampler is not
-  reproduced - parity unpinned for resampled input).
+  RIFF PCM 8/16/24/32-bit and IEEE float32, channels averaged, peak-normalised.  Resampling lives on the
+  GPU: `Megatts.forward` sends a file at another sample rate through `runtime.MelFrontEnd.from_audio`
+  (csrc/resample.hip).  `load_audio` itself still rejects such a file unless `resample=True`, which keeps
+  scipy's host polyphase filter for callers without a GPU - a different filter from the GPU's; librosa's
+  soxr resampler is reproduced by neither (parity unpinned for resampled input).
 * WAV out: `torchaudio.save('test.wav', audio, 16000)` (models/megatts2.py:375) writes 32-bit float PCM
   for a float32 tensor; `write_wav` does the same by default, or 16-bit PCM with clipping.
 * Packed weights: the three Lightning checkpoints are pickles read through `torch.load`

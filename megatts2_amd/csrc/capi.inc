@@ -668,6 +668,50 @@ int mt2_mel_spectrogram(mt2_model* m, void* stream, const mt2_audio_config* ac, 
     MT2_API_END
 }
 
+// models/megatts2.py:335  librosa.load(wav, sr=16000): the length / ratio rule of the resampler, without a HIP call
+int mt2_resample_query(int sr_in, int sr_out, long long L, long long* L_out, int* o, int* n, int* taps) {
+    MT2_API_BEGIN
+    ResampleRule r{};
+    if (const char* why = resample_rule(sr_in, sr_out, &r)) throw Error(std::string("mt2_resample_query: ") + why);
+    MT2_REQUIRE(L >= 0 && L <= INT_MAX, "L outside [0, 2^31)");
+    if (L_out) *L_out = resample_out_len(r, L);
+    if (o) *o = r.o;
+    if (n) *n = r.n;
+    if (taps) *taps = r.taps;
+    MT2_API_END
+}
+
+// models/megatts2.py:335  the filter the device applies, phase-major [n][taps] (host only: lets a test pin it without a GPU)
+int mt2_resample_table(int sr_in, int sr_out, float* table) {
+    MT2_API_BEGIN
+    ResampleRule r{};
+    if (const char* why = resample_rule(sr_in, sr_out, &r)) throw Error(std::string("mt2_resample_table: ") + why);
+    MT2_REQUIRE(table != nullptr, "null table");
+    resample_table(r, table, false);
+    MT2_API_END
+}
+
+// models/megatts2.py:335-336  librosa.load(wav, sr=16000) [+ librosa.util.normalize with MT2_RESAMPLE_NORMALIZE] for a ragged batch
+int mt2_resample(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sr_in, int sr_out, int flags,
+                 float* out, int Lout_max, int32_t* out_lens) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr && B >= 1 && L_max >= 1 && Lout_max >= 1, "bad arguments");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    resample_run(c, wav, lens, L_max, B, sr_in, sr_out, flags, out, Lout_max, out_lens);
+    MT2_API_END
+}
+
+// models/megatts2.py:336  librosa.util.normalize alone (audio already at the model's rate)
+int mt2_peak_normalize(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, float* out) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr && B >= 1 && L_max >= 1, "bad arguments");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    peak_normalize_run(c, wav, lens, L_max, B, out);
+    MT2_API_END
+}
+
 // :361-368 [+370]  zq = vq.decode(p_codes) repeated x8, cat([tc_latent_expand, zq]), decoder, optional vocoder - the part of
 // Megatts.forward behind the PLM, shared by mt2_synthesize_batch and mt2_synthesize_prompt_conditioned.  xdec: [D.R, H + Dq]
 // rows whose first H columns already hold the length-regulated tc_latents.

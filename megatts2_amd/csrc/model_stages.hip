@@ -1550,6 +1550,73 @@ static void mel_spectrogram_run(const Ctx& c, const mt2_audio_config& ac, const 
     MT2_HIP(launch_unpack_rows(mrows, ac.n_mels, ac.n_mels, T_max, 0, ip.dev(o_map), mel, Fr, c.s));
 }
 
+// ---------------------------------------------------------------------------------------------------
+// prompt audio at any sample rate (models/megatts2.py:335-336: librosa.load(wav, sr=16000), librosa.util.normalize):
+// the polyphase resampler of resample.hip and the per-utterance peak normalisation, in front of the mel front-end.
+
+static const float* resample_prepare(mt2_model& m, const ResampleRule& r) {
+    float*& d = m.rs_tables[{r.o, r.n}];
+    if (d) return d;
+    std::vector<float> h((size_t)r.n * r.taps);
+    resample_table(r, h.data(), true);
+    float* t = nullptr;
+    MT2_HIP(hipMalloc(reinterpret_cast<void**>(&t), h.size() * sizeof(float)));
+    m.dev_allocs.push_back(t);
+    MT2_HIP(hipMemcpy(t, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return d = t;
+}
+
+static void resample_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int sr_in, int sr_out, int flags,
+                         float* out, int Lout_max, int32_t* out_lens) {
+    // everything is checked before the first launch: a refused call leaves `out` as it was
+    ResampleRule r{};
+    if (const char* why = resample_rule(sr_in, sr_out, &r)) throw Error(std::string("mt2_resample: ") + why);
+    MT2_REQUIRE((flags & ~MT2_RESAMPLE_NORMALIZE) == 0, "unknown resample flag");
+    MT2_REQUIRE(wav != nullptr && out != nullptr && lens != nullptr && ((uintptr_t)wav & 3) == 0, "bad buffers");
+    std::vector<int> len(lens, lens + B), lout(B), tile_b, tile_i0;
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
+        const long long lo = resample_out_len(r, lens[b]);
+        MT2_REQUIRE(lo <= Lout_max, "Lout_max smaller than ceil(n * L / o)");
+        lout[b] = (int)lo;
+    }
+    for (int b = 0; b < B; ++b)
+        for (long long i0 = 0; i0 * r.n < Lout_max; i0 += r.tb) { tile_b.push_back(b); tile_i0.push_back((int)i0); }
+    ResampleP p{};
+    p.table = resample_prepare(c.m, r);
+    IntPlan ip;
+    const int o_b = ip.add(tile_b), o_i0 = ip.add(tile_i0), o_len = ip.add(len), o_lout = ip.add(lout);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    p.wav = wav; p.L_max = L_max; p.r = r;
+    p.tile_b = ip.dev(o_b); p.tile_i0 = ip.dev(o_i0); p.tiles = (int)tile_b.size();
+    p.len = ip.dev(o_len); p.lout = ip.dev(o_lout);
+    p.out = out; p.Lout_max = Lout_max;
+    if (flags & MT2_RESAMPLE_NORMALIZE) {
+        p.peak = c.ws.get<unsigned>(B);
+        MT2_HIP(hipMemsetAsync(p.peak, 0, sizeof(unsigned) * B, c.s));
+    }
+    MT2_HIP(launch_resample_rows(p, c.s));
+    if (p.peak) MT2_HIP(launch_scale_rows(out, Lout_max, p.lout, p.peak, out, Lout_max, Lout_max, B, c.s));
+    if (out_lens) std::copy(lout.begin(), lout.end(), out_lens);
+}
+
+// out[b, :] = wav[b, :] / max |wav[b, :len[b]]| (audio_io.normalize), zeros beyond len[b]
+static void peak_normalize_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, float* out) {
+    MT2_REQUIRE(wav != nullptr && out != nullptr && lens != nullptr, "bad buffers");
+    int mx = 0;
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
+        mx = std::max(mx, lens[b]);
+    }
+    IntPlan ip;
+    const int o_len = ip.add(std::vector<int>(lens, lens + B));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    unsigned* peak = c.ws.get<unsigned>(B);
+    MT2_HIP(hipMemsetAsync(peak, 0, sizeof(unsigned) * B, c.s));
+    MT2_HIP(launch_peak_rows(wav, L_max, ip.dev(o_len), mx, B, peak, c.s));
+    MT2_HIP(launch_scale_rows(wav, L_max, ip.dev(o_len), peak, out, L_max, L_max, B, c.s));
+}
+
 }  // namespace mt2
 
 // the C ABI lives in capi.hip and includes this translation unit's helpers

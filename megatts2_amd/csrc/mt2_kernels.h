@@ -326,4 +326,34 @@ hipError_t launch_fill_reflect(float* x, int ld, int C, const int* start, const 
 // no-op kernel named mt2::stage_marker_kernel<ID> (ID 0..15): stage boundary in a kernel trace
 hipError_t launch_stage_marker(int id, hipStream_t s);
 
+// ---- sample-rate conversion of prompt audio (resample.hip; reference models/megatts2.py:335-336) --------------------------
+// The polyphase rule of one (sr_in, sr_out) pair, reduced by their gcd: o input samples per block of n output samples, `taps`
+// = 2 * width + o filter taps per phase; tb = output blocks per workgroup (the window of (tb - 1) * o + taps inputs sits in LDS).
+struct ResampleRule { int o, n, width, taps, tb; };
+// host only, no HIP call: nullptr and *r filled, or the reason the pair is refused (rates <= 0, equal rates, a table n * taps * 4
+// bytes over 8 MiB, a phase that does not fit the LDS window)
+const char* resample_rule(int sr_in, int sr_out, ResampleRule* r);
+long long resample_out_len(const ResampleRule& r, long long L);      // ceil(n * L / o)
+// the filter in double, rounded once to f32: [n][taps] phase-major, or [taps][n] tap-major (what the kernel reads)
+void resample_table(const ResampleRule& r, float* table, bool tap_major);
+// out[b, j] = sum_k table[k][j % n] * wav[b, (j / n) * o - width + k] for j < lout[b] (wav = 0 outside [0, len[b])), 0 for
+// lout[b] <= j < Lout_max.  Workgroup t owns the output blocks [tile_i0[t], tile_i0[t] + tb) of utterance tile_b[t]; the tiles cover
+// [0, Lout_max) of every utterance.  peak != nullptr: peak[b] = max(peak[b], max_j |out[b, j]|) as the u32 pattern of the float.
+struct ResampleP {
+    const float* wav; int L_max;              // [B, L_max]
+    int a0;                                   // (address of wav / 4) % 4 - which elements sit on 16 bytes; set by the launcher
+    const float* table; ResampleRule r;
+    const int* tile_b; const int* tile_i0; int tiles;
+    const int* len; const int* lout;
+    float* out; int Lout_max;
+    unsigned* peak;
+};
+hipError_t launch_resample_rows(const ResampleP& p, hipStream_t s);
+// peak[b] = max(peak[b], max_{j < len[b]} |x[b * stride + j]|), same encoding (zero the words first)
+hipError_t launch_peak_rows(const float* x, long long stride, const int* len, int max_len, int B, unsigned* peak, hipStream_t s);
+// librosa.util.normalize per utterance: out[b, j] = x[b, j] / peak[b] for j < len[b] (unchanged while peak[b] < FLT_MIN), 0 for
+// len[b] <= j < width; out may be x
+hipError_t launch_scale_rows(const float* x, long long xstride, const int* len, const unsigned* peak, float* out, long long ostride,
+                             int width, int B, hipStream_t s);
+
 }  // namespace mt2

@@ -201,6 +201,8 @@ struct mt2_model {
     mt2_audio_config fe_cfg{};
     float *fe_basis = nullptr, *fe_fb = nullptr;
     int fe_nfreq = 0, fe_nfreq_pad = 0;
+    // resampler filter tables, tap-major, by reduced ratio (o, n) = (sr_in, sr_out) / gcd: built and uploaded on first use
+    std::map<std::pair<int, int>, float*> rs_tables;
 
     bool profiling = false;
     std::vector<std::string> stage_names;

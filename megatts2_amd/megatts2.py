@@ -32,19 +32,27 @@ def _np_sd(sd) -> Dict[str, np.ndarray]:
 _FRONTEND = None
 
 
-def extract_mel_spec(samples):
-    """reference modules/tokenizer.py:107-125: 1-D waveform tensor (16 kHz) -> mel [80, T] (the reference
-    returns channels first and `Megatts.forward` transposes it, models/megatts2.py:339).  Runs on the GPU
-    (runtime.MelFrontEnd); a [B, L] input gives [B, 80, T]."""
-    import torch
+def _frontend():
     global _FRONTEND
     if _FRONTEND is None:
         from .runtime import MelFrontEnd
         _FRONTEND = MelFrontEnd()
+    return _FRONTEND
+
+
+def extract_mel_spec(samples, sample_rate: Optional[int] = None):
+    """reference modules/tokenizer.py:107-125: 1-D waveform tensor (16 kHz) -> mel [80, T] (the reference
+    returns channels first and `Megatts.forward` transposes it, models/megatts2.py:339).  Runs on the GPU
+    (runtime.MelFrontEnd); a [B, L] input gives [B, 80, T].  sample_rate: the rate of `samples` when it is not
+    16 kHz - they are resampled on the GPU first (MelFrontEnd.resample, not normalised)."""
+    import torch
+    fe = _frontend()
     x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
     batched = x.dim() == 2
     x = (x if batched else x.unsqueeze(0)).to("cuda", torch.float32)
-    mel = _FRONTEND(x).transpose(1, 2)
+    if sample_rate is not None and int(sample_rate) != fe.audio.sample_rate:
+        x = fe.resample(x, int(sample_rate))[0]
+    mel = fe(x).transpose(1, 2)
     return mel if batched else mel[0]
 
 
@@ -529,17 +537,28 @@ class Megatts:
         return out[0], out[1]
 
     # -- the reference's entry point (models/megatts2.py:325-375).  Prompt audio: every *.wav of the directory
-    # is loaded (16 kHz mono), peak-normalised, turned into a mel by extract_mel_spec (on the GPU) and the mels
-    # are concatenated along time (:332-344).  Text -> phone ids is the reference's G2P (pypinyin + MFA
+    # is loaded (mono), peak-normalised, turned into a mel by extract_mel_spec (on the GPU) and the mels
+    # are concatenated along time (:332-344).  A file at another rate than 16 kHz is resampled as `librosa.load(wav,
+    # sr=16000)` does it there (:335) - on the GPU (MelFrontEnd.from_audio; its own filter, parity with librosa's
+    # unpinned); resample=False rejects such a file instead.  Text -> phone ids is the reference's G2P (pypinyin + MFA
     # dictionary, host side, outside the hot path); when it is not importable pass `phone_tokens` instead.
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
-                phones: Optional[Sequence[str]] = None):
+                phones: Optional[Sequence[str]] = None, resample: bool = True):
         import torch
         from . import audio_io
         wavs = sorted(glob.glob(f"{wavs_dir}/*.wav"))
         if not wavs:
             raise NativeError(f"no *.wav under {wavs_dir}")
-        mels = [extract_mel_spec(torch.from_numpy(audio_io.load_audio(w, HIFIGAN_SR))).transpose(0, 1) for w in wavs]
+
+        def prompt_mel(w):
+            y, sr = audio_io.read_wav(w)
+            if sr == HIFIGAN_SR:          # audio_io.load_audio's two steps
+                return extract_mel_spec(torch.from_numpy(audio_io.normalize(y))).transpose(0, 1)
+            if not resample:
+                raise ValueError(f"{w}: {sr} Hz, expected {HIFIGAN_SR} Hz (resample=False)")
+            return _frontend().from_audio(torch.from_numpy(y).unsqueeze(0).cuda(), sr)[0][0]
+
+        mels = [prompt_mel(w) for w in wavs]
         mels_prompt = mels[0]
         mels = torch.cat(mels, dim=0).unsqueeze(0)
         if phone_tokens is None:

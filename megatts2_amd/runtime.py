@@ -23,6 +23,7 @@ MAX_POSITIONS = 8192       # rows of the sine tables (the reference builds 4000 
 MT2_RUN_PLM, MT2_RUN_VOCODER, MT2_SKIP_ADM, MT2_PROMPT_VQPE = 1, 2, 4, 8
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 ACT_LOGCLAMP = 4          # epilogue only: log(max(v, pro_slope))
+MT2_RESAMPLE_NORMALIZE = 1
 
 
 class NativeError(RuntimeError):
@@ -84,6 +85,7 @@ def load_library():
     lib.mt2_model_create.argtypes = [C.POINTER(MT2Config)]
     lib.mt2_model_destroy.argtypes = [C.c_void_p]
     lib.mt2_model_destroy.restype = None
+    lib.mt2_resample_query.argtypes = [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 4
     _LIB = lib
     return lib
 
@@ -656,6 +658,42 @@ class MelFrontEnd:
         _check(self.lib.mt2_mel_spectrogram(self.h, _stream(), C.byref(self.ac), _ptr(wav), _iptr(ln), L, B, _ptr(mel), T))
         return mel
 
+    def resample(self, wav, sr_in: int, lens=None, normalize: bool = False, out=None):
+        """`librosa.load(wav, sr=audio.sample_rate)` of the reference (models/megatts2.py:335) for a ragged batch on the device, by the
+        rule of csrc/resample.hip (parity with librosa's soxr filter is unpinned): wav f32 [B, L] (device) at sr_in ->
+        (f32 [B, max L_out], out_lens int32 [B]) with L_out = ceil(n * L / o), zeros beyond out_lens[b]; samples beyond lens[b] are
+        never read.  normalize: each utterance divided by its peak as well (:336).  out: a contiguous f32 [B, >= max L_out] device
+        tensor to write into.  sr_in == audio.sample_rate is an error: there is nothing to resample."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+        assert ln.shape == (B,)
+        if out is None:
+            out = torch.empty(B, resample_query(sr_in, self.audio.sample_rate, int(ln.max()))[0], device=wav.device, dtype=torch.float32)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        out_lens = np.zeros(B, np.int32)
+        _check(self.lib.mt2_resample(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, int(sr_in), self.audio.sample_rate,
+                                     MT2_RESAMPLE_NORMALIZE if normalize else 0, _ptr(out), out.shape[1], _iptr(out_lens)))
+        return out, out_lens
+
+    def from_audio(self, wav, sr_in: int, lens=None):
+        """Prompt audio at any sample rate -> (mel [B, T, n_mels], mel_lens): resample to audio.sample_rate, peak-normalise and
+        extract the mel (models/megatts2.py:335-336,339) with no host round trip.  Audio that already has that rate is only
+        normalised, by the same kernels."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        if int(sr_in) == self.audio.sample_rate:
+            ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+            y = torch.empty_like(wav)
+            _check(self.lib.mt2_peak_normalize(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, _ptr(y)))
+        else:
+            y, ln = self.resample(wav, sr_in, lens, normalize=True)
+        return self(y, ln), 1 + ln // self.audio.hop_length
+
 
 # ---- kernel-level entry points -------------------------------------------------------------------------
 
@@ -1089,6 +1127,21 @@ def op_gemm_route(M, N, K, taps=1, dil=1, groups=1, pro_act=ACT_NONE, operands=0
     out = [C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_int(0)]
     _check(load_library().mt2_gemm_route(M, N, K, taps, dil, groups, pro_act, operands, misaligned, force_cfg, x3h, *map(C.byref, out)))
     return tuple(v.value for v in out)
+
+
+def resample_query(sr_in: int, sr_out: int, L: int = 0):
+    """mt2_resample_query (no device needed) -> (L_out, o, n, taps) of resampling L samples from sr_in to sr_out."""
+    lo, o, n, k = C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(load_library().mt2_resample_query(int(sr_in), int(sr_out), int(L), C.byref(lo), C.byref(o), C.byref(n), C.byref(k)))
+    return lo.value, o.value, n.value, k.value
+
+
+def resample_table(sr_in: int, sr_out: int) -> np.ndarray:
+    """mt2_resample_table (no device needed) -> the f32 filter [n, taps] the device applies for this pair of rates."""
+    _, _, n, k = resample_query(sr_in, sr_out)
+    h = np.empty((n, k), np.float32)
+    _check(load_library().mt2_resample_table(int(sr_in), int(sr_out), h.ctypes.data_as(C.c_void_p)))
+    return h
 
 
 def bench_gemm(M, N, K, taps=1, force_cfg=-1, iters=20, w_copies=1, dil=1, flags=0):

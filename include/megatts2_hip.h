@@ -491,6 +491,41 @@ int mt2_op_attention_x3h(void* stream, const float* Q, int ldq, const float* K, 
                          float* O, int ldo, const int32_t* q_start, const int32_t* q_len, const int32_t* kv_start,
                          const int32_t* kv_len, int B, int H, int D, int max_qlen, float scale, int lds_waves, int max_kvlen,
                          int32_t* range_flag);
+/* Kernel tests of the attention launches' GEOMETRY (tests/test_gpu_attention_geometry.py): one launch with every field of its
+ * parameter block (csrc/mt2_kernels.h, AttnP) given explicitly - nothing is defaulted, no flag rides on another argument.
+ * Ragged geometry: q_start / q_len / kv_start / kv_len (device int32 [B], all four or none) give the row range of sequence b in Q and
+ * in K / V; its output rows start at o_start[b] (device int32 [B], may be NULL: q_start[b]).  Uniform geometry (the four arrays
+ * NULL): sequence b starts at row b * u_qstride (queries) and b * u_kvstride (keys), has u_qlen / u_kvlen rows, and writes output rows
+ * b * u_ostride + i (u_ostride = 0: u_qstride; o_start, when given, takes precedence here as well).  max_qlen sizes the grid;
+ * max_kvlen: longest key range of a ragged launch (0 = unknown).  lds_min_qlen / x6_min_qlen: first query count served by the
+ * LDS-tiled / matrix-pipe kernels (0: never); lds_waves: 0, 4 or 8 query tiles per workgroup of those; ds_short: 1 lets D = 64 / 96 with
+ * at most 128 keys run on the head-dim-split kernel; x3h: 1 = the matrix-pipe kernel in its fp16-pipe form; o_planes: 1 = O receives fp16
+ * planes (ldo % 32 == 0, O on 128 bytes).  range_flag (device int32, may be NULL): |= 1 when a value at or beyond 65504 was converted
+ * to fp16.  kernel_out (host, may be NULL): the kernel the routing chose (MT2_ATTN_*; MT2_ATTN_NONE: nothing to launch, or rejected).
+ * struct_bytes = sizeof(mt2_attn_desc) as the caller sees it: a mirror of the struct laid out differently is an error, not a launch.
+ * Nothing about the buffers' sizes is known here: the caller answers for every row the geometry names. */
+enum { MT2_ATTN_NONE = 0, MT2_ATTN_GENERIC = 1, MT2_ATTN_REG = 2, MT2_ATTN_DS = 3, MT2_ATTN_LDS = 4, MT2_ATTN_X6 = 5, MT2_ATTN_X3H = 6 };
+typedef struct mt2_attn_desc {
+    int32_t struct_bytes;
+    const float* Q; int32_t ldq;
+    const float* K; int32_t ldk;
+    const float* V; int32_t ldv;
+    float* O; int32_t ldo;
+    const int32_t* q_start; const int32_t* q_len; const int32_t* kv_start; const int32_t* kv_len; const int32_t* o_start;
+    int32_t u_qstride, u_qlen, u_kvstride, u_kvlen, u_ostride;
+    int32_t B, H, D, max_qlen, max_kvlen; float scale;
+    int32_t lds_min_qlen, x6_min_qlen, lds_waves, ds_short, x3h, o_planes;
+    int32_t* range_flag;
+    int32_t* kernel_out;
+} mt2_attn_desc;
+int mt2_op_attention_desc(void* stream, const mt2_attn_desc* d);
+/* test hook, no device needed: what launch_attention (csrc/attention.hip, attn_route) would do with the launch `d` describes - no
+ * pointer of `d` is dereferenced (Q / K / V / O may be NULL; O's alignment and whether q_start is NULL are looked at).  err: the
+ * hipError_t it would return before launching (0: it launches, or there is nothing to launch); kernel: MT2_ATTN_*; tmpl[4]: the template
+ * arguments that matter - head dim D (generic kernel: DT, 32-column tiles per wave), query tiles per workgroup, key tiles per workgroup
+ * (head-dim-split kernel), split-KV waves (register kernel; generic kernel: waves across the head dim); launch[4]: grid x, y, z and
+ * block size; lds: dynamic LDS bytes.  Returns 0, or -1 for a NULL or mis-sized descriptor. */
+int mt2_attention_route(const mt2_attn_desc* d, int32_t* err, int32_t* kernel, int32_t* tmpl, int32_t* launch, long long* lds);
 /* Launch trace of the GEMM/conv engine (measurement only): between begin and end every launch is
  * bracketed by HIP events on its own stream.  end() reports, per tile configuration, the number of
  * launches, the executed FLOPs (2*M*N*K*groups) and the summed kernel time in ms, plus a last entry named

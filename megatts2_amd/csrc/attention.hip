@@ -409,20 +409,19 @@ __global__ __launch_bounds__(768) void attn_f32_ds_kernel(AttnP p) {
     }
 }
 template <int D>
-static hipError_t launch_attn_ds(const AttnP& p, int nkv, hipStream_t s) {
+static hipError_t launch_attn_ds(const AttnP& p, const AttnRoute& r, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};      // per device (dyn_lds_once)
     constexpr int NS = D / 32;
-    const size_t lds = (size_t)nkv * NS * (16 + 18) * 64 * sizeof(float);
     {                       // up to 4 x 3 waves: 102 KiB
         hipError_t e = dyn_lds_once(attr_done, reinterpret_cast<const void*>(attn_f32_ds_kernel<D>),
                                     (size_t)4 * NS * (16 + 18) * 64 * sizeof(float));
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(attn_f32_ds_kernel<D>, dim3((p.max_qlen + 31) / 32, p.H, p.B), dim3(64 * nkv * NS), lds, s, p);
+    hipLaunchKernelGGL(attn_f32_ds_kernel<D>, dim3(r.gx, r.gy, r.gz), dim3(r.block), r.lds, s, p);
     return hipGetLastError();
 }
 
-// Very long sequences (default: >= 640 queries, AttnP::lds_min_qlen): the LDS-tiled form.  The register kernel above gives every 32-query tile its own
+// Very long sequences (default: >= 640 queries, see attn_route): the LDS-tiled form.  The register kernel above gives every 32-query tile its own
 // workgroup and lets each of its waves fetch "its" K / V tiles from memory - right for the <= 3 key tiles of a 70-position
 // step (one round trip per launch), wrong for 834 positions: 27 query tiles re-read the whole K / V of the head, a wave
 // holds ~270 registers (one wave per SIMD) and the matrix pipe idles through every softmax and every load
@@ -568,23 +567,19 @@ __global__ __launch_bounds__(64 * NWQ) void attn_f32_lds_kernel(AttnP p) {
 }
 
 template <int D, int NWQ>
-static hipError_t launch_attn_lds(const AttnP& p, hipStream_t s) {
+static hipError_t launch_attn_lds(const AttnP& p, const AttnRoute& r, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};      // per device (dyn_lds_once)
     void (*fn)(AttnP) = attn_f32_lds_kernel<D, NWQ>;
-    const size_t lds = (size_t)4 * 32 * (D + 4) * sizeof(float);
-    if (lds > 48 * 1024) {
-        hipError_t e = dyn_lds_once(attr_done, reinterpret_cast<const void*>(fn), lds);
+    if (r.lds > 48 * 1024) {
+        hipError_t e = dyn_lds_once(attr_done, reinterpret_cast<const void*>(fn), r.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(fn, dim3((p.max_qlen + 32 * NWQ - 1) / (32 * NWQ), p.H, p.B), dim3(64 * NWQ), lds, s, p);
+    hipLaunchKernelGGL(fn, dim3(r.gx, r.gy, r.gz), dim3(r.block), r.lds, s, p);
     return hipGetLastError();
 }
 template <int D>
-static hipError_t launch_attn_lds_d(const AttnP& p, hipStream_t s) {
-    // 4 query tiles per workgroup (two workgroups per CU) unless 8 is asked for: profiles/r03_attn_bench.txt - 8x96 at
-    // 834 positions 189 us (register kernel) / 141 (4) / 213 (8); 16x64 at 646: 137 / 142 / 133
-    if (p.lds_waves == 8) return launch_attn_lds<D, 8>(p, s);
-    return launch_attn_lds<D, 4>(p, s);
+static hipError_t launch_attn_lds_d(const AttnP& p, const AttnRoute& r, hipStream_t s) {
+    return r.nwq == 8 ? launch_attn_lds<D, 8>(p, r, s) : launch_attn_lds<D, 4>(p, r, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -923,39 +918,49 @@ __global__ __launch_bounds__(64 * NWQ) __attribute__((amdgpu_waves_per_eu(2))) v
         }
 }
 
-template <int D, int NWQ, bool H3 = false>
-static hipError_t launch_attn_x6(const AttnP& p, hipStream_t s) {
+template <int D, int NWQ, bool H3>
+static hipError_t launch_attn_x6(const AttnP& p, const AttnRoute& r, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};      // per device (dyn_lds_once)
     void (*fn)(AttnP) = attn_x6_kernel<D, NWQ, H3>;
-    const size_t lds = (size_t)(H3 ? 2 : 3) * (32 * (D * 2 + 16) + D * 80);
-    if (lds > 48 * 1024) {
-        hipError_t e = dyn_lds_once(attr_done, reinterpret_cast<const void*>(fn), lds);
+    if (r.lds > 48 * 1024) {
+        hipError_t e = dyn_lds_once(attr_done, reinterpret_cast<const void*>(fn), r.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(fn, dim3((p.max_qlen + 32 * NWQ - 1) / (32 * NWQ), p.H, p.B), dim3(64 * NWQ), lds, s, p);
+    hipLaunchKernelGGL(fn, dim3(r.gx, r.gy, r.gz), dim3(r.block), r.lds, s, p);
     return hipGetLastError();
 }
 template <int D>
-static hipError_t launch_attn_x6_d(const AttnP& p, hipStream_t s) {
-    // the K / V split of a tile is paid once per workgroup: 8 query tiles per workgroup once there are enough of them
-    const bool w8 = p.lds_waves == 8 || (p.lds_waves != 4 && p.max_qlen >= 600);      // profiles/r03_attn_bench.txt
-    if (p.x3h) return w8 ? launch_attn_x6<D, 8, true>(p, s) : launch_attn_x6<D, 4, true>(p, s);
-    return w8 ? launch_attn_x6<D, 8>(p, s) : launch_attn_x6<D, 4>(p, s);
+static hipError_t launch_attn_x6_d(const AttnP& p, const AttnRoute& r, hipStream_t s) {
+    if (r.kernel == ATTN_X3H) return r.nwq == 8 ? launch_attn_x6<D, 8, true>(p, r, s) : launch_attn_x6<D, 4, true>(p, r, s);
+    return r.nwq == 8 ? launch_attn_x6<D, 8, false>(p, r, s) : launch_attn_x6<D, 4, false>(p, r, s);
 }
 
-hipError_t launch_attention(const AttnP& p, hipStream_t s) {
-    if (p.B <= 0 || p.H <= 0 || p.max_qlen <= 0) return hipSuccess;
-    if (p.D % 32 != 0 || (p.ldq & 3) || (p.ldk & 3) || (p.ldo & 3)) return hipErrorInvalidValue;
-    if (p.o_planes && ((p.ldo & 31) || (((unsigned long long)p.O) & 127))) return hipErrorInvalidValue;      // whole 128-byte blocks per row
-    if ((p.D == 64 || p.D == 96) && p.x6_min_qlen > 0 && p.max_qlen >= p.x6_min_qlen && ((p.ldq | p.ldk) & 3) == 0)
-        return p.D == 64 ? launch_attn_x6_d<64>(p, s) : launch_attn_x6_d<96>(p, s);
+// The kernel choice (host only, no HIP call): every condition on the launch parameters lives here and nowhere else.
+AttnRoute attn_route(const AttnP& p) {
+    AttnRoute r{hipSuccess, ATTN_NONE, 0, 1, 0, 0, 0, 0, 0, 0, 0};
+    if (p.B <= 0 || p.H <= 0 || p.max_qlen <= 0) return r;
+    r.err = hipErrorInvalidValue;
+    if (p.D % 32 != 0 || (p.ldq & 3) || (p.ldk & 3) || (p.ldo & 3)) return r;
+    if (p.o_planes && ((p.ldo & 31) || (((unsigned long long)p.O) & 127))) return r;      // whole 128-byte blocks per row
+    const auto route = [&](int kernel, int d, int qtiles, unsigned block, size_t lds) {
+        r.err = hipSuccess; r.kernel = kernel; r.d = d;
+        r.gx = (unsigned)((p.max_qlen + 32 * qtiles - 1) / (32 * qtiles)); r.gy = (unsigned)p.H; r.gz = (unsigned)p.B;
+        r.block = block; r.lds = lds;
+        return r;
+    };
+    if ((p.D == 64 || p.D == 96) && p.x6_min_qlen > 0 && p.max_qlen >= p.x6_min_qlen && ((p.ldq | p.ldk) & 3) == 0) {
+        // the K / V split of a tile is paid once per workgroup: 8 query tiles per workgroup once there are enough of them
+        const bool w8 = p.lds_waves == 8 || (p.lds_waves != 4 && p.max_qlen >= 600);      // profiles/r03_attn_bench.txt
+        r.nwq = w8 ? 8 : 4;
+        return route(p.x3h ? ATTN_X3H : ATTN_X6, p.D, r.nwq, 64u * r.nwq, (size_t)(p.x3h ? 2 : 3) * (32 * (p.D * 2 + 16) + p.D * 80));
+    }
     if (p.D <= 128 && p.max_qlen >= p.lds_min_qlen && p.lds_min_qlen > 0 && (p.ldv & 3) == 0) {
-        switch (p.D) {        // long sequences: K / V tiles shared by 8 query tiles through LDS
-            case 32: return launch_attn_lds_d<32>(p, s);
-            case 64: return launch_attn_lds_d<64>(p, s);
-            case 96: return launch_attn_lds_d<96>(p, s);
-            default: return launch_attn_lds_d<128>(p, s);
-        }
+        // long sequences: K / V tiles shared by the query tiles of a workgroup through LDS.  4 query tiles per workgroup (two
+        // workgroups per CU) unless 8 is asked for: profiles/r03_attn_bench.txt - 8x96 at 834 positions 189 us (register kernel) /
+        // 141 (4) / 213 (8); 16x64 at 646: 137 / 142 / 133
+        const int D = p.D == 32 || p.D == 64 || p.D == 96 ? p.D : 128;
+        r.nwq = p.lds_waves == 8 ? 8 : 4;
+        return route(ATTN_LDS, D, r.nwq, 64u * r.nwq, (size_t)4 * 32 * (D + 4) * sizeof(float));
     }
     if (p.D <= 128) {
         // split-KV width: the longest key range of the launch (uniform geometry knows it exactly; ragged
@@ -964,34 +969,58 @@ hipError_t launch_attention(const AttnP& p, hipStream_t s) {
         if (p.ds_short && (p.D == 64 || p.D == 96) && kvmax <= 128 && (!p.q_start || p.max_kvlen > 0)) {      // kvmax must be a true bound
             // the AR steps' short sequences: key tiles x head-dim slices (attn_f32_ds_kernel)
             const int nkv = (kvmax + 31) / 32;
-            return p.D == 64 ? launch_attn_ds<64>(p, nkv < 1 ? 1 : nkv, s) : launch_attn_ds<96>(p, nkv < 1 ? 1 : nkv, s);
+            r.nkv = nkv < 1 ? 1 : nkv;
+            const int NS = p.D / 32;
+            return route(ATTN_DS, p.D, 1, 64u * r.nkv * NS, (size_t)r.nkv * NS * (16 + 18) * 64 * sizeof(float));
         }
         int nwv = (kvmax + 31) / 32;
         nwv = nwv < 1 ? 1 : (nwv > 4 ? 4 : nwv);
+        r.nwv = nwv;
+        const int D = p.D == 32 || p.D == 64 || p.D == 96 ? p.D : 128;
         const int DT = p.D / 32;
-        const size_t lds = nwv > 1 ? (size_t)(nwv - 1) * (DT * 16 + 2) * 64 * sizeof(float) : 0;
-        dim3 grid((p.max_qlen + 31) / 32, p.H, p.B), block(64 * nwv);
-        switch (p.D) {
-            case 32: hipLaunchKernelGGL(attn_f32_reg_kernel<32>, grid, block, lds, s, p); break;
-            case 64: hipLaunchKernelGGL(attn_f32_reg_kernel<64>, grid, block, lds, s, p); break;
-            case 96: hipLaunchKernelGGL(attn_f32_reg_kernel<96>, grid, block, lds, s, p); break;
-            default: hipLaunchKernelGGL(attn_f32_reg_kernel<128>, grid, block, lds, s, p); break;
-        }
-        return hipGetLastError();
+        return route(ATTN_REG, D, 1, 64u * nwv, nwv > 1 ? (size_t)(nwv - 1) * (DT * 16 + 2) * 64 * sizeof(float) : 0);
     }
     const int tiles = p.D / 32;
     int nw = (p.D + 127) / 128;
     while (nw <= 4 && tiles % nw != 0) ++nw;
-    if (nw > 4 || tiles / nw > 4) return hipErrorInvalidValue;
-    const int dt = tiles / nw;
-    dim3 grid((p.max_qlen + 31) / 32, p.H, p.B), block(64 * nw);
-    switch (dt) {
-        case 1: hipLaunchKernelGGL(attn_f32_kernel<1>, grid, block, 0, s, p); break;
-        case 2: hipLaunchKernelGGL(attn_f32_kernel<2>, grid, block, 0, s, p); break;
-        case 3: hipLaunchKernelGGL(attn_f32_kernel<3>, grid, block, 0, s, p); break;
-        default: hipLaunchKernelGGL(attn_f32_kernel<4>, grid, block, 0, s, p); break;
+    if (nw > 4 || tiles / nw > 4) return r;
+    r.nwv = nw;
+    return route(ATTN_GENERIC, tiles / nw, 1, 64u * nw, 0);
+}
+
+hipError_t launch_attention(const AttnP& p, hipStream_t s) {
+    const AttnRoute r = attn_route(p);
+    if (r.err != hipSuccess) return r.err;
+    const dim3 grid(r.gx, r.gy, r.gz), block(r.block);
+    switch (r.kernel) {
+        case ATTN_NONE: return hipSuccess;
+        case ATTN_X6:
+        case ATTN_X3H: return r.d == 64 ? launch_attn_x6_d<64>(p, r, s) : launch_attn_x6_d<96>(p, r, s);
+        case ATTN_LDS:
+            switch (r.d) {
+                case 32: return launch_attn_lds_d<32>(p, r, s);
+                case 64: return launch_attn_lds_d<64>(p, r, s);
+                case 96: return launch_attn_lds_d<96>(p, r, s);
+                default: return launch_attn_lds_d<128>(p, r, s);
+            }
+        case ATTN_DS: return r.d == 64 ? launch_attn_ds<64>(p, r, s) : launch_attn_ds<96>(p, r, s);
+        case ATTN_REG:
+            switch (r.d) {
+                case 32: hipLaunchKernelGGL(attn_f32_reg_kernel<32>, grid, block, r.lds, s, p); break;
+                case 64: hipLaunchKernelGGL(attn_f32_reg_kernel<64>, grid, block, r.lds, s, p); break;
+                case 96: hipLaunchKernelGGL(attn_f32_reg_kernel<96>, grid, block, r.lds, s, p); break;
+                default: hipLaunchKernelGGL(attn_f32_reg_kernel<128>, grid, block, r.lds, s, p); break;
+            }
+            return hipGetLastError();
+        default:
+            switch (r.d) {
+                case 1: hipLaunchKernelGGL(attn_f32_kernel<1>, grid, block, 0, s, p); break;
+                case 2: hipLaunchKernelGGL(attn_f32_kernel<2>, grid, block, 0, s, p); break;
+                case 3: hipLaunchKernelGGL(attn_f32_kernel<3>, grid, block, 0, s, p); break;
+                default: hipLaunchKernelGGL(attn_f32_kernel<4>, grid, block, 0, s, p); break;
+            }
+            return hipGetLastError();
     }
-    return hipGetLastError();
 }
 
 }  // namespace mt2

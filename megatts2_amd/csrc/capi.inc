@@ -1440,6 +1440,47 @@ int mt2_op_attention_x3h(void* stream, const float* Q, int ldq, const float* K, 
     MT2_API_END
 }
 
+// Kernel tests of the launch geometry: every field of AttnP given explicitly (mt2_attn_desc), and the route that launch takes
+static_assert(MT2_ATTN_NONE == ATTN_NONE && MT2_ATTN_GENERIC == ATTN_GENERIC && MT2_ATTN_REG == ATTN_REG && MT2_ATTN_DS == ATTN_DS &&
+              MT2_ATTN_LDS == ATTN_LDS && MT2_ATTN_X6 == ATTN_X6 && MT2_ATTN_X3H == ATTN_X3H, "kernel ids of the C ABI");
+static AttnP attn_from_desc(const mt2_attn_desc& d) {
+    AttnP a{};
+    a.Q = d.Q; a.ldq = d.ldq; a.K = d.K; a.ldk = d.ldk; a.V = d.V; a.ldv = d.ldv; a.O = d.O; a.ldo = d.ldo;
+    a.q_start = d.q_start; a.q_len = d.q_len; a.kv_start = d.kv_start; a.kv_len = d.kv_len; a.o_start = d.o_start;
+    a.u_qstride = d.u_qstride; a.u_qlen = d.u_qlen; a.u_kvstride = d.u_kvstride; a.u_kvlen = d.u_kvlen; a.u_ostride = d.u_ostride;
+    a.B = d.B; a.H = d.H; a.D = d.D; a.max_qlen = d.max_qlen; a.max_kvlen = d.max_kvlen; a.scale = d.scale;
+    a.lds_min_qlen = d.lds_min_qlen; a.x6_min_qlen = d.x6_min_qlen; a.lds_waves = d.lds_waves; a.ds_short = d.ds_short;
+    a.x3h = d.x3h; a.o_planes = d.o_planes; a.x3h_flag = d.range_flag;
+    return a;
+}
+int mt2_op_attention_desc(void* stream, const mt2_attn_desc* d) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(d != nullptr, "null descriptor");
+    MT2_REQUIRE(d->struct_bytes == (int32_t)sizeof(mt2_attn_desc), "descriptor size mismatch");
+    if (d->kernel_out) *d->kernel_out = MT2_ATTN_NONE;
+    const bool ragged = d->q_start != nullptr;
+    MT2_REQUIRE(d->Q && d->K && d->V && d->O, "bad arguments");
+    MT2_REQUIRE(ragged ? (d->q_len && d->kv_start && d->kv_len) : (!d->q_len && !d->kv_start && !d->kv_len),
+                "bad arguments: q_start, q_len, kv_start and kv_len come together or not at all");
+    MT2_REQUIRE(ragged || (d->u_qstride >= 0 && d->u_kvstride >= 0 && d->u_ostride >= 0 && d->u_qlen >= 0 && d->u_kvlen >= 0),
+                "bad arguments: negative uniform geometry");
+    MT2_REQUIRE(d->lds_waves == 0 || d->lds_waves == 4 || d->lds_waves == 8, "lds_waves must be 0, 4 or 8");
+    const AttnP a = attn_from_desc(*d);
+    if (d->kernel_out) *d->kernel_out = attn_route(a).kernel;
+    MT2_HIP(launch_attention(a, (hipStream_t)stream));
+    MT2_API_END
+}
+int mt2_attention_route(const mt2_attn_desc* d, int32_t* err, int32_t* kernel, int32_t* tmpl, int32_t* launch, long long* lds) {
+    if (!d || d->struct_bytes != (int32_t)sizeof(mt2_attn_desc)) return -1;
+    const AttnRoute r = attn_route(attn_from_desc(*d));
+    if (err) *err = (int32_t)r.err;
+    if (kernel) *kernel = r.kernel;
+    if (tmpl) { tmpl[0] = r.d; tmpl[1] = r.nwq; tmpl[2] = r.nkv; tmpl[3] = r.nwv; }
+    if (launch) { launch[0] = (int32_t)r.gx; launch[1] = (int32_t)r.gy; launch[2] = (int32_t)r.gz; launch[3] = (int32_t)r.block; }
+    if (lds) *lds = (long long)r.lds;
+    return 0;
+}
+
 int mt2_bench_gemm(void* stream, int M, int N, int K, int taps, int dil, int flags, int force_cfg, int iters,
                    int w_copies, float* avg_ms, char* cfg_name, int cfg_name_cap, double* sustained_ghz) {
     MT2_API_BEGIN

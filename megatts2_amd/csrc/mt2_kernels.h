@@ -230,6 +230,28 @@ struct AttnP {
     int o_planes = 0;         // 1: O receives fp16 planes (planes_store.h: the A operand of the out-projection's GemmP::a_planes launch; same
     int* x3h_flag = nullptr;  // bytes and row stride as f32; D % 32 == 0, ldo % 32 == 0, O on 128 bytes); x3h_flag: the range guard's device word
 };
+// attn_route decides, without a HIP call, what launch_attention does with a launch - the one place where a kernel is chosen:
+// err (hipSuccess: it launches, or there is nothing to launch: kernel == ATTN_NONE), the kernel, the template arguments that
+// matter for it, and the launch geometry.  launch_attention launches from this result and decides nothing itself.
+enum AttnKernel {
+    ATTN_NONE = 0,      // nothing to launch (B, H or max_qlen <= 0) or rejected
+    ATTN_GENERIC = 1,   // attn_f32_kernel<dt>: wide heads, nwv waves of dt 32-column tiles each
+    ATTN_REG = 2,       // attn_f32_reg_kernel<d>: nwv split-KV waves
+    ATTN_DS = 3,        // attn_f32_ds_kernel<d>: nkv key tiles x d / 32 head-dim slices
+    ATTN_LDS = 4,       // attn_f32_lds_kernel<d, nwq>
+    ATTN_X6 = 5,        // attn_x6_kernel<d, nwq>: bf16 pipe, six products
+    ATTN_X3H = 6,       // attn_x6_kernel<d, nwq, true>: fp16 pipe, three products
+};
+struct AttnRoute {
+    hipError_t err; int kernel;
+    int d;              // template head dim D (reg, ds, lds, x6, x3h); generic: DT, the 32-column tiles per wave
+    int nwq;            // query tiles (= waves) per workgroup (lds, x6, x3h; otherwise 1)
+    int nkv;            // key tiles per workgroup (ds; otherwise 0)
+    int nwv;            // split-KV waves (reg), waves across the head dim (generic); otherwise 0
+    unsigned gx, gy, gz, block;
+    size_t lds;         // dynamic LDS bytes
+};
+AttnRoute attn_route(const AttnP& p);
 hipError_t launch_attention(const AttnP& p, hipStream_t s);
 
 // ---- row utilities (rowops.hip) ------------------------------------------------------------------

@@ -1122,6 +1122,72 @@ def op_attention_x3h(Q, K, V, q_start, q_len, kv_start, kv_len, H, D, scale, lds
     return O, int(flag[0].item())
 
 
+# ---- test-only entry into the attention launches' geometry (tests/test_gpu_attention_geometry.py, tests/test_attention_route_host.py)
+
+ATTN_KERNELS = ("none", "generic", "reg", "ds", "lds", "x6", "x3h")      # MT2_ATTN_* of include/megatts2_hip.h, by id
+
+
+class MT2AttnDesc(C.Structure):
+    """ctypes mirror of mt2_attn_desc (include/megatts2_hip.h): one attention launch with every field of its parameter block explicit."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("Q", C.c_void_p), ("ldq", C.c_int32),
+        ("K", C.c_void_p), ("ldk", C.c_int32),
+        ("V", C.c_void_p), ("ldv", C.c_int32),
+        ("O", C.c_void_p), ("ldo", C.c_int32),
+        ("q_start", C.c_void_p), ("q_len", C.c_void_p), ("kv_start", C.c_void_p), ("kv_len", C.c_void_p), ("o_start", C.c_void_p),
+        ("u_qstride", C.c_int32), ("u_qlen", C.c_int32), ("u_kvstride", C.c_int32), ("u_kvlen", C.c_int32), ("u_ostride", C.c_int32),
+        ("B", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("max_qlen", C.c_int32), ("max_kvlen", C.c_int32), ("scale", C.c_float),
+        ("lds_min_qlen", C.c_int32), ("x6_min_qlen", C.c_int32), ("lds_waves", C.c_int32), ("ds_short", C.c_int32),
+        ("x3h", C.c_int32), ("o_planes", C.c_int32),
+        ("range_flag", C.c_void_p),
+        ("kernel_out", C.POINTER(C.c_int32)),
+    ]
+
+
+def _attn_desc(Q, ldq, K, ldk, V, ldv, O, ldo, *, B, H, D, max_qlen, scale, q_start=None, q_len=None, kv_start=None, kv_len=None,
+               o_start=None, u_qstride=0, u_qlen=0, u_kvstride=0, u_kvlen=0, u_ostride=0, max_kvlen=0, lds_min_qlen, x6_min_qlen,
+               lds_waves, ds_short, x3h, o_planes, flag=None):
+    """Q / K / V / O, the start / len arrays and flag: device tensors (their data pointer is the operand: a view into a larger buffer
+    moves it), plain integer addresses (the route query never dereferences them) or None."""
+    def addr(x):
+        return None if x is None else (int(x) if isinstance(x, int) else x.data_ptr())
+    d = MT2AttnDesc()
+    d.struct_bytes = C.sizeof(MT2AttnDesc)
+    d.Q, d.ldq, d.K, d.ldk, d.V, d.ldv, d.O, d.ldo = addr(Q), ldq, addr(K), ldk, addr(V), ldv, addr(O), ldo
+    d.q_start, d.q_len, d.kv_start, d.kv_len, d.o_start = addr(q_start), addr(q_len), addr(kv_start), addr(kv_len), addr(o_start)
+    d.u_qstride, d.u_qlen, d.u_kvstride, d.u_kvlen, d.u_ostride = u_qstride, u_qlen, u_kvstride, u_kvlen, u_ostride
+    d.B, d.H, d.D, d.max_qlen, d.max_kvlen, d.scale = B, H, D, max_qlen, max_kvlen, scale
+    d.lds_min_qlen, d.x6_min_qlen, d.lds_waves, d.ds_short, d.x3h, d.o_planes = lds_min_qlen, x6_min_qlen, lds_waves, ds_short, x3h, o_planes
+    d.range_flag = addr(flag)
+    return d
+
+
+def op_attention_desc(Q, ldq, K, ldk, V, ldv, O, ldo, **geometry):
+    """mt2_op_attention_desc: one attention launch in the ragged (q_start, q_len, kv_start, kv_len[, o_start]) or the uniform (u_*)
+    geometry, nothing defaulted: B, H, D, max_qlen, scale, lds_min_qlen, x6_min_qlen, lds_waves, ds_short, x3h and o_planes are required
+    keywords.  Writes O in place and returns the name of the kernel the routing chose (ATTN_KERNELS)."""
+    d = _attn_desc(Q, ldq, K, ldk, V, ldv, O, ldo, **geometry)
+    kernel = C.c_int32(0)
+    d.kernel_out = C.pointer(kernel)
+    _check(load_library().mt2_op_attention_desc(_stream(), C.byref(d)))
+    return ATTN_KERNELS[kernel.value]
+
+
+def attention_route(ldq, ldk, ldv, ldo, *, Q=128, K=128, V=128, O=128, **geometry):
+    """mt2_attention_route (no device needed): what launch_attention would do with the launch -> dict: err (hipError_t; 0 with kernel
+    "none": nothing to launch), kernel (ATTN_KERNELS), d (template head dim; generic kernel: 32-column tiles per wave), nwq (query tiles
+    per workgroup), nkv (key tiles: ds), nwv (split-KV waves: reg; waves across the head dim: generic), grid (x, y, z), block, lds (bytes).
+    Pointers are addresses that are never dereferenced: pass any non-zero integer for a start / len array that exists."""
+    d = _attn_desc(Q, ldq, K, ldk, V, ldv, O, ldo, **geometry)
+    err, kernel, lds = C.c_int32(0), C.c_int32(0), C.c_longlong(0)
+    tmpl, launch = (C.c_int32 * 4)(), (C.c_int32 * 4)()
+    if load_library().mt2_attention_route(C.byref(d), C.byref(err), C.byref(kernel), tmpl, launch, C.byref(lds)) != 0:
+        raise NativeError("mt2_attention_route: null or mis-sized descriptor")
+    return {"err": err.value, "kernel": ATTN_KERNELS[kernel.value], "d": tmpl[0], "nwq": tmpl[1], "nkv": tmpl[2], "nwv": tmpl[3],
+            "grid": (launch[0], launch[1], launch[2]), "block": launch[3], "lds": lds.value}
+
+
 def op_gemm_route(M, N, K, taps=1, dil=1, groups=1, pro_act=ACT_NONE, operands=0, misaligned=0, force_cfg=-1, x3h=15):
     """mt2_gemm_route (no device needed) -> (hipError_t, config index, variant, LDS bytes, planes bits) of the launch launch_gemm would make."""
     out = [C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_int(0)]

@@ -251,6 +251,37 @@ int mt2_resample(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, co
 int mt2_peak_normalize(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
                        float* out);
 
+/* ---- leading / trailing silence of prompt audio (models/megatts2.py:337: `librosa.effects.trim(y, top_db=20)`, commented out there
+ * because its prompts are pre-cut; prepare_ds.py --trim_wav).  librosa is not on hand to compare with, so parity with it is unpinned,
+ * as for the resampler; the rule is our own statement of what librosa documents for effects.trim with ref = np.max, centred frames
+ * and zero padding, with the frame and hop FIXED (128 ms / 32 ms at 16 kHz; the hop is a multiple of the mel hop of 256, so every
+ * cut falls on a mel-frame boundary).  For one utterance x[0 .. L), L >= 1:
+ *   s[j] = sum of x[i]^2 over i in [512 j, 512 j + 512) and [0, L), in f32, j = 0 .. ceil(L / 512) - 1;  s[j] = 0 outside
+ *   F = 1 + L / 512 frames;  e[f] = s[f - 2] + s[f - 1] + s[f] + s[f + 1]    (the zero-padded window [512 f - 1024, 512 f + 1024))
+ *   E = max_f e[f];  c = (float)pow(10.0, -top_db / 10.0), computed in double and rounded once
+ *   frame f is kept iff e[f] > E * c   (one f32 product: 10 log10(mse / max mse) > -top_db without the logarithm)
+ *   start = 512 f_first,  end = min(L, 512 (f_last + 1)) over the kept frames (the frame holding E is kept, so end > start)
+ *   E < FLT_MIN (all zeros, or squares that underflow): the utterance is left whole, start = 0, end = L - the convention of the peak
+ *   normalisation, and unlike librosa, which returns an empty signal
+ *   out[j] = x[start + j] for j < end - start, an exact copy; zeros up to Lout_max
+ * The order of a block's sum depends on the sample's index in its utterance alone, so a batch is bit-identical to its utterances
+ * trimmed one by one, energies included.  Input must be finite; a non-finite sample does not fault and still gives bounds inside
+ * [0, L], nothing more.  Refused (error, nothing launched, `out` untouched): top_db not finite or <= 0; lens[b] < 1 or > L_max;
+ * Lout_max < max_b lens[b] (the cut is not known before the call: size `out` for no trimming); F_max < 1 + max_b lens[b] / 512 while
+ * `energy` is given; `out` overlapping `wav`. */
+#define MT2_TRIM_FRAME 2048
+#define MT2_TRIM_HOP 512
+/* models/megatts2.py:337  F = 1 + L / 512 and the f32 factor c of one length and one top_db; host only, no HIP call (outputs may be NULL) */
+int mt2_trim_query(long long L, float top_db, int* frames, float* factor);
+/* models/megatts2.py:337  wav f32 [B, L_max] (device) -> out f32 [B, Lout_max] (device); samples beyond lens[b] are never read.
+ * bounds (host, int32 [B][2] = start, end; may be NULL): the cut is found on the device and the copy reads it there, so only a
+ * caller that asks for `bounds` pays for it - one copy of 2 B ints to the host and ONE stream synchronise inside the call, as
+ * mt2_synthesize_batch does for the durations; with bounds == NULL the call only enqueues.  energy (device f32 [B, F_max], may be
+ * NULL): e[f] of each utterance, zeros in [F_b, F_max).  Scratch comes from the handle's arena; `m` may be a bare handle. */
+int mt2_trim_silence(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                     float top_db, float* out /*[B, Lout_max]*/, int Lout_max, int32_t* bounds /*host [B][2], may be NULL*/,
+                     float* energy /*[B, F_max] or NULL*/, int F_max);
+
 /* ---- the whole of Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) for a batch,
  * activations staying in the packed internal layout between stages.
  *   forced_dur   (host, optional) int32 [B, Np_max]: replaces the ADM's integer durations AFTER the ADM

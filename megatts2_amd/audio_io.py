@@ -7,6 +7,8 @@
   (csrc/resample.hip).  `load_audio` itself still rejects such a file unless `resample=True`, which keeps
   scipy's host polyphase filter for callers without a GPU - a different filter from the GPU's; librosa's
   soxr resampler is reproduced by neither (parity unpinned for resampled input).
+  The silence trimming of the reference's next line (:337, `librosa.effects.trim`, commented out there) is on the GPU too
+  (runtime.MelFrontEnd.trim, csrc/trim.hip); `trim_alignment` here cuts a prompt's phone alignment to match.
 * WAV out: `torchaudio.save('test.wav', audio, 16000)` (models/megatts2.py:375) writes 32-bit float PCM
   for a float32 tensor; `write_wav` does the same by default, or 16-bit PCM with clipping.
 * Packed weights: the three Lightning checkpoints are pickles read through `torch.load`
@@ -80,6 +82,29 @@ def load_audio(path: str, sr: int = 16000, resample: bool = False) -> np.ndarray
         g = gcd(sr, file_sr)
         y = resample_poly(y, sr // g, file_sr // g).astype(np.float32)
     return normalize(y)
+
+
+def trim_alignment(phone_tokens, durations, start: int, end: int, hop: int = 256):
+    """The phone alignment of a prompt whose audio was cut to the samples [start, end) (runtime.MelFrontEnd.trim /
+    from_audio(trim_db=..., return_bounds=True)) -> (phone_tokens', durations').  The cut prompt has T' = 1 + (end - start) // hop
+    mel frames, the original frames [s, s + T') with s = start // hop; each phone keeps the frames of its span that lie in that
+    range, a phone left with none is dropped, and the result sums to T'.  ValueError when start is no multiple of hop (the cut
+    would fall inside a mel frame) or when s + T' exceeds sum(durations) (the alignment does not cover the cut audio).  This is
+    what makes a trimmed prompt usable with Megatts.synthesize_prompt_conditioned / synthesize_prosody_interpolated."""
+    tok, dur = np.asarray(phone_tokens).reshape(-1), np.asarray(durations).reshape(-1).astype(np.int64)
+    if tok.shape != dur.shape:
+        raise ValueError("phone_tokens and durations differ in length")
+    if start % hop != 0:
+        raise ValueError(f"start = {start} is not a multiple of the mel hop {hop}")
+    if not 0 <= start <= end:
+        raise ValueError(f"bad cut [{start}, {end})")
+    s, frames = start // hop, 1 + (end - start) // hop
+    if s + frames > int(dur.sum()):
+        raise ValueError(f"the cut frames [{s}, {s + frames}) reach beyond the alignment's {int(dur.sum())} frames")
+    last = np.cumsum(dur)
+    kept = np.clip(np.minimum(last, s + frames) - np.maximum(last - dur, s), 0, None)
+    keep = kept > 0
+    return tok[keep], kept[keep].astype(np.int32)
 
 
 def write_wav(path: str, samples, sample_rate: int = 16000, encoding: str = "PCM_F") -> None:

@@ -712,6 +712,27 @@ int mt2_peak_normalize(mt2_model* m, void* stream, const float* wav, const int32
     MT2_API_END
 }
 
+// models/megatts2.py:337  librosa.effects.trim: the frame count and the f32 threshold factor of the rule, without a HIP call
+int mt2_trim_query(long long L, float top_db, int* frames, float* factor) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(L >= 1 && L <= INT_MAX - 4 * MT2_TRIM_HOP, "L outside [1, 2^31 - 2048)");
+    MT2_REQUIRE(std::isfinite(top_db) && top_db > 0.0f, "top_db must be finite and > 0");
+    if (frames) *frames = trim_frames(L);
+    if (factor) *factor = trim_factor(top_db);
+    MT2_API_END
+}
+
+// models/megatts2.py:337  librosa.effects.trim(y, top_db) for a ragged batch
+int mt2_trim_silence(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, float top_db, float* out,
+                     int Lout_max, int32_t* bounds, float* energy, int F_max) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr && B >= 1 && L_max >= 1 && Lout_max >= 1, "bad arguments");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    trim_run(c, wav, lens, L_max, B, top_db, out, Lout_max, bounds, energy, F_max);
+    MT2_API_END
+}
+
 // :361-368 [+370]  zq = vq.decode(p_codes) repeated x8, cat([tc_latent_expand, zq]), decoder, optional vocoder - the part of
 // Megatts.forward behind the PLM, shared by mt2_synthesize_batch and mt2_synthesize_prompt_conditioned.  xdec: [D.R, H + Dq]
 // rows whose first H columns already hold the length-regulated tc_latents.

@@ -1617,6 +1617,46 @@ static void peak_normalize_run(const Ctx& c, const float* wav, const int* lens, 
     MT2_HIP(launch_scale_rows(wav, L_max, ip.dev(o_len), peak, out, L_max, L_max, B, c.s));
 }
 
+// models/megatts2.py:337  librosa.effects.trim: leading / trailing silence cut off by the rule of trim.hip.  The cut is found and
+// applied on the device; it travels to the host (one copy, one synchronise) only for a caller that asks for `bounds`.
+static void trim_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, float top_db, float* out, int Lout_max,
+                     int32_t* bounds, float* energy, int F_max) {
+    // everything is checked before the first launch: a refused call leaves `out` as it was
+    MT2_REQUIRE(std::isfinite(top_db) && top_db > 0.0f, "top_db must be finite and > 0");
+    MT2_REQUIRE(wav != nullptr && out != nullptr && lens != nullptr && ((uintptr_t)wav & 3) == 0 && ((uintptr_t)out & 3) == 0, "bad buffers");
+    int mx = 0;
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
+        mx = std::max(mx, lens[b]);
+    }
+    MT2_REQUIRE(mx <= INT_MAX - 4 * MT2_TRIM_HOP && B <= 65535, "waveform too long or batch too large");
+    MT2_REQUIRE(Lout_max >= mx, "Lout_max smaller than the longest utterance (the cut is not known before the call)");
+    MT2_REQUIRE(energy == nullptr || F_max >= trim_frames(mx), "F_max smaller than 1 + max length / 512");
+    const uintptr_t w0 = (uintptr_t)wav, w1 = w0 + sizeof(float) * (size_t)B * L_max;
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + sizeof(float) * (size_t)B * Lout_max;
+    MT2_REQUIRE(o1 <= w0 || w1 <= o0, "out overlaps wav");
+    IntPlan ip;
+    const int o_len = ip.add(std::vector<int>(lens, lens + B));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    TrimP p{};
+    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = mx; p.B = B;
+    p.factor = trim_factor(top_db);
+    p.NB = (mx + MT2_TRIM_HOP - 1) / MT2_TRIM_HOP;
+    p.sums = c.ws.get<float>((size_t)B * p.NB);
+    unsigned* words = c.ws.get<unsigned>((size_t)3 * B);          // peak | first | last
+    p.peak = words; p.first = words + B; p.last = reinterpret_cast<int*>(words + 2 * B);
+    p.out = out; p.Lout_max = Lout_max; p.energy = energy; p.F_max = F_max;
+    MT2_HIP(hipMemsetAsync(p.peak, 0, sizeof(unsigned) * B, c.s));
+    MT2_HIP(hipMemsetAsync(p.first, 0xFF, sizeof(unsigned) * 2 * B, c.s));      // first = UINT_MAX, last = -1
+    MT2_HIP(launch_trim(p, c.s));
+    if (bounds) {
+        unsigned* st = static_cast<unsigned*>(c.m.pinned().alloc(sizeof(unsigned) * 2 * B));      // handle-owned staging
+        MT2_HIP(hipMemcpyAsync(st, p.first, sizeof(unsigned) * 2 * B, hipMemcpyDeviceToHost, c.s));
+        MT2_HIP(hipStreamSynchronize(c.s));
+        for (int b = 0; b < B; ++b) trim_bounds(st[b], (int)st[B + b], lens[b], &bounds[2 * b], &bounds[2 * b + 1]);
+    }
+}
+
 }  // namespace mt2
 
 // the C ABI lives in capi.hip and includes this translation unit's helpers

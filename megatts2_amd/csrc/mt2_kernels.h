@@ -378,4 +378,30 @@ hipError_t launch_peak_rows(const float* x, long long stride, const int* len, in
 hipError_t launch_scale_rows(const float* x, long long xstride, const int* len, const unsigned* peak, float* out, long long ostride,
                              int width, int B, hipStream_t s);
 
+// ---- leading / trailing silence of prompt audio (trim.hip; reference models/megatts2.py:337, librosa.effects.trim) ------------
+// host only, no HIP call: F = 1 + L / 512 frames, c = (float)pow(10.0, -top_db / 10.0)
+int trim_frames(long long L);
+float trim_factor(float top_db);
+// The cut of one utterance from the two words the kernels leave (first kept frame by atomic min from UINT_MAX, last by atomic max
+// from -1): [512 first, min(L, 512 (last + 1))).  Words that name no kept frame - or no frame of this utterance, which only a
+// non-finite sample can bring about - leave the utterance whole, so the cut is inside [0, L] whatever the input.
+__host__ __device__ inline void trim_bounds(unsigned first, int last, int L, int* start, int* end) {
+    const bool whole = last < 0 || last >= 1 + L / 512 || first > (unsigned)last;
+    const long long e = 512ll * ((long long)last + 1);
+    *start = whole ? 0 : 512 * (int)first;
+    *end = whole || e > L ? L : (int)e;
+}
+// Four launches on one stream, each one grid over the ragged batch: block sums -> frame energies + peak -> first / last kept frame
+// -> compaction copy.  The caller zeroes peak[], sets first[] to UINT_MAX and last[] to -1 in front.
+struct TrimP {
+    const float* wav; int L_max;              // [B, L_max]; samples at or beyond len[b] are never read
+    const int* len; int max_len, B;           // device [B]; max_b len[b]
+    float factor;                             // trim_factor(top_db)
+    float* sums; int NB;                      // scratch [B, NB], NB >= ceil(max_len / 512)
+    unsigned* peak; unsigned* first; int* last;      // scratch [B] each
+    float* out; int Lout_max;                 // [B, Lout_max], Lout_max >= max_len
+    float* energy; int F_max;                 // optional [B, F_max], F_max >= 1 + max_len / 512: e[f], zeros in [F_b, F_max)
+};
+hipError_t launch_trim(const TrimP& p, hipStream_t s);
+
 }  // namespace mt2

@@ -40,11 +40,13 @@ def _frontend():
     return _FRONTEND
 
 
-def extract_mel_spec(samples, sample_rate: Optional[int] = None):
+def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None):
     """reference modules/tokenizer.py:107-125: 1-D waveform tensor (16 kHz) -> mel [80, T] (the reference
     returns channels first and `Megatts.forward` transposes it, models/megatts2.py:339).  Runs on the GPU
     (runtime.MelFrontEnd); a [B, L] input gives [B, 80, T].  sample_rate: the rate of `samples` when it is not
-    16 kHz - they are resampled on the GPU first (MelFrontEnd.resample, not normalised)."""
+    16 kHz - they are resampled on the GPU first (MelFrontEnd.resample, not normalised).  trim_db: leading and
+    trailing silence is cut off first (MelFrontEnd.trim, `librosa.effects.trim(y, top_db=trim_db)` of :337; a batch
+    is cut per row, T follows the longest row and the frames behind a shorter row's own are zero)."""
     import torch
     fe = _frontend()
     x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
@@ -52,7 +54,10 @@ def extract_mel_spec(samples, sample_rate: Optional[int] = None):
     x = (x if batched else x.unsqueeze(0)).to("cuda", torch.float32)
     if sample_rate is not None and int(sample_rate) != fe.audio.sample_rate:
         x = fe.resample(x, int(sample_rate))[0]
-    mel = fe(x).transpose(1, 2)
+    lens = None
+    if trim_db is not None:
+        x, lens, _ = fe.trim(x, top_db=trim_db)
+    mel = fe(x, lens).transpose(1, 2)
     return mel if batched else mel[0]
 
 
@@ -392,7 +397,9 @@ class Megatts:
         on (reference modules/datamodule.py:161-177,196-212) at inference: the prompt's length-regulated, max-pooled
         tc_latents in front of the target's, the prompt's VQ-PE codes behind the BOS, greedy decoding from there.
         `prompt_phone_tokens` int64 [B, Npp] / `prompt_durations` int32 [B, Npp] are the prompt utterance's own phones and
-        alignment (sum = prompt frames).  ONE native call (mt2_synthesize_prompt_conditioned): the MRTE mel encoder runs once
+        alignment (sum = prompt frames).  A prompt whose silence was cut off (`MelFrontEnd.from_audio(trim_db=...,
+        return_bounds=True)`) needs its alignment cut the same way: `audio_io.trim_alignment(prompt_phone_tokens,
+        prompt_durations, start, end)`.  ONE native call (mt2_synthesize_prompt_conditioned): the MRTE mel encoder runs once
         for both phone sets, the prompt's VQ-PE beside the ADM on the handle's side stream, nothing leaves the device between
         the stages but the durations.  `synthesize_prompt_conditioned_staged` is the same computation as ten C-ABI stage
         calls (round 3's form; kept as the cross-check of the fused entry point)."""
@@ -540,10 +547,13 @@ class Megatts:
     # is loaded (mono), peak-normalised, turned into a mel by extract_mel_spec (on the GPU) and the mels
     # are concatenated along time (:332-344).  A file at another rate than 16 kHz is resampled as `librosa.load(wav,
     # sr=16000)` does it there (:335) - on the GPU (MelFrontEnd.from_audio; its own filter, parity with librosa's
-    # unpinned); resample=False rejects such a file instead.  Text -> phone ids is the reference's G2P (pypinyin + MFA
+    # unpinned); resample=False rejects such a file instead.  trim_db: the leading and trailing silence of every prompt
+    # file is cut off behind the normalisation, `librosa.effects.trim(y, top_db=trim_db)` of :337 (commented out there:
+    # its prompts are pre-cut) - on the GPU as well (MelFrontEnd.from_audio(trim_db=...), 16 kHz files included); None
+    # leaves the audio whole.  Text -> phone ids is the reference's G2P (pypinyin + MFA
     # dictionary, host side, outside the hot path); when it is not importable pass `phone_tokens` instead.
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
-                phones: Optional[Sequence[str]] = None, resample: bool = True):
+                phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None):
         import torch
         from . import audio_io
         wavs = sorted(glob.glob(f"{wavs_dir}/*.wav"))
@@ -552,11 +562,11 @@ class Megatts:
 
         def prompt_mel(w):
             y, sr = audio_io.read_wav(w)
-            if sr == HIFIGAN_SR:          # audio_io.load_audio's two steps
+            if sr == HIFIGAN_SR and trim_db is None:          # audio_io.load_audio's two steps
                 return extract_mel_spec(torch.from_numpy(audio_io.normalize(y))).transpose(0, 1)
-            if not resample:
+            if sr != HIFIGAN_SR and not resample:
                 raise ValueError(f"{w}: {sr} Hz, expected {HIFIGAN_SR} Hz (resample=False)")
-            return _frontend().from_audio(torch.from_numpy(y).unsqueeze(0).cuda(), sr)[0][0]
+            return _frontend().from_audio(torch.from_numpy(y).unsqueeze(0).cuda(), sr, trim_db=trim_db)[0][0]
 
         mels = [prompt_mel(w) for w in wavs]
         mels_prompt = mels[0]

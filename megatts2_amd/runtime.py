@@ -24,6 +24,7 @@ MT2_RUN_PLM, MT2_RUN_VOCODER, MT2_SKIP_ADM, MT2_PROMPT_VQPE = 1, 2, 4, 8
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 ACT_LOGCLAMP = 4          # epilogue only: log(max(v, pro_slope))
 MT2_RESAMPLE_NORMALIZE = 1
+TRIM_FRAME, TRIM_HOP = 2048, 512      # MT2_TRIM_FRAME, MT2_TRIM_HOP
 
 
 class NativeError(RuntimeError):
@@ -86,6 +87,8 @@ def load_library():
     lib.mt2_model_destroy.argtypes = [C.c_void_p]
     lib.mt2_model_destroy.restype = None
     lib.mt2_resample_query.argtypes = [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 4
+    lib.mt2_trim_query.argtypes = [C.c_longlong, C.c_float, C.c_void_p, C.c_void_p]
+    lib.mt2_trim_silence.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     _LIB = lib
     return lib
 
@@ -678,10 +681,37 @@ class MelFrontEnd:
                                      MT2_RESAMPLE_NORMALIZE if normalize else 0, _ptr(out), out.shape[1], _iptr(out_lens)))
         return out, out_lens
 
-    def from_audio(self, wav, sr_in: int, lens=None):
+    def trim(self, wav, lens=None, top_db: float = 60.0, out=None, return_energy: bool = False):
+        """`librosa.effects.trim(y, top_db)` of the reference (models/megatts2.py:337; top_db defaults to librosa's 60, the reference
+        writes 20) for a ragged batch on the device, by the rule of csrc/trim.hip - frames of 2048 samples every 512, a frame kept
+        while its energy is above max energy * 10^(-top_db / 10); parity with librosa is unpinned.  wav f32 [B, L] (device) ->
+        (out f32 [B, max lens], out_lens int32 [B], bounds int32 [B, 2]) with out[b, :out_lens[b]] = wav[b, start:end] exactly and
+        zeros behind; an all-zero utterance is left whole.  Samples beyond lens[b] are never read.  out: a contiguous f32
+        [B, >= max lens] device tensor to write into (not wav).  return_energy: a fourth result, the frame energies f32
+        [B, 1 + max lens // 512] (device).  The call waits for the device once, for the bounds."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+        assert ln.shape == (B,)
+        if out is None:
+            out = torch.empty(B, max(int(ln.max()), 1), device=wav.device, dtype=torch.float32)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        F = 1 + max(int(ln.max()), 0) // TRIM_HOP
+        energy = torch.empty(B, F, device=wav.device, dtype=torch.float32) if return_energy else None
+        bounds = np.zeros((B, 2), np.int32)
+        _check(self.lib.mt2_trim_silence(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, float(top_db), _ptr(out), out.shape[1],
+                                         _iptr(bounds), _ptr(energy), F))
+        res = (out, bounds[:, 1] - bounds[:, 0], bounds)
+        return res + (energy,) if return_energy else res
+
+    def from_audio(self, wav, sr_in: int, lens=None, trim_db: Optional[float] = None, return_bounds: bool = False):
         """Prompt audio at any sample rate -> (mel [B, T, n_mels], mel_lens): resample to audio.sample_rate, peak-normalise and
         extract the mel (models/megatts2.py:335-336,339) with no host round trip.  Audio that already has that rate is only
-        normalised, by the same kernels."""
+        normalised, by the same kernels.  trim_db: leading / trailing silence is cut off between the normalisation and the mel
+        (`trim`, :337 - the reference's order); None leaves the audio whole.  return_bounds: a third result, int32 [B, 2] = the
+        (start, end) of each utterance within its resampled audio."""
         import torch
         assert wav.is_cuda and wav.dim() == 2
         wav = wav.contiguous().to(torch.float32)
@@ -692,7 +722,13 @@ class MelFrontEnd:
             _check(self.lib.mt2_peak_normalize(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, _ptr(y)))
         else:
             y, ln = self.resample(wav, sr_in, lens, normalize=True)
-        return self(y, ln), 1 + ln // self.audio.hop_length
+        bounds = None
+        if trim_db is not None:
+            y, ln, bounds = self.trim(y, ln, trim_db)
+        res = (self(y, ln), 1 + ln // self.audio.hop_length)
+        if return_bounds:
+            res += (np.stack([np.zeros_like(ln), ln], axis=1) if bounds is None else bounds,)
+        return res
 
 
 # ---- kernel-level entry points -------------------------------------------------------------------------
@@ -1200,6 +1236,14 @@ def resample_query(sr_in: int, sr_out: int, L: int = 0):
     lo, o, n, k = C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0)
     _check(load_library().mt2_resample_query(int(sr_in), int(sr_out), int(L), C.byref(lo), C.byref(o), C.byref(n), C.byref(k)))
     return lo.value, o.value, n.value, k.value
+
+
+def trim_query(L: int, top_db: float):
+    """mt2_trim_query (no device needed) -> (frames, factor): F = 1 + L // 512 and the f32 factor 10^(-top_db / 10) a frame's
+    energy is compared with, as a numpy float32."""
+    f, c = C.c_int(0), C.c_float(0)
+    _check(load_library().mt2_trim_query(int(L), float(top_db), C.byref(f), C.byref(c)))
+    return f.value, np.float32(c.value)
 
 
 def resample_table(sr_in: int, sr_out: int) -> np.ndarray:

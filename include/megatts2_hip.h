@@ -282,6 +282,55 @@ int mt2_trim_silence(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/
                      float top_db, float* out /*[B, Lout_max]*/, int Lout_max, int32_t* bounds /*host [B][2], may be NULL*/,
                      float* energy /*[B, F_max] or NULL*/, int F_max);
 
+/* ---- dynamic time warping of one mel onto another (csrc/dtw.hip).  Megatts.align_prompt warps the model's own synthesis of the
+ * prompt's phones onto the real prompt mel and carries the phone boundaries through the warp: the `prompt_durations` of
+ * mt2_synthesize_prompt_conditioned without the Montreal Forced Aligner TextGrids the reference reads (prepare_ds.py,
+ * utils/textgrid.py; out of scope here).  The same call is the DTW mel distance between two utterances.  The rule is our own, held
+ * to its own restatement (tests/dtw_ref.py); alignment quality on real speech is unpinned.  Per utterance b, X f32 [Tx, D] (the
+ * synthetic mel), Y f32 [Ty, D] (the real one), Tx, Ty >= 1, D >= 1 (80 in the model):
+ *   cost        c[i, j] = sum_k (x[i, k] - y[j, k])^2 in f32, ONE chain over k ascending: acc = 0; d = x - y; acc = fmaf(d, d, acc).
+ *               No split across lanes, no atomics, an order that does not depend on the tile: c depends on the two rows alone,
+ *               and a ragged batch is bit-identical to its utterances alone.
+ *   accumulate  one f32 add per cell: A[0, 0] = c[0, 0];  A[i, 0] = c[i, 0] + A[i-1, 0];  A[0, j] = c[0, j] + A[0, j-1];
+ *               otherwise A[i, j] = c[i, j] + min(A[i-1, j-1], A[i-1, j], A[i, j-1])
+ *   direction   diagonal if A[i-1, j-1] <= both others; else up (i-1, j) if A[i-1, j] <= A[i, j-1]; else left (i, j-1).
+ *               Row 0 is always left, column 0 always up.  Given c, A and the directions are exactly reproducible in numpy float32.
+ *   path        backtracked from (Tx-1, Ty-1) to (0, 0); reported as lo[j] / hi[j], the smallest / largest i on the path in column
+ *               j.  Steps are (1,1), (1,0), (0,1), so lo[0] = 0, hi[Ty-1] = Tx-1, lo[j+1] in {hi[j], hi[j] + 1}: lo / hi hold the
+ *               whole path.  steps = its number of cells, total = A[Tx-1, Ty-1].  Entries j >= Ty_b of lo / hi are -1.
+ *   durations   synthetic durations s[p] >= 0 over Np phones, sum s = Tx, cum[p] = sum_{q<p} s[q]: real frame j belongs to the phone
+ *               p with cum[p] <= hi[j] < cum[p+1]; dur[p] counts them = lower_bound(hi, cum[p+1]) - lower_bound(hi, cum[p]) (hi is
+ *               non-decreasing); sum dur = Ty exactly.  A phone with s[p] = 0, or one swallowed by a vertical run, gets 0
+ *               (mt2_synthesize_prompt_conditioned accepts zero durations).
+ * Inputs must be finite; a non-finite value does not fault and still gives a path inside the matrix, nothing more.
+ * Refused (error, nothing launched, outputs untouched - never a clamp or a silent band): B < 1 or D < 1; Tx_max or Ty_max outside
+ * [1, MT2_DTW_MAX_LEN]; a length outside [1, its max]; B > 65535. */
+#define MT2_DTW_MAX_LEN 4096        /* cap of Tx_max and Ty_max */
+#define MT2_DTW_DIR_COLS 16         /* columns of 2-bit directions per u32 scratch word */
+/* Arena bytes one mt2_dtw_align call of this geometry takes at most; host only, no HIP call.  With r(n) = n rounded up to 256:
+ *   r(4 B ceil(Tx_max / 64) 64 ceil((Ty_max + 63) / 64) 64)  the costs in the skewed layout the accumulation reads (strips of 64
+ *   rows, each 64 lanes wide over the Ty + 63 steps of its walk, in whole periods of 64; taken whether or not `cost` is given)
+ *   + r(4 B Tx_max ceil(Ty_max / 16))  the packed directions  +  r(4 (2 B + 8))  the lengths' one upload */
+int mt2_dtw_query(int Tx_max, int Ty_max, int D, int B, long long* workspace_bytes);
+/* X f32 [B, Tx_max, D], Y f32 [B, Ty_max, D] (device; rows at or beyond x_lens[b] / y_lens[b] are never read) -> lo, hi int32
+ * [B, Ty_max], steps int32 [B], total f32 [B] (device).  x_lens, y_lens: host int32 [B].  cost, acc (device f32 [B, Tx_max, Ty_max],
+ * each may be NULL): c and A; cells outside an utterance's Tx_b x Ty_b are left untouched.  Scratch comes from the handle's arena;
+ * `m` may be a bare handle.  The call only enqueues, it does not synchronise. */
+int mt2_dtw_align(mt2_model* m, void* stream, const float* X, const int32_t* x_lens /*host*/, int Tx_max, const float* Y,
+                  const int32_t* y_lens /*host*/, int Ty_max, int D, int B, int32_t* lo, int32_t* hi, int32_t* steps, float* total,
+                  float* cost /*or NULL*/, float* acc /*or NULL*/);
+/* The durations rule for a batch: hi int32 [B, Ty_max] (device, as mt2_dtw_align left it for these y_lens), syn_dur host int32
+ * [B, Np_max] (entries at or beyond phone_lens[b] are ignored), phone_lens host int32 [B] -> dur_out_host int32 [B, Np_max], zeros at
+ * or beyond phone_lens[b].  One copy to the host and ONE stream synchronise inside the call, as mt2_trim_silence does for its
+ * bounds.  The x-length is not an argument: by the path rule it is hi[b, y_lens[b] - 1] + 1, which travels to the host in the same
+ * copy, and sum_p syn_dur[b, p] is compared with it there.  Refused before anything is launched: B < 1, Np_max < 1, Ty_max outside
+ * [1, MT2_DTW_MAX_LEN], a y-length outside [1, Ty_max], a phone count outside [1, Np_max], a negative synthetic duration, a sum
+ * of them outside [1, MT2_DTW_MAX_LEN].  Refused behind the copy, with dur_out_host untouched: hi not covering Ty
+ * (hi[b, y_lens[b] - 1] < 0, or the durations not summing to y_lens[b]), or sum_p syn_dur[b, p] != hi[b, y_lens[b] - 1] + 1. */
+int mt2_align_durations(mt2_model* m, void* stream, const int32_t* hi, const int32_t* y_lens /*host*/, int Ty_max,
+                        const int32_t* syn_dur /*host*/, const int32_t* phone_lens /*host*/, int Np_max, int B,
+                        int32_t* dur_out_host);
+
 /* ---- the whole of Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) for a batch,
  * activations staying in the packed internal layout between stages.
  *   forced_dur   (host, optional) int32 [B, Np_max]: replaces the ADM's integer durations AFTER the ADM

@@ -733,6 +733,45 @@ int mt2_trim_silence(mt2_model* m, void* stream, const float* wav, const int32_t
     MT2_API_END
 }
 
+// DTW of a synthesised mel onto a real one (dtw.hip): the arena bytes of one call, without a HIP call
+int mt2_dtw_query(int Tx_max, int Ty_max, int D, int B, long long* workspace_bytes) {
+    MT2_API_BEGIN
+    dtw_check_geometry(Tx_max, Ty_max, D, B);
+    if (workspace_bytes) *workspace_bytes = dtw_workspace_bytes(Tx_max, Ty_max, B);
+    MT2_API_END
+}
+
+// every refusal is decided on the host before the first HIP call
+int mt2_dtw_align(mt2_model* m, void* stream, const float* X, const int32_t* x_lens, int Tx_max, const float* Y, const int32_t* y_lens,
+                  int Ty_max, int D, int B, int32_t* lo, int32_t* hi, int32_t* steps, float* total, float* cost, float* acc) {
+    MT2_API_BEGIN
+    dtw_check_geometry(Tx_max, Ty_max, D, B);
+    dtw_check_lens(x_lens, Tx_max, y_lens, Ty_max, B);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    dtw_run(c, X, x_lens, Tx_max, Y, y_lens, Ty_max, D, B, lo, hi, steps, total, cost, acc);
+    MT2_API_END
+}
+
+int mt2_align_durations(mt2_model* m, void* stream, const int32_t* hi, const int32_t* y_lens, int Ty_max, const int32_t* syn_dur,
+                        const int32_t* phone_lens, int Np_max, int B, int32_t* dur_out_host) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(Np_max >= 1, "Np_max < 1");
+    MT2_REQUIRE(Ty_max >= 1 && Ty_max <= MT2_DTW_MAX_LEN, "Ty_max outside [1, MT2_DTW_MAX_LEN]");
+    MT2_REQUIRE(y_lens != nullptr && syn_dur != nullptr && phone_lens != nullptr && dur_out_host != nullptr, "a host array is NULL");
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(y_lens[b] >= 1 && y_lens[b] <= Ty_max, "y length outside [1, Ty_max]");
+        MT2_REQUIRE(phone_lens[b] >= 1 && phone_lens[b] <= Np_max, "phone count outside [1, Np_max]");
+    }
+    MT2_REQUIRE(m != nullptr && hi != nullptr, "null model handle or hi");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    align_durations_run(c, hi, y_lens, Ty_max, syn_dur, phone_lens, Np_max, B, dur_out_host);
+    MT2_API_END
+}
+
 // :361-368 [+370]  zq = vq.decode(p_codes) repeated x8, cat([tc_latent_expand, zq]), decoder, optional vocoder - the part of
 // Megatts.forward behind the PLM, shared by mt2_synthesize_batch and mt2_synthesize_prompt_conditioned.  xdec: [D.R, H + Dq]
 // rows whose first H columns already hold the length-regulated tc_latents.

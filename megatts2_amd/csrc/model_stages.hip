@@ -1657,6 +1657,88 @@ static void trim_run(const Ctx& c, const float* wav, const int* lens, int L_max,
     }
 }
 
+// The lengths of a DTW call, checked before anything else (host only)
+static void dtw_check_geometry(int Tx_max, int Ty_max, int D, int B) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(D >= 1, "D < 1");
+    MT2_REQUIRE(Tx_max >= 1 && Tx_max <= MT2_DTW_MAX_LEN, "Tx_max outside [1, MT2_DTW_MAX_LEN]");
+    MT2_REQUIRE(Ty_max >= 1 && Ty_max <= MT2_DTW_MAX_LEN, "Ty_max outside [1, MT2_DTW_MAX_LEN]");
+}
+static void dtw_check_lens(const int* x_lens, int Tx_max, const int* y_lens, int Ty_max, int B) {
+    MT2_REQUIRE(x_lens != nullptr && y_lens != nullptr, "x_lens / y_lens is NULL");
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(x_lens[b] >= 1 && x_lens[b] <= Tx_max, "x length outside [1, Tx_max]");
+        MT2_REQUIRE(y_lens[b] >= 1 && y_lens[b] <= Ty_max, "y length outside [1, Ty_max]");
+    }
+}
+
+// DTW of X onto Y by the rule of dtw.hip: cost -> accumulate -> backtrack on the caller's stream, nothing else
+static void dtw_run(const Ctx& c, const float* X, const int* x_lens, int Tx_max, const float* Y, const int* y_lens, int Ty_max, int D,
+                    int B, int* lo, int* hi, int* steps, float* total, float* cost, float* acc) {
+    MT2_REQUIRE(X != nullptr && Y != nullptr && lo != nullptr && hi != nullptr && steps != nullptr && total != nullptr, "bad buffers");
+    DtwP p{};
+    p.X = X; p.Tx_max = Tx_max; p.Y = Y; p.Ty_max = Ty_max; p.D = D; p.B = B;
+    p.max_tx = *std::max_element(x_lens, x_lens + B); p.max_ty = *std::max_element(y_lens, y_lens + B);
+    IntPlan ip;
+    const int o_x = ip.add(std::vector<int>(x_lens, x_lens + B)), o_y = ip.add(std::vector<int>(y_lens, y_lens + B));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    p.x_len = ip.dev(o_x); p.y_len = ip.dev(o_y);
+    p.cost = cost;
+    p.S_max = (Tx_max + 63) / 64; p.TS = (int)dtw_skew_steps(Ty_max);
+    p.skew = c.ws.get<float>((size_t)B * p.S_max * p.TS * 64);
+    p.DW = (int)dtw_dir_words(Ty_max);
+    p.dirs = c.ws.get<unsigned>((size_t)B * Tx_max * p.DW);
+    p.acc = acc; p.lo = lo; p.hi = hi; p.steps = steps; p.total = total;
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(launch_dtw_cost(p, c.s));
+    st.mark("dtw_cost");
+    MT2_HIP(launch_dtw_accumulate(p, c.s));
+    st.mark("dtw_accumulate");
+    MT2_HIP(launch_dtw_backtrack(p, c.s));
+    st.mark("dtw_backtrack");
+    st.finish();
+}
+
+// phone durations of the real utterance from the path's hi[] and the synthetic durations (dtw.hip, "durations"); the x-length is
+// read from the path itself (hi[Ty_b - 1] + 1) in the call's one copy to the host
+static void align_durations_run(const Ctx& c, const int* hi, const int* y_lens, int Ty_max, const int* syn_dur, const int* phone_lens,
+                                int Np_max, int B, int* dur_out_host) {
+    std::vector<int> cum((size_t)B * (Np_max + 1), 0);
+    for (int b = 0; b < B; ++b) {
+        long long sum = 0;
+        for (int q = 0; q < Np_max; ++q) {
+            if (q < phone_lens[b]) {
+                MT2_REQUIRE(syn_dur[(size_t)b * Np_max + q] >= 0, "negative synthetic duration");
+                sum += syn_dur[(size_t)b * Np_max + q];
+                MT2_REQUIRE(sum <= MT2_DTW_MAX_LEN, "synthetic durations sum beyond MT2_DTW_MAX_LEN");
+            }
+            cum[(size_t)b * (Np_max + 1) + q + 1] = (int)sum;
+        }
+        MT2_REQUIRE(sum >= 1, "synthetic durations sum to 0");
+    }
+    IntPlan ip;
+    const int o_y = ip.add(std::vector<int>(y_lens, y_lens + B)), o_n = ip.add(std::vector<int>(phone_lens, phone_lens + B));
+    const int o_cum = ip.add(cum);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    AlignDurP p{};
+    p.hi = hi; p.Ty_max = Ty_max; p.y_len = ip.dev(o_y); p.cum = ip.dev(o_cum); p.np_len = ip.dev(o_n); p.Np_max = Np_max; p.B = B;
+    const size_t n = (size_t)B * Np_max + B;
+    p.dur = c.ws.get<int>(n); p.last = p.dur + (size_t)B * Np_max;
+    MT2_HIP(launch_dtw_durations(p, c.s));
+    int* st = static_cast<int*>(c.m.pinned().alloc(sizeof(int) * n));      // handle-owned staging
+    MT2_HIP(hipMemcpyAsync(st, p.dur, sizeof(int) * n, hipMemcpyDeviceToHost, c.s));
+    MT2_HIP(hipStreamSynchronize(c.s));
+    for (int b = 0; b < B; ++b) {
+        const int last = st[(size_t)B * Np_max + b], tx = cum[(size_t)b * (Np_max + 1) + Np_max];
+        long long sum = 0;
+        for (int q = 0; q < Np_max; ++q) sum += st[(size_t)b * Np_max + q];
+        MT2_REQUIRE(last >= 0 && last < MT2_DTW_MAX_LEN && sum == y_lens[b], "hi does not cover the y length");
+        MT2_REQUIRE(tx == last + 1, "synthetic durations do not sum to the x length of the path (hi[Ty - 1] + 1)");
+    }
+    std::copy(st, st + (size_t)B * Np_max, dur_out_host);
+}
+
 }  // namespace mt2
 
 // the C ABI lives in capi.hip and includes this translation unit's helpers

@@ -404,4 +404,37 @@ struct TrimP {
 };
 hipError_t launch_trim(const TrimP& p, hipStream_t s);
 
+// ---- dynamic time warping of a synthesised mel onto a real one (dtw.hip; the rule is in its header and in megatts2_hip.h) --------
+// host only, no HIP call: u32 words of packed directions per row, and the arena bytes of one mt2_dtw_align call
+long long dtw_dir_words(int Ty_max);
+long long dtw_skew_steps(int Ty_max);          // 64 ceil((Ty_max + 63) / 64): steps a strip of 64 skewed rows takes, in whole periods
+long long dtw_workspace_bytes(int Tx_max, int Ty_max, int B);
+// Three launches on one stream, each over the ragged batch: cost -> accumulate (one workgroup per utterance) -> backtrack (one wave
+// per utterance).  Cells outside an utterance's Tx_b x Ty_b are neither read nor written.
+struct DtwP {
+    const float* X; int Tx_max;               // [B, Tx_max, D]; rows at or beyond x_len[b] are never read
+    const float* Y; int Ty_max;               // [B, Ty_max, D]; likewise y_len[b]
+    int D, B;
+    const int* x_len; const int* y_len;       // device [B]
+    int max_tx, max_ty;                       // max_b of the lengths
+    float* cost;                              // optional [B, Tx_max, Ty_max]: c in the caller's layout
+    float* skew; int S_max, TS;               // scratch [B, S_max, TS, 64]: c[64 s + l, t - l] at [s][t][l] - what the 64 lanes of a strip
+                                              // read at step t is one contiguous line; S_max >= ceil(max_tx / 64), TS >= dtw_skew_steps(max_ty)
+    unsigned* dirs; int DW;                   // scratch [B, Tx_max, DW], DW >= dtw_dir_words(max_ty): 2 bits a cell, 16 columns a word
+    float* acc;                               // optional [B, Tx_max, Ty_max]: A itself
+    int* lo; int* hi;                         // [B, Ty_max]; -1 in [Ty_b, Ty_max)
+    int* steps; float* total;                 // [B]
+};
+hipError_t launch_dtw_cost(const DtwP& p, hipStream_t s);
+hipError_t launch_dtw_accumulate(const DtwP& p, hipStream_t s);
+hipError_t launch_dtw_backtrack(const DtwP& p, hipStream_t s);
+// dur[b, p] = lower_bound(hi_b, cum[b, p+1]) - lower_bound(hi_b, cum[b, p]) for p < np_len[b], 0 up to Np_max; last[b] = hi_b[Ty_b - 1]
+struct AlignDurP {
+    const int* hi; int Ty_max;                // [B, Ty_max]
+    const int* y_len; const int* cum;         // device [B]; [B, Np_max + 1] exclusive prefix sums of the synthetic durations
+    const int* np_len; int Np_max, B;         // device [B]
+    int* dur; int* last;                      // [B, Np_max]; [B]
+};
+hipError_t launch_dtw_durations(const AlignDurP& p, hipStream_t s);
+
 }  // namespace mt2

@@ -390,33 +390,66 @@ class Megatts:
                                             run_plm=forced_codes is None, vocoder=vocoder, return_aux=return_aux,
                                             sampling=sampling, seeds=seeds)
 
-    def synthesize_prompt_conditioned(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations, phone_lens=None,
+    def align_prompt(self, prompt_phone_tokens, mels, prompt_phone_lens=None, mel_lens=None, return_aux: bool = False):
+        """The phone-level alignment of a prompt utterance to its own phones, made by the model itself - the `prompt_durations` of
+        `synthesize_prompt_conditioned` / `synthesize_prosody_interpolated` without the Montreal Forced Aligner TextGrids the
+        reference reads during data preparation (prepare_ds.py, utils/textgrid.py).  `prompt_phone_tokens` int64 [B, Npp], `mels`
+        f32 [B, Tp, 80] -> host int32 [B, Npp], row b summing to mel_lens[b] exactly (a phone may get 0).  Three steps: `synthesize`
+        on the prompt's own phones under the prompt's own timbre (greedy PLM, no vocoder: the ADM's durations and a synthetic mel);
+        `dtw` of that mel onto `mels` (csrc/dtw.hip); `align_durations`, which gives real frame j to the phone that owns the
+        synthetic frame hi[j].  Always greedy, so the alignment is deterministic.  return_aux: (durations, dict) with the synthetic
+        durations `syn_dur` (host int32 [B, Npp]), `syn_lens`, and the path's lo, hi, steps, total (device).  Both lengths of the
+        warp are capped at runtime.DTW_MAX_LEN = 4096 frames (MT2_DTW_MAX_LEN): a prompt longer than that, or a synthesis of it that
+        comes out longer (the ADM may give a phone up to 128 frames - untrained durations on many phones), is refused with a
+        NativeError from mt2_dtw_align, never clamped.  Alignment quality on real speech is unpinned: there is no aligner here to
+        compare with."""
+        nat = self.native
+        B = prompt_phone_tokens.shape[0]
+        ml = nat._lens(mel_lens, B, mels.shape[1])
+        ppl = nat._lens(prompt_phone_lens, B, prompt_phone_tokens.shape[1])
+        syn, syn_lens, aux = nat.synthesize_batch(prompt_phone_tokens, ppl, mels, ml, return_aux=True)
+        syn_lens = np.asarray(syn_lens, np.int32)
+        syn_dur = aux["dur"].cpu().numpy().astype(np.int32)
+        path = nat.dtw(syn[:, :max(int(syn_lens.max()), 1)], mels, syn_lens, ml)
+        dur = nat.align_durations(path["hi"], ml, syn_dur, ppl)
+        if not return_aux:
+            return dur
+        path.update(syn_dur=syn_dur, syn_lens=syn_lens)
+        return dur, path
+
+    def synthesize_prompt_conditioned(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations=None, phone_lens=None,
                                       mel_lens=None, prompt_phone_lens=None, forced_durations=None, vocoder: bool = False,
                                       return_aux: bool = False, sampling=None, seeds=None):
         """Synthesis with the PLM conditioned on the prompt's prosody - the layout the PLM is trained
         on (reference modules/datamodule.py:161-177,196-212) at inference: the prompt's length-regulated, max-pooled
         tc_latents in front of the target's, the prompt's VQ-PE codes behind the BOS, greedy decoding from there.
         `prompt_phone_tokens` int64 [B, Npp] / `prompt_durations` int32 [B, Npp] are the prompt utterance's own phones and
-        alignment (sum = prompt frames).  A prompt whose silence was cut off (`MelFrontEnd.from_audio(trim_db=...,
+        alignment (sum = prompt frames); `prompt_durations=None` takes the alignment from `align_prompt` (the model's own synthesis
+        of the prompt warped onto it by DTW), a given array exactly the path it always took.  A prompt whose silence was cut off (`MelFrontEnd.from_audio(trim_db=...,
         return_bounds=True)`) needs its alignment cut the same way: `audio_io.trim_alignment(prompt_phone_tokens,
         prompt_durations, start, end)`.  ONE native call (mt2_synthesize_prompt_conditioned): the MRTE mel encoder runs once
         for both phone sets, the prompt's VQ-PE beside the ADM on the handle's side stream, nothing leaves the device between
         the stages but the durations.  `synthesize_prompt_conditioned_staged` is the same computation as ten C-ABI stage
         calls (round 3's form; kept as the cross-check of the fused entry point)."""
+        if prompt_durations is None:
+            prompt_durations = self.align_prompt(prompt_phone_tokens, mels, prompt_phone_lens, mel_lens)
         out = self.native.synthesize_prompt_conditioned(phone_tokens, phone_lens, mels, mel_lens, prompt_phone_tokens,
                                                         prompt_phone_lens, prompt_durations, forced_dur=forced_durations,
                                                         vocoder=vocoder, sampling=sampling, seeds=seeds)
         return out if return_aux else (out[0], out[1])
 
-    def synthesize_prompt_conditioned_staged(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations, phone_lens=None,
+    def synthesize_prompt_conditioned_staged(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations=None, phone_lens=None,
                                              mel_lens=None, prompt_phone_lens=None, forced_durations=None, vocoder: bool = False,
                                              return_aux: bool = False):
         """The stage-call composition of `synthesize_prompt_conditioned`: tc_latent (prompt, target), vqpe_forward, adm_infer,
-        length_regulate, max_pool, plm_infer_prompted, then synthesize_batch with the decoded codes forced."""
+        length_regulate, max_pool, plm_infer_prompted, then synthesize_batch with the decoded codes forced.
+        `prompt_durations=None`: `align_prompt`, as there."""
         import torch
         nat = self.native
         B = phone_tokens.shape[0]
         mel_lens = nat._lens(mel_lens, B, mels.shape[1])
+        if prompt_durations is None:
+            prompt_durations = self.align_prompt(prompt_phone_tokens, mels, prompt_phone_lens, mel_lens)
         pd = np.asarray(prompt_durations.detach().cpu().numpy() if hasattr(prompt_durations, "detach") else prompt_durations,
                         np.int32).reshape(B, -1)
         ppl = nat._lens(prompt_phone_lens, B, prompt_phone_tokens.shape[1])
@@ -449,8 +482,8 @@ class Megatts:
         aux["dur"], aux["prompt_codes"] = dur, codes_p[:, :P]
         return (out[0], out[1], aux) if return_aux else (out[0], out[1])
 
-    def synthesize_prosody_interpolated(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations, rhythm_mels,
-                                        rhythm_phone_tokens, rhythm_durations, gamma, phone_lens=None, mel_lens=None,
+    def synthesize_prosody_interpolated(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations=None, rhythm_mels=None,
+                                        rhythm_phone_tokens=None, rhythm_durations=None, gamma=None, phone_lens=None, mel_lens=None,
                                         prompt_phone_lens=None, rhythm_mel_lens=None, rhythm_phone_lens=None,
                                         forced_durations=None, vocoder: bool = False, return_aux: bool = False, sampling=None,
                                         seeds=None):
@@ -461,11 +494,19 @@ class Megatts:
         timbre prompt's pooled tc_latents and VQ-PE codes, context B's the rhythm prompt's (its phones and alignment through MRTE
         with its own mel, its own VQ-PE codes).  gamma = 0 is `synthesize_prompt_conditioned`; the timbre comes from `mels` at every
         gamma.  Composed from stage calls like `synthesize_prompt_conditioned_staged`; all prompts of the call must have one pooled
-        length P (ValueError otherwise)."""
+        length P (ValueError otherwise).  `prompt_durations=None` / `rhythm_durations=None`: that prompt's alignment comes from
+        `align_prompt` (each prompt synthesised under its own timbre and warped onto itself by DTW); `rhythm_mels`,
+        `rhythm_phone_tokens` and `gamma` have defaults only because they follow an optional parameter, and are required."""
         import torch
         nat = self.native
         B = phone_tokens.shape[0]
         st = self.generator.cfg.vqpe.stride
+        if rhythm_mels is None or rhythm_phone_tokens is None or gamma is None:
+            raise TypeError("synthesize_prosody_interpolated needs rhythm_mels, rhythm_phone_tokens and gamma")
+        if prompt_durations is None:
+            prompt_durations = self.align_prompt(prompt_phone_tokens, mels, prompt_phone_lens, mel_lens)
+        if rhythm_durations is None:
+            rhythm_durations = self.align_prompt(rhythm_phone_tokens, rhythm_mels, rhythm_phone_lens, rhythm_mel_lens)
 
         def prompt_side(pm, pm_lens, pp, pp_lens, pdur):
             pm_lens = nat._lens(pm_lens, B, pm.shape[1])

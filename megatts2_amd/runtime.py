@@ -25,6 +25,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 ACT_LOGCLAMP = 4          # epilogue only: log(max(v, pro_slope))
 MT2_RESAMPLE_NORMALIZE = 1
 TRIM_FRAME, TRIM_HOP = 2048, 512      # MT2_TRIM_FRAME, MT2_TRIM_HOP
+DTW_MAX_LEN, DTW_DIR_COLS = 4096, 16  # MT2_DTW_MAX_LEN, MT2_DTW_DIR_COLS
 
 
 class NativeError(RuntimeError):
@@ -89,6 +90,9 @@ def load_library():
     lib.mt2_resample_query.argtypes = [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 4
     lib.mt2_trim_query.argtypes = [C.c_longlong, C.c_float, C.c_void_p, C.c_void_p]
     lib.mt2_trim_silence.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.mt2_dtw_query.argtypes = [C.c_int] * 4 + [C.c_void_p]
+    lib.mt2_dtw_align.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+    lib.mt2_align_durations.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -162,6 +166,32 @@ def _iptr(a: Optional[np.ndarray]):
 def _stream() -> C.c_void_p:
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _dtw(lib, h, X, Y, x_lens=None, y_lens=None, return_cost: bool = False, return_acc: bool = False):
+    """mt2_dtw_align on the handle `h` (NativeModel.dtw and MelFrontEnd.dtw): X f32 [B, Tx, D] warped onto Y f32 [B, Ty, D] by the
+    rule of csrc/dtw.hip -> dict of device tensors: lo, hi int32 [B, Ty] (the smallest / largest row of X on the path in each
+    column of Y; -1 at or beyond y_lens[b]), steps int32 [B] (cells on the path), total f32 [B] (the DTW distance A[Tx-1, Ty-1]),
+    and on request cost / acc f32 [B, Tx, Ty] (zeros outside an utterance's own cells).  Rows beyond the lengths are never read.
+    The call only enqueues."""
+    import torch
+    assert X.is_cuda and Y.is_cuda and X.dim() == 3 and Y.dim() == 3 and X.shape[0] == Y.shape[0] and X.shape[2] == Y.shape[2]
+    X, Y = X.contiguous().to(torch.float32), Y.contiguous().to(torch.float32)
+    B, Tx, D = X.shape
+    Ty = Y.shape[1]
+    xl = np.full(B, Tx, np.int32) if x_lens is None else _i32(x_lens)
+    yl = np.full(B, Ty, np.int32) if y_lens is None else _i32(y_lens)
+    assert xl.shape == (B,) and yl.shape == (B,)
+    dev = X.device
+    out = {"lo": torch.empty(B, Ty, device=dev, dtype=torch.int32), "hi": torch.empty(B, Ty, device=dev, dtype=torch.int32),
+           "steps": torch.empty(B, device=dev, dtype=torch.int32), "total": torch.empty(B, device=dev, dtype=torch.float32)}
+    if return_cost:
+        out["cost"] = torch.zeros(B, Tx, Ty, device=dev, dtype=torch.float32)
+    if return_acc:
+        out["acc"] = torch.zeros(B, Tx, Ty, device=dev, dtype=torch.float32)
+    _check(lib.mt2_dtw_align(h, _stream(), _ptr(X), _iptr(xl), Tx, _ptr(Y), _iptr(yl), Ty, D, B, _ptr(out["lo"]), _ptr(out["hi"]),
+                             _ptr(out["steps"]), _ptr(out["total"]), _ptr(out.get("cost")), _ptr(out.get("acc"))))
+    return out
 
 
 class NativeModel:
@@ -552,6 +582,27 @@ class NativeModel:
         P = -(-int(ml[0]) // st)
         return mel, mel_lens, {"dur": dur_out, "codes": codes_out, "wav": wav, "prompt_codes": pcodes[:, :P]}
 
+    # ---- alignment of a prompt to its phones without an external aligner (csrc/dtw.hip)
+    def dtw(self, X, Y, x_lens=None, y_lens=None, return_cost: bool = False, return_acc: bool = False):
+        """Dynamic time warping of X f32 [B, Tx, D] onto Y f32 [B, Ty, D] (`_dtw`): dict of device tensors lo, hi, steps, total
+        [, cost, acc]."""
+        return _dtw(self.lib, self.h, X, Y, x_lens, y_lens, return_cost, return_acc)
+
+    def align_durations(self, hi, y_lens, syn_dur, phone_lens=None):
+        """mt2_align_durations: the path's `hi` int32 [B, Ty] (device, from `dtw` with these y_lens) and the synthetic durations
+        `syn_dur` int32 [B, Np] (sum over phone_lens[b] = the x-length of utterance b) -> host int32 [B, Np]: the frames of Y that
+        each phone owns, row sums = y_lens.  Waits for the device once."""
+        import torch
+        assert hi.is_cuda and hi.dim() == 2
+        hi = hi.contiguous().to(torch.int32)
+        B, Ty = hi.shape
+        sd = _i32(syn_dur.detach().cpu().numpy() if hasattr(syn_dur, "detach") else syn_dur).reshape(B, -1)
+        Np = sd.shape[1]
+        yl, pl = self._lens(y_lens, B, Ty), self._lens(phone_lens, B, Np)
+        out = np.zeros((B, Np), np.int32)
+        _check(self.lib.mt2_align_durations(self.h, _stream(), _ptr(hi), _iptr(yl), Ty, _iptr(sd), _iptr(pl), Np, B, _iptr(out)))
+        return out
+
     # ---- tuning / measurement (every switch lives in THIS handle; the library has no mutable globals)
     def set_option(self, name: str, value: int) -> None:
         _check(self.lib.mt2_set_option(self.h, name.encode(), int(value)))
@@ -705,6 +756,11 @@ class MelFrontEnd:
                                          _iptr(bounds), _ptr(energy), F))
         res = (out, bounds[:, 1] - bounds[:, 0], bounds)
         return res + (energy,) if return_energy else res
+
+    def dtw(self, X, Y, x_lens=None, y_lens=None, return_cost: bool = False, return_acc: bool = False):
+        """Dynamic time warping of X f32 [B, Tx, D] onto Y f32 [B, Ty, D] on the bare handle (`_dtw`, as NativeModel.dtw): e.g. the
+        DTW mel distance `total` between two utterances of different length."""
+        return _dtw(self.lib, self.h, X, Y, x_lens, y_lens, return_cost, return_acc)
 
     def from_audio(self, wav, sr_in: int, lens=None, trim_db: Optional[float] = None, return_bounds: bool = False):
         """Prompt audio at any sample rate -> (mel [B, T, n_mels], mel_lens): resample to audio.sample_rate, peak-normalise and
@@ -1244,6 +1300,15 @@ def trim_query(L: int, top_db: float):
     f, c = C.c_int(0), C.c_float(0)
     _check(load_library().mt2_trim_query(int(L), float(top_db), C.byref(f), C.byref(c)))
     return f.value, np.float32(c.value)
+
+
+def dtw_query(Tx_max: int, Ty_max: int, D: int = 80, B: int = 1) -> int:
+    """mt2_dtw_query (no device needed) -> the arena bytes one dtw call of this geometry takes at most: with r(n) = n rounded up to
+    256, r(4 B ceil(Tx / 64) 64 ceil((Ty + 63) / 64) 64) for the skewed costs + r(4 B Tx ceil(Ty / 16)) for the packed directions +
+    r(4 (2 B + 8)) for the lengths."""
+    n = C.c_longlong(0)
+    _check(load_library().mt2_dtw_query(int(Tx_max), int(Ty_max), int(D), int(B), C.byref(n)))
+    return n.value
 
 
 def resample_table(sr_in: int, sr_out: int) -> np.ndarray:

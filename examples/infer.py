@@ -25,6 +25,9 @@ def main() -> None:
     ap.add_argument("--symbol-table")
     ap.add_argument("--wavs-dir", required=True, help="prompt *.wav files, any sample rate (resampled to 16 kHz on the GPU)")
     ap.add_argument("--trim-db", type=float, help="cut the prompts' leading / trailing silence below this many dB under their peak frame (e.g. 40)")
+    ap.add_argument("--vocoder", choices=("hifigan", "griffin-lim"), default="hifigan",
+                    help="hifigan: the hub model's generator, when a local copy is found; griffin-lim: no weights needed (buzzy: a fallback)")
+    ap.add_argument("--gl-iters", type=int, default=32, help="Griffin-Lim iterations")
     ap.add_argument("--text")
     ap.add_argument("--phones", help="comma separated phone token ids (bypasses the G2P)")
     ap.add_argument("--out", default="test.wav")
@@ -42,8 +45,10 @@ def main() -> None:
         tts = M.Megatts(a.g_ckpt, a.g_config, a.plm_ckpt, a.plm_config, a.adm_ckpt, a.adm_config, a.symbol_table)
     tts.eval()
     phones = [int(v) for v in a.phones.split(",")] if a.phones else None
-    mel, lens, _ = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db)
-    print(f"{int(lens[0])} mel frames -> {a.out if tts.hifi_gan is not None else '(no vocoder loaded: mel only)'}")
+    gl = {"n_iter": a.gl_iters} if a.vocoder == "griffin-lim" else None
+    mel, lens, _ = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl)
+    wrote = gl is not None or tts.hifi_gan is not None
+    print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
 
 
 if __name__ == "__main__":

@@ -331,6 +331,59 @@ int mt2_align_durations(mt2_model* m, void* stream, const int32_t* hi, const int
                         const int32_t* syn_dur /*host*/, const int32_t* phone_lens /*host*/, int Np_max, int B,
                         int32_t* dur_out_host);
 
+/* ---- Griffin-Lim vocoder (csrc/griffinlim.hip): log-mel -> audio with no weights, the fallback behind mt2_hifigan (whose weights are a
+ * third-party hub model) and a debugging aid - intelligible but buzzy, not a replacement.  No counterpart in the reference; parity with
+ * librosa.griffinlim / torchaudio.transforms.GriffinLim is unpinned, the rule is our own, held to tests/griffinlim_ref.py.  With the
+ * audio configuration's n_fft N, hop h, F = N / 2 + 1, taps = N / h >= 2, S = 2 F rounded up to 4, Fp = F rounded up to 4, w the
+ * front-end's window, for one utterance with log-mel M f32 [T, n_mels] and a 64-bit seed; output x f32 [L], L = (T - 1) h (the exact
+ * inverse of the front-end's framing: 1 + L / h = T, no inference padding):
+ *   mel -> linear  P = fb^T (fb fb^T)^-1 by Cholesky in double from the f32 filterbank fb, rounded once to f32;
+ *                  A[t, f] = max(0, sum_j expf(M[t, j]) P[f, j]).  A Gram matrix that is not positive definite is refused
+ *                  (n_fft 64 with 80 mels: 32 filters cover no bin).
+ *   phase          u = (x0 >> 8) 2^-24, x0 the first word of Philox4x32-10 with key = seed and counter (t F + f, 0, 0, 0) - the generator
+ *                  of mt2_sampling; theta = 2 pi u in f32; S0[t, f] = A[t, f] (cos theta, sin theta).
+ *   inverse STFT   y_t = irfft_N(S_t) w (imaginary parts of bins 0 and N / 2 ignored), a GEMM against a basis built in double and
+ *                  rounded once; s[p] = sum_t y_t[p - t h], e[p] = sum_t w2[p - t h] over the existing frames 0 <= t < T covering p, in
+ *                  ascending t, plain f32 adds, w2 = w^2 rounded once from double; x[n] = s[n + N/2] / e[n + N/2]
+ *                  (torch.istft, center=True, length = (T - 1) h).  No atomics, no sum split across lanes.
+ *   forward STFT   exactly mt2_mel_spectrogram's before its magnitude.
+ *   iteration      c = (float)(momentum / (1 + momentum)), Rprev = 0; for k < n_iter: x_k = istft(S_k), R = stft(x_k), D = R - c Rprev,
+ *                  S_{k+1} = D (A / (|D| + 1e-16)), Rprev = R; x = istft(S_{n_iter}).  n_iter = 0: the inverse STFT of S0.
+ *   residual       resid[k, t] = sum_f (|R_k[t, f]| - A[t, f])^2 for k = 0 .. n_iter (entry n_iter costs one extra STFT of x; paid only
+ *                  when the buffer is given); spectral convergence of round k = sqrt(sum_t resid[k, t] / sum A^2), left to the caller.
+ * A sample, a frame and a residual depend on their utterance alone and the two large GEMMs run on one fixed f32 tile whatever the row
+ * count, so a ragged batch is bit-identical to its utterances alone.  Both GEMMs stay on the f32 MFMA tiles (their bases are not in
+ * the weight store and have no fp16 planes): exp(M) beyond the fp16 range is an ordinary number and mt2_x3h_guard is not involved.
+ * Refused (error, nothing launched, outputs untouched): B < 1; n_iter < 0; momentum outside [0, 1); a T_b outside
+ * [N / (2 h) + 2, T_max] (the reflect padding needs L_b > N / 2); L_max < (max T_b - 1) h; taps < 2; the rank-deficient filterbank.
+ * Frames at or beyond T_b are never read, NaN included.  `m` may be a bare handle; the constants of a configuration are built on the
+ * first call that needs them (a synchronous copy) and kept in the handle; scratch comes from the handle's arena. */
+/* wav f32 [B, L_max] (device), lens host -> spec f32 [B, T_max, S] (device): frame t = [re(0..F-1) | im(0..F-1) | zero pad], T_b =
+ * 1 + L_b / h, zeros in frames at or beyond T_b.  The same launches and refusals as mt2_mel_spectrogram up to its magnitude. */
+int mt2_stft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* wav, const int32_t* lens /*host*/, int L_max, int B,
+             float* spec, int T_max);
+/* spec f32 [B, T_max, S] in mt2_stft's layout (pad columns are not read), frame_lens host int32 [B] -> wav f32 [B, L_max]:
+ * (T_b - 1) h samples, zeros beyond.  Refusals as mt2_griffin_lim's for the lengths.  The call only enqueues. */
+int mt2_istft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* spec, const int32_t* frame_lens /*host*/, int T_max,
+              int B, float* wav, int L_max);
+/* mel f32 [B, T_max, n_mels] -> mag f32 [B, T_max, Fp] = A, zeros in columns F .. Fp - 1 and in frames at or beyond mel_lens[b]
+ * (1 <= mel_lens[b] <= T_max). */
+int mt2_mel_to_linear(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* mel, const int32_t* mel_lens /*host*/, int T_max,
+                      int B, float* mag);
+/* Arena bytes and output length of one mt2_griffin_lim call; host only, no HIP call (outputs may be NULL; mel_lens NULL: every T_b =
+ * T_max).  It refuses what mt2_griffin_lim refuses, the rank-deficient filterbank included.  With r(n) = n rounded up to 256, q(n) = n rounded up
+ * to 4, Fr = sum_b T_b, Rb = sum_b (T_b - 1 + taps):
+ *   r(4 (2 q(Rb) + 4 q(Fr) + 2 q(B) + (want_resid ? q(2 B) + Fr : 2 B)))   the call's one upload of row maps, lengths and seeds
+ *   + r(4 Fr n_mels) + r(4 Fr Fp) + 3 r(4 Fr S) + r(4 Fr N) + r(4 Rb h)     exp(M), A, S / R / Rprev, the frames, the block buffer
+ * L_out = (max_b T_b - 1) h. */
+int mt2_griffin_lim_query(const mt2_audio_config* ac, const int32_t* mel_lens /*host or NULL*/, int T_max, int B, int n_iter,
+                          double momentum, int want_resid, long long* workspace_bytes, long long* L_out);
+/* mel f32 [B, T_max, n_mels] (device), mel_lens host int32 [B], seeds host uint64 [B] -> wav f32 [B, L_max] (device): (T_b - 1) h
+ * samples, zeros beyond.  resid (device f32 [B, n_iter + 1, T_max] or NULL): the residual rows, zeros at or beyond T_b.  Stage
+ * events (mt2_set_profiling): gl_setup, gl_iterations, gl_final.  The call only enqueues, it does not synchronise. */
+int mt2_griffin_lim(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* mel, const int32_t* mel_lens /*host*/, int T_max,
+                    int B, int n_iter, double momentum, const uint64_t* seeds /*host*/, float* wav, int L_max, float* resid /*or NULL*/);
+
 /* ---- the whole of Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) for a batch,
  * activations staying in the packed internal layout between stages.
  *   forced_dur   (host, optional) int32 [B, Np_max]: replaces the ADM's integer durations AFTER the ADM

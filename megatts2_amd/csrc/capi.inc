@@ -733,6 +733,75 @@ int mt2_trim_silence(mt2_model* m, void* stream, const float* wav, const int32_t
     MT2_API_END
 }
 
+// the STFT the mel front-end takes its magnitude of, for a ragged batch (the front half of mt2_mel_spectrogram, shared with it)
+int mt2_stft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* wav, const int32_t* lens, int L_max, int B, float* spec,
+             int T_max) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr && ac != nullptr && B >= 1, "bad arguments");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    stft_only_run(c, *ac, wav, lens, L_max, B, spec, T_max);
+    MT2_API_END
+}
+
+// torch.istft(center=True, length = (T - 1) hop) by the rule of griffinlim.hip; every refusal is decided on the host before the first HIP call
+int mt2_istft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* spec, const int32_t* frame_lens, int T_max, int B,
+              float* wav, int L_max) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr && ac != nullptr, "null model handle or audio configuration");
+    gl_check_config(*ac);
+    gl_check_lens(*ac, frame_lens, T_max, B, L_max);
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    istft_run(c, *ac, spec, frame_lens, T_max, B, wav, L_max);
+    MT2_API_END
+}
+
+// log-mel -> linear magnitude by the pseudo-inverse of the front-end's filterbank (griffinlim.hip, step 1)
+int mt2_mel_to_linear(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* mel, const int32_t* mel_lens, int T_max, int B,
+                      float* mag) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr && ac != nullptr && B >= 1, "bad arguments");
+    gl_check_config(*ac);
+    (void)gl_pinv(*ac).size();      // the rank-deficient filterbank is refused without a HIP call
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    mel_to_linear_run(c, *ac, mel, mel_lens, T_max, B, mag);
+    MT2_API_END
+}
+
+// Griffin-Lim: the arena bytes and the output length of one call, without a HIP call - and every refusal of mt2_griffin_lim (L_max,
+// which is not an argument here, aside)
+int mt2_griffin_lim_query(const mt2_audio_config* ac, const int32_t* mel_lens, int T_max, int B, int n_iter, double momentum,
+                          int want_resid, long long* workspace_bytes, long long* L_out) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(ac != nullptr, "null audio configuration");
+    gl_check_config(*ac);
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    std::vector<int> T(B, T_max);
+    if (mel_lens) T.assign(mel_lens, mel_lens + B);
+    const long long L = (long long)(*std::max_element(T.begin(), T.end()) - 1) * ac->hop_length;
+    gl_check_call(*ac, T.data(), T_max, B, n_iter, momentum, std::max(L, 0ll));
+    (void)gl_pinv(*ac).size();      // the rank-deficient filterbank
+    if (workspace_bytes) *workspace_bytes = gl_workspace_bytes(*ac, T.data(), B, want_resid != 0);
+    if (L_out) *L_out = L;
+    MT2_API_END
+}
+
+// every refusal is decided on the host before the first HIP call
+int mt2_griffin_lim(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* mel, const int32_t* mel_lens, int T_max, int B,
+                    int n_iter, double momentum, const uint64_t* seeds, float* wav, int L_max, float* resid) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr && ac != nullptr, "null model handle or audio configuration");
+    gl_check_call(*ac, mel_lens, T_max, B, n_iter, momentum, L_max);
+    MT2_REQUIRE(mel != nullptr && seeds != nullptr && wav != nullptr, "bad buffers");
+    if (!(m->gl_P && std::memcmp(&m->fe_cfg, ac, sizeof(*ac)) == 0)) (void)gl_pinv(*ac).size();      // rank-deficient filterbank: refused here
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    griffin_lim_run(c, *ac, mel, mel_lens, T_max, B, n_iter, momentum, seeds, wav, L_max, resid);
+    MT2_API_END
+}
+
 // DTW of a synthesised mel onto a real one (dtw.hip): the arena bytes of one call, without a HIP call
 int mt2_dtw_query(int Tx_max, int Ty_max, int D, int B, long long* workspace_bytes) {
     MT2_API_BEGIN
@@ -1398,6 +1467,11 @@ int mt2_op_row(void* stream, const char* op, void* const* ptrs, int nptrs, const
         {"codebook_rows", 4, 4, 0, [](ROW_ARGS) { return launch_codebook_rows(ROW_PF(0), ROW_PL(1), ROW_PI(2), ROW_PFW(3), ROW_INT(0), ROW_INT(1), ROW_INT(2), ROW_INT(3), s); }},
         {"reflect_pad_blocks", 5, 4, 0, [](ROW_ARGS) { return launch_reflect_pad_blocks(ROW_PF(0), ROW_LONG(0), ROW_PI(1), ROW_PI(2), ROW_PI(3), ROW_INT(1), ROW_INT(2), ROW_PFW(4), ROW_INT(3), s); }},
         {"magnitude", 2, 4, 0, [](ROW_ARGS) { return launch_magnitude(ROW_PF(0), ROW_INT(0), ROW_INT(1), ROW_PFW(1), ROW_INT(2), ROW_INT(3), s); }},
+        {"gl_exp_rows", 3, 2, 0, [](ROW_ARGS) { return launch_gl_exp_rows(ROW_PF(0), ROW_INT(0), ROW_PI(1), ROW_PFW(2), ROW_INT(1), s); }},
+        {"gl_phase_init", 5, 4, 0, [](ROW_ARGS) { return launch_gl_phase_init(ROW_PF(0), ROW_INT(0), ROW_PI(1), ROW_PI(2), static_cast<const uint32_t*>(ptrs[3]), ROW_PFW(4), ROW_INT(1), ROW_INT(2), ROW_INT(3), s); }},
+        {"istft_ola_blocks", 7, 3, 0, [](ROW_ARGS) { return launch_istft_ola_blocks(ROW_PF(0), ROW_INT(0), ROW_INT(1), ROW_PF(1), ROW_PI(2), ROW_PI(3), ROW_PI(4), ROW_PI(5), ROW_PFW(6), ROW_INT(2), s); }},
+        {"istft_ola_wav", 5, 4, 0, [](ROW_ARGS) { return launch_istft_ola_wav(ROW_PF(0), ROW_INT(0), ROW_INT(1), ROW_PF(1), ROW_PI(2), ROW_PI(3), ROW_PFW(4), ROW_INT(2), ROW_INT(3), s); }},
+        {"gl_phase_update", 6, 5, 1, [](ROW_ARGS) { return launch_gl_phase_update(ROW_PF(0), ROW_PFW(1), ROW_PF(2), ROW_INT(0), ROW_PFW(3), ROW_INT(1), ROW_INT(2), flts[0], ROW_PFW(4), ROW_PI(5), ROW_INT(3), ROW_INT(4), s); }},
     };
 #undef ROW_ARGS
 #undef ROW_PF

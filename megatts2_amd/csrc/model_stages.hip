@@ -5,6 +5,7 @@
 // positional indices restarting at 0.
 #include "mt2_model.h"
 #include "x3h_planes.h"
+#include "gemm_tiles.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1463,26 +1464,16 @@ static double mel_to_hz_slaney(double mel) {
     const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
     return mel >= min_log_mel ? min_log_hz * std::exp(logstep * (mel - min_log_mel)) : f_sp * mel;
 }
-static void frontend_prepare(mt2_model& m, const mt2_audio_config& ac) {
-    if (m.fe_basis && std::memcmp(&m.fe_cfg, &ac, sizeof(ac)) == 0) return;
-    MT2_REQUIRE(ac.n_fft >= 8 && ac.hop_length >= 4 && ac.hop_length % 4 == 0 && ac.n_fft % ac.hop_length == 0,
-                "n_fft must be a multiple of hop_length, hop_length a multiple of 4");
-    MT2_REQUIRE(ac.win_length >= 1 && ac.win_length <= ac.n_fft && ac.n_mels >= 1 && ac.n_mels % 4 == 0,
-                "win_length <= n_fft, n_mels a multiple of 4");
-    MT2_REQUIRE(ac.f_max > ac.f_min && ac.sample_rate > 0 && ac.clip > 0.0f, "bad audio configuration");
-    const int N = ac.n_fft, F = N / 2 + 1, Fp = (F + 3) & ~3;
+// the analysis window in double: periodic Hann of win_length, centred in n_fft (torch.stft centres a short window inside n_fft)
+static std::vector<double> frontend_window(const mt2_audio_config& ac) {
     const double PI = 3.14159265358979323846;
-    std::vector<double> win(N, 0.0);
-    const int left = (N - ac.win_length) / 2;       // torch.stft centres a short window inside n_fft
+    std::vector<double> win(ac.n_fft, 0.0);
+    const int left = (ac.n_fft - ac.win_length) / 2;
     for (int k = 0; k < ac.win_length; ++k) win[left + k] = 0.5 - 0.5 * std::cos(2.0 * PI * k / ac.win_length);
-    std::vector<float> basis((size_t)2 * F * N);
-    for (int f = 0; f < F; ++f)
-        for (int k = 0; k < N; ++k) {
-            const double ang = 2.0 * PI * (double)(((long long)f * k) % N) / N;
-            basis[(size_t)f * N + k] = (float)(win[k] * std::cos(ang));
-            basis[(size_t)(F + f) * N + k] = (float)(-win[k] * std::sin(ang));
-        }
-    // torchaudio.functional.melscale_fbanks(n_freqs=F, f_min, f_max, n_mels, sample_rate, "slaney", "slaney")
+    return win;
+}
+// torchaudio.functional.melscale_fbanks(n_freqs=F, f_min, f_max, n_mels, sample_rate, "slaney", "slaney"), rounded to f32: [n_mels, Fp]
+static std::vector<float> frontend_filterbank(const mt2_audio_config& ac, int F, int Fp) {
     std::vector<float> fb((size_t)ac.n_mels * Fp, 0.0f);
     const double m_min = hz_to_mel_slaney(ac.f_min), m_max = hz_to_mel_slaney(ac.f_max);
     std::vector<double> fpts(ac.n_mels + 2);
@@ -1496,24 +1487,47 @@ static void frontend_prepare(mt2_model& m, const mt2_audio_config& ac) {
             fb[(size_t)j * Fp + f] = (float)(std::max(0.0, std::min(down, up)) * enorm);
         }
     }
-    auto up = [&](const std::vector<float>& v) {
-        float* d = nullptr;
-        MT2_HIP(hipMalloc(reinterpret_cast<void**>(&d), v.size() * sizeof(float)));
-        MT2_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-        m.dev_allocs.push_back(d);
-        return d;
-    };
-    m.fe_basis = up(basis);
-    m.fe_fb = up(fb);
+    return fb;
+}
+static void frontend_check(const mt2_audio_config& ac) {
+    MT2_REQUIRE(ac.n_fft >= 8 && ac.hop_length >= 4 && ac.hop_length % 4 == 0 && ac.n_fft % ac.hop_length == 0,
+                "n_fft must be a multiple of hop_length, hop_length a multiple of 4");
+    MT2_REQUIRE(ac.win_length >= 1 && ac.win_length <= ac.n_fft && ac.n_mels >= 1 && ac.n_mels % 4 == 0,
+                "win_length <= n_fft, n_mels a multiple of 4");
+    MT2_REQUIRE(ac.f_max > ac.f_min && ac.sample_rate > 0 && ac.clip > 0.0f, "bad audio configuration");
+}
+static float* frontend_upload(mt2_model& m, const std::vector<float>& v) {
+    float* d = nullptr;
+    MT2_HIP(hipMalloc(reinterpret_cast<void**>(&d), v.size() * sizeof(float)));
+    MT2_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+    m.dev_allocs.push_back(d);
+    return d;
+}
+static void frontend_prepare(mt2_model& m, const mt2_audio_config& ac) {
+    if (m.fe_basis && std::memcmp(&m.fe_cfg, &ac, sizeof(ac)) == 0) return;
+    frontend_check(ac);
+    const int N = ac.n_fft, F = N / 2 + 1, Fp = (F + 3) & ~3;
+    const double PI = 3.14159265358979323846;
+    const std::vector<double> win = frontend_window(ac);
+    std::vector<float> basis((size_t)2 * F * N);
+    for (int f = 0; f < F; ++f)
+        for (int k = 0; k < N; ++k) {
+            const double ang = 2.0 * PI * (double)(((long long)f * k) % N) / N;
+            basis[(size_t)f * N + k] = (float)(win[k] * std::cos(ang));
+            basis[(size_t)(F + f) * N + k] = (float)(-win[k] * std::sin(ang));
+        }
+    m.fe_basis = frontend_upload(m, basis);
+    m.fe_fb = frontend_upload(m, frontend_filterbank(ac, F, Fp));
     m.fe_nfreq = F; m.fe_nfreq_pad = Fp;
     m.fe_cfg = ac;
+    m.gl_ibasis = m.gl_w2 = m.gl_P = nullptr;      // the Griffin-Lim constants follow the configuration: rebuilt on their next use
 }
 
-static void mel_spectrogram_run(const Ctx& c, const mt2_audio_config& ac, const float* wav, const int* lens, int L_max,
-                                int B, float* mel, int T_max) {
-    mt2_model& m = c.m;
-    frontend_prepare(m, ac);
-    const int hop = ac.hop_length, taps = ac.n_fft / hop, pad = ac.n_fft / 2, F = m.fe_nfreq, Fp = m.fe_nfreq_pad;
+// The packed rows of a ragged batch of waveforms in front of the STFT convolution: utterance b owns T_b - 1 + taps hop-sized blocks of
+// its reflect-padded signal and T_b = 1 + L_b / hop frame rows; frame t reads blocks t .. t + taps - 1
+struct StftRows { int Rb, Fr, o_b, o_t, o_len, o_base, o_map; };
+static StftRows stft_plan(IntPlan& ip, const mt2_audio_config& ac, const int* lens, int L_max, int B, int T_max) {
+    const int hop = ac.hop_length, taps = ac.n_fft / hop, pad = ac.n_fft / 2;
     std::vector<int> blk_b, blk_t, rowbase, rowmap, len(lens, lens + B);
     for (int b = 0; b < B; ++b) {
         MT2_REQUIRE(lens[b] > pad && lens[b] <= L_max, "waveform shorter than n_fft/2 + 1 samples (reflect padding) or > L_max");
@@ -1522,21 +1536,40 @@ static void mel_spectrogram_run(const Ctx& c, const mt2_audio_config& ac, const 
         for (int t = 0; t < T - 1 + taps; ++t) { blk_b.push_back(b); blk_t.push_back(t); }
         for (int t = 0; t < T; ++t) { rowbase.push_back(row0 + t); rowmap.push_back(b * T_max + t); }
     }
-    const int Rb = (int)blk_b.size(), Fr = (int)rowbase.size();
+    StftRows r{};
+    r.Rb = (int)blk_b.size(); r.Fr = (int)rowbase.size();
+    r.o_b = ip.add(blk_b); r.o_t = ip.add(blk_t); r.o_len = ip.add(len); r.o_base = ip.add(rowbase); r.o_map = ip.add(rowmap);
+    return r;
+}
+// STFT = Conv1d over hop-sized blocks against the windowed DFT basis: spec[m] = [re(0..F-1) | im(0..F-1)] of frame m, row pitch 2F
+// rounded up to 4
+static void stft_gemm(const Ctx& c, const mt2_audio_config& ac, const float* xp, int Rb, const int* rowbase, float* spec, int Fr) {
+    const int F = c.m.fe_nfreq;
+    GemmP p{};
+    p.X = xp; p.ldx = ac.hop_length; p.Rx = Rb; p.rowbase = rowbase; p.taps = ac.n_fft / ac.hop_length; p.Cin = ac.hop_length;
+    p.W = c.m.fe_basis; p.C = spec; p.ldc = (2 * F + 3) & ~3; p.M = Fr; p.N = 2 * F;
+    gemm(c, p);
+}
+// the front half of the mel front-end: reflect padding into blocks, then the STFT convolution -> spec [Fr, lds]
+static float* stft_run(const Ctx& c, const mt2_audio_config& ac, const float* wav, int L_max, const IntPlan& ip, const StftRows& r) {
+    const int hop = ac.hop_length, pad = ac.n_fft / 2;
+    float* xp = c.ws.get<float>((size_t)r.Rb * hop);
+    MT2_HIP(launch_reflect_pad_blocks(wav, L_max, ip.dev(r.o_b), ip.dev(r.o_t), ip.dev(r.o_len), hop, pad, xp, r.Rb, c.s));
+    float* spec = c.ws.get<float>((size_t)r.Fr * ((2 * c.m.fe_nfreq + 3) & ~3));
+    stft_gemm(c, ac, xp, r.Rb, ip.dev(r.o_base), spec, r.Fr);
+    return spec;
+}
+
+static void mel_spectrogram_run(const Ctx& c, const mt2_audio_config& ac, const float* wav, const int* lens, int L_max,
+                                int B, float* mel, int T_max) {
+    mt2_model& m = c.m;
+    frontend_prepare(m, ac);
+    const int F = m.fe_nfreq, Fp = m.fe_nfreq_pad;
     IntPlan ip;
-    const int o_b = ip.add(blk_b), o_t = ip.add(blk_t), o_len = ip.add(len), o_base = ip.add(rowbase),
-              o_map = ip.add(rowmap);
+    const StftRows r = stft_plan(ip, ac, lens, L_max, B, T_max);
     ip.upload(c.ws, c.m.pinned(), c.s);
-    float* xp = c.ws.get<float>((size_t)Rb * hop);
-    MT2_HIP(launch_reflect_pad_blocks(wav, L_max, ip.dev(o_b), ip.dev(o_t), ip.dev(o_len), hop, pad, xp, Rb, c.s));
-    const int lds = (2 * F + 3) & ~3;
-    float* spec = c.ws.get<float>((size_t)Fr * lds);
-    {   // STFT = Conv1d over hop-sized blocks: frame t reads blocks t .. t+taps-1
-        GemmP p{};
-        p.X = xp; p.ldx = hop; p.Rx = Rb; p.rowbase = ip.dev(o_base); p.taps = taps; p.Cin = hop;
-        p.W = m.fe_basis; p.C = spec; p.ldc = lds; p.M = Fr; p.N = 2 * F;
-        gemm(c, p);
-    }
+    const float* spec = stft_run(c, ac, wav, L_max, ip, r);
+    const int lds = (2 * F + 3) & ~3, Fr = r.Fr;
     float* mag = c.ws.get<float>((size_t)Fr * Fp);
     MT2_HIP(launch_magnitude(spec, lds, F, mag, Fp, Fr, c.s));
     float* mrows = c.ws.get<float>((size_t)Fr * ac.n_mels);
@@ -1547,7 +1580,288 @@ static void mel_spectrogram_run(const Ctx& c, const mt2_audio_config& ac, const 
         gemm(c, p);
     }
     MT2_HIP(hipMemsetAsync(mel, 0, sizeof(float) * (size_t)B * T_max * ac.n_mels, c.s));
-    MT2_HIP(launch_unpack_rows(mrows, ac.n_mels, ac.n_mels, T_max, 0, ip.dev(o_map), mel, Fr, c.s));
+    MT2_HIP(launch_unpack_rows(mrows, ac.n_mels, ac.n_mels, T_max, 0, ip.dev(r.o_map), mel, Fr, c.s));
+}
+
+// spec f32 [B, T_max, lds] (re | im | zero pad; zeros in frames at or beyond T_b) = the STFT the mel front-end takes its magnitude of
+static void stft_only_run(const Ctx& c, const mt2_audio_config& ac, const float* wav, const int* lens, int L_max, int B, float* spec_out,
+                          int T_max) {
+    MT2_REQUIRE(wav != nullptr && lens != nullptr && spec_out != nullptr, "bad buffers");
+    frontend_prepare(c.m, ac);
+    IntPlan ip;
+    const StftRows r = stft_plan(ip, ac, lens, L_max, B, T_max);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    const float* spec = stft_run(c, ac, wav, L_max, ip, r);
+    const int lds = (2 * c.m.fe_nfreq + 3) & ~3;
+    MT2_HIP(hipMemsetAsync(spec_out, 0, sizeof(float) * (size_t)B * T_max * lds, c.s));
+    MT2_HIP(launch_unpack_rows(spec, lds, lds, T_max, 0, ip.dev(r.o_map), spec_out, r.Fr, c.s));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Griffin-Lim vocoder (griffinlim.hip holds the rule): mel -> linear magnitude by the filterbank's pseudo-inverse, random phase, then
+// n_iter rounds of inverse STFT -> forward STFT -> phase update.  Four launches a round: the inverse-DFT GEMM, the overlap-add (which
+// writes the STFT's reflect-padded block buffer itself), the STFT GEMM of the front-end and the phase update.
+//
+// Route of the two large GEMMs: fe_basis and the inverse basis are uploaded here, outside the weight store, so they have neither bf16
+// nor fp16 planes - both launches run on the f32 MFMA tiles, never on the fp16 pipe, and the range guard (mt2_x3h_guard) has nothing to
+// watch: exp of an untrained model's log-mel beyond 65504 stays an ordinary f32 number.  The tile itself is FIXED (64x64, three-stage
+// ring, no K split) instead of chosen from the row count: the K-split tiles sum in another order, and a ragged batch must be
+// bit-identical to its utterances alone.
+struct FixedTile {
+    EngineOpts& o;
+    int old;
+    explicit FixedTile(EngineOpts& oo) : o(oo), old(oo.force_cfg) { if (old < 0) o.force_cfg = CFG_DMA64x64_S3; }
+    ~FixedTile() { o.force_cfg = old; }
+};
+
+// the geometry every Griffin-Lim entry point checks before anything else (host only)
+static void gl_check_config(const mt2_audio_config& ac) {
+    frontend_check(ac);
+    MT2_REQUIRE(ac.n_fft / ac.hop_length >= 2, "n_fft / hop_length < 2: the overlap-added squared window has zeros");
+}
+static int gl_min_frames(const mt2_audio_config& ac) { return ac.n_fft / (2 * ac.hop_length) + 2; }
+static void gl_check_lens(const mt2_audio_config& ac, const int* T, int T_max, int B, long long L_max) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(T != nullptr && T_max >= 1, "mel_lens is NULL or T_max < 1");
+    long long rows = 0;
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(T[b] >= gl_min_frames(ac) && T[b] <= T_max, "a frame count outside [n_fft / (2 hop) + 2, T_max]");
+        MT2_REQUIRE(L_max >= (long long)(T[b] - 1) * ac.hop_length, "L_max smaller than (max T - 1) * hop_length");
+        rows += T[b] + ac.n_fft / ac.hop_length;
+    }
+    MT2_REQUIRE(rows * (ac.n_fft + 4) <= INT_MAX, "batch too large for 32-bit row indices");
+}
+// arena bytes of one griffin_lim_run (the closed form is in megatts2_hip.h)
+static long long gl_workspace_bytes(const mt2_audio_config& ac, const int* T, int B, bool resid) {
+    auto up = [](long long n) { return (n + 255) & ~255ll; };
+    auto p4 = [](long long n) { return (n + 3) & ~3ll; };
+    const int N = ac.n_fft, hop = ac.hop_length, F = N / 2 + 1, Fp = (F + 3) & ~3, lds = (2 * F + 3) & ~3;
+    long long Fr = 0, Rb = 0;
+    for (int b = 0; b < B; ++b) { Fr += T[b]; Rb += T[b] - 1 + N / hop; }
+    const long long ints = 2 * p4(Rb) + 4 * p4(Fr) + 2 * p4(B) + (resid ? p4(2 * B) + Fr : 2 * B);
+    return up(4 * ints) + up(4 * Fr * ac.n_mels) + up(4 * Fr * Fp) + 3 * up(4 * Fr * lds) + up(4 * Fr * N) + up(4 * Rb * hop);
+}
+
+// the inverse basis [N, lds] (window and the 1/N, 2/N Hermitian weights folded in, zero columns for the imaginary parts of bins 0 and
+// N/2 and for the pad) and the squared window: built in double on the first call that inverts an STFT, rounded once
+static void gl_prepare_istft(mt2_model& m, const mt2_audio_config& ac) {
+    gl_check_config(ac);
+    const int N = ac.n_fft, F = N / 2 + 1, lds = (2 * F + 3) & ~3, hop = ac.hop_length, pad = N / 2;
+    const bool same = m.fe_basis && std::memcmp(&m.fe_cfg, &ac, sizeof(ac)) == 0;
+    if (same && m.gl_ibasis) return;
+    const double PI = 3.14159265358979323846;
+    const std::vector<double> win = frontend_window(ac);
+    std::vector<float> w2(N), ib((size_t)N * lds, 0.0f);
+    for (int k = 0; k < N; ++k) w2[k] = (float)(win[k] * win[k]);
+    for (int p = pad; p < pad + N; ++p) {      // the envelope at the left edge and in the interior (the right edge mirrors the left)
+        float e = 0.0f;
+        for (int t = p >= N ? (p - N) / hop + 1 : 0; t <= p / hop; ++t) e += w2[p - t * hop];
+        MT2_REQUIRE(e > 1e-11f, "the overlap-added squared window has zeros (win_length too short for this hop)");
+    }
+    for (int k = 0; k < N; ++k)
+        for (int f = 0; f < F; ++f) {
+            const bool edge = f == 0 || 2 * f == N;
+            const double ang = 2.0 * PI * (double)(((long long)f * k) % N) / N, wt = win[k] * (edge ? 1.0 : 2.0) / N;
+            ib[(size_t)k * lds + f] = (float)(wt * std::cos(ang));
+            ib[(size_t)k * lds + F + f] = edge ? 0.0f : (float)(-wt * std::sin(ang));
+        }
+    frontend_prepare(m, ac);
+    m.gl_ibasis = frontend_upload(m, ib);
+    m.gl_w2 = frontend_upload(m, w2);
+}
+// P = fb^T (fb fb^T)^-1 [Fp, n_mels] (rows F .. Fp-1 zero) by Cholesky in double from the f32 filterbank; refused when the Gram matrix
+// is not positive definite (filters without a bin: n_fft too small for n_mels)
+static std::vector<float> gl_pinv(const mt2_audio_config& ac) {
+    const int F = ac.n_fft / 2 + 1, Fp = (F + 3) & ~3, J = ac.n_mels;
+    const std::vector<float> fb = frontend_filterbank(ac, F, Fp);
+    std::vector<double> G((size_t)J * J, 0.0);
+    double dmax = 0.0;
+    for (int i = 0; i < J; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double s = 0.0;
+            for (int f = 0; f < F; ++f) s += (double)fb[(size_t)i * Fp + f] * (double)fb[(size_t)j * Fp + f];
+            G[(size_t)i * J + j] = G[(size_t)j * J + i] = s;
+            if (i == j) dmax = std::max(dmax, s);
+        }
+    std::vector<double> Lc((size_t)J * J, 0.0);
+    for (int i = 0; i < J; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double s = G[(size_t)i * J + j];
+            for (int k = 0; k < j; ++k) s -= Lc[(size_t)i * J + k] * Lc[(size_t)j * J + k];
+            if (i == j) {
+                if (!(s > 1e-12 * dmax))
+                    throw Error("griffin_lim: the mel filterbank is rank deficient (fb fb^T is not positive definite: a filter covers no bin)");
+                Lc[(size_t)i * J + i] = std::sqrt(s);
+            } else {
+                Lc[(size_t)i * J + j] = s / Lc[(size_t)j * J + j];
+            }
+        }
+    std::vector<float> P((size_t)Fp * J, 0.0f);
+    std::vector<double> y(J);
+    for (int f = 0; f < F; ++f) {      // G x = fb[:, f]:  P[f, :] = x
+        for (int i = 0; i < J; ++i) {
+            double s = fb[(size_t)i * Fp + f];
+            for (int k = 0; k < i; ++k) s -= Lc[(size_t)i * J + k] * y[k];
+            y[i] = s / Lc[(size_t)i * J + i];
+        }
+        for (int i = J - 1; i >= 0; --i) {
+            double s = y[i];
+            for (int k = i + 1; k < J; ++k) s -= Lc[(size_t)k * J + i] * y[k];
+            y[i] = s / Lc[(size_t)i * J + i];
+        }
+        for (int i = 0; i < J; ++i) P[(size_t)f * J + i] = (float)y[i];
+    }
+    return P;
+}
+static void gl_prepare_pinv(mt2_model& m, const mt2_audio_config& ac) {
+    gl_check_config(ac);
+    if (m.fe_basis && std::memcmp(&m.fe_cfg, &ac, sizeof(ac)) == 0 && m.gl_P) return;
+    const std::vector<float> P = gl_pinv(ac);      // may refuse: before anything is uploaded
+    frontend_prepare(m, ac);
+    m.gl_P = frontend_upload(m, P);
+}
+
+// frame rows of a ragged batch of spectra / mels: utterance b owns rows row0[b] .. + T[b] and T[b] - 1 + taps blocks
+struct GlRows {
+    std::vector<int> blk_b, blk_t, rowbase, map, row_b, row_t, row0;
+    int Rb = 0, Fr = 0;
+};
+static GlRows gl_rows(const mt2_audio_config& ac, const int* T, int B, int T_max) {
+    GlRows g;
+    const int taps = ac.n_fft / ac.hop_length;
+    for (int b = 0; b < B; ++b) {
+        const int blk0 = (int)g.blk_b.size();
+        g.row0.push_back((int)g.rowbase.size());
+        for (int t = 0; t < T[b] - 1 + taps; ++t) { g.blk_b.push_back(b); g.blk_t.push_back(t); }
+        for (int t = 0; t < T[b]; ++t) { g.rowbase.push_back(blk0 + t); g.map.push_back(b * T_max + t); g.row_b.push_back(b); g.row_t.push_back(t); }
+    }
+    g.Rb = (int)g.blk_b.size(); g.Fr = (int)g.rowbase.size();
+    return g;
+}
+// frames[Fr, N] = S[Fr, lds] x inverse basis
+static void istft_gemm(const Ctx& c, const mt2_audio_config& ac, const float* S, float* frames, int Fr) {
+    const int lds = (2 * c.m.fe_nfreq + 3) & ~3;
+    GemmP p{};
+    p.X = S; p.ldx = lds; p.Rx = Fr; p.Cin = lds; p.W = c.m.gl_ibasis; p.C = frames; p.ldc = ac.n_fft; p.M = Fr; p.N = ac.n_fft;
+    gemm(c, p);
+}
+
+// torch.istft(center=True, length = (T - 1) hop) of spec f32 [B, T_max, lds] (re | im | pad, as stft_only_run leaves it) -> wav [B, L_max]
+static void istft_run(const Ctx& c, const mt2_audio_config& ac, const float* spec, const int* T, int T_max, int B, float* wav, int L_max) {
+    gl_check_config(ac);
+    gl_check_lens(ac, T, T_max, B, L_max);
+    MT2_REQUIRE(spec != nullptr && wav != nullptr, "bad buffers");
+    gl_prepare_istft(c.m, ac);
+    const int N = ac.n_fft, F = c.m.fe_nfreq, lds = (2 * F + 3) & ~3;
+    const GlRows g = gl_rows(ac, T, B, T_max);
+    IntPlan ip;
+    const int o_map = ip.add(g.map), o_row0 = ip.add(g.row0), o_T = ip.add(std::vector<int>(T, T + B));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    float* S = c.ws.get<float>((size_t)g.Fr * lds);
+    MT2_HIP(hipMemsetAsync(S, 0, sizeof(float) * (size_t)g.Fr * lds, c.s));      // the pad columns meet zero basis columns: 0 x garbage must not be NaN
+    MT2_HIP(launch_pack_rows(spec, lds, T_max, 0, ip.dev(o_map), S, lds, g.Fr, c.s));
+    float* frames = c.ws.get<float>((size_t)g.Fr * N);
+    {
+        FixedTile ft(c.m.opts);
+        istft_gemm(c, ac, S, frames, g.Fr);
+    }
+    MT2_HIP(launch_istft_ola_wav(frames, N, ac.hop_length, c.m.gl_w2, ip.dev(o_row0), ip.dev(o_T), wav, L_max, B, c.s));
+}
+
+// A f32 [B, T_max, Fp] = max(0, exp(mel) P^T), zeros in frames at or beyond T_b and in columns F .. Fp-1
+static void mel_to_linear_rows(const Ctx& c, const mt2_audio_config& ac, const float* mel, const int* melmap, float* E, float* A, int Fr) {
+    const int Fp = c.m.fe_nfreq_pad;
+    MT2_HIP(launch_gl_exp_rows(mel, ac.n_mels, melmap, E, Fr, c.s));
+    GemmP p{};
+    p.X = E; p.ldx = ac.n_mels; p.Rx = Fr; p.Cin = ac.n_mels; p.W = c.m.gl_P; p.C = A; p.ldc = Fp; p.M = Fr; p.N = Fp; p.epi_act = ACT_RELU;
+    FixedTile ft(c.m.opts);
+    gemm(c, p);
+}
+static void mel_to_linear_run(const Ctx& c, const mt2_audio_config& ac, const float* mel, const int* T, int T_max, int B, float* out) {
+    gl_check_config(ac);
+    MT2_REQUIRE(B >= 1 && B <= 65535 && T != nullptr && T_max >= 1 && mel != nullptr && out != nullptr, "bad arguments");
+    for (int b = 0; b < B; ++b) MT2_REQUIRE(T[b] >= 1 && T[b] <= T_max, "a frame count outside [1, T_max]");
+    gl_prepare_pinv(c.m, ac);
+    const int Fp = c.m.fe_nfreq_pad;
+    std::vector<int> map;
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < T[b]; ++t) map.push_back(b * T_max + t);
+    const int Fr = (int)map.size();
+    IntPlan ip;
+    const int o_map = ip.add(map);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    float* E = c.ws.get<float>((size_t)Fr * ac.n_mels);
+    float* A = c.ws.get<float>((size_t)Fr * Fp);
+    mel_to_linear_rows(c, ac, mel, ip.dev(o_map), E, A, Fr);
+    MT2_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * T_max * Fp, c.s));
+    MT2_HIP(launch_unpack_rows(A, Fp, Fp, T_max, 0, ip.dev(o_map), out, Fr, c.s));
+}
+
+// every refusal of mt2_griffin_lim that needs no device (shared with mt2_griffin_lim_query)
+static void gl_check_call(const mt2_audio_config& ac, const int* T, int T_max, int B, int n_iter, double momentum, long long L_max) {
+    gl_check_config(ac);
+    MT2_REQUIRE(n_iter >= 0 && n_iter <= 100000, "n_iter outside [0, 100000]");
+    MT2_REQUIRE(momentum >= 0.0 && momentum < 1.0, "momentum outside [0, 1)");
+    gl_check_lens(ac, T, T_max, B, L_max);
+}
+
+static void griffin_lim_run(const Ctx& c, const mt2_audio_config& ac, const float* mel, const int* T, int T_max, int B, int n_iter,
+                            double momentum, const uint64_t* seeds, float* wav, int L_max, float* resid) {
+    // everything is checked before the first launch: a refused call leaves `wav` and `resid` as they were
+    gl_check_call(ac, T, T_max, B, n_iter, momentum, L_max);
+    MT2_REQUIRE(mel != nullptr && seeds != nullptr && wav != nullptr, "bad buffers");
+    gl_prepare_pinv(c.m, ac);
+    gl_prepare_istft(c.m, ac);
+    mt2_model& m = c.m;
+    const int N = ac.n_fft, hop = ac.hop_length, F = m.fe_nfreq, Fp = m.fe_nfreq_pad, lds = (2 * F + 3) & ~3;
+    const float cm = (float)(momentum / (1.0 + momentum));
+    const GlRows g = gl_rows(ac, T, B, T_max);
+    const int Fr = g.Fr, Rb = g.Rb;
+    std::vector<int> sd(2 * (size_t)B);
+    for (int b = 0; b < B; ++b) { sd[2 * b] = (int)(uint32_t)(seeds[b] & 0xFFFFFFFFu); sd[2 * b + 1] = (int)(uint32_t)(seeds[b] >> 32); }
+    IntPlan ip;
+    const int o_b = ip.add(g.blk_b), o_t = ip.add(g.blk_t), o_base = ip.add(g.rowbase), o_map = ip.add(g.map), o_rb = ip.add(g.row_b),
+              o_rt = ip.add(g.row_t), o_row0 = ip.add(g.row0), o_T = ip.add(std::vector<int>(T, T + B)), o_seed = ip.add(sd);
+    int o_rmap = -1;
+    if (resid) {
+        std::vector<int> rmap(Fr);
+        for (int r = 0; r < Fr; ++r) rmap[r] = g.row_b[r] * (n_iter + 1) * T_max + g.row_t[r];
+        MT2_REQUIRE((long long)B * (n_iter + 1) * T_max <= INT_MAX, "resid too large for 32-bit indices");
+        o_rmap = ip.add(rmap);
+    }
+    ip.upload(c.ws, m.pinned(), c.s);
+    float* E = c.ws.get<float>((size_t)Fr * ac.n_mels);
+    float* A = c.ws.get<float>((size_t)Fr * Fp);
+    float* S = c.ws.get<float>((size_t)Fr * lds);
+    float* R = c.ws.get<float>((size_t)Fr * lds);
+    float* Rprev = c.ws.get<float>((size_t)Fr * lds);
+    float* frames = c.ws.get<float>((size_t)Fr * N);
+    float* xp = c.ws.get<float>((size_t)Rb * hop);
+    const int* rmap = resid ? ip.dev(o_rmap) : nullptr;
+    Stages st(m, c.s);
+    st.mark("start");
+    if (resid) MT2_HIP(hipMemsetAsync(resid, 0, sizeof(float) * (size_t)B * (n_iter + 1) * T_max, c.s));
+    mel_to_linear_rows(c, ac, mel, ip.dev(o_map), E, A, Fr);
+    MT2_HIP(launch_gl_phase_init(A, Fp, ip.dev(o_rb), ip.dev(o_rt), reinterpret_cast<const uint32_t*>(ip.dev(o_seed)), S, lds, F, Fr, c.s));
+    if (n_iter > 0) MT2_HIP(hipMemsetAsync(Rprev, 0, sizeof(float) * (size_t)Fr * lds, c.s));
+    st.mark("gl_setup");
+    FixedTile ft(m.opts);
+    for (int k = 0; k < n_iter; ++k) {
+        istft_gemm(c, ac, S, frames, Fr);
+        MT2_HIP(launch_istft_ola_blocks(frames, N, hop, m.gl_w2, ip.dev(o_b), ip.dev(o_t), ip.dev(o_row0), ip.dev(o_T), xp, Rb, c.s));
+        stft_gemm(c, ac, xp, Rb, ip.dev(o_base), R, Fr);
+        MT2_HIP(launch_gl_phase_update(R, Rprev, A, Fp, S, lds, F, cm, resid ? resid + (size_t)k * T_max : nullptr, rmap, Fr, 1, c.s));
+    }
+    st.mark("gl_iterations");
+    istft_gemm(c, ac, S, frames, Fr);
+    MT2_HIP(launch_istft_ola_wav(frames, N, hop, m.gl_w2, ip.dev(o_row0), ip.dev(o_T), wav, L_max, B, c.s));
+    if (resid) {      // entry n_iter: one extra STFT of the output, paid only on request
+        MT2_HIP(launch_istft_ola_blocks(frames, N, hop, m.gl_w2, ip.dev(o_b), ip.dev(o_t), ip.dev(o_row0), ip.dev(o_T), xp, Rb, c.s));
+        stft_gemm(c, ac, xp, Rb, ip.dev(o_base), R, Fr);
+        MT2_HIP(launch_gl_phase_update(R, nullptr, A, Fp, nullptr, lds, F, cm, resid + (size_t)n_iter * T_max, rmap, Fr, 0, c.s));
+    }
+    st.mark("gl_final");
+    st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -437,4 +437,23 @@ struct AlignDurP {
 };
 hipError_t launch_dtw_durations(const AlignDurP& p, hipStream_t s);
 
+// ---- Griffin-Lim vocoder (griffinlim.hip; the rule is in its header and in megatts2_hip.h) -------------------------------------------
+// Frames of a ragged batch are packed rows: utterance b owns rows row0[b] .. row0[b] + T[b] of S / R / Rprev ([rows, lds]: re(0..F-1) |
+// im(0..F-1) | zero pad, lds = 2F rounded up to 4), of A ([rows, lda]) and of the inverse-DFT GEMM's frames ([rows, N]).
+// out[r, :] = expf(mel[rowmap[r], :]), C % 4 == 0
+hipError_t launch_gl_exp_rows(const float* mel, int C, const int* rowmap, float* out, int R, hipStream_t s);
+// S[r] = A[r] (cos, sin)(2 pi u), u the Philox draw of (seeds[2 b], seeds[2 b + 1]) at counter row_t[r] F + f, b = row_b[r]; A == nullptr: A = 1
+hipError_t launch_gl_phase_init(const float* A, int lda, const int* row_b, const int* row_t, const uint32_t* seeds, float* S, int lds_,
+                                int F, int R, hipStream_t s);
+// the overlap-add (s / e, existing frames in ascending t; w2 [N] = the squared window) in gather form, written as the reflect-padded
+// hop-block buffer of the STFT convolution (the layout of launch_reflect_pad_blocks: utterance b owns T[b] - 1 + N / hop blocks) ...
+hipError_t launch_istft_ola_blocks(const float* frames, int N, int hop, const float* w2, const int* blk_b, const int* blk_t,
+                                   const int* row0, const int* Tlen, float* out, int Rb, hipStream_t s);
+// ... and as wav[b, n] for n < (T[b] - 1) hop, zeros up to L_max (L_max >= every length)
+hipError_t launch_istft_ola_wav(const float* frames, int N, int hop, const float* w2, const int* row0, const int* Tlen, float* wav,
+                                int L_max, int B, hipStream_t s);
+// update != 0: D = R - c Rprev, S = D (A / (|D| + 1e-16)), Rprev = R.  resid != nullptr: resid[rmap[r]] = sum_f (|R[r, f]| - A[r, f])^2
+hipError_t launch_gl_phase_update(const float* R, float* Rprev, const float* A, int lda, float* S, int lds_, int F, float c, float* resid,
+                                  const int* rmap, int rows, int update, hipStream_t s);
+
 }  // namespace mt2

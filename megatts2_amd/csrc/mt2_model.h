@@ -201,6 +201,9 @@ struct mt2_model {
     mt2_audio_config fe_cfg{};
     float *fe_basis = nullptr, *fe_fb = nullptr;
     int fe_nfreq = 0, fe_nfreq_pad = 0;
+    // Griffin-Lim constants of fe_cfg, each built on the first call that needs it (model_stages.hip): inverse STFT basis [n_fft, 2F
+    // padded to 4], squared window [n_fft], pseudo-inverse of the mel filterbank [F padded to 4, n_mels]
+    float *gl_ibasis = nullptr, *gl_w2 = nullptr, *gl_P = nullptr;
     // resampler filter tables, tap-major, by reduced ratio (o, n) = (sr_in, sr_out) / gcd: built and uploaded on first use
     std::map<std::pair<int, int>, float*> rs_tables;
 

@@ -18,6 +18,7 @@
 // u32 keys of z (ballot / popcount counts, index tie-break by a lane scan), the top-p cut a bisection over the f32 bit
 // patterns of w (w >= 0: the patterns order like the values) with wave sums.  No LDS, no scratch.
 #include "mt2_kernels.h"
+#include "philox.h"
 #include <math.h>
 
 namespace mt2 {
@@ -25,21 +26,6 @@ namespace {
 
 constexpr int kPer = 16;           // logits per lane
 constexpr int kMaxN = 64 * kPer;   // one wave covers the row
-
-__device__ __forceinline__ uint32_t philox_x0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
 
 // larger value <-> larger key; -0 and +0 are one value
 __device__ __forceinline__ uint32_t order_key(float z) {

@@ -382,13 +382,34 @@ class Megatts:
 
     # -- batched tensor-level pipeline (the measured hot path)
     def synthesize(self, phone_tokens, mels, phone_lens=None, mel_lens=None, forced_durations=None,
-                   forced_codes=None, vocoder: bool = False, return_aux: bool = False, sampling=None, seeds=None):
+                   forced_codes=None, vocoder: bool = False, return_aux: bool = False, sampling=None, seeds=None,
+                   griffin_lim=None):
         """phone_tokens int64 [B, Np], mels f32 [B, Tp, 80] -> (mel [B, Tm, 80], mel_lens) - the
         no_grad block of Megatts.forward (models/megatts2.py:353-368) for every utterance of the batch.
-        `sampling` (sampling.PLMSampling; None = greedy) / `seeds` (int64 [B] or one int s -> s + b): sampled PLM codes."""
-        return self.native.synthesize_batch(phone_tokens, phone_lens, mels, mel_lens, forced_durations, forced_codes,
-                                            run_plm=forced_codes is None, vocoder=vocoder, return_aux=return_aux,
-                                            sampling=sampling, seeds=seeds)
+        `sampling` (sampling.PLMSampling; None = greedy) / `seeds` (int64 [B] or one int s -> s + b): sampled PLM codes.
+        `griffin_lim` (None = off, exactly the call above; True or a dict of vocode_griffin_lim's keyword arguments): the generated
+        mel is vocoded by Griffin-Lim instead of HiFi-GAN and the result is (mel, mel_lens, aux) with aux["wav"] f32
+        [B, (max mel_lens - 1) * hop], utterance b holding (mel_lens[b] - 1) * hop samples - no inference padding, unlike
+        decode_batch."""
+        if griffin_lim is None or griffin_lim is False:
+            return self.native.synthesize_batch(phone_tokens, phone_lens, mels, mel_lens, forced_durations, forced_codes,
+                                                run_plm=forced_codes is None, vocoder=vocoder, return_aux=return_aux,
+                                                sampling=sampling, seeds=seeds)
+        if vocoder:
+            raise ValueError("vocoder=True (HiFi-GAN) and griffin_lim are two vocoders for one mel: pass one")
+        mel, out_lens, aux = self.native.synthesize_batch(phone_tokens, phone_lens, mels, mel_lens, forced_durations, forced_codes,
+                                                          run_plm=forced_codes is None, vocoder=False, return_aux=True,
+                                                          sampling=sampling, seeds=seeds)
+        aux["wav"] = self.vocode_griffin_lim(mel, out_lens, **(griffin_lim if isinstance(griffin_lim, dict) else {}))
+        return mel, out_lens, aux
+
+    def vocode_griffin_lim(self, mel, mel_lens=None, n_iter: int = 32, momentum: float = 0.99, seeds=0, return_resid: bool = False):
+        """Audio from a log-mel with no vocoder weights: mel f32 [B, T, 80] (device) -> wav f32 [B, (T - 1) * hop] by the
+        Griffin-Lim rule of csrc/griffinlim.hip (MelFrontEnd.griffin_lim), utterance b holding (mel_lens[b] - 1) * hop samples and
+        zeros beyond: the exact inverse of the mel front-end's framing, without HiFi-GAN's inference padding.  Intelligible but
+        buzzy - the fallback when the hub's HiFi-GAN weights are not on hand and a way to listen to a synthetic or partly trained
+        model, not a replacement for HiFi-GAN.  Every utterance needs at least n_fft / (2 hop) + 2 = 4 frames."""
+        return _frontend().griffin_lim(mel, mel_lens, n_iter=n_iter, momentum=momentum, seeds=seeds, return_resid=return_resid)
 
     def align_prompt(self, prompt_phone_tokens, mels, prompt_phone_lens=None, mel_lens=None, return_aux: bool = False):
         """The phone-level alignment of a prompt utterance to its own phones, made by the model itself - the `prompt_durations` of
@@ -593,9 +614,15 @@ class Megatts:
     # its prompts are pre-cut) - on the GPU as well (MelFrontEnd.from_audio(trim_db=...), 16 kHz files included); None
     # leaves the audio whole.  Text -> phone ids is the reference's G2P (pypinyin + MFA
     # dictionary, host side, outside the hot path); when it is not importable pass `phone_tokens` instead.
+    # vocoder: None is the reference's behaviour - HiFi-GAN when its weights were found, otherwise no audio and no file;
+    # "griffin_lim" (or a dict of vocode_griffin_lim's keyword arguments) vocodes the first prompt mel and the generated mel by
+    # Griffin-Lim, concatenates them as the HiFi-GAN branch does, sets aux["wav"] and writes out_path.  That audio has
+    # (T - 1) * hop samples per mel of T frames and no inference padding, unlike decode_batch.
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
-                phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None):
+                phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None, vocoder=None):
         import torch
+        if not (vocoder is None or vocoder == "griffin_lim" or isinstance(vocoder, dict)):
+            raise ValueError(f"vocoder={vocoder!r}: None (HiFi-GAN when loaded) or 'griffin_lim'")
         from . import audio_io
         wavs = sorted(glob.glob(f"{wavs_dir}/*.wav"))
         if not wavs:
@@ -626,6 +653,14 @@ class Megatts:
                 raise NativeError("phone symbols given but no symbol_table was passed to Megatts(...)")
             phone_tokens = self.ttc.phone2token(phones)               # :350-351
         phone_tokens = torch.as_tensor(np.asarray(phone_tokens)).to(torch.int64).reshape(1, -1).cuda()
+        if vocoder is not None:
+            gl = vocoder if isinstance(vocoder, dict) else {}
+            mel, mel_lens, aux = self.synthesize(phone_tokens, mels, return_aux=True, griffin_lim=gl or True)
+            if out_path:
+                prompt = self.vocode_griffin_lim(mels_prompt.unsqueeze(0).contiguous(), **gl)[0]
+                audio = torch.cat([prompt, aux["wav"][0, :(int(mel_lens[0]) - 1) * HIFIGAN_HOP_LENGTH]])
+                audio_io.write_wav(out_path, audio, HIFIGAN_SR)
+            return mel, mel_lens, aux
         mel, mel_lens, aux = self.synthesize(phone_tokens, mels, vocoder=self.hifi_gan is not None, return_aux=True)
         if self.hifi_gan is not None and out_path:
             # :370-375  prompt audio (vocoded first prompt mel) followed by the generated audio; decode_batch output

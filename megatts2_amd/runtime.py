@@ -93,6 +93,11 @@ def load_library():
     lib.mt2_dtw_query.argtypes = [C.c_int] * 4 + [C.c_void_p]
     lib.mt2_dtw_align.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
     lib.mt2_align_durations.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_stft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.mt2_istft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.mt2_mel_to_linear.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_griffin_lim_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mt2_griffin_lim.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -762,6 +767,100 @@ class MelFrontEnd:
         DTW mel distance `total` between two utterances of different length."""
         return _dtw(self.lib, self.h, X, Y, x_lens, y_lens, return_cost, return_acc)
 
+    # ---- Griffin-Lim vocoder (csrc/griffinlim.hip): the STFT, its inverse, mel -> linear and the iteration
+    def _frame_lens(self, lens, B: int, T: int) -> np.ndarray:
+        ln = np.full(B, T, np.int32) if lens is None else _i32(lens)
+        assert ln.shape == (B,)
+        return ln
+
+    def stft(self, wav, lens=None):
+        """wav f32 [B, L] (device) -> complex64 [B, 1 + L // hop, n_fft // 2 + 1]: the STFT the mel front-end takes its magnitude of
+        (torch.stft with center=True, reflect padding, periodic Hann); frames beyond 1 + lens[b] // hop are zero."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        ln = self._frame_lens(lens, B, L)
+        T, F = 1 + int(ln.max()) // self.audio.hop_length, self.audio.n_fft // 2 + 1
+        S = (2 * F + 3) & ~3
+        spec = torch.empty(B, T, S, device=wav.device, dtype=torch.float32)
+        _check(self.lib.mt2_stft(self.h, _stream(), C.byref(self.ac), _ptr(wav), _iptr(ln), L, B, _ptr(spec), T))
+        return torch.complex(spec[..., :F], spec[..., F:2 * F])
+
+    def istft(self, spec, frame_lens=None, out=None):
+        """complex64 [B, T, n_fft // 2 + 1] (device) -> wav f32 [B, (T - 1) * hop]: `torch.istft(center=True, length=(T - 1) * hop)` by
+        the rule of csrc/griffinlim.hip, utterance b holding (frame_lens[b] - 1) * hop samples and zeros beyond; frames at or beyond
+        frame_lens[b] are never read.  out: a contiguous f32 [B, >= (max T_b - 1) * hop] device tensor to write into."""
+        import torch
+        assert spec.is_cuda and spec.dim() == 3 and spec.is_complex()
+        B, T, F = spec.shape
+        assert F == self.audio.n_fft // 2 + 1
+        ln = self._frame_lens(frame_lens, B, T)
+        S = (2 * F + 3) & ~3
+        packed = torch.zeros(B, T, S, device=spec.device, dtype=torch.float32)
+        packed[..., :F] = spec.real
+        packed[..., F:2 * F] = spec.imag
+        if out is None:
+            out = torch.empty(B, max((int(ln.max()) - 1) * self.audio.hop_length, 1), device=spec.device, dtype=torch.float32)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        _check(self.lib.mt2_istft(self.h, _stream(), C.byref(self.ac), _ptr(packed), _iptr(ln), T, B, _ptr(out), out.shape[1]))
+        return out
+
+    def mel_to_linear(self, mel, mel_lens=None):
+        """log-mel f32 [B, T, n_mels] (device) -> linear magnitude f32 [B, T, n_fft // 2 + 1] = max(0, exp(mel) @ P^T), P the
+        pseudo-inverse of the front-end's filterbank; zeros in frames at or beyond mel_lens[b], which are never read."""
+        import torch
+        assert mel.is_cuda and mel.dim() == 3 and mel.shape[2] == self.audio.n_mels
+        mel = mel.contiguous().to(torch.float32)
+        B, T, _ = mel.shape
+        ln = self._frame_lens(mel_lens, B, T)
+        F = self.audio.n_fft // 2 + 1
+        mag = torch.empty(B, T, (F + 3) & ~3, device=mel.device, dtype=torch.float32)
+        _check(self.lib.mt2_mel_to_linear(self.h, _stream(), C.byref(self.ac), _ptr(mel), _iptr(ln), T, B, _ptr(mag)))
+        return mag[..., :F]
+
+    def griffin_lim(self, mel, mel_lens=None, n_iter: int = 32, momentum: float = 0.99, seeds=0, return_resid: bool = False, out=None,
+                    resid_out=None):
+        """Griffin-Lim vocoder by the rule of csrc/griffinlim.hip: log-mel f32 [B, T, n_mels] (device) -> wav f32 [B, (T - 1) * hop],
+        utterance b holding (mel_lens[b] - 1) * hop samples - the exact inverse of the front-end's framing, with no inference padding
+        (unlike HiFi-GAN's decode_batch) - and zeros beyond.  No weights: intelligible but buzzy audio, a fallback and a debugging
+        aid, not a replacement for HiFi-GAN.  seeds: as sampling.seed_array (an int s means s + b); the initial phase depends on
+        (seed, frame, bin) alone, so a batch gives what its utterances give alone, bit for bit.  return_resid: also f32
+        [B, n_iter + 1, T] with sum_f (|STFT(x_k)| - A)^2 per frame (one extra STFT).  out / resid_out: contiguous f32 device tensors
+        [B, >= (max T_b - 1) * hop] / [B, n_iter + 1, T] to write into.  The call only enqueues."""
+        import torch
+        from .sampling import seed_array
+        assert mel.is_cuda and mel.dim() == 3 and mel.shape[2] == self.audio.n_mels
+        mel = mel.contiguous().to(torch.float32)
+        B, T, _ = mel.shape
+        ln = self._frame_lens(mel_lens, B, T)
+        sd = seed_array(seeds, B)
+        if out is None:
+            out = torch.empty(B, max((int(ln.max()) - 1) * self.audio.hop_length, 1), device=mel.device, dtype=torch.float32)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        resid = resid_out
+        if resid is None and return_resid:
+            resid = torch.empty(B, max(int(n_iter), 0) + 1, T, device=mel.device, dtype=torch.float32)
+        if resid is not None:
+            assert resid.is_cuda and resid.is_contiguous() and resid.dtype == torch.float32 and resid.shape == (B, int(n_iter) + 1, T)
+        _check(self.lib.mt2_griffin_lim(self.h, _stream(), C.byref(self.ac), _ptr(mel), _iptr(ln), T, B, int(n_iter), float(momentum),
+                                        sd.ctypes.data_as(C.c_void_p), _ptr(out), out.shape[1], _ptr(resid)))
+        return (out, resid) if resid is not None else out
+
+    def set_profiling(self, on: bool) -> None:
+        _check(self.lib.mt2_set_profiling(self.h, 1 if on else 0))
+
+    def last_stage_ms(self) -> Dict[str, float]:
+        names = (C.c_char_p * 16)()
+        ms = (C.c_float * 16)()
+        n = self.lib.mt2_last_stage_ms(self.h, names, ms, 16)
+        return {names[i].decode(): float(ms[i]) for i in range(max(n, 0))}
+
+    def workspace_high_water(self) -> int:
+        n = C.c_size_t(0)
+        _check(self.lib.mt2_workspace_high_water(self.h, C.byref(n)))
+        return n.value
+
     def from_audio(self, wav, sr_in: int, lens=None, trim_db: Optional[float] = None, return_bounds: bool = False):
         """Prompt audio at any sample rate -> (mel [B, T, n_mels], mel_lens): resample to audio.sample_rate, peak-normalise and
         extract the mel (models/megatts2.py:335-336,339) with no host round trip.  Audio that already has that rate is only
@@ -1089,6 +1188,11 @@ def op_row_sqnorm(E, D, ee, N): op_row("row_sqnorm", E, D, ee, N)
 def op_codebook_rows(E, codes, codemap, out, ldo, Dq, R, bins): op_row("codebook_rows", E, codes, codemap, out, ldo, Dq, R, bins)
 def op_reflect_pad_blocks(wav, wstride, blk_b, blk_t, len_, hop, pad, out, R): op_row("reflect_pad_blocks", wav, wstride, blk_b, blk_t, len_, hop, pad, out, R)
 def op_magnitude(spec, lds_, F, out, ldo, M): op_row("magnitude", spec, lds_, F, out, ldo, M)
+def op_gl_exp_rows(mel, Cc, rowmap, out, R): op_row("gl_exp_rows", mel, Cc, rowmap, out, R)
+def op_gl_phase_init(A, lda, row_b, row_t, seeds, S, lds_, F, R): op_row("gl_phase_init", A, lda, row_b, row_t, seeds, S, lds_, F, R)
+def op_istft_ola_blocks(frames, N, hop, w2, blk_b, blk_t, row0, T, out, Rb): op_row("istft_ola_blocks", frames, N, hop, w2, blk_b, blk_t, row0, T, out, Rb)
+def op_istft_ola_wav(frames, N, hop, w2, row0, T, wav, L_max, B): op_row("istft_ola_wav", frames, N, hop, w2, row0, T, wav, L_max, B)
+def op_gl_phase_update(R, Rprev, A, lda, S, lds_, F, c, resid, rmap, rows, update): op_row("gl_phase_update", R, Rprev, A, lda, S, lds_, F, float(c), resid, rmap, rows, update)
 
 
 # ---- test-only entry into GROUPED launches of the GEMM engine (tests/test_gpu_gemm_groups.py, tests/test_gemm_groups_host.py): the
@@ -1309,6 +1413,23 @@ def dtw_query(Tx_max: int, Ty_max: int, D: int = 80, B: int = 1) -> int:
     n = C.c_longlong(0)
     _check(load_library().mt2_dtw_query(int(Tx_max), int(Ty_max), int(D), int(B), C.byref(n)))
     return n.value
+
+
+def griffin_lim_query(audio, mel_lens=None, T_max: Optional[int] = None, B: Optional[int] = None, n_iter: int = 32,
+                      momentum: float = 0.99, return_resid: bool = False):
+    """mt2_griffin_lim_query (no device needed) -> (arena bytes, L_out) of one MelFrontEnd.griffin_lim call: mel_lens int [B] (or
+    None with T_max and B: every utterance T_max frames), L_out = (max T_b - 1) * hop.  It refuses what the call refuses, the
+    rank-deficient filterbank included.  The closed form is in include/megatts2_hip.h."""
+    ac = MT2AudioConfig(audio.sample_rate, audio.n_fft, audio.hop_length, audio.win_length, audio.n_mels, audio.f_min, audio.f_max,
+                        audio.clip)
+    ln = None if mel_lens is None else _i32(mel_lens)
+    if ln is not None:
+        B = int(ln.size) if B is None else B
+        T_max = int(ln.max()) if T_max is None and ln.size else T_max
+    n, lo = C.c_longlong(0), C.c_longlong(0)
+    _check(load_library().mt2_griffin_lim_query(C.byref(ac), _iptr(ln), int(T_max or 0), int(B or 0), int(n_iter), float(momentum),
+                                                1 if return_resid else 0, C.byref(n), C.byref(lo)))
+    return n.value, lo.value
 
 
 def resample_table(sr_in: int, sr_out: int) -> np.ndarray:

@@ -28,6 +28,8 @@ def main() -> None:
     ap.add_argument("--vocoder", choices=("hifigan", "griffin-lim"), default="hifigan",
                     help="hifigan: the hub model's generator, when a local copy is found; griffin-lim: no weights needed (buzzy: a fallback)")
     ap.add_argument("--gl-iters", type=int, default=32, help="Griffin-Lim iterations")
+    ap.add_argument("--report-pitch", action="store_true",
+                    help="print the pitch moments (YIN on the GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
     ap.add_argument("--text")
     ap.add_argument("--phones", help="comma separated phone token ids (bypasses the G2P)")
     ap.add_argument("--out", default="test.wav")
@@ -49,6 +51,14 @@ def main() -> None:
     mel, lens, _ = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl)
     wrote = gl is not None or tts.hifi_gan is not None
     print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
+    if a.report_pitch:
+        import glob
+        from megatts2_amd import audio_io
+        report = [("prompt", sorted(glob.glob(f"{a.wavs_dir}/*.wav"))[0], a.trim_db)] + ([("generated", a.out, None)] if wrote else [])
+        for what, path, trim_db in report:
+            y, sr = audio_io.read_wav(path)
+            st = M.pitch_stats(M.extract_f0(y, sr, trim_db=trim_db))
+            print(f"pitch of the {what} ({path}): " + ", ".join(f"{k} {float(v[0]):.4g}" for k, v in st.items()))
 
 
 if __name__ == "__main__":

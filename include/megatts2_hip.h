@@ -384,6 +384,53 @@ int mt2_griffin_lim_query(const mt2_audio_config* ac, const int32_t* mel_lens /*
 int mt2_griffin_lim(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* mel, const int32_t* mel_lens /*host*/, int T_max,
                     int B, int n_iter, double momentum, const uint64_t* seeds /*host*/, float* wav, int L_max, float* resid /*or NULL*/);
 
+/* ---- F0 tracking by YIN (de Cheveigne & Kawahara 2002, steps 2-5; csrc/f0.hip) and the pitch moments of a track.  No reference
+ * counterpart: the reference tree has no pitch tracker (it would take one from librosa or pyworld).  Parity with librosa.yin / pyin
+ * is unpinned - neither is on hand - and quality on real speech is unpinned as well; the rule is our own statement and the tests
+ * hold the kernel to it.  Frames are the mel front-end's at the same hop, so f0[t] belongs to mel frame t.  For one utterance
+ * x[0 .. L), L >= 1, with W = MT2_F0_WINDOW:
+ *   T = 1 + L / hop frames;  frame t reads x over [hop t - 512, hop t + 512), a sample outside [0, L) being a zero by its index,
+ *   never a read;  s = hop t - 512
+ *   tau_min = ceil(sample_rate / fmax), tau_max = floor(sample_rate / fmin); refused, not clamped, unless
+ *   2 <= tau_min < tau_max <= MT2_F0_MAX_LAG
+ *   d[tau] = sum_{j = 0}^{W - 1} (x[s + j] - x[s + j + tau])^2, tau = 0 .. 256 (all 257, whatever tau_max): in f32 ONE chain over j
+ *   ascending, e = a - b rounded, acc = fma(e, e, acc) from 0;  d[0] is exactly 0
+ *   c[0] = 0, c[tau] = c[tau - 1] + d[tau] (one f32 add each, tau ascending);  d'[0] = 1,  d'[tau] = (d[tau] * (float)tau) / c[tau]
+ *   (one f32 product, one true f32 division), 1 where c[tau] is not > 0
+ *   tau0 = the smallest tau in [tau_min, tau_max] with d'[tau] < threshold;  from tau0 up while tau + 1 <= tau_max and
+ *   d'[tau + 1] < d'[tau]: the end of the walk is tau*.  No such tau0: tau* = the smallest tau in [tau_min, tau_max] attaining the
+ *   minimum of d' (a NaN never wins; all NaN: tau_min).  cmnd = d'[tau*];  the frame is voiced iff d'[tau*] < threshold
+ *   voiced frames with tau* - 1 >= 1 and tau* + 1 <= tau_max:  a, b, c = d'[tau* - 1], d'[tau*], d'[tau* + 1];  den = (a - 2 b) + c;
+ *   delta = (a - c) / (2 den) if den > 0, else 0 (also 0 without both neighbours);  f0 = (float)sample_rate / ((float)tau* + delta),
+ *   every operation rounded on its own;  unvoiced frames: f0 = 0
+ * The order of every sum depends on the sample's index in its utterance alone: a ragged batch is bit-identical to its utterances
+ * alone.  Non-finite samples cannot fault, cannot write outside the outputs and do not change a frame whose window does not hold
+ * one; nothing more is promised.  Frames in [T_b, T_max) are written as unvoiced: f0 0, cmnd 1, lag 0, d 0.
+ * Refused (error, nothing launched, every output as it was): B < 1 or > 65535; lens[b] < 1 or > L_max; hop outside [1, 1024];
+ * fmin / fmax not finite or <= 0; the lag condition; threshold outside (0, 1]; T_max < 1 + max_b lens[b] / hop; an output
+ * overlapping wav.
+ * Moments of f0 [B, T_max] over the voiced frames (f0 > 0) of utterance b among its first frame_lens[b], all sums in double, two
+ * passes, in an order that depends on the frame index alone (not on the batch slot or T_max):  n;  mu = sum f / n;
+ * m_k = sum (f - mu)^k / n, k = 2, 3, 4;  stats[b] = n, n / T_b, mu, sqrt(m2), m3 / m2^1.5, m4 / m2^2 - 3;  n = 0: all zeros;
+ * m2 = 0: sigma = skew = kurt = 0. */
+#define MT2_F0_FRAME 1024
+#define MT2_F0_WINDOW 768
+#define MT2_F0_MAX_LAG 256
+/* T = 1 + L / hop, the lag range and the arena bytes of one mt2_f0_yin call (of any batch: the lengths alone); host only, no HIP
+ * call (outputs may be NULL).  Refuses what mt2_f0_yin refuses of these arguments, and L outside [1, 2^31). */
+int mt2_f0_query(int sample_rate, int hop, float fmin, float fmax, long long L, int* frames, int* lag_min, int* lag_max,
+                 long long* workspace_bytes);
+/* wav f32 [B, L_max] (device), lens host int32 [B] -> f0 f32 [B, T_max] (device; Hz, 0 = unvoiced).  Optional (NULL to skip), device:
+ * cmnd f32 [B, T_max] = d'[tau*], lag int32 [B, T_max] = tau*, diff f32 [B, T_max, 257] = d - written to memory only for a caller that
+ * passes it.  ONE launch for the batch; the call only enqueues, it does not synchronise.  `m` may be a bare handle. */
+int mt2_f0_yin(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+               int sample_rate, int hop, float fmin, float fmax, float threshold, float* f0 /*[B, T_max]*/, float* cmnd /*or NULL*/,
+               int32_t* lag /*or NULL*/, int T_max, float* diff /*or NULL*/);
+/* f0 f32 [B, T_max] (device), frame_lens host int32 [B] in [1, T_max] -> stats f64 [B, 6] (device).  One launch, a workgroup per
+ * utterance; the call only enqueues.  Refused: B < 1 or > 65535, a frame count outside [1, T_max], stats overlapping f0. */
+int mt2_f0_stats(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/, const int32_t* frame_lens /*host*/, int T_max, int B,
+                 double* stats /*[B, 6]*/);
+
 /* ---- the whole of Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) for a batch,
  * activations staying in the packed internal layout between stages.
  *   forced_dur   (host, optional) int32 [B, Np_max]: replaces the ADM's integer durations AFTER the ADM

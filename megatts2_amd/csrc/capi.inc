@@ -733,6 +733,45 @@ int mt2_trim_silence(mt2_model* m, void* stream, const float* wav, const int32_t
     MT2_API_END
 }
 
+// F0 by YIN: the frame count, the lag range and the arena bytes of the rule, without a HIP call
+int mt2_f0_query(int sample_rate, int hop, float fmin, float fmax, long long L, int* frames, int* lag_min, int* lag_max,
+                 long long* workspace_bytes) {
+    MT2_API_BEGIN
+    int lo = 0, hi = 0;
+    f0_check_rule(sample_rate, hop, fmin, fmax, &lo, &hi);
+    MT2_REQUIRE(L >= 1 && L <= INT_MAX, "L outside [1, 2^31)");
+    if (frames) *frames = (int)(1 + L / hop);
+    if (lag_min) *lag_min = lo;
+    if (lag_max) *lag_max = hi;
+    if (workspace_bytes) *workspace_bytes = (4ll * 65535 + 255) & ~255ll;      // the lengths of the largest batch, nothing else
+    MT2_API_END
+}
+
+// F0, voicing and (optionally) d'[tau*], tau* and d of a ragged batch; every refusal is decided on the host before the first HIP call
+int mt2_f0_yin(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sample_rate, int hop, float fmin,
+               float fmax, float threshold, float* f0, float* cmnd, int32_t* lag, int T_max, float* diff) {
+    MT2_API_BEGIN
+    int lo = 0, hi = 0;
+    f0_check_rule(sample_rate, hop, fmin, fmax, &lo, &hi);
+    const int mx = f0_check_call(wav, lens, L_max, B, hop, threshold, f0, cmnd, lag, T_max, diff);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    f0_run(c, wav, lens, L_max, B, mx, sample_rate, hop, lo, hi, threshold, f0, cmnd, lag, T_max, diff);
+    MT2_API_END
+}
+
+// the pitch moments of f0 tracks over their voiced frames
+int mt2_f0_stats(mt2_model* m, void* stream, const float* f0, const int32_t* frame_lens, int T_max, int B, double* stats) {
+    MT2_API_BEGIN
+    f0_stats_check(f0, frame_lens, T_max, B, stats);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    f0_stats_run(c, f0, frame_lens, T_max, B, stats);
+    MT2_API_END
+}
+
 // the STFT the mel front-end takes its magnitude of, for a ragged batch (the front half of mt2_mel_spectrogram, shared with it)
 int mt2_stft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* wav, const int32_t* lens, int L_max, int B, float* spec,
              int T_max) {

@@ -1971,6 +1971,64 @@ static void trim_run(const Ctx& c, const float* wav, const int* lens, int L_max,
     }
 }
 
+// ---- F0 by YIN and the pitch moments (f0.hip) ------------------------------------------------------------------------------------
+// The parameters of the rule, checked before anything else (host only); -> (tau_min, tau_max)
+static void f0_check_rule(int sample_rate, int hop, float fmin, float fmax, int* lag_min, int* lag_max) {
+    MT2_REQUIRE(sample_rate >= 1, "sample_rate < 1");
+    MT2_REQUIRE(hop >= 1 && hop <= MT2_F0_FRAME, "hop outside [1, 1024]");
+    MT2_REQUIRE(std::isfinite(fmin) && std::isfinite(fmax) && fmin > 0.0f && fmax > 0.0f, "fmin / fmax must be finite and > 0");
+    MT2_REQUIRE(f0_lags(sample_rate, fmin, fmax, lag_min, lag_max),
+                "lags refused: need 2 <= ceil(sample_rate / fmax) < floor(sample_rate / fmin) <= 256");
+}
+static bool f0_overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a != nullptr && b != nullptr && a0 < b0 + nb && b0 < a0 + na;
+}
+// every refusal of mt2_f0_yin, decided on the host before the first HIP call; -> max_b lens[b]
+static int f0_check_call(const float* wav, const int* lens, int L_max, int B, int hop, float threshold, const float* f0, const float* cmnd,
+                         const int32_t* lag, int T_max, const float* diff) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(wav != nullptr && lens != nullptr && f0 != nullptr && L_max >= 1, "bad buffers");
+    MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)f0 | (uintptr_t)cmnd | (uintptr_t)lag | (uintptr_t)diff) & 3) == 0, "misaligned buffers");
+    MT2_REQUIRE(threshold > 0.0f && threshold <= 1.0f, "threshold outside (0, 1]");
+    int mx = 0;
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
+        mx = std::max(mx, lens[b]);
+    }
+    MT2_REQUIRE(T_max >= 1 + mx / hop, "T_max smaller than 1 + max length / hop");
+    const size_t nw = sizeof(float) * (size_t)B * L_max, nt = sizeof(float) * (size_t)B * T_max;
+    MT2_REQUIRE(!f0_overlaps(f0, nt, wav, nw) && !f0_overlaps(cmnd, nt, wav, nw) && !f0_overlaps(lag, nt, wav, nw) &&
+                    !f0_overlaps(diff, nt * (MT2_F0_MAX_LAG + 1), wav, nw),
+                "an output overlaps wav");
+    return mx;
+}
+// enqueues only: the lengths travel in the call's one IntPlan upload
+static void f0_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, int hop, int lag_min,
+                   int lag_max, float threshold, float* f0, float* cmnd, int32_t* lag, int T_max, float* diff) {
+    IntPlan ip;
+    const int o_len = ip.add(std::vector<int>(lens, lens + B));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    F0P p{};
+    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B;
+    p.sample_rate = sample_rate; p.hop = hop; p.lag_min = lag_min; p.lag_max = lag_max; p.threshold = threshold;
+    p.f0 = f0; p.T_max = T_max; p.cmnd = cmnd; p.lag = lag; p.diff = diff;
+    MT2_HIP(launch_f0_yin(p, c.s));
+}
+static void f0_stats_check(const float* f0, const int* frame_lens, int T_max, int B, const double* stats) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(f0 != nullptr && frame_lens != nullptr && stats != nullptr && T_max >= 1, "bad buffers");
+    MT2_REQUIRE(((uintptr_t)f0 & 3) == 0 && ((uintptr_t)stats & 7) == 0, "misaligned buffers");
+    for (int b = 0; b < B; ++b) MT2_REQUIRE(frame_lens[b] >= 1 && frame_lens[b] <= T_max, "frame count outside [1, T_max]");
+    MT2_REQUIRE(!f0_overlaps(stats, sizeof(double) * 6 * (size_t)B, f0, sizeof(float) * (size_t)B * T_max), "stats overlaps f0");
+}
+static void f0_stats_run(const Ctx& c, const float* f0, const int* frame_lens, int T_max, int B, double* stats) {
+    IntPlan ip;
+    const int o_len = ip.add(std::vector<int>(frame_lens, frame_lens + B));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    MT2_HIP(launch_f0_stats(f0, ip.dev(o_len), T_max, B, stats, c.s));
+}
+
 // The lengths of a DTW call, checked before anything else (host only)
 static void dtw_check_geometry(int Tx_max, int Ty_max, int D, int B) {
     MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");

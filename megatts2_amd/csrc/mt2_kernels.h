@@ -456,4 +456,22 @@ hipError_t launch_istft_ola_wav(const float* frames, int N, int hop, const float
 hipError_t launch_gl_phase_update(const float* R, float* Rprev, const float* A, int lda, float* S, int lds_, int F, float c, float* resid,
                                   const int* rmap, int rows, int update, hipStream_t s);
 
+// ---- F0 by YIN and the pitch moments (f0.hip; the rule is in its header and in megatts2_hip.h) ------------------------------------
+// host only, no HIP call: tau_min = ceil(sr / fmax), tau_max = floor(sr / fmin); false where the rule refuses (non-finite or
+// non-positive frequencies, or not 2 <= tau_min < tau_max <= MT2_F0_MAX_LAG)
+bool f0_lags(int sample_rate, float fmin, float fmax, int* lag_min, int* lag_max);
+// One launch over (frames, b) of a ragged batch, one workgroup per frame.  Frames in [T_b, T_max) are written as unvoiced.
+struct F0P {
+    const float* wav; int L_max;              // [B, L_max]; samples at or beyond len[b] are never read
+    const int* len; int max_len, B;           // device [B]; max_b len[b]
+    int sample_rate, hop, lag_min, lag_max;
+    float threshold;
+    float* f0; int T_max;                     // [B, T_max], T_max >= 1 + max_len / hop
+    float* cmnd; int* lag;                    // optional [B, T_max]: d'[tau*], tau*
+    float* diff;                              // optional [B, T_max, MT2_F0_MAX_LAG + 1]: d
+};
+hipError_t launch_f0_yin(const F0P& p, hipStream_t s);
+// stats[b, 0 .. 6) (double) = n, n / T_b, mean, sigma, skewness, excess kurtosis of f0[b, t] > 0 over t < frame_len[b]; a workgroup per utterance
+hipError_t launch_f0_stats(const float* f0, const int* frame_len, int T_max, int B, double* stats, hipStream_t s);
+
 }  // namespace mt2

@@ -61,6 +61,43 @@ def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Option
     return mel if batched else mel[0]
 
 
+def extract_f0(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, **yin):
+    """F0 track of a 1-D waveform (16 kHz) -> f0 [T] in Hz, 0 where a frame is unvoiced: YIN on the GPU by the rule of csrc/f0.hip
+    (MelFrontEnd.f0; no reference counterpart, parity with librosa.yin / pyin and quality on real speech unpinned).  sample_rate and
+    trim_db are extract_mel_spec's, applied first in the same way, so f0[t] belongs to mel frame t of the same call; a [B, L] input
+    gives [B, T].  **yin: MelFrontEnd.f0's arguments (fmin, fmax, threshold, hop, return_cmnd, return_lag, return_diff); with an
+    extra asked for the result is MelFrontEnd.f0's tuple."""
+    import torch
+    fe = _frontend()
+    x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
+    batched = x.dim() == 2
+    x = (x if batched else x.unsqueeze(0)).to("cuda", torch.float32)
+    if sample_rate is not None and int(sample_rate) != fe.audio.sample_rate:
+        x = fe.resample(x, int(sample_rate))[0]
+    lens = None
+    if trim_db is not None:
+        x, lens, _ = fe.trim(x, top_db=trim_db)
+    res = fe.f0(x, lens, **yin)
+    if batched:
+        return res
+    return tuple(r[0] for r in res) if isinstance(res, tuple) else res[0]
+
+
+PITCH_STATS = ("voiced_frames", "voiced_fraction", "mean_hz", "std_hz", "skewness", "kurtosis")
+
+
+def pitch_stats(f0, frame_lens=None) -> Dict[str, np.ndarray]:
+    """The per-utterance pitch moments by which prosody transfer is usually reported, over the voiced frames (f0 > 0) among the
+    first frame_lens[b] of f0 [T] or [B, T] (MelFrontEnd.f0_stats: double sums on the GPU) -> dict of float64 numpy arrays [B]
+    ([1] for a 1-D track): voiced_frames, voiced_fraction, mean_hz, std_hz, skewness, kurtosis (excess).  Without a voiced frame
+    every entry is 0."""
+    import torch
+    x = f0 if hasattr(f0, "is_cuda") else torch.as_tensor(np.asarray(f0, np.float32))
+    x = (x if x.dim() == 2 else x.unsqueeze(0)).to("cuda", torch.float32)
+    st = _frontend().f0_stats(x, frame_lens).cpu().numpy()
+    return {k: st[:, i].copy() for i, k in enumerate(PITCH_STATS)}
+
+
 class LengthRegulator:
     """reference modules/mrte.py:34-60 (FastSpeech length regulator) as a device gather."""
 

@@ -25,6 +25,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 ACT_LOGCLAMP = 4          # epilogue only: log(max(v, pro_slope))
 MT2_RESAMPLE_NORMALIZE = 1
 TRIM_FRAME, TRIM_HOP = 2048, 512      # MT2_TRIM_FRAME, MT2_TRIM_HOP
+F0_FRAME, F0_WINDOW, F0_MAX_LAG = 1024, 768, 256      # MT2_F0_FRAME, MT2_F0_WINDOW, MT2_F0_MAX_LAG
 DTW_MAX_LEN, DTW_DIR_COLS = 4096, 16  # MT2_DTW_MAX_LEN, MT2_DTW_DIR_COLS
 
 
@@ -98,6 +99,9 @@ def load_library():
     lib.mt2_mel_to_linear.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
     lib.mt2_griffin_lim_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
     lib.mt2_griffin_lim.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.mt2_f0_query.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_longlong] + [C.c_void_p] * 4
+    lib.mt2_f0_yin.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+    lib.mt2_f0_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -762,6 +766,47 @@ class MelFrontEnd:
         res = (out, bounds[:, 1] - bounds[:, 0], bounds)
         return res + (energy,) if return_energy else res
 
+    def f0(self, wav, lens=None, fmin: float = 62.5, fmax: float = 500.0, threshold: float = 0.15, hop: Optional[int] = None,
+           return_cmnd: bool = False, return_lag: bool = False, return_diff: bool = False, out=None):
+        """F0 track of a ragged batch by YIN, the rule of csrc/f0.hip (no reference counterpart; parity with librosa.yin / pyin and
+        quality on real speech are unpinned): wav f32 [B, L] (device) at audio.sample_rate -> f0 f32 [B, 1 + max lens // hop] in Hz,
+        0 where a frame is unvoiced or lies behind its utterance's own 1 + lens[b] // hop.  hop defaults to the mel front-end's, so
+        f0[b, t] belongs to mel frame t.  Samples beyond lens[b] are never read.  The extras follow f0 in this order, device tensors:
+        return_cmnd f32 [B, T] (the normalised difference at the chosen lag; voiced iff < threshold), return_lag int32 [B, T],
+        return_diff f32 [B, T, 257] (the difference function).  out: a contiguous f32 [B, >= T] device tensor to write f0 into (the
+        extras then have its width).  The call only enqueues."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+        assert ln.shape == (B,)
+        hop = self.audio.hop_length if hop is None else int(hop)
+        if out is None:
+            out = torch.empty(B, 1 + max(int(ln.max()), 0) // max(hop, 1), device=wav.device, dtype=torch.float32)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        T = out.shape[1]
+        cmnd = torch.empty(B, T, device=wav.device, dtype=torch.float32) if return_cmnd else None
+        lag = torch.empty(B, T, device=wav.device, dtype=torch.int32) if return_lag else None
+        diff = torch.empty(B, T, F0_MAX_LAG + 1, device=wav.device, dtype=torch.float32) if return_diff else None
+        _check(self.lib.mt2_f0_yin(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, self.audio.sample_rate, hop, float(fmin), float(fmax),
+                                   float(threshold), _ptr(out), _ptr(cmnd), _ptr(lag), T, _ptr(diff)))
+        extras = tuple(x for x in (cmnd, lag, diff) if x is not None)
+        return (out,) + extras if extras else out
+
+    def f0_stats(self, f0, frame_lens=None):
+        """Pitch moments of f0 f32 [B, T] (device) over the voiced frames (f0 > 0) among the first frame_lens[b] of each row ->
+        float64 [B, 6] (device): n, n / T_b, mean, sigma, skewness, excess kurtosis - all zeros without a voiced frame.  Sums in
+        double, two passes (csrc/f0.hip).  The call only enqueues."""
+        import torch
+        assert f0.is_cuda and f0.dim() == 2
+        f0 = f0.contiguous().to(torch.float32)
+        B, T = f0.shape
+        ln = self._frame_lens(frame_lens, B, T)
+        stats = torch.empty(B, 6, device=f0.device, dtype=torch.float64)
+        _check(self.lib.mt2_f0_stats(self.h, _stream(), _ptr(f0), _iptr(ln), T, B, _ptr(stats)))
+        return stats
+
     def dtw(self, X, Y, x_lens=None, y_lens=None, return_cost: bool = False, return_acc: bool = False):
         """Dynamic time warping of X f32 [B, Tx, D] onto Y f32 [B, Ty, D] on the bare handle (`_dtw`, as NativeModel.dtw): e.g. the
         DTW mel distance `total` between two utterances of different length."""
@@ -1404,6 +1449,15 @@ def trim_query(L: int, top_db: float):
     f, c = C.c_int(0), C.c_float(0)
     _check(load_library().mt2_trim_query(int(L), float(top_db), C.byref(f), C.byref(c)))
     return f.value, np.float32(c.value)
+
+
+def f0_query(L: int, sample_rate: int = 16000, hop: int = 256, fmin: float = 62.5, fmax: float = 500.0):
+    """mt2_f0_query (no device needed) -> (frames, lag_min, lag_max, workspace_bytes): T = 1 + L // hop, tau_min = ceil(sr / fmax),
+    tau_max = floor(sr / fmin) and the arena bytes of one MelFrontEnd.f0 call; NativeError where the rule refuses."""
+    f, lo, hi, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0)
+    _check(load_library().mt2_f0_query(int(sample_rate), int(hop), float(fmin), float(fmax), int(L), C.byref(f), C.byref(lo), C.byref(hi),
+                                       C.byref(ws)))
+    return f.value, lo.value, hi.value, ws.value
 
 
 def dtw_query(Tx_max: int, Ty_max: int, D: int = 80, B: int = 1) -> int:

@@ -489,7 +489,7 @@ int mt2_synthesize_prompt_conditioned_sampled(mt2_model* m, void* stream, const 
                                               float* wav, int64_t* prompt_codes, const mt2_sampling* sampling);
 
 /* ---- tuning.  Every switch lives in the handle (no process-global state): two handles do not see each other's settings.  None
- * changes results beyond f32 summation order.  The 30 names of round 6 (default in parentheses; the options the A/B records closed
+ * changes results beyond f32 summation order.  The 31 names (default in parentheses; the options the A/B records closed
  * were retired with their code and are unknown names now):
  *   stream groups   "ar_groups" (2; 1..8: the sequences of an autoregressive run are dealt into that many independent kernel chains
  *                   on internal HIP streams that fork from and join back into `stream`), "adm_groups" / "plm_groups" (0: per-stage
@@ -501,7 +501,9 @@ int mt2_synthesize_prompt_conditioned_sampled(mt2_model* m, void* stream, const 
  *                   kernel incl. its LayerNorm prologue), "skinny_nw" (16), "skinny_pairs" (1), "ln_pairs_adm" (2: LayerNorm
  *                   statistics handed from GEMM to GEMM in the ADM's layers), "ln_pairs_maxm" (1280), "ldr_prio" (3: s_setprio of the
  *                   loader waves), "a_planes" (3: bit mask of the producers that hand an activation to an x3h GEMM as fp16 planes -
- *                   1 LayerNorm kernels, 2 ff.0's epilogue -> ff.3, 4 attention -> out-projection);
+ *                   1 LayerNorm kernels, 2 ff.0's epilogue -> ff.3, 4 attention -> out-projection), "pair_fuse" (3: bit mask
+ *                   of the HiFi-GAN stages whose resblock conv pairs x + conv2(lrelu(conv1(lrelu(x)))) run as ONE launch, bit-identical
+ *                   to the two launches - 1 the 32-channel stage, 2 the 64-channel stage, 4 the 128-channel stage);
  *   thresholds      "t_x3h_128" (72), "t_x6_256" (160), "t_x6_128" (72), "t_ks4" (256), "t_ks2" (640), "t32" (64), "t32x32" (160)
  *                   (tile counts at which the tile choice changes), "attn_x6_min" (192), "attn_lds_min" (640) (queries per sequence);
  *   measurement     "force_gemm_config" (-1), "stage_markers" (0), "ldr64" (0).
@@ -726,6 +728,20 @@ const char* mt2_gemm_config_name(int idx);
  * 1024 C).  force_cfg / x3h: the options of the same names.  Returns 0. */
 int mt2_gemm_route(int M, int N, int K, int taps, int dil, int groups, int pro_act, int operands, int misaligned, int force_cfg,
                    int x3h, int* err, int* cfg, int* variant, long long* lds, int* planes);
+/* test hook, no device needed: what launch_conv_pair (csrc/gemm_x3h.hip, conv_pair_route) would do with the resblock conv pair of C
+ * channels, `taps` taps, first dilation `dil` over R rows - err: 0 it launches (or R <= 0: nothing to launch, grid 0), hipErrorNotSupported
+ * (801) the two-launch form keeps the pair, hipErrorInvalidValue (1) bad arguments; lds: dynamic LDS bytes; grid / block: the launch;
+ * bm / bmo: rows per pass / output rows per workgroup.  flags: 1 reflect padding, 2 no fp16 planes, 4 an operand of 2 GiB or more,
+ * 8 an operand off its alignment.  pair_fuse / x3h: the options of the same names.  Returns 0. */
+int mt2_conv_pair_route(int R, int C, int taps, int dil, int flags, int pair_fuse, int x3h, int* err, long long* lds, int* grid,
+                        int* block, int* bm, int* bmo);
+/* test entry: Y [R, ldy] = X + conv2(lrelu(conv1(lrelu(X)))) on the fused pair kernel - X [R, ldx] f32 (C channels), both weight
+ * matrices [C][taps * C] as fp16 planes (mt2_x3h_split) with their inverse row scales, conv1 dilation `dil`, conv2 dilation 1, rows
+ * with valid[m] == 0 written as zeros; pair_fuse: the option's mask (a clear bit answers hipErrorNotSupported as an error); range_flag
+ * as mt2_op_gemm_x3h. */
+int mt2_op_conv_pair(void* stream, const float* X, int ldx, int R, int C, int taps, int dil, float slope, const void* Wh1,
+                     const float* inv1, const float* bias1, const void* Wh2, const float* inv2, const float* bias2,
+                     const int32_t* valid, float* Y, int ldy, int pair_fuse, int32_t* range_flag);
 /* time `iters` back-to-back launches of one GEMM / conv (taps, dilation) with HIP events on `stream`, cycling
  * through `w_copies` copies of the weight matrix (> 1: weights are not L2-resident from the previous launch);
  * flags bit0: leaky-ReLU prologue, bit1: bias + residual + row-mask epilogue, bit2: clock probe - one wave of the

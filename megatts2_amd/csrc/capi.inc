@@ -322,6 +322,7 @@ static int* option_slot(mt2_model* m, const std::string& n) {
     if (n == "ln_pairs_adm") return &m->opts.ln_pairs_adm;
     if (n == "ln_pairs_maxm") return &m->opts.ln_pairs_maxm;
     if (n == "a_planes") return &m->opts.a_planes;
+    if (n == "pair_fuse") return &m->opts.pair_fuse;
     return nullptr;
 }
 static bool* option_flag(mt2_model* m, const std::string& n) {
@@ -1226,6 +1227,49 @@ int mt2_gemm_route(int M, int N, int K, int taps, int dil, int groups, int pro_a
     if (lds) *lds = (long long)r.lds;
     if (planes) *planes = (gemm_takes_planes(p, o) ? 1 : 0) | (gemm_writes_planes(p, o) ? 2 : 0);
     return 0;
+}
+
+// What launch_conv_pair would do with a resblock conv pair, without making it (conv_pair_route; no device needed).  Dense rows (ldx = ldy
+// = C), dummy pointers that are never dereferenced.  flags: 1 reflect padding, 2 no fp16 planes, 4 R is taken as the row count of an
+// operand of 2 GiB (ldx = 2^31 / (4 R) rounded up), 8 the output sits 4 bytes off its alignment.
+int mt2_conv_pair_route(int R, int C, int taps, int dil, int flags, int pair_fuse, int x3h, int* err, long long* lds, int* grid,
+                        int* block, int* bm, int* bmo) {
+    alignas(128) static char dummy[8 * 128];
+    PairP p{};
+    p.X = (const float*)dummy; p.ldx = C; p.R = R; p.C = C; p.taps = taps; p.dil = dil; p.slope = 0.1f;
+    if (!(flags & 2)) { p.Wh1 = dummy + 128; p.inv1 = (const float*)(dummy + 256); p.Wh2 = dummy + 384; p.inv2 = (const float*)(dummy + 512); }
+    p.bias1 = (const float*)(dummy + 640); p.bias2 = (const float*)(dummy + 768);
+    p.wh_ldb = 4ll * (((long long)taps * C + 31) / 32 * 32);
+    p.Y = (float*)(dummy + 896 + ((flags & 8) ? 4 : 0)); p.ldy = C;
+    p.reflect = (flags & 1) ? 1 : 0;
+    if ((flags & 4) && R > 0) p.ldx = (int)((((1ll << 31) / 4 + R - 1) / R + 3) & ~3ll);
+    EngineOpts o;
+    o.pair_fuse = pair_fuse;
+    o.x3h = x3h;
+    const PairRoute r = conv_pair_route(p, o);
+    if (err) *err = (int)r.err;
+    if (lds) *lds = (long long)r.lds;
+    if (grid) *grid = (int)r.grid;
+    if (block) *block = (int)r.block;
+    if (bm) *bm = r.bm;
+    if (bmo) *bmo = r.bmo;
+    return 0;
+}
+// Kernel test of the fused pair: one launch_conv_pair with the per-call EngineOpts of mt2_op_gemm (pair_fuse: the mask)
+int mt2_op_conv_pair(void* stream, const float* X, int ldx, int R, int C, int taps, int dil, float slope, const void* Wh1,
+                     const float* inv1, const float* bias1, const void* Wh2, const float* inv2, const float* bias2,
+                     const int32_t* valid, float* Y, int ldy, int pair_fuse, int32_t* range_flag) {
+    MT2_API_BEGIN
+    PairP p{};
+    p.X = X; p.ldx = ldx; p.R = R; p.C = C; p.taps = taps; p.dil = dil; p.slope = slope;
+    p.Wh1 = Wh1; p.inv1 = inv1; p.bias1 = bias1; p.Wh2 = Wh2; p.inv2 = inv2; p.bias2 = bias2;
+    p.wh_ldb = 4ll * (((long long)taps * C + 31) / 32 * 32);
+    p.valid = valid; p.Y = Y; p.ldy = ldy;
+    EngineOpts o;
+    o.pair_fuse = pair_fuse;
+    o.x3h_flag = range_flag;
+    MT2_HIP(launch_conv_pair(p, (hipStream_t)stream, &o));
+    MT2_API_END
 }
 
 int mt2_op_gemm(void* stream, const float* X, int ldx, int Rx, const int32_t* rowbase, int a_mul, int shift0,

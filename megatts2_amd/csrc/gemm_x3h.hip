@@ -1188,6 +1188,406 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_win_x3h_kernel(Gem
     else epilogue<TM, TN>(p, acc, 0, m0 + wm * WTM, wn * WTN, lane);
 }
 
+// ===================================================================================================
+// The FUSED RESBLOCK PAIR  y = h + conv2(lrelu(conv1(lrelu(h))))  of the vocoder (conv1: k taps, dilation d; conv2: k taps, dilation
+// 1; C = Cin = Cout = 32 QS) as ONE launch of the window kernel's pieces: two passes over memory (read h, write y - plus the
+// residual re-read of lines the workgroup fetched microseconds earlier) where the two conv_win_x3h_kernel launches make five.
+//
+// One workgroup, one window region, two phases.  The OUTPUT tile is BMo = BM - (k - 1) rows [o0, o0 + BMo); conv1 produces the BM
+// rows t1[t0 .. t0 + BM), t0 = o0 - (k - 1) / 2 - the output rows plus conv2's halo - so both convolutions are full BM-row passes.
+//   phase 1: the h window (BM + (k - 1) d rows from t0 - (k - 1) / 2 * d) -> fp16 planes in place (leaky ReLU, range guard) -> conv1's
+//            K loop -> in registers (acc_hi + 2^-11 acc_lo) inv_n + bias, leaky ReLU, row mask (rows outside [0, R) and masked rows: 0)
+//   barrier: every wave has finished with the h planes; t1 goes into the SAME region as f32 rows (the layout the window load leaves)
+//            and through the SAME in-place split (no activation; its guard feeds the same flag) - rows 0 .. BM - 1 only, the rows
+//            behind them keep stale h planes
+//   phase 2: conv2's K loop over the t1 window as a full BM-row pass (local output row j reads t1 rows j .. j + k - 1: the last k - 1
+//            output rows read into the stale planes and are DISCARDED), then the window kernel's epilogue on BMo rows.
+// Every value is computed by the expression, the MFMA order and the split of the two launches it replaces: the result is bit-identical
+// (tests/test_gpu_conv_pair.py), the range flag too (both forms convert every row of h and every row of t1 at least once).
+template <int PRO, int QS, int NT, int MAXT>
+__device__ __forceinline__ void pair_rows_to_planes(float* win, int tid, int WRp, int nrows, float slope, float& amax) {
+    // conv_win_x3h_kernel's in-place pass over rows [0, nrows) of every 32-channel slice: read everything, barrier, write
+    const unsigned lds_w = (unsigned)(unsigned long long)(__attribute__((address_space(3))) float*)win;
+    const int ntask = QS * nrows * 4;                     // (row block, j): f32 slots 2 j, 2 j + 1 -> hi slot j, lo slot 4 + j
+    f32x4 in[MAXT][2];
+    int rbk_[MAXT];
+    __builtin_amdgcn_s_barrier();                         // every wave's rows have landed / are written
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) {
+        const int t = tid + u * NT;
+        const int tt = t < ntask ? t : 0;
+        const int rr = tt >> 2, j = tt & 3;
+        const int q = rr / nrows, row = rr - q * nrows;
+        const int rbk = q * WRp + row;
+        rbk_[u] = rbk;
+        const int swz = (row >> 1) & 7;
+        const unsigned base = lds_w + (unsigned)rbk * 128;
+        in[u][0] = lds_read_b128(base + (unsigned)(((2 * j) ^ swz) * 16));
+        in[u][1] = lds_read_b128(base + (unsigned)(((2 * j + 1) ^ swz) * 16));
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) asm volatile("" : "+v"(in[u][0]), "+v"(in[u][1]));
+    __builtin_amdgcn_s_barrier();                         // everything has been read
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) {
+        const int t = tid + u * NT;
+        if (t < ntask) {
+            const int j = t & 3, rbk = rbk_[u];
+            const int swz = ((rbk % WRp) >> 1) & 7;
+            u32x4 ph, pl;
+            split2_f16<PRO>(in[u][0], in[u][1], slope, ph, pl, amax);
+            char* dst = reinterpret_cast<char*>(win) + (size_t)rbk * 128;
+            *reinterpret_cast<u32x4*>(dst + ((j ^ swz) * 16)) = ph;
+            *reinterpret_cast<u32x4*>(dst + (((4 + j) ^ swz) * 16)) = pl;
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the planes are in LDS before this wave's next barrier
+}
+
+template <int QS, int BM, int BN, int WGM, int WGN, int NST, int NL>
+__global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_pair_x3h_kernel(PairP p) {
+    constexpr int NW = WGM * WGN;
+    constexpr int WTM = BM / WGM, WTN = BN / WGN;
+    constexpr int TM = WTM / 32, TN = WTN / 32;
+    constexpr int BPIECES = BN / 8;
+    constexpr int NI = NL;
+    constexpr int B_IT = (BPIECES + NI - 1) / NI;
+    constexpr int STAGE_B = B_IT * NI * 1024;
+    constexpr int NT = (NW + NL) * 64;
+    constexpr int MAXT1 = (QS * (BM + 64) * 4 + NT - 1) / NT;       // conv_pair_route: (k - 1) d <= 64
+    constexpr int MAXT2 = (QS * BM * 4 + NT - 1) / NT;
+    static_assert(NL > 0 && WTM % 32 == 0 && WTN % 32 == 0 && NST >= 3 && (NST - 2) * B_IT < 64 && BN == 32 * QS, "config");
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool loader = wave_all >= NW;
+    const int wave = loader ? wave_all - NW : wave_all;
+    const int wm = wave / WGN, wn = wave % WGN;
+    const int taps = p.taps;
+    const int WR = BM + (taps - 1) * p.dil, WRp = (WR + 7) & ~7;
+    const int BMo = BM - (taps - 1);
+    char* ring = reinterpret_cast<char*>(smem);
+    float* win = smem + NST * STAGE_B / 4;                          // [QS][WRp][32] f32 / planes, slot-swizzled rows
+
+    const int ntm = (p.R + BMo - 1) / BMo;
+    const int bid = blockIdx.x;
+    const int xcd = bid & 7, qq = ntm >> 3, rr = ntm & 7;
+    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int o0 = tile * BMo;                                      // first output row
+    const int t0 = o0 - (taps - 1) / 2;                             // global row of t1's local row 0
+
+    const float* __restrict__ X = p.X;
+    const long long zoff_x = (const float*)g_zero16 - X;
+    const int ldx = p.ldx, Rx = p.R;
+    {   // ---- the f32 window of h, once
+        const int lrow = lane >> 3;
+        const int ppq = WRp >> 3, pieces = QS * ppq;
+        const int row_first = t0 - (taps - 1) / 2 * p.dil;
+        for (int pc = wave_all; pc < pieces; pc += NW + NL) {
+            const int q = pc / ppq, r8 = pc - q * ppq;
+            const int row = r8 * 8 + lrow;
+            const int grow = row_first + row;
+            const int slot = (lane & 7) ^ ((row >> 1) & 7);
+            const bool ok = (row < WR) & ((unsigned)grow < (unsigned)Rx);
+            const long long off = ok ? (long long)grow * ldx + q * 32 + slot * 4 : zoff_x;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(X + off),
+                                             (__attribute__((address_space(3))) void*)(win + (q * WRp + r8 * 8) * 32), 16, 0, 0);
+        }
+    }
+    // ---- weight chunks through the ring (conv_win_x3h_kernel's pieces; both matrices are [C, k C]: one lane offset serves both).
+    // Buffer loads only: conv_pair_route sends operands of 2 GiB or more to the two-launch form
+    const int nk = taps * QS;
+    constexpr unsigned kOut = 0x80000000u;
+    unsigned vob[B_IT];
+#pragma unroll
+    for (int j = 0; j < B_IT; ++j) {
+        const int pc = j * NI + wave;
+        const int n = pc * 8 + (lane >> 3);
+        const int sl = (lane & 7) ^ ((n >> 1) & 7);
+        vob[j] = (pc < BPIECES && n < BN) ? (unsigned)(n * (int)p.wh_ldb + sl * 16) : kOut;
+    }
+    auto issue = [&](const __amdgpu_buffer_rsrc_t& rs, int c, int st) __attribute__((always_inline)) {
+        char* Bs = ring + st * STAGE_B + wave * 1024;
+#pragma unroll
+        for (int j = 0; j < B_IT; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(Bs + j * NI * 1024), 16, (int)vob[j], c * 128, 0, 0);
+    };
+    // the loader waves' side of one K loop: the first ring stages are in flight
+    auto loader_loop = [&](const __amdgpu_buffer_rsrc_t& rs) __attribute__((always_inline)) {
+        for (int c = 0; c < nk; ++c) {
+            if (c == 0) { if (NST - 2 < nk) wait_vmcnt<(NST - 2) * B_IT>(); else wait_vmcnt<0>(); }
+            else if (c + NST - 3 < nk) wait_vmcnt<(NST - 3) * B_IT>();
+            else wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+            if (c >= 1 && c + NST - 2 < nk) issue(rs, c + NST - 2, (c + NST - 2) % NST);
+        }
+    };
+    if (loader) {
+        const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.Wh1)), 0, (int)kOut, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.Wh2)), 0, (int)kOut, 0x00020000);
+        loader_priority(p.ldr_prio);
+#pragma unroll
+        for (int st = 0; st < NST - 1; ++st)
+            if (st < nk) issue(rs1, st, st);
+        if (nk >= NST - 1) wait_vmcnt<(NST - 1) * B_IT>();      // the window pieces (older than the ring's) have landed
+        else wait_vmcnt<0>();
+        float amax = 0.0f;
+        pair_rows_to_planes<ACT_LRELU, QS, NT, MAXT1>(win, tid, WRp, WRp, p.slope, amax);
+        if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+        loader_loop(rs1);
+        __builtin_amdgcn_s_barrier();                            // every compute wave has left conv1's K loop: ring and window are free
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int st = 0; st < NST - 1; ++st)
+            if (st < nk) issue(rs2, st, st);
+        amax = 0.0f;
+        pair_rows_to_planes<ACT_NONE, QS, NT, MAXT2>(win, tid, WRp, BM, p.slope, amax);
+        if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+        loader_loop(rs2);
+        return;
+    }
+    // ---- compute waves.  Phase 1's epilogue operands, one load each: the row mask of the wave's 32-row blocks of t1 as a ballot (rows
+    // outside [0, R) count as masked), bias and inverse row scale of the lane's columns
+    unsigned vmask[TM];
+    {
+        int vv[TM];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int g = t0 + wm * WTM + i * 32 + (lane & 31);
+            const bool ok = (unsigned)g < (unsigned)Rx;
+            vv[i] = ok ? (p.valid ? p.valid[g] : 1) : 0;
+        }
+        wait_vmcnt<0>();               // this compute wave's window pieces (and the masks)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) vmask[i] = (unsigned)__builtin_amdgcn_ballot_w64(vv[i] != 0);
+    }
+    float amax = 0.0f;
+    pair_rows_to_planes<ACT_LRELU, QS, NT, MAXT1>(win, tid, WRp, WRp, p.slope, amax);
+    if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+
+    f32x16 acc[TM][TN], acl[TM][TN];
+    const int half = lane >> 5;
+    const unsigned lds_ring = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)ring;
+    const unsigned lds_win = (unsigned)(unsigned long long)(__attribute__((address_space(3))) float*)win;
+    const int nrow = wn * WTN + (lane & 31);
+    const unsigned b_lane = lds_ring + nrow * 128;
+    const int swzb = (nrow >> 1) & 7;
+    unsigned koffb[2][2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        koffb[b][0] = (unsigned)(((b * 2 + half) ^ swzb) * 16);
+        koffb[b][1] = (unsigned)(((4 + b * 2 + half) ^ swzb) * 16);
+    }
+    const int arow0 = wm * WTM + (lane & 31);
+    // conv_win_x3h_kernel's cross-chunk fragment pipeline (see there), run once per convolution
+    constexpr int N1 = 2 * TM + 2 * TN;
+    static_assert(N1 <= 15, "lgkmcnt is four bits wide");
+    u32x4 ra[2][TM][2];
+    u32x4 rb[2][2][TN];
+    auto fetch_a = [&](int b, unsigned sa, int swza) __attribute__((always_inline)) {
+        const unsigned vh = sa + (unsigned)(((b * 2 + half) ^ swza) * 16), vl = sa + (unsigned)(((4 + b * 2 + half) ^ swza) * 16);
+        static_for(std::make_integer_sequence<int, TM>{}, [&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            ra[b][i][0] = __builtin_bit_cast(u32x4, lds_read_b128_imm<i * 32 * BK * 4>(vh));
+            ra[b][i][1] = __builtin_bit_cast(u32x4, lds_read_b128_imm<i * 32 * BK * 4>(vl));
+        });
+    };
+    auto fetch_b = [&](int b, unsigned sb) __attribute__((always_inline)) {
+        const unsigned vb0 = sb + koffb[b][0], vb1 = sb + koffb[b][1];
+        static_for(std::make_integer_sequence<int, TN>{}, [&](auto ic) {
+            constexpr int j = decltype(ic)::value;
+            rb[b][0][j] = __builtin_bit_cast(u32x4, lds_read_b128_imm<j * 32 * 128>(vb0));
+            rb[b][1][j] = __builtin_bit_cast(u32x4, lds_read_b128_imm<j * 32 * 128>(vb1));
+        });
+    };
+    auto tie_set = [&](int b) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(ra[b][i][0]), "+v"(ra[b][i][1]));
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(rb[b][pl][j]));
+    };
+    auto products = [&](int b) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const f16x8 Ah = __builtin_bit_cast(f16x8, ra[b][i][0]), Al = __builtin_bit_cast(f16x8, ra[b][i][1]);
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acl[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, __builtin_bit_cast(f16x8, rb[b][1][j]), acl[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, __builtin_bit_cast(f16x8, rb[b][0][j]), acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acl[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, __builtin_bit_cast(f16x8, rb[b][0][j]), acl[i][j], 0, 0, 0);
+        }
+    };
+    // one convolution over the planes in the window: acc = (acc_hi + 2^-11 acc_lo) * inv_n on return
+    auto kloop = [&](const int dil, const float* __restrict__ wh_inv) __attribute__((always_inline)) {
+        float inv_s[TN];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) inv_s[j] = wh_inv[wn * WTN + j * 32 + (lane & 31)];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.0f; acl[i][j][e] = 0.0f; }
+        __builtin_amdgcn_s_barrier();                     // the window's planes are written and the weights of chunk 0 have landed
+        asm volatile("" ::: "memory");
+        {
+            const unsigned sa0 = lds_win + (unsigned)(arow0 * BK) * 4;
+            const int swz0 = (arow0 >> 1) & 7;
+            fetch_a(0, sa0, swz0); fetch_b(0, b_lane); fetch_a(1, sa0, swz0); fetch_b(1, b_lane);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        int stn = 1 % NST, tapn = 0, qn = 1;              // chunk c + 1: its ring stage, tap and 32-channel slice
+        if (qn == QS) { qn = 0; tapn = 1; }
+        auto chunk = [&](auto last_c) __attribute__((always_inline)) {
+            constexpr bool last = decltype(last_c)::value;
+            const int arow = arow0 + tapn * dil;
+            const int swza = (arow >> 1) & 7;
+            const unsigned sa = lds_win + (unsigned)((qn * WRp + arow) * BK) * 4;
+            const unsigned sb = b_lane + (unsigned)stn * STAGE_B;
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                if (last && b == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                else asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(N1) : "memory");
+                tie_set(b);
+                __builtin_amdgcn_sched_barrier(0);
+                products(b);
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (!last) {
+                    if (b == 0) {
+                        __builtin_amdgcn_s_barrier();     // the weights of chunk c + 1 have landed
+                        asm volatile("" ::: "memory");
+                    }
+                    fetch_a(b, sa, swza);                 // A(q + 2), B(q + 2)
+                    fetch_b(b, sb);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            stn = stn + 1 == NST ? 0 : stn + 1;
+            if (++qn == QS) { qn = 0; ++tapn; }
+        };
+        for (int c = 0; c + 1 < nk; ++c) chunk(std::false_type{});
+        chunk(std::true_type{});
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    float v = __builtin_fmaf(acl[i][j][e], kX3hLoInv, acc[i][j][e]) * inv_s[j];
+                    asm volatile("" : "+v"(v));           // the product is rounded on its own, as in front of the window kernel's epilogue
+                    acc[i][j][e] = v;
+                }
+    };
+    // ---- phase 1: t1 = mask * lrelu(conv1(lrelu(h)) + bias1), into the window region as f32 rows
+    kloop(p.dil, p.inv1);
+    {
+        float b1[TN];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) b1[j] = p.bias1 ? p.bias1[wn * WTN + j * 32 + (lane & 31)] : 0.0f;
+        const float slope = p.slope;
+        __builtin_amdgcn_s_barrier();                     // every wave has left conv1's K loop: the h planes are dead
+        asm volatile("" ::: "memory");
+        const int c = lane & 31;
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int r32 = (e & 3) + 8 * (e >> 2) + 4 * half;
+                const int row = wm * WTM + i * 32 + r32;
+                const bool on = (vmask[i] >> r32) & 1u;
+                float* dst = win + row * 32 + ((((c >> 2) ^ ((row >> 1) & 7)) << 2) | (c & 3));
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    float v = acc[i][j][e] + b1[j];
+                    v = v >= 0.0f ? v : v * slope;
+                    dst[((wn * WTN) / 32 + j) * WRp * 32] = on ? v : 0.0f;
+                }
+            }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    amax = 0.0f;
+    pair_rows_to_planes<ACT_NONE, QS, NT, MAXT2>(win, tid, WRp, BM, p.slope, amax);
+    if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+    // ---- phase 2: y = mask * (conv2(t1) + bias2 + h) on the first BMo rows of the pass
+    kloop(1, p.inv2);
+    GemmP e{};
+    e.bias = p.bias2; e.R = p.X; e.ldr = p.ldx; e.valid = p.valid; e.C = p.Y; e.ldc = p.ldy;
+    e.M = min(p.R, o0 + BMo); e.N = BN; e.epi_act = ACT_NONE; e.pro_slope = p.slope; e.out_scale = 1.0f;
+    if (epilogue_t4_ok(e)) epilogue_t4<TM, TN>(e, acc, 0, o0 + wm * WTM, wn * WTN, lane);
+    else epilogue<TM, TN>(e, acc, 0, o0 + wm * WTM, wn * WTN, lane);
+}
+
+// host side of the pair: the three tiles (the window tiles 98 / 99 / 100), the route and the launch
+typedef void (*PairKernel)(PairP);
+struct PairTile { int C, bm, threads; size_t ring; PairKernel fn; };
+#define MT2_PAIR_TILE(QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                                    \
+    { BN_, BM_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * (((2 * BN_ / 16 + NL_ - 1) / NL_) * NL_ * 1024),                        \
+      conv_pair_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, NL_> }
+static const PairTile kPairTiles[3] = {
+    MT2_PAIR_TILE(1, 256, 32, 8, 1, 4, 4), MT2_PAIR_TILE(2, 256, 64, 8, 1, 4, 4), MT2_PAIR_TILE(4, 128, 128, 4, 2, 3, 4),
+};
+
+PairRoute conv_pair_route(const PairP& p, const EngineOpts& o) {
+    PairRoute r{hipSuccess, -1, 0, 0, 0, 0, 0};
+    const auto fail = [&r](hipError_t e) { r.err = e; r.tile = -1; r.lds = 0; r.grid = r.block = 0; r.bm = r.bmo = 0; return r; };
+    if (p.R <= 0) return r;                                          // nothing to launch
+    if (p.taps < 2 || p.dil < 1 || p.C <= 0) return fail(hipErrorInvalidValue);
+    // the two-launch form keeps everything the pair kernel was not built for
+    const int t = p.C == 32 ? 0 : (p.C == 64 ? 1 : (p.C == 128 ? 2 : -1));
+    if (t < 0 || !((o.pair_fuse >> t) & 1)) return fail(hipErrorNotSupported);
+    if (p.reflect || (long long)(p.taps - 1) * p.dil > 64) return fail(hipErrorNotSupported);
+    // ... and everything that would not run on the x3h window tiles as two launches (the pair is bit-identical to THOSE)
+    if (!o.win_conv || !o.x6_conv || !(o.x3h & 4) || o.force_cfg >= 0 || o.ldr64) return fail(hipErrorNotSupported);
+    if (!p.Wh1 || !p.Wh2 || !p.inv1 || !p.inv2) return fail(hipErrorNotSupported);      // missing planes
+    const long long two_g = 1ll << 31;
+    if ((long long)p.R * p.ldx * 4 >= two_g || (long long)p.R * p.ldy * 4 >= two_g || (long long)p.C * p.wh_ldb >= two_g - 1)
+        return fail(hipErrorNotSupported);
+    if (!p.X || !p.Y || p.ldx < p.C || p.ldy < p.C || p.wh_ldb < 4ll * p.taps * p.C) return fail(hipErrorInvalidValue);
+    // (the window kernel's epilogue has a scalar-store form for operands off 16 bytes; the pair kernel leaves them to it)
+    if (((p.ldx | p.ldy) & 3) || (p.wh_ldb & 127) || (((unsigned long long)p.Wh1 | (unsigned long long)p.Wh2) & 127) ||
+        (((unsigned long long)p.X | (unsigned long long)p.Y | (unsigned long long)p.bias1 | (unsigned long long)p.bias2) & 15))
+        return fail(hipErrorNotSupported);
+    const PairTile& c = kPairTiles[t];
+    const int wrp = (c.bm + (p.taps - 1) * p.dil + 7) & ~7;
+    r.tile = t;
+    r.bm = c.bm;
+    r.bmo = c.bm - (p.taps - 1);
+    r.lds = c.ring + (size_t)(p.C / 32) * wrp * BK * sizeof(float);
+    r.grid = (unsigned)((p.R + r.bmo - 1) / r.bmo);
+    r.block = (unsigned)c.threads;
+    return r;
+}
+
+static std::atomic<unsigned long long> g_pair_attr_done[3];
+
+hipError_t launch_conv_pair(const PairP& p_in, hipStream_t s, EngineOpts* opts) {
+    static const EngineOpts kDefaults;
+    const EngineOpts& o = opts ? *opts : kDefaults;
+    const PairRoute r = conv_pair_route(p_in, o);
+    if (r.err != hipSuccess || r.grid == 0) return r.err;
+    const PairTile& c = kPairTiles[r.tile];
+    PairP p = p_in;
+    p.x3h_flag = o.x3h_flag;
+    p.ldr_prio = o.ldr_prio;
+    // the attribute covers the widest window ((k - 1) d <= 64)
+    const size_t lds_attr = c.ring + (size_t)(p.C / 32) * ((c.bm + 64 + 7) & ~7) * BK * sizeof(float);
+    const hipError_t e = dyn_lds_once(g_pair_attr_done[r.tile], reinterpret_cast<const void*>(c.fn), lds_attr);
+    if (e != hipSuccess) return e;
+    if (opts) opts->last_cfg = "x3hpair";
+    hipLaunchKernelGGL(c.fn, dim3(r.grid), dim3(r.block), r.lds, s, p);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------
 // host side: the table rows of this unit's tiles (gemm_tiles.h; gemm_dispatch.hip places them and routes launches)
 

@@ -242,6 +242,29 @@ static void conv_same(const Ctx& c, const float* x, int ldx, int R, const ConvW&
     gemm(c, p);
 }
 
+// y = x + conv2(lrelu(conv1(lrelu(x)))) (ResBlock1's pair: conv1 dilated, conv2 dilation 1, both k taps, C -> C) as one launch of
+// the fused pair kernel; false: conv_pair_route keeps the two-launch form for this pair (nothing was launched)
+static bool conv_pair(const Ctx& c, const float* x, int C, int R, const ConvW& w1, const ConvW& w2, int dil, float slope,
+                      bool reflect, float* y, const int* valid) {
+    if (w1.k != w2.k || w1.cin != C || w1.cout != C || w2.cin != C || w2.cout != C) return false;
+    GemmP g1{}, g2{};
+    g1.W = w1.w; g1.taps = w1.k; g1.Cin = C; g1.groups = 1;
+    g2.W = w2.w; g2.taps = w2.k; g2.Cin = C; g2.groups = 1;
+    attach_planes(c.m, g1);
+    attach_planes(c.m, g2);
+    if (!g1.W3 || !g2.W3 || g1.wh_ldb != g2.wh_ldb) return false;        // (the two launches would not run on the x3h tiles either)
+    PairP p{};
+    p.X = x; p.ldx = C; p.R = R; p.C = C; p.taps = w1.k; p.dil = dil; p.slope = slope;
+    p.Wh1 = g1.Wh; p.inv1 = g1.wh_inv; p.bias1 = w1.b;
+    p.Wh2 = g2.Wh; p.inv2 = g2.wh_inv; p.bias2 = w2.b;
+    p.wh_ldb = g1.wh_ldb ? g1.wh_ldb : 4ll * ((w1.k * C + 31) / 32 * 32);
+    p.valid = valid; p.Y = y; p.ldy = C; p.reflect = reflect ? 1 : 0;
+    const hipError_t e = launch_conv_pair(p, c.s, &c.m.opts);
+    if (e == hipErrorNotSupported) return false;
+    MT2_HIP(e);
+    return true;
+}
+
 static void layernorm(const Ctx& c, const float* x, int ldx, const float* g, const float* b, int M, int C,
                       float* out, int ldo, const int* valid = nullptr, int valid_rows = 0,
                       const float* R1 = nullptr, int ldr1 = 0, int r1_rows = 0, int rows_per_group = 0,
@@ -1422,6 +1445,12 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
                 // x + conv2(lrelu(conv1(lrelu(x)))): the inner leaky ReLU has ONE consumer, so it is applied once in
                 // conv1's epilogue instead of on every operand fragment of conv2 (same values, no VALU in that loop)
                 if (n > 0) halo(cj, const_cast<float*>(h), ch, (r.k - 1) / 2 * r.dil[n]);
+                // ... and both convolutions as ONE launch where conv_pair_route takes the pair (option pair_fuse): t1 never leaves
+                // the workgroup's LDS.  Bit-identical; NotSupported keeps the two launches below
+                if (m.opts.pair_fuse && conv_pair(cj, h, ch, (int)R, r.c1[n], r.c2[n], r.dil[n], slope, reflect, out, valid)) {
+                    h = out;
+                    continue;
+                }
                 conv_same(cj, h, ch, (int)R, r.c1[n], t1, ch, valid, ACT_LRELU, slope, ACT_LRELU, nullptr, 0, r.dil[n]);
                 halo(cj, t1, ch, (r.k - 1) / 2);
                 conv_same(cj, t1, ch, (int)R, r.c2[n], out, ch, valid, ACT_NONE, slope, ACT_NONE, h, ch, 1);

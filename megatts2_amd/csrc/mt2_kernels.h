@@ -111,6 +111,8 @@ struct EngineOpts {
                                  // weights come with fp16 planes (GemmP::Wh); bits: 1 the 128x128 loader tile, 2 the K-split tiles of the
                                  // AR steps, 4 the window convolutions, 8 the long-sequence attention kernel (AttnP::x3h: C5 -3.3 %,
                                  // profiles/r06_opts_ab_block6_attention_x3h.txt); 0: everything stays x6
+    int pair_fuse = 3;           // the vocoder's resblock conv pairs as ONE launch (PairP, conv_pair_x3h_kernel): bit 0 the 32-channel stage,
+                                 // bit 1 the 64-channel stage, bit 2 the 128-channel stage (profiles/conv_pair_fusion_ab.txt)
     int* x3h_flag = nullptr;     // device word of the range guard (GemmP::x3h_flag); the model handle owns one
     int t_x3h_128 = 72;          // x3h: from this many 128x128 tiles on the loader tile instead of the K-split tiles (t_x6_128's role)
     int t_x6_256 = 160, t_x6_128 = 72;   // ... from this many 256x128 / 128x128 tiles on (profiles/r02_gemm_sweep_x6.txt)
@@ -159,6 +161,34 @@ struct EngineOpts {
 struct GemmRoute { hipError_t err; int cfg; int variant; size_t lds; int stat_nt, stat_w; };
 GemmRoute gemm_route(const GemmP& p, const EngineOpts& o);
 hipError_t launch_gemm(const GemmP& p, hipStream_t s, EngineOpts* o = nullptr);
+// The vocoder's resblock pair  Y = X + conv2(lrelu(conv1(lrelu(X))))  as ONE launch (conv_pair_x3h_kernel, gemm_x3h.hip): conv1 with
+// `taps` taps and dilation `dil`, conv2 with `taps` taps and dilation 1, both "same" convolutions C -> C over the R gap-padded rows of
+// X, the leaky ReLU's slope `slope`, rows with valid[m] == 0 written as zeros (and read as zeros by conv2).  The weights come as the fp16
+// planes of GemmP::Wh ([C][taps * C / 32] blocks of 128 bytes, wh_ldb bytes between rows, both matrices alike) with the inverse row
+// scales inv1 / inv2.  Bit-identical to the two launch_gemm calls on the x3h window tiles that it replaces.
+struct PairP {
+    const float* X; int ldx;
+    int R, C, taps, dil;
+    float slope;
+    const void* Wh1; const float* inv1; const float* bias1;
+    const void* Wh2; const float* inv2; const float* bias2;
+    long long wh_ldb;
+    const int* valid;
+    float* Y; int ldy;
+    int reflect = 0;            // 1: the caller runs the vocoder with reflect padding (halo rows between the two convolutions): never fused
+    int* x3h_flag = nullptr;    // set by launch_conv_pair from EngineOpts::x3h_flag
+    int ldr_prio = 0;           // ... from EngineOpts::ldr_prio
+};
+// conv_pair_route decides, without a HIP call, what launch_conv_pair does (the gemm_route pattern).  err: hipSuccess - it launches (or
+// R <= 0: nothing to launch, grid 0); hipErrorNotSupported - the caller keeps the two-launch form: C not in {32, 64, 128} or its bit
+// of EngineOpts::pair_fuse clear, reflect padding, (taps - 1) dil > 64, missing planes, an operand of 2 GiB or more, an operand off its alignment (X, Y,
+// biases on 16 bytes, planes and wh_ldb on 128, ldx / ldy multiples of 4), or engine options under which the two launches would not
+// run on the x3h window tiles (win_conv / x6_conv / x3h bit 2 off, a forced configuration, ldr64); hipErrorInvalidValue - taps < 2,
+// dil < 1, C <= 0, X or Y null, ldx / ldy < C, wh_ldb < 4 taps C.  tile: 0 / 1 / 2 = 32 / 64 / 128 channels; bm rows per pass, bmo = bm - (taps - 1) output rows per
+// workgroup, grid = ceil(R / bmo), lds = ring + (C / 32) * ceil8(bm + (taps - 1) dil) * 128 bytes.
+struct PairRoute { hipError_t err; int tile; size_t lds; unsigned grid, block; int bm, bmo; };
+PairRoute conv_pair_route(const PairP& p, const EngineOpts& o);
+hipError_t launch_conv_pair(const PairP& p, hipStream_t s, EngineOpts* o = nullptr);
 // would launch_gemm run this launch (planes attached, no prologue) on an x3h tile that takes its A operand as fp16 planes (a_planes)?
 bool gemm_takes_planes(const GemmP& p, const EngineOpts& o);
 // would launch_gemm run this launch on an x3h loader tile whose epilogue can store C as fp16 planes (GemmP::c_planes)?

@@ -1079,6 +1079,33 @@ def op_conv_x3h(X, W, bias=None, R=None, valid=None, shift0=0, taps=1, dil=1, Ci
     return (out, int(flag[0].item())) if want_flag else out
 
 
+def op_conv_pair(X, W1, b1, W2, b2, taps, dil, slope, valid=None, channels=None, out=None, pair_fuse=7, want_flag=False):
+    """mt2_op_conv_pair: out = X + conv2(lrelu(conv1(lrelu(X)))) on the fused pair kernel.  X [R, ldx] f32 of which the first `channels`
+    columns are the channels (all when None), W1 / W2 [C, taps * C] f32 (split into fp16 planes here), conv1 dilation dil, conv2 dilation 1, rows with
+    valid == 0 written as zeros.  out [R, ldy >= C] (allocated [R, C] when None) receives the C columns.  want_flag -> (out, flag)."""
+    import torch
+    lib = load_library()
+    Cc = channels or X.shape[1]
+    R = X.shape[0]
+    p1, i1 = (t.to(X.device) for t in split_f16x2_rows(W1))
+    p2, i2 = (t.to(X.device) for t in split_f16x2_rows(W2))
+    if out is None:
+        out = torch.empty(R, Cc, device=X.device, dtype=torch.float32)
+    flag = torch.zeros(4, device=X.device, dtype=torch.int32)
+    _check(lib.mt2_op_conv_pair(_stream(), _ptr(X), X.shape[1], R, Cc, taps, dil, C.c_float(slope), _ptr(p1), _ptr(i1), _ptr(b1),
+                                _ptr(p2), _ptr(i2), _ptr(b2), _ptr(valid), _ptr(out), out.shape[1], pair_fuse, _ptr(flag)))
+    return (out, int(flag[0].item())) if want_flag else out
+
+
+def op_conv_pair_route(R, Cn, taps, dil, flags=0, pair_fuse=7, x3h=15):
+    """mt2_conv_pair_route (no device needed) -> dict(err, lds, grid, block, bm, bmo) of the launch launch_conv_pair would make.
+    flags: 1 reflect padding, 2 no fp16 planes, 4 an operand of 2 GiB, 8 an operand off its alignment."""
+    err, lds, grid, block, bm, bmo = C.c_int(0), C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    load_library().mt2_conv_pair_route(R, Cn, taps, dil, flags, pair_fuse, x3h, C.byref(err), C.byref(lds), C.byref(grid), C.byref(block),
+                                       C.byref(bm), C.byref(bmo))
+    return {"err": err.value, "lds": lds.value, "grid": grid.value, "block": block.value, "bm": bm.value, "bmo": bmo.value}
+
+
 def op_gemm_x6_ln(X, W, bias=None, R=None, M=None, a_mul=1, shift0=0, epi_act=ACT_NONE, force_cfg=-1, want_stats=False,
                   ln=None, eps=1e-5, x3h=False):
     """mt2_op_gemm_x6_ln: one linear launch on an x6 tile.  want_stats -> also returns (pairs [M, nt, 2], pair width) written by

@@ -1005,14 +1005,15 @@ def split_bf16x3(W):
 
 
 def op_conv_x6(X, W, bias=None, R=None, valid=None, shift0=0, taps=1, dil=1, Cin=None, pro_act=ACT_NONE, pro_slope=0.0,
-               epi_act=ACT_NONE, force_cfg=-1):
-    """Window convolution with bf16 weight planes (mt2_op_gemm_x6): X [rows, Cin] f32, W [N, taps*Cin] f32."""
+               epi_act=ACT_NONE, force_cfg=-1, out=None):
+    """Window convolution with bf16 weight planes (mt2_op_gemm_x6): X [rows, Cin] f32, W [N, taps*Cin] f32; out [rows, N] f32 when given."""
     import torch
     lib = load_library()
     Cin = Cin or X.shape[1]
     N, M = W.shape[0], X.shape[0]
     W3 = split_bf16x3(W).to(X.device)
-    out = torch.empty(M, N, device=X.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(M, N, device=X.device, dtype=torch.float32)
     _check(lib.mt2_op_gemm_x6(_stream(), _ptr(X), X.shape[1], M, shift0, taps, dil, Cin, _ptr(W), _ptr(W3), _ptr(bias),
                               _ptr(R), R.shape[1] if R is not None else 0, _ptr(valid), _ptr(out), N, M, N, pro_act,
                               C.c_float(pro_slope), epi_act, force_cfg))
@@ -1058,7 +1059,7 @@ def x3h_split_native(W):
 
 
 def op_conv_x3h(X, W, bias=None, R=None, valid=None, shift0=0, taps=1, dil=1, Cin=None, pro_act=ACT_NONE, pro_slope=0.0,
-                epi_act=ACT_NONE, force_cfg=-1, want_flag=False):
+                epi_act=ACT_NONE, force_cfg=-1, want_flag=False, out=None):
     """mt2_op_gemm_x3h: one GEMM / convolution launch with the weights given as f32, as bf16 planes and as fp16 planes (so that
     every tile configuration can be forced): X [rows, Cin] f32, W [N, taps*Cin] f32.  want_flag -> (out, range flag).
     Test conventions of the entry point: force_cfg + 1000 = the same launch with the loaders' 64-bit address form; + 2000 = X holds
@@ -1071,7 +1072,8 @@ def op_conv_x3h(X, W, bias=None, R=None, valid=None, shift0=0, taps=1, dil=1, Ci
     W3 = split_bf16x3(W).to(X.device)
     ph, inv = split_f16x2_rows(W)
     ph, inv = ph.to(X.device), inv.to(X.device)
-    out = torch.empty(M, N, device=X.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(M, N, device=X.device, dtype=torch.float32)
     flag = torch.zeros(4, device=X.device, dtype=torch.int32)
     _check(lib.mt2_op_gemm_x3h(_stream(), _ptr(X), X.shape[1], M, shift0, taps, dil, Cin, _ptr(W), _ptr(W3), _ptr(ph), _ptr(inv),
                                _ptr(bias), _ptr(R), R.shape[1] if R is not None else 0, _ptr(valid), _ptr(out), N, M, N, pro_act,

@@ -501,7 +501,8 @@ int mt2_synthesize_prompt_conditioned_sampled(mt2_model* m, void* stream, const 
  *                   kernel incl. its LayerNorm prologue), "skinny_nw" (16), "skinny_pairs" (1), "ln_pairs_adm" (2: LayerNorm
  *                   statistics handed from GEMM to GEMM in the ADM's layers), "ln_pairs_maxm" (1280), "ldr_prio" (3: s_setprio of the
  *                   loader waves), "a_planes" (3: bit mask of the producers that hand an activation to an x3h GEMM as fp16 planes -
- *                   1 LayerNorm kernels, 2 ff.0's epilogue -> ff.3, 4 attention -> out-projection), "pair_fuse" (3: bit mask
+ *                   1 LayerNorm kernels, 2 ff.0's epilogue -> ff.3, 4 attention -> out-projection), "up_fuse" (3: bit mask 1 | 2 = the MRF mean in front of the 64- | 128-channel
+ *                   stride-2 upsampler fused into it), "pair_fuse" (3: bit mask
  *                   of the HiFi-GAN stages whose resblock conv pairs x + conv2(lrelu(conv1(lrelu(x)))) run as ONE launch, bit-identical
  *                   to the two launches - 1 the 32-channel stage, 2 the 64-channel stage, 4 the 128-channel stage);
  *   thresholds      "t_x3h_128" (72), "t_x6_256" (160), "t_x6_128" (72), "t_ks4" (256), "t_ks2" (640), "t32" (64), "t32x32" (160)
@@ -742,6 +743,20 @@ int mt2_conv_pair_route(int R, int C, int taps, int dil, int flags, int pair_fus
 int mt2_op_conv_pair(void* stream, const float* X, int ldx, int R, int C, int taps, int dil, float slope, const void* Wh1,
                      const float* inv1, const float* bias1, const void* Wh2, const float* inv2, const float* bias2,
                      const int32_t* valid, float* Y, int ldy, int pair_fuse, int32_t* range_flag);
+/* test hook, no device needed: what launch_up_mrf (csrc/gemm_x3h.hip, up_mrf_route) would do with the fused MRF mean + stride-`stride`
+ * transposed convolution of `ch` input channels over R rows - err / lds / grid / block as mt2_conv_pair_route; bm: rows per workgroup.
+ * flags: 1 no fp16 planes, 2 an operand of 2 GiB or more, 4 the output off its alignment, 8 the planes off theirs, 16 a row stride that
+ * is no multiple of 4, 32 a null input, 64 an output row stride below the width, 128 the bias off its alignment.  up_fuse / x3h: the
+ * options of the same names; off: 1 win_conv off, 2 x6_conv off, 4 a forced configuration, 8 ldr64.  Returns 0. */
+int mt2_up_mrf_route(int R, int ch, int stride, int flags, int up_fuse, int x3h, int off, int* err, long long* lds, int* grid, int* block,
+                     int* bm);
+/* test entry: Y [R, ldy] (= [2 R, ch / 2] time-major) = ConvTranspose1d(stride 2) of lrelu(((X0 + X1) + X2) * scale) on the fused kernel -
+ * X0 / X1 / X2 [R, ldx] f32 (ch channels), Wh / inv: the [ch][2 ch] matrix [wlo rows | whi rows] as fp16 planes (mt2_x3h_split) with its
+ * inverse row scales, bias [ch / 2], rows with valid[q] == 0 written as zeros; up_fuse: the option's mask (a clear bit answers
+ * hipErrorNotSupported as an error); range_flag as mt2_op_gemm_x3h. */
+int mt2_op_up_mrf(void* stream, const float* X0, const float* X1, const float* X2, int ldx, int R, int ch, float scale, float slope,
+                  const void* Wh, const float* inv, const float* bias, const int32_t* valid, float* Y, int ldy, int up_fuse,
+                  int32_t* range_flag);
 /* time `iters` back-to-back launches of one GEMM / conv (taps, dilation) with HIP events on `stream`, cycling
  * through `w_copies` copies of the weight matrix (> 1: weights are not L2-resident from the previous launch);
  * flags bit0: leaky-ReLU prologue, bit1: bias + residual + row-mask epilogue, bit2: clock probe - one wave of the

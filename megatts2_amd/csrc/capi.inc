@@ -323,6 +323,7 @@ static int* option_slot(mt2_model* m, const std::string& n) {
     if (n == "ln_pairs_maxm") return &m->opts.ln_pairs_maxm;
     if (n == "a_planes") return &m->opts.a_planes;
     if (n == "pair_fuse") return &m->opts.pair_fuse;
+    if (n == "up_fuse") return &m->opts.up_fuse;
     return nullptr;
 }
 static bool* option_flag(mt2_model* m, const std::string& n) {
@@ -1269,6 +1270,56 @@ int mt2_op_conv_pair(void* stream, const float* X, int ldx, int R, int C, int ta
     o.pair_fuse = pair_fuse;
     o.x3h_flag = range_flag;
     MT2_HIP(launch_conv_pair(p, (hipStream_t)stream, &o));
+    MT2_API_END
+}
+
+// What launch_up_mrf would do with a fused MRF mean + stride-`stride` upsampler of `ch` input channels over R rows, without making it
+// (up_mrf_route; no device needed).  Dense rows (ldx = ldy = ch), dummy pointers that are never dereferenced.  flags: 1 no fp16 planes,
+// 2 R is taken as the row count of an operand of 2 GiB (ldx = 2^31 / (4 R) rounded up), 4 the output sits 4 bytes off its alignment,
+// 8 the planes sit 16 bytes off theirs, 16 ldx = ch + 2 (no multiple of 4), 32 X1 is null, 64 ldy = ch - 4 (below the width),
+// 128 the bias sits 4 bytes off its alignment.  off: engine options switched away from their defaults - 1 win_conv off, 2 x6_conv off,
+// 4 a forced configuration, 8 ldr64.
+int mt2_up_mrf_route(int R, int ch, int stride, int flags, int up_fuse, int x3h, int off, int* err, long long* lds, int* grid, int* block,
+                     int* bm) {
+    alignas(128) static char dummy[8 * 128];
+    UpMrfP p{};
+    p.X0 = (const float*)dummy; p.X1 = (flags & 32) ? nullptr : (const float*)(dummy + 128); p.X2 = (const float*)(dummy + 256);
+    p.ldx = ch; p.R = R; p.ch = ch; p.stride = stride; p.scale = 1.0f / 3.0f; p.slope = 0.1f;
+    if (!(flags & 1)) { p.Wh = dummy + 384 + ((flags & 8) ? 16 : 0); p.inv = (const float*)(dummy + 512); }
+    p.bias = (const float*)(dummy + 640 + ((flags & 128) ? 4 : 0));
+    p.wh_ldb = 8ll * ch;
+    p.Y = (float*)(dummy + 768 + ((flags & 4) ? 4 : 0)); p.ldy = ch;
+    if ((flags & 2) && R > 0) p.ldx = (int)((((1ll << 31) / 4 + R - 1) / R + 3) & ~3ll);
+    if (flags & 16) p.ldx = ch + 2;
+    if (flags & 64) p.ldy = ch - 4;
+    EngineOpts o;
+    o.up_fuse = up_fuse;
+    o.x3h = x3h;
+    if (off & 1) o.win_conv = false;
+    if (off & 2) o.x6_conv = false;
+    if (off & 4) o.force_cfg = 0;
+    if (off & 8) o.ldr64 = true;
+    const UpMrfRoute r = up_mrf_route(p, o);
+    if (err) *err = (int)r.err;
+    if (lds) *lds = (long long)r.lds;
+    if (grid) *grid = (int)r.grid;
+    if (block) *block = (int)r.block;
+    if (bm) *bm = r.bm;
+    return 0;
+}
+// Kernel test of the fused MRF mean + upsampler: one launch_up_mrf with per-call EngineOpts (up_fuse: the mask)
+int mt2_op_up_mrf(void* stream, const float* X0, const float* X1, const float* X2, int ldx, int R, int ch, float scale, float slope,
+                  const void* Wh, const float* inv, const float* bias, const int32_t* valid, float* Y, int ldy, int up_fuse,
+                  int32_t* range_flag) {
+    MT2_API_BEGIN
+    UpMrfP p{};
+    p.X0 = X0; p.X1 = X1; p.X2 = X2; p.ldx = ldx; p.R = R; p.ch = ch; p.stride = 2; p.scale = scale; p.slope = slope;
+    p.Wh = Wh; p.inv = inv; p.bias = bias; p.wh_ldb = 8ll * ch;
+    p.valid = valid; p.Y = Y; p.ldy = ldy;
+    EngineOpts o;
+    o.up_fuse = up_fuse;
+    o.x3h_flag = range_flag;
+    MT2_HIP(launch_up_mrf(p, (hipStream_t)stream, &o));
     MT2_API_END
 }
 

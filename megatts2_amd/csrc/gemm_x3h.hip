@@ -1588,6 +1588,351 @@ hipError_t launch_conv_pair(const PairP& p_in, hipStream_t s, EngineOpts* opts) 
     return hipGetLastError();
 }
 
+// ===================================================================================================
+// The MRF MEAN of a vocoder stage and the stride-2 TRANSPOSED CONVOLUTION of the next one as ONE launch of the window kernel's pieces
+// (ch = 32 QS input channels, co = ch / 2 output channels, BN = 2 co = ch columns: [phase 0 | phase 1] of an output row pair):
+//   m[r, c] = lrelu(((x0[r, c] + x1[r, c]) + x2[r, c]) * scale)         avg3_kernel's operation order, rows outside [0, R): zeros
+//   Y[q, n] = valid[q] ? bias[n mod co] + sum_c m[q - 1 + h, c] Wcat[n, c] + sum_c m[q + h, c] Wcat[n, ch + c] : 0,   h = n >= co
+// i.e. a two-tap window convolution whose second column half reads one row further down.  The x0 window (BM + 2 rows from q0 - 1) comes
+// into LDS by DMA as in conv_win_x3h_kernel; the in-place planes pass ALSO takes each task's 32 bytes of x1 and x2 from global memory
+// (requested before the first barrier), forms the mean, applies the leaky ReLU and splits - the mean never exists in memory, and the
+// three inputs are read once where avg3 + two GEMM halves read 3 + 1 + 1 tensors and wrote one more.  K loop: the window kernel's
+// cross-chunk fragment pipeline over the 2 QS chunks of Wcat (chunk = (tap, 32-channel slice)).  WGN = 2 (128 channels): the wave's
+// column half IS the phase, its A rows sit `wn` lower; WGN = 1 (64 channels): the wave's two 32-column tiles are the two phases, each
+// with its own A fragments (NPH = 2).  Epilogue: the 16-byte-store one (row mask; the bias is added in registers, its index wraps at co).
+template <int QS, int BM, int BN, int WGM, int WGN, int NST, int NL>
+__global__ __launch_bounds__((WGM * WGN + NL) * 64) void up_mrf_x3h_kernel(UpMrfP p) {
+    constexpr int NW = WGM * WGN;
+    constexpr int WTM = BM / WGM, WTN = BN / WGN;
+    constexpr int TM = WTM / 32, TN = WTN / 32;
+    constexpr int NPH = WGN == 2 ? 1 : 2;                 // phases among one wave's column tiles
+    constexpr int CO = BN / 2;
+    constexpr int BPIECES = BN / 8;
+    constexpr int NI = NL;
+    constexpr int B_IT = (BPIECES + NI - 1) / NI;
+    constexpr int STAGE_B = B_IT * NI * 1024;
+    constexpr int NT = (NW + NL) * 64;
+    constexpr int WR = BM + 2, WRp = (WR + 7) & ~7;
+    constexpr int NTASK = QS * WRp * 4, MAXT = (NTASK + NT - 1) / NT;   // (row block, j): f32 slots 2 j, 2 j + 1 -> hi slot j, lo slot 4 + j
+    constexpr int NK = 2 * QS;                            // chunks: tap t = c / QS, slice c % QS
+    static_assert(NL > 0 && WTM % 32 == 0 && WTN % 32 == 0 && NST >= 3 && (NST - 2) * B_IT < 64 && BN == 32 * QS, "config");
+    static_assert((WGN == 2 && WTN == CO) || (WGN == 1 && TN == 2), "a wave's columns are one phase, or one 32-column tile per phase");
+    static_assert(NK >= NST - 1 && QS >= 2, "the ring's first stages are whole chunks of this launch");
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool loader = wave_all >= NW;
+    const int wave = loader ? wave_all - NW : wave_all;
+    const int wm = wave / WGN, wn = wave % WGN;
+    char* ring = reinterpret_cast<char*>(smem);
+    float* win = smem + NST * STAGE_B / 4;                          // [QS][WRp][32] f32 / planes, slot-swizzled rows
+
+    const int ntm = (p.R + BM - 1) / BM;
+    const int bid = blockIdx.x;
+    const int xcd = bid & 7, qq = ntm >> 3, rr = ntm & 7;
+    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int m0 = tile * BM;                                       // first output row pair
+    const int row_first = m0 - 1;                                   // global row of the window's row 0
+    const int ldx = p.ldx, Rx = p.R;
+
+    {   // ---- the f32 window of x0, once
+        const float* __restrict__ X = p.X0;
+        const long long zoff_x = (const float*)g_zero16 - X;
+        const int lrow = lane >> 3;
+        constexpr int ppq = WRp >> 3, pieces = QS * ppq;
+        for (int pc = wave_all; pc < pieces; pc += NW + NL) {
+            const int q = pc / ppq, r8 = pc - q * ppq;
+            const int row = r8 * 8 + lrow;
+            const int grow = row_first + row;
+            const int slot = (lane & 7) ^ ((row >> 1) & 7);
+            const bool ok = (row < WR) & ((unsigned)grow < (unsigned)Rx);
+            const long long off = ok ? (long long)grow * ldx + q * 32 + slot * 4 : zoff_x;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(X + off),
+                                             (__attribute__((address_space(3))) void*)(win + (q * WRp + r8 * 8) * 32), 16, 0, 0);
+        }
+    }
+    // ---- this thread's pieces of x1 and x2: the 8 channels of each of its tasks, in flight across the barrier below
+    f32x4 xb[MAXT][2], xc[MAXT][2];
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) {
+        const int t = tid + u * NT;
+        const int tt = t < NTASK ? t : 0;
+        const int rbk = tt >> 2, j = tt & 3;
+        const int q = rbk / WRp, row = rbk - q * WRp;
+        const int grow = row_first + row;
+        const bool ok = (t < NTASK) & (row < WR) & ((unsigned)grow < (unsigned)Rx);
+        const long long off = (long long)grow * ldx + q * 32 + j * 8;
+        const float* s1 = ok ? p.X1 + off : (const float*)g_zero16;
+        const float* s2 = ok ? p.X2 + off : (const float*)g_zero16;
+        const int o2 = ok ? 4 : 0;
+        xb[u][0] = *reinterpret_cast<const f32x4*>(s1); xb[u][1] = *reinterpret_cast<const f32x4*>(s1 + o2);
+        xc[u][0] = *reinterpret_cast<const f32x4*>(s2); xc[u][1] = *reinterpret_cast<const f32x4*>(s2 + o2);
+    }
+    // ---- weight chunks through the ring (conv_win_x3h_kernel's pieces).  Buffer loads only: up_mrf_route keeps operands of 2 GiB or
+    // more on the three-launch form
+    constexpr unsigned kOut = 0x80000000u;
+    unsigned vob[B_IT];
+#pragma unroll
+    for (int j = 0; j < B_IT; ++j) {
+        const int pc = j * NI + wave;
+        const int n = pc * 8 + (lane >> 3);
+        const int sl = (lane & 7) ^ ((n >> 1) & 7);
+        vob[j] = (pc < BPIECES && n < BN) ? (unsigned)(n * (int)p.wh_ldb + sl * 16) : kOut;
+    }
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.Wh)), 0, (int)kOut, 0x00020000);
+    auto issue = [&](int c, int st) __attribute__((always_inline)) {
+        char* Bs = ring + st * STAGE_B + wave * 1024;
+#pragma unroll
+        for (int j = 0; j < B_IT; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(Bs + j * NI * 1024), 16, (int)vob[j], c * 128, 0, 0);
+    };
+    if (loader) {
+        loader_priority(p.ldr_prio);
+#pragma unroll
+        for (int st = 0; st < NST - 1; ++st) issue(st, st);
+        wait_vmcnt<(NST - 1) * B_IT>();                   // the window pieces and x1 / x2 (older than the ring's) have landed
+    } else {
+        wait_vmcnt<0>();                                  // this compute wave's window pieces
+    }
+    // ---- window -> fp16 planes of lrelu(mean) in place: read everything, barrier, write (conv_win_x3h_kernel's pass)
+    float amax = 0.0f;
+    {
+        const unsigned lds_w = (unsigned)(unsigned long long)(__attribute__((address_space(3))) float*)win;
+        f32x4 in[MAXT][2];
+        __builtin_amdgcn_s_barrier();                     // every wave's window pieces have landed
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int u = 0; u < MAXT; ++u) {
+            const int t = tid + u * NT;
+            const int tt = t < NTASK ? t : 0;
+            const int rbk = tt >> 2, j = tt & 3;
+            const int swz = ((rbk % WRp) >> 1) & 7;
+            const unsigned base = lds_w + (unsigned)rbk * 128;
+            in[u][0] = lds_read_b128(base + (unsigned)(((2 * j) ^ swz) * 16));
+            in[u][1] = lds_read_b128(base + (unsigned)(((2 * j + 1) ^ swz) * 16));
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int u = 0; u < MAXT; ++u) asm volatile("" : "+v"(in[u][0]), "+v"(in[u][1]));
+        __builtin_amdgcn_s_barrier();                     // everything has been read
+        asm volatile("" ::: "memory");
+        const float scale = p.scale, slope = p.slope;
+#pragma unroll
+        for (int u = 0; u < MAXT; ++u) {
+            const int t = tid + u * NT;
+            if (t < NTASK) {
+                const int rbk = t >> 2, j = t & 3;
+                const int swz = ((rbk % WRp) >> 1) & 7;
+                f32x4 mv[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) mv[h][e] = ((in[u][h][e] + xb[u][h][e]) + xc[u][h][e]) * scale;
+                u32x4 ph, pl;
+                split2_f16<ACT_LRELU>(mv[0], mv[1], slope, ph, pl, amax);
+                char* dst = reinterpret_cast<char*>(win) + (size_t)rbk * 128;
+                *reinterpret_cast<u32x4*>(dst + ((j ^ swz) * 16)) = ph;
+                *reinterpret_cast<u32x4*>(dst + (((4 + j) ^ swz) * 16)) = pl;
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the planes are in LDS before this wave's next barrier
+    }
+    if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+    if (loader) {
+        // cross-chunk form: at barrier c the weights of chunk c-1 are still being read - the free stage is chunk c-2's
+        for (int c = 0; c < NK; ++c) {
+            if (c == 0) { if (NST - 2 < NK) wait_vmcnt<(NST - 2) * B_IT>(); else wait_vmcnt<0>(); }
+            else if (c + NST - 3 < NK) wait_vmcnt<(NST - 3) * B_IT>();
+            else wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+            if (c >= 1 && c + NST - 2 < NK) issue(c + NST - 2, (c + NST - 2) % NST);
+        }
+        return;
+    }
+    // ---- compute waves: inverse row scale and bias of the lane's columns (the bias index wraps at co: both phases share it)
+    float inv_s[TN], bs[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = wn * WTN + j * 32 + (lane & 31);
+        inv_s[j] = p.inv[n];
+        bs[j] = p.bias ? p.bias[n & (CO - 1)] : 0.0f;
+    }
+    f32x16 acc[TM][TN], acl[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.0f; acl[i][j][e] = 0.0f; }
+
+    const int half = lane >> 5;
+    const unsigned lds_ring = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)ring;
+    const unsigned lds_win = (unsigned)(unsigned long long)(__attribute__((address_space(3))) float*)win;
+    const int nrow = wn * WTN + (lane & 31);
+    const unsigned b_lane = lds_ring + nrow * 128;
+    const int swzb = (nrow >> 1) & 7;
+    unsigned koffb[2][2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        koffb[b][0] = (unsigned)(((b * 2 + half) ^ swzb) * 16);
+        koffb[b][1] = (unsigned)(((4 + b * 2 + half) ^ swzb) * 16);
+    }
+    // window row of the lane's output row for tap 0 of the wave's first phase (window row 0 = global row m0 - 1)
+    const int arow0 = wm * WTM + (lane & 31) + (NPH == 1 ? wn : 0);
+    // conv_win_x3h_kernel's cross-chunk fragment pipeline (see there); with NPH = 2 a k block carries one A set per phase
+    constexpr int N1 = 2 * NPH * TM + 2 * TN;
+    static_assert(N1 <= 15, "lgkmcnt is four bits wide");
+    u32x4 ra[2][NPH][TM][2];
+    u32x4 rb[2][2][TN];
+    auto fetch_a = [&](int b, int q, int arow) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ph = 0; ph < NPH; ++ph) {
+            const int row = arow + ph;
+            const int swza = (row >> 1) & 7;
+            const unsigned sa = lds_win + (unsigned)((q * WRp + row) * BK) * 4;
+            const unsigned vh = sa + (unsigned)(((b * 2 + half) ^ swza) * 16), vl = sa + (unsigned)(((4 + b * 2 + half) ^ swza) * 16);
+            static_for(std::make_integer_sequence<int, TM>{}, [&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                ra[b][ph][i][0] = __builtin_bit_cast(u32x4, lds_read_b128_imm<i * 32 * BK * 4>(vh));
+                ra[b][ph][i][1] = __builtin_bit_cast(u32x4, lds_read_b128_imm<i * 32 * BK * 4>(vl));
+            });
+        }
+    };
+    auto fetch_b = [&](int b, unsigned sb) __attribute__((always_inline)) {
+        const unsigned vb0 = sb + koffb[b][0], vb1 = sb + koffb[b][1];
+        static_for(std::make_integer_sequence<int, TN>{}, [&](auto ic) {
+            constexpr int j = decltype(ic)::value;
+            rb[b][0][j] = __builtin_bit_cast(u32x4, lds_read_b128_imm<j * 32 * 128>(vb0));
+            rb[b][1][j] = __builtin_bit_cast(u32x4, lds_read_b128_imm<j * 32 * 128>(vb1));
+        });
+    };
+    auto tie_set = [&](int b) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ph = 0; ph < NPH; ++ph)
+#pragma unroll
+            for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(ra[b][ph][i][0]), "+v"(ra[b][ph][i][1]));
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(rb[b][pl][j]));
+    };
+    // cross terms first (into the low accumulators), column tiles innermost; column tile j takes the A set of its phase
+    auto products = [&](int b) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acl[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ra[b][NPH == 1 ? 0 : j][i][0]),
+                                                                   __builtin_bit_cast(f16x8, rb[b][1][j]), acl[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ra[b][NPH == 1 ? 0 : j][i][0]),
+                                                                   __builtin_bit_cast(f16x8, rb[b][0][j]), acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acl[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ra[b][NPH == 1 ? 0 : j][i][1]),
+                                                                   __builtin_bit_cast(f16x8, rb[b][0][j]), acl[i][j], 0, 0, 0);
+        }
+    };
+    __builtin_amdgcn_s_barrier();                         // the window's planes are written and the weights of chunk 0 have landed
+    asm volatile("" ::: "memory");
+    fetch_a(0, 0, arow0); fetch_b(0, b_lane); fetch_a(1, 0, arow0); fetch_b(1, b_lane);
+    __builtin_amdgcn_sched_barrier(0);
+    int stn = 1 % NST, tapn = 0, qn = 1;                  // chunk c + 1: its ring stage, tap and 32-channel slice (QS >= 2)
+    auto chunk = [&](auto last_c) __attribute__((always_inline)) {
+        constexpr bool last = decltype(last_c)::value;
+        const int arow = arow0 + tapn;
+        const unsigned sb = b_lane + (unsigned)stn * STAGE_B;
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            if (last && b == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(N1) : "memory");
+            tie_set(b);
+            __builtin_amdgcn_sched_barrier(0);
+            products(b);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!last) {
+                if (b == 0) {
+                    __builtin_amdgcn_s_barrier();         // the weights of chunk c + 1 have landed
+                    asm volatile("" ::: "memory");
+                }
+                fetch_a(b, qn, arow);                     // A(q + 2), B(q + 2)
+                fetch_b(b, sb);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        stn = stn + 1 == NST ? 0 : stn + 1;
+        if (++qn == QS) { qn = 0; ++tapn; }
+    };
+    for (int c = 0; c + 1 < NK; ++c) chunk(std::false_type{});
+    chunk(std::true_type{});
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                float v = __builtin_fmaf(acl[i][j][e], kX3hLoInv, acc[i][j][e]) * inv_s[j];
+                asm volatile("" : "+v"(v));               // the product is rounded on its own, as in front of the window kernel's epilogue
+                acc[i][j][e] = v + bs[j];
+            }
+    GemmP e{};
+    e.valid = p.valid; e.C = p.Y; e.ldc = p.ldy; e.M = p.R; e.N = BN; e.epi_act = ACT_NONE; e.out_scale = 1.0f;
+    epilogue_t4<TM, TN>(e, acc, 0, m0 + wm * WTM, wn * WTN, lane);      // up_mrf_route: Y on 16 bytes, ldy a multiple of 4
+}
+
+// host side of the fused mean + upsampler: the two tiles (the geometry of the window tiles 99 / 100), the route and the launch
+typedef void (*UpMrfKernel)(UpMrfP);
+struct UpMrfTile { int ch, bm, threads; size_t ring; UpMrfKernel fn; };
+#define MT2_UPMRF_TILE(QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                                   \
+    { BN_, BM_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * (((2 * BN_ / 16 + NL_ - 1) / NL_) * NL_ * 1024),                        \
+      up_mrf_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, NL_> }
+static const UpMrfTile kUpMrfTiles[2] = { MT2_UPMRF_TILE(2, 256, 64, 8, 1, 4, 4), MT2_UPMRF_TILE(4, 128, 128, 4, 2, 3, 4) };
+
+UpMrfRoute up_mrf_route(const UpMrfP& p, const EngineOpts& o) {
+    UpMrfRoute r{hipSuccess, -1, 0, 0, 0, 0};
+    const auto fail = [&r](hipError_t e) { r.err = e; r.tile = -1; r.lds = 0; r.grid = r.block = 0; r.bm = 0; return r; };
+    if (p.R <= 0) return r;                                          // nothing to launch
+    // the three-launch form (avg3 + the two GEMM halves) keeps everything this kernel was not built for
+    const int t = p.ch == 64 ? 0 : (p.ch == 128 ? 1 : -1);
+    if (t < 0 || p.stride != 2 || !((o.up_fuse >> t) & 1)) return fail(hipErrorNotSupported);
+    if (!o.win_conv || !o.x6_conv || !(o.x3h & 4) || o.force_cfg >= 0 || o.ldr64) return fail(hipErrorNotSupported);
+    if (!p.Wh || !p.inv) return fail(hipErrorNotSupported);          // missing planes
+    const long long two_g = 1ll << 31;
+    if ((long long)p.R * p.ldx * 4 >= two_g || (long long)p.R * p.ldy * 4 >= two_g || (long long)p.ch * p.wh_ldb >= two_g - 1)
+        return fail(hipErrorNotSupported);
+    if (!p.X0 || !p.X1 || !p.X2 || !p.Y || p.ldx < p.ch || p.ldy < p.ch || p.wh_ldb < 8ll * p.ch) return fail(hipErrorInvalidValue);
+    if (((p.ldx | p.ldy) & 3) || (p.wh_ldb & 127) || ((unsigned long long)p.Wh & 127) ||
+        (((unsigned long long)p.X0 | (unsigned long long)p.X1 | (unsigned long long)p.X2 | (unsigned long long)p.Y | (unsigned long long)p.bias) & 15))
+        return fail(hipErrorNotSupported);
+    const UpMrfTile& c = kUpMrfTiles[t];
+    r.tile = t;
+    r.bm = c.bm;
+    r.lds = c.ring + (size_t)(p.ch / 32) * ((c.bm + 2 + 7) & ~7) * BK * sizeof(float);
+    r.grid = (unsigned)((p.R + c.bm - 1) / c.bm);
+    r.block = (unsigned)c.threads;
+    return r;
+}
+
+static std::atomic<unsigned long long> g_upmrf_attr_done[2];
+
+hipError_t launch_up_mrf(const UpMrfP& p_in, hipStream_t s, EngineOpts* opts) {
+    static const EngineOpts kDefaults;
+    const EngineOpts& o = opts ? *opts : kDefaults;
+    const UpMrfRoute r = up_mrf_route(p_in, o);
+    if (r.err != hipSuccess || r.grid == 0) return r.err;
+    const UpMrfTile& c = kUpMrfTiles[r.tile];
+    UpMrfP p = p_in;
+    p.x3h_flag = o.x3h_flag;
+    p.ldr_prio = o.ldr_prio;
+    const hipError_t e = dyn_lds_once(g_upmrf_attr_done[r.tile], reinterpret_cast<const void*>(c.fn), r.lds);
+    if (e != hipSuccess) return e;
+    if (opts) opts->last_cfg = "x3hupmrf";
+    hipLaunchKernelGGL(c.fn, dim3(r.grid), dim3(r.block), r.lds, s, p);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------
 // host side: the table rows of this unit's tiles (gemm_tiles.h; gemm_dispatch.hip places them and routes launches)
 

@@ -454,6 +454,11 @@ void finalize_model(mt2_model& m) {
             UpW u;
             u.cin = ch; u.cout = co; u.stride = s;
             u.wlo = L.upload(lo, (size_t)2 * ch); u.whi = L.upload(hi, (size_t)2 * ch); u.bias = L.upload(bias);
+            if (s == 2) {       // both phases as ONE matrix: the fused MRF mean + upsampler launch (up_mrf_x3h_kernel) reads it through its planes
+                std::vector<float> cat(lo);
+                cat.insert(cat.end(), hi.begin(), hi.end());
+                u.wcat = L.upload(cat, (size_t)2 * ch);
+            }
             m.hg_up.push_back(u);
             for (int j = 0; j < c.hg_n_res; ++j) {
                 ResW r;

@@ -265,6 +265,24 @@ static bool conv_pair(const Ctx& c, const float* x, int C, int R, const ConvW& w
     return true;
 }
 
+// lrelu(mean of the three resblock outputs) -> ConvTranspose1d(stride 2) of the next vocoder stage as one launch of the fused kernel;
+// false: up_mrf_route keeps launch_avg3 + the two GEMM halves for this boundary (nothing was launched)
+static bool up_mrf(const Ctx& c, const float* const* rb, int ch, int R, const UpW& u, float slope, float* up, const int* valid) {
+    if (!u.wcat || u.cin != ch || u.cout * 2 != ch) return false;
+    GemmP g{};
+    g.W = u.wcat; g.taps = 2; g.Cin = ch; g.groups = 1;
+    attach_planes(c.m, g);
+    UpMrfP p{};
+    p.X0 = rb[0]; p.X1 = rb[1]; p.X2 = rb[2]; p.ldx = ch; p.R = R; p.ch = ch; p.stride = u.stride;
+    p.scale = 1.0f / 3.0f; p.slope = slope;
+    p.Wh = g.Wh; p.inv = g.wh_inv; p.bias = u.bias; p.wh_ldb = g.wh_ldb ? g.wh_ldb : 8ll * ch;
+    p.valid = valid; p.Y = up; p.ldy = 2 * u.cout;
+    const hipError_t e = launch_up_mrf(p, c.s, &c.m.opts);
+    if (e == hipErrorNotSupported) return false;
+    MT2_HIP(e);
+    return true;
+}
+
 static void layernorm(const Ctx& c, const float* x, int ldx, const float* g, const float* b, int M, int C,
                       float* out, int ldo, const int* valid = nullptr, int valid_rows = 0,
                       const float* R1 = nullptr, int ldr1 = 0, int r1_rows = 0, int rows_per_group = 0,
@@ -1394,13 +1412,26 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
     }
     conv_same(c, xmel, cfg.hg_in_dim, (int)R, m.hg_pre, x, ch, M0.d_valid);
     const int* valid = M0.d_valid;
+    const float* const* mrf = nullptr;        // the previous stage's three resblock outputs while their mean has not been formed yet
+    float* rb[3] = {nullptr, nullptr, nullptr};
     for (int i = 0; i < cfg.hg_n_up; ++i) {
         const UpW& u = m.hg_up[i];
         const int s = u.stride, co = u.cout, hs = s / 2;
         MT2_REQUIRE(R * s < (1ll << 31), "waveform row count exceeds int32");
         // ConvTranspose1d as two phase GEMMs over the input rows; output [R, s*co] IS [R*s, co] time-major
         float* up = c.ws.get<float>((size_t)R * s * co);
-        for (int half = 0; half < 2; ++half) {
+        // ... or, where the input is the MRF mean of the previous stage and has no other consumer, mean -> leaky ReLU -> both phases as
+        // ONE launch (up_mrf_route; option up_fuse): the mean never exists in memory.  NotSupported keeps the three launches below
+        bool fused = false;
+        if (mrf) {
+            fused = m.opts.up_fuse && up_mrf(c, mrf, ch, (int)R, u, slope, up, valid);
+            if (!fused) {
+                x = c.ws.get<float>((size_t)R * ch);
+                MT2_HIP(launch_avg3(mrf[0], mrf[1], mrf[2], 1.0f / 3.0f, x, R * ch, c.s));
+            }
+            mrf = nullptr;
+        }
+        for (int half = 0; half < 2 && !fused; ++half) {
             GemmP p{};
             p.X = x; p.ldx = ch; p.Rx = (int)R; p.taps = 2; p.shift0 = half == 0 ? -1 : 0; p.Cin = ch;
             p.W = half == 0 ? u.wlo : u.whi; p.bias = u.bias; p.valid = valid;
@@ -1418,7 +1449,6 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
         // The three resblocks of a stage only share their input: each runs on its own stream (the caller's + two
         // side streams), so that one chain's launch tails (868 tiles on 256 CUs at stage 1) are filled by the others.
         const size_t per = (size_t)R * ch;
-        float* rb[3] = {nullptr, nullptr, nullptr};
         MT2_REQUIRE(cfg.hg_n_res == 3, "HiFi-GAN V1 uses three resblocks per stage");
         const int nside = m.opts.voc_streams > 1 ? 2 : 0;
         ensure_aux(m, nside);
@@ -1469,6 +1499,10 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
                                                   m.hg_post.b, 0.01f, valid, wav, c.s);
             if (e == hipSuccess) return wav;
             if (e != hipErrorNotSupported) MT2_HIP(e);      // not supported (LDS): the two-launch form below
+        }
+        if (i + 1 < cfg.hg_n_up) {     // the next stage's upsampler is the mean's only consumer: it may form it itself
+            mrf = rb;
+            continue;
         }
         x = c.ws.get<float>(per);
         MT2_HIP(launch_avg3(rb[0], rb[1], rb[2], 1.0f / 3.0f, x, (long long)per, c.s));

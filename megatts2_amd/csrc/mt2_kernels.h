@@ -113,6 +113,8 @@ struct EngineOpts {
                                  // profiles/r06_opts_ab_block6_attention_x3h.txt); 0: everything stays x6
     int pair_fuse = 3;           // the vocoder's resblock conv pairs as ONE launch (PairP, conv_pair_x3h_kernel): bit 0 the 32-channel stage,
                                  // bit 1 the 64-channel stage, bit 2 the 128-channel stage (profiles/conv_pair_fusion_ab.txt)
+    int up_fuse = 3;             // the vocoder's MRF mean + the next stage's stride-2 upsampler as ONE launch (UpMrfP, up_mrf_x3h_kernel): bit 0 the
+                                 // 64-channel boundary (64 -> 32), bit 1 the 128-channel one (128 -> 64) (profiles/up_mrf_fusion_ab.txt)
     int* x3h_flag = nullptr;     // device word of the range guard (GemmP::x3h_flag); the model handle owns one
     int t_x3h_128 = 72;          // x3h: from this many 128x128 tiles on the loader tile instead of the K-split tiles (t_x6_128's role)
     int t_x6_256 = 160, t_x6_128 = 72;   // ... from this many 256x128 / 128x128 tiles on (profiles/r02_gemm_sweep_x6.txt)
@@ -189,6 +191,32 @@ struct PairP {
 struct PairRoute { hipError_t err; int tile; size_t lds; unsigned grid, block; int bm, bmo; };
 PairRoute conv_pair_route(const PairP& p, const EngineOpts& o);
 hipError_t launch_conv_pair(const PairP& p, hipStream_t s, EngineOpts* o = nullptr);
+// The MRF mean of a vocoder stage and the stride-2 ConvTranspose1d of the next stage as ONE launch (up_mrf_x3h_kernel, gemm_x3h.hip), with
+// co = ch / 2, h(n) = (n >= co), rows outside [0, R) reading as zeros:
+//   m[r, c] = lrelu(((X0[r, c] + X1[r, c]) + X2[r, c]) * scale; slope)                      (avg3_kernel's operation order)
+//   Y[q, n] = valid[q] ? bias[n mod co] + sum_c m[q - 1 + h, c] Wcat[n, c] + sum_c m[q + h, c] Wcat[n, ch + c] : 0
+// Y is [R, 2 co] = [2 R, co] time-major.  Wcat [2 co][2 ch] (rows 0 .. co - 1: UpW::wlo, rows co ..: UpW::whi) comes as the fp16 planes
+// of GemmP::Wh with its inverse row scales; products in the x3h form.  Replaces launch_avg3 + the two GEMM halves of the upsampler.
+struct UpMrfP {
+    const float* X0; const float* X1; const float* X2; int ldx;     // the three resblock outputs [R, ch], one row stride
+    int R, ch, stride;
+    float scale, slope;
+    const void* Wh; const float* inv; const float* bias; long long wh_ldb;
+    const int* valid;
+    float* Y; int ldy;
+    int* x3h_flag = nullptr;    // set by launch_up_mrf from EngineOpts::x3h_flag
+    int ldr_prio = 0;           // ... from EngineOpts::ldr_prio
+};
+// up_mrf_route decides, without a HIP call, what launch_up_mrf does (the conv_pair_route pattern).  err: hipSuccess - it launches (or
+// R <= 0: nothing to launch, grid 0); hipErrorNotSupported - the caller keeps the three launches: ch not in {64, 128} or its bit of
+// EngineOpts::up_fuse clear, stride != 2, missing planes, engine options under which the window kernels do not run in the x3h form
+// (win_conv / x6_conv / x3h bit 2 off, a forced configuration, ldr64), an operand of 2 GiB or more, an operand off its alignment (X0 /
+// X1 / X2 / Y / bias on 16 bytes, planes and wh_ldb on 128, ldx / ldy multiples of 4); hipErrorInvalidValue - X0 / X1 / X2 / Y null, ldx /
+// ldy < ch, wh_ldb < 8 ch.  tile: 0 / 1 = 64 / 128 channels; bm rows (output row pairs) per workgroup, grid = ceil(R / bm), lds = ring +
+// (ch / 32) * ceil8(bm + 2) * 128 bytes.
+struct UpMrfRoute { hipError_t err; int tile; size_t lds; unsigned grid, block; int bm; };
+UpMrfRoute up_mrf_route(const UpMrfP& p, const EngineOpts& o);
+hipError_t launch_up_mrf(const UpMrfP& p, hipStream_t s, EngineOpts* o = nullptr);
 // would launch_gemm run this launch (planes attached, no prologue) on an x3h tile that takes its A operand as fp16 planes (a_planes)?
 bool gemm_takes_planes(const GemmP& p, const EngineOpts& o);
 // would launch_gemm run this launch on an x3h loader tile whose epilogue can store C as fp16 planes (GemmP::c_planes)?

@@ -114,7 +114,8 @@ struct EncW {
     int d = 0, ff = 0, heads = 0;
     bool conv_ff = false;
 };
-struct UpW { float *wlo, *whi, *bias; int cin, cout, stride; };
+struct UpW { float *wlo, *whi, *bias; int cin, cout, stride;
+             float* wcat = nullptr; };   // stride 2: [wlo rows | whi rows] as one [2 cout][2 cin] matrix with planes (UpMrfP)
 struct ResW { ConvW c1[3], c2[3]; int k; int dil[3]; };
 
 struct StageTimer {

@@ -1108,6 +1108,34 @@ def op_conv_pair_route(R, Cn, taps, dil, flags=0, pair_fuse=7, x3h=15):
     return {"err": err.value, "lds": lds.value, "grid": grid.value, "block": block.value, "bm": bm.value, "bmo": bmo.value}
 
 
+def op_up_mrf(X0, X1, X2, Wcat, bias, slope, scale=1.0 / 3.0, valid=None, channels=None, out=None, up_fuse=3, want_flag=False):
+    """mt2_op_up_mrf: out [R, ldy >= ch] = stride-2 transposed convolution of lrelu(((X0 + X1) + X2) * scale) on the fused kernel.  X0 / X1 /
+    X2 [R, ldx] f32 of which the first `channels` columns are the ch channels (all when None), Wcat [ch, 2 ch] f32 = [wlo rows | whi rows]
+    (split into fp16 planes here), bias [ch / 2], rows with valid == 0 written as zeros.  want_flag -> (out, range flag)."""
+    import torch
+    lib = load_library()
+    ch = channels or X0.shape[1]
+    R = X0.shape[0]
+    assert X1.shape == X0.shape and X2.shape == X0.shape
+    ph, inv = (t.to(X0.device) for t in split_f16x2_rows(Wcat))
+    if out is None:
+        out = torch.empty(R, ch, device=X0.device, dtype=torch.float32)
+    flag = torch.zeros(4, device=X0.device, dtype=torch.int32)
+    _check(lib.mt2_op_up_mrf(_stream(), _ptr(X0), _ptr(X1), _ptr(X2), X0.shape[1], R, ch, C.c_float(scale), C.c_float(slope), _ptr(ph),
+                             _ptr(inv), _ptr(bias), _ptr(valid), _ptr(out), out.shape[1], up_fuse, _ptr(flag)))
+    return (out, int(flag[0].item())) if want_flag else out
+
+
+def op_up_mrf_route(R, ch, stride=2, flags=0, up_fuse=3, x3h=15, off=0):
+    """mt2_up_mrf_route (no device needed) -> dict(err, lds, grid, block, bm) of the launch launch_up_mrf would make.  flags: 1 no fp16
+    planes, 2 an operand of 2 GiB, 4 output off 16 bytes, 8 planes off 128 bytes, 16 ldx no multiple of 4, 32 a null input, 64 ldy below the
+    width, 128 bias off 16 bytes; off: 1 win_conv off, 2 x6_conv off, 4 forced configuration, 8 ldr64."""
+    err, lds, grid, block, bm = C.c_int(0), C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    load_library().mt2_up_mrf_route(R, ch, stride, flags, up_fuse, x3h, off, C.byref(err), C.byref(lds), C.byref(grid), C.byref(block),
+                                    C.byref(bm))
+    return {"err": err.value, "lds": lds.value, "grid": grid.value, "block": block.value, "bm": bm.value}
+
+
 def op_gemm_x6_ln(X, W, bias=None, R=None, M=None, a_mul=1, shift0=0, epi_act=ACT_NONE, force_cfg=-1, want_stats=False,
                   ln=None, eps=1e-5, x3h=False):
     """mt2_op_gemm_x6_ln: one linear launch on an x6 tile.  want_stats -> also returns (pairs [M, nt, 2], pair width) written by

@@ -29,7 +29,9 @@ def main() -> None:
                     help="hifigan: the hub model's generator, when a local copy is found; griffin-lim: no weights needed (buzzy: a fallback)")
     ap.add_argument("--gl-iters", type=int, default=32, help="Griffin-Lim iterations")
     ap.add_argument("--report-pitch", action="store_true",
-                    help="print the pitch moments (YIN on the GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
+                    help="print the pitch moments (F0 tracked on the GPU, see --pitch-tracker) of the first prompt and, when a vocoder produced audio, of the generated audio")
+    ap.add_argument("--pitch-tracker", choices=("yin", "viterbi"), default="yin",
+                    help="--report-pitch by plain YIN, or by the Viterbi pass over its lag costs (robust to octave errors)")
     ap.add_argument("--text")
     ap.add_argument("--phones", help="comma separated phone token ids (bypasses the G2P)")
     ap.add_argument("--out", default="test.wav")
@@ -57,7 +59,7 @@ def main() -> None:
         report = [("prompt", sorted(glob.glob(f"{a.wavs_dir}/*.wav"))[0], a.trim_db)] + ([("generated", a.out, None)] if wrote else [])
         for what, path, trim_db in report:
             y, sr = audio_io.read_wav(path)
-            st = M.pitch_stats(M.extract_f0(y, sr, trim_db=trim_db))
+            st = M.pitch_stats(M.extract_f0(y, sr, trim_db=trim_db, method=a.pitch_tracker))
             print(f"pitch of the {what} ({path}): " + ", ".join(f"{k} {float(v[0]):.4g}" for k, v in st.items()))
 
 

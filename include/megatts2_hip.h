@@ -426,6 +426,40 @@ int mt2_f0_query(int sample_rate, int hop, float fmin, float fmax, long long L, 
 int mt2_f0_yin(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
                int sample_rate, int hop, float fmin, float fmax, float threshold, float* f0 /*[B, T_max]*/, float* cmnd /*or NULL*/,
                int32_t* lag /*or NULL*/, int T_max, float* diff /*or NULL*/);
+/* ---- A second tracker beside YIN, off by default: a Viterbi pass over YIN's lag costs (csrc/f0.hip), the usual cure (pYIN, RAPT)
+ * for YIN's octave errors - where the even harmonics dominate, d'[tau0 / 2] already dips under the threshold and "the first dip"
+ * answers an octave high.  One lag per frame is chosen by the frame's whole d' curve plus a cost for jumping between frames.  The
+ * rule is our own; parity with librosa.pyin is unpinned, as for YIN.  Per utterance: the frames, d, c and d' are exactly those above
+ * (the same device code), tau_min and tau_max too.  n = tau_max - tau_min + 1 (at most 255) states, state k the lag tau_min + k.
+ * Every operation is one f32 operation rounded on its own, no fma:
+ *   lg[k]    = (float) log2((double)(tau_min + k))   (built in double on the host, rounded once)
+ *   bias[k]  = octave_cost * (lg[k] - lg[0])
+ *   o[t, k]  = q + bias[k],  q = d'[t, tau_min + k] if that is finite, else 1: every cost is finite by construction
+ *   tr(j, k) = jump_cost * |lg[k] - lg[j]|: the jump in octaves times a weight, over all n x n pairs, no band
+ *   delta[0, k] = o[0, k];  for t >= 1:  best = min_j (delta[t - 1, j] + tr(j, k)), j ascending with a strict <, so the smallest j
+ *   wins a tie;  psi[t, k] = that j;  delta'[k] = o[t, k] + best;  m = min_k delta'[k];  delta[t, k] = delta'[k] - m (the per-frame
+ *   renormalisation keeps f32 resolution on long clips)
+ *   k*[T - 1] = the smallest k attaining min delta[T - 1, .];  k*[t - 1] = psi[t, k*[t]];  T = 1: the arg-min alone
+ *   tau* = tau_min + k*[t];  cmnd = d'[t, tau*];  the frame is voiced iff cmnd < threshold - YIN's own criterion at the tracked lag:
+ *   there is no unvoiced state and octave_cost never enters the voicing decision;  f0 by the parabola above, 0 when unvoiced
+ * octave_cost (default 0.02) and jump_cost (default 0.5) must be finite and >= 0; jump_cost = 0 makes the frames independent.
+ * Nothing depends on the batch slot, L_max or T_max: a ragged batch is bit-identical to its utterances alone.  A non-finite sample
+ * cannot fault, cannot write outside the outputs and cannot move tau* outside [tau_min, tau_max]; UNLIKE YIN it may change frames
+ * anywhere in its utterance, because the path is global.  Frames in [T_b, T_max) are written as mt2_f0_yin writes them.
+ *
+ * mt2_f0_track_query: host only, no HIP call (outputs may be NULL) - T = 1 + L / hop, the lag range, n and the arena bytes of one
+ * mt2_f0_track call with B utterances and T_max = T:  r(4 (4 ceil(B / 4) + 256)) for the lengths and lg + r(4 B T 257) for d' +
+ * r(256 B T) for psi, r(x) = x rounded up to a multiple of 256.  Refuses what mt2_f0_track refuses of these arguments, and L
+ * outside [1, 2^31). */
+int mt2_f0_track_query(int sample_rate, int hop, float fmin, float fmax, float octave_cost, float jump_cost, long long L, int B,
+                       int* frames, int* lag_min, int* lag_max, int* states, long long* workspace_bytes);
+/* Arguments and outputs as mt2_f0_yin (diff is d, the same bits as mt2_f0_yin's).  Two launches for the batch: d' of every frame to
+ * arena scratch, then one workgroup per utterance for the recurrence, the backtrack and the refinement (stage events, with
+ * mt2_set_profiling: f0_cmnd, f0_viterbi).  The call only enqueues.  Refused (error, nothing launched, every output as it was):
+ * everything mt2_f0_yin refuses, and a negative or non-finite octave_cost or jump_cost. */
+int mt2_f0_track(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                 int sample_rate, int hop, float fmin, float fmax, float threshold, float octave_cost, float jump_cost,
+                 float* f0 /*[B, T_max]*/, float* cmnd /*or NULL*/, int32_t* lag /*or NULL*/, int T_max, float* diff /*or NULL*/);
 /* f0 f32 [B, T_max] (device), frame_lens host int32 [B] in [1, T_max] -> stats f64 [B, 6] (device).  One launch, a workgroup per
  * utterance; the call only enqueues.  Refused: B < 1 or > 65535, a frame count outside [1, T_max], stats overlapping f0. */
 int mt2_f0_stats(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/, const int32_t* frame_lens /*host*/, int T_max, int B,

@@ -763,6 +763,41 @@ int mt2_f0_yin(mt2_model* m, void* stream, const float* wav, const int32_t* lens
     MT2_API_END
 }
 
+// F0 by the Viterbi pass over YIN's lag costs: frames, lag range, state count and arena bytes (B utterances, the longest of L
+// samples), without a HIP call
+int mt2_f0_track_query(int sample_rate, int hop, float fmin, float fmax, float octave_cost, float jump_cost, long long L, int B,
+                       int* frames, int* lag_min, int* lag_max, int* states, long long* workspace_bytes) {
+    MT2_API_BEGIN
+    int lo = 0, hi = 0;
+    f0_check_rule(sample_rate, hop, fmin, fmax, &lo, &hi);
+    f0_track_check_costs(octave_cost, jump_cost);
+    MT2_REQUIRE(L >= 1 && L <= INT_MAX, "L outside [1, 2^31)");
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    const long long T = 1 + L / hop;
+    if (frames) *frames = (int)T;
+    if (lag_min) *lag_min = lo;
+    if (lag_max) *lag_max = hi;
+    if (states) *states = hi - lo + 1;
+    if (workspace_bytes) *workspace_bytes = f0_track_bytes(B, T);
+    MT2_API_END
+}
+
+// the same outputs as mt2_f0_yin by the second rule; every refusal is decided on the host before the first HIP call
+int mt2_f0_track(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sample_rate, int hop, float fmin,
+                 float fmax, float threshold, float octave_cost, float jump_cost, float* f0, float* cmnd, int32_t* lag, int T_max,
+                 float* diff) {
+    MT2_API_BEGIN
+    int lo = 0, hi = 0;
+    f0_check_rule(sample_rate, hop, fmin, fmax, &lo, &hi);
+    f0_track_check_costs(octave_cost, jump_cost);
+    const int mx = f0_check_call(wav, lens, L_max, B, hop, threshold, f0, cmnd, lag, T_max, diff);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    f0_track_run(c, wav, lens, L_max, B, mx, sample_rate, hop, lo, hi, threshold, octave_cost, jump_cost, f0, cmnd, lag, T_max, diff);
+    MT2_API_END
+}
+
 // the pitch moments of f0 tracks over their voiced frames
 int mt2_f0_stats(mt2_model* m, void* stream, const float* f0, const int32_t* frame_lens, int T_max, int B, double* stats) {
     MT2_API_BEGIN

@@ -2078,6 +2078,44 @@ static void f0_run(const Ctx& c, const float* wav, const int* lens, int L_max, i
     p.f0 = f0; p.T_max = T_max; p.cmnd = cmnd; p.lag = lag; p.diff = diff;
     MT2_HIP(launch_f0_yin(p, c.s));
 }
+// mt2_f0_track: the two costs, and the arena bytes of a call with B utterances and T_max frames - r(4 (4 ceil(B / 4) + 256)) for the
+// lengths and the lg table + r(4 B T_max 257) for d' + r(256 B T_max) for psi, r(x) = x rounded up to 256
+static void f0_track_check_costs(float octave_cost, float jump_cost) {
+    MT2_REQUIRE(std::isfinite(octave_cost) && octave_cost >= 0.0f, "octave_cost must be finite and >= 0");
+    MT2_REQUIRE(std::isfinite(jump_cost) && jump_cost >= 0.0f, "jump_cost must be finite and >= 0");
+}
+static long long f0_track_bytes(long long B, long long T_max) {
+    auto r = [](long long x) { return (x + 255) & ~255ll; };
+    return r(4 * (((B + 3) & ~3ll) + 256)) + r(4 * B * T_max * (MT2_F0_MAX_LAG + 1)) + r(256 * B * T_max);
+}
+// enqueues only: the lengths and the lg table travel in the call's one IntPlan upload
+static void f0_track_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, int hop,
+                         int lag_min, int lag_max, float threshold, float octave_cost, float jump_cost, float* f0, float* cmnd,
+                         int32_t* lag, int T_max, float* diff) {
+    float lg[256];
+    f0_track_table(lag_min, lag_max, lg);
+    std::vector<int> bits(256);
+    std::memcpy(bits.data(), lg, sizeof(lg));
+    IntPlan ip;
+    const int o_len = ip.add(std::vector<int>(lens, lens + B)), o_lg = ip.add(bits);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    F0TrackP q{};
+    F0P& p = q.y;
+    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B;
+    p.sample_rate = sample_rate; p.hop = hop; p.lag_min = lag_min; p.lag_max = lag_max; p.threshold = threshold;
+    p.f0 = f0; p.T_max = T_max; p.cmnd = cmnd; p.lag = lag; p.diff = diff;
+    q.octave_cost = octave_cost; q.jump_cost = jump_cost;
+    q.lg = reinterpret_cast<const float*>(ip.dev(o_lg));
+    q.dprime = c.ws.get<float>((size_t)B * T_max * (MT2_F0_MAX_LAG + 1));
+    q.psi = c.ws.get<unsigned char>((size_t)B * T_max * 256);
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(launch_f0_cmnd(q, c.s));
+    st.mark("f0_cmnd");
+    MT2_HIP(launch_f0_viterbi(q, c.s));
+    st.mark("f0_viterbi");
+    st.finish();
+}
 static void f0_stats_check(const float* f0, const int* frame_lens, int T_max, int B, const double* stats) {
     MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
     MT2_REQUIRE(f0 != nullptr && frame_lens != nullptr && stats != nullptr && T_max >= 1, "bad buffers");

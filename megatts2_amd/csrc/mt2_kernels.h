@@ -529,6 +529,20 @@ struct F0P {
     float* diff;                              // optional [B, T_max, MT2_F0_MAX_LAG + 1]: d
 };
 hipError_t launch_f0_yin(const F0P& p, hipStream_t s);
+// The second tracker (mt2_f0_track): a Viterbi pass over d'.  lg [256] (device): f0_track_table's; dprime [B, T_max, 257] and psi
+// [B, T_max, 256] are scratch.  Two launches: d' of every frame (a workgroup per frame), then a workgroup per utterance for the
+// recurrence, the backtrack and the refinement, in this order on one stream.  y.diff / y.cmnd / y.lag are optional as in launch_f0_yin.
+struct F0TrackP {
+    F0P y;
+    float octave_cost, jump_cost;             // finite, >= 0
+    const float* lg;
+    float* dprime;
+    unsigned char* psi;
+};
+// host only: lg[k] = (float)log2((double)(lag_min + k)) for lag_min + k <= lag_max, 0 behind; 256 entries
+void f0_track_table(int lag_min, int lag_max, float* lg);
+hipError_t launch_f0_cmnd(const F0TrackP& p, hipStream_t s);          // d' -> p.dprime; frames in [T_b, T_max) written as unvoiced
+hipError_t launch_f0_viterbi(const F0TrackP& p, hipStream_t s);       // p.dprime -> f0, cmnd, lag of the frames below T_b
 // stats[b, 0 .. 6) (double) = n, n / T_b, mean, sigma, skewness, excess kurtosis of f0[b, t] > 0 over t < frame_len[b]; a workgroup per utterance
 hipError_t launch_f0_stats(const float* f0, const int* frame_len, int T_max, int B, double* stats, hipStream_t s);
 

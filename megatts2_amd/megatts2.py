@@ -61,13 +61,16 @@ def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Option
     return mel if batched else mel[0]
 
 
-def extract_f0(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, **yin):
+def extract_f0(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, method: str = "yin", **yin):
     """F0 track of a 1-D waveform (16 kHz) -> f0 [T] in Hz, 0 where a frame is unvoiced: YIN on the GPU by the rule of csrc/f0.hip
     (MelFrontEnd.f0; no reference counterpart, parity with librosa.yin / pyin and quality on real speech unpinned).  sample_rate and
     trim_db are extract_mel_spec's, applied first in the same way, so f0[t] belongs to mel frame t of the same call; a [B, L] input
     gives [B, T].  **yin: MelFrontEnd.f0's arguments (fmin, fmax, threshold, hop, return_cmnd, return_lag, return_diff); with an
-    extra asked for the result is MelFrontEnd.f0's tuple."""
+    extra asked for the result is MelFrontEnd.f0's tuple.  method="viterbi": the second tracker (MelFrontEnd.f0_track, a Viterbi
+    pass over YIN's lag costs that cures its octave-high frames), which also takes octave_cost and jump_cost."""
     import torch
+    if method not in ("yin", "viterbi"):
+        raise ValueError("method must be 'yin' or 'viterbi'")
     fe = _frontend()
     x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
     batched = x.dim() == 2
@@ -77,7 +80,7 @@ def extract_f0(samples, sample_rate: Optional[int] = None, trim_db: Optional[flo
     lens = None
     if trim_db is not None:
         x, lens, _ = fe.trim(x, top_db=trim_db)
-    res = fe.f0(x, lens, **yin)
+    res = (fe.f0 if method == "yin" else fe.f0_track)(x, lens, **yin)
     if batched:
         return res
     return tuple(r[0] for r in res) if isinstance(res, tuple) else res[0]

@@ -101,6 +101,8 @@ def load_library():
     lib.mt2_griffin_lim.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.mt2_f0_query.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_longlong] + [C.c_void_p] * 4
     lib.mt2_f0_yin.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+    lib.mt2_f0_track_query.argtypes = [C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_longlong, C.c_int] + [C.c_void_p] * 5
+    lib.mt2_f0_track.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 5 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
     lib.mt2_f0_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]
     _LIB = lib
     return lib
@@ -791,6 +793,35 @@ class MelFrontEnd:
         diff = torch.empty(B, T, F0_MAX_LAG + 1, device=wav.device, dtype=torch.float32) if return_diff else None
         _check(self.lib.mt2_f0_yin(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, self.audio.sample_rate, hop, float(fmin), float(fmax),
                                    float(threshold), _ptr(out), _ptr(cmnd), _ptr(lag), T, _ptr(diff)))
+        extras = tuple(x for x in (cmnd, lag, diff) if x is not None)
+        return (out,) + extras if extras else out
+
+    def f0_track(self, wav, lens=None, fmin: float = 62.5, fmax: float = 500.0, threshold: float = 0.15, hop: Optional[int] = None,
+                 octave_cost: float = 0.02, jump_cost: float = 0.5, return_cmnd: bool = False, return_lag: bool = False,
+                 return_diff: bool = False, out=None):
+        """F0 track of a ragged batch by the second tracker, a Viterbi pass over YIN's lag costs (mt2_f0_track; the rule is in
+        include/megatts2_hip.h and csrc/f0.hip): one lag per frame by the frame's whole d' curve plus jump_cost per octave jumped
+        between frames and octave_cost per octave of lag, which cures YIN's octave-high frames on signals with dominant even
+        harmonics.  A frame is voiced iff d' at the tracked lag < threshold.  Arguments, outputs and extras as MelFrontEnd.f0.  A
+        non-finite sample may change frames anywhere in its utterance (the path is global), never another utterance's.  The call
+        only enqueues."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+        assert ln.shape == (B,)
+        hop = self.audio.hop_length if hop is None else int(hop)
+        if out is None:
+            out = torch.empty(B, 1 + max(int(ln.max()), 0) // max(hop, 1), device=wav.device, dtype=torch.float32)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        T = out.shape[1]
+        cmnd = torch.empty(B, T, device=wav.device, dtype=torch.float32) if return_cmnd else None
+        lag = torch.empty(B, T, device=wav.device, dtype=torch.int32) if return_lag else None
+        diff = torch.empty(B, T, F0_MAX_LAG + 1, device=wav.device, dtype=torch.float32) if return_diff else None
+        _check(self.lib.mt2_f0_track(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, self.audio.sample_rate, hop, float(fmin), float(fmax),
+                                     float(threshold), float(octave_cost), float(jump_cost), _ptr(out), _ptr(cmnd), _ptr(lag), T,
+                                     _ptr(diff)))
         extras = tuple(x for x in (cmnd, lag, diff) if x is not None)
         return (out,) + extras if extras else out
 
@@ -1515,6 +1546,17 @@ def f0_query(L: int, sample_rate: int = 16000, hop: int = 256, fmin: float = 62.
     _check(load_library().mt2_f0_query(int(sample_rate), int(hop), float(fmin), float(fmax), int(L), C.byref(f), C.byref(lo), C.byref(hi),
                                        C.byref(ws)))
     return f.value, lo.value, hi.value, ws.value
+
+
+def f0_track_query(L: int, B: int = 1, sample_rate: int = 16000, hop: int = 256, fmin: float = 62.5, fmax: float = 500.0,
+                   octave_cost: float = 0.02, jump_cost: float = 0.5):
+    """mt2_f0_track_query (no device needed) -> (frames, lag_min, lag_max, states, workspace_bytes) of one MelFrontEnd.f0_track call
+    with B utterances, the longest of L samples: T = 1 + L // hop, n = lag_max - lag_min + 1 and, with r(x) = x rounded up to 256,
+    r(4 (4 ceil(B / 4) + 256)) + r(4 B T 257) + r(256 B T) arena bytes; NativeError where the rule refuses."""
+    f, lo, hi, n, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0)
+    _check(load_library().mt2_f0_track_query(int(sample_rate), int(hop), float(fmin), float(fmax), float(octave_cost), float(jump_cost),
+                                             int(L), int(B), C.byref(f), C.byref(lo), C.byref(hi), C.byref(n), C.byref(ws)))
+    return f.value, lo.value, hi.value, n.value, ws.value
 
 
 def dtw_query(Tx_max: int, Ty_max: int, D: int = 80, B: int = 1) -> int:

@@ -32,6 +32,10 @@ def main() -> None:
                     help="print the pitch moments (F0 tracked on the GPU, see --pitch-tracker) of the first prompt and, when a vocoder produced audio, of the generated audio")
     ap.add_argument("--pitch-tracker", choices=("yin", "viterbi"), default="yin",
                     help="--report-pitch by plain YIN, or by the Viterbi pass over its lag costs (robust to octave errors)")
+    ap.add_argument("--report-prosody", action="store_true",
+                    help="print the duration moments of the output and, when a vocoder produced audio, one line per phone (frames, voiced frames, "
+                         "mean Hz, semitones above 55 Hz, energy in dB; F0 by --pitch-tracker) and the DTW pitch-contour distance between the "
+                         "first prompt and the generated audio")
     ap.add_argument("--text")
     ap.add_argument("--phones", help="comma separated phone token ids (bypasses the G2P)")
     ap.add_argument("--out", default="test.wav")
@@ -50,7 +54,7 @@ def main() -> None:
     tts.eval()
     phones = [int(v) for v in a.phones.split(",")] if a.phones else None
     gl = {"n_iter": a.gl_iters} if a.vocoder == "griffin-lim" else None
-    mel, lens, _ = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl)
+    mel, lens, aux = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl)
     wrote = gl is not None or tts.hifi_gan is not None
     print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
     if a.report_pitch:
@@ -61,6 +65,28 @@ def main() -> None:
             y, sr = audio_io.read_wav(path)
             st = M.pitch_stats(M.extract_f0(y, sr, trim_db=trim_db, method=a.pitch_tracker))
             print(f"pitch of the {what} ({path}): " + ", ".join(f"{k} {float(v[0]):.4g}" for k, v in st.items()))
+    if a.report_prosody:
+        import glob
+        import math
+        from megatts2_amd import audio_io
+        ds = M.duration_stats(aux["dur"])
+        print("durations of the output: " + ", ".join(f"{k} {float(v[0]):.4g}" for k, v in ds.items()))
+        if not wrote:
+            print("no phone-level pitch, energy or pitch distance: no vocoder produced audio to track (--vocoder griffin-lim needs no weights)")
+            return
+        pr = tts.output_prosody(lens, aux, tracker=a.pitch_tracker)      # the generated audio alone, not the written file (prompt in front)
+        ph = pr["phones"]
+        ids = phones if phones is not None else ["-"] * ph["frames"].shape[1]      # ids made from --text stay inside the call
+        for i, tok in enumerate(ids):
+            e = float(ph["mean_energy"][0, i])
+            db = f"{10 * math.log10(e):.1f} dB" if e > 0 else "-inf dB"
+            print(f"phone {i:3d} token {tok}: frames {int(ph['frames'][0, i])}, voiced {int(ph['voiced_frames'][0, i])}, "
+                  f"{float(ph['mean_hz'][0, i]):.1f} Hz, {float(ph['mean_semitones'][0, i]):.2f} st above 55 Hz, {db}")
+        path = sorted(glob.glob(f"{a.wavs_dir}/*.wav"))[0]
+        y, sr = audio_io.read_wav(path)
+        pd = M.pitch_distance(M.extract_f0(y, sr, trim_db=a.trim_db, method=a.pitch_tracker), pr["f0"][0], lens_b=pr["frame_lens"][:1])
+        print(f"pitch-contour distance, first prompt ({path}) to the generated audio: {float(pd['rms_semitones'][0]):.3f} semitones rms over "
+              f"{int(pd['steps'][0])} DTW steps ({int(pd['voiced_a'][0])} and {int(pd['voiced_b'][0])} voiced frames; centred, so the register does not count)")
 
 
 if __name__ == "__main__":

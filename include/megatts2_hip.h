@@ -465,6 +465,53 @@ int mt2_f0_track(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, co
 int mt2_f0_stats(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/, const int32_t* frame_lens /*host*/, int T_max, int B,
                  double* stats /*[B, 6]*/);
 
+/* ---- Per-phone prosody (csrc/prosody.hip): an energy contour on the mel's frames, the segment reduction of an F0 track over phone
+ * durations, and the voiced frames of a track compacted to a semitone contour, which turns mt2_dtw_align with D = 1 into a pitch-
+ * contour distance.  No reference counterpart (it would take pitch and energy from librosa or pyworld): the rules are our own,
+ * parity with any outside library and quality on real speech are unpinned, and the tests hold the kernels to the rules.  For all
+ * three: every sum is taken in an order that depends on the sample / frame / phone index within its utterance alone, so a ragged
+ * batch is bit-identical to its utterances alone, whatever the slot, L_max, T_max or Np_max;  a non-finite input cannot fault,
+ * cannot write outside the outputs and cannot change an output whose inputs do not hold it;  `m` may be a bare handle;  the
+ * lengths travel in the call's one upload and the call only enqueues;  every refusal is decided on the host before the first HIP
+ * call (error, nothing launched, every output as it was).
+ *
+ * mt2_frame_energy.  wav f32 [B, L_max] (device), lens host int32 [B], hop in [1, 1024] -> energy f32 [B, T_max] (device).  For one
+ * utterance x[0 .. L):  T = 1 + L / hop;  frame t reads [hop t - 512, hop t + 512) - MT2_F0_FRAME samples, exactly the F0 frames, so
+ * energy[t], f0[t] and mel frame t coincide;  a sample outside [0, L) is a zero by its index and is never read.  energy[t] = the
+ * mean square of the 1024 samples in f32 by one wave:  lane l runs ONE chain acc = fma(x, x, acc) from 0 over the in-frame offsets
+ * 256 i + 4 l + r, i = 0 .. 3 outer, r = 0 .. 3 inner;  the 64 partial sums meet in the xor butterfly 32, 16, 8, 4, 2, 1;  one
+ * product by 2^-10 (exact).  Frames in [T_b, T_max) are written 0.  Refused: what mt2_f0_yin refuses of B, lens, hop and T_max, and
+ * energy overlapping wav. */
+int mt2_frame_energy(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B, int hop,
+                     float* energy /*[B, T_max]*/, int T_max);
+/* mt2_phone_prosody.  f0 f32 [B, T_max], energy f32 [B, T_max] or NULL, dur int32 [B, Np_max] (all device - dur as the ADM leaves
+ * it), phone_lens and frame_lens host int32 [B] -> out f64 [B, Np_max, 8] (device, 16-byte aligned), optionally dur_sum int64 [B]
+ * (device).  For utterance b with Np phones and T frames:  start[p] = sum_{q < p} max(dur[q], 0) in int64;  phone p owns the frames
+ * [min(start, T), min(start + max(dur[p], 0), T)), taken in ascending order;  a frame is voiced iff f0 > 0 (a NaN is not).  The
+ * fields of out[b, p], all in double:
+ *   0 start (clipped)   1 frames owned   2 voiced frames among them   3 mean f0 in Hz over the voiced frames
+ *   4 mean of 12 log2((double)f0 / 55) over the voiced frames (semitones above A1)   5 min f0   6 max f0 over the voiced frames
+ *   7 mean of energy over all owned frames (0 when energy is NULL)
+ * 3 - 6 are 0 without a voiced frame, 7 is 0 without a frame;  rows p >= phone_lens[b] are all zeros;  dur beyond phone_lens[b] and
+ * frames beyond frame_lens[b] are never read.  dur_sum[b] = the unclipped sum of max(dur, 0): the caller compares it with T_b, the
+ * kernel decides nothing.  One launch, a workgroup per utterance.  Refused: B < 1 or > 65535; a phone count outside [1, Np_max]; a
+ * frame count outside [1, T_max]; overlapping buffers. */
+#define MT2_PROSODY_FIELDS 8
+int mt2_phone_prosody(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/, const float* energy /*or NULL*/,
+                      const int32_t* dur /*device [B, Np_max]*/, const int32_t* phone_lens /*host*/, int Np_max,
+                      const int32_t* frame_lens /*host*/, int T_max, int B, double* out /*[B, Np_max, 8]*/, long long* dur_sum /*or NULL*/);
+/* mt2_pitch_contour.  f0 f32 [B, T_max] (device), frame_lens host int32 [B], center 0 / 1 -> st f32 [B, T_max], n_voiced int32 [B],
+ * optionally index int32 [B, T_max] (all device).  The voiced frames (f0 > 0) among the first T_b are kept in order - a stable
+ * compaction by the exclusive count of voiced flags in front of each frame.  s = 12 log2((double)f0);  with center, mu = sum s / n in
+ * double in the order of the pitch moments (thread i sums the frames i, i + 256, ... ascending, the 256 partial sums meet in a fixed
+ * tree) and st[k] = (float)(s - mu), rounded once;  without, st[k] = (float)s.  index[k] = the frame entry k came from.  Entries in
+ * [n, T_max) are written 0 / -1;  n = 0: the whole row is 0 / -1 and n_voiced 0.  One launch, a workgroup per utterance.
+ * mt2_dtw_align with D = 1 on two such contours gives `total` and `steps`: sqrt(total / steps) is the distance in semitones along the
+ * path - centring removes the speaker's register, the warp the speaking rate, compaction keeps unvoiced gaps from counting as pitch.
+ * Refused: B < 1 or > 65535; a frame count outside [1, T_max]; center not 0 or 1; overlapping buffers. */
+int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/, const int32_t* frame_lens /*host*/, int T_max, int B,
+                      int center, float* st /*[B, T_max]*/, int32_t* n_voiced /*[B]*/, int32_t* index /*or NULL*/);
+
 /* ---- the whole of Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) for a batch,
  * activations staying in the packed internal layout between stages.
  *   forced_dur   (host, optional) int32 [B, Np_max]: replaces the ADM's integer durations AFTER the ADM

@@ -809,6 +809,42 @@ int mt2_f0_stats(mt2_model* m, void* stream, const float* f0, const int32_t* fra
     MT2_API_END
 }
 
+// the energy contour on the F0 / mel frames (prosody.hip); every refusal is decided on the host before the first HIP call
+int mt2_frame_energy(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int hop, float* energy,
+                     int T_max) {
+    MT2_API_BEGIN
+    const int mx = energy_check(wav, lens, L_max, B, hop, energy, T_max);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    energy_run(c, wav, lens, L_max, B, mx, hop, energy, T_max);
+    MT2_API_END
+}
+
+// the segment reduction of an F0 track (and an energy contour) over phone durations
+int mt2_phone_prosody(mt2_model* m, void* stream, const float* f0, const float* energy, const int32_t* dur, const int32_t* phone_lens,
+                      int Np_max, const int32_t* frame_lens, int T_max, int B, double* out, long long* dur_sum) {
+    MT2_API_BEGIN
+    phone_prosody_check(f0, energy, dur, phone_lens, Np_max, frame_lens, T_max, B, out, dur_sum);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    phone_prosody_run(c, f0, energy, dur, phone_lens, Np_max, frame_lens, T_max, B, out, dur_sum);
+    MT2_API_END
+}
+
+// the voiced frames of F0 tracks compacted to semitone contours
+int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0, const int32_t* frame_lens, int T_max, int B, int center, float* st,
+                      int32_t* n_voiced, int32_t* index) {
+    MT2_API_BEGIN
+    pitch_contour_check(f0, frame_lens, T_max, B, center, st, n_voiced, index);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    pitch_contour_run(c, f0, frame_lens, T_max, B, center, st, n_voiced, index);
+    MT2_API_END
+}
+
 // the STFT the mel front-end takes its magnitude of, for a ragged batch (the front half of mt2_mel_spectrogram, shared with it)
 int mt2_stft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* wav, const int32_t* lens, int L_max, int B, float* spec,
              int T_max) {

@@ -2130,6 +2130,82 @@ static void f0_stats_run(const Ctx& c, const float* f0, const int* frame_lens, i
     MT2_HIP(launch_f0_stats(f0, ip.dev(o_len), T_max, B, stats, c.s));
 }
 
+// ---- per-phone prosody (prosody.hip): every refusal is decided here, on the host, before the first HIP call -------------------------
+// mt2_frame_energy; -> max_b lens[b]
+static int energy_check(const float* wav, const int* lens, int L_max, int B, int hop, const float* energy, int T_max) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(hop >= 1 && hop <= MT2_F0_FRAME, "hop outside [1, 1024]");
+    MT2_REQUIRE(wav != nullptr && lens != nullptr && energy != nullptr && L_max >= 1, "bad buffers");
+    MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)energy) & 3) == 0, "misaligned buffers");
+    int mx = 0;
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
+        mx = std::max(mx, lens[b]);
+    }
+    MT2_REQUIRE(T_max >= 1 + mx / hop, "T_max smaller than 1 + max length / hop");
+    MT2_REQUIRE(!f0_overlaps(energy, sizeof(float) * (size_t)B * T_max, wav, sizeof(float) * (size_t)B * L_max), "energy overlaps wav");
+    return mx;
+}
+static void energy_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int hop, float* energy, int T_max) {
+    IntPlan ip;
+    const int o_len = ip.add(std::vector<int>(lens, lens + B));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    EnergyP p{};
+    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B; p.hop = hop; p.energy = energy; p.T_max = T_max;
+    MT2_HIP(launch_frame_energy(p, c.s));
+}
+// mt2_phone_prosody
+static void phone_prosody_check(const float* f0, const float* energy, const int* dur, const int* phone_lens, int Np_max,
+                                const int* frame_lens, int T_max, int B, const double* out, const long long* dur_sum) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(f0 != nullptr && dur != nullptr && phone_lens != nullptr && frame_lens != nullptr && out != nullptr && Np_max >= 1 &&
+                    T_max >= 1, "bad buffers");
+    MT2_REQUIRE((((uintptr_t)f0 | (uintptr_t)energy | (uintptr_t)dur) & 3) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)dur_sum & 7) == 0,
+                "misaligned buffers");
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(phone_lens[b] >= 1 && phone_lens[b] <= Np_max, "phone count outside [1, Np_max]");
+        MT2_REQUIRE(frame_lens[b] >= 1 && frame_lens[b] <= T_max, "frame count outside [1, T_max]");
+    }
+    const size_t nt = sizeof(float) * (size_t)B * T_max, nd = sizeof(int) * (size_t)B * Np_max, no = sizeof(double) * 8 * (size_t)B * Np_max,
+                 ns = sizeof(long long) * (size_t)B;
+    MT2_REQUIRE(!f0_overlaps(out, no, f0, nt) && !f0_overlaps(out, no, energy, nt) && !f0_overlaps(out, no, dur, nd) &&
+                    !f0_overlaps(dur_sum, ns, f0, nt) && !f0_overlaps(dur_sum, ns, energy, nt) && !f0_overlaps(dur_sum, ns, dur, nd) &&
+                    !f0_overlaps(dur_sum, ns, out, no),
+                "overlapping buffers");
+}
+static void phone_prosody_run(const Ctx& c, const float* f0, const float* energy, const int* dur, const int* phone_lens, int Np_max,
+                              const int* frame_lens, int T_max, int B, double* out, long long* dur_sum) {
+    IntPlan ip;
+    const int o_np = ip.add(std::vector<int>(phone_lens, phone_lens + B)), o_t = ip.add(std::vector<int>(frame_lens, frame_lens + B));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    PhoneProsodyP p{};
+    p.f0 = f0; p.energy = energy; p.T_max = T_max; p.dur = dur; p.Np_max = Np_max; p.np_len = ip.dev(o_np); p.t_len = ip.dev(o_t);
+    p.B = B; p.out = out; p.dur_sum = dur_sum;
+    MT2_HIP(launch_phone_prosody(p, c.s));
+}
+// mt2_pitch_contour
+static void pitch_contour_check(const float* f0, const int* frame_lens, int T_max, int B, int center, const float* st, const int* n_voiced,
+                                const int* index) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(center == 0 || center == 1, "center must be 0 or 1");
+    MT2_REQUIRE(f0 != nullptr && frame_lens != nullptr && st != nullptr && n_voiced != nullptr && T_max >= 1, "bad buffers");
+    MT2_REQUIRE((((uintptr_t)f0 | (uintptr_t)st | (uintptr_t)n_voiced | (uintptr_t)index) & 3) == 0, "misaligned buffers");
+    for (int b = 0; b < B; ++b) MT2_REQUIRE(frame_lens[b] >= 1 && frame_lens[b] <= T_max, "frame count outside [1, T_max]");
+    const size_t nt = sizeof(float) * (size_t)B * T_max, nb = sizeof(int) * (size_t)B;
+    MT2_REQUIRE(!f0_overlaps(st, nt, f0, nt) && !f0_overlaps(index, nt, f0, nt) && !f0_overlaps(n_voiced, nb, f0, nt) &&
+                    !f0_overlaps(st, nt, index, nt) && !f0_overlaps(st, nt, n_voiced, nb) && !f0_overlaps(index, nt, n_voiced, nb),
+                "overlapping buffers");
+}
+static void pitch_contour_run(const Ctx& c, const float* f0, const int* frame_lens, int T_max, int B, int center, float* st, int* n_voiced,
+                              int* index) {
+    IntPlan ip;
+    const int o_t = ip.add(std::vector<int>(frame_lens, frame_lens + B));
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    PitchContourP p{};
+    p.f0 = f0; p.T_max = T_max; p.t_len = ip.dev(o_t); p.B = B; p.center = center; p.st = st; p.n_voiced = n_voiced; p.index = index;
+    MT2_HIP(launch_pitch_contour(p, c.s));
+}
+
 // The lengths of a DTW call, checked before anything else (host only)
 static void dtw_check_geometry(int Tx_max, int Ty_max, int D, int B) {
     MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");

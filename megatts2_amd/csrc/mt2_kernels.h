@@ -546,4 +546,35 @@ hipError_t launch_f0_viterbi(const F0TrackP& p, hipStream_t s);       // p.dprim
 // stats[b, 0 .. 6) (double) = n, n / T_b, mean, sigma, skewness, excess kurtosis of f0[b, t] > 0 over t < frame_len[b]; a workgroup per utterance
 hipError_t launch_f0_stats(const float* f0, const int* frame_len, int T_max, int B, double* stats, hipStream_t s);
 
+// ---- per-phone prosody (prosody.hip; the rules are in its header and in megatts2_hip.h) ---------------------------------------------
+// energy[b, t] = the mean square of the F0 frame t of utterance b (a wave per frame); frames in [T_b, T_max) are written 0
+struct EnergyP {
+    const float* wav; int L_max;              // [B, L_max]; samples at or beyond len[b] are never read
+    const int* len; int max_len, B;           // device [B]; max_b len[b]
+    int hop;
+    float* energy; int T_max;                 // [B, T_max], T_max >= 1 + max_len / hop
+};
+hipError_t launch_frame_energy(const EnergyP& p, hipStream_t s);
+// out[b, p, 0 .. 8) (double, 16-byte aligned) of the phones p < np_len[b] over the frames below t_len[b]; zero rows up to Np_max.
+// A workgroup per utterance.
+struct PhoneProsodyP {
+    const float* f0; const float* energy;     // [B, T_max]; energy optional
+    int T_max;
+    const int* dur; int Np_max;               // device [B, Np_max]; entries at or beyond np_len[b] are never read
+    const int* np_len; const int* t_len;      // device [B]
+    int B;
+    double* out;                              // [B, Np_max, 8]
+    long long* dur_sum;                       // optional [B]: the unclipped sum of max(dur, 0)
+};
+hipError_t launch_phone_prosody(const PhoneProsodyP& p, hipStream_t s);
+// the voiced frames of f0 below t_len[b] compacted in order to st = 12 log2 f0 (- their mean with center); a workgroup per utterance
+struct PitchContourP {
+    const float* f0; int T_max;               // [B, T_max]
+    const int* t_len; int B;                  // device [B]
+    int center;
+    float* st; int* n_voiced;                 // [B, T_max] (zeros in [n, T_max)); [B]
+    int* index;                               // optional [B, T_max]: the frame of entry k, -1 in [n, T_max)
+};
+hipError_t launch_pitch_contour(const PitchContourP& p, hipStream_t s);
+
 }  // namespace mt2

@@ -101,6 +101,103 @@ def pitch_stats(f0, frame_lens=None) -> Dict[str, np.ndarray]:
     return {k: st[:, i].copy() for i, k in enumerate(PITCH_STATS)}
 
 
+def extract_energy(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, **kw):
+    """Energy contour of a 1-D waveform (16 kHz) -> f32 [T]: the mean square of the 1024 samples around each mel frame, on the GPU
+    by the rule of csrc/prosody.hip (MelFrontEnd.energy; no reference counterpart, parity with librosa's rms unpinned).  sample_rate
+    and trim_db are extract_f0's, applied first in exactly the same way, so energy[t], f0[t] and mel frame t of one call coincide; a
+    [B, L] input gives [B, T].  **kw: MelFrontEnd.energy's hop and out."""
+    import torch
+    fe = _frontend()
+    x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
+    batched = x.dim() == 2
+    x = (x if batched else x.unsqueeze(0)).to("cuda", torch.float32)
+    if sample_rate is not None and int(sample_rate) != fe.audio.sample_rate:
+        x = fe.resample(x, int(sample_rate))[0]
+    lens = None
+    if trim_db is not None:
+        x, lens, _ = fe.trim(x, top_db=trim_db)
+    res = fe.energy(x, lens, **kw)
+    return res if batched else res[0]
+
+
+PHONE_PROSODY = ("start", "frames", "voiced_frames", "mean_hz", "mean_semitones", "min_hz", "max_hz", "mean_energy")
+DURATION_STATS = ("phones", "realised_fraction", "mean_frames", "std_frames", "skewness", "kurtosis")
+
+
+def phone_prosody(f0, durations, energy=None, phone_lens=None, frame_lens=None, check_sum: bool = False) -> Dict[str, np.ndarray]:
+    """Phone-level pitch and energy: the segment reduction of an F0 track f0 [T] or [B, T] over phone durations [Np] or [B, Np]
+    (frames per phone: aux["dur"] of a synthesis call on the device, or a host alignment such as align_prompt's), on the GPU by
+    the rule of csrc/prosody.hip (MelFrontEnd.phone_prosody) -> dict of float64 numpy arrays [B, Np]: start, frames,
+    voiced_frames, mean_hz, mean_semitones (above 55 Hz), min_hz, max_hz (over the phone's voiced frames; 0 without one) and
+    mean_energy (over all its frames; 0 without `energy`, a track of extract_energy).  Phone p owns the frames from the sum of the
+    durations before it, clipped to frame_lens[b]; entries at or beyond phone_lens[b] are zeros.  check_sum: ValueError unless the
+    durations of every row sum to its frame count exactly."""
+    import torch
+
+    def dev(a):
+        a = a if hasattr(a, "is_cuda") else torch.as_tensor(np.asarray(a, np.float32))
+        return (a if a.dim() == 2 else a.unsqueeze(0)).to("cuda", torch.float32)
+
+    x = dev(f0)
+    d = durations if hasattr(durations, "is_cuda") else torch.as_tensor(np.asarray(durations, np.int32))
+    d = d if d.dim() == 2 else d.unsqueeze(0)
+    fe = _frontend()
+    out, total = fe.phone_prosody(x, d, None if energy is None else dev(energy), phone_lens, frame_lens, return_sum=True)
+    if check_sum:
+        want = fe._frame_lens(frame_lens, x.shape[0], x.shape[1])
+        got = total.cpu().numpy()
+        if not np.array_equal(got, want):
+            raise ValueError(f"durations sum to {got.tolist()} frames, the tracks have {want.tolist()}")
+    out = out.cpu().numpy()
+    return {k: out[:, :, i].copy() for i, k in enumerate(PHONE_PROSODY)}
+
+
+def duration_stats(durations, phone_lens=None) -> Dict[str, np.ndarray]:
+    """The moments of phone duration by which rhythm is reported beside pitch_stats: over the realised phones (duration > 0) among
+    the first phone_lens[b] of durations [Np] or [B, Np] (frames) -> dict of float64 numpy arrays [B]: phones, realised_fraction,
+    mean_frames, std_frames, skewness, kurtosis (excess).  A composition, no kernel of its own: the durations as f32 (exact below
+    2^24) go through MelFrontEnd.f0_stats, which already leaves zeros out and sums in double."""
+    import torch
+    d = durations if hasattr(durations, "is_cuda") else torch.as_tensor(np.asarray(durations, np.int32))
+    d = (d if d.dim() == 2 else d.unsqueeze(0)).to("cuda", torch.float32)
+    st = _frontend().f0_stats(d, phone_lens).cpu().numpy()
+    return {k: st[:, i].copy() for i, k in enumerate(DURATION_STATS)}
+
+
+def pitch_distance(f0_a, f0_b, lens_a=None, lens_b=None, center: bool = True) -> Dict[str, np.ndarray]:
+    """The DTW distance between pitch contours: f0_a [Ta] or [B, Ta] and f0_b [Tb] or [B, Tb] -> dict of numpy arrays [B]:
+    rms_semitones (float64) = sqrt(total / steps) of the warp of a's contour onto b's, steps, voiced_a, voiced_b (ints).  Each
+    track's voiced frames are compacted to semitones (MelFrontEnd.pitch_contour), so unvoiced gaps do not count as pitch; center
+    takes each contour's own mean off, which removes the speaker's register; the warp (MelFrontEnd.dtw with D = 1) removes the
+    speaking rate.  One copy of the voiced counts to the host in between.  A pair where either side has no voiced frame gets NaN
+    (steps 0) and is left out of the DTW call.  More than runtime.DTW_MAX_LEN = 4096 voiced frames on a side is the DTW's own
+    refusal (NativeError), never clamped.  The rule is our own; no outside library's distance is matched."""
+    import torch
+
+    def dev(a):
+        a = a if hasattr(a, "is_cuda") else torch.as_tensor(np.asarray(a, np.float32))
+        return (a if a.dim() == 2 else a.unsqueeze(0)).to("cuda", torch.float32)
+
+    fe = _frontend()
+    xa, xb = dev(f0_a), dev(f0_b)
+    B = xa.shape[0]
+    assert xb.shape[0] == B
+    sa, na = fe.pitch_contour(xa, lens_a, center=center)
+    sb, nb = fe.pitch_contour(xb, lens_b, center=center)
+    n = torch.stack([na, nb]).cpu().numpy()
+    res = {"rms_semitones": np.full(B, np.nan), "steps": np.zeros(B, np.int64), "voiced_a": n[0].astype(np.int64),
+           "voiced_b": n[1].astype(np.int64)}
+    keep = np.nonzero((n[0] > 0) & (n[1] > 0))[0]
+    if keep.size:
+        rows = torch.as_tensor(keep, device=xa.device)
+        ta, tb = int(n[0, keep].max()), int(n[1, keep].max())
+        path = fe.dtw(sa[rows, :ta].unsqueeze(2), sb[rows, :tb].unsqueeze(2), n[0, keep], n[1, keep])
+        steps = path["steps"].cpu().numpy().astype(np.int64)
+        res["steps"][keep] = steps
+        res["rms_semitones"][keep] = np.sqrt(path["total"].cpu().numpy().astype(np.float64) / steps)
+    return res
+
+
 class LengthRegulator:
     """reference modules/mrte.py:34-60 (FastSpeech length regulator) as a device gather."""
 
@@ -450,6 +547,32 @@ class Megatts:
         buzzy - the fallback when the hub's HiFi-GAN weights are not on hand and a way to listen to a synthetic or partly trained
         model, not a replacement for HiFi-GAN.  Every utterance needs at least n_fft / (2 hop) + 2 = 4 frames."""
         return _frontend().griffin_lim(mel, mel_lens, n_iter=n_iter, momentum=momentum, seeds=seeds, return_resid=return_resid)
+
+    def output_prosody(self, mel_lens, aux, tracker: str = "yin", phone_lens=None):
+        """Phone-level prosody of a synthesis call's own output: `mel_lens` and `aux` as `synthesize(..., return_aux=True)` returned
+        them with a vocoder on (aux["wav"] the audio, aux["dur"] the ADM's durations, device).  HiFi-GAN audio carries
+        inference_padding * hop samples on both sides of every utterance, which are removed first; Griffin-Lim audio has none.
+        Frame t of the tracks is then mel frame t.  F0 (tracker "yin" or "viterbi") and energy are tracked on the GPU and reduced
+        over the durations with frame_lens = mel_lens -> dict: "phones" (phone_prosody's dict, [B, Np]), "durations"
+        (duration_stats' dict, [B]), "f0" and "energy" (device f32 [B, T], T >= max mel_lens) and "frame_lens"."""
+        if tracker not in ("yin", "viterbi"):
+            raise ValueError("tracker must be 'yin' or 'viterbi'")
+        wav, dur = aux.get("wav"), aux["dur"]
+        if wav is None:
+            raise ValueError("aux has no audio: synthesize with vocoder=True or griffin_lim=True")
+        fe = _frontend()
+        hop = fe.audio.hop_length
+        ml = np.asarray(mel_lens, np.int32).reshape(-1)
+        top = int(ml.max())
+        pad = int(getattr(self.hifi_gan.cfg, "inference_padding", 0)) if self.hifi_gan is not None else 0
+        if self.hifi_gan is not None and wav.shape[1] >= (top + 2 * pad) * hop:      # HiFi-GAN: (mel_lens + 2 pad) hop samples a row
+            x, lens = wav[:, pad * hop:(pad + top) * hop].contiguous(), ml * hop
+        else:                                                                         # Griffin-Lim: (mel_lens - 1) hop samples
+            x, lens = wav, (ml - 1) * hop
+        f0 = (fe.f0 if tracker == "yin" else fe.f0_track)(x, lens)
+        energy = fe.energy(x, lens)
+        return {"phones": phone_prosody(f0, dur, energy, phone_lens, ml), "durations": duration_stats(dur, phone_lens), "f0": f0,
+                "energy": energy, "frame_lens": ml}
 
     def align_prompt(self, prompt_phone_tokens, mels, prompt_phone_lens=None, mel_lens=None, return_aux: bool = False):
         """The phone-level alignment of a prompt utterance to its own phones, made by the model itself - the `prompt_durations` of

@@ -27,6 +27,7 @@ MT2_RESAMPLE_NORMALIZE = 1
 TRIM_FRAME, TRIM_HOP = 2048, 512      # MT2_TRIM_FRAME, MT2_TRIM_HOP
 F0_FRAME, F0_WINDOW, F0_MAX_LAG = 1024, 768, 256      # MT2_F0_FRAME, MT2_F0_WINDOW, MT2_F0_MAX_LAG
 DTW_MAX_LEN, DTW_DIR_COLS = 4096, 16  # MT2_DTW_MAX_LEN, MT2_DTW_DIR_COLS
+PROSODY_FIELDS = 8                    # MT2_PROSODY_FIELDS
 
 
 class NativeError(RuntimeError):
@@ -104,6 +105,9 @@ def load_library():
     lib.mt2_f0_track_query.argtypes = [C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_longlong, C.c_int] + [C.c_void_p] * 5
     lib.mt2_f0_track.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 5 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
     lib.mt2_f0_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_frame_energy.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.mt2_phone_prosody.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mt2_pitch_contour.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
     _LIB = lib
     return lib
 
@@ -837,6 +841,70 @@ class MelFrontEnd:
         stats = torch.empty(B, 6, device=f0.device, dtype=torch.float64)
         _check(self.lib.mt2_f0_stats(self.h, _stream(), _ptr(f0), _iptr(ln), T, B, _ptr(stats)))
         return stats
+
+    # ---- per-phone prosody (csrc/prosody.hip)
+    def energy(self, wav, lens=None, hop: Optional[int] = None, out=None):
+        """Energy contour of a ragged batch on the mel's frames (mt2_frame_energy; the rule is in include/megatts2_hip.h): wav f32
+        [B, L] (device) -> f32 [B, 1 + max lens // hop], the mean square of the 1024 samples [hop t - 512, hop t + 512) - exactly
+        the F0 frames, so energy[b, t], f0[b, t] and mel frame t coincide; zeros behind an utterance's own 1 + lens[b] // hop.
+        Samples beyond lens[b] are never read.  hop defaults to the mel front-end's.  out: a contiguous f32 [B, >= T] device tensor
+        to write into.  No reference counterpart; parity with librosa's rms is unpinned.  The call only enqueues."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+        assert ln.shape == (B,)
+        hop = self.audio.hop_length if hop is None else int(hop)
+        if out is None:
+            out = torch.empty(B, 1 + max(int(ln.max()), 0) // max(hop, 1), device=wav.device, dtype=torch.float32)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        _check(self.lib.mt2_frame_energy(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, hop, _ptr(out), out.shape[1]))
+        return out
+
+    def phone_prosody(self, f0, dur, energy=None, phone_lens=None, frame_lens=None, return_sum: bool = False):
+        """The segment reduction of an F0 track over phone durations (mt2_phone_prosody): f0 f32 [B, T] (device), dur int [B, Np] (a
+        device tensor as aux["dur"] is, or a host array such as align_prompt's, which is uploaded here), optionally energy f32
+        [B, T] -> float64 [B, Np, 8] (device): start, frames, voiced frames, mean Hz, mean semitones above 55 Hz, min Hz, max Hz,
+        mean energy of every phone, phone p owning the frames [sum of the durations before it, + its own) clipped to
+        frame_lens[b]; a negative duration counts as 0; rows at or beyond phone_lens[b] are zeros.  return_sum: (out, int64 [B]
+        device) with the unclipped sum of the durations of each row.  The call only enqueues."""
+        import torch
+        assert f0.is_cuda and f0.dim() == 2
+        f0 = f0.contiguous().to(torch.float32)
+        B, T = f0.shape
+        dur = dur if hasattr(dur, "is_cuda") else torch.from_numpy(_i32(dur))
+        assert dur.dim() == 2 and dur.shape[0] == B
+        dur = dur.to(f0.device, torch.int32).contiguous()
+        Np = dur.shape[1]
+        if energy is not None:
+            assert energy.is_cuda and energy.shape == f0.shape
+            energy = energy.contiguous().to(torch.float32)
+        pl = np.full(B, Np, np.int32) if phone_lens is None else _i32(phone_lens)
+        assert pl.shape == (B,)
+        fl = self._frame_lens(frame_lens, B, T)
+        out = torch.empty(B, Np, PROSODY_FIELDS, device=f0.device, dtype=torch.float64)
+        total = torch.empty(B, device=f0.device, dtype=torch.int64) if return_sum else None
+        _check(self.lib.mt2_phone_prosody(self.h, _stream(), _ptr(f0), _ptr(energy), _ptr(dur), _iptr(pl), Np, _iptr(fl), T, B, _ptr(out),
+                                          _ptr(total)))
+        return (out, total) if return_sum else out
+
+    def pitch_contour(self, f0, frame_lens=None, center: bool = True, return_index: bool = False):
+        """The voiced frames (f0 > 0) among the first frame_lens[b] of f0 f32 [B, T] (device), kept in order, as semitones
+        12 log2 f0 (mt2_pitch_contour) -> (st f32 [B, T], n_voiced int32 [B]) on the device, zeros behind the n_voiced[b] entries of
+        a row.  center: the mean of the row's own entries (a double sum) is taken off, which removes the speaker's register.
+        return_index: a third result int32 [B, T], the frame each entry came from (-1 behind).  Two such contours through `dtw`
+        with D = 1 give the pitch-contour distance sqrt(total / steps).  The call only enqueues."""
+        import torch
+        assert f0.is_cuda and f0.dim() == 2
+        f0 = f0.contiguous().to(torch.float32)
+        B, T = f0.shape
+        fl = self._frame_lens(frame_lens, B, T)
+        st = torch.empty(B, T, device=f0.device, dtype=torch.float32)
+        n = torch.empty(B, device=f0.device, dtype=torch.int32)
+        index = torch.empty(B, T, device=f0.device, dtype=torch.int32) if return_index else None
+        _check(self.lib.mt2_pitch_contour(self.h, _stream(), _ptr(f0), _iptr(fl), T, B, 1 if center else 0, _ptr(st), _ptr(n), _ptr(index)))
+        return (st, n, index) if return_index else (st, n)
 
     def dtw(self, X, Y, x_lens=None, y_lens=None, return_cost: bool = False, return_acc: bool = False):
         """Dynamic time warping of X f32 [B, Tx, D] onto Y f32 [B, Ty, D] on the bare handle (`_dtw`, as NativeModel.dtw): e.g. the

@@ -432,6 +432,13 @@ __device__ __forceinline__ void loader_priority(int prio) {
     else if (prio == 1) __builtin_amdgcn_s_setprio(1);
 }
 
+// Row tile of workgroup `bid` among ntm (the window kernels: one column tile).  Workgroups are dealt round-robin to the 8 XCDs; each
+// XCD gets a contiguous run of row tiles, so that neighbouring tiles - which share their window halo - meet in ONE XCD's L2.
+__device__ __forceinline__ int xcd_row_tile(int bid, int ntm) {
+    const int xcd = bid & 7, qq = ntm >> 3, rr = ntm & 7;
+    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+}
+
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field on gfx9");
     __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));   // expcnt/lgkmcnt: no wait

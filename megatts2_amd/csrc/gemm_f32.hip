@@ -445,11 +445,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_win_f32_kernel(GemmP p) {
     float* ring = smem;
     float* win = smem + NST * STAGE;                                // [QS][WRp][32], slot-swizzled rows
 
-    const int ntm = (p.M + BM - 1) / BM;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, qq = ntm >> 3, rr = ntm & 7;
-    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);   // contiguous run per XCD
-    const int m0 = tile * BM;
+    const int m0 = xcd_row_tile(blockIdx.x, (p.M + BM - 1) / BM) * BM;     // contiguous run per XCD
 
     const float* __restrict__ X = p.X;
     const float* __restrict__ W = p.W;
@@ -640,11 +636,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_win_x6_kernel(Gemm
     char* ring = reinterpret_cast<char*>(smem);
     float* win = smem + NST * STAGE_B / 4;                          // [QS][WRp][32] f32, slot-swizzled rows
 
-    const int ntm = (p.M + BM - 1) / BM;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, qq = ntm >> 3, rr = ntm & 7;
-    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-    const int m0 = tile * BM;
+    const int m0 = xcd_row_tile(blockIdx.x, (p.M + BM - 1) / BM) * BM;
 
     const float* __restrict__ X = p.X;
     const unsigned short* __restrict__ W3 = reinterpret_cast<const unsigned short*>(p.W3);

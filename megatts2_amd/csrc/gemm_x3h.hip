@@ -96,6 +96,10 @@ __device__ __forceinline__ void split2_f16(const f32x4& lo, const f32x4& hi, flo
     }
 }
 
+}  // namespace mt2
+#include "x3h_window.h"      // what the window family shares (and the range guard's line): a part of this unit, needs everything above
+namespace mt2 {
+
 // NL loader waves refill the ring (f32 A rows + two fp16 weight planes), the WGM x WGN compute waves never issue a vector-memory
 // instruction inside the K loop.  PRO: prologue activation of the A values (ACT_*), or PRO_LNX: the pair-fed algebraic LayerNorm /
 // row-statistics epilogue form (K loop of ACT_NONE).
@@ -590,7 +594,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void gemm_x3h_ldr_kernel(Gem
         }
     }
     // range guard: an activation at or beyond the largest finite fp16 was converted somewhere in this wave's rows
-    if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+    MT2_X3H_GUARD_RAISE(p, amax, lane);
     // C = (acc_hi + 2^-11 acc_lo) * inv_n
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -842,7 +846,7 @@ __global__ __launch_bounds__((WGM * WGN * KS + NL) * 64) void gemm_x3h_ks_kernel
             p.dbg[8] = __builtin_readcyclecounter() - tcyc0;
         }
     }
-    if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+    MT2_X3H_GUARD_RAISE(p, amax, lane);
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = __builtin_fmaf(acl[e], kX3hLoInv, acc[e]);
     // ---- sum the KS partial tiles through LDS (every DMA has been waited for; the barrier orders the last operand reads),
@@ -904,14 +908,9 @@ __global__ __launch_bounds__((WGM * WGN * KS + NL) * 64) void gemm_x3h_ks_kernel
 // barrier (gemm_x3h_ldr_kernel's cross-chunk form).
 template <int QS, int BM, int BN, int WGM, int WGN, int NST, int PRO, int NL>
 __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_win_x3h_kernel(GemmP p) {
-    constexpr int NW = WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
-    constexpr int BPIECES = BN / 8;                       // 1-KiB pieces of one weight chunk: 8 rows x 128 B ([hi | lo] blocks)
-    constexpr int NI = NL;                                // waves that issue the ring refill: the NL loader waves
-    constexpr int B_IT = (BPIECES + NI - 1) / NI;
-    constexpr int STAGE_B = B_IT * NI * 1024;             // BYTES per ring stage (dummy slots included)
-    static_assert(NL > 0 && WTM % 32 == 0 && WTN % 32 == 0 && NST >= 3 && (NST - 2) * B_IT < 64 && BN == 32 * QS, "config");
+    using G = WinGeom<QS, BM, BN, WGM, WGN, NST, NL>;     // the family's tile constants and their static_assert (x3h_window.h)
+    constexpr int NW = G::NW, WTM = G::WTM, WTN = G::WTN, TM = G::TM, TN = G::TN;
+    constexpr int BPIECES = G::BPIECES, NI = NL, B_IT = G::B_IT, STAGE_B = G::STAGE_B;     // NI: the waves that issue the ring refill
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -925,9 +924,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_win_x3h_kernel(Gem
     float* win = smem + NST * STAGE_B / 4;                          // [QS][WRp][32] f32, slot-swizzled rows
 
     const int ntm = (p.M + BM - 1) / BM;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, qq = ntm >> 3, rr = ntm & 7;
-    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int tile = xcd_row_tile(blockIdx.x, ntm);
     const int m0 = tile * BM;
 
     const float* __restrict__ X = p.X;
@@ -1042,7 +1039,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_win_x3h_kernel(Gem
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the planes are in LDS before this wave's next barrier
     }
-    if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+    MT2_X3H_GUARD_RAISE(p, amax, lane);
     if (loader) {
         // cross-chunk form (the compute waves' K loop below): at barrier c the weights of chunk c-1 are still being read - the stage
         // that is free is chunk c-2's, and chunk c + NST - 2 goes there
@@ -1249,17 +1246,12 @@ __device__ __forceinline__ void pair_rows_to_planes(float* win, int tid, int WRp
 
 template <int QS, int BM, int BN, int WGM, int WGN, int NST, int NL>
 __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_pair_x3h_kernel(PairP p) {
-    constexpr int NW = WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
-    constexpr int BPIECES = BN / 8;
-    constexpr int NI = NL;
-    constexpr int B_IT = (BPIECES + NI - 1) / NI;
-    constexpr int STAGE_B = B_IT * NI * 1024;
-    constexpr int NT = (NW + NL) * 64;
+    using G = WinGeom<QS, BM, BN, WGM, WGN, NST, NL>;     // the family's tile constants and their static_assert (x3h_window.h)
+    constexpr int NW = G::NW, WTM = G::WTM, WTN = G::WTN, TM = G::TM, TN = G::TN;
+    constexpr int BPIECES = G::BPIECES, NI = NL, B_IT = G::B_IT, STAGE_B = G::STAGE_B;     // NI: the waves that issue the ring refill
+    constexpr int NT = G::NT;
     constexpr int MAXT1 = (QS * (BM + 64) * 4 + NT - 1) / NT;       // conv_pair_route: (k - 1) d <= 64
     constexpr int MAXT2 = (QS * BM * 4 + NT - 1) / NT;
-    static_assert(NL > 0 && WTM % 32 == 0 && WTN % 32 == 0 && NST >= 3 && (NST - 2) * B_IT < 64 && BN == 32 * QS, "config");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1274,9 +1266,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_pair_x3h_kernel(Pa
     float* win = smem + NST * STAGE_B / 4;                          // [QS][WRp][32] f32 / planes, slot-swizzled rows
 
     const int ntm = (p.R + BMo - 1) / BMo;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, qq = ntm >> 3, rr = ntm & 7;
-    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int tile = xcd_row_tile(blockIdx.x, ntm);
     const int o0 = tile * BMo;                                      // first output row
     const int t0 = o0 - (taps - 1) / 2;                             // global row of t1's local row 0
 
@@ -1337,7 +1327,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_pair_x3h_kernel(Pa
         else wait_vmcnt<0>();
         float amax = 0.0f;
         pair_rows_to_planes<ACT_LRELU, QS, NT, MAXT1>(win, tid, WRp, WRp, p.slope, amax);
-        if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+        MT2_X3H_GUARD_RAISE(p, amax, lane);
         loader_loop(rs1);
         __builtin_amdgcn_s_barrier();                            // every compute wave has left conv1's K loop: ring and window are free
         asm volatile("" ::: "memory");
@@ -1346,7 +1336,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_pair_x3h_kernel(Pa
             if (st < nk) issue(rs2, st, st);
         amax = 0.0f;
         pair_rows_to_planes<ACT_NONE, QS, NT, MAXT2>(win, tid, WRp, BM, p.slope, amax);
-        if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+        MT2_X3H_GUARD_RAISE(p, amax, lane);
         loader_loop(rs2);
         return;
     }
@@ -1367,7 +1357,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_pair_x3h_kernel(Pa
     }
     float amax = 0.0f;
     pair_rows_to_planes<ACT_LRELU, QS, NT, MAXT1>(win, tid, WRp, WRp, p.slope, amax);
-    if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+    MT2_X3H_GUARD_RAISE(p, amax, lane);
 
     f32x16 acc[TM][TN], acl[TM][TN];
     const int half = lane >> 5;
@@ -1517,7 +1507,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_pair_x3h_kernel(Pa
     }
     amax = 0.0f;
     pair_rows_to_planes<ACT_NONE, QS, NT, MAXT2>(win, tid, WRp, BM, p.slope, amax);
-    if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+    MT2_X3H_GUARD_RAISE(p, amax, lane);
     // ---- phase 2: y = mask * (conv2(t1) + bias2 + h) on the first BMo rows of the pass
     kloop(1, p.inv2);
     GemmP e{};
@@ -1531,7 +1521,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_pair_x3h_kernel(Pa
 typedef void (*PairKernel)(PairP);
 struct PairTile { int C, bm, threads; size_t ring; PairKernel fn; };
 #define MT2_PAIR_TILE(QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                                    \
-    { BN_, BM_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * (((2 * BN_ / 16 + NL_ - 1) / NL_) * NL_ * 1024),                        \
+    { BN_, BM_, WinGeom<QS_, BM_, BN_, WM_, WN_, NST_, NL_>::NT, WinGeom<QS_, BM_, BN_, WM_, WN_, NST_, NL_>::ring_bytes(),    \
       conv_pair_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, NL_> }
 static const PairTile kPairTiles[3] = {
     MT2_PAIR_TILE(1, 256, 32, 8, 1, 4, 4), MT2_PAIR_TILE(2, 256, 64, 8, 1, 4, 4), MT2_PAIR_TILE(4, 128, 128, 4, 2, 3, 4),
@@ -1547,22 +1537,18 @@ PairRoute conv_pair_route(const PairP& p, const EngineOpts& o) {
     if (t < 0 || !((o.pair_fuse >> t) & 1)) return fail(hipErrorNotSupported);
     if (p.reflect || (long long)(p.taps - 1) * p.dil > 64) return fail(hipErrorNotSupported);
     // ... and everything that would not run on the x3h window tiles as two launches (the pair is bit-identical to THOSE)
-    if (!o.win_conv || !o.x6_conv || !(o.x3h & 4) || o.force_cfg >= 0 || o.ldr64) return fail(hipErrorNotSupported);
+    if (!x3h_window_engine(o)) return fail(hipErrorNotSupported);
     if (!p.Wh1 || !p.Wh2 || !p.inv1 || !p.inv2) return fail(hipErrorNotSupported);      // missing planes
-    const long long two_g = 1ll << 31;
-    if ((long long)p.R * p.ldx * 4 >= two_g || (long long)p.R * p.ldy * 4 >= two_g || (long long)p.C * p.wh_ldb >= two_g - 1)
-        return fail(hipErrorNotSupported);
+    if (!win_below_2g(p.R, p.ldx, p.ldy, p.C, p.wh_ldb)) return fail(hipErrorNotSupported);
     if (!p.X || !p.Y || p.ldx < p.C || p.ldy < p.C || p.wh_ldb < 4ll * p.taps * p.C) return fail(hipErrorInvalidValue);
-    // (the window kernel's epilogue has a scalar-store form for operands off 16 bytes; the pair kernel leaves them to it)
-    if (((p.ldx | p.ldy) & 3) || (p.wh_ldb & 127) || (((unsigned long long)p.Wh1 | (unsigned long long)p.Wh2) & 127) ||
-        (((unsigned long long)p.X | (unsigned long long)p.Y | (unsigned long long)p.bias1 | (unsigned long long)p.bias2) & 15))
+    if (!win_aligned(p.ldx, p.ldy, p.wh_ldb, (unsigned long long)p.Wh1 | (unsigned long long)p.Wh2,
+                     (unsigned long long)p.X | (unsigned long long)p.Y | (unsigned long long)p.bias1 | (unsigned long long)p.bias2))
         return fail(hipErrorNotSupported);
     const PairTile& c = kPairTiles[t];
-    const int wrp = (c.bm + (p.taps - 1) * p.dil + 7) & ~7;
     r.tile = t;
     r.bm = c.bm;
     r.bmo = c.bm - (p.taps - 1);
-    r.lds = c.ring + (size_t)(p.C / 32) * wrp * BK * sizeof(float);
+    r.lds = c.ring + win_lds_bytes(p.C, c.bm, (p.taps - 1) * p.dil);
     r.grid = (unsigned)((p.R + r.bmo - 1) / r.bmo);
     r.block = (unsigned)c.threads;
     return r;
@@ -1580,8 +1566,7 @@ hipError_t launch_conv_pair(const PairP& p_in, hipStream_t s, EngineOpts* opts) 
     p.x3h_flag = o.x3h_flag;
     p.ldr_prio = o.ldr_prio;
     // the attribute covers the widest window ((k - 1) d <= 64)
-    const size_t lds_attr = c.ring + (size_t)(p.C / 32) * ((c.bm + 64 + 7) & ~7) * BK * sizeof(float);
-    const hipError_t e = dyn_lds_once(g_pair_attr_done[r.tile], reinterpret_cast<const void*>(c.fn), lds_attr);
+    const hipError_t e = dyn_lds_once(g_pair_attr_done[r.tile], reinterpret_cast<const void*>(c.fn), c.ring + win_lds_bytes(p.C, c.bm, 64));
     if (e != hipSuccess) return e;
     if (opts) opts->last_cfg = "x3hpair";
     hipLaunchKernelGGL(c.fn, dim3(r.grid), dim3(r.block), r.lds, s, p);
@@ -1602,20 +1587,15 @@ hipError_t launch_conv_pair(const PairP& p_in, hipStream_t s, EngineOpts* opts) 
 // with its own A fragments (NPH = 2).  Epilogue: the 16-byte-store one (row mask; the bias is added in registers, its index wraps at co).
 template <int QS, int BM, int BN, int WGM, int WGN, int NST, int NL>
 __global__ __launch_bounds__((WGM * WGN + NL) * 64) void up_mrf_x3h_kernel(UpMrfP p) {
-    constexpr int NW = WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
+    using G = WinGeom<QS, BM, BN, WGM, WGN, NST, NL>;     // the family's tile constants and their static_assert (x3h_window.h)
+    constexpr int NW = G::NW, WTM = G::WTM, WTN = G::WTN, TM = G::TM, TN = G::TN;
+    constexpr int BPIECES = G::BPIECES, NI = NL, B_IT = G::B_IT, STAGE_B = G::STAGE_B;     // NI: the waves that issue the ring refill
     constexpr int NPH = WGN == 2 ? 1 : 2;                 // phases among one wave's column tiles
     constexpr int CO = BN / 2;
-    constexpr int BPIECES = BN / 8;
-    constexpr int NI = NL;
-    constexpr int B_IT = (BPIECES + NI - 1) / NI;
-    constexpr int STAGE_B = B_IT * NI * 1024;
-    constexpr int NT = (NW + NL) * 64;
+    constexpr int NT = G::NT;
     constexpr int WR = BM + 2, WRp = (WR + 7) & ~7;
     constexpr int NTASK = QS * WRp * 4, MAXT = (NTASK + NT - 1) / NT;   // (row block, j): f32 slots 2 j, 2 j + 1 -> hi slot j, lo slot 4 + j
     constexpr int NK = 2 * QS;                            // chunks: tap t = c / QS, slice c % QS
-    static_assert(NL > 0 && WTM % 32 == 0 && WTN % 32 == 0 && NST >= 3 && (NST - 2) * B_IT < 64 && BN == 32 * QS, "config");
     static_assert((WGN == 2 && WTN == CO) || (WGN == 1 && TN == 2), "a wave's columns are one phase, or one 32-column tile per phase");
     static_assert(NK >= NST - 1 && QS >= 2, "the ring's first stages are whole chunks of this launch");
 
@@ -1629,9 +1609,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void up_mrf_x3h_kernel(UpMrf
     float* win = smem + NST * STAGE_B / 4;                          // [QS][WRp][32] f32 / planes, slot-swizzled rows
 
     const int ntm = (p.R + BM - 1) / BM;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, qq = ntm >> 3, rr = ntm & 7;
-    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int tile = xcd_row_tile(blockIdx.x, ntm);
     const int m0 = tile * BM;                                       // first output row pair
     const int row_first = m0 - 1;                                   // global row of the window's row 0
     const int ldx = p.ldx, Rx = p.R;
@@ -1738,7 +1716,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void up_mrf_x3h_kernel(UpMrf
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the planes are in LDS before this wave's next barrier
     }
-    if (p.x3h_flag != nullptr && __builtin_amdgcn_ballot_w64(amax >= kX3hMaxIn) != 0ull && lane == 0) atomicOr(p.x3h_flag, 1);
+    MT2_X3H_GUARD_RAISE(p, amax, lane);
     if (loader) {
         // cross-chunk form: at barrier c the weights of chunk c-1 are still being read - the free stage is chunk c-2's
         for (int c = 0; c < NK; ++c) {
@@ -1886,7 +1864,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void up_mrf_x3h_kernel(UpMrf
 typedef void (*UpMrfKernel)(UpMrfP);
 struct UpMrfTile { int ch, bm, threads; size_t ring; UpMrfKernel fn; };
 #define MT2_UPMRF_TILE(QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                                   \
-    { BN_, BM_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * (((2 * BN_ / 16 + NL_ - 1) / NL_) * NL_ * 1024),                        \
+    { BN_, BM_, WinGeom<QS_, BM_, BN_, WM_, WN_, NST_, NL_>::NT, WinGeom<QS_, BM_, BN_, WM_, WN_, NST_, NL_>::ring_bytes(),    \
       up_mrf_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, NL_> }
 static const UpMrfTile kUpMrfTiles[2] = { MT2_UPMRF_TILE(2, 256, 64, 8, 1, 4, 4), MT2_UPMRF_TILE(4, 128, 128, 4, 2, 3, 4) };
 
@@ -1897,19 +1875,17 @@ UpMrfRoute up_mrf_route(const UpMrfP& p, const EngineOpts& o) {
     // the three-launch form (avg3 + the two GEMM halves) keeps everything this kernel was not built for
     const int t = p.ch == 64 ? 0 : (p.ch == 128 ? 1 : -1);
     if (t < 0 || p.stride != 2 || !((o.up_fuse >> t) & 1)) return fail(hipErrorNotSupported);
-    if (!o.win_conv || !o.x6_conv || !(o.x3h & 4) || o.force_cfg >= 0 || o.ldr64) return fail(hipErrorNotSupported);
+    if (!x3h_window_engine(o)) return fail(hipErrorNotSupported);
     if (!p.Wh || !p.inv) return fail(hipErrorNotSupported);          // missing planes
-    const long long two_g = 1ll << 31;
-    if ((long long)p.R * p.ldx * 4 >= two_g || (long long)p.R * p.ldy * 4 >= two_g || (long long)p.ch * p.wh_ldb >= two_g - 1)
-        return fail(hipErrorNotSupported);
+    if (!win_below_2g(p.R, p.ldx, p.ldy, p.ch, p.wh_ldb)) return fail(hipErrorNotSupported);
     if (!p.X0 || !p.X1 || !p.X2 || !p.Y || p.ldx < p.ch || p.ldy < p.ch || p.wh_ldb < 8ll * p.ch) return fail(hipErrorInvalidValue);
-    if (((p.ldx | p.ldy) & 3) || (p.wh_ldb & 127) || ((unsigned long long)p.Wh & 127) ||
-        (((unsigned long long)p.X0 | (unsigned long long)p.X1 | (unsigned long long)p.X2 | (unsigned long long)p.Y | (unsigned long long)p.bias) & 15))
+    if (!win_aligned(p.ldx, p.ldy, p.wh_ldb, (unsigned long long)p.Wh,
+                     (unsigned long long)p.X0 | (unsigned long long)p.X1 | (unsigned long long)p.X2 | (unsigned long long)p.Y | (unsigned long long)p.bias))
         return fail(hipErrorNotSupported);
     const UpMrfTile& c = kUpMrfTiles[t];
     r.tile = t;
     r.bm = c.bm;
-    r.lds = c.ring + (size_t)(p.ch / 32) * ((c.bm + 2 + 7) & ~7) * BK * sizeof(float);
+    r.lds = c.ring + win_lds_bytes(p.ch, c.bm, 2);
     r.grid = (unsigned)((p.R + c.bm - 1) / c.bm);
     r.block = (unsigned)c.threads;
     return r;
@@ -1949,9 +1925,9 @@ hipError_t launch_up_mrf(const UpMrfP& p_in, hipStream_t s, EngineOpts* opts) {
       { gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_NONE>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_RELU>, \
         gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_LRELU>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_APL>, \
         gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_LNX> }, PIPE_X3H, 0, KS_, 32 }
-// window convolution: ring stage = 2 planes x BN x 64 B, in whole KiB per loader wave
+// window convolution: ring stage = 2 planes x BN x 64 B, in whole KiB per loader wave (WinGeom, x3h_window.h)
 #define MT2_X3H_WIN(IDX_, QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                               \
-    { IDX_, BM_, BN_, (WM_* WN_ + NL_) * 64, (size_t)NST_ * (((2 * BN_ / 16 + NL_ - 1) / NL_) * NL_ * 1024),                  \
+    { IDX_, BM_, BN_, WinGeom<QS_, BM_, BN_, WM_, WN_, NST_, NL_>::NT, WinGeom<QS_, BM_, BN_, WM_, WN_, NST_, NL_>::ring_bytes(), \
       "x3hwin" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "+" #NL_ "_s" #NST_,                                                          \
       { conv_win_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_NONE, NL_>, conv_win_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_RELU, NL_>, \
         conv_win_x3h_kernel<QS_, BM_, BN_, WM_, WN_, NST_, ACT_LRELU, NL_> }, PIPE_X3H, QS_ }

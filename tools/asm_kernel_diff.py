@@ -5,9 +5,15 @@
     python tools/asm_kernel_diff.py before.s after.s
 
 Per kernel symbol: the instruction stream (labels renumbered per function, so the order of the kernels in the file does not matter)
-and the resource block (.amdhsa_kernel ... .end_amdhsa_kernel: VGPRs, SGPRs, LDS, scratch) must be identical.  Exit status 1 otherwise."""
+and the resource block (.amdhsa_kernel ... .end_amdhsa_kernel: VGPRs, SGPRs, LDS, scratch) must be identical.  Exit status 1 otherwise.
+
+    python tools/asm_kernel_diff.py --opcodes before.s after.s
+
+also prints, for each kernel whose instruction stream differs, the opcodes whose counts changed: the record of a DEVICE-side refactor
+(same matrix, LDS, memory, barrier and wait instructions; what moved is address arithmetic)."""
 import re
 import sys
+from collections import Counter
 
 
 def kernels(path):
@@ -35,7 +41,13 @@ def kernels(path):
     return body, meta
 
 
-def main(a, b):
+def opcode_changes(x, y):
+    """The opcodes whose counts differ between two instruction streams, as 'opcode before -> after' (labels and directives left out)."""
+    cx, cy = (Counter(l.split()[0] for l in s if not l.endswith(":") and not l.startswith(".")) for s in (x, y))
+    return [f"{op} {cx[op]} -> {cy[op]}" for op in sorted(set(cx) | set(cy)) if cx[op] != cy[op]]
+
+
+def main(a, b, opcodes=False):
     (ba, ma), (bb, mb) = kernels(a), kernels(b)
     bad = 0
     for what, x, y in (("instruction stream", ba, bb), ("resource block", ma, mb)):
@@ -46,6 +58,9 @@ def main(a, b):
             elif x[k] != y[k]:
                 print(f"{what} differs: {k}")
                 bad += 1
+                if opcodes and x is ba:
+                    ch = opcode_changes(x[k], y[k])
+                    print(f"    {len(x[k])} -> {len(y[k])} lines; " + ("; ".join(ch) if ch else "every opcode count unchanged"))
     n_inst = sum(len(v) for v in ba.values())
     print(f"{len(ba)} / {len(bb)} kernels, {len(ma)} / {len(mb)} resource blocks, {n_inst} instruction lines compared: "
           + ("identical" if not bad else f"{bad} difference(s)"))
@@ -53,4 +68,5 @@ def main(a, b):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    args = [a for a in sys.argv[1:] if a != "--opcodes"]
+    sys.exit(main(args[0], args[1], opcodes="--opcodes" in sys.argv[1:]))

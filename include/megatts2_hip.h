@@ -800,6 +800,21 @@ int mt2_gemm_trace_end(mt2_model* m, int cap, const char** names, int64_t* launc
 /* text table "config M N K groups launches ms tflops" of the traced launches grouped by shape, slowest first;
  * call BEFORE mt2_gemm_trace_end (which frees the records); returns the bytes written or -1 */
 int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top);
+/* Form log of the autoregressive step wiring (tests).  Between begin and end every decision the step layers of the ADM / PLM take
+ * (csrc/model_stages.hip, ar_step_layers) is recorded as one text line, in call order:
+ *     <kind> <point> <form> key=value ...
+ *   kind   the layer that issued it: first-fill, first-incr, mid, last-skinny, last-split, last-fused
+ *   ln_linear   skinny-ln | skinny-ln-pairs | pair-fed | plain | plain+planes      M= N= tile= nw=
+ *   residual    split (S > 1 K slices) | stat (un-split, row statistics handed on) | nostat      S= stat_nt= stat_w= a_planes= M= K= tile= nw=
+ *               (tile: the configuration name of the GEMM; nw: the waves that split K if it ran on the tile-major weight-streaming kernel, else 0)
+ *   ln_pending  reduce (S > 0 slabs summed) | plain      S= h_planes= M=
+ *   attention   generic | reg | ds | lds | x6 | x3h      o_planes= B= qlen= kvlen=
+ *   tail        fpl | nofpl (ff.0 stores fp16 planes for ff.3 or not)      S1= S2= M= att_planes=
+ * The log is per handle and off by default; it observes only - nothing is timed, no HIP call is made for it, and the launches and
+ * their arguments are the same with it on or off.  end() turns it off, writes the lines ('\n'-separated, NUL-terminated) into buf
+ * and returns the bytes written, or -1 (NULL arguments, or the text does not fit cap); the records are dropped either way. */
+int mt2_form_log_begin(mt2_model* m);
+int mt2_form_log_end(mt2_model* m, char* buf, int cap);
 int mt2_gemm_config_count(void);
 const char* mt2_gemm_config_name(int idx);
 /* test hook, no device needed: what the GEMM front door (gemm_dispatch.hip) would do with the dense launch M x N x K (taps, dilation,

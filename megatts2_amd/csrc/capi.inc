@@ -1261,6 +1261,37 @@ int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top) {
     std::lock_guard<std::mutex> lk(m->call_mutex);
     return gemm_trace_shapes(m->opts, buf, cap, top);
 }
+// Form log of the AR step wiring (mt2_model::form_log; written by form_note in model_stages.hip): host-side text only
+int mt2_form_log_begin(mt2_model* m) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    std::lock_guard<std::mutex> lk(m->call_mutex);
+    m->form_log.clear();
+    m->form_kind = nullptr;
+    m->form_log_on = true;
+    MT2_API_END
+}
+int mt2_form_log_end(mt2_model* m, char* buf, int cap) {
+    if (!m || !buf || cap <= 0) return -1;
+    std::lock_guard<std::mutex> lk(m->call_mutex);
+    m->form_log_on = false;
+    m->form_kind = nullptr;
+    size_t need = 0;
+    for (const std::string& l : m->form_log) need += l.size() + 1;
+    int off = -1;
+    if (need < (size_t)cap) {
+        off = 0;
+        for (const std::string& l : m->form_log) {
+            std::memcpy(buf + off, l.data(), l.size());
+            off += (int)l.size();
+            buf[off++] = '\n';
+        }
+        buf[off] = 0;
+    }
+    m->form_log.clear();
+    m->form_log.shrink_to_fit();
+    return off;
+}
 int mt2_gemm_config_count(void) { return gemm_num_configs(); }
 const char* mt2_gemm_config_name(int idx) { return gemm_config_name(idx); }
 

@@ -405,13 +405,14 @@ hipError_t launch_gemm(const GemmP& p_in, hipStream_t s, EngineOpts* opts) {
     const EngineOpts& o = opts ? *opts : kDefaults;
     const GemmRoute r = gemm_route(p_in, o);
     if (r.cfg < 0 && r.err == hipSuccess) return hipSuccess;    // nothing to launch
-    if (opts) { opts->last_stat_nt = r.stat_nt; opts->last_stat_w = r.stat_w; }
+    if (opts) { opts->last_stat_nt = r.stat_nt; opts->last_stat_w = r.stat_w; opts->last_sk_nw = 0; }
     if (r.err != hipSuccess) return r.err;
     GemmP p = p_in;
     if (!r.stat_nt) p.stat_out = nullptr;                       // the chosen kernel has no row-statistics epilogue for this launch
     p.stat_nt = r.stat_nt; p.stat_w = r.stat_w;
     if (r.cfg == CFG_SKINNYTM32 || r.cfg == CFG_SKINNYTM64) {
         p.sk_nw = o.skinny_nw;
+        if (opts) opts->last_sk_nw = gemm_skinny_tm_waves(p);
         return traced_launch(opts, r.cfg, p, s, [&] { return launch_gemm_skinny_tm(p, s); });
     }
     if (r.cfg == CFG_SKINNY32 || r.cfg == CFG_SKINNY64) return traced_launch(opts, r.cfg, p, s, [&] { return launch_gemm_skinny(p, s); });

@@ -436,27 +436,36 @@ bool gemm_skinny_tm_eligible(const GemmP& p, int max_rows) {
            pro_ok && p.a_mul >= 1 && (reinterpret_cast<uintptr_t>(p.X) & 15) == 0;
 }
 
+// the waves that split K in the launch below: the one place where GemmP::sk_nw, M, K and the prologue turn into a wave count
+int gemm_skinny_tm_waves(const GemmP& p) {
+    const int kc = p.K >> 6;
+    if (p.sk_nw != 16 || p.M > 48) return 8;
+    if (p.M <= 32) return kc >= 16 ? 16 : (kc == 12 ? 12 : 8);
+    return kc == 12 ? 12 : (kc == 16 && p.pro_act != 3 ? 16 : 8);
+}
+
 hipError_t launch_gemm_skinny_tm(const GemmP& p, hipStream_t s) {
     if (!gemm_skinny_tm_eligible(p, 64)) return hipErrorInvalidValue;
     const bool ln = p.pro_act == 3;
     const int per_wave = ((p.K >> 6) + 7) / 8;          // K chunks of the busiest wave
+    const int nw = gemm_skinny_tm_waves(p);
     // GemmP::sk_nw == 16 (option skinny_nw, default since round 5): SIXTEEN waves split K - four per SIMD, one 64-wide chunk each at
     // K = 1024 (a wave's dependent MFMA chain and its share of the loads halve; the LDS reduction sums 16 slabs in wave order) -
     // or TWELVE when K has only twelve chunks (the ADM's d = 768).  M <= 32 only (registers: 128 / 168 per wave).  Interleaved
     // A/B on the one-utterance path: C1 42.5 -> 41.75 ms (profiles/r05_opts_ab.txt).
-    if (p.sk_nw == 16 && p.M <= 32 && (p.K >> 6) >= 16) {
+    if (nw == 16 && p.M <= 32) {
         if (p.M <= 16) return ln ? sk_tm_launch<1, 1, true, 16>(p, s) : (per_wave > 2 ? sk_tm_launch<1, 2, false, 16>(p, s) : sk_tm_launch<1, 1, false, 16>(p, s));
         return ln ? sk_tm_launch<2, 1, true, 16>(p, s) : (per_wave > 2 ? sk_tm_launch<2, 2, false, 16>(p, s) : sk_tm_launch<2, 1, false, 16>(p, s));
     }
-    if (p.sk_nw == 16 && p.M <= 32 && (p.K >> 6) == 12) {
+    if (nw == 12 && p.M <= 32) {
         if (p.M <= 16) return ln ? sk_tm_launch<1, 1, true, 12>(p, s) : sk_tm_launch<1, 1, false, 12>(p, s);
         return ln ? sk_tm_launch<2, 1, true, 12>(p, s) : sk_tm_launch<2, 1, false, 12>(p, s);
     }
     // three row tiles (the ADM's steps 33 .. 48 of a lone utterance): twelve waves at K = 768 (168 registers per wave); sixteen at
     // K = 1024 for the plain prologue only (128 registers: the LayerNorm form and a second chunk in flight would spill)
-    if (p.sk_nw == 16 && p.M > 32 && p.M <= 48 && (p.K >> 6) == 12)
+    if (nw == 12)
         return ln ? sk_tm_launch<3, 1, true, 12>(p, s) : sk_tm_launch<3, 1, false, 12>(p, s);
-    if (p.sk_nw == 16 && p.M > 32 && p.M <= 48 && (p.K >> 6) >= 16 && (p.K >> 6) <= 16 && !ln) return sk_tm_launch<3, 1, false, 16>(p, s);
+    if (nw == 16) return sk_tm_launch<3, 1, false, 16>(p, s);
     switch ((p.M + 15) / 16) {
         case 1:
             if (ln) return sk_tm_launch<1, 2, true>(p, s);

@@ -9,6 +9,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdarg>
+#include <cstdio>
 #include <cstring>
 #include <numeric>
 
@@ -67,6 +69,26 @@ struct Ctx {
     hipStream_t s;
     Arena& ws;
 };
+
+// One line of the form log (mt2_model::form_log): "kind point form key=value ...".  Written only between mt2_form_log_begin and
+// mt2_form_log_end and only inside ar_step_layers (form_kind set); it records a decision already taken and takes none.
+static void form_kind(const Ctx& c, const char* kind) {      // the layer kind of the entries that follow (nothing is written with the log off)
+    if (c.m.form_log_on) c.m.form_kind = kind;
+}
+struct FormScope {      // ar_step_layers: no kind outlives it, on any exit path - nothing outside the AR steps is logged
+    mt2_model& m;
+    ~FormScope() { m.form_kind = nullptr; }
+};
+static void form_note(const Ctx& c, const char* point, const char* form, const char* fmt = "", ...) {
+    if (!c.m.form_log_on || !c.m.form_kind) return;
+    char buf[256];
+    int n = snprintf(buf, sizeof buf, "%s %s %s ", c.m.form_kind, point, form);
+    va_list ap;
+    va_start(ap, fmt);
+    if (n > 0 && n < (int)sizeof buf) vsnprintf(buf + n, sizeof buf - n, fmt, ap);
+    va_end(ap);
+    c.m.form_log.emplace_back(buf);
+}
 
 // the bf16 planes of a weight pointer, if its buffer has them (mt2_model::planes, sorted by base)
 static void attach_planes(const mt2_model& m, GemmP& p) {
@@ -200,7 +222,11 @@ static void ln_linear(const Ctx& c, const float* x, int ldx, int Rx, int a_mul, 
             // launch_gemm routes to the tile-major kernel only when its own conditions hold too; with another routing the
             // LayerNorm-prologue form may not exist for the tile it picks: fall through like the branches below
             const hipError_t e = launch_gemm(q, c.s, &c.m.opts);
-            if (e == hipSuccess) return;
+            if (e == hipSuccess) {
+                form_note(c, "ln_linear", q.ln_stat ? "skinny-ln-pairs" : "skinny-ln", "M=%d N=%d tile=%s nw=%d", M, N, c.m.opts.last_cfg,
+                          c.m.opts.last_sk_nw);
+                return;
+            }
             if (e != hipErrorNotSupported) MT2_HIP(e);
         }
     }
@@ -214,7 +240,10 @@ static void ln_linear(const Ctx& c, const float* x, int ldx, int Rx, int a_mul, 
         q.pro_act = 5; q.W = w.Wl; q.bias = w.c; q.ln_g = w.s; q.ln_stat = st->stat; q.ln_nt = st->stat_nt; q.ln_w = st->stat_w;
         attach_planes(c.m, q);
         const hipError_t e = launch_gemm(q, c.s, &c.m.opts);
-        if (e == hipSuccess) return;
+        if (e == hipSuccess) {
+            form_note(c, "ln_linear", "pair-fed", "M=%d N=%d tile=%s nw=0", M, N, c.m.opts.last_cfg);
+            return;
+        }
         if (e != hipErrorNotSupported) MT2_HIP(e);
     }
     const bool planes = linear_takes_planes(c, h_scratch, K, M, w.W, w.bias, N, K, y, ldy, epi_act);
@@ -223,6 +252,7 @@ static void ln_linear(const Ctx& c, const float* x, int ldx, int Rx, int a_mul, 
     q.M = M; q.C = K; q.eps = 1e-5f; q.act = ACT_NONE; q.out_planes = planes ? 1 : 0; q.x3h_flag = c.m.opts.x3h_flag;
     MT2_HIP(launch_layernorm(q, c.s));
     linear(c, h_scratch, K, M, w.W, w.bias, N, K, y, ldy, nullptr, 0, nullptr, epi_act, planes, c_planes);
+    form_note(c, "ln_linear", planes ? "plain+planes" : "plain", "M=%d N=%d tile=%s nw=%d", M, N, c.m.opts.last_cfg, c.m.opts.last_sk_nw);
 }
 static LnOps ln1_qkv(const EncLayerW& w, int d, int n0 = 0) {
     return ln_ops(w.ln1g, w.ln1b, w.wqkv, w.bqkv, w.wqkv_l, w.sqkv, w.cqkv, n0, d);
@@ -384,6 +414,14 @@ static AttnP attn_params(const Ctx& c, int H, int D) {
     return a;
 }
 static AttnP attn_params(const Ctx& c, const EncW& e) { return attn_params(c, e.heads, e.d / e.heads); }
+// form log: the kernel attn_route chose for a launch just made
+static void form_note_attention(const Ctx& c, const AttnP& a) {
+    if (!c.m.form_log_on || !c.m.form_kind) return;
+    static const char* const kName[] = {"none", "generic", "reg", "ds", "lds", "x6", "x3h"};
+    const int k = attn_route(a).kernel;
+    form_note(c, "attention", k >= 0 && k <= ATTN_X3H ? kName[k] : "?", "o_planes=%d B=%d qlen=%d kvlen=%d", a.o_planes, a.B, a.max_qlen,
+              a.u_kvlen);
+}
 static void attention_self(const Ctx& c, const EncW& e, const AttnGeom& g, const float* qkv, float* att, bool o_planes = false) {
     AttnP a = attn_params(c, e);
     a.o_planes = o_planes ? 1 : 0;
@@ -394,6 +432,7 @@ static void attention_self(const Ctx& c, const EncW& e, const AttnGeom& g, const
     a.u_qstride = g.u_stride; a.u_qlen = g.u_len; a.u_kvstride = g.u_stride; a.u_kvlen = g.u_len;
     a.B = g.B; a.max_qlen = g.max_len; a.max_kvlen = g.max_len;
     MT2_HIP(launch_attention(a, c.s));
+    form_note_attention(c, a);
 }
 static void encoder_layer(const Ctx& c, const EncW& e, const EncLayerW& w, float* x, int M, const AttnGeom& g,
                           const int* valid, const EncScratch& s) {
@@ -468,6 +507,8 @@ static void linear_splitk(const Ctx& c, const float* x, int ldx, int M, const fl
     GemmP p = splitk_params(x, ldx, M, W, N, K, S, parts);
     p.a_planes = a_planes ? 1 : 0;
     gemm(c, p);
+    form_note(c, "residual", "split", "S=%d stat_nt=0 stat_w=0 a_planes=%d M=%d K=%d tile=%s nw=%d", S, p.a_planes, M, K, c.m.opts.last_cfg,
+              c.m.opts.last_sk_nw);
 }
 // h = LayerNorm(x) after applying a pending update to x (in place)
 static void ln_pending(const Ctx& c, float* x, int d, int M, const Pending& in, const float* g, const float* b,
@@ -477,6 +518,7 @@ static void ln_pending(const Ctx& c, float* x, int d, int M, const Pending& in, 
         q.x = x; q.ldx = d; q.gamma = g; q.beta = b; q.out = h; q.ldo = d; q.M = M; q.C = d; q.eps = 1e-5f; q.act = ACT_NONE;
         q.out_planes = h_planes ? 1 : 0; q.x3h_flag = c.m.opts.x3h_flag;
         MT2_HIP(launch_layernorm(q, c.s));
+        form_note(c, "ln_pending", "plain", "S=0 h_planes=%d M=%d", q.out_planes, M);
         return;
     }
     LnReduceP p{};
@@ -484,6 +526,7 @@ static void ln_pending(const Ctx& c, float* x, int d, int M, const Pending& in, 
     p.gamma = g; p.beta = b; p.xout = x; p.ldx = d; p.hout = h; p.ldh = d; p.M = M; p.C = d; p.eps = 1e-5f;
     p.h_planes = h_planes ? 1 : 0; p.x3h_flag = c.m.opts.x3h_flag;
     MT2_HIP(launch_ln_reduce(p, c.s));
+    form_note(c, "ln_pending", "reduce", "S=%d h_planes=%d M=%d", in.S, p.h_planes, M);
 }
 // h = LN(x (+ the pending split-K update)), y = act(h W^T + b): h travels as fp16 planes when the GEMM takes them
 static void ln_pending_linear(const Ctx& c, float* x, int d, int M, const Pending& in, const float* g, const float* b, float* h,
@@ -516,6 +559,8 @@ static Pending linear_residual(const Ctx& c, const float* a, int lda, int M, con
     gemm(c, p);
     Pending r{};
     if (want && c.m.opts.last_stat_nt > 0) { r.stat = stat; r.stat_nt = c.m.opts.last_stat_nt; r.stat_w = c.m.opts.last_stat_w; }
+    form_note(c, "residual", r.stat ? "stat" : "nostat", "S=1 stat_nt=%d stat_w=%d a_planes=%d M=%d K=%d tile=%s nw=%d", r.stat_nt, r.stat_w,
+              p.a_planes, M, K, c.m.opts.last_cfg, c.m.opts.last_sk_nw);
     return r;
 }
 // K slices of the two residual GEMMs of an AR layer (out-projection K = d, ff.3 K = ff)
@@ -558,6 +603,7 @@ static Pending ar_layer_tail(const Ctx& c, const EncW& e, const EncLayerW& w, fl
                                 : residual_params(c, s.f, e.ff, M, w.ff1w, w.ff1b, d, e.ff, x, s.stat, nullptr, 0);
         fpl = gemm_writes_planes(planned(c, q0), c.m.opts) && gemm_takes_planes(planned(c, q3), c.m.opts);
     }
+    form_note(c, "tail", fpl ? "fpl" : "nofpl", "S1=%d S2=%d M=%d att_planes=%d", S1, S2, M, att_planes ? 1 : 0);
     if (S1 > 1) {
         linear_splitk(c, att, d, M, w.wo, d, d, S1, s.parts, att_planes);
         Pending p1{s.parts, (long long)M * d, S1, w.bo};
@@ -578,6 +624,7 @@ static Pending encoder_layer_ar(const Ctx& c, const EncW& e, const EncLayerW& w,
                                 const EncScratch& s, const Pending& in) {
     MT2_REQUIRE(!e.conv_ff, "AR step layers use the Linear feed-forward");
     const int d = e.d;
+    form_kind(c, "mid");
     if (in.S) {
         ln_pending_linear(c, x, d, M, in, w.ln1g, w.ln1b, s.h, w.wqkv, w.bqkv, 3 * d, s.qkv, 3 * d);
     } else {
@@ -604,6 +651,7 @@ static void encoder_layer_last(const Ctx& c, const EncW& e, const EncLayerW& w, 
         // a handful of rows (one utterance's steps): Q | K | V of ALL rows in ONE weight-streaming launch - the Q rows that
         // are not the last of their sequence cost nothing measurable at M <= 64, a second launch costs ~8 us
         float* qkv = s.qkv;                              // [M, 3d]
+        form_kind(c, "last-skinny");
         if (in.S) {
             ln_pending(c, x, d, M, in, w.ln1g, w.ln1b, s.h);
             linear(c, s.h, d, M, w.wqkv, w.bqkv, 3 * d, d, qkv, 3 * d);
@@ -614,6 +662,7 @@ static void encoder_layer_last(const Ctx& c, const EncW& e, const EncLayerW& w, 
         a.K = qkv + d; a.ldk = 3 * d; a.V = qkv + 2 * d; a.ldv = 3 * d;
         a.u_ostride = 1;
     } else if (in.S) {
+        form_kind(c, "last-split");
         ln_pending(c, x, d, M, in, w.ln1g, w.ln1b, s.h);
         linear(c, s.h, d, M, w.wqkv + (size_t)d * d, w.bqkv + d, 2 * d, d, kv, 2 * d);
         GemmP p{};
@@ -621,6 +670,7 @@ static void encoder_layer_last(const Ctx& c, const EncW& e, const EncLayerW& w, 
         p.C = q; p.ldc = d; p.M = A; p.N = d;
         gemm(c, p);
     } else {   // LN1 fused into both consumers: K|V of all rows, Q of the last row of each sequence
+        form_kind(c, "last-fused");
         ln_linear(c, x, d, M, 1, 0, M, ln1_qkv(w, d, d), 2 * d, d, kv, 2 * d, s.h, ACT_NONE, &in);
         ln_linear(c, x, d, M, n, n - 1, A, ln1_qkv(w, d), d, d, q, d, s.f, ACT_NONE, &in);
     }
@@ -631,6 +681,7 @@ static void encoder_layer_last(const Ctx& c, const EncW& e, const EncLayerW& w, 
     a.O = att; a.ldo = d;
     a.u_qlen = 1; a.u_kvstride = n; a.u_kvlen = n; a.B = A; a.max_qlen = 1;
     MT2_HIP(launch_attention(a, c.s));
+    form_note_attention(c, a);
     // y = x[last rows] + out_proj(att): the residual rows sit n*d floats apart starting at row n-1
     const Pending py = linear_residual(c, att, d, A, w.wo, w.bo, d, d, y, s.stat, x + (size_t)(n - 1) * d, n * d);
     ln_linear(c, y, d, A, 1, 0, A, ln2_ff0(w, d), e.ff, d, s.f, e.ff, s.h, ACT_RELU, &py);   // LN2 -> ff.0
@@ -645,6 +696,7 @@ static Pending encoder_layer_first_cached(const Ctx& c, const EncW& e, const Enc
                                           float* qkv_cache, int cs, const EncScratch& s, bool fill_all) {
     MT2_REQUIRE(!e.conv_ff, "AR step layers use the Linear feed-forward");
     const int d = e.d, M = A * n;
+    form_kind(c, fill_all && n > 1 ? "first-fill" : "first-incr");
     if (fill_all && n > 1) {
         // first step of a run that starts from a forced history (prompt prefix, teacher-forced tests): the cache
         // has no rows yet - LN1 -> QKV of ALL n rows, compact, then one strided copy into the cache layout
@@ -663,6 +715,7 @@ static Pending encoder_layer_first_cached(const Ctx& c, const EncW& e, const Enc
     const bool opl = ar_outproj_takes_planes(c, e, w, x, M, s.att, s);
     a.o_planes = opl ? 1 : 0;
     MT2_HIP(launch_attention(a, c.s));
+    form_note_attention(c, a);
     return ar_layer_tail(c, e, w, x, M, s.att, s, opl);
 }
 
@@ -671,6 +724,7 @@ static Pending encoder_layer_first_cached(const Ctx& c, const EncW& e, const Enc
 static const float* ar_step_layers(const Ctx& c, const EncW& e, float* x, int n, int A, float* qkv_cache, int cs,
                                    const EncScratch& sc, float* ylast, bool fill_cache = false) {
     const int L = (int)e.layers.size();
+    const FormScope form_scope{c.m};
     AttnGeom g;
     g.u_stride = n; g.u_len = n; g.B = A; g.max_len = n;
     Pending pend;

@@ -144,6 +144,7 @@ struct EngineOpts {
     std::vector<TraceRec> trace;
     const char* last_cfg = "";   // name of the tile configuration the last launch used
     int last_stat_nt = 0, last_stat_w = 0;   // GemmP::stat_out of the last launch: pairs per row / columns per pair (0: none written)
+    int last_sk_nw = 0;          // waves that split K in the last launch, if it ran on the tile-major weight-streaming kernel (else 0)
     int ln_pairs = 0;            // (the value in force for the stage that is running: ln_pairs_adm inside the ADM, 0 elsewhere)
     int ln_pairs_adm = 2;        // ADM layers with more than skinny_rows rows: the residual GEMMs (out-projection, ff.3) write row statistics
                                  // as (mean, M2) pairs per wave tile in their epilogue and LN1 -> QKV / LN2 -> ff.0 run as ONE pair-fed
@@ -227,6 +228,7 @@ hipError_t launch_gemm_skinny(const GemmP& p, hipStream_t s);
 // ... on a tile-major weight copy (GemmP::Wtm), optionally with the LayerNorm prologue (pro_act == 3, groups == 1, K <= 1024)
 bool gemm_skinny_tm_eligible(const GemmP& p, int max_rows);
 hipError_t launch_gemm_skinny_tm(const GemmP& p, hipStream_t s);
+int gemm_skinny_tm_waves(const GemmP& p);      // the waves that split K in that launch: 8, 12 or 16 (GemmP::sk_nw, M, K, prologue)
 hipError_t launch_tile_major(const float* W, int N, int K, float* out, hipStream_t s);   // row-major [N, K] -> tile-major blocks
 int gemm_num_configs();
 const char* gemm_config_name(int idx);

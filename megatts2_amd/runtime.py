@@ -676,6 +676,28 @@ class NativeModel:
         return [{"config": names[i].decode(), "launches": int(launches[i]), "flops": float(flops[i]), "ms": float(ms[i])}
                 for i in range(n)]
 
+    def form_log_begin(self) -> None:
+        """Start recording the decisions of the AR step wiring (mt2_form_log_begin): observation only, off by default."""
+        _check(self.lib.mt2_form_log_begin(self.h))
+
+    def form_log_end(self):
+        """-> list of tuples (kind, point, form, attrs) in call order since form_log_begin(): the layer kind (first-fill, first-incr,
+        mid, last-skinny, last-split, last-fused), the decision point (ln_linear, residual, ln_pending, attention, tail), the form
+        taken there and a dict of the entry's key=value fields (ints where they parse as ints) - include/megatts2_hip.h."""
+        buf = C.create_string_buffer(1 << 20)
+        n = self.lib.mt2_form_log_end(self.h, buf, len(buf))
+        if n < 0:
+            raise NativeError("form log failed (or longer than the buffer)")
+        out = []
+        for line in buf.value.decode().splitlines():
+            kind, point, form, *kv = line.split()
+            attrs = {}
+            for item in kv:
+                k, v = item.split("=", 1)
+                attrs[k] = int(v) if v.lstrip("-").isdigit() else v
+            out.append((kind, point, form, attrs))
+        return out
+
     def set_profiling(self, on: bool) -> None:
         _check(self.lib.mt2_set_profiling(self.h, 1 if on else 0))
 

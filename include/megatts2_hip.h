@@ -800,8 +800,9 @@ int mt2_gemm_trace_end(mt2_model* m, int cap, const char** names, int64_t* launc
 /* text table "config M N K groups launches ms tflops" of the traced launches grouped by shape, slowest first;
  * call BEFORE mt2_gemm_trace_end (which frees the records); returns the bytes written or -1 */
 int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top);
-/* Form log of the autoregressive step wiring (tests).  Between begin and end every decision the step layers of the ADM / PLM take
- * (csrc/model_stages.hip, ar_step_layers) is recorded as one text line, in call order:
+/* Form log of the autoregressive step wiring and of the vocoder wiring (tests).  Between begin and end every decision the step layers
+ * of the ADM / PLM (csrc/model_stages.hip, ar_step_layers) and the HiFi-GAN generator (hifigan_rows) take is recorded as one text line,
+ * in call order:
  *     <kind> <point> <form> key=value ...
  *   kind   the layer that issued it: first-fill, first-incr, mid, last-skinny, last-split, last-fused
  *   ln_linear   skinny-ln | skinny-ln-pairs | pair-fed | plain | plain+planes      M= N= tile= nw=
@@ -810,6 +811,15 @@ int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top);
  *   ln_pending  reduce (S > 0 slabs summed) | plain      S= h_planes= M=
  *   attention   generic | reg | ds | lds | x6 | x3h      o_planes= B= qlen= kvlen=
  *   tail        fpl | nofpl (ff.0 stores fp16 planes for ff.3 or not)      S1= S2= M= att_planes=
+ * and of the vocoder (ch: channels, R: rows of the stage, tile: the configuration name of the launch):
+ *   kind   voc-pre, voc-stage<i> (upsampler i and its three resblocks), voc-post
+ *   pre         gemm (conv_pre)      ch= R= tile=
+ *   upsample    halves (one entry per GEMM half: half=) | fused (MRF mean + upsampler as one launch)      ch= R= tile=
+ *   mean        avg3 | in-upsample | in-post: where the mean of the stage's three resblocks is formed      ch= R=
+ *   pair        fused | two (tile / tile2: the first and second convolution)      j= n= ch= k= dil= R= tile= [tile2=]
+ *   halo        fill (reflect edge mode: one entry per halo fill)      width= G=
+ *   streams     1 | 3: the streams the stage's three resblock chains run on      ch= R=
+ *   post        fused (mean + conv_post + tanh as one launch) | gemm      ch= k= R= tile=
  * The log is per handle and off by default; it observes only - nothing is timed, no HIP call is made for it, and the launches and
  * their arguments are the same with it on or off.  end() turns it off, writes the lines ('\n'-separated, NUL-terminated) into buf
  * and returns the bytes written, or -1 (NULL arguments, or the text does not fit cap); the records are dropped either way. */

@@ -237,6 +237,29 @@ int mt2_workspace_reserve(mt2_model* m, size_t bytes) {
     MT2_API_END
 }
 
+// Gap rows between the utterances of a vocoder batch, at the mel level.  A zero-padded "same" convolution of one utterance has to read
+// zeros behind its ends, never a neighbour's rows: at every stage the gap - times the rows per mel frame there - covers the stage's
+// widest halo, (k - 1) / 2 x dilation; the reflect edge mode (speechbrain) keeps TWO halos in every gap.  Never less than the 4 / 8
+// rows of the production generator (x8 first: conv_pre k7 3 mel rows, stage 0 25 rows of 8, stage 1 25 of 64), so its row layout is
+// what it always was; a generator whose first rate is small (x2: 25 rows of 2) gets the 13 rows it needs instead of its
+// neighbours' samples.
+static int vocoder_gap(const mt2_model& m) {
+    const mt2_config& cfg = m.cfg;
+    const long long halos = cfg.hg_reflect_pad ? 2 : 1;
+    long long gap = cfg.hg_reflect_pad ? 8 : 4, scale = 1;
+    const auto need = [&](long long halo) { gap = std::max(gap, (halos * halo + scale - 1) / scale); };
+    need((m.hg_pre.k - 1) / 2);
+    for (int i = 0; i < cfg.hg_n_up; ++i) {
+        scale *= cfg.hg_up_rates[i];
+        for (int j = 0; j < cfg.hg_n_res && (size_t)(i * cfg.hg_n_res + j) < m.hg_res.size(); ++j) {
+            const ResW& r = m.hg_res[(size_t)i * cfg.hg_n_res + j];
+            for (int n = 0; n < 3; ++n) need((long long)(r.k - 1) / 2 * r.dil[n]);
+        }
+    }
+    need((m.hg_post.k - 1) / 2);
+    return (int)gap;
+}
+
 // Upper bound of the arena bytes one mt2_synthesize_batch call of this geometry takes (every utterance at the
 // maxima).  Mirrors the allocations of the stage drivers; tests/test_gpu_stages.py checks bound >= high-water.
 int mt2_workspace_query(const mt2_model* m, int B, int Np_max, int Tp_max, int Tm_cap, int flags, size_t* bytes) {
@@ -280,7 +303,7 @@ int mt2_workspace_query(const mt2_model* m, int B, int Np_max, int Tp_max, int T
     }
     if (flags & MT2_RUN_VOCODER) {
         const long long pad = cfg.hg_inference_padding;
-        long long R = rows(Tm_cap + 2 * pad, cfg.hg_reflect_pad ? 8 : 4), ch = cfg.hg_init_channels;
+        long long R = rows(Tm_cap + 2 * pad, vocoder_gap(*m)), ch = cfg.hg_init_channels;
         f += 4 * R + R * cfg.mel_bins + R * ch;
         for (int i = 0; i < cfg.hg_n_up; ++i) {
             R *= cfg.hg_up_rates[i];
@@ -618,9 +641,7 @@ static VocRows vocoder_rows(const Ctx& c, const std::vector<int>& first, const i
     for (int b = 0; b < B; ++b) plen[b] = lens[b] + 2 * pad;
     IntPlan ip;
     VocRows v;
-    // gap rows between utterances at the mel level: 4 cover the zero-padded dilated convs (x hop per stage); the reflect
-    // edge mode (speechbrain) keeps TWO halos in every gap (conv_pre k7: 2 x 3 mel rows; stage 1: 2 x 25 of 64 rows)
-    v.M0 = make_rows(plen.data(), B, cfg.hg_reflect_pad ? 8 : 4);
+    v.M0 = make_rows(plen.data(), B, vocoder_gap(c.m));
     const RowPlanOffsets o = plan_rows(ip, v.M0);
     const int o_src = ip.add(padded_src(v.M0, first, lens, pad));
     ip.upload(c.ws, c.m.pinned(), c.s);
@@ -1261,7 +1282,7 @@ int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top) {
     std::lock_guard<std::mutex> lk(m->call_mutex);
     return gemm_trace_shapes(m->opts, buf, cap, top);
 }
-// Form log of the AR step wiring (mt2_model::form_log; written by form_note in model_stages.hip): host-side text only
+// Form log of the AR step and vocoder wiring (mt2_model::form_log; written by form_note in model_stages.hip): host-side text only
 int mt2_form_log_begin(mt2_model* m) {
     MT2_API_BEGIN
     MT2_REQUIRE(m != nullptr, "null model handle");

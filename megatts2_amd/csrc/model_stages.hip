@@ -71,11 +71,11 @@ struct Ctx {
 };
 
 // One line of the form log (mt2_model::form_log): "kind point form key=value ...".  Written only between mt2_form_log_begin and
-// mt2_form_log_end and only inside ar_step_layers (form_kind set); it records a decision already taken and takes none.
+// mt2_form_log_end and only inside ar_step_layers and hifigan_rows (form_kind set); it records a decision already taken and takes none.
 static void form_kind(const Ctx& c, const char* kind) {      // the layer kind of the entries that follow (nothing is written with the log off)
     if (c.m.form_log_on) c.m.form_kind = kind;
 }
-struct FormScope {      // ar_step_layers: no kind outlives it, on any exit path - nothing outside the AR steps is logged
+struct FormScope {      // ar_step_layers, hifigan_rows: no kind outlives it, on any exit path - nothing outside them is logged
     mt2_model& m;
     ~FormScope() { m.form_kind = nullptr; }
 };
@@ -1437,7 +1437,8 @@ static VqpeResult vqpe_rows(const Ctx& c, IntPlan& ip, const float* mel, int mel
 }
 
 // ---------------------------------------------------------------------------------------------------
-// HiFi-GAN V1 generator on mel rows [M0.R, in_dim] (gap 4) -> waveform rows [M0.R * hop] (1 channel, tanh'ed)
+// HiFi-GAN V1 generator on mel rows [M0.R, in_dim] -> waveform rows [M0.R * hop] (1 channel, tanh'ed).  The gap between utterances is
+// vocoder_gap's (capi.inc): 4 mel rows for the production generator, 8 in reflect mode
 
 static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
     mt2_model& m = c.m;
@@ -1458,13 +1459,19 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
         MT2_REQUIRE((long long)min_len * scale > G, "reflect padding must be smaller than the utterance (as F.pad raises): "
                                                     "utterance too short for the vocoder's reflect-padded convolutions");
         MT2_HIP(launch_fill_reflect(buf, width, width, M0.d_start, M0.d_len, M0.B, scale, G, cc.s));
+        form_note(cc, "halo", "fill", "width=%d G=%d", width, G);
     };
+    // form log (tests): kinds voc-pre, voc-stage<i>, voc-post; the MRF mean is booked on the stage whose resblocks it averages
+    char kind[24];
+    const FormScope form_scope{m};
+    form_kind(c, "voc-pre");
     float* x = c.ws.get<float>((size_t)R * ch);
     if (reflect) {      // conv_pre reads its input in place: mirror the mel rows first (the rows are ours: a packed copy)
         MT2_REQUIRE((cfg.hg_in_dim & 3) == 0, "reflect padding needs a mel width that is a multiple of 4");
         halo(c, const_cast<float*>(xmel), cfg.hg_in_dim, (m.hg_pre.k - 1) / 2);
     }
     conv_same(c, xmel, cfg.hg_in_dim, (int)R, m.hg_pre, x, ch, M0.d_valid);
+    form_note(c, "pre", "gemm", "ch=%d R=%lld tile=%s", ch, R, m.opts.last_cfg);
     const int* valid = M0.d_valid;
     const float* const* mrf = nullptr;        // the previous stage's three resblock outputs while their mean has not been formed yet
     float* rb[3] = {nullptr, nullptr, nullptr};
@@ -1483,8 +1490,12 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
                 x = c.ws.get<float>((size_t)R * ch);
                 MT2_HIP(launch_avg3(mrf[0], mrf[1], mrf[2], 1.0f / 3.0f, x, R * ch, c.s));
             }
+            form_note(c, "mean", fused ? "in-upsample" : "avg3", "ch=%d R=%lld", ch, R);
             mrf = nullptr;
         }
+        snprintf(kind, sizeof kind, "voc-stage%d", i);
+        form_kind(c, kind);
+        if (fused) form_note(c, "upsample", "fused", "ch=%d R=%lld tile=%s", ch, R, m.opts.last_cfg);
         for (int half = 0; half < 2 && !fused; ++half) {
             GemmP p{};
             p.X = x; p.ldx = ch; p.Rx = (int)R; p.taps = 2; p.shift0 = half == 0 ? -1 : 0; p.Cin = ch;
@@ -1492,6 +1503,7 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
             p.C = up + (half == 0 ? 0 : hs * co); p.ldc = s * co; p.M = (int)R; p.N = hs * co;
             p.pro_act = ACT_LRELU; p.pro_slope = slope;
             gemm(c, p);
+            form_note(c, "upsample", "halves", "half=%d ch=%d R=%lld tile=%s", half, ch, R, m.opts.last_cfg);
         }
         int* v2 = c.ws.get<int>((size_t)R * s);
         MT2_HIP(launch_expand_mask(valid, s, v2, R * s, c.s));
@@ -1506,6 +1518,11 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
         MT2_REQUIRE(cfg.hg_n_res == 3, "HiFi-GAN V1 uses three resblocks per stage");
         const int nside = m.opts.voc_streams > 1 ? 2 : 0;
         ensure_aux(m, nside);
+        form_note(c, "streams", nside ? "3" : "1", "ch=%d R=%lld", ch, R);
+        for (int j = 0; j < 3; ++j)      // zero padding IS the gap: no convolution of the stage may reach across it into a neighbour
+            for (int n = 0; n < 3 && !reflect; ++n)
+                MT2_REQUIRE((long long)(m.hg_res[i * 3 + j].k - 1) / 2 * m.hg_res[i * 3 + j].dil[n] <= (long long)M0.G * scale || M0.B < 2,
+                            "the gap between utterances is narrower than a resblock convolution's halo");
         if (reflect) {     // the three chains share `up`: one halo wide enough for the widest first convolution, before the fork
             int g0 = 0;
             for (int j = 0; j < 3; ++j) g0 = std::max(g0, (m.hg_res[i * 3 + j].k - 1) / 2 * m.hg_res[i * 3 + j].dil[0]);
@@ -1532,12 +1549,16 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
                 // ... and both convolutions as ONE launch where conv_pair_route takes the pair (option pair_fuse): t1 never leaves
                 // the workgroup's LDS.  Bit-identical; NotSupported keeps the two launches below
                 if (m.opts.pair_fuse && conv_pair(cj, h, ch, (int)R, r.c1[n], r.c2[n], r.dil[n], slope, reflect, out, valid)) {
+                    form_note(cj, "pair", "fused", "j=%d n=%d ch=%d k=%d dil=%d R=%lld tile=%s", j, n, ch, r.k, r.dil[n], R, m.opts.last_cfg);
                     h = out;
                     continue;
                 }
                 conv_same(cj, h, ch, (int)R, r.c1[n], t1, ch, valid, ACT_LRELU, slope, ACT_LRELU, nullptr, 0, r.dil[n]);
+                const char* tile1 = m.opts.last_cfg;
                 halo(cj, t1, ch, (r.k - 1) / 2);
                 conv_same(cj, t1, ch, (int)R, r.c2[n], out, ch, valid, ACT_NONE, slope, ACT_NONE, h, ch, 1);
+                form_note(cj, "pair", "two", "j=%d n=%d ch=%d k=%d dil=%d R=%lld tile=%s tile2=%s", j, n, ch, r.k, r.dil[n], R, tile1,
+                          m.opts.last_cfg);
                 h = out;
             }
         }
@@ -1551,7 +1572,12 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
             float* wav = c.ws.get<float>((size_t)R);
             const hipError_t e = launch_conv_post(rb[0], rb[1], rb[2], 1.0f / 3.0f, R, ch, m.hg_post.k, m.hg_post.w,
                                                   m.hg_post.b, 0.01f, valid, wav, c.s);
-            if (e == hipSuccess) return wav;
+            if (e == hipSuccess) {
+                form_note(c, "mean", "in-post", "ch=%d R=%lld", ch, R);
+                form_kind(c, "voc-post");
+                form_note(c, "post", "fused", "ch=%d k=%d R=%lld tile=conv_post", ch, m.hg_post.k, R);
+                return wav;
+            }
             if (e != hipErrorNotSupported) MT2_HIP(e);      // not supported (LDS): the two-launch form below
         }
         if (i + 1 < cfg.hg_n_up) {     // the next stage's upsampler is the mean's only consumer: it may form it itself
@@ -1560,10 +1586,13 @@ static float* hifigan_rows(const Ctx& c, const float* xmel, const RowSet& M0) {
         }
         x = c.ws.get<float>(per);
         MT2_HIP(launch_avg3(rb[0], rb[1], rb[2], 1.0f / 3.0f, x, (long long)per, c.s));
+        form_note(c, "mean", "avg3", "ch=%d R=%lld", ch, R);
     }
+    form_kind(c, "voc-post");
     float* wav = c.ws.get<float>((size_t)R);
     halo(c, x, ch, (m.hg_post.k - 1) / 2);
     conv_same(c, x, ch, (int)R, m.hg_post, wav, 1, valid, ACT_LRELU, 0.01f, ACT_TANH);
+    form_note(c, "post", "gemm", "ch=%d k=%d R=%lld tile=%s", ch, m.hg_post.k, R, m.opts.last_cfg);
     return wav;
 }
 

@@ -36,6 +36,11 @@ def main() -> None:
                     help="print the duration moments of the output and, when a vocoder produced audio, one line per phone (frames, voiced frames, "
                          "mean Hz, semitones above 55 Hz, energy in dB; F0 by --pitch-tracker) and the DTW pitch-contour distance between the "
                          "first prompt and the generated audio")
+    ap.add_argument("--output-lufs", type=float,
+                    help="bring the vocoded prompt and the generated audio each to this integrated loudness (ITU-R BS.1770, e.g. -23) before they are written")
+    ap.add_argument("--peak-ceiling", type=float, default=0.0, help="with --output-lufs: cap the gain so that the sample peak stays at or below this (e.g. 0.99)")
+    ap.add_argument("--report-loudness", action="store_true",
+                    help="print integrated LUFS, sample peak in dBFS and block counts (measured on the GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
     ap.add_argument("--text")
     ap.add_argument("--phones", help="comma separated phone token ids (bypasses the G2P)")
     ap.add_argument("--out", default="test.wav")
@@ -54,9 +59,26 @@ def main() -> None:
     tts.eval()
     phones = [int(v) for v in a.phones.split(",")] if a.phones else None
     gl = {"n_iter": a.gl_iters} if a.vocoder == "griffin-lim" else None
-    mel, lens, aux = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl)
+    mel, lens, aux = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl, loudness_lufs=a.output_lufs,
+                         peak_ceiling=a.peak_ceiling)
     wrote = gl is not None or tts.hifi_gan is not None
     print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
+    if a.report_loudness:
+        import glob
+        import math
+        from megatts2_amd import audio_io
+        path = sorted(glob.glob(f"{a.wavs_dir}/*.wav"))[0]
+        y, sr = audio_io.read_wav(path)
+        report = [(f"first prompt ({path}, as the file holds it)", M.measure_loudness(y, sr))]
+        if wrote:          # the generated audio alone, as the vocoder (and --output-lufs) left it on the device - not the written file
+            n = (int(lens[0]) - 1) * C.HIFIGAN_HOP_LENGTH if gl is not None else (int(lens[0]) + 2 * tts.hifi_gan.cfg.inference_padding) * tts.hifi_gan.cfg.hop
+            report.append(("generated audio", M.measure_loudness(aux["wav"][:1], C.HIFIGAN_SR, lens=[n])))
+        for what, st in report:
+            pk = float(st["sample_peak"][0])
+            print(f"loudness of the {what}: {float(st['integrated_lufs'][0]):.2f} LUFS integrated, sample peak "
+                  f"{20 * math.log10(pk) if pk > 0 else float('-inf'):.2f} dBFS, {int(st['blocks'][0])} blocks of 400 ms, "
+                  f"{int(st['blocks_over_absolute_gate'][0])} over -70 LUFS, {int(st['blocks_over_both_gates'][0])} over the relative gate at "
+                  f"{float(st['relative_gate_lufs'][0]):.2f} LUFS")
     if a.report_pitch:
         import glob
         from megatts2_amd import audio_io

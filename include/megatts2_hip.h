@@ -512,6 +512,61 @@ int mt2_phone_prosody(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/
 int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/, const int32_t* frame_lens /*host*/, int T_max, int B,
                       int center, float* st /*[B, T_max]*/, int32_t* n_voiced /*[B]*/, int32_t* index /*or NULL*/);
 
+/* ---- Integrated loudness and loudness normalisation (csrc/loudness.hip): ITU-R BS.1770-4 gated loudness, which EBU R 128 builds on, of
+ * a ragged batch of mono utterances, and each utterance brought to a target loudness by one gain.  No reference counterpart (the
+ * reference peak-normalises its prompts, models/megatts2.py:336, and leaves the output level alone).  Parity with pyloudnorm /
+ * libebur128 is unpinned - neither is on hand; the kernels are held to the standard's own figures (a full-scale 997 Hz sine at 48 kHz
+ * reads -3.01 LKFS), to the analytic steady-state reading of a sine, and to the float64 restatement tests/loudness_ref.py.  True peak
+ * (4x oversampled) and loudness range (EBU Tech 3342) are out of scope.  THE RULE, for one utterance x f32 [L] at sample_rate:
+ *  1 sample_rate is a multiple of 10 in [8000, 192000], never rounded.  h = sample_rate / 10 (the 100 ms sub-block);  ns = L / h
+ *    complete sub-blocks;  nb = max(0, ns - 3) blocks of 400 ms with 75 % overlap - only blocks wholly inside the signal count.
+ *  2 K-weighting coefficients in double from the analogue prototypes (at 48 kHz they reproduce the standard's table to 1e-13):
+ *    shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196;  K = tan(pi f0 / sr), Vh = 10^(G / 20),
+ *               Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2;  b = (Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0,
+ *               (Vh - Vb K / Q + K^2) / a0;  a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0
+ *    high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773, K and a0 as above;  b = 1, -2, 1;  a1, a2 as above
+ *  3 The shelf, then the high-pass, each in transposed direct form II in double:  y = b0 v + s1;  s1 = b1 v - a1 y + s2;
+ *    s2 = b2 v - a2 y.  Zero state in front of sample 0;  the input is (double)x[i];  a sample at or beyond L is never read.  (The
+ *    high-pass has a double pole at radius 0.985 at 16 kHz, 0.995 at 48 kHz: a direct form in f32 loses the low band.)  The device
+ *    runs the recurrence in chunks of h samples - from zero state, the states carried by M = A^h, then again from the true entry
+ *    state - which is exact up to rounding (1e-13 relative in the sub-block sums).
+ *  4 S[j] = sum of y[i]^2 over sub-block j;  z[k] = (((S[k] + S[k+1]) + S[k+2]) + S[k+3]) / (4 h);  l[k] = -0.691 + 10 log10 z[k]
+ *    (-inf for z = 0).  Gamma = -0.691 + 10 log10(mean of z over l > -70) - 10;  I = -0.691 + 10 log10(mean of z over l > -70 and
+ *    l > Gamma);  no block over the absolute gate (nb = 0, silence): I = Gamma = -inf.  A block is over a gate unless l <= gate, so
+ *    a NaN block counts.  Means are taken in a fixed order of the block index: partial sums over k = i, i + 256, ... ascending for
+ *    i < 256, then a halving tree.
+ *  5 stats f64 [8] per utterance:  0 I   1 nb   2 blocks over the absolute gate   3 blocks over both gates   4 Gamma
+ *    5 sample peak max |x[i]| over i < L (a NaN sample is passed over)   6 max_k l[k] (-inf for nb = 0)   7 the linear gain of 6
+ *    (1 for the measuring call).  momentary f64 [NB_max]: l[k], -inf for k >= nb.
+ *  6 Normalisation:  g = 10^((target_lufs - I) / 20) in double;  with peak_ceiling > 0, g = min(g, peak_ceiling / peak);  g is rounded
+ *    once to f32;  where the ceiling binds, g then moves by whole ulps (at most 4 each way) to the largest f32 whose f32 product
+ *    with the peak is at or under the ceiling - the output's peak is <= the ceiling and within 2 ulp of it;
+ *    out[i] = x[i] g, one f32 product;  zeros in [L, L_max).  g = 1 exactly, the utterance copied unchanged, when I is not finite
+ *    (too short, silent, a non-finite sample) or g does not fit f32 - the peak normaliser's convention for silence.  The gain is
+ *    formed and read on the device: the normalising call only enqueues.
+ *  7 A non-finite sample cannot fault or write outside the outputs;  it makes its own utterance's loudness NaN from the sub-block
+ *    that holds it on (the recurrence carries it to the end) and changes no bit of another utterance.  Every arithmetic order depends
+ *    on the sample's, sub-block's or block's index in its utterance alone, so a ragged batch is bit-identical to its utterances
+ *    alone, whatever the slot, L_max or B.
+ * Refused, on the host before the first HIP call, every output as it was:  B < 1 or > 65535;  a length outside [1, L_max] or beyond
+ * 2^31 - 153600;  the rate;  a non-finite target_lufs or peak_ceiling;  NB_max < 1 or smaller than the blocks of the longest
+ * utterance while `momentary` is given;  `out` overlapping `wav` other than out == wav;  stats / momentary overlapping anything.
+ * `m` may be a bare handle;  scratch comes from its arena. */
+#define MT2_LOUDNESS_FIELDS 8
+/* h, nb, the ten coefficients (b0 b1 b2 a1 a2 of the shelf, then of the high-pass) and the arena bytes of a call with ONE utterance of L
+ * samples;  host only, no HIP call (outputs may be NULL).  A call with B utterances, the longest with ns sub-blocks, takes
+ * r(4 (4 ceil(B / 4) + 32)) + r(32 B ns) + r(8 B ns) + r(8 B) bytes, r(x) = max(256, x rounded up to 256). */
+int mt2_loudness_query(int sample_rate, long long L, int* sub_block, int* blocks, double* coeffs /*[10]*/, long long* workspace_bytes);
+/* wav f32 [B, L_max] (device), lens host int32 [B] -> stats f64 [B, 8] (device), optionally momentary f64 [B, NB_max] (device).  Four
+ * launches; the call only enqueues. */
+int mt2_loudness(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                 int sample_rate, double* stats /*[B, 8]*/, double* momentary /*[B, NB_max] or NULL*/, int NB_max);
+/* -> out f32 [B, L_max] (device; may be wav itself), optionally stats f64 [B, 8] (device) of the INPUT, the gain in field 7.  Five
+ * launches; no copy to the host and no wait. */
+int mt2_loudness_normalize(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                           int sample_rate, double target_lufs, double peak_ceiling /*<= 0: none*/, float* out /*[B, L_max]*/,
+                           double* stats /*[B, 8] or NULL*/);
+
 /* ---- the whole of Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) for a batch,
  * activations staying in the packed internal layout between stages.
  *   forced_dur   (host, optional) int32 [B, Np_max]: replaces the ADM's integer durations AFTER the ADM

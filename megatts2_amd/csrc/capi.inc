@@ -866,6 +866,46 @@ int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0, const int32_t
     MT2_API_END
 }
 
+// integrated loudness (loudness.hip): the sub-block, the block count, the K-weighting coefficients (b0 b1 b2 a1 a2 of the shelf, then
+// of the high-pass) and the arena bytes of a call with ONE utterance of L samples, without a HIP call (outputs may be NULL)
+int mt2_loudness_query(int sample_rate, long long L, int* sub_block, int* blocks, double* coeffs, long long* workspace_bytes) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
+    MT2_REQUIRE(L >= 1 && L <= INT_MAX - 8 * 19200, "L outside [1, 2^31 - 153600)");
+    const int h = sample_rate / 10;
+    if (sub_block) *sub_block = h;
+    if (blocks) *blocks = (int)std::max(L / h - 3, 0ll);
+    if (coeffs) loudness_coeffs(sample_rate, coeffs);
+    if (workspace_bytes) *workspace_bytes = loudness_workspace_bytes(sample_rate, L, 1);
+    MT2_API_END
+}
+
+// integrated loudness of a ragged batch; every refusal is decided on the host before the first HIP call
+int mt2_loudness(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sample_rate, double* stats,
+                 double* momentary, int NB_max) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(stats != nullptr, "null stats");
+    const int mx = loudness_check(wav, lens, L_max, B, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    loudness_run(c, wav, lens, L_max, B, mx, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max);
+    MT2_API_END
+}
+
+// each utterance brought to target_lufs, the gain formed and read on the device; every refusal is decided on the host before the first HIP call
+int mt2_loudness_normalize(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sample_rate,
+                           double target_lufs, double peak_ceiling, float* out, double* stats) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(out != nullptr, "null out");
+    const int mx = loudness_check(wav, lens, L_max, B, sample_rate, target_lufs, peak_ceiling, out, stats, nullptr, 0);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    loudness_run(c, wav, lens, L_max, B, mx, sample_rate, target_lufs, peak_ceiling, out, stats, nullptr, 0);
+    MT2_API_END
+}
+
 // the STFT the mel front-end takes its magnitude of, for a ragged batch (the front half of mt2_mel_spectrogram, shared with it)
 int mt2_stft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* wav, const int32_t* lens, int L_max, int B, float* spec,
              int T_max) {

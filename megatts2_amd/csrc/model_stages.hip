@@ -2289,6 +2289,71 @@ static void pitch_contour_run(const Ctx& c, const float* f0, const int* frame_le
     MT2_HIP(launch_pitch_contour(p, c.s));
 }
 
+// ---- integrated loudness and loudness normalisation (loudness.hip): every refusal is decided here, on the host, before the first HIP call
+// -> max_b lens[b].  out == nullptr: the measuring call
+static int loudness_check(const float* wav, const int* lens, int L_max, int B, int sample_rate, double target_lufs, double peak_ceiling,
+                          const float* out, const double* stats, const double* momentary, int NB_max) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
+    MT2_REQUIRE(std::isfinite(target_lufs) && std::isfinite(peak_ceiling), "target_lufs / peak_ceiling must be finite");
+    MT2_REQUIRE(wav != nullptr && lens != nullptr && L_max >= 1, "bad buffers");
+    MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)out) & 3) == 0 && (((uintptr_t)stats | (uintptr_t)momentary) & 7) == 0, "misaligned buffers");
+    int mx = 0;
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
+        mx = std::max(mx, lens[b]);
+    }
+    MT2_REQUIRE(mx <= INT_MAX - 8 * 19200, "waveform too long");
+    const int nb = std::max(mx / (sample_rate / 10) - 3, 0);
+    MT2_REQUIRE(momentary == nullptr || (NB_max >= 1 && NB_max >= nb), "NB_max smaller than the blocks of the longest utterance (or < 1)");
+    const size_t nw = sizeof(float) * (size_t)B * L_max, nst = sizeof(double) * 8 * (size_t)B, nm = sizeof(double) * (size_t)B * std::max(NB_max, 0);
+    MT2_REQUIRE(out == nullptr || out == wav || !f0_overlaps(out, nw, wav, nw), "out overlaps wav without being wav");
+    MT2_REQUIRE(!f0_overlaps(stats, nst, wav, nw) && !f0_overlaps(momentary, nm, wav, nw) && !f0_overlaps(stats, nst, out, nw) &&
+                    !f0_overlaps(momentary, nm, out, nw) && !f0_overlaps(stats, nst, momentary, nm),
+                "overlapping buffers");
+    return mx;
+}
+// enqueues only: the lengths and the carry matrix travel in the call's one IntPlan upload; the gain is formed and read on the device
+static void loudness_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, double target_lufs,
+                         double peak_ceiling, float* out, double* stats, double* momentary, int NB_max) {
+    LoudnessP p{};
+    p.h = sample_rate / 10;
+    loudness_coeffs(sample_rate, p.c);
+    if (c.m.loud_rate != sample_rate) {          // a function of the rate alone: kept by the handle
+        loudness_carry_matrix(p.c, p.h, c.m.loud_M);
+        c.m.loud_rate = sample_rate;
+    }
+    std::vector<int> mbits(32);
+    std::memcpy(mbits.data(), c.m.loud_M, sizeof(c.m.loud_M));
+    IntPlan ip;
+    const int o_len = ip.add(std::vector<int>(lens, lens + B)), o_m = ip.add(mbits);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B; p.M = ip.dev(o_m);
+    p.NS = max_len / p.h;
+    p.state = c.ws.get<double>((size_t)B * p.NS * 4);
+    p.sums = c.ws.get<double>((size_t)B * p.NS);
+    unsigned* words = c.ws.get<unsigned>((size_t)2 * B);          // peak | gain
+    p.peak = words;
+    p.gain = out ? reinterpret_cast<float*>(words + B) : nullptr;
+    p.target_lufs = target_lufs; p.peak_ceiling = peak_ceiling; p.out = out; p.stats = stats; p.momentary = momentary; p.NB_max = NB_max;
+    MT2_HIP(hipMemsetAsync(p.peak, 0, sizeof(unsigned) * B, c.s));
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(launch_loudness_filter(p, c.s));
+    st.mark("loud_zero_state");
+    MT2_HIP(launch_loudness_carry(p, c.s));
+    st.mark("loud_carry");
+    MT2_HIP(launch_loudness_sums(p, c.s));
+    st.mark("loud_sums");
+    MT2_HIP(launch_loudness_gate(p, c.s));
+    st.mark("loud_gate");
+    if (out) {
+        MT2_HIP(launch_loudness_scale(p, c.s));
+        st.mark("loud_scale");
+    }
+    st.finish();
+}
+
 // The lengths of a DTW call, checked before anything else (host only)
 static void dtw_check_geometry(int Tx_max, int Ty_max, int D, int B) {
     MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");

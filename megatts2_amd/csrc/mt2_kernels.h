@@ -579,4 +579,34 @@ struct PitchContourP {
 };
 hipError_t launch_pitch_contour(const PitchContourP& p, hipStream_t s);
 
+// ---- integrated loudness and loudness normalisation (loudness.hip; the rule is in its header and in megatts2_hip.h) ------------------
+// host only, no HIP call: the rate the rule accepts (a multiple of 10 in [8000, 192000]); c[10] = b0 b1 b2 a1 a2 of the shelf, then of
+// the high-pass; M[16] = A^h row-major, the zero-input state transition of one sub-block; the arena bytes of a call with B utterances,
+// the longest of max_len samples
+bool loudness_rate_ok(int sample_rate);
+void loudness_coeffs(int sample_rate, double* c);
+void loudness_carry_matrix(const double* c, int h, double* M);
+long long loudness_workspace_bytes(int sample_rate, long long max_len, long long B);
+// Four launches on one stream in this order - zero-state chunks + peak -> carry -> sub-block sums -> blocks, gates, gain, stats - and
+// a fifth, scale, for the normalising call.  The caller zeroes peak[] in front.
+struct LoudnessP {
+    const float* wav; int L_max;              // [B, L_max]; samples at or beyond len[b] are never read
+    const int* len; int max_len, B;           // device [B]; max_b len[b]
+    int h;                                    // sample_rate / 10: the sub-block, which is the chunk
+    double c[10];                             // loudness_coeffs
+    const int* M;                             // device, 16 doubles (8-byte aligned): loudness_carry_matrix
+    double* state; double* sums; int NS;      // scratch [B, NS, 4] and [B, NS], NS >= max_len / h
+    unsigned* peak;                           // scratch [B]: the bit pattern of max |x|
+    float* gain;                              // [B] or nullptr (the measuring call: gain 1)
+    double target_lufs, peak_ceiling;         // read only with gain
+    float* out;                               // [B, L_max] for launch_loudness_scale; may be wav
+    double* stats;                            // optional [B, 8]
+    double* momentary; int NB_max;            // optional [B, NB_max], NB_max >= max_len / h - 3: l[k], -inf behind the utterance's blocks
+};
+hipError_t launch_loudness_filter(const LoudnessP& p, hipStream_t s);
+hipError_t launch_loudness_carry(const LoudnessP& p, hipStream_t s);
+hipError_t launch_loudness_sums(const LoudnessP& p, hipStream_t s);
+hipError_t launch_loudness_gate(const LoudnessP& p, hipStream_t s);
+hipError_t launch_loudness_scale(const LoudnessP& p, hipStream_t s);
+
 }  // namespace mt2

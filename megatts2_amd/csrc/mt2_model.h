@@ -213,6 +213,9 @@ struct mt2_model {
     // Griffin-Lim constants of fe_cfg, each built on the first call that needs it (model_stages.hip): inverse STFT basis [n_fft, 2F
     // padded to 4], squared window [n_fft], pseudo-inverse of the mel filterbank [F padded to 4, n_mels]
     float *gl_ibasis = nullptr, *gl_w2 = nullptr, *gl_P = nullptr;
+    // loudness (loudness.hip): the carry matrix A^h of the last sample rate seen (host; 4 h filter steps to build)
+    int loud_rate = 0;
+    double loud_M[16] = {};
     // resampler filter tables, tap-major, by reduced ratio (o, n) = (sr_in, sr_out) / gcd: built and uploaded on first use
     std::map<std::pair<int, int>, float*> rs_tables;
 

@@ -120,6 +120,24 @@ def extract_energy(samples, sample_rate: Optional[int] = None, trim_db: Optional
     return res if batched else res[0]
 
 
+LOUDNESS_STATS = ("integrated_lufs", "blocks", "blocks_over_absolute_gate", "blocks_over_both_gates", "relative_gate_lufs", "sample_peak",
+                  "max_momentary_lufs", "gain")
+
+
+def measure_loudness(samples, sample_rate: Optional[int] = None, lens=None) -> Dict[str, np.ndarray]:
+    """Integrated loudness (ITU-R BS.1770-4, gated - the measure EBU R 128 builds on) of a 1-D waveform or a [B, L] batch, on the GPU
+    by the rule of csrc/loudness.hip (MelFrontEnd.loudness; no reference counterpart, parity with pyloudnorm / libebur128 unpinned,
+    true peak and loudness range out of scope) -> dict of float64 numpy arrays [B] ([1] for a 1-D waveform): integrated_lufs (-inf
+    under 0.4 s or for silence), blocks, blocks_over_absolute_gate, blocks_over_both_gates, relative_gate_lufs, sample_peak (linear),
+    max_momentary_lufs, gain (1).  sample_rate: the rate of `samples` (default 16 kHz), a multiple of 10 in [8000, 192000] - the
+    audio is measured at its own rate, nothing is resampled.  lens: the real samples of each row."""
+    import torch
+    x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
+    x = (x if x.dim() == 2 else x.unsqueeze(0)).to("cuda", torch.float32)
+    st = _frontend().loudness(x, lens, sample_rate=sample_rate).cpu().numpy()
+    return {k: st[:, i].copy() for i, k in enumerate(LOUDNESS_STATS)}
+
+
 PHONE_PROSODY = ("start", "frames", "voiced_frames", "mean_hz", "mean_semitones", "min_hz", "max_hz", "mean_energy")
 DURATION_STATS = ("phones", "realised_fraction", "mean_frames", "std_frames", "skewness", "kurtosis")
 
@@ -520,14 +538,30 @@ class Megatts:
     # -- batched tensor-level pipeline (the measured hot path)
     def synthesize(self, phone_tokens, mels, phone_lens=None, mel_lens=None, forced_durations=None,
                    forced_codes=None, vocoder: bool = False, return_aux: bool = False, sampling=None, seeds=None,
-                   griffin_lim=None):
+                   griffin_lim=None, loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0):
         """phone_tokens int64 [B, Np], mels f32 [B, Tp, 80] -> (mel [B, Tm, 80], mel_lens) - the
         no_grad block of Megatts.forward (models/megatts2.py:353-368) for every utterance of the batch.
         `sampling` (sampling.PLMSampling; None = greedy) / `seeds` (int64 [B] or one int s -> s + b): sampled PLM codes.
         `griffin_lim` (None = off, exactly the call above; True or a dict of vocode_griffin_lim's keyword arguments): the generated
         mel is vocoded by Griffin-Lim instead of HiFi-GAN and the result is (mel, mel_lens, aux) with aux["wav"] f32
         [B, (max mel_lens - 1) * hop], utterance b holding (mel_lens[b] - 1) * hop samples - no inference padding, unlike
-        decode_batch."""
+        decode_batch.
+        `loudness_lufs` (None = off, exactly the call without it): aux["wav"] - HiFi-GAN's with vocoder=True and return_aux=True, or
+        Griffin-Lim's - is brought to this integrated loudness per utterance over its real samples, in place on the device
+        (MelFrontEnd.loudness_normalize; `peak_ceiling` > 0 caps the gain so that the sample peak stays under it; an utterance under
+        0.4 s or silent keeps its level)."""
+        if loudness_lufs is not None:
+            gl_on = not (griffin_lim is None or griffin_lim is False)
+            if not gl_on and not (vocoder and return_aux):
+                raise ValueError("loudness_lufs needs audio to normalise: vocoder=True with return_aux=True, or griffin_lim")
+            mel, out_lens, aux = self.synthesize(phone_tokens, mels, phone_lens, mel_lens, forced_durations, forced_codes, vocoder,
+                                                 True, sampling, seeds, griffin_lim)
+            hg = self.native.hg_cfg
+            n = np.asarray(out_lens, np.int64)
+            n = (n - 1) * HIFIGAN_HOP_LENGTH if gl_on else (n + 2 * int(getattr(hg, "inference_padding", 0))) * hg.hop
+            _frontend().loudness_normalize(aux["wav"], np.maximum(n, 1).astype(np.int32), float(loudness_lufs), float(peak_ceiling),
+                                           sample_rate=HIFIGAN_SR, out=aux["wav"])
+            return mel, out_lens, aux
         if griffin_lim is None or griffin_lim is False:
             return self.native.synthesize_batch(phone_tokens, phone_lens, mels, mel_lens, forced_durations, forced_codes,
                                                 run_plm=forced_codes is None, vocoder=vocoder, return_aux=return_aux,
@@ -781,9 +815,20 @@ class Megatts:
     # "griffin_lim" (or a dict of vocode_griffin_lim's keyword arguments) vocodes the first prompt mel and the generated mel by
     # Griffin-Lim, concatenates them as the HiFi-GAN branch does, sets aux["wav"] and writes out_path.  That audio has
     # (T - 1) * hop samples per mel of T frames and no inference padding, unlike decode_batch.
+    # loudness_lufs: None leaves the levels as the vocoder produced them; a number brings the vocoded prompt and the generated audio
+    # EACH to that integrated loudness (BS.1770, MelFrontEnd.loudness_normalize; peak_ceiling > 0 caps the gain by the sample peak)
+    # before they are concatenated and written, with either vocoder - the two halves of the file then sound equally loud.
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
-                phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None, vocoder=None):
+                phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None, vocoder=None,
+                loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0):
         import torch
+        level = {} if loudness_lufs is None else {"loudness_lufs": float(loudness_lufs), "peak_ceiling": float(peak_ceiling)}
+
+        def levelled(x):          # the vocoded prompt, a 1-D device tensor
+            if loudness_lufs is None:
+                return x
+            return _frontend().loudness_normalize(x.unsqueeze(0), None, float(loudness_lufs), float(peak_ceiling), sample_rate=HIFIGAN_SR)[0]
+
         if not (vocoder is None or vocoder == "griffin_lim" or isinstance(vocoder, dict)):
             raise ValueError(f"vocoder={vocoder!r}: None (HiFi-GAN when loaded) or 'griffin_lim'")
         from . import audio_io
@@ -818,18 +863,19 @@ class Megatts:
         phone_tokens = torch.as_tensor(np.asarray(phone_tokens)).to(torch.int64).reshape(1, -1).cuda()
         if vocoder is not None:
             gl = vocoder if isinstance(vocoder, dict) else {}
-            mel, mel_lens, aux = self.synthesize(phone_tokens, mels, return_aux=True, griffin_lim=gl or True)
+            mel, mel_lens, aux = self.synthesize(phone_tokens, mels, return_aux=True, griffin_lim=gl or True, **level)
             if out_path:
-                prompt = self.vocode_griffin_lim(mels_prompt.unsqueeze(0).contiguous(), **gl)[0]
+                prompt = levelled(self.vocode_griffin_lim(mels_prompt.unsqueeze(0).contiguous(), **gl)[0])
                 audio = torch.cat([prompt, aux["wav"][0, :(int(mel_lens[0]) - 1) * HIFIGAN_HOP_LENGTH]])
                 audio_io.write_wav(out_path, audio, HIFIGAN_SR)
             return mel, mel_lens, aux
-        mel, mel_lens, aux = self.synthesize(phone_tokens, mels, vocoder=self.hifi_gan is not None, return_aux=True)
+        mel, mel_lens, aux = self.synthesize(phone_tokens, mels, vocoder=self.hifi_gan is not None, return_aux=True,
+                                             **(level if self.hifi_gan is not None else {}))
         if self.hifi_gan is not None and out_path:
             # :370-375  prompt audio (vocoded first prompt mel) followed by the generated audio; decode_batch output
             # includes the generator's inference padding on both sides, exactly as the reference concatenates it
             hg = self.hifi_gan.cfg
-            prompt = self.hifi_gan.decode_batch(mels_prompt.transpose(0, 1).unsqueeze(0).contiguous())[0, 0]
+            prompt = levelled(self.hifi_gan.decode_batch(mels_prompt.transpose(0, 1).unsqueeze(0).contiguous())[0, 0])
             audio = torch.cat([prompt, aux["wav"][0, :(int(mel_lens[0]) + 2 * hg.inference_padding) * hg.hop]])
             audio_io.write_wav(out_path, audio, HIFIGAN_SR)
         return mel, mel_lens, aux

@@ -28,6 +28,7 @@ TRIM_FRAME, TRIM_HOP = 2048, 512      # MT2_TRIM_FRAME, MT2_TRIM_HOP
 F0_FRAME, F0_WINDOW, F0_MAX_LAG = 1024, 768, 256      # MT2_F0_FRAME, MT2_F0_WINDOW, MT2_F0_MAX_LAG
 DTW_MAX_LEN, DTW_DIR_COLS = 4096, 16  # MT2_DTW_MAX_LEN, MT2_DTW_DIR_COLS
 PROSODY_FIELDS = 8                    # MT2_PROSODY_FIELDS
+LOUDNESS_FIELDS = 8                   # MT2_LOUDNESS_FIELDS
 
 
 class NativeError(RuntimeError):
@@ -108,6 +109,9 @@ def load_library():
     lib.mt2_frame_energy.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_phone_prosody.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.mt2_pitch_contour.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib.mt2_loudness_query.argtypes = [C.c_int, C.c_longlong] + [C.c_void_p] * 4
+    lib.mt2_loudness.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.mt2_loudness_normalize.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -794,6 +798,54 @@ class MelFrontEnd:
                                          _iptr(bounds), _ptr(energy), F))
         res = (out, bounds[:, 1] - bounds[:, 0], bounds)
         return res + (energy,) if return_energy else res
+
+    def loudness(self, wav, lens=None, sample_rate: Optional[int] = None, return_momentary: bool = False):
+        """Integrated loudness (ITU-R BS.1770-4, gated; what EBU R 128 builds on) of a ragged batch of mono utterances on the device, by
+        the rule of csrc/loudness.hip / include/megatts2_hip.h; parity with pyloudnorm / libebur128 is unpinned, true peak and
+        loudness range are out of scope.  wav f32 [B, L] (device) at sample_rate (default audio.sample_rate; a multiple of 10 in
+        [8000, 192000]) -> stats f64 [B, 8] (device): integrated LUFS (-inf for an utterance under 0.4 s or silent, NaN behind a
+        non-finite sample), blocks, blocks over the absolute gate, blocks over both gates, the relative gate, the sample peak, the
+        maximum momentary loudness, 1.0.  return_momentary: also f64 [B, max(1, blocks of the longest)] with the loudness of every
+        400 ms block (every 100 ms), -inf behind an utterance's own blocks.  Samples beyond lens[b] are never read.  The call only
+        enqueues."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+        assert ln.shape == (B,)
+        sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
+        stats = torch.empty(B, LOUDNESS_FIELDS, device=wav.device, dtype=torch.float64)
+        mom, NB = None, 0
+        if return_momentary:
+            NB = max(1, max(int(ln.max()), 0) // max(sr // 10, 1) - 3)
+            mom = torch.empty(B, NB, device=wav.device, dtype=torch.float64)
+        _check(self.lib.mt2_loudness(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, _ptr(stats), _ptr(mom), NB))
+        return (stats, mom) if return_momentary else stats
+
+    def loudness_normalize(self, wav, lens=None, target_lufs: float = -23.0, peak_ceiling: float = 0.0, sample_rate: Optional[int] = None,
+                           out=None, return_stats: bool = False):
+        """Each utterance of a ragged batch brought to target_lufs by one gain g = 10^((target - I) / 20), I its integrated loudness
+        (`loudness`): wav f32 [B, L] (device) -> out f32 [B, L] with out[b, :lens[b]] = wav[b, :lens[b]] * g_b (one f32 product) and
+        zeros behind.  peak_ceiling > 0: g is capped so that the sample peak stays at or below it (the sample peak, not the true
+        peak).  An utterance whose loudness is not finite - under 0.4 s, silent, holding a non-finite sample - is copied unchanged
+        (g = 1).  out: a contiguous f32 [B, L] device tensor to write into; it may be wav itself.  return_stats: also the f64
+        [B, 8] of `loudness` for the INPUT, with g in the last field.  The gain is formed and read on the device: the call only
+        enqueues, with no copy to the host and no wait."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+        assert ln.shape == (B,)
+        sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
+        if out is None:
+            out = torch.empty_like(wav)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == wav.shape
+        stats = torch.empty(B, LOUDNESS_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
+        _check(self.lib.mt2_loudness_normalize(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs), float(peak_ceiling),
+                                               _ptr(out), _ptr(stats)))
+        return (out, stats) if return_stats else out
 
     def f0(self, wav, lens=None, fmin: float = 62.5, fmax: float = 500.0, threshold: float = 0.15, hop: Optional[int] = None,
            return_cmnd: bool = False, return_lag: bool = False, return_diff: bool = False, out=None):
@@ -1628,6 +1680,16 @@ def trim_query(L: int, top_db: float):
     f, c = C.c_int(0), C.c_float(0)
     _check(load_library().mt2_trim_query(int(L), float(top_db), C.byref(f), C.byref(c)))
     return f.value, np.float32(c.value)
+
+
+def loudness_query(sample_rate: int, L: int):
+    """mt2_loudness_query (no device needed) -> (sub_block, blocks, coeffs, workspace_bytes): h = sample_rate // 10, nb =
+    max(0, L // h - 3), the ten K-weighting coefficients as float64 (b0 b1 b2 a1 a2 of the shelf, then of the high-pass) and the arena
+    bytes of a MelFrontEnd.loudness / loudness_normalize call with one utterance of L samples; NativeError where the rule refuses."""
+    h, nb, ws = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    c = np.zeros(10, np.float64)
+    _check(load_library().mt2_loudness_query(int(sample_rate), int(L), C.byref(h), C.byref(nb), c.ctypes.data_as(C.c_void_p), C.byref(ws)))
+    return h.value, nb.value, c, ws.value
 
 
 def f0_query(L: int, sample_rate: int = 16000, hop: int = 256, fmin: float = 62.5, fmax: float = 500.0):

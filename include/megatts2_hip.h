@@ -90,6 +90,14 @@ int mt2_model_memory(const mt2_model* m, size_t* weight_bytes, size_t* workspace
 int mt2_workspace_query(const mt2_model* m, int B, int Np_max, int Tp_max, int Tm_cap, int flags, size_t* bytes);
 int mt2_workspace_reserve(mt2_model* m, size_t bytes);
 int mt2_workspace_high_water(const mt2_model* m, size_t* bytes);
+/* test hooks: control and inspect what the arena holds.  A call resets the arena to offset 0 and never clears it, so the bytes it finds
+ * there are the previous call's (or the driver's); no result may depend on them (tests/test_gpu_workspace_poison.py).  Both wait for
+ * the handle's pending call, whatever stream it is on, and return with their own device work finished.
+ * mt2_workspace_fill: every byte of every arena chunk (its whole size, used or not) := `byte` (0..255); capacity, high-water mark and
+ * options are untouched.  mt2_workspace_peek: `bytes` arena bytes from `offset` -> `dst_host`; `offset` runs over the chunks in
+ * allocation order; a range that leaves the capacity (mt2_model_memory) is an error. */
+int mt2_workspace_fill(mt2_model* m, int byte);
+int mt2_workspace_peek(mt2_model* m, size_t offset, void* dst_host /*host*/, size_t bytes);
 
 /* ---- MRTE.tc_latent(phone, mel) (modules/mrte.py:154-171)
  * phone int64 [B, Np_max], mel f32 [B, Tp_max, mel_bins] -> out f32 [B, Np_max, hidden]. */

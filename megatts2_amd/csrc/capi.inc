@@ -237,6 +237,28 @@ int mt2_workspace_reserve(mt2_model* m, size_t bytes) {
     MT2_API_END
 }
 
+// Test hooks (tests/test_gpu_workspace_poison.py): the arena is never cleared between calls, so what a call finds there is what the
+// previous call left.  These two let a test decide what that is, and look at what a call left.  Both wait for the handle's pending
+// call first (its kernels may still be reading the arena) and return with their own device work finished.
+int mt2_workspace_fill(mt2_model* m, int byte) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    MT2_REQUIRE(byte >= 0 && byte <= 255, "fill byte must be in 0..255");
+    std::lock_guard<std::mutex> lk(m->call_mutex);
+    if (m->call_pending) MT2_HIP(hipEventSynchronize(m->ev_call_end));
+    m->ws.fill(byte);
+    MT2_API_END
+}
+
+int mt2_workspace_peek(mt2_model* m, size_t offset, void* dst_host, size_t bytes) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(m != nullptr && (dst_host != nullptr || bytes == 0), "null argument");
+    std::lock_guard<std::mutex> lk(m->call_mutex);
+    if (m->call_pending) MT2_HIP(hipEventSynchronize(m->ev_call_end));
+    m->ws.peek(offset, dst_host, bytes);
+    MT2_API_END
+}
+
 // Gap rows between the utterances of a vocoder batch, at the mel level.  A zero-padded "same" convolution of one utterance has to read
 // zeros behind its ends, never a neighbour's rows: at every stage the gap - times the rows per mel frame there - covers the stage's
 // widest halo, (k - 1) / 2 x dilation; the reflect edge mode (speechbrain) keeps TWO halos in every gap.  Never less than the 4 / 8

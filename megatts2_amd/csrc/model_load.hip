@@ -46,6 +46,23 @@ size_t Arena::capacity() const {
     for (auto& c : chunks_) t += c.size;
     return t;
 }
+void Arena::fill(int byte) {
+    for (auto& c : chunks_) MT2_HIP(hipMemsetAsync(c.p, byte, c.size, nullptr));
+    MT2_HIP(hipStreamSynchronize(nullptr));
+}
+void Arena::peek(size_t offset, void* dst_host, size_t bytes) const {
+    MT2_REQUIRE(offset <= capacity() && bytes <= capacity() - offset, "workspace peek leaves the arena");
+    char* dst = static_cast<char*>(dst_host);
+    for (auto& c : chunks_) {
+        if (offset >= c.size) { offset -= c.size; continue; }
+        if (bytes == 0) break;
+        const size_t n = std::min(bytes, c.size - offset);
+        MT2_HIP(hipMemcpy(dst, c.p + offset, n, hipMemcpyDeviceToHost));
+        dst += n;
+        bytes -= n;
+        offset = 0;
+    }
+}
 void* Arena::alloc(size_t bytes) {
     bytes = (bytes + 255) & ~size_t(255);
     if (bytes == 0) bytes = 256;

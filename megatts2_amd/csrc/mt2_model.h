@@ -34,6 +34,10 @@ class Arena {
     size_t capacity() const;
     size_t high_water() const { return high_; }      // most bytes in use at once since construction
     void reserve(size_t bytes);                      // make sure one chunk of at least `bytes` exists
+    // test hooks (mt2_workspace_fill / _peek): every byte of every chunk (its whole size, not `used`) set to `byte`; bytes copied to
+    // the host from `offset`, which runs over the chunks in allocation order.  Both return with the device work done.
+    void fill(int byte);
+    void peek(size_t offset, void* dst_host, size_t bytes) const;
 
   private:
     struct Chunk { char* p; size_t size, used; };

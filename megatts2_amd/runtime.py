@@ -112,6 +112,8 @@ def load_library():
     lib.mt2_loudness_query.argtypes = [C.c_int, C.c_longlong] + [C.c_void_p] * 4
     lib.mt2_loudness.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     lib.mt2_loudness_normalize.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    lib.mt2_workspace_fill.argtypes = [C.c_void_p, C.c_int]
+    lib.mt2_workspace_peek.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     _LIB = lib
     return lib
 
@@ -210,6 +212,18 @@ def _dtw(lib, h, X, Y, x_lens=None, y_lens=None, return_cost: bool = False, retu
         out["acc"] = torch.zeros(B, Tx, Ty, device=dev, dtype=torch.float32)
     _check(lib.mt2_dtw_align(h, _stream(), _ptr(X), _iptr(xl), Tx, _ptr(Y), _iptr(yl), Ty, D, B, _ptr(out["lo"]), _ptr(out["hi"]),
                              _ptr(out["steps"]), _ptr(out["total"]), _ptr(out.get("cost")), _ptr(out.get("acc"))))
+    return out
+
+
+def _workspace_fill(lib, h, byte: int) -> None:
+    """mt2_workspace_fill (test hook): every byte of the handle's arena := byte, after the handle's pending call; waits."""
+    _check(lib.mt2_workspace_fill(h, int(byte)))
+
+
+def _workspace_peek(lib, h, offset: int, nbytes: int) -> np.ndarray:
+    """mt2_workspace_peek (test hook): `nbytes` arena bytes from `offset` (over the chunks in allocation order) -> np.uint8 array."""
+    out = np.empty(int(nbytes), np.uint8)
+    _check(lib.mt2_workspace_peek(h, C.c_size_t(int(offset)), out.ctypes.data_as(C.c_void_p), C.c_size_t(int(nbytes))))
     return out
 
 
@@ -651,6 +665,14 @@ class NativeModel:
         _check(self.lib.mt2_workspace_high_water(self.h, C.byref(n)))
         return n.value
 
+    def workspace_fill(self, byte: int) -> None:
+        """Test hook: set every byte of the activation arena (`_workspace_fill`); results must not depend on it."""
+        _workspace_fill(self.lib, self.h, byte)
+
+    def workspace_peek(self, offset: int, nbytes: int) -> np.ndarray:
+        """Test hook: arena bytes as a np.uint8 array (`_workspace_peek`)."""
+        return _workspace_peek(self.lib, self.h, offset, nbytes)
+
     def gemm_trace_begin(self) -> None:
         _check(self.lib.mt2_gemm_trace_begin(self.h))
 
@@ -1079,6 +1101,23 @@ class MelFrontEnd:
         n = C.c_size_t(0)
         _check(self.lib.mt2_workspace_high_water(self.h, C.byref(n)))
         return n.value
+
+    def workspace_fill(self, byte: int) -> None:
+        """Test hook: set every byte of the activation arena (`_workspace_fill`); results must not depend on it."""
+        _workspace_fill(self.lib, self.h, byte)
+
+    def workspace_peek(self, offset: int, nbytes: int) -> np.ndarray:
+        """Test hook: arena bytes as a np.uint8 array (`_workspace_peek`)."""
+        return _workspace_peek(self.lib, self.h, offset, nbytes)
+
+    def workspace_reserve(self, nbytes: int) -> None:
+        _check(self.lib.mt2_workspace_reserve(self.h, C.c_size_t(int(nbytes))))
+
+    def memory(self):
+        """(weight bytes, workspace bytes) of the bare handle, as NativeModel.memory."""
+        w, s = C.c_size_t(0), C.c_size_t(0)
+        _check(self.lib.mt2_model_memory(self.h, C.byref(w), C.byref(s)))
+        return w.value, s.value
 
     def from_audio(self, wav, sr_in: int, lens=None, trim_db: Optional[float] = None, return_bounds: bool = False):
         """Prompt audio at any sample rate -> (mel [B, T, n_mels], mel_lens): resample to audio.sample_rate, peak-normalise and

@@ -39,6 +39,12 @@ def main() -> None:
     ap.add_argument("--output-lufs", type=float,
                     help="bring the vocoded prompt and the generated audio each to this integrated loudness (ITU-R BS.1770, e.g. -23) before they are written")
     ap.add_argument("--peak-ceiling", type=float, default=0.0, help="with --output-lufs: cap the gain so that the sample peak stays at or below this (e.g. 0.99)")
+    ap.add_argument("--true-peak-ceiling", type=float, metavar="DB",
+                    help="with --output-lufs: cap the gain so that the true peak (oversampled to at least 192 kHz) stays at or below this many dBTP "
+                         "(e.g. -1, what EBU R 128 delivery asks); not together with --peak-ceiling")
+    ap.add_argument("--report-ebu", action="store_true",
+                    help="print true peak in dBTP, loudness range (EBU Tech 3342) and maximum short-term and momentary loudness (measured on the "
+                         "GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
     ap.add_argument("--report-loudness", action="store_true",
                     help="print integrated LUFS, sample peak in dBFS and block counts (measured on the GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
     ap.add_argument("--text")
@@ -60,7 +66,7 @@ def main() -> None:
     phones = [int(v) for v in a.phones.split(",")] if a.phones else None
     gl = {"n_iter": a.gl_iters} if a.vocoder == "griffin-lim" else None
     mel, lens, aux = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl, loudness_lufs=a.output_lufs,
-                         peak_ceiling=a.peak_ceiling)
+                         peak_ceiling=a.peak_ceiling, true_peak_ceiling_dbtp=a.true_peak_ceiling)
     wrote = gl is not None or tts.hifi_gan is not None
     print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
     if a.report_loudness:
@@ -79,6 +85,20 @@ def main() -> None:
                   f"{20 * math.log10(pk) if pk > 0 else float('-inf'):.2f} dBFS, {int(st['blocks'][0])} blocks of 400 ms, "
                   f"{int(st['blocks_over_absolute_gate'][0])} over -70 LUFS, {int(st['blocks_over_both_gates'][0])} over the relative gate at "
                   f"{float(st['relative_gate_lufs'][0]):.2f} LUFS")
+    if a.report_ebu:
+        import glob
+        from megatts2_amd import audio_io
+        path = sorted(glob.glob(f"{a.wavs_dir}/*.wav"))[0]
+        y, sr = audio_io.read_wav(path)
+        report = [(f"first prompt ({path}, as the file holds it)", M.measure_loudness(y, sr, ebu=True))]
+        if wrote:          # the generated audio alone, as the vocoder (and --output-lufs / --true-peak-ceiling) left it on the device
+            n = (int(lens[0]) - 1) * C.HIFIGAN_HOP_LENGTH if gl is not None else (int(lens[0]) + 2 * tts.hifi_gan.cfg.inference_padding) * tts.hifi_gan.cfg.hop
+            report.append(("generated audio", M.measure_loudness(aux["wav"][:1], C.HIFIGAN_SR, lens=[n], ebu=True)))
+        for what, st in report:
+            print(f"EBU-mode figures of the {what}: true peak {float(st['true_peak_dbtp'][0]):.2f} dBTP ({int(st['oversampling'][0])}x oversampled), "
+                  f"loudness range {float(st['lra'][0]):.2f} LU over {int(st['short_term_blocks_over_both_gates'][0])} of "
+                  f"{int(st['short_term_blocks'][0])} blocks of 3 s, maximum short-term {float(st['short_term_max'][0]):.2f} LUFS, maximum "
+                  f"momentary {float(st['max_momentary_lufs'][0]):.2f} LUFS")
     if a.report_pitch:
         import glob
         from megatts2_amd import audio_io

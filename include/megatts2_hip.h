@@ -525,7 +525,8 @@ int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/
  * reference peak-normalises its prompts, models/megatts2.py:336, and leaves the output level alone).  Parity with pyloudnorm /
  * libebur128 is unpinned - neither is on hand; the kernels are held to the standard's own figures (a full-scale 997 Hz sine at 48 kHz
  * reads -3.01 LKFS), to the analytic steady-state reading of a sine, and to the float64 restatement tests/loudness_ref.py.  True peak
- * (4x oversampled) and loudness range (EBU Tech 3342) are out of scope.  THE RULE, for one utterance x f32 [L] at sample_rate:
+ * (oversampled) and loudness range (EBU Tech 3342) are measured by the calls of the next section, which leave these as they are.
+ * THE RULE, for one utterance x f32 [L] at sample_rate:
  *  1 sample_rate is a multiple of 10 in [8000, 192000], never rounded.  h = sample_rate / 10 (the 100 ms sub-block);  ns = L / h
  *    complete sub-blocks;  nb = max(0, ns - 3) blocks of 400 ms with 75 % overlap - only blocks wholly inside the signal count.
  *  2 K-weighting coefficients in double from the analogue prototypes (at 48 kHz they reproduce the standard's table to 1e-13):
@@ -574,6 +575,66 @@ int mt2_loudness(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, co
 int mt2_loudness_normalize(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
                            int sample_rate, double target_lufs, double peak_ceiling /*<= 0: none*/, float* out /*[B, L_max]*/,
                            double* stats /*[B, 8] or NULL*/);
+
+/* ---- EBU-mode metering (csrc/ebu.hip): what EBU R 128 / Tech 3341 asks of a meter beside integrated and momentary loudness - true
+ * peak, short-term loudness and loudness range - and normalisation under a true-peak ceiling.  No reference counterpart.  Parity with
+ * libebur128 / pyloudnorm is unpinned - neither is on hand; Tech 3341 cases 20-23 and Tech 3342 cases 5-6 need the EBU's recorded
+ * files, which are not on hand either.  The kernels are held to analytic truths (the true peak of a band-limited tone is its amplitude
+ * whatever the sampling phase; the loudness range of a two-level tone is the difference of the levels, Tech 3342 cases 1-4) and to the
+ * float64 restatement tests/ebu_ref.py.  THE RULE, for one utterance x f32 [L] at sample_rate; h, ns and S[j] as in the loudness rule:
+ *  1 True peak (ITU-R BS.1770-4 Annex 2, with a filter of this library's own).  o = ceil(192000 / sample_rate) phases: 12 at 16 kHz, 9 at
+ *    22.05 kHz, 4 at 48 kHz, 1 at 192 kHz, at most 24.  Phase 0 is the sample itself, unfiltered, so true peak >= sample peak holds
+ *    exactly.  Phases p = 1 .. o - 1 are a Kaiser-windowed sinc with its cutoff at Nyquist: Z = 12 zero crossings a side (24 taps per
+ *    phase), beta = 8;  h[p][k] = sinc(t) I0(beta sqrt(1 - (t / Z)^2)) / I0(beta), t = (k - Z + 1) - p / o, k = 0 .. 2 Z - 1, sinc(t) =
+ *    sin(pi t) / (pi t), built in double and rounded once to f32.  y[i o + p] = sum_k h[p][k] x[i - Z + 1 + k], one f32 fma chain from
+ *    0 with k ascending;  x = 0 outside [0, L);  i runs over [-Z, L), so the ringing in front of and behind the signal counts.
+ *    TP = max |y|, taken with v > m from m = 0: a NaN never wins, an Inf does (the sample peak's convention).  dBTP = 20 log10 TP.
+ *    With these constants tones of amplitude A at fs/4 (0 and 45 degrees), fs/6 (60) and fs/8 (67.5) under a 10 ms raised-cosine
+ *    fade read within +0.003 / -0.108 dB of A at 8, 16, 22.05, 44.1 and 48 kHz (Tech 3341 allows +0.2 / -0.4);  an abrupt onset
+ *    overshoots by up to 0.7 dB, which is a property of the truncated signal.
+ *  2 Short-term loudness.  nst = max(0, ns - 29) blocks of 3 s every 100 ms, only blocks wholly inside the signal.  z3[k] = (S[k] +
+ *    ... + S[k + 29]) / (30 h), summed ascending from S[k];  s[k] = -0.691 + 10 log10 z3[k] (-inf for z3 = 0).
+ *  3 Loudness range (EBU Tech 3342).  Gamma_r = -0.691 + 10 log10(mean of z3 over s > -70) - 20, the mean in the fixed order of the
+ *    loudness rule (partial sums over k = i, i + 256, ... ascending for i < 256, then a halving tree);  -inf with no block over -70.
+ *    A block is over a gate unless s <= gate, so a NaN block counts.  Over the n blocks over both gates, sorted ascending g[0 .. n)
+ *    with a NaN last:  P10 = g[((n - 1) 10 + 50) / 100], P95 = g[((n - 1) 95 + 50) / 100] in integer division (Tech 3342's
+ *    round((n - 1) p / 100 + 1) in 0-based integers);  LRA = P95 - P10;  n = 0 (under 3 s, or silent): LRA, P10 and P95 are NaN.  The
+ *    two are elements of the set, selected exactly.  A non-finite sample makes every later block of its utterance NaN, hence its LRA
+ *    NaN unless it sits in the last 5 % of the blocks, and changes nothing of another utterance.
+ *  4 stats f64 [18] per utterance:  0-7 the row of mt2_loudness, bit for bit (7 the gain of 5 below; 1 for the measuring call)
+ *    8 TP (linear)   9 o   10 LRA   11 nst   12 short-term blocks over the absolute gate   13 over both gates   14 Gamma_r   15 P10
+ *    16 P95   17 max_k s[k] (-inf for nst = 0).  short_term f64 [NST_max]: s[k], -inf for k >= nst.
+ *  5 Normalisation under a true-peak ceiling:  g = 10^((target_lufs - I) / 20) in double;  where TP > 0 and c = 10^(ceiling_dbtp / 20) /
+ *    TP is smaller, g = c;  g is rounded once to f32 - toward zero where the cap binds, to nearest otherwise;  out[i] = x[i] g, one f32
+ *    product;  zeros in [L, L_max).  g = 1 exactly and the utterance copied unchanged when I is not finite or g does not fit f32.  A
+ *    binding ceiling lowers the loudness reached (one gain, no limiter).  The gain is formed and read on the device: the call only
+ *    enqueues.
+ *  6 The max and the selection are order-free and every sum's order depends on the block's index in its utterance alone, so a ragged
+ *    batch is bit-identical to its utterances alone, whatever the slot, L_max or B.  A sample at or beyond L is never read.
+ * Refused, on the host before the first HIP call, every output as it was:  all that mt2_loudness refuses;  a non-finite ceiling_dbtp;
+ * NST_max < 1 or smaller than the short-term blocks of the longest utterance while `short_term` is given;  overlapping buffers.
+ * `m` may be a bare handle;  scratch comes from its arena. */
+#define MT2_EBU_FIELDS 18
+#define MT2_TP_ZERO_CROSSINGS 12
+#define MT2_TP_TAPS 24
+#define MT2_TP_TILE 1024 /* positions i of one workgroup of the true-peak kernel: tile t holds i in [1024 t - 12, 1024 (t + 1) - 12) */
+/* o, the taps per phase, the tile of the true-peak kernel, nst and the arena bytes of a call with ONE utterance of L samples;  host
+ * only, no HIP call (outputs may be NULL).  A call with B utterances, the longest with ns sub-blocks and nst short-term blocks, takes
+ * r(4 (4 ceil(B / 4) + 32 + 24 o)) + r(32 B ns) + r(8 B ns) + r(12 B) + r(64 B) + r(8 B nst) bytes, r(x) = max(256, x rounded up to
+ * 256): lengths, carry matrix and filter table; chunk states; S; the peak, gain and true-peak words; the loudness rows; z3 / keys. */
+int mt2_ebu_query(int sample_rate, long long L, int* oversample, int* taps, int* tile, int* short_term_blocks, long long* workspace_bytes);
+/* the interpolation table f32 [o][24] of rule 1 (row 0 is the unit sample);  host only, no HIP call */
+int mt2_true_peak_table(int sample_rate, float* table /*[o][24]*/);
+/* wav f32 [B, L_max] (device), lens host int32 [B] -> stats f64 [B, 18] (device), optionally momentary f64 [B, NB_max] as mt2_loudness
+ * writes it and short_term f64 [B, NST_max] (device).  Six launches; the call only enqueues. */
+int mt2_loudness_ebu(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                     int sample_rate, double* stats /*[B, 18]*/, double* momentary /*[B, NB_max] or NULL*/, int NB_max,
+                     double* short_term /*[B, NST_max] or NULL*/, int NST_max);
+/* -> out f32 [B, L_max] (device; may be wav itself), optionally stats f64 [B, 18] (device) of the INPUT, the gain in field 7.  Seven
+ * launches; no copy to the host and no wait. */
+int mt2_loudness_normalize_tp(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                              int sample_rate, double target_lufs, double ceiling_dbtp, float* out /*[B, L_max]*/,
+                              double* stats /*[B, 18] or NULL*/);
 
 /* ---- the whole of Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) for a batch,
  * activations staying in the packed internal layout between stages.

@@ -928,6 +928,57 @@ int mt2_loudness_normalize(mt2_model* m, void* stream, const float* wav, const i
     MT2_API_END
 }
 
+// EBU-mode metering (ebu.hip): the oversampling factor, the taps per phase, the tile of the true-peak kernel, the short-term blocks and
+// the arena bytes of a call with ONE utterance of L samples, without a HIP call (outputs may be NULL)
+int mt2_ebu_query(int sample_rate, long long L, int* oversample, int* taps, int* tile, int* short_term_blocks, long long* workspace_bytes) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
+    MT2_REQUIRE(L >= 1 && L <= INT_MAX - 8 * 19200, "L outside [1, 2^31 - 153600)");
+    if (oversample) *oversample = true_peak_oversample(sample_rate);
+    if (taps) *taps = MT2_TP_TAPS;
+    if (tile) *tile = MT2_TP_TILE;
+    if (short_term_blocks) *short_term_blocks = (int)std::max(L / (sample_rate / 10) - 29, 0ll);
+    if (workspace_bytes) *workspace_bytes = ebu_workspace_bytes(sample_rate, L, 1);
+    MT2_API_END
+}
+
+// the true-peak interpolation table [o][24] of a rate, without a HIP call
+int mt2_true_peak_table(int sample_rate, float* table) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
+    MT2_REQUIRE(table != nullptr, "null table");
+    true_peak_table(sample_rate, table);
+    MT2_API_END
+}
+
+// integrated, momentary and short-term loudness, loudness range and true peak of a ragged batch; every refusal is decided on the host
+// before the first HIP call
+int mt2_loudness_ebu(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sample_rate, double* stats,
+                     double* momentary, int NB_max, double* short_term, int NST_max) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(stats != nullptr, "null stats");
+    const int mx = ebu_check(wav, lens, L_max, B, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max, short_term, NST_max);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    ebu_run(c, wav, lens, L_max, B, mx, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max, short_term, NST_max);
+    MT2_API_END
+}
+
+// each utterance brought to target_lufs under a true-peak ceiling, the gain formed and read on the device; every refusal is decided on
+// the host before the first HIP call
+int mt2_loudness_normalize_tp(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sample_rate,
+                              double target_lufs, double ceiling_dbtp, float* out, double* stats) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(out != nullptr, "null out");
+    const int mx = ebu_check(wav, lens, L_max, B, sample_rate, target_lufs, ceiling_dbtp, out, stats, nullptr, 0, nullptr, 0);
+    MT2_REQUIRE(m != nullptr, "null model handle");
+    if (mt2_device_check() != 0) throw Error(g_last_error);
+    MT2_CALL(m, stream);
+    ebu_run(c, wav, lens, L_max, B, mx, sample_rate, target_lufs, ceiling_dbtp, out, stats, nullptr, 0, nullptr, 0);
+    MT2_API_END
+}
+
 // the STFT the mel front-end takes its magnitude of, for a ragged batch (the front half of mt2_mel_spectrogram, shared with it)
 int mt2_stft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* wav, const int32_t* lens, int L_max, int B, float* spec,
              int T_max) {

@@ -2354,6 +2354,85 @@ static void loudness_run(const Ctx& c, const float* wav, const int* lens, int L_
     st.finish();
 }
 
+// ---- EBU-mode metering (ebu.hip) behind the loudness kernels: every refusal is decided here, on the host, before the first HIP call
+// -> max_b lens[b].  out == nullptr: the measuring call
+static int ebu_check(const float* wav, const int* lens, int L_max, int B, int sample_rate, double target_lufs, double ceiling_dbtp,
+                     const float* out, const double* stats, const double* momentary, int NB_max, const double* short_term, int NST_max) {
+    const int mx = loudness_check(wav, lens, L_max, B, sample_rate, target_lufs, ceiling_dbtp, out, nullptr, momentary, NB_max);
+    MT2_REQUIRE((((uintptr_t)stats | (uintptr_t)short_term) & 7) == 0, "misaligned buffers");
+    const int nst = std::max(mx / (sample_rate / 10) - 29, 0);
+    MT2_REQUIRE(short_term == nullptr || (NST_max >= 1 && NST_max >= nst), "NST_max smaller than the short-term blocks of the longest utterance (or < 1)");
+    const size_t nw = sizeof(float) * (size_t)B * L_max, ns = sizeof(double) * MT2_EBU_FIELDS * (size_t)B,
+                 nm = sizeof(double) * (size_t)B * std::max(NB_max, 0), nt = sizeof(double) * (size_t)B * std::max(NST_max, 0);
+    MT2_REQUIRE(!f0_overlaps(stats, ns, wav, nw) && !f0_overlaps(stats, ns, out, nw) && !f0_overlaps(stats, ns, momentary, nm) &&
+                    !f0_overlaps(stats, ns, short_term, nt) && !f0_overlaps(short_term, nt, wav, nw) && !f0_overlaps(short_term, nt, out, nw) &&
+                    !f0_overlaps(short_term, nt, momentary, nm),
+                "overlapping buffers");
+    return mx;
+}
+// enqueues only: the lengths, the carry matrix and the filter table travel in the call's one IntPlan upload; the loudness kernels run
+// as in loudness_run and leave their row in the arena; the gain is formed and read on the device
+static void ebu_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, double target_lufs,
+                    double ceiling_dbtp, float* out, double* stats, double* momentary, int NB_max, double* short_term, int NST_max) {
+    LoudnessP p{};
+    p.h = sample_rate / 10;
+    loudness_coeffs(sample_rate, p.c);
+    if (c.m.loud_rate != sample_rate) {
+        loudness_carry_matrix(p.c, p.h, c.m.loud_M);
+        c.m.loud_rate = sample_rate;
+    }
+    EbuP e{};
+    e.o = true_peak_oversample(sample_rate);
+    std::vector<int> mbits(32), tbits((size_t)e.o * MT2_TP_TAPS);
+    std::memcpy(mbits.data(), c.m.loud_M, sizeof(c.m.loud_M));
+    {
+        std::vector<float> table(tbits.size());
+        true_peak_table(sample_rate, table.data());
+        std::memcpy(tbits.data(), table.data(), sizeof(float) * table.size());
+    }
+    IntPlan ip;
+    const int o_len = ip.add(std::vector<int>(lens, lens + B)), o_m = ip.add(mbits), o_t = ip.add(tbits);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B; p.M = ip.dev(o_m);
+    p.NS = max_len / p.h;
+    p.state = c.ws.get<double>((size_t)B * p.NS * 4);
+    p.sums = c.ws.get<double>((size_t)B * p.NS);
+    unsigned* words = c.ws.get<unsigned>((size_t)3 * B);          // peak | gain | true peak
+    double* row8 = c.ws.get<double>((size_t)8 * B);
+    p.peak = words;
+    p.gain = nullptr;                                             // the gate kernel measures; ebu.hip forms the gain
+    p.stats = row8; p.momentary = momentary; p.NB_max = NB_max;
+    e.wav = wav; e.L_max = L_max; e.len = p.len; e.max_len = max_len; e.B = B; e.h = p.h;
+    e.table = reinterpret_cast<const float*>(ip.dev(o_t));
+    e.tp = words + 2 * B;
+    e.sums = p.sums; e.NS = p.NS; e.row8 = row8;
+    e.NST = std::max(p.NS - 29, 0);
+    e.keys = c.ws.get<double>((size_t)B * e.NST);
+    e.gain = out ? reinterpret_cast<float*>(words + B) : nullptr;
+    e.target_lufs = target_lufs; e.ceiling_dbtp = ceiling_dbtp; e.stats = stats; e.short_term = short_term; e.NST_max = NST_max;
+    MT2_HIP(hipMemsetAsync(words, 0, sizeof(unsigned) * 3 * B, c.s));
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(launch_loudness_filter(p, c.s));
+    st.mark("loud_zero_state");
+    MT2_HIP(launch_loudness_carry(p, c.s));
+    st.mark("loud_carry");
+    MT2_HIP(launch_loudness_sums(p, c.s));
+    st.mark("loud_sums");
+    MT2_HIP(launch_loudness_gate(p, c.s));
+    st.mark("loud_gate");
+    MT2_HIP(launch_true_peak(e, c.s));
+    st.mark("ebu_true_peak");
+    MT2_HIP(launch_loudness_range(e, c.s));
+    st.mark("ebu_range");
+    if (out) {
+        p.gain = e.gain; p.out = out;
+        MT2_HIP(launch_loudness_scale(p, c.s));
+        st.mark("loud_scale");
+    }
+    st.finish();
+}
+
 // The lengths of a DTW call, checked before anything else (host only)
 static void dtw_check_geometry(int Tx_max, int Ty_max, int D, int B) {
     MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");

@@ -609,4 +609,29 @@ hipError_t launch_loudness_sums(const LoudnessP& p, hipStream_t s);
 hipError_t launch_loudness_gate(const LoudnessP& p, hipStream_t s);
 hipError_t launch_loudness_scale(const LoudnessP& p, hipStream_t s);
 
+// ---- true peak, short-term loudness and loudness range (ebu.hip; the rule is in its header and in megatts2_hip.h) --------------------
+// host only, no HIP call: o = ceil(192000 / sample_rate); table [o][MT2_TP_TAPS] f32 (row 0 the unit sample); the arena bytes of a call
+// with B utterances, the longest of max_len samples
+int true_peak_oversample(int sample_rate);
+void true_peak_table(int sample_rate, float* table);
+long long ebu_workspace_bytes(int sample_rate, long long max_len, long long B);
+// Two launches behind the four of LoudnessP on the same stream: launch_true_peak any time after tp[] is zeroed, launch_loudness_range
+// behind both it and launch_loudness_gate (which wrote row8 with gain 1).  The normalising call then runs launch_loudness_scale on `gain`.
+struct EbuP {
+    const float* wav; int L_max;              // [B, L_max]; samples at or beyond len[b] are never read
+    const int* len; int max_len, B;           // device [B]; max_b len[b]
+    int h, o;                                 // sample_rate / 10; true_peak_oversample
+    const float* table;                       // device [o][MT2_TP_TAPS]: true_peak_table
+    unsigned* tp;                             // scratch [B], zeroed on the stream: the bit pattern of the true peak
+    const double* sums; int NS;               // S[b, j] as launch_loudness_sums left it
+    const double* row8;                       // [B, 8] as launch_loudness_gate left it
+    double* keys; int NST;                    // scratch [B, NST], NST >= max_len / h - 29: z3, then the keys of the select
+    float* gain;                              // [B] or nullptr (the measuring call)
+    double target_lufs, ceiling_dbtp;         // read only with gain
+    double* stats;                            // optional [B, MT2_EBU_FIELDS]
+    double* short_term; int NST_max;          // optional [B, NST_max], NST_max >= max_len / h - 29: s[k], -inf behind the utterance's blocks
+};
+hipError_t launch_true_peak(const EbuP& p, hipStream_t s);
+hipError_t launch_loudness_range(const EbuP& p, hipStream_t s);
+
 }  // namespace mt2

@@ -124,16 +124,31 @@ LOUDNESS_STATS = ("integrated_lufs", "blocks", "blocks_over_absolute_gate", "blo
                   "max_momentary_lufs", "gain")
 
 
-def measure_loudness(samples, sample_rate: Optional[int] = None, lens=None) -> Dict[str, np.ndarray]:
+EBU_STATS = ("true_peak", "oversampling", "lra", "short_term_blocks", "short_term_blocks_over_absolute_gate",
+             "short_term_blocks_over_both_gates", "lra_relative_gate_lufs", "lra_p10_lufs", "lra_p95_lufs", "short_term_max")
+
+
+def measure_loudness(samples, sample_rate: Optional[int] = None, lens=None, ebu: bool = False) -> Dict[str, np.ndarray]:
     """Integrated loudness (ITU-R BS.1770-4, gated - the measure EBU R 128 builds on) of a 1-D waveform or a [B, L] batch, on the GPU
-    by the rule of csrc/loudness.hip (MelFrontEnd.loudness; no reference counterpart, parity with pyloudnorm / libebur128 unpinned,
-    true peak and loudness range out of scope) -> dict of float64 numpy arrays [B] ([1] for a 1-D waveform): integrated_lufs (-inf
+    by the rule of csrc/loudness.hip (MelFrontEnd.loudness; no reference counterpart, parity with pyloudnorm / libebur128 unpinned;
+    true peak and loudness range with ebu=True) -> dict of float64 numpy arrays [B] ([1] for a 1-D waveform): integrated_lufs (-inf
     under 0.4 s or for silence), blocks, blocks_over_absolute_gate, blocks_over_both_gates, relative_gate_lufs, sample_peak (linear),
     max_momentary_lufs, gain (1).  sample_rate: the rate of `samples` (default 16 kHz), a multiple of 10 in [8000, 192000] - the
-    audio is measured at its own rate, nothing is resampled.  lens: the real samples of each row."""
+    audio is measured at its own rate, nothing is resampled.  lens: the real samples of each row.
+    ebu (False = exactly the call above): the rest of an EBU-mode meter (EBU R 128 / Tech 3341; MelFrontEnd.loudness_ebu, csrc/ebu.hip)
+    is added to the dict, the first eight entries keeping their bits: true_peak (linear, oversampled to at least 192 kHz),
+    true_peak_dbtp, oversampling, lra (loudness range in LU by EBU Tech 3342; NaN under 3 s or for silence), short_term_blocks
+    (3 s every 100 ms), short_term_blocks_over_absolute_gate, short_term_blocks_over_both_gates, lra_relative_gate_lufs,
+    lra_p10_lufs, lra_p95_lufs, short_term_max."""
     import torch
     x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
     x = (x if x.dim() == 2 else x.unsqueeze(0)).to("cuda", torch.float32)
+    if ebu:
+        st = _frontend().loudness_ebu(x, lens, sample_rate=sample_rate).cpu().numpy()
+        res = {k: st[:, i].copy() for i, k in enumerate(LOUDNESS_STATS + EBU_STATS)}
+        with np.errstate(divide="ignore"):
+            res["true_peak_dbtp"] = 20.0 * np.log10(res["true_peak"])
+        return res
     st = _frontend().loudness(x, lens, sample_rate=sample_rate).cpu().numpy()
     return {k: st[:, i].copy() for i, k in enumerate(LOUDNESS_STATS)}
 
@@ -538,7 +553,8 @@ class Megatts:
     # -- batched tensor-level pipeline (the measured hot path)
     def synthesize(self, phone_tokens, mels, phone_lens=None, mel_lens=None, forced_durations=None,
                    forced_codes=None, vocoder: bool = False, return_aux: bool = False, sampling=None, seeds=None,
-                   griffin_lim=None, loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0):
+                   griffin_lim=None, loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0,
+                   true_peak_ceiling_dbtp: Optional[float] = None):
         """phone_tokens int64 [B, Np], mels f32 [B, Tp, 80] -> (mel [B, Tm, 80], mel_lens) - the
         no_grad block of Megatts.forward (models/megatts2.py:353-368) for every utterance of the batch.
         `sampling` (sampling.PLMSampling; None = greedy) / `seeds` (int64 [B] or one int s -> s + b): sampled PLM codes.
@@ -549,7 +565,11 @@ class Megatts:
         `loudness_lufs` (None = off, exactly the call without it): aux["wav"] - HiFi-GAN's with vocoder=True and return_aux=True, or
         Griffin-Lim's - is brought to this integrated loudness per utterance over its real samples, in place on the device
         (MelFrontEnd.loudness_normalize; `peak_ceiling` > 0 caps the gain so that the sample peak stays under it; an utterance under
-        0.4 s or silent keeps its level)."""
+        0.4 s or silent keeps its level).  `true_peak_ceiling_dbtp` (None = off; needs loudness_lufs, excludes peak_ceiling > 0):
+        the gain is capped so that the TRUE peak stays at or under this many dBTP (e.g. -1.0), which the sample-peak ceiling cannot
+        promise - a 16 kHz signal has crests up to 3 dB over its samples."""
+        if true_peak_ceiling_dbtp is not None and loudness_lufs is None:
+            raise ValueError("true_peak_ceiling_dbtp caps the gain of the loudness normalisation: it needs loudness_lufs")
         if loudness_lufs is not None:
             gl_on = not (griffin_lim is None or griffin_lim is False)
             if not gl_on and not (vocoder and return_aux):
@@ -560,7 +580,7 @@ class Megatts:
             n = np.asarray(out_lens, np.int64)
             n = (n - 1) * HIFIGAN_HOP_LENGTH if gl_on else (n + 2 * int(getattr(hg, "inference_padding", 0))) * hg.hop
             _frontend().loudness_normalize(aux["wav"], np.maximum(n, 1).astype(np.int32), float(loudness_lufs), float(peak_ceiling),
-                                           sample_rate=HIFIGAN_SR, out=aux["wav"])
+                                           sample_rate=HIFIGAN_SR, out=aux["wav"], true_peak_ceiling_dbtp=true_peak_ceiling_dbtp)
             return mel, out_lens, aux
         if griffin_lim is None or griffin_lim is False:
             return self.native.synthesize_batch(phone_tokens, phone_lens, mels, mel_lens, forced_durations, forced_codes,
@@ -818,16 +838,22 @@ class Megatts:
     # loudness_lufs: None leaves the levels as the vocoder produced them; a number brings the vocoded prompt and the generated audio
     # EACH to that integrated loudness (BS.1770, MelFrontEnd.loudness_normalize; peak_ceiling > 0 caps the gain by the sample peak)
     # before they are concatenated and written, with either vocoder - the two halves of the file then sound equally loud.
+    # true_peak_ceiling_dbtp (None = off; needs loudness_lufs): each half's gain is capped so that its true peak stays under this many dBTP.
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
                 phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None, vocoder=None,
-                loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0):
+                loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0, true_peak_ceiling_dbtp: Optional[float] = None):
         import torch
+        if true_peak_ceiling_dbtp is not None and loudness_lufs is None:
+            raise ValueError("true_peak_ceiling_dbtp caps the gain of the loudness normalisation: it needs loudness_lufs")
         level = {} if loudness_lufs is None else {"loudness_lufs": float(loudness_lufs), "peak_ceiling": float(peak_ceiling)}
+        if true_peak_ceiling_dbtp is not None:
+            level["true_peak_ceiling_dbtp"] = float(true_peak_ceiling_dbtp)
 
         def levelled(x):          # the vocoded prompt, a 1-D device tensor
             if loudness_lufs is None:
                 return x
-            return _frontend().loudness_normalize(x.unsqueeze(0), None, float(loudness_lufs), float(peak_ceiling), sample_rate=HIFIGAN_SR)[0]
+            return _frontend().loudness_normalize(x.unsqueeze(0), None, float(loudness_lufs), float(peak_ceiling), sample_rate=HIFIGAN_SR,
+                                                  true_peak_ceiling_dbtp=true_peak_ceiling_dbtp)[0]
 
         if not (vocoder is None or vocoder == "griffin_lim" or isinstance(vocoder, dict)):
             raise ValueError(f"vocoder={vocoder!r}: None (HiFi-GAN when loaded) or 'griffin_lim'")

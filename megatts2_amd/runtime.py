@@ -29,6 +29,7 @@ F0_FRAME, F0_WINDOW, F0_MAX_LAG = 1024, 768, 256      # MT2_F0_FRAME, MT2_F0_WIN
 DTW_MAX_LEN, DTW_DIR_COLS = 4096, 16  # MT2_DTW_MAX_LEN, MT2_DTW_DIR_COLS
 PROSODY_FIELDS = 8                    # MT2_PROSODY_FIELDS
 LOUDNESS_FIELDS = 8                   # MT2_LOUDNESS_FIELDS
+EBU_FIELDS, TP_ZERO_CROSSINGS, TP_TAPS, TP_TILE = 18, 12, 24, 1024      # MT2_EBU_FIELDS, MT2_TP_ZERO_CROSSINGS, MT2_TP_TAPS, MT2_TP_TILE
 
 
 class NativeError(RuntimeError):
@@ -112,6 +113,10 @@ def load_library():
     lib.mt2_loudness_query.argtypes = [C.c_int, C.c_longlong] + [C.c_void_p] * 4
     lib.mt2_loudness.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     lib.mt2_loudness_normalize.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    lib.mt2_ebu_query.argtypes = [C.c_int, C.c_longlong] + [C.c_void_p] * 5
+    lib.mt2_true_peak_table.argtypes = [C.c_int, C.c_void_p]
+    lib.mt2_loudness_ebu.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.mt2_loudness_normalize_tp.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
     lib.mt2_workspace_fill.argtypes = [C.c_void_p, C.c_int]
     lib.mt2_workspace_peek.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     _LIB = lib
@@ -823,8 +828,8 @@ class MelFrontEnd:
 
     def loudness(self, wav, lens=None, sample_rate: Optional[int] = None, return_momentary: bool = False):
         """Integrated loudness (ITU-R BS.1770-4, gated; what EBU R 128 builds on) of a ragged batch of mono utterances on the device, by
-        the rule of csrc/loudness.hip / include/megatts2_hip.h; parity with pyloudnorm / libebur128 is unpinned, true peak and
-        loudness range are out of scope.  wav f32 [B, L] (device) at sample_rate (default audio.sample_rate; a multiple of 10 in
+        the rule of csrc/loudness.hip / include/megatts2_hip.h; parity with pyloudnorm / libebur128 is unpinned; true peak and
+        loudness range are `loudness_ebu`'s.  wav f32 [B, L] (device) at sample_rate (default audio.sample_rate; a multiple of 10 in
         [8000, 192000]) -> stats f64 [B, 8] (device): integrated LUFS (-inf for an utterance under 0.4 s or silent, NaN behind a
         non-finite sample), blocks, blocks over the absolute gate, blocks over both gates, the relative gate, the sample peak, the
         maximum momentary loudness, 1.0.  return_momentary: also f64 [B, max(1, blocks of the longest)] with the loudness of every
@@ -845,12 +850,44 @@ class MelFrontEnd:
         _check(self.lib.mt2_loudness(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, _ptr(stats), _ptr(mom), NB))
         return (stats, mom) if return_momentary else stats
 
+    def loudness_ebu(self, wav, lens=None, sample_rate: Optional[int] = None, return_momentary: bool = False, return_short_term: bool = False):
+        """The figures of an EBU-mode meter (EBU R 128 / Tech 3341) for a ragged batch of mono utterances on the device, by the rules of
+        csrc/loudness.hip and csrc/ebu.hip (include/megatts2_hip.h); parity with libebur128 / pyloudnorm is unpinned.  wav f32 [B, L]
+        (device) at sample_rate (default audio.sample_rate; a multiple of 10 in [8000, 192000]) -> stats f64 [B, 18] (device): fields
+        0-7 are `loudness`'s row bit for bit; 8 the true peak (linear; oversampled ceil(192000 / sample_rate) times, never under the
+        sample peak), 9 the oversampling factor, 10 the loudness range in LU (EBU Tech 3342; NaN under 3 s or for silence), 11 the
+        short-term blocks (3 s, every 100 ms), 12 those over -70 LUFS, 13 those over both gates, 14 the relative gate (20 LU under
+        the gated mean), 15 / 16 the 10th / 95th percentile, 17 the maximum short-term loudness.  return_momentary: also f64
+        [B, max(1, blocks of the longest)] as `loudness` returns it.  return_short_term: also f64 [B, max(1, short-term blocks of the
+        longest)], -inf behind an utterance's own blocks.  Samples beyond lens[b] are never read.  The call only enqueues."""
+        import torch
+        assert wav.is_cuda and wav.dim() == 2
+        wav = wav.contiguous().to(torch.float32)
+        B, L = wav.shape
+        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+        assert ln.shape == (B,)
+        sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
+        stats = torch.empty(B, EBU_FIELDS, device=wav.device, dtype=torch.float64)
+        ns = max(int(ln.max()), 0) // max(sr // 10, 1)
+        mom, NB, sht, NST = None, 0, None, 0
+        if return_momentary:
+            NB = max(1, ns - 3)
+            mom = torch.empty(B, NB, device=wav.device, dtype=torch.float64)
+        if return_short_term:
+            NST = max(1, ns - 29)
+            sht = torch.empty(B, NST, device=wav.device, dtype=torch.float64)
+        _check(self.lib.mt2_loudness_ebu(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, _ptr(stats), _ptr(mom), NB, _ptr(sht), NST))
+        res = (stats,) + ((mom,) if return_momentary else ()) + ((sht,) if return_short_term else ())
+        return res if len(res) > 1 else stats
+
     def loudness_normalize(self, wav, lens=None, target_lufs: float = -23.0, peak_ceiling: float = 0.0, sample_rate: Optional[int] = None,
-                           out=None, return_stats: bool = False):
+                           out=None, return_stats: bool = False, true_peak_ceiling_dbtp: Optional[float] = None):
         """Each utterance of a ragged batch brought to target_lufs by one gain g = 10^((target - I) / 20), I its integrated loudness
         (`loudness`): wav f32 [B, L] (device) -> out f32 [B, L] with out[b, :lens[b]] = wav[b, :lens[b]] * g_b (one f32 product) and
         zeros behind.  peak_ceiling > 0: g is capped so that the sample peak stays at or below it (the sample peak, not the true
-        peak).  An utterance whose loudness is not finite - under 0.4 s, silent, holding a non-finite sample - is copied unchanged
+        peak).  true_peak_ceiling_dbtp (None = off, exactly the call without it; e.g. -1.0): g is capped so that the true peak
+        (`loudness_ebu`) stays at or below 10^(dBTP / 20) - what a delivery specification means by a ceiling; it cannot be combined
+        with peak_ceiling > 0, and return_stats then gives the f64 [B, 18] of `loudness_ebu`.  An utterance whose loudness is not finite - under 0.4 s, silent, holding a non-finite sample - is copied unchanged
         (g = 1).  out: a contiguous f32 [B, L] device tensor to write into; it may be wav itself.  return_stats: also the f64
         [B, 8] of `loudness` for the INPUT, with g in the last field.  The gain is formed and read on the device: the call only
         enqueues, with no copy to the host and no wait."""
@@ -864,6 +901,13 @@ class MelFrontEnd:
         if out is None:
             out = torch.empty_like(wav)
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == wav.shape
+        if true_peak_ceiling_dbtp is not None:
+            if peak_ceiling > 0:
+                raise ValueError("peak_ceiling and true_peak_ceiling_dbtp exclude each other: state the ceiling one way")
+            stats = torch.empty(B, EBU_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
+            _check(self.lib.mt2_loudness_normalize_tp(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs),
+                                                      float(true_peak_ceiling_dbtp), _ptr(out), _ptr(stats)))
+            return (out, stats) if return_stats else out
         stats = torch.empty(B, LOUDNESS_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
         _check(self.lib.mt2_loudness_normalize(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs), float(peak_ceiling),
                                                _ptr(out), _ptr(stats)))
@@ -1729,6 +1773,25 @@ def loudness_query(sample_rate: int, L: int):
     c = np.zeros(10, np.float64)
     _check(load_library().mt2_loudness_query(int(sample_rate), int(L), C.byref(h), C.byref(nb), c.ctypes.data_as(C.c_void_p), C.byref(ws)))
     return h.value, nb.value, c, ws.value
+
+
+def ebu_query(sample_rate: int, L: int):
+    """mt2_ebu_query (no device needed) -> (oversample, taps, tile, short_term_blocks, workspace_bytes): o = ceil(192000 / sample_rate),
+    the taps of one phase of the true-peak filter (24), the positions one workgroup of the true-peak kernel takes (tile t holds
+    i in [tile * t - 12, tile * (t + 1) - 12)), nst = max(0, L // h - 29) and the arena bytes of a MelFrontEnd.loudness_ebu /
+    loudness_normalize(true_peak_ceiling_dbtp=) call with one utterance of L samples; NativeError where the rule refuses."""
+    o, taps, tile, nst, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0)
+    _check(load_library().mt2_ebu_query(int(sample_rate), int(L), C.byref(o), C.byref(taps), C.byref(tile), C.byref(nst), C.byref(ws)))
+    return o.value, taps.value, tile.value, nst.value, ws.value
+
+
+def true_peak_table(sample_rate: int):
+    """mt2_true_peak_table (no device needed) -> the interpolation table of the true-peak rule, float32 [o, 24]; row 0 is the unit
+    sample."""
+    o = ebu_query(sample_rate, 1)[0]
+    table = np.zeros((o, TP_TAPS), np.float32)
+    _check(load_library().mt2_true_peak_table(int(sample_rate), table.ctypes.data_as(C.c_void_p)))
+    return table
 
 
 def f0_query(L: int, sample_rate: int = 16000, hop: int = 256, fmin: float = 62.5, fmax: float = 500.0):

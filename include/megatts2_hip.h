@@ -933,7 +933,7 @@ int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top);
  *   residual    split (S > 1 K slices) | stat (un-split, row statistics handed on) | nostat      S= stat_nt= stat_w= a_planes= M= K= tile= nw=
  *               (tile: the configuration name of the GEMM; nw: the waves that split K if it ran on the tile-major weight-streaming kernel, else 0)
  *   ln_pending  reduce (S > 0 slabs summed) | plain      S= h_planes= M=
- *   attention   generic | reg | ds | lds | x6 | x3h      o_planes= B= qlen= kvlen=
+ *   attention   generic | reg | ds | lds | x6 | x3h      o_planes= B= qlen= kvlen= D=  (ragged launches: kvlen is the longest key range)
  *   tail        fpl | nofpl (ff.0 stores fp16 planes for ff.3 or not)      S1= S2= M= att_planes=
  * and of the vocoder (ch: channels, R: rows of the stage, tile: the configuration name of the launch):
  *   kind   voc-pre, voc-stage<i> (upsampler i and its three resblocks), voc-post
@@ -944,6 +944,13 @@ int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top);
  *   halo        fill (reflect edge mode: one entry per halo fill)      width= G=
  *   streams     1 | 3: the streams the stage's three resblock chains run on      ch= R=
  *   post        fused (mean + conv_post + tanh as one launch) | gemm      ch= k= R= tile=
+ * and of the parallel stages in front of and behind the AR steps (tile: the configuration name of the launch; M: rows with their gaps):
+ *   kind   mel-encoder (MRTE mel encoder), phone-encoder, cross (the cross attention of MRTE.tc_latent), vqpe, decoder
+ *   conv        first | block (a ConvBlock of a residual stack) | mid (the strided middle convolution) | last | ff (conv-FF)
+ *               tile= M= N= taps= groups= shared= (the groups read one input) wshared= (one weight) relued= (input stored ReLU'd) a_planes=
+ *   linear      qkv | out | ff | q | kv | vq (the VQ distance GEMM)      tile= M= N= K= nw=
+ *   ln          block (ReLU folded into the store) | residual (a stack's last, with the residual add) | plain      out_planes= act= M= groups=
+ *   attention   as above
  * The log is per handle and off by default; it observes only - nothing is timed, no HIP call is made for it, and the launches and
  * their arguments are the same with it on or off.  end() turns it off, writes the lines ('\n'-separated, NUL-terminated) into buf
  * and returns the bytes written, or -1 (NULL arguments, or the text does not fit cap); the records are dropped either way. */

@@ -299,7 +299,7 @@ int mt2_workspace_query(const mt2_model* m, int B, int Np_max, int Tp_max, int T
         return M * d + 3 * M * d + (long long)B * d + G * enc(0, d, ff) + enc(M + 2ll * B * G, d, ff) - enc(0, d, ff);
     };
     const long long H = cfg.mrte_hidden, st = cfg.mrte_stride;
-    const long long FR = rows(Tp_max, (int)std::max<long long>(st / 2, 2)), XR = rows((Tp_max - 1) / st + 1, 2), PR = rows(Np_max, 2);
+    const long long FR = rows(Tp_max, prompt_mel_gap(cfg)), XR = rows((Tp_max - 1) / st + 1, mel_context_gap(cfg)), PR = rows(Np_max, phone_gap(cfg));
     long long f = 0;                                                              // floats (ints counted as floats)
     f += 16 * (FR + XR + PR) + 64;                                               // integer plans
     f += FR * cfg.mel_bins + FR * H + 4 * FR * H * cfg.mrte_n_layer + XR * H * cfg.mrte_n_layer;
@@ -309,7 +309,7 @@ int mt2_workspace_query(const mt2_model* m, int B, int Np_max, int Tp_max, int T
         f += PR * cfg.adm_tc_emb_dim + (long long)B * (Np_max + 1) + 8ll * B;
         f += ar(cfg.adm_emb_dim + cfg.adm_tc_emb_dim, 4ll * cfg.adm_emb_dim, Np_max, m->adm_groups);
     }
-    const long long DR = rows(Tm_cap, 2), DIN = H + cfg.vq_dim, Tq = (Tm_cap + cfg.vq_stride - 1) / cfg.vq_stride;
+    const long long DR = rows(Tm_cap, decoder_gap(cfg)), DIN = H + cfg.vq_dim, Tq = (Tm_cap + cfg.vq_stride - 1) / cfg.vq_stride;
     f += 8 * DR + 4ll * B * Tq + DR * DIN + (long long)B * Tq * H + (long long)B * Np_max;
     if (flags & MT2_RUN_PLM) {
         const long long d = cfg.plm_vq_dim + cfg.plm_tc_dim;
@@ -318,7 +318,7 @@ int mt2_workspace_query(const mt2_model* m, int B, int Np_max, int Tp_max, int T
     }
     f += DR * cfg.dec_hidden * 5 + DR * cfg.mel_bins;
     if (flags & MT2_PROMPT_VQPE) {      // vqpe_rows on the prompt mel
-        const long long VR = rows(Tp_max, 2), QR = rows((Tp_max + cfg.vq_stride - 1) / cfg.vq_stride, 2);
+        const long long VR = rows(Tp_max, vqpe_gap(cfg)), QR = rows((Tp_max + cfg.vq_stride - 1) / cfg.vq_stride, vqpe_gap(cfg));
         const long long C = cfg.vq_hidden, G = cfg.vq_n_layers;
         f += 16 * (VR + QR) + VR * cfg.mel_bins + VR * C + 4 * VR * C * G + G * QR * C + 4 * QR * C * G + QR * C;
         f += QR * cfg.vq_dim + QR * cfg.vq_bins + 2 * QR;
@@ -484,7 +484,7 @@ int mt2_length_regulate(mt2_model* m, void* stream, const float* x, const int32_
     MT2_REQUIRE(B >= 1 && D >= 1, "bad arguments");
     MT2_CALL(m, stream);
     IntPlan ip;
-    FramePlan fp = plan_frames(ip, dur, Np_max, lens, B, iota_rows(B, Np_max), 8, 0, Tm_max);
+    FramePlan fp = plan_frames(ip, m->cfg, dur, Np_max, lens, B, iota_rows(B, Np_max), 8, 0, Tm_max);
     MT2_REQUIRE(fp.D.maxlen <= Tm_max, "Tm_max smaller than the longest regulated utterance");
     ip.upload(c.ws, c.m.pinned(), c.s);
     float* rows = c.ws.get<float>((size_t)fp.D.R * D);
@@ -640,7 +640,7 @@ int mt2_mel_decoder(mt2_model* m, void* stream, const float* x, const int32_t* l
     const int DIN = m->dec_first.cin, NM = m->cfg.mel_bins;
     for (int b = 0; b < B; ++b) MT2_REQUIRE(lens[b] >= 1 && lens[b] <= T_max, "length out of range");
     IntPlan ip;
-    RowSet D = make_rows(lens, B, 2);
+    RowSet D = make_rows(lens, B, decoder_gap(m->cfg));
     RowPlanOffsets oD = plan_rows(ip, D);
     const int o_map = plan_rowmap(ip, D, T_max);
     ip.upload(c.ws, c.m.pinned(), c.s);
@@ -1221,7 +1221,7 @@ int mt2_synthesize_batch_sampled(mt2_model* m, void* stream, const int64_t* phon
     const int32_t* dur = adm_durations(c, st, tc, phone_lens, Np_max, B, !(flags & MT2_SKIP_ADM), forced_dur, dur_out, dur_host);
     // :356-358  length regulation (gather) and max_pool1d(8, ceil) conditioning
     IntPlan ip;
-    FramePlan fp = plan_frames(ip, dur, Np_max, phone_lens, B, tc.P.off, cfg.vq_stride, Tq_cap, Tm_cap);
+    FramePlan fp = plan_frames(ip, cfg, dur, Np_max, phone_lens, B, tc.P.off, cfg.vq_stride, Tq_cap, Tm_cap);
     check_frames(fp, B, Tm_cap, Tq_cap, mel_lens);
     ip.upload(c.ws, c.m.pinned(), c.s);
     bind_rows(ip, fp.oD, fp.D);
@@ -1316,9 +1316,9 @@ int mt2_synthesize_prompt_conditioned_sampled(mt2_model* m, void* stream, const 
     // :356-358 for both sides: length regulation (gather) into ONE row buffer [prompt frames | target frames], then ONE
     // ceil-mode max-pool launch that writes the PLM conditioning of utterance b as [P prompt rows | tq[b] target rows]
     IntPlan ip;
-    FramePlan fp = plan_frames(ip, dur, Np_max, phone_lens, B, tc.P.off, pool, Tq_cap, Tm_cap);
+    FramePlan fp = plan_frames(ip, cfg, dur, Np_max, phone_lens, B, tc.P.off, pool, Tq_cap, Tm_cap);
     std::vector<int> prow0(tc.P.off.begin() + B, tc.P.off.end());
-    FramePlan pp = plan_frames(ip, prompt_dur, Npp_max, prompt_phone_lens, B, prow0, pool, 0, 0);
+    FramePlan pp = plan_frames(ip, cfg, prompt_dur, Npp_max, prompt_phone_lens, B, prow0, pool, 0, 0);
     check_frames(fp, B, Tm_cap, Tq_cap, mel_lens);
     std::vector<int> total(B), q0(B);
     int qr = 0;
@@ -1395,7 +1395,8 @@ int mt2_gemm_trace_shapes(mt2_model* m, char* buf, int cap, int top) {
     std::lock_guard<std::mutex> lk(m->call_mutex);
     return gemm_trace_shapes(m->opts, buf, cap, top);
 }
-// Form log of the AR step and vocoder wiring (mt2_model::form_log; written by form_note in model_stages.hip): host-side text only
+// Form log of the AR step wiring, the vocoder wiring and the parallel stages - MRTE mel encoder, phone encoder and cross attention, VQ
+// prosody encoder, mel decoder - (mt2_model::form_log; written by form_note in model_stages.hip): host-side text only
 int mt2_form_log_begin(mt2_model* m) {
     MT2_API_BEGIN
     MT2_REQUIRE(m != nullptr, "null model handle");

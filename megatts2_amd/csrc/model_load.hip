@@ -343,6 +343,10 @@ void finalize_model(mt2_model& m) {
     m.has_plm = L.has("plm.predict_layer.weight");
     MT2_REQUIRE(m.has_g || m.has_adm || m.has_plm || L.has("hifigan.conv_pre.weight"), "no tensors were loaded");
     if (m.has_g) {
+    // "same" padding is (k - 1) / 2 on both sides: with an even kernel the reference's own output is a row short and its residual
+    // adds fail - refused here, not at the first launch
+    MT2_REQUIRE(c.mrte_kernel >= 1 && (c.mrte_kernel & 1) && c.vq_kernel >= 1 && (c.vq_kernel & 1) && c.dec_kernel >= 1 && (c.dec_kernel & 1),
+                "the convolution kernel sizes of G (mrte mel_kernel_size, vqpe kernel_size, decoder kernel_size) must be odd");
     // ---- G.mrte
     m.phone_emb = L.mat("G.mrte.phone_embedding.word_embeddings.weight", c.phone_vocab, H);
     (void)L.get("G.mrte.phone_pos_embedding.alpha", {1});

@@ -38,6 +38,21 @@ static RowSet make_rows(const int* lens, int B, int G) {
     return rs;
 }
 
+// Gap rows between the utterances of a batch, per row set of the parallel stages.  Zero padding IS the gap: a "same" convolution of
+// one utterance has to read zeros behind its ends, never a neighbour's rows, so the gap covers the widest halo, (k - 1) / 2, of the
+// convolutions that run over the row set - the kernels come from the checkpoint's configuration.  Never less than the 2 rows (8 prompt
+// rows) of the production model (kernels 3 and 5, stride 16), whose row layout is what it always was.  mt2_workspace_query counts the
+// same gaps; the stage drivers refuse a row set narrower than their halo (require_gap).
+static int halo_of(int k) { return (k - 1) / 2; }
+static int prompt_mel_gap(const mt2_config& cfg) { return std::max({cfg.mrte_stride / 2, halo_of(cfg.mrte_kernel), 2}); }
+static int mel_context_gap(const mt2_config& cfg) { return std::max(halo_of(cfg.mrte_kernel), 2); }
+static int phone_gap(const mt2_config&) { return 2; }      // the conv-FF kernel is the literal 5 (encoder_layer)
+static int decoder_gap(const mt2_config& cfg) { return std::max(halo_of(cfg.dec_kernel), 2); }
+static int vqpe_gap(const mt2_config& cfg) { return std::max(halo_of(cfg.vq_kernel), 2); }      // frame rows and pooled rows
+static void require_gap(const RowSet& rs, int halo) {
+    MT2_REQUIRE(rs.G >= halo, "the gap between utterances is narrower than a convolution's halo");
+}
+
 struct RowPlanOffsets { int valid, start, len; };
 static RowPlanOffsets plan_rows(IntPlan& ip, const RowSet& rs) {
     std::vector<int> valid(rs.R, 0);
@@ -71,11 +86,12 @@ struct Ctx {
 };
 
 // One line of the form log (mt2_model::form_log): "kind point form key=value ...".  Written only between mt2_form_log_begin and
-// mt2_form_log_end and only inside ar_step_layers and hifigan_rows (form_kind set); it records a decision already taken and takes none.
+// mt2_form_log_end and only inside ar_step_layers, hifigan_rows and the drivers of the parallel stages - mel_context_rows, tc_latent_rows,
+// vqpe_rows, decoder_rows - (form_kind set); it records a decision already taken and takes none.
 static void form_kind(const Ctx& c, const char* kind) {      // the layer kind of the entries that follow (nothing is written with the log off)
     if (c.m.form_log_on) c.m.form_kind = kind;
 }
-struct FormScope {      // ar_step_layers, hifigan_rows: no kind outlives it, on any exit path - nothing outside them is logged
+struct FormScope {      // ar_step_layers, hifigan_rows, the parallel stages: no kind outlives it, on any exit path - nothing outside them is logged
     mt2_model& m;
     ~FormScope() { m.form_kind = nullptr; }
 };
@@ -88,6 +104,19 @@ static void form_note(const Ctx& c, const char* point, const char* form, const c
     if (n > 0 && n < (int)sizeof buf) vsnprintf(buf + n, sizeof buf - n, fmt, ap);
     va_end(ap);
     c.m.form_log.emplace_back(buf);
+}
+
+// form log of the parallel stages (kinds mel-encoder, phone-encoder, cross, vqpe, decoder): a convolution just launched - which of
+// first | block | mid | last | ff; `shared`: the groups read one input (strideX = 0), `wshared`: one weight (strideW = 0); relued: the
+// input is stored ReLU'd (no prologue) - and a linear layer just launched
+static void form_note_conv(const Ctx& c, const char* which, const GemmP& p, bool relued = false) {
+    if (!c.m.form_log_on || !c.m.form_kind) return;
+    const int G = p.groups > 0 ? p.groups : 1;
+    form_note(c, "conv", which, "tile=%s M=%d N=%d taps=%d groups=%d shared=%d wshared=%d relued=%d a_planes=%d", c.m.opts.last_cfg, p.M, p.N,
+              p.taps > 0 ? p.taps : 1, G, G > 1 && p.strideX == 0 ? 1 : 0, G > 1 && p.strideW == 0 ? 1 : 0, relued ? 1 : 0, p.a_planes);
+}
+static void form_note_linear(const Ctx& c, const char* which, int M, int N, int K) {
+    form_note(c, "linear", which, "tile=%s M=%d N=%d K=%d nw=%d", c.m.opts.last_cfg, M, N, K, c.m.opts.last_sk_nw);
 }
 
 // the bf16 planes of a weight pointer, if its buffer has them (mt2_model::planes, sorted by base)
@@ -264,12 +293,13 @@ static LnOps ln2_ff0(const EncLayerW& w, int d) {
 // nn.Conv1d(k, stride 1, padding (k-1)/2 * dil, dilation dil) over gap-padded rows
 static void conv_same(const Ctx& c, const float* x, int ldx, int R, const ConvW& w, float* y, int ldy,
                       const int* valid, int pro_act = ACT_NONE, float slope = 0.f, int epi_act = ACT_NONE,
-                      const float* Rsd = nullptr, int ldr = 0, int dil = 1) {
+                      const float* Rsd = nullptr, int ldr = 0, int dil = 1, const char* note = nullptr) {
     GemmP p{};
     p.X = x; p.ldx = ldx; p.Rx = R; p.taps = w.k; p.dil = dil; p.shift0 = -((w.k - 1) / 2) * dil; p.Cin = w.cin;
     p.W = w.w; p.bias = w.b; p.R = Rsd; p.ldr = ldr; p.valid = valid; p.C = y; p.ldc = ldy; p.M = R; p.N = w.cout;
     p.pro_act = pro_act; p.pro_slope = slope; p.epi_act = epi_act;
     gemm(c, p);
+    if (note) form_note_conv(c, note, p);      // (the parallel stages; the vocoder books its convolutions itself)
 }
 
 // y = x + conv2(lrelu(conv1(lrelu(x)))) (ResBlock1's pair: conv1 dilated, conv2 dilation 1, both k taps, C -> C) as one launch of
@@ -359,7 +389,9 @@ static float* run_stack(const Ctx& c, const StackW& w, const float* x_in, bool s
         };
         for (int blk = 0; blk < w.nblock; ++blk) {
             const size_t e = w.idx(st, blk);
-            gemm(c, block_conv(blk, bin, bin_shared, bin_relued, bin_planes));
+            const GemmP launched = block_conv(blk, bin, bin_shared, bin_relued, bin_planes);
+            gemm(c, launched);
+            form_note_conv(c, "block", launched, bin_relued);
             const bool last = blk == w.nblock - 1;
             bool planes = false;
             if (!last && (c.m.opts.a_planes & 1)) {       // will the next block's conv take Y as planes?
@@ -373,6 +405,7 @@ static float* run_stack(const Ctx& c, const StackW& w, const float* x_in, bool s
                           cur_shared ? R : 0, R);
             else   // next ConvBlock starts with ReLU (convnet.py:24): fold it into this LayerNorm's store
                 layernorm(c, T, C, w.g + e * C, w.be + e * C, R * G, C, Y, C, valid, R, nullptr, 0, 0, R, ACT_RELU, planes);
+            form_note(c, "ln", last ? "residual" : "block", "out_planes=%d act=%d M=%d groups=%d", planes ? 1 : 0, last ? 0 : 1, R, G);
             bin = Y;
             bin_shared = false;
             bin_relued = !last;
@@ -419,8 +452,8 @@ static void form_note_attention(const Ctx& c, const AttnP& a) {
     if (!c.m.form_log_on || !c.m.form_kind) return;
     static const char* const kName[] = {"none", "generic", "reg", "ds", "lds", "x6", "x3h"};
     const int k = attn_route(a).kernel;
-    form_note(c, "attention", k >= 0 && k <= ATTN_X3H ? kName[k] : "?", "o_planes=%d B=%d qlen=%d kvlen=%d", a.o_planes, a.B, a.max_qlen,
-              a.u_kvlen);
+    form_note(c, "attention", k >= 0 && k <= ATTN_X3H ? kName[k] : "?", "o_planes=%d B=%d qlen=%d kvlen=%d D=%d", a.o_planes, a.B, a.max_qlen,
+              a.kv_len ? a.max_kvlen : a.u_kvlen, a.D);      // (ragged launches: the longest key range)
 }
 static void attention_self(const Ctx& c, const EncW& e, const AttnGeom& g, const float* qkv, float* att, bool o_planes = false) {
     AttnP a = attn_params(c, e);
@@ -438,19 +471,26 @@ static void encoder_layer(const Ctx& c, const EncW& e, const EncLayerW& w, float
                           const int* valid, const EncScratch& s) {
     const int d = e.d;
     layernorm(c, x, d, w.ln1g, w.ln1b, M, d, s.h, d, valid);
+    form_note(c, "ln", "plain", "out_planes=0 act=0 M=%d groups=1", M);
     linear(c, s.h, d, M, w.wqkv, w.bqkv, 3 * d, d, s.qkv, 3 * d);
+    form_note_linear(c, "qkv", M, 3 * d, d);
     attention_self(c, e, g, s.qkv, s.att);
     linear(c, s.att, d, M, w.wo, w.bo, d, d, x, d, x, d, valid);            // x = x + out_proj(att)
+    form_note_linear(c, "out", M, d, d);
     if (e.conv_ff) {
         // x = norm2(x); x = x + conv2(relu(conv1(x)))   (transformer.py:95-99; residual from the NORMED x)
         layernorm(c, x, d, w.ln2g, w.ln2b, M, d, s.h, d, valid);
+        form_note(c, "ln", "plain", "out_planes=0 act=0 M=%d groups=1", M);
         ConvW c1{w.ff0w, w.ff0b, e.ff, d, 5}, c2{w.ff1w, w.ff1b, d, e.ff, 5};
-        conv_same(c, s.h, d, M, c1, s.f, e.ff, valid, ACT_NONE, 0.f, ACT_RELU);
-        conv_same(c, s.f, e.ff, M, c2, x, d, valid, ACT_NONE, 0.f, ACT_NONE, s.h, d);
+        conv_same(c, s.h, d, M, c1, s.f, e.ff, valid, ACT_NONE, 0.f, ACT_RELU, nullptr, 0, 1, "ff");
+        conv_same(c, s.f, e.ff, M, c2, x, d, valid, ACT_NONE, 0.f, ACT_NONE, s.h, d, 1, "ff");
     } else {
         layernorm(c, x, d, w.ln2g, w.ln2b, M, d, s.h, d, valid);
+        form_note(c, "ln", "plain", "out_planes=0 act=0 M=%d groups=1", M);
         linear(c, s.h, d, M, w.ff0w, w.ff0b, e.ff, d, s.f, e.ff, nullptr, 0, nullptr, ACT_RELU);
+        form_note_linear(c, "ff", M, e.ff, d);
         linear(c, s.f, e.ff, M, w.ff1w, w.ff1b, d, e.ff, x, d, x, d, valid);
+        form_note_linear(c, "ff", M, d, e.ff);
     }
 }
 
@@ -783,6 +823,11 @@ static float* mel_context_rows(const Ctx& c, const float* xmel, int ld_mel, RowS
                                const int* d_rowbase) {
     mt2_model& m = c.m;
     const int C = m.cfg.mrte_hidden, G = m.mel_s1.groups;
+    // zero padding IS the gap: no convolution may reach across it into a neighbour (prompt_mel_gap, mel_context_gap)
+    require_gap(F, std::max({halo_of(m.mel_first.k), halo_of(m.mel_s1.k), m.cfg.mrte_stride / 2}));
+    require_gap(X, std::max(halo_of(m.mel_s2.k), halo_of(m.mel_last.k)));
+    const FormScope form_scope{m};
+    form_kind(c, "mel-encoder");
     float* h0 = c.ws.get<float>((size_t)F.R * C);
     {
         GemmP p{};
@@ -790,6 +835,7 @@ static float* mel_context_rows(const Ctx& c, const float* xmel, int ld_mel, RowS
         p.Cin = m.mel_first.cin; p.W = m.mel_first.w; p.bias = m.mel_first.b; p.valid = F.d_valid;
         p.C = h0; p.ldc = C; p.M = F.R; p.N = C;
         gemm(c, p);
+        form_note_conv(c, "first", p);
     }
     float* s1 = run_stack(c, m.mel_s1, h0, true, F.R, F.d_valid);
     float* mid = c.ws.get<float>((size_t)G * X.R * C);
@@ -799,12 +845,13 @@ static float* mel_context_rows(const Ctx& c, const float* xmel, int ld_mel, RowS
         p.taps = m.mel_mid.k; p.Cin = C; p.W = m.mel_mid.w; p.strideW = 0; p.bias = m.mel_mid.b; p.strideB = 0;
         p.valid = X.d_valid; p.C = mid; p.strideC = (long long)X.R * C; p.ldc = C; p.M = X.R; p.N = C; p.groups = G;
         gemm(c, p);
+        form_note_conv(c, "mid", p);
     }
     float* s2 = run_stack(c, m.mel_s2, mid, false, X.R, X.d_valid);
     float* sum = c.ws.get<float>((size_t)X.R * C);
     MT2_HIP(launch_sum_groups(s2, (long long)X.R * C, G, C, sum, C, C, X.R, c.s));
     float* ctx = c.ws.get<float>((size_t)X.R * C);
-    conv_same(c, sum, C, X.R, m.mel_last, ctx, C, X.d_valid);
+    conv_same(c, sum, C, X.R, m.mel_last, ctx, C, X.d_valid, ACT_NONE, 0.f, ACT_NONE, nullptr, 0, 1, "last");
     return ctx;
 }
 
@@ -816,13 +863,13 @@ struct MelPlan {
 static MelPlan plan_mel(IntPlan& ip, const mt2_config& cfg, const int* mel_lens, int B, int Tp_max, int Tc_max) {
     MelPlan mp;
     const int s = cfg.mrte_stride;
-    mp.F = make_rows(mel_lens, B, std::max(s / 2, 2));
+    mp.F = make_rows(mel_lens, B, prompt_mel_gap(cfg));
     std::vector<int> xl(B);
     for (int b = 0; b < B; ++b) {
         MT2_REQUIRE(mel_lens[b] >= 1 && mel_lens[b] <= Tp_max, "prompt mel length out of range");
         xl[b] = (mel_lens[b] - 1) / s + 1;      // Conv1d(k = s+1, stride s, pad s/2) output length
     }
-    mp.X = make_rows(xl.data(), B, 2);
+    mp.X = make_rows(xl.data(), B, mel_context_gap(cfg));
     mp.oF = plan_rows(ip, mp.F);
     mp.oX = plan_rows(ip, mp.X);
     mp.o_rowmapF = plan_rowmap(ip, mp.F, Tp_max);
@@ -940,7 +987,9 @@ static TcResult tc_latent_rows(const Ctx& c, const std::vector<PhoneSet>& sets, 
             MT2_REQUIRE(sets[s_].lens[b] >= 1 && sets[s_].lens[b] <= sets[s_].Np_max, "phone length out of range");
             all_lens[s_ * B + b] = sets[s_].lens[b];
         }
-    RowSet P = make_rows(all_lens.data(), BS, 2);
+    RowSet P = make_rows(all_lens.data(), BS, phone_gap(cfg));
+    require_gap(P, halo_of(5));                       // the conv-FF kernel of encoder_layer
+    const FormScope form_scope{m};
     MT2_REQUIRE(P.maxlen <= cfg.max_positions, "phone sequence longer than the positional table");
     RowPlanOffsets oP = plan_rows(ip, P);
     std::vector<int> idmap(P.R, -1);                 // row -> index into ITS SET's padded [B, Np_max] id tensor (gap rows: -1)
@@ -1000,25 +1049,32 @@ static TcResult tc_latent_rows(const Ctx& c, const std::vector<PhoneSet>& sets, 
     EncScratch sc = enc_scratch(c, m.phone_enc, P.R);
     AttnGeom g;
     g.start = P.d_start; g.len = P.d_len; g.B = BS; g.max_len = P.maxlen;
+    form_kind(c, "phone-encoder");                    // (mel_context_rows has left no kind behind)
     for (auto& lw : m.phone_enc.layers) encoder_layer(cp, m.phone_enc, lw, x, P.R, g, P.d_valid, sc);
 
     // cross attention, ONE head of width H (mrte.py:131-135,167), LayerNorm, ReLU (:168-169)
+    form_kind(c, "cross");
     float* q = sc.h;
     linear(cp, x, H, P.R, m.x_wq, m.x_bq, H, H, q, H);
+    form_note_linear(c, "q", P.R, H, H);
     MT2_HIP(hipEventRecord(m.ev_join[0], side));
     MT2_HIP(hipStreamWaitEvent(c.s, m.ev_join[0], 0));
     float* kv = c.ws.get<float>((size_t)mp.X.R * 2 * H);
     linear(c, ctx, H, mp.X.R, m.x_wkv, m.x_bkv, 2 * H, H, kv, 2 * H);
+    form_note_linear(c, "kv", mp.X.R, 2 * H, H);
     AttnP a = attn_params(c, 1, H);
     a.Q = q; a.ldq = H; a.K = kv; a.ldk = 2 * H; a.V = kv + H; a.ldv = 2 * H; a.O = sc.att; a.ldo = H;
     a.q_start = P.d_start; a.q_len = P.d_len;
     a.kv_start = S > 1 ? ip2.dev(o_kvs) : mp.X.d_start; a.kv_len = S > 1 ? ip2.dev(o_kvl) : mp.X.d_len;
     a.B = BS; a.max_qlen = P.maxlen; a.max_kvlen = mp.X.maxlen;
     MT2_HIP(launch_attention(a, c.s));
+    form_note_attention(c, a);
     float* o = c.ws.get<float>((size_t)P.R * H);
     linear(c, sc.att, H, P.R, m.x_wo, m.x_bo, H, H, o, H);
+    form_note_linear(c, "out", P.R, H, H);
     float* tc = c.ws.get<float>((size_t)P.R * H);
     layernorm(c, o, H, m.x_ng, m.x_nb, P.R, H, tc, H, P.d_valid, 0, nullptr, 0, 0, 0, ACT_RELU);
+    form_note(c, "ln", "plain", "out_planes=0 act=1 M=%d groups=1", P.R);
     return {tc, P};
 }
 static TcResult tc_latent_rows(const Ctx& c, const int64_t* phone, const int* phone_lens, int Np_max,
@@ -1308,7 +1364,7 @@ static void plm_run(const Ctx& c, const float* cond, int ld_c, const std::vector
 // length regulation, PLM conditioning, decoder
 
 struct FramePlan {
-    RowSet D;                 // mel frames, gap 2
+    RowSet D;                 // mel frames, gap decoder_gap
     std::vector<int> tq;      // prosody tokens per utterance
     std::vector<int> q_row0;  // first cond row of each utterance (compact, no gaps)
     int Qrows = 0;
@@ -1316,7 +1372,7 @@ struct FramePlan {
     RowPlanOffsets oD;
 };
 // dur: host [B, dstride]; tc rows of utterance b start at tc_row0[b]; codes are addressed as b*code_stride + q
-static FramePlan plan_frames(IntPlan& ip, const int* dur, int dstride, const int* lens, int B,
+static FramePlan plan_frames(IntPlan& ip, const mt2_config& cfg, const int* dur, int dstride, const int* lens, int B,
                              const std::vector<int>& tc_row0, int pool, int code_stride, int out_stride) {
     FramePlan fp;
     std::vector<int> tm(B);
@@ -1329,7 +1385,7 @@ static FramePlan plan_frames(IntPlan& ip, const int* dur, int dstride, const int
         MT2_REQUIRE(s < (1 << 24), "utterance too long");
         tm[b] = (int)s;
     }
-    fp.D = make_rows(tm.data(), B, 2);
+    fp.D = make_rows(tm.data(), B, decoder_gap(cfg));
     fp.oD = plan_rows(ip, fp.D);
     fp.o_rowmapD = plan_rowmap(ip, fp.D, out_stride > 0 ? out_stride : 1);
     std::vector<int> tcmap(fp.D.R, -1), codemap(fp.D.R, -1);
@@ -1365,11 +1421,14 @@ static FramePlan plan_frames(IntPlan& ip, const int* dur, int dstride, const int
 static float* decoder_rows(const Ctx& c, const float* xdec, const RowSet& D) {
     mt2_model& m = c.m;
     const int H = m.cfg.dec_hidden, DIN = m.dec_first.cin;
+    require_gap(D, std::max({halo_of(m.dec_first.k), halo_of(m.dec_stack.k), halo_of(m.dec_last.k)}));      // decoder_gap
+    const FormScope form_scope{m};
+    form_kind(c, "decoder");
     float* h0 = c.ws.get<float>((size_t)D.R * H);
-    conv_same(c, xdec, DIN, D.R, m.dec_first, h0, H, D.d_valid);
+    conv_same(c, xdec, DIN, D.R, m.dec_first, h0, H, D.d_valid, ACT_NONE, 0.f, ACT_NONE, nullptr, 0, 1, "first");
     float* s = run_stack(c, m.dec_stack, h0, true, D.R, D.d_valid);
     float* mel = c.ws.get<float>((size_t)D.R * m.cfg.mel_bins);
-    conv_same(c, s, H, D.R, m.dec_last, mel, m.cfg.mel_bins, D.d_valid);
+    conv_same(c, s, H, D.R, m.dec_last, mel, m.cfg.mel_bins, D.d_valid, ACT_NONE, 0.f, ACT_NONE, nullptr, 0, 1, "last");
     return mel;
 }
 
@@ -1383,13 +1442,17 @@ static VqpeResult vqpe_rows(const Ctx& c, IntPlan& ip, const float* mel, int mel
     const mt2_config& cfg = m.cfg;
     const int C = cfg.vq_hidden, G = m.vq_s1.groups, st = cfg.vq_stride, Dq = cfg.vq_dim;
     VqpeResult r;
-    r.F = make_rows(lens, B, 2);
+    r.F = make_rows(lens, B, vqpe_gap(cfg));
     std::vector<int> ql(B);
     for (int b = 0; b < B; ++b) {
         MT2_REQUIRE(lens[b] >= 1 && lens[b] <= T_max, "mel length out of range");
         ql[b] = (lens[b] + st - 1) / st;
     }
-    r.Q = make_rows(ql.data(), B, 2);
+    r.Q = make_rows(ql.data(), B, vqpe_gap(cfg));
+    require_gap(r.F, std::max(halo_of(m.vq_first.k), halo_of(m.vq_s1.k)));
+    require_gap(r.Q, std::max(halo_of(m.vq_s2.k), halo_of(m.vq_last.k)));
+    const FormScope form_scope{m};
+    form_kind(c, "vqpe");
     RowPlanOffsets oF = plan_rows(ip, r.F), oQ = plan_rows(ip, r.Q);
     r.o_rowmapF = plan_rowmap(ip, r.F, T_max);
     r.o_rowmapQ = plan_rowmap(ip, r.Q, Tq_max);
@@ -1416,6 +1479,7 @@ static VqpeResult vqpe_rows(const Ctx& c, IntPlan& ip, const float* mel, int mel
         p.Cin = m.vq_first.cin; p.W = m.vq_first.w; p.bias = m.vq_first.b; p.valid = r.F.d_valid;
         p.C = h0; p.ldc = C; p.M = r.F.R; p.N = C;
         gemm(c, p);
+        form_note_conv(c, "first", p);
     }
     float* s1 = run_stack(c, m.vq_s1, h0, true, r.F.R, r.F.d_valid);
     float* mid = c.ws.get<float>((size_t)G * r.Q.R * C);     // MaxPool1d(stride, ceil_mode=True), vqpe.py:38
@@ -1426,10 +1490,11 @@ static VqpeResult vqpe_rows(const Ctx& c, IntPlan& ip, const float* mel, int mel
     float* sum = c.ws.get<float>((size_t)r.Q.R * C);
     MT2_HIP(launch_sum_groups(s2, (long long)r.Q.R * C, G, C, sum, C, C, r.Q.R, c.s));
     r.ze = c.ws.get<float>((size_t)r.Q.R * Dq);
-    conv_same(c, sum, C, r.Q.R, m.vq_last, r.ze, Dq, r.Q.d_valid);
+    conv_same(c, sum, C, r.Q.R, m.vq_last, r.ze, Dq, r.Q.d_valid, ACT_NONE, 0.f, ACT_NONE, nullptr, 0, 1, "last");
     // EuclideanCodebook.quantize: distance GEMM + ordered argmax
     float* xe = c.ws.get<float>((size_t)r.Q.R * cfg.vq_bins);
     linear(c, r.ze, Dq, r.Q.R, m.codebook, nullptr, cfg.vq_bins, Dq, xe, cfg.vq_bins);
+    form_note_linear(c, "vq", r.Q.R, cfg.vq_bins, Dq);
     r.idx = c.ws.get<int64_t>(r.Q.R);
     MT2_HIP(launch_vq_argmin(r.ze, Dq, Dq, xe, cfg.vq_bins, m.codebook_sq, cfg.vq_bins, r.Q.d_valid, r.idx, r.Q.R,
                              c.s));

@@ -177,10 +177,11 @@ struct mt2_model {
 
     mt2::EngineOpts opts;     // tuning / measurement switches of THIS handle (no process globals)
 
-    // form log (tests; mt2_form_log_begin / _end): while it is on, every decision point of the AR step wiring and of the vocoder
-    // wiring (model_stages.hip: ar_step_layers and what it calls; hifigan_rows) appends one text line "kind point form key=value ...",
-    // in call order.  It observes only: nothing is timed, no HIP call is made for it, no launch or argument depends on it.  form_kind
-    // is the layer kind / vocoder stage whose entries are being written (nullptr outside those two functions: nothing is logged there).
+    // form log (tests; mt2_form_log_begin / _end): while it is on, every decision point of the AR step wiring, of the vocoder wiring
+    // and of the parallel stages (model_stages.hip: ar_step_layers and what it calls; hifigan_rows; mel_context_rows, tc_latent_rows,
+    // vqpe_rows, decoder_rows with run_stack and encoder_layer) appends one text line "kind point form key=value ...", in call order.
+    // It observes only: nothing is timed, no HIP call is made for it, no launch or argument depends on it.  form_kind is the layer
+    // kind / vocoder stage / parallel stage whose entries are being written (nullptr outside those drivers: nothing is logged there).
     bool form_log_on = false;
     const char* form_kind = nullptr;
     std::vector<std::string> form_log;

@@ -708,13 +708,14 @@ class NativeModel:
                 for i in range(n)]
 
     def form_log_begin(self) -> None:
-        """Start recording the decisions of the AR step and vocoder wiring (mt2_form_log_begin): observation only, off by default."""
+        """Start recording the decisions of the AR step wiring, the vocoder wiring and the parallel stages (mt2_form_log_begin):
+        observation only, off by default."""
         _check(self.lib.mt2_form_log_begin(self.h))
 
     def form_log_end(self):
         """-> list of tuples (kind, point, form, attrs) in call order since form_log_begin(): the layer kind (first-fill, first-incr,
-        mid, last-skinny, last-split, last-fused; voc-pre, voc-stage<i>, voc-post), the decision point (ln_linear, residual, ln_pending,
-        attention, tail; pre, upsample, mean, pair, halo, streams, post), the form
+        mid, last-skinny, last-split, last-fused; voc-pre, voc-stage<i>, voc-post; mel-encoder, phone-encoder, cross, vqpe, decoder), the
+        decision point (ln_linear, residual, ln_pending, attention, tail; pre, upsample, mean, pair, halo, streams, post; conv, linear, ln), the form
         taken there and a dict of the entry's key=value fields (ints where they parse as ints) - include/megatts2_hip.h."""
         buf = C.create_string_buffer(1 << 20)
         n = self.lib.mt2_form_log_end(self.h, buf, len(buf))

@@ -102,6 +102,15 @@ thread_local CallScope* CallScope::open_call = nullptr;
 #define MT2_CALL(m_, stream_)          \
     CallScope scope_((m_), (stream_)); \
     Ctx c{*(m_), scope_.s, (m_)->ws}
+// the tail of the audio wrappers, behind their argument checks (every refusal of the arguments is decided before the handle is looked
+// at, and before the first HIP call): the device, then the call.  MT2_AUDIO_CALL checks the handle first, for the wrappers whose
+// argument checks have not
+#define MT2_DEVICE_CALL(m_, stream_)                            \
+    if (mt2_device_check() != 0) throw Error(g_last_error);     \
+    MT2_CALL(m_, stream_)
+#define MT2_AUDIO_CALL(m_, stream_)                             \
+    MT2_REQUIRE((m_) != nullptr, "null model handle");          \
+    MT2_DEVICE_CALL(m_, stream_)
 
 // utterance rows with `pad` replicated frames on both sides (speechbrain HifiganGenerator.inference pads the mel with
 // F.pad(c, (p, p), "replicate") before the generator): returns per-row source index into a [*, stride] layout
@@ -707,8 +716,7 @@ int mt2_mel_spectrogram(mt2_model* m, void* stream, const mt2_audio_config* ac, 
                         int L_max, int B, float* mel, int T_max) {
     MT2_API_BEGIN
     MT2_REQUIRE(m != nullptr && ac != nullptr && B >= 1, "bad arguments");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_DEVICE_CALL(m, stream);
     mel_spectrogram_run(c, *ac, wav, lens, L_max, B, mel, T_max);
     MT2_API_END
 }
@@ -741,8 +749,7 @@ int mt2_resample(mt2_model* m, void* stream, const float* wav, const int32_t* le
                  float* out, int Lout_max, int32_t* out_lens) {
     MT2_API_BEGIN
     MT2_REQUIRE(m != nullptr && B >= 1 && L_max >= 1 && Lout_max >= 1, "bad arguments");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_DEVICE_CALL(m, stream);
     resample_run(c, wav, lens, L_max, B, sr_in, sr_out, flags, out, Lout_max, out_lens);
     MT2_API_END
 }
@@ -751,8 +758,7 @@ int mt2_resample(mt2_model* m, void* stream, const float* wav, const int32_t* le
 int mt2_peak_normalize(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, float* out) {
     MT2_API_BEGIN
     MT2_REQUIRE(m != nullptr && B >= 1 && L_max >= 1, "bad arguments");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_DEVICE_CALL(m, stream);
     peak_normalize_run(c, wav, lens, L_max, B, out);
     MT2_API_END
 }
@@ -772,8 +778,7 @@ int mt2_trim_silence(mt2_model* m, void* stream, const float* wav, const int32_t
                      int Lout_max, int32_t* bounds, float* energy, int F_max) {
     MT2_API_BEGIN
     MT2_REQUIRE(m != nullptr && B >= 1 && L_max >= 1 && Lout_max >= 1, "bad arguments");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_DEVICE_CALL(m, stream);
     trim_run(c, wav, lens, L_max, B, top_db, out, Lout_max, bounds, energy, F_max);
     MT2_API_END
 }
@@ -788,7 +793,7 @@ int mt2_f0_query(int sample_rate, int hop, float fmin, float fmax, long long L, 
     if (frames) *frames = (int)(1 + L / hop);
     if (lag_min) *lag_min = lo;
     if (lag_max) *lag_max = hi;
-    if (workspace_bytes) *workspace_bytes = (4ll * 65535 + 255) & ~255ll;      // the lengths of the largest batch, nothing else
+    if (workspace_bytes) *workspace_bytes = (long long)arena_round(sizeof(int) * 65535);      // the lengths of the largest batch, nothing else
     MT2_API_END
 }
 
@@ -799,10 +804,8 @@ int mt2_f0_yin(mt2_model* m, void* stream, const float* wav, const int32_t* lens
     int lo = 0, hi = 0;
     f0_check_rule(sample_rate, hop, fmin, fmax, &lo, &hi);
     const int mx = f0_check_call(wav, lens, L_max, B, hop, threshold, f0, cmnd, lag, T_max, diff);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
-    f0_run(c, wav, lens, L_max, B, mx, sample_rate, hop, lo, hi, threshold, f0, cmnd, lag, T_max, diff);
+    MT2_AUDIO_CALL(m, stream);
+    f0_run(c, {wav, lens, L_max, B, mx, sample_rate, hop, lo, hi, threshold, f0, cmnd, lag, T_max, diff});
     MT2_API_END
 }
 
@@ -821,7 +824,7 @@ int mt2_f0_track_query(int sample_rate, int hop, float fmin, float fmax, float o
     if (lag_min) *lag_min = lo;
     if (lag_max) *lag_max = hi;
     if (states) *states = hi - lo + 1;
-    if (workspace_bytes) *workspace_bytes = f0_track_bytes(B, T);
+    if (workspace_bytes) *workspace_bytes = f0_track_arena_bytes(B, T);
     MT2_API_END
 }
 
@@ -834,10 +837,8 @@ int mt2_f0_track(mt2_model* m, void* stream, const float* wav, const int32_t* le
     f0_check_rule(sample_rate, hop, fmin, fmax, &lo, &hi);
     f0_track_check_costs(octave_cost, jump_cost);
     const int mx = f0_check_call(wav, lens, L_max, B, hop, threshold, f0, cmnd, lag, T_max, diff);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
-    f0_track_run(c, wav, lens, L_max, B, mx, sample_rate, hop, lo, hi, threshold, octave_cost, jump_cost, f0, cmnd, lag, T_max, diff);
+    MT2_AUDIO_CALL(m, stream);
+    f0_track_run(c, {wav, lens, L_max, B, mx, sample_rate, hop, lo, hi, threshold, f0, cmnd, lag, T_max, diff}, octave_cost, jump_cost);
     MT2_API_END
 }
 
@@ -845,9 +846,7 @@ int mt2_f0_track(mt2_model* m, void* stream, const float* wav, const int32_t* le
 int mt2_f0_stats(mt2_model* m, void* stream, const float* f0, const int32_t* frame_lens, int T_max, int B, double* stats) {
     MT2_API_BEGIN
     f0_stats_check(f0, frame_lens, T_max, B, stats);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_AUDIO_CALL(m, stream);
     f0_stats_run(c, f0, frame_lens, T_max, B, stats);
     MT2_API_END
 }
@@ -857,9 +856,7 @@ int mt2_frame_energy(mt2_model* m, void* stream, const float* wav, const int32_t
                      int T_max) {
     MT2_API_BEGIN
     const int mx = energy_check(wav, lens, L_max, B, hop, energy, T_max);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_AUDIO_CALL(m, stream);
     energy_run(c, wav, lens, L_max, B, mx, hop, energy, T_max);
     MT2_API_END
 }
@@ -869,9 +866,7 @@ int mt2_phone_prosody(mt2_model* m, void* stream, const float* f0, const float* 
                       int Np_max, const int32_t* frame_lens, int T_max, int B, double* out, long long* dur_sum) {
     MT2_API_BEGIN
     phone_prosody_check(f0, energy, dur, phone_lens, Np_max, frame_lens, T_max, B, out, dur_sum);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_AUDIO_CALL(m, stream);
     phone_prosody_run(c, f0, energy, dur, phone_lens, Np_max, frame_lens, T_max, B, out, dur_sum);
     MT2_API_END
 }
@@ -881,9 +876,7 @@ int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0, const int32_t
                       int32_t* n_voiced, int32_t* index) {
     MT2_API_BEGIN
     pitch_contour_check(f0, frame_lens, T_max, B, center, st, n_voiced, index);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_AUDIO_CALL(m, stream);
     pitch_contour_run(c, f0, frame_lens, T_max, B, center, st, n_voiced, index);
     MT2_API_END
 }
@@ -898,7 +891,7 @@ int mt2_loudness_query(int sample_rate, long long L, int* sub_block, int* blocks
     if (sub_block) *sub_block = h;
     if (blocks) *blocks = (int)std::max(L / h - 3, 0ll);
     if (coeffs) loudness_coeffs(sample_rate, coeffs);
-    if (workspace_bytes) *workspace_bytes = loudness_workspace_bytes(sample_rate, L, 1);
+    if (workspace_bytes) *workspace_bytes = loudness_arena_bytes(sample_rate, L, 1, false);
     MT2_API_END
 }
 
@@ -908,9 +901,7 @@ int mt2_loudness(mt2_model* m, void* stream, const float* wav, const int32_t* le
     MT2_API_BEGIN
     MT2_REQUIRE(stats != nullptr, "null stats");
     const int mx = loudness_check(wav, lens, L_max, B, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_AUDIO_CALL(m, stream);
     loudness_run(c, wav, lens, L_max, B, mx, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max);
     MT2_API_END
 }
@@ -921,9 +912,7 @@ int mt2_loudness_normalize(mt2_model* m, void* stream, const float* wav, const i
     MT2_API_BEGIN
     MT2_REQUIRE(out != nullptr, "null out");
     const int mx = loudness_check(wav, lens, L_max, B, sample_rate, target_lufs, peak_ceiling, out, stats, nullptr, 0);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_AUDIO_CALL(m, stream);
     loudness_run(c, wav, lens, L_max, B, mx, sample_rate, target_lufs, peak_ceiling, out, stats, nullptr, 0);
     MT2_API_END
 }
@@ -938,7 +927,7 @@ int mt2_ebu_query(int sample_rate, long long L, int* oversample, int* taps, int*
     if (taps) *taps = MT2_TP_TAPS;
     if (tile) *tile = MT2_TP_TILE;
     if (short_term_blocks) *short_term_blocks = (int)std::max(L / (sample_rate / 10) - 29, 0ll);
-    if (workspace_bytes) *workspace_bytes = ebu_workspace_bytes(sample_rate, L, 1);
+    if (workspace_bytes) *workspace_bytes = loudness_arena_bytes(sample_rate, L, 1, true);
     MT2_API_END
 }
 
@@ -958,9 +947,7 @@ int mt2_loudness_ebu(mt2_model* m, void* stream, const float* wav, const int32_t
     MT2_API_BEGIN
     MT2_REQUIRE(stats != nullptr, "null stats");
     const int mx = ebu_check(wav, lens, L_max, B, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max, short_term, NST_max);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_AUDIO_CALL(m, stream);
     ebu_run(c, wav, lens, L_max, B, mx, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max, short_term, NST_max);
     MT2_API_END
 }
@@ -972,9 +959,7 @@ int mt2_loudness_normalize_tp(mt2_model* m, void* stream, const float* wav, cons
     MT2_API_BEGIN
     MT2_REQUIRE(out != nullptr, "null out");
     const int mx = ebu_check(wav, lens, L_max, B, sample_rate, target_lufs, ceiling_dbtp, out, stats, nullptr, 0, nullptr, 0);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_AUDIO_CALL(m, stream);
     ebu_run(c, wav, lens, L_max, B, mx, sample_rate, target_lufs, ceiling_dbtp, out, stats, nullptr, 0, nullptr, 0);
     MT2_API_END
 }
@@ -984,8 +969,7 @@ int mt2_stft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float
              int T_max) {
     MT2_API_BEGIN
     MT2_REQUIRE(m != nullptr && ac != nullptr && B >= 1, "bad arguments");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_DEVICE_CALL(m, stream);
     stft_only_run(c, *ac, wav, lens, L_max, B, spec, T_max);
     MT2_API_END
 }
@@ -997,8 +981,7 @@ int mt2_istft(mt2_model* m, void* stream, const mt2_audio_config* ac, const floa
     MT2_REQUIRE(m != nullptr && ac != nullptr, "null model handle or audio configuration");
     gl_check_config(*ac);
     gl_check_lens(*ac, frame_lens, T_max, B, L_max);
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_DEVICE_CALL(m, stream);
     istft_run(c, *ac, spec, frame_lens, T_max, B, wav, L_max);
     MT2_API_END
 }
@@ -1010,8 +993,7 @@ int mt2_mel_to_linear(mt2_model* m, void* stream, const mt2_audio_config* ac, co
     MT2_REQUIRE(m != nullptr && ac != nullptr && B >= 1, "bad arguments");
     gl_check_config(*ac);
     (void)gl_pinv(*ac).size();      // the rank-deficient filterbank is refused without a HIP call
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_DEVICE_CALL(m, stream);
     mel_to_linear_run(c, *ac, mel, mel_lens, T_max, B, mag);
     MT2_API_END
 }
@@ -1029,7 +1011,7 @@ int mt2_griffin_lim_query(const mt2_audio_config* ac, const int32_t* mel_lens, i
     const long long L = (long long)(*std::max_element(T.begin(), T.end()) - 1) * ac->hop_length;
     gl_check_call(*ac, T.data(), T_max, B, n_iter, momentum, std::max(L, 0ll));
     (void)gl_pinv(*ac).size();      // the rank-deficient filterbank
-    if (workspace_bytes) *workspace_bytes = gl_workspace_bytes(*ac, T.data(), B, want_resid != 0);
+    if (workspace_bytes) *workspace_bytes = gl_arena_bytes(*ac, T.data(), B, want_resid != 0);
     if (L_out) *L_out = L;
     MT2_API_END
 }
@@ -1042,8 +1024,7 @@ int mt2_griffin_lim(mt2_model* m, void* stream, const mt2_audio_config* ac, cons
     gl_check_call(*ac, mel_lens, T_max, B, n_iter, momentum, L_max);
     MT2_REQUIRE(mel != nullptr && seeds != nullptr && wav != nullptr, "bad buffers");
     if (!(m->gl_P && std::memcmp(&m->fe_cfg, ac, sizeof(*ac)) == 0)) (void)gl_pinv(*ac).size();      // rank-deficient filterbank: refused here
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_DEVICE_CALL(m, stream);
     griffin_lim_run(c, *ac, mel, mel_lens, T_max, B, n_iter, momentum, seeds, wav, L_max, resid);
     MT2_API_END
 }
@@ -1052,7 +1033,7 @@ int mt2_griffin_lim(mt2_model* m, void* stream, const mt2_audio_config* ac, cons
 int mt2_dtw_query(int Tx_max, int Ty_max, int D, int B, long long* workspace_bytes) {
     MT2_API_BEGIN
     dtw_check_geometry(Tx_max, Ty_max, D, B);
-    if (workspace_bytes) *workspace_bytes = dtw_workspace_bytes(Tx_max, Ty_max, B);
+    if (workspace_bytes) *workspace_bytes = dtw_arena_bytes(Tx_max, Ty_max, B);
     MT2_API_END
 }
 
@@ -1062,9 +1043,7 @@ int mt2_dtw_align(mt2_model* m, void* stream, const float* X, const int32_t* x_l
     MT2_API_BEGIN
     dtw_check_geometry(Tx_max, Ty_max, D, B);
     dtw_check_lens(x_lens, Tx_max, y_lens, Ty_max, B);
-    MT2_REQUIRE(m != nullptr, "null model handle");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_AUDIO_CALL(m, stream);
     dtw_run(c, X, x_lens, Tx_max, Y, y_lens, Ty_max, D, B, lo, hi, steps, total, cost, acc);
     MT2_API_END
 }
@@ -1076,13 +1055,10 @@ int mt2_align_durations(mt2_model* m, void* stream, const int32_t* hi, const int
     MT2_REQUIRE(Np_max >= 1, "Np_max < 1");
     MT2_REQUIRE(Ty_max >= 1 && Ty_max <= MT2_DTW_MAX_LEN, "Ty_max outside [1, MT2_DTW_MAX_LEN]");
     MT2_REQUIRE(y_lens != nullptr && syn_dur != nullptr && phone_lens != nullptr && dur_out_host != nullptr, "a host array is NULL");
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(y_lens[b] >= 1 && y_lens[b] <= Ty_max, "y length outside [1, Ty_max]");
-        MT2_REQUIRE(phone_lens[b] >= 1 && phone_lens[b] <= Np_max, "phone count outside [1, Np_max]");
-    }
+    check_lens(y_lens, B, Ty_max, "y length outside [1, Ty_max]");
+    check_lens(phone_lens, B, Np_max, "phone count outside [1, Np_max]");
     MT2_REQUIRE(m != nullptr && hi != nullptr, "null model handle or hi");
-    if (mt2_device_check() != 0) throw Error(g_last_error);
-    MT2_CALL(m, stream);
+    MT2_DEVICE_CALL(m, stream);
     align_durations_run(c, hi, y_lens, Ty_max, syn_dur, phone_lens, Np_max, B, dur_out_host);
     MT2_API_END
 }

@@ -62,12 +62,6 @@ long long dtw_dir_words(int Ty_max) { return ((long long)Ty_max + MT2_DTW_DIR_CO
 
 long long dtw_skew_steps(int Ty_max) { return kStrip * (((long long)Ty_max + 2 * kStrip - 2) / kStrip); }
 
-long long dtw_workspace_bytes(int Tx_max, int Ty_max, int B) {
-    auto up = [](long long n) { return (n + 255) & ~255ll; };
-    const long long strips = ((long long)Tx_max + kStrip - 1) / kStrip;
-    return up(4ll * B * strips * dtw_skew_steps(Ty_max) * kStrip) + up(4ll * B * Tx_max * dtw_dir_words(Ty_max)) + up(4ll * (2 * B + 8));
-}
-
 // c for one parallelogram of 64 rows x 64 steps: rows i0 + l, columns j = t0 + u - l (l, u < 64) - the cells the strip's 64 lanes
 // visit in 64 consecutive steps of the accumulation.  Thread (tl, tu) of 16 x 16 owns the cells (l, u) = (tl + 16 r, tu + 16 c),
 // each ONE fma chain over k; lanes that differ in tl write 16 consecutive floats of the skewed scratch.  127 rows of Y are staged.

@@ -22,6 +22,7 @@
 // The max and the select are order-free and every sum's order depends on the block's index in its utterance alone, so a ragged batch
 // is bit-identical to its utterances alone.  A sample at or beyond L is never read.
 #include "../../include/megatts2_hip.h"
+#include "mt2_block_reduce.h"
 #include "mt2_kernels.h"
 
 #include <limits.h>
@@ -63,12 +64,6 @@ void true_peak_table(int sample_rate, float* table) {
             const double s = t == 0.0 ? 1.0 : sin(kPi * t) / (kPi * t);
             table[p * kTaps + k] = p == 0 ? (k == kZ - 1 ? 1.0f : 0.0f) : (float)(s * w);
         }
-}
-
-long long ebu_workspace_bytes(int sample_rate, long long max_len, long long B) {
-    auto r = [](long long x) { return std::max((x + 255) & ~255ll, 256ll); };
-    const long long NS = max_len / (sample_rate / 10), NST = std::max(NS - 29, 0ll), o = true_peak_oversample(sample_rate);
-    return r(4 * (((B + 3) & ~3ll) + 32 + kTaps * o)) + r(32 * B * NS) + r(8 * B * NS) + r(12 * B) + r(64 * B) + r(8 * B * NST);
 }
 
 // positions i in [tile * kTile - Z, (tile + 1) * kTile - Z) of one utterance: xs[q] = x[i0 - Z + 1 + q] (0 outside [0, L)), so that the
@@ -127,29 +122,10 @@ __global__ __launch_bounds__(kTpThreads) void true_peak_kernel(EbuP p) {
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) pk = fmaxf(pk, __shfl_xor(pk, d));
-    // ordered like the floats while they are >= 0.  The word only grows, so a wave whose max is not over the value it reads - however
-    // stale - has nothing to add: most waves skip the atomic, which otherwise queue on the one cache line that holds every utterance's word
-    if ((t & 63) == 0 && pk > 0.0f) {
-        const unsigned bits = __float_as_uint(pk);
-        if (bits > __hip_atomic_load(p.tp + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.tp + b, bits);
-    }
+    wave_peak_merge<true>(pk, p.tp + b);      // most waves skip the atomic
 }
 
 namespace {
-// the sum of v and of n over the workgroup in the gate kernel's fixed tree (256 -> 1); every thread gets the result
-__device__ __forceinline__ void range_tree_sum(double* sv, int* sn, double* v, int* n) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    sv[t] = *v; sn[t] = *n;
-    __syncthreads();
-    for (int s = kRangeThreads / 2; s > 0; s >>= 1) {
-        if (t < s) { sv[t] += sv[t + s]; sn[t] += sn[t + s]; }
-        __syncthreads();
-    }
-    *v = sv[0]; *n = sn[0];
-}
 // ordered like the doubles, a NaN of either sign last; never 0, which marks a block under a gate
 __device__ __forceinline__ unsigned long long range_key(double s) {
     if (s != s) return ~0ull;
@@ -223,7 +199,7 @@ __global__ __launch_bounds__(kRangeThreads) void loudness_range_kernel(EbuP p) {
     }
     if (p.short_term)
         for (int k = nst + t; k < p.NST_max; k += kRangeThreads) p.short_term[(long long)b * p.NST_max + k] = ninf;
-    range_tree_sum(sv, sn, &sum, &cnt);
+    block_tree_sum<kRangeThreads>(sv, sn, &sum, &cnt);
     const int n_abs = cnt;
     const double gamma = n_abs > 0 ? -0.691 + 10.0 * log10(sum / (double)n_abs) - 20.0 : ninf;
     sum = 0.0; cnt = 0;
@@ -233,16 +209,9 @@ __global__ __launch_bounds__(kRangeThreads) void loudness_range_kernel(EbuP p) {
         K[k] = over ? range_key(s) : 0ull;
         cnt += over ? 1 : 0;
     }
-    range_tree_sum(sv, sn, &sum, &cnt);
+    block_tree_sum<kRangeThreads>(sv, sn, &sum, &cnt);
     const int n = cnt;
-    __syncthreads();
-    sv[t] = smax;
-    __syncthreads();
-    for (int s = kRangeThreads / 2; s > 0; s >>= 1) {
-        if (t < s) sv[t] = fmax(sv[t], sv[t + s]);
-        __syncthreads();
-    }
-    smax = sv[0];
+    smax = block_tree_max<kRangeThreads>(sv, smax);
     double p10 = nan(""), p95 = nan("");
     if (n > 0) {                                                              // uniform over the workgroup
         p10 = range_unkey(range_select(K, nst, (unsigned)(((long long)(n - 1) * 10 + 50) / 100), hist, pick));

@@ -52,6 +52,7 @@
 // A workgroup per utterance: thread i sums the frames i, i + 256, ... ascending, then the 256 partial sums meet in a fixed tree
 // (stride 128, 64, ... 1): the order depends on the frame index alone, not on the batch slot or T_max.
 #include "../../include/megatts2_hip.h"
+#include "mt2_block_reduce.h"
 #include "mt2_kernels.h"
 
 #include <limits.h>
@@ -391,18 +392,6 @@ hipError_t launch_f0_viterbi(const F0TrackP& q, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the 256 partial sums of a workgroup in a fixed tree; the result is in every thread
-__device__ __forceinline__ double f0_tree_sum(double* red, double v) {
-    __syncthreads();                           // the previous use of red[] is over
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __global__ __launch_bounds__(kThreads) void f0_stats_kernel(const float* __restrict__ f0, const int* __restrict__ frame_len, int T_max,
                                                             double* __restrict__ stats) {
     __shared__ double red[kThreads];
@@ -413,8 +402,8 @@ __global__ __launch_bounds__(kThreads) void f0_stats_kernel(const float* __restr
         const float v = f[t];
         if (v > 0.0f) { cnt += 1.0; sum += (double)v; }
     }
-    const double n = f0_tree_sum(red, cnt);
-    const double total = f0_tree_sum(red, sum);
+    const double n = block_tree_sum<kThreads>(red, cnt);
+    const double total = block_tree_sum<kThreads>(red, sum);
     double* __restrict__ out = stats + 6ll * b;
     if (!(n > 0.0)) {
         if (threadIdx.x < 6) out[threadIdx.x] = 0.0;
@@ -429,7 +418,7 @@ __global__ __launch_bounds__(kThreads) void f0_stats_kernel(const float* __restr
             s2 += e2; s3 += e2 * e; s4 += e2 * e2;
         }
     }
-    const double m2 = f0_tree_sum(red, s2) / n, m3 = f0_tree_sum(red, s3) / n, m4 = f0_tree_sum(red, s4) / n;
+    const double m2 = block_tree_sum<kThreads>(red, s2) / n, m3 = block_tree_sum<kThreads>(red, s3) / n, m4 = block_tree_sum<kThreads>(red, s4) / n;
     if (threadIdx.x == 0) {
         out[0] = n; out[1] = n / (double)T; out[2] = mu;
         const bool flat = !(m2 > 0.0);

@@ -22,6 +22,7 @@
 // tree).  Neither the slot, L_max, the batch size nor the grid enters, so a ragged batch is bit-identical to its utterances alone.
 // A sample at or beyond L is never read.
 #include "../../include/megatts2_hip.h"
+#include "mt2_block_reduce.h"
 #include "mt2_kernels.h"
 
 #include <limits.h>
@@ -120,12 +121,6 @@ void loudness_carry_matrix(const double* c, int h, double* M) {
     }
 }
 
-long long loudness_workspace_bytes(int sample_rate, long long max_len, long long B) {
-    auto r = [](long long x) { return std::max((x + 255) & ~255ll, 256ll); };
-    const long long NS = max_len / (sample_rate / 10);
-    return r(4 * (((B + 3) & ~3ll) + 32)) + r(32 * B * NS) + r(8 * B * NS) + r(8 * B);
-}
-
 // 1: the zero-state end state of every complete chunk, and the utterance's sample peak (the tail behind the last complete chunk
 // included: thread ns takes it, for the peak alone)
 __global__ __launch_bounds__(kChunkThreads) void loudness_zero_state_kernel(LoudnessP p) {
@@ -143,9 +138,7 @@ __global__ __launch_bounds__(kChunkThreads) void loudness_zero_state_kernel(Loud
             out[1] = make_double2(st[2], st[3]);
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) pk = fmaxf(pk, __shfl_xor(pk, d));
-    if (threadIdx.x == 0 && pk > 0.0f) atomicMax(p.peak + b, __float_as_uint(pk));      // ordered like the floats while they are >= 0
+    wave_peak_merge<false>(pk, p.peak + b);
 }
 
 // 2: state[b, j] (the zero-state end of chunk j) becomes the state chunk j is ENTERED with.  One wave per utterance: 64 chunks are
@@ -195,18 +188,6 @@ __device__ __forceinline__ double block_loudness(const double* __restrict__ S, i
     *z = (((S[k] + S[k + 1]) + S[k + 2]) + S[k + 3]) * inv4h;
     return -0.691 + 10.0 * log10(*z);
 }
-// the sum of v and of n over the workgroup in a fixed tree (256 -> 1); every thread gets the result
-__device__ __forceinline__ void tree_sum(double* sv, int* sn, double* v, int* n) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    sv[t] = *v; sn[t] = *n;
-    __syncthreads();
-    for (int s = kGateThreads / 2; s > 0; s >>= 1) {
-        if (t < s) { sv[t] += sv[t + s]; sn[t] += sn[t + s]; }
-        __syncthreads();
-    }
-    *v = sv[0]; *n = sn[0];
-}
 }  // namespace
 
 // blocks, both gates, the gain and the eight doubles of one utterance.  A block is over a gate unless l <= gate: a NaN block counts,
@@ -228,7 +209,7 @@ __global__ __launch_bounds__(kGateThreads) void loudness_gate_kernel(LoudnessP p
     }
     if (p.momentary)
         for (int k = nb + t; k < p.NB_max; k += kGateThreads) p.momentary[(long long)b * p.NB_max + k] = ninf;
-    tree_sum(sv, sn, &sum, &cnt);
+    block_tree_sum<kGateThreads>(sv, sn, &sum, &cnt);
     const int n_abs = cnt;
     const double gamma = n_abs > 0 ? -0.691 + 10.0 * log10(sum / (double)n_abs) - 10.0 : ninf;
     sum = 0.0; cnt = 0;
@@ -237,14 +218,8 @@ __global__ __launch_bounds__(kGateThreads) void loudness_gate_kernel(LoudnessP p
         const double l = block_loudness(S, k, inv4h, &z);
         if (!(l <= -70.0) && !(l <= gamma)) { sum += z; ++cnt; }
     }
-    tree_sum(sv, sn, &sum, &cnt);
-    __syncthreads();
-    sv[t] = lmax;
-    __syncthreads();
-    for (int s = kGateThreads / 2; s > 0; s >>= 1) {
-        if (t < s) sv[t] = fmax(sv[t], sv[t + s]);
-        __syncthreads();
-    }
+    block_tree_sum<kGateThreads>(sv, sn, &sum, &cnt);
+    lmax = block_tree_max<kGateThreads>(sv, lmax);
     if (t != 0) return;
     const double I = cnt > 0 ? -0.691 + 10.0 * log10(sum / (double)cnt) : ninf;
     const float peak = __uint_as_float(p.peak[b]);
@@ -270,7 +245,7 @@ __global__ __launch_bounds__(kGateThreads) void loudness_gate_kernel(LoudnessP p
     }
     if (p.stats) {
         double* __restrict__ o = p.stats + (long long)b * 8;
-        o[0] = I; o[1] = (double)nb; o[2] = (double)n_abs; o[3] = (double)cnt; o[4] = gamma; o[5] = (double)peak; o[6] = sv[0]; o[7] = (double)g;
+        o[0] = I; o[1] = (double)nb; o[2] = (double)n_abs; o[3] = (double)cnt; o[4] = gamma; o[5] = (double)peak; o[6] = lmax; o[7] = (double)g;
     }
 }
 

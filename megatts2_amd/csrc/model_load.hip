@@ -64,8 +64,7 @@ void Arena::peek(size_t offset, void* dst_host, size_t bytes) const {
     }
 }
 void* Arena::alloc(size_t bytes) {
-    bytes = (bytes + 255) & ~size_t(255);
-    if (bytes == 0) bytes = 256;
+    bytes = arena_round(bytes);
     for (auto& c : chunks_) {
         if (c.size - c.used >= bytes) {
             void* p = c.p + c.used;
@@ -106,10 +105,10 @@ void* PinnedPool::alloc(size_t bytes) {
     return p;
 }
 
-int IntPlan::add(const std::vector<int>& v) {
+int IntPlan::add(const int* v, size_t n) {
     while (h_.size() & 3) h_.push_back(0);
     const int off = (int)h_.size();
-    h_.insert(h_.end(), v.begin(), v.end());
+    h_.insert(h_.end(), v, v + n);
     return off;
 }
 int IntPlan::add_fill(size_t n, int value) {
@@ -118,9 +117,7 @@ int IntPlan::add_fill(size_t n, int value) {
     h_.resize(h_.size() + n, value);
     return off;
 }
-void IntPlan::upload(Arena& a, PinnedPool& pin, hipStream_t s) {
-    if (h_.empty()) h_.push_back(0);
-    d_ = a.get<int>(h_.size());
+void IntPlan::send(PinnedPool& pin, hipStream_t s) {
     void* stage = pin.alloc(h_.size() * sizeof(int));     // outlives this object: recycled two API calls later
     std::memcpy(stage, h_.data(), h_.size() * sizeof(int));
     MT2_HIP(hipMemcpyAsync(d_, stage, h_.size() * sizeof(int), hipMemcpyHostToDevice, s));

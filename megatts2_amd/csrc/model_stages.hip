@@ -1809,6 +1809,34 @@ static void stft_only_run(const Ctx& c, const mt2_audio_config& ac, const float*
 }
 
 // ---------------------------------------------------------------------------------------------------
+// What every ragged-batch audio call decides on the host, stated once.
+// The ragged-length contract: lens[b] in [1, cap], refused with `msg` (the call's own wording); -> max_b lens[b]
+static int check_lens(const int* lens, int B, int cap, const char* msg) {
+    int mx = 0;
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= cap, msg);
+        mx = std::max(mx, lens[b]);
+    }
+    return mx;
+}
+// a caller's buffer; a NULL one (an optional output that was not asked for) overlaps nothing
+struct Span { const void* p; size_t n; };
+static bool spans_overlap(const Span& a, const Span& b) {
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return a.p != nullptr && b.p != nullptr && a0 < b0 + b.n && b0 < a0 + a.n;
+}
+// does an output overlap an input or another output?
+static bool outputs_overlap(std::initializer_list<Span> outs, std::initializer_list<Span> ins) {
+    for (const Span* o = outs.begin(); o != outs.end(); ++o) {
+        for (const Span& i : ins)
+            if (spans_overlap(*o, i)) return true;
+        for (const Span* q = o + 1; q != outs.end(); ++q)
+            if (spans_overlap(*o, *q)) return true;
+    }
+    return false;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Griffin-Lim vocoder (griffinlim.hip holds the rule): mel -> linear magnitude by the filterbank's pseudo-inverse, random phase, then
 // n_iter rounds of inverse STFT -> forward STFT -> phase update.  Four launches a round: the inverse-DFT GEMM, the overlap-add (which
 // writes the STFT's reflect-padded block buffer itself), the STFT GEMM of the front-end and the phase update.
@@ -1842,15 +1870,31 @@ static void gl_check_lens(const mt2_audio_config& ac, const int* T, int T_max, i
     }
     MT2_REQUIRE(rows * (ac.n_fft + 4) <= INT_MAX, "batch too large for 32-bit row indices");
 }
-// arena bytes of one griffin_lim_run (the closed form is in megatts2_hip.h)
-static long long gl_workspace_bytes(const mt2_audio_config& ac, const int* T, int B, bool resid) {
-    auto up = [](long long n) { return (n + 255) & ~255ll; };
-    auto p4 = [](long long n) { return (n + 3) & ~3ll; };
-    const int N = ac.n_fft, hop = ac.hop_length, F = N / 2 + 1, Fp = (F + 3) & ~3, lds = (2 * F + 3) & ~3;
-    long long Fr = 0, Rb = 0;
-    for (int b = 0; b < B; ++b) { Fr += T[b]; Rb += T[b] - 1 + N / hop; }
-    const long long ints = 2 * p4(Rb) + 4 * p4(Fr) + 2 * p4(B) + (resid ? p4(2 * B) + Fr : 2 * B);
-    return up(4 * ints) + up(4 * Fr * ac.n_mels) + up(4 * Fr * Fp) + 3 * up(4 * Fr * lds) + up(4 * Fr * N) + up(4 * Rb * hop);
+// the arena of one griffin_lim_run, in carve order (the closed form is in megatts2_hip.h): the plan, exp(M), A, S / R / Rprev, the
+// frames, the block buffer.  Fr frame rows and Rb hop blocks in the batch
+struct GlWs { float *E, *A, *S, *R, *Rprev, *frames, *xp; };
+template <class Ws> static GlWs gl_carve(Ws& ws, IntPlan& ip, const mt2_audio_config& ac, size_t Fr, size_t Rb) {
+    const size_t N = ac.n_fft, F = N / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
+    GlWs w{};
+    ip.carve(ws);
+    w.E = ws.template get<float>(Fr * ac.n_mels);
+    w.A = ws.template get<float>(Fr * Fp);
+    w.S = ws.template get<float>(Fr * lds);
+    w.R = ws.template get<float>(Fr * lds);
+    w.Rprev = ws.template get<float>(Fr * lds);
+    w.frames = ws.template get<float>(Fr * N);
+    w.xp = ws.template get<float>(Rb * ac.hop_length);
+    return w;
+}
+static long long gl_arena_bytes(const mt2_audio_config& ac, const int* T, int B, bool resid) {
+    size_t Fr = 0, Rb = 0;
+    for (int b = 0; b < B; ++b) { Fr += T[b]; Rb += T[b] - 1 + ac.n_fft / ac.hop_length; }
+    IntPlan ip;      // the entries of griffin_lim_run's plan, by size
+    for (size_t n : {Rb, Rb, Fr, Fr, Fr, Fr, (size_t)B, (size_t)B, 2 * (size_t)B}) ip.add_fill(n, 0);
+    if (resid) ip.add_fill(Fr, 0);
+    ArenaCount count;
+    gl_carve(count, ip, ac, Fr, Rb);
+    return (long long)count.bytes;
 }
 
 // the inverse basis [N, lds] (window and the 1/N, 2/N Hermitian weights folded in, zero columns for the imaginary parts of bins 0 and
@@ -1966,7 +2010,7 @@ static void istft_run(const Ctx& c, const mt2_audio_config& ac, const float* spe
     const int N = ac.n_fft, F = c.m.fe_nfreq, lds = (2 * F + 3) & ~3;
     const GlRows g = gl_rows(ac, T, B, T_max);
     IntPlan ip;
-    const int o_map = ip.add(g.map), o_row0 = ip.add(g.row0), o_T = ip.add(std::vector<int>(T, T + B));
+    const int o_map = ip.add(g.map), o_row0 = ip.add(g.row0), o_T = ip.add(T, B);
     ip.upload(c.ws, c.m.pinned(), c.s);
     float* S = c.ws.get<float>((size_t)g.Fr * lds);
     MT2_HIP(hipMemsetAsync(S, 0, sizeof(float) * (size_t)g.Fr * lds, c.s));      // the pad columns meet zero basis columns: 0 x garbage must not be NaN
@@ -1991,7 +2035,7 @@ static void mel_to_linear_rows(const Ctx& c, const mt2_audio_config& ac, const f
 static void mel_to_linear_run(const Ctx& c, const mt2_audio_config& ac, const float* mel, const int* T, int T_max, int B, float* out) {
     gl_check_config(ac);
     MT2_REQUIRE(B >= 1 && B <= 65535 && T != nullptr && T_max >= 1 && mel != nullptr && out != nullptr, "bad arguments");
-    for (int b = 0; b < B; ++b) MT2_REQUIRE(T[b] >= 1 && T[b] <= T_max, "a frame count outside [1, T_max]");
+    check_lens(T, B, T_max, "a frame count outside [1, T_max]");
     gl_prepare_pinv(c.m, ac);
     const int Fp = c.m.fe_nfreq_pad;
     std::vector<int> map;
@@ -2032,7 +2076,7 @@ static void griffin_lim_run(const Ctx& c, const mt2_audio_config& ac, const floa
     for (int b = 0; b < B; ++b) { sd[2 * b] = (int)(uint32_t)(seeds[b] & 0xFFFFFFFFu); sd[2 * b + 1] = (int)(uint32_t)(seeds[b] >> 32); }
     IntPlan ip;
     const int o_b = ip.add(g.blk_b), o_t = ip.add(g.blk_t), o_base = ip.add(g.rowbase), o_map = ip.add(g.map), o_rb = ip.add(g.row_b),
-              o_rt = ip.add(g.row_t), o_row0 = ip.add(g.row0), o_T = ip.add(std::vector<int>(T, T + B)), o_seed = ip.add(sd);
+              o_rt = ip.add(g.row_t), o_row0 = ip.add(g.row0), o_T = ip.add(T, B), o_seed = ip.add(sd);
     int o_rmap = -1;
     if (resid) {
         std::vector<int> rmap(Fr);
@@ -2040,36 +2084,30 @@ static void griffin_lim_run(const Ctx& c, const mt2_audio_config& ac, const floa
         MT2_REQUIRE((long long)B * (n_iter + 1) * T_max <= INT_MAX, "resid too large for 32-bit indices");
         o_rmap = ip.add(rmap);
     }
-    ip.upload(c.ws, m.pinned(), c.s);
-    float* E = c.ws.get<float>((size_t)Fr * ac.n_mels);
-    float* A = c.ws.get<float>((size_t)Fr * Fp);
-    float* S = c.ws.get<float>((size_t)Fr * lds);
-    float* R = c.ws.get<float>((size_t)Fr * lds);
-    float* Rprev = c.ws.get<float>((size_t)Fr * lds);
-    float* frames = c.ws.get<float>((size_t)Fr * N);
-    float* xp = c.ws.get<float>((size_t)Rb * hop);
+    const GlWs w = gl_carve(c.ws, ip, ac, Fr, Rb);
+    ip.send(m.pinned(), c.s);
     const int* rmap = resid ? ip.dev(o_rmap) : nullptr;
     Stages st(m, c.s);
     st.mark("start");
     if (resid) MT2_HIP(hipMemsetAsync(resid, 0, sizeof(float) * (size_t)B * (n_iter + 1) * T_max, c.s));
-    mel_to_linear_rows(c, ac, mel, ip.dev(o_map), E, A, Fr);
-    MT2_HIP(launch_gl_phase_init(A, Fp, ip.dev(o_rb), ip.dev(o_rt), reinterpret_cast<const uint32_t*>(ip.dev(o_seed)), S, lds, F, Fr, c.s));
-    if (n_iter > 0) MT2_HIP(hipMemsetAsync(Rprev, 0, sizeof(float) * (size_t)Fr * lds, c.s));
+    mel_to_linear_rows(c, ac, mel, ip.dev(o_map), w.E, w.A, Fr);
+    MT2_HIP(launch_gl_phase_init(w.A, Fp, ip.dev(o_rb), ip.dev(o_rt), reinterpret_cast<const uint32_t*>(ip.dev(o_seed)), w.S, lds, F, Fr, c.s));
+    if (n_iter > 0) MT2_HIP(hipMemsetAsync(w.Rprev, 0, sizeof(float) * (size_t)Fr * lds, c.s));
     st.mark("gl_setup");
     FixedTile ft(m.opts);
     for (int k = 0; k < n_iter; ++k) {
-        istft_gemm(c, ac, S, frames, Fr);
-        MT2_HIP(launch_istft_ola_blocks(frames, N, hop, m.gl_w2, ip.dev(o_b), ip.dev(o_t), ip.dev(o_row0), ip.dev(o_T), xp, Rb, c.s));
-        stft_gemm(c, ac, xp, Rb, ip.dev(o_base), R, Fr);
-        MT2_HIP(launch_gl_phase_update(R, Rprev, A, Fp, S, lds, F, cm, resid ? resid + (size_t)k * T_max : nullptr, rmap, Fr, 1, c.s));
+        istft_gemm(c, ac, w.S, w.frames, Fr);
+        MT2_HIP(launch_istft_ola_blocks(w.frames, N, hop, m.gl_w2, ip.dev(o_b), ip.dev(o_t), ip.dev(o_row0), ip.dev(o_T), w.xp, Rb, c.s));
+        stft_gemm(c, ac, w.xp, Rb, ip.dev(o_base), w.R, Fr);
+        MT2_HIP(launch_gl_phase_update(w.R, w.Rprev, w.A, Fp, w.S, lds, F, cm, resid ? resid + (size_t)k * T_max : nullptr, rmap, Fr, 1, c.s));
     }
     st.mark("gl_iterations");
-    istft_gemm(c, ac, S, frames, Fr);
-    MT2_HIP(launch_istft_ola_wav(frames, N, hop, m.gl_w2, ip.dev(o_row0), ip.dev(o_T), wav, L_max, B, c.s));
+    istft_gemm(c, ac, w.S, w.frames, Fr);
+    MT2_HIP(launch_istft_ola_wav(w.frames, N, hop, m.gl_w2, ip.dev(o_row0), ip.dev(o_T), wav, L_max, B, c.s));
     if (resid) {      // entry n_iter: one extra STFT of the output, paid only on request
-        MT2_HIP(launch_istft_ola_blocks(frames, N, hop, m.gl_w2, ip.dev(o_b), ip.dev(o_t), ip.dev(o_row0), ip.dev(o_T), xp, Rb, c.s));
-        stft_gemm(c, ac, xp, Rb, ip.dev(o_base), R, Fr);
-        MT2_HIP(launch_gl_phase_update(R, nullptr, A, Fp, nullptr, lds, F, cm, resid + (size_t)n_iter * T_max, rmap, Fr, 0, c.s));
+        MT2_HIP(launch_istft_ola_blocks(w.frames, N, hop, m.gl_w2, ip.dev(o_b), ip.dev(o_t), ip.dev(o_row0), ip.dev(o_T), w.xp, Rb, c.s));
+        stft_gemm(c, ac, w.xp, Rb, ip.dev(o_base), w.R, Fr);
+        MT2_HIP(launch_gl_phase_update(w.R, nullptr, w.A, Fp, nullptr, lds, F, cm, resid + (size_t)n_iter * T_max, rmap, Fr, 0, c.s));
     }
     st.mark("gl_final");
     st.finish();
@@ -2098,9 +2136,9 @@ static void resample_run(const Ctx& c, const float* wav, const int* lens, int L_
     if (const char* why = resample_rule(sr_in, sr_out, &r)) throw Error(std::string("mt2_resample: ") + why);
     MT2_REQUIRE((flags & ~MT2_RESAMPLE_NORMALIZE) == 0, "unknown resample flag");
     MT2_REQUIRE(wav != nullptr && out != nullptr && lens != nullptr && ((uintptr_t)wav & 3) == 0, "bad buffers");
-    std::vector<int> len(lens, lens + B), lout(B), tile_b, tile_i0;
+    check_lens(lens, B, L_max, "waveform length outside [1, L_max]");
+    std::vector<int> lout(B), tile_b, tile_i0;
     for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
         const long long lo = resample_out_len(r, lens[b]);
         MT2_REQUIRE(lo <= Lout_max, "Lout_max smaller than ceil(n * L / o)");
         lout[b] = (int)lo;
@@ -2110,7 +2148,7 @@ static void resample_run(const Ctx& c, const float* wav, const int* lens, int L_
     ResampleP p{};
     p.table = resample_prepare(c.m, r);
     IntPlan ip;
-    const int o_b = ip.add(tile_b), o_i0 = ip.add(tile_i0), o_len = ip.add(len), o_lout = ip.add(lout);
+    const int o_b = ip.add(tile_b), o_i0 = ip.add(tile_i0), o_len = ip.add(lens, B), o_lout = ip.add(lout);
     ip.upload(c.ws, c.m.pinned(), c.s);
     p.wav = wav; p.L_max = L_max; p.r = r;
     p.tile_b = ip.dev(o_b); p.tile_i0 = ip.dev(o_i0); p.tiles = (int)tile_b.size();
@@ -2128,13 +2166,9 @@ static void resample_run(const Ctx& c, const float* wav, const int* lens, int L_
 // out[b, :] = wav[b, :] / max |wav[b, :len[b]]| (audio_io.normalize), zeros beyond len[b]
 static void peak_normalize_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, float* out) {
     MT2_REQUIRE(wav != nullptr && out != nullptr && lens != nullptr, "bad buffers");
-    int mx = 0;
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
-        mx = std::max(mx, lens[b]);
-    }
+    const int mx = check_lens(lens, B, L_max, "waveform length outside [1, L_max]");
     IntPlan ip;
-    const int o_len = ip.add(std::vector<int>(lens, lens + B));
+    const int o_len = ip.add(lens, B);
     ip.upload(c.ws, c.m.pinned(), c.s);
     unsigned* peak = c.ws.get<unsigned>(B);
     MT2_HIP(hipMemsetAsync(peak, 0, sizeof(unsigned) * B, c.s));
@@ -2149,19 +2183,13 @@ static void trim_run(const Ctx& c, const float* wav, const int* lens, int L_max,
     // everything is checked before the first launch: a refused call leaves `out` as it was
     MT2_REQUIRE(std::isfinite(top_db) && top_db > 0.0f, "top_db must be finite and > 0");
     MT2_REQUIRE(wav != nullptr && out != nullptr && lens != nullptr && ((uintptr_t)wav & 3) == 0 && ((uintptr_t)out & 3) == 0, "bad buffers");
-    int mx = 0;
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
-        mx = std::max(mx, lens[b]);
-    }
+    const int mx = check_lens(lens, B, L_max, "waveform length outside [1, L_max]");
     MT2_REQUIRE(mx <= INT_MAX - 4 * MT2_TRIM_HOP && B <= 65535, "waveform too long or batch too large");
     MT2_REQUIRE(Lout_max >= mx, "Lout_max smaller than the longest utterance (the cut is not known before the call)");
     MT2_REQUIRE(energy == nullptr || F_max >= trim_frames(mx), "F_max smaller than 1 + max length / 512");
-    const uintptr_t w0 = (uintptr_t)wav, w1 = w0 + sizeof(float) * (size_t)B * L_max;
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + sizeof(float) * (size_t)B * Lout_max;
-    MT2_REQUIRE(o1 <= w0 || w1 <= o0, "out overlaps wav");
+    MT2_REQUIRE(!spans_overlap({out, sizeof(float) * (size_t)B * Lout_max}, {wav, sizeof(float) * (size_t)B * L_max}), "out overlaps wav");
     IntPlan ip;
-    const int o_len = ip.add(std::vector<int>(lens, lens + B));
+    const int o_len = ip.add(lens, B);
     ip.upload(c.ws, c.m.pinned(), c.s);
     TrimP p{};
     p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = mx; p.B = B;
@@ -2191,10 +2219,6 @@ static void f0_check_rule(int sample_rate, int hop, float fmin, float fmax, int*
     MT2_REQUIRE(f0_lags(sample_rate, fmin, fmax, lag_min, lag_max),
                 "lags refused: need 2 <= ceil(sample_rate / fmax) < floor(sample_rate / fmin) <= 256");
 }
-static bool f0_overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a != nullptr && b != nullptr && a0 < b0 + nb && b0 < a0 + na;
-}
 // every refusal of mt2_f0_yin, decided on the host before the first HIP call; -> max_b lens[b]
 static int f0_check_call(const float* wav, const int* lens, int L_max, int B, int hop, float threshold, const float* f0, const float* cmnd,
                          const int32_t* lag, int T_max, const float* diff) {
@@ -2202,60 +2226,71 @@ static int f0_check_call(const float* wav, const int* lens, int L_max, int B, in
     MT2_REQUIRE(wav != nullptr && lens != nullptr && f0 != nullptr && L_max >= 1, "bad buffers");
     MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)f0 | (uintptr_t)cmnd | (uintptr_t)lag | (uintptr_t)diff) & 3) == 0, "misaligned buffers");
     MT2_REQUIRE(threshold > 0.0f && threshold <= 1.0f, "threshold outside (0, 1]");
-    int mx = 0;
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
-        mx = std::max(mx, lens[b]);
-    }
+    const int mx = check_lens(lens, B, L_max, "waveform length outside [1, L_max]");
     MT2_REQUIRE(T_max >= 1 + mx / hop, "T_max smaller than 1 + max length / hop");
     const size_t nw = sizeof(float) * (size_t)B * L_max, nt = sizeof(float) * (size_t)B * T_max;
-    MT2_REQUIRE(!f0_overlaps(f0, nt, wav, nw) && !f0_overlaps(cmnd, nt, wav, nw) && !f0_overlaps(lag, nt, wav, nw) &&
-                    !f0_overlaps(diff, nt * (MT2_F0_MAX_LAG + 1), wav, nw),
+    const Span w{wav, nw};
+    MT2_REQUIRE(!spans_overlap({f0, nt}, w) && !spans_overlap({cmnd, nt}, w) && !spans_overlap({lag, nt}, w) &&
+                    !spans_overlap({diff, nt * (MT2_F0_MAX_LAG + 1)}, w),
                 "an output overlaps wav");
     return mx;
 }
-// enqueues only: the lengths travel in the call's one IntPlan upload
-static void f0_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, int hop, int lag_min,
-                   int lag_max, float threshold, float* f0, float* cmnd, int32_t* lag, int T_max, float* diff) {
-    IntPlan ip;
-    const int o_len = ip.add(std::vector<int>(lens, lens + B));
-    ip.upload(c.ws, c.m.pinned(), c.s);
+// what mt2_f0_yin and mt2_f0_track share of their arguments, and the kernels' F0P of it (`len`: the lengths on the device)
+struct F0Args {
+    const float* wav; const int* lens; int L_max, B, max_len, sample_rate, hop, lag_min, lag_max; float threshold;
+    float* f0; float* cmnd; int32_t* lag; int T_max; float* diff;
+};
+static F0P f0_params(const F0Args& a, const int* len) {
     F0P p{};
-    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B;
-    p.sample_rate = sample_rate; p.hop = hop; p.lag_min = lag_min; p.lag_max = lag_max; p.threshold = threshold;
-    p.f0 = f0; p.T_max = T_max; p.cmnd = cmnd; p.lag = lag; p.diff = diff;
-    MT2_HIP(launch_f0_yin(p, c.s));
+    p.wav = a.wav; p.L_max = a.L_max; p.len = len; p.max_len = a.max_len; p.B = a.B;
+    p.sample_rate = a.sample_rate; p.hop = a.hop; p.lag_min = a.lag_min; p.lag_max = a.lag_max; p.threshold = a.threshold;
+    p.f0 = a.f0; p.T_max = a.T_max; p.cmnd = a.cmnd; p.lag = a.lag; p.diff = a.diff;
+    return p;
 }
-// mt2_f0_track: the two costs, and the arena bytes of a call with B utterances and T_max frames - r(4 (4 ceil(B / 4) + 256)) for the
-// lengths and the lg table + r(4 B T_max 257) for d' + r(256 B T_max) for psi, r(x) = x rounded up to 256
+// enqueues only: the lengths travel in the call's one IntPlan upload
+static void f0_run(const Ctx& c, const F0Args& a) {
+    IntPlan ip;
+    const int o_len = ip.add(a.lens, a.B);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    MT2_HIP(launch_f0_yin(f0_params(a, ip.dev(o_len)), c.s));
+}
+// mt2_f0_track: the two costs
 static void f0_track_check_costs(float octave_cost, float jump_cost) {
     MT2_REQUIRE(std::isfinite(octave_cost) && octave_cost >= 0.0f, "octave_cost must be finite and >= 0");
     MT2_REQUIRE(std::isfinite(jump_cost) && jump_cost >= 0.0f, "jump_cost must be finite and >= 0");
 }
-static long long f0_track_bytes(long long B, long long T_max) {
-    auto r = [](long long x) { return (x + 255) & ~255ll; };
-    return r(4 * (((B + 3) & ~3ll) + 256)) + r(4 * B * T_max * (MT2_F0_MAX_LAG + 1)) + r(256 * B * T_max);
+// ... and the arena of a call with B utterances and T_max frames, in carve order: the plan (the lengths and the lg table), d', psi
+struct F0TrackWs { float* dprime; unsigned char* psi; };
+template <class Ws> static F0TrackWs f0_track_carve(Ws& ws, IntPlan& ip, size_t B, size_t T_max) {
+    F0TrackWs w{};
+    ip.carve(ws);
+    w.dprime = ws.template get<float>(B * T_max * (MT2_F0_MAX_LAG + 1));
+    w.psi = ws.template get<unsigned char>(B * T_max * 256);
+    return w;
+}
+static long long f0_track_arena_bytes(int B, long long T_max) {
+    IntPlan ip;
+    ip.add_fill(B, 0);
+    ip.add_fill(256, 0);
+    ArenaCount count;
+    f0_track_carve(count, ip, B, T_max);
+    return (long long)count.bytes;
 }
 // enqueues only: the lengths and the lg table travel in the call's one IntPlan upload
-static void f0_track_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, int hop,
-                         int lag_min, int lag_max, float threshold, float octave_cost, float jump_cost, float* f0, float* cmnd,
-                         int32_t* lag, int T_max, float* diff) {
+static void f0_track_run(const Ctx& c, const F0Args& a, float octave_cost, float jump_cost) {
     float lg[256];
-    f0_track_table(lag_min, lag_max, lg);
+    f0_track_table(a.lag_min, a.lag_max, lg);
     std::vector<int> bits(256);
     std::memcpy(bits.data(), lg, sizeof(lg));
     IntPlan ip;
-    const int o_len = ip.add(std::vector<int>(lens, lens + B)), o_lg = ip.add(bits);
-    ip.upload(c.ws, c.m.pinned(), c.s);
+    const int o_len = ip.add(a.lens, a.B), o_lg = ip.add(bits);
+    const F0TrackWs w = f0_track_carve(c.ws, ip, a.B, a.T_max);
+    ip.send(c.m.pinned(), c.s);
     F0TrackP q{};
-    F0P& p = q.y;
-    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B;
-    p.sample_rate = sample_rate; p.hop = hop; p.lag_min = lag_min; p.lag_max = lag_max; p.threshold = threshold;
-    p.f0 = f0; p.T_max = T_max; p.cmnd = cmnd; p.lag = lag; p.diff = diff;
+    q.y = f0_params(a, ip.dev(o_len));
     q.octave_cost = octave_cost; q.jump_cost = jump_cost;
     q.lg = reinterpret_cast<const float*>(ip.dev(o_lg));
-    q.dprime = c.ws.get<float>((size_t)B * T_max * (MT2_F0_MAX_LAG + 1));
-    q.psi = c.ws.get<unsigned char>((size_t)B * T_max * 256);
+    q.dprime = w.dprime; q.psi = w.psi;
     Stages st(c.m, c.s);
     st.mark("start");
     MT2_HIP(launch_f0_cmnd(q, c.s));
@@ -2268,12 +2303,12 @@ static void f0_stats_check(const float* f0, const int* frame_lens, int T_max, in
     MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
     MT2_REQUIRE(f0 != nullptr && frame_lens != nullptr && stats != nullptr && T_max >= 1, "bad buffers");
     MT2_REQUIRE(((uintptr_t)f0 & 3) == 0 && ((uintptr_t)stats & 7) == 0, "misaligned buffers");
-    for (int b = 0; b < B; ++b) MT2_REQUIRE(frame_lens[b] >= 1 && frame_lens[b] <= T_max, "frame count outside [1, T_max]");
-    MT2_REQUIRE(!f0_overlaps(stats, sizeof(double) * 6 * (size_t)B, f0, sizeof(float) * (size_t)B * T_max), "stats overlaps f0");
+    check_lens(frame_lens, B, T_max, "frame count outside [1, T_max]");
+    MT2_REQUIRE(!spans_overlap({stats, sizeof(double) * 6 * (size_t)B}, {f0, sizeof(float) * (size_t)B * T_max}), "stats overlaps f0");
 }
 static void f0_stats_run(const Ctx& c, const float* f0, const int* frame_lens, int T_max, int B, double* stats) {
     IntPlan ip;
-    const int o_len = ip.add(std::vector<int>(frame_lens, frame_lens + B));
+    const int o_len = ip.add(frame_lens, B);
     ip.upload(c.ws, c.m.pinned(), c.s);
     MT2_HIP(launch_f0_stats(f0, ip.dev(o_len), T_max, B, stats, c.s));
 }
@@ -2285,18 +2320,14 @@ static int energy_check(const float* wav, const int* lens, int L_max, int B, int
     MT2_REQUIRE(hop >= 1 && hop <= MT2_F0_FRAME, "hop outside [1, 1024]");
     MT2_REQUIRE(wav != nullptr && lens != nullptr && energy != nullptr && L_max >= 1, "bad buffers");
     MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)energy) & 3) == 0, "misaligned buffers");
-    int mx = 0;
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
-        mx = std::max(mx, lens[b]);
-    }
+    const int mx = check_lens(lens, B, L_max, "waveform length outside [1, L_max]");
     MT2_REQUIRE(T_max >= 1 + mx / hop, "T_max smaller than 1 + max length / hop");
-    MT2_REQUIRE(!f0_overlaps(energy, sizeof(float) * (size_t)B * T_max, wav, sizeof(float) * (size_t)B * L_max), "energy overlaps wav");
+    MT2_REQUIRE(!spans_overlap({energy, sizeof(float) * (size_t)B * T_max}, {wav, sizeof(float) * (size_t)B * L_max}), "energy overlaps wav");
     return mx;
 }
 static void energy_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int hop, float* energy, int T_max) {
     IntPlan ip;
-    const int o_len = ip.add(std::vector<int>(lens, lens + B));
+    const int o_len = ip.add(lens, B);
     ip.upload(c.ws, c.m.pinned(), c.s);
     EnergyP p{};
     p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B; p.hop = hop; p.energy = energy; p.T_max = T_max;
@@ -2310,21 +2341,16 @@ static void phone_prosody_check(const float* f0, const float* energy, const int*
                     T_max >= 1, "bad buffers");
     MT2_REQUIRE((((uintptr_t)f0 | (uintptr_t)energy | (uintptr_t)dur) & 3) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)dur_sum & 7) == 0,
                 "misaligned buffers");
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(phone_lens[b] >= 1 && phone_lens[b] <= Np_max, "phone count outside [1, Np_max]");
-        MT2_REQUIRE(frame_lens[b] >= 1 && frame_lens[b] <= T_max, "frame count outside [1, T_max]");
-    }
+    check_lens(phone_lens, B, Np_max, "phone count outside [1, Np_max]");
+    check_lens(frame_lens, B, T_max, "frame count outside [1, T_max]");
     const size_t nt = sizeof(float) * (size_t)B * T_max, nd = sizeof(int) * (size_t)B * Np_max, no = sizeof(double) * 8 * (size_t)B * Np_max,
                  ns = sizeof(long long) * (size_t)B;
-    MT2_REQUIRE(!f0_overlaps(out, no, f0, nt) && !f0_overlaps(out, no, energy, nt) && !f0_overlaps(out, no, dur, nd) &&
-                    !f0_overlaps(dur_sum, ns, f0, nt) && !f0_overlaps(dur_sum, ns, energy, nt) && !f0_overlaps(dur_sum, ns, dur, nd) &&
-                    !f0_overlaps(dur_sum, ns, out, no),
-                "overlapping buffers");
+    MT2_REQUIRE(!outputs_overlap({{out, no}, {dur_sum, ns}}, {{f0, nt}, {energy, nt}, {dur, nd}}), "overlapping buffers");
 }
 static void phone_prosody_run(const Ctx& c, const float* f0, const float* energy, const int* dur, const int* phone_lens, int Np_max,
                               const int* frame_lens, int T_max, int B, double* out, long long* dur_sum) {
     IntPlan ip;
-    const int o_np = ip.add(std::vector<int>(phone_lens, phone_lens + B)), o_t = ip.add(std::vector<int>(frame_lens, frame_lens + B));
+    const int o_np = ip.add(phone_lens, B), o_t = ip.add(frame_lens, B);
     ip.upload(c.ws, c.m.pinned(), c.s);
     PhoneProsodyP p{};
     p.f0 = f0; p.energy = energy; p.T_max = T_max; p.dur = dur; p.Np_max = Np_max; p.np_len = ip.dev(o_np); p.t_len = ip.dev(o_t);
@@ -2338,16 +2364,14 @@ static void pitch_contour_check(const float* f0, const int* frame_lens, int T_ma
     MT2_REQUIRE(center == 0 || center == 1, "center must be 0 or 1");
     MT2_REQUIRE(f0 != nullptr && frame_lens != nullptr && st != nullptr && n_voiced != nullptr && T_max >= 1, "bad buffers");
     MT2_REQUIRE((((uintptr_t)f0 | (uintptr_t)st | (uintptr_t)n_voiced | (uintptr_t)index) & 3) == 0, "misaligned buffers");
-    for (int b = 0; b < B; ++b) MT2_REQUIRE(frame_lens[b] >= 1 && frame_lens[b] <= T_max, "frame count outside [1, T_max]");
+    check_lens(frame_lens, B, T_max, "frame count outside [1, T_max]");
     const size_t nt = sizeof(float) * (size_t)B * T_max, nb = sizeof(int) * (size_t)B;
-    MT2_REQUIRE(!f0_overlaps(st, nt, f0, nt) && !f0_overlaps(index, nt, f0, nt) && !f0_overlaps(n_voiced, nb, f0, nt) &&
-                    !f0_overlaps(st, nt, index, nt) && !f0_overlaps(st, nt, n_voiced, nb) && !f0_overlaps(index, nt, n_voiced, nb),
-                "overlapping buffers");
+    MT2_REQUIRE(!outputs_overlap({{st, nt}, {index, nt}, {n_voiced, nb}}, {{f0, nt}}), "overlapping buffers");
 }
 static void pitch_contour_run(const Ctx& c, const float* f0, const int* frame_lens, int T_max, int B, int center, float* st, int* n_voiced,
                               int* index) {
     IntPlan ip;
-    const int o_t = ip.add(std::vector<int>(frame_lens, frame_lens + B));
+    const int o_t = ip.add(frame_lens, B);
     ip.upload(c.ws, c.m.pinned(), c.s);
     PitchContourP p{};
     p.f0 = f0; p.T_max = T_max; p.t_len = ip.dev(o_t); p.B = B; p.center = center; p.st = st; p.n_voiced = n_voiced; p.index = index;
@@ -2363,25 +2387,48 @@ static int loudness_check(const float* wav, const int* lens, int L_max, int B, i
     MT2_REQUIRE(std::isfinite(target_lufs) && std::isfinite(peak_ceiling), "target_lufs / peak_ceiling must be finite");
     MT2_REQUIRE(wav != nullptr && lens != nullptr && L_max >= 1, "bad buffers");
     MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)out) & 3) == 0 && (((uintptr_t)stats | (uintptr_t)momentary) & 7) == 0, "misaligned buffers");
-    int mx = 0;
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(lens[b] >= 1 && lens[b] <= L_max, "waveform length outside [1, L_max]");
-        mx = std::max(mx, lens[b]);
-    }
+    const int mx = check_lens(lens, B, L_max, "waveform length outside [1, L_max]");
     MT2_REQUIRE(mx <= INT_MAX - 8 * 19200, "waveform too long");
     const int nb = std::max(mx / (sample_rate / 10) - 3, 0);
     MT2_REQUIRE(momentary == nullptr || (NB_max >= 1 && NB_max >= nb), "NB_max smaller than the blocks of the longest utterance (or < 1)");
     const size_t nw = sizeof(float) * (size_t)B * L_max, nst = sizeof(double) * 8 * (size_t)B, nm = sizeof(double) * (size_t)B * std::max(NB_max, 0);
-    MT2_REQUIRE(out == nullptr || out == wav || !f0_overlaps(out, nw, wav, nw), "out overlaps wav without being wav");
-    MT2_REQUIRE(!f0_overlaps(stats, nst, wav, nw) && !f0_overlaps(momentary, nm, wav, nw) && !f0_overlaps(stats, nst, out, nw) &&
-                    !f0_overlaps(momentary, nm, out, nw) && !f0_overlaps(stats, nst, momentary, nm),
-                "overlapping buffers");
+    MT2_REQUIRE(out == wav || !spans_overlap({out, nw}, {wav, nw}), "out overlaps wav without being wav");
+    MT2_REQUIRE(!outputs_overlap({{stats, nst}, {momentary, nm}}, {{wav, nw}, {out, nw}}), "overlapping buffers");
     return mx;
 }
-// enqueues only: the lengths and the carry matrix travel in the call's one IntPlan upload; the gain is formed and read on the device
-static void loudness_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, double target_lufs,
-                         double peak_ceiling, float* out, double* stats, double* momentary, int NB_max) {
-    LoudnessP p{};
+// The arena of one loudness / EBU call, in carve order: the plan (the lengths, the carry matrix and, for EBU, the filter table), the
+// chunk states, S, the words (peak | gain, and EBU's true peak) and, for EBU alone, the loudness rows and z3 / the keys
+struct LoudWs { double *state, *sums; unsigned* words; double *row8, *keys; };
+template <class Ws> static LoudWs loudness_carve(Ws& ws, IntPlan& ip, size_t B, int NS, bool ebu) {
+    LoudWs w{};
+    ip.carve(ws);
+    w.state = ws.template get<double>(B * NS * 4);
+    w.sums = ws.template get<double>(B * NS);
+    w.words = ws.template get<unsigned>((ebu ? 3 : 2) * B);
+    if (ebu) {
+        w.row8 = ws.template get<double>(8 * B);
+        w.keys = ws.template get<double>(B * std::max(NS - 29, 0));
+    }
+    return w;
+}
+// B utterances, the longest of max_len samples
+static long long loudness_arena_bytes(int sample_rate, long long max_len, int B, bool ebu) {
+    IntPlan ip;
+    ip.add_fill(B, 0);
+    ip.add_fill(32, 0);
+    if (ebu) ip.add_fill((size_t)true_peak_oversample(sample_rate) * MT2_TP_TAPS, 0);
+    ArenaCount count;
+    loudness_carve(count, ip, B, (int)(max_len / (sample_rate / 10)), ebu);
+    return (long long)count.bytes;
+}
+// What the loudness and the EBU call share, up to and including the gate kernel and its mark.  The caller has set the gate's own
+// fields of p (targets, out, stats, momentary); the rest of p is filled here.  `tbits`: nullptr, or what the EBU call adds - its
+// filter table as the plan's third entry, the third word row, the loudness rows and the keys.  Its gate kernel only measures, into
+// the rows (ebu.hip forms the gain); the loudness call's forms the gain where there is an `out` to scale.
+// -> the arena, and the table on the device
+struct LoudChain { LoudWs w; const float* table; };
+static LoudChain loudness_chain(const Ctx& c, Stages& st, LoudnessP& p, const float* wav, const int* lens, int L_max, int B, int max_len,
+                                int sample_rate, const std::vector<int>* tbits) {
     p.h = sample_rate / 10;
     loudness_coeffs(sample_rate, p.c);
     if (c.m.loud_rate != sample_rate) {          // a function of the rate alone: kept by the handle
@@ -2391,18 +2438,15 @@ static void loudness_run(const Ctx& c, const float* wav, const int* lens, int L_
     std::vector<int> mbits(32);
     std::memcpy(mbits.data(), c.m.loud_M, sizeof(c.m.loud_M));
     IntPlan ip;
-    const int o_len = ip.add(std::vector<int>(lens, lens + B)), o_m = ip.add(mbits);
-    ip.upload(c.ws, c.m.pinned(), c.s);
-    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B; p.M = ip.dev(o_m);
+    const int o_len = ip.add(lens, B), o_m = ip.add(mbits), o_t = tbits ? ip.add(*tbits) : 0;
     p.NS = max_len / p.h;
-    p.state = c.ws.get<double>((size_t)B * p.NS * 4);
-    p.sums = c.ws.get<double>((size_t)B * p.NS);
-    unsigned* words = c.ws.get<unsigned>((size_t)2 * B);          // peak | gain
-    p.peak = words;
-    p.gain = out ? reinterpret_cast<float*>(words + B) : nullptr;
-    p.target_lufs = target_lufs; p.peak_ceiling = peak_ceiling; p.out = out; p.stats = stats; p.momentary = momentary; p.NB_max = NB_max;
-    MT2_HIP(hipMemsetAsync(p.peak, 0, sizeof(unsigned) * B, c.s));
-    Stages st(c.m, c.s);
+    const LoudWs w = loudness_carve(c.ws, ip, B, p.NS, tbits != nullptr);
+    ip.send(c.m.pinned(), c.s);
+    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B; p.M = ip.dev(o_m);
+    p.state = w.state; p.sums = w.sums; p.peak = w.words;
+    if (tbits) p.stats = w.row8;
+    else if (p.out) p.gain = reinterpret_cast<float*>(w.words + B);
+    MT2_HIP(hipMemsetAsync(w.words, 0, sizeof(unsigned) * (tbits ? 3 : 1) * B, c.s));
     st.mark("start");
     MT2_HIP(launch_loudness_filter(p, c.s));
     st.mark("loud_zero_state");
@@ -2412,6 +2456,15 @@ static void loudness_run(const Ctx& c, const float* wav, const int* lens, int L_
     st.mark("loud_sums");
     MT2_HIP(launch_loudness_gate(p, c.s));
     st.mark("loud_gate");
+    return {w, tbits ? reinterpret_cast<const float*>(ip.dev(o_t)) : nullptr};
+}
+// enqueues only: the lengths and the carry matrix travel in the call's one IntPlan upload; the gain is formed and read on the device
+static void loudness_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, double target_lufs,
+                         double peak_ceiling, float* out, double* stats, double* momentary, int NB_max) {
+    LoudnessP p{};
+    p.target_lufs = target_lufs; p.peak_ceiling = peak_ceiling; p.out = out; p.stats = stats; p.momentary = momentary; p.NB_max = NB_max;
+    Stages st(c.m, c.s);
+    (void)loudness_chain(c, st, p, wav, lens, L_max, B, max_len, sample_rate, nullptr);
     if (out) {
         MT2_HIP(launch_loudness_scale(p, c.s));
         st.mark("loud_scale");
@@ -2429,63 +2482,34 @@ static int ebu_check(const float* wav, const int* lens, int L_max, int B, int sa
     MT2_REQUIRE(short_term == nullptr || (NST_max >= 1 && NST_max >= nst), "NST_max smaller than the short-term blocks of the longest utterance (or < 1)");
     const size_t nw = sizeof(float) * (size_t)B * L_max, ns = sizeof(double) * MT2_EBU_FIELDS * (size_t)B,
                  nm = sizeof(double) * (size_t)B * std::max(NB_max, 0), nt = sizeof(double) * (size_t)B * std::max(NST_max, 0);
-    MT2_REQUIRE(!f0_overlaps(stats, ns, wav, nw) && !f0_overlaps(stats, ns, out, nw) && !f0_overlaps(stats, ns, momentary, nm) &&
-                    !f0_overlaps(stats, ns, short_term, nt) && !f0_overlaps(short_term, nt, wav, nw) && !f0_overlaps(short_term, nt, out, nw) &&
-                    !f0_overlaps(short_term, nt, momentary, nm),
-                "overlapping buffers");
+    MT2_REQUIRE(!outputs_overlap({{stats, ns}, {short_term, nt}}, {{wav, nw}, {out, nw}, {momentary, nm}}), "overlapping buffers");
     return mx;
 }
 // enqueues only: the lengths, the carry matrix and the filter table travel in the call's one IntPlan upload; the loudness kernels run
 // as in loudness_run and leave their row in the arena; the gain is formed and read on the device
 static void ebu_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, double target_lufs,
                     double ceiling_dbtp, float* out, double* stats, double* momentary, int NB_max, double* short_term, int NST_max) {
-    LoudnessP p{};
-    p.h = sample_rate / 10;
-    loudness_coeffs(sample_rate, p.c);
-    if (c.m.loud_rate != sample_rate) {
-        loudness_carry_matrix(p.c, p.h, c.m.loud_M);
-        c.m.loud_rate = sample_rate;
-    }
     EbuP e{};
     e.o = true_peak_oversample(sample_rate);
-    std::vector<int> mbits(32), tbits((size_t)e.o * MT2_TP_TAPS);
-    std::memcpy(mbits.data(), c.m.loud_M, sizeof(c.m.loud_M));
+    std::vector<int> tbits((size_t)e.o * MT2_TP_TAPS);
     {
         std::vector<float> table(tbits.size());
         true_peak_table(sample_rate, table.data());
         std::memcpy(tbits.data(), table.data(), sizeof(float) * table.size());
     }
-    IntPlan ip;
-    const int o_len = ip.add(std::vector<int>(lens, lens + B)), o_m = ip.add(mbits), o_t = ip.add(tbits);
-    ip.upload(c.ws, c.m.pinned(), c.s);
-    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B; p.M = ip.dev(o_m);
-    p.NS = max_len / p.h;
-    p.state = c.ws.get<double>((size_t)B * p.NS * 4);
-    p.sums = c.ws.get<double>((size_t)B * p.NS);
-    unsigned* words = c.ws.get<unsigned>((size_t)3 * B);          // peak | gain | true peak
-    double* row8 = c.ws.get<double>((size_t)8 * B);
-    p.peak = words;
-    p.gain = nullptr;                                             // the gate kernel measures; ebu.hip forms the gain
-    p.stats = row8; p.momentary = momentary; p.NB_max = NB_max;
+    LoudnessP p{};
+    p.momentary = momentary; p.NB_max = NB_max;
+    Stages st(c.m, c.s);
+    const LoudChain ch = loudness_chain(c, st, p, wav, lens, L_max, B, max_len, sample_rate, &tbits);
+    unsigned* const words = ch.w.words;                           // peak | gain | true peak
     e.wav = wav; e.L_max = L_max; e.len = p.len; e.max_len = max_len; e.B = B; e.h = p.h;
-    e.table = reinterpret_cast<const float*>(ip.dev(o_t));
+    e.table = ch.table;
     e.tp = words + 2 * B;
-    e.sums = p.sums; e.NS = p.NS; e.row8 = row8;
+    e.sums = p.sums; e.NS = p.NS; e.row8 = ch.w.row8;
     e.NST = std::max(p.NS - 29, 0);
-    e.keys = c.ws.get<double>((size_t)B * e.NST);
+    e.keys = ch.w.keys;
     e.gain = out ? reinterpret_cast<float*>(words + B) : nullptr;
     e.target_lufs = target_lufs; e.ceiling_dbtp = ceiling_dbtp; e.stats = stats; e.short_term = short_term; e.NST_max = NST_max;
-    MT2_HIP(hipMemsetAsync(words, 0, sizeof(unsigned) * 3 * B, c.s));
-    Stages st(c.m, c.s);
-    st.mark("start");
-    MT2_HIP(launch_loudness_filter(p, c.s));
-    st.mark("loud_zero_state");
-    MT2_HIP(launch_loudness_carry(p, c.s));
-    st.mark("loud_carry");
-    MT2_HIP(launch_loudness_sums(p, c.s));
-    st.mark("loud_sums");
-    MT2_HIP(launch_loudness_gate(p, c.s));
-    st.mark("loud_gate");
     MT2_HIP(launch_true_peak(e, c.s));
     st.mark("ebu_true_peak");
     MT2_HIP(launch_loudness_range(e, c.s));
@@ -2507,10 +2531,25 @@ static void dtw_check_geometry(int Tx_max, int Ty_max, int D, int B) {
 }
 static void dtw_check_lens(const int* x_lens, int Tx_max, const int* y_lens, int Ty_max, int B) {
     MT2_REQUIRE(x_lens != nullptr && y_lens != nullptr, "x_lens / y_lens is NULL");
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(x_lens[b] >= 1 && x_lens[b] <= Tx_max, "x length outside [1, Tx_max]");
-        MT2_REQUIRE(y_lens[b] >= 1 && y_lens[b] <= Ty_max, "y length outside [1, Ty_max]");
-    }
+    check_lens(x_lens, B, Tx_max, "x length outside [1, Tx_max]");
+    check_lens(y_lens, B, Ty_max, "y length outside [1, Ty_max]");
+}
+// the arena of one dtw_run, in carve order: the plan (both lengths), the costs in the skewed layout (strips of 64 rows), the packed
+// directions
+struct DtwWs { float* skew; unsigned* dirs; };
+template <class Ws> static DtwWs dtw_carve(Ws& ws, IntPlan& ip, size_t Tx_max, int Ty_max, size_t B) {
+    DtwWs w{};
+    ip.carve(ws);
+    w.skew = ws.template get<float>(B * ((Tx_max + 63) / 64) * dtw_skew_steps(Ty_max) * 64);
+    w.dirs = ws.template get<unsigned>(B * Tx_max * dtw_dir_words(Ty_max));
+    return w;
+}
+static long long dtw_arena_bytes(int Tx_max, int Ty_max, int B) {
+    IntPlan ip;
+    ip.add_fill(2 * (size_t)B + 8, 0);      // the documented figure ("at most"): room for both lengths and the gap between them
+    ArenaCount count;
+    dtw_carve(count, ip, Tx_max, Ty_max, B);
+    return (long long)count.bytes;
 }
 
 // DTW of X onto Y by the rule of dtw.hip: cost -> accumulate -> backtrack on the caller's stream, nothing else
@@ -2521,14 +2560,13 @@ static void dtw_run(const Ctx& c, const float* X, const int* x_lens, int Tx_max,
     p.X = X; p.Tx_max = Tx_max; p.Y = Y; p.Ty_max = Ty_max; p.D = D; p.B = B;
     p.max_tx = *std::max_element(x_lens, x_lens + B); p.max_ty = *std::max_element(y_lens, y_lens + B);
     IntPlan ip;
-    const int o_x = ip.add(std::vector<int>(x_lens, x_lens + B)), o_y = ip.add(std::vector<int>(y_lens, y_lens + B));
-    ip.upload(c.ws, c.m.pinned(), c.s);
+    const int o_x = ip.add(x_lens, B), o_y = ip.add(y_lens, B);
+    const DtwWs w = dtw_carve(c.ws, ip, Tx_max, Ty_max, B);
+    ip.send(c.m.pinned(), c.s);
     p.x_len = ip.dev(o_x); p.y_len = ip.dev(o_y);
     p.cost = cost;
-    p.S_max = (Tx_max + 63) / 64; p.TS = (int)dtw_skew_steps(Ty_max);
-    p.skew = c.ws.get<float>((size_t)B * p.S_max * p.TS * 64);
-    p.DW = (int)dtw_dir_words(Ty_max);
-    p.dirs = c.ws.get<unsigned>((size_t)B * Tx_max * p.DW);
+    p.S_max = (Tx_max + 63) / 64; p.TS = (int)dtw_skew_steps(Ty_max); p.skew = w.skew;
+    p.DW = (int)dtw_dir_words(Ty_max); p.dirs = w.dirs;
     p.acc = acc; p.lo = lo; p.hi = hi; p.steps = steps; p.total = total;
     Stages st(c.m, c.s);
     st.mark("start");
@@ -2559,7 +2597,7 @@ static void align_durations_run(const Ctx& c, const int* hi, const int* y_lens, 
         MT2_REQUIRE(sum >= 1, "synthetic durations sum to 0");
     }
     IntPlan ip;
-    const int o_y = ip.add(std::vector<int>(y_lens, y_lens + B)), o_n = ip.add(std::vector<int>(phone_lens, phone_lens + B));
+    const int o_y = ip.add(y_lens, B), o_n = ip.add(phone_lens, B);
     const int o_cum = ip.add(cum);
     ip.upload(c.ws, c.m.pinned(), c.s);
     AlignDurP p{};

@@ -465,10 +465,9 @@ struct TrimP {
 hipError_t launch_trim(const TrimP& p, hipStream_t s);
 
 // ---- dynamic time warping of a synthesised mel onto a real one (dtw.hip; the rule is in its header and in megatts2_hip.h) --------
-// host only, no HIP call: u32 words of packed directions per row, and the arena bytes of one mt2_dtw_align call
+// host only, no HIP call: u32 words of packed directions per row
 long long dtw_dir_words(int Ty_max);
 long long dtw_skew_steps(int Ty_max);          // 64 ceil((Ty_max + 63) / 64): steps a strip of 64 skewed rows takes, in whole periods
-long long dtw_workspace_bytes(int Tx_max, int Ty_max, int B);
 // Three launches on one stream, each over the ragged batch: cost -> accumulate (one workgroup per utterance) -> backtrack (one wave
 // per utterance).  Cells outside an utterance's Tx_b x Ty_b are neither read nor written.
 struct DtwP {
@@ -581,12 +580,10 @@ hipError_t launch_pitch_contour(const PitchContourP& p, hipStream_t s);
 
 // ---- integrated loudness and loudness normalisation (loudness.hip; the rule is in its header and in megatts2_hip.h) ------------------
 // host only, no HIP call: the rate the rule accepts (a multiple of 10 in [8000, 192000]); c[10] = b0 b1 b2 a1 a2 of the shelf, then of
-// the high-pass; M[16] = A^h row-major, the zero-input state transition of one sub-block; the arena bytes of a call with B utterances,
-// the longest of max_len samples
+// the high-pass; M[16] = A^h row-major, the zero-input state transition of one sub-block
 bool loudness_rate_ok(int sample_rate);
 void loudness_coeffs(int sample_rate, double* c);
 void loudness_carry_matrix(const double* c, int h, double* M);
-long long loudness_workspace_bytes(int sample_rate, long long max_len, long long B);
 // Four launches on one stream in this order - zero-state chunks + peak -> carry -> sub-block sums -> blocks, gates, gain, stats - and
 // a fifth, scale, for the normalising call.  The caller zeroes peak[] in front.
 struct LoudnessP {
@@ -610,11 +607,9 @@ hipError_t launch_loudness_gate(const LoudnessP& p, hipStream_t s);
 hipError_t launch_loudness_scale(const LoudnessP& p, hipStream_t s);
 
 // ---- true peak, short-term loudness and loudness range (ebu.hip; the rule is in its header and in megatts2_hip.h) --------------------
-// host only, no HIP call: o = ceil(192000 / sample_rate); table [o][MT2_TP_TAPS] f32 (row 0 the unit sample); the arena bytes of a call
-// with B utterances, the longest of max_len samples
+// host only, no HIP call: o = ceil(192000 / sample_rate); table [o][MT2_TP_TAPS] f32 (row 0 the unit sample)
 int true_peak_oversample(int sample_rate);
 void true_peak_table(int sample_rate, float* table);
-long long ebu_workspace_bytes(int sample_rate, long long max_len, long long B);
 // Two launches behind the four of LoudnessP on the same stream: launch_true_peak any time after tp[] is zeroed, launch_loudness_range
 // behind both it and launch_loudness_gate (which wrote row8 with gain 1).  The normalising call then runs launch_loudness_scale on `gain`.
 struct EbuP {

@@ -23,6 +23,9 @@ void check_hip(hipError_t e, const char* what, const char* file, int line);
                                         std::to_string(__LINE__));                               \
     } while (0)
 
+// what one allocation takes from the arena: a multiple of 256 bytes, never none
+inline size_t arena_round(size_t bytes) { return bytes == 0 ? 256 : (bytes + 255) & ~size_t(255); }
+
 // Bump allocator over hipMalloc'd chunks; reset() at the start of every API call.  Chunks persist, so
 // after the first call of a given shape no allocation happens on the hot path.
 class Arena {
@@ -43,6 +46,13 @@ class Arena {
     struct Chunk { char* p; size_t size, used; };
     std::vector<Chunk> chunks_;
     size_t high_ = 0;
+};
+
+// The arena's stand-in for the byte queries (mt2_*_query): a call's carve, written once over "an arena", run over this adds up
+// what the same carve takes from the real one.  The pointers it hands out are not for use.
+struct ArenaCount {
+    size_t bytes = 0;
+    template <class T> T* get(size_t n) { bytes += arena_round(n * sizeof(T)); return nullptr; }
 };
 
 // Host staging for H2D copies of small plans: PINNED memory owned by the handle.  hipMemcpyAsync from a pageable
@@ -79,10 +89,17 @@ struct RowSet {
 // all small integer arrays of one API call, uploaded with ONE H2D copy
 class IntPlan {
   public:
-    int add(const std::vector<int>& v);
+    int add(const int* v, size_t n);
+    int add(const std::vector<int>& v) { return add(v.data(), v.size()); }
     int add_fill(size_t n, int value);
     std::vector<int>& host() { return h_; }
-    void upload(Arena& a, PinnedPool& pin, hipStream_t s);
+    // the plan's place in the arena (or its bytes in an ArenaCount), then the copy into it: upload() is both
+    template <class A> void carve(A& a) {
+        if (h_.empty()) h_.push_back(0);
+        d_ = a.template get<int>(h_.size());
+    }
+    void send(PinnedPool& pin, hipStream_t s);
+    void upload(Arena& a, PinnedPool& pin, hipStream_t s) { carve(a); send(pin, s); }
     const int* dev(int offset) const { return d_ + offset; }
 
   private:

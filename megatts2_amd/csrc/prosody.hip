@@ -32,6 +32,7 @@
 // bit-identical to its utterances alone, whatever the slot, L_max, T_max or Np_max.  A non-finite input cannot fault, cannot write
 // outside the outputs and cannot change an output whose inputs do not hold it.
 #include "../../include/megatts2_hip.h"
+#include "mt2_block_reduce.h"
 #include "mt2_kernels.h"
 
 #include <math.h>
@@ -169,18 +170,6 @@ hipError_t launch_phone_prosody(const PhoneProsodyP& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the 256 partial sums of a workgroup in a fixed tree (stride 128 .. 1), as f0_stats_kernel's; the result is in every thread
-__device__ __forceinline__ double prosody_tree_sum(double* red, double v) {
-    __syncthreads();                           // the previous use of red[] is over
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __global__ __launch_bounds__(kThreads) void pitch_contour_kernel(PitchContourP p) {
     __shared__ double red[kThreads];
     __shared__ int wsum[kWaves];
@@ -195,8 +184,8 @@ __global__ __launch_bounds__(kThreads) void pitch_contour_kernel(PitchContourP p
             const float v = f0[t];
             if (v > 0.0f) { cnt += 1.0; sum += 12.0 * log2((double)v); }
         }
-        const double n = prosody_tree_sum(red, cnt);
-        const double total = prosody_tree_sum(red, sum);
+        const double n = block_tree_sum<kThreads>(red, cnt);
+        const double total = block_tree_sum<kThreads>(red, sum);
         if (n > 0.0) mu = total / n;
     }
     int base = 0;                                                          // the voiced frames in front of this chunk (uniform)

@@ -11,6 +11,7 @@
 //
 // Every output sample is ONE f32 fma chain over k ascending: it depends on its utterance's samples and on (o, n) only - not on
 // the tile size, the batch, the slot or L_max - so a ragged batch is bit-identical to its utterances resampled one by one.
+#include "mt2_block_reduce.h"
 #include "mt2_kernels.h"
 
 #include <float.h>
@@ -83,19 +84,6 @@ void resample_table(const ResampleRule& r, float* table, bool tap_major) {
         }
 }
 
-// max over the workgroup of a non-negative value, merged into *word: an ordinary vector atomic max on the u32 pattern of the
-// float (ordered like the floats themselves while they are >= 0) - order-independent, so the peak is deterministic
-__device__ __forceinline__ void merge_peak(float v, float* red, unsigned* word) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        if (m > 0.0f) atomicMax(word, __float_as_uint(m));
-    }
-}
-
 // One workgroup = one utterance's run of tb consecutive output blocks (block i = outputs i * n .. i * n + n - 1, all fed by the
 // inputs i * o - width .. i * o - width + taps - 1).  The run's input window is staged ONCE in LDS with 16-byte loads; a sample
 // outside [0, len) is a zero by its index, never a read.  Lanes walk the run's outputs, phase fastest; the table is tap-major [taps][n],
@@ -162,7 +150,7 @@ __global__ __launch_bounds__(kThreads) void resample_rows_kernel(ResampleP p) {
         }
     }
     for (long long j = max(j0, (long long)Lout) + threadIdx.x; j < j1; j += kThreads) out[j] = 0.0f;
-    if (p.peak) merge_peak(peak, red, p.peak + b);
+    if (p.peak) block_peak_merge(peak, red, p.peak + b);
 }
 
 hipError_t launch_resample_rows(const ResampleP& p, hipStream_t s) {
@@ -183,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void peak_rows_kernel(const float* x, lon
     float v = 0.0f;
     for (long long j = (long long)blockIdx.x * kThreads + threadIdx.x; j < L; j += (long long)gridDim.x * kThreads)
         v = fmaxf(v, fabsf(xr[j]));
-    merge_peak(v, red, peak + b);
+    block_peak_merge(v, red, peak + b);
 }
 hipError_t launch_peak_rows(const float* x, long long stride, const int* len, int max_len, int B, unsigned* peak, hipStream_t s) {
     if (B <= 0 || max_len <= 0) return hipSuccess;

@@ -14,6 +14,7 @@
 // Neither the address, the batch slot nor L_max enters, so a ragged batch is bit-identical to its utterances alone, energies
 // included.  A sample at or beyond L is a zero by its index, never a read.
 #include "../../include/megatts2_hip.h"
+#include "mt2_block_reduce.h"
 #include "mt2_kernels.h"
 
 #include <float.h>
@@ -82,15 +83,7 @@ __global__ __launch_bounds__(kThreads) void trim_frame_energy_kernel(TrimP p) {
     float e = 0.0f;
     if (f < F) e = frame_energy(p.sums + (long long)b * p.NB, f, nb);
     if (p.energy && f < p.F_max) p.energy[(long long)b * p.F_max + f] = e;
-    float v = e;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        if (m > 0.0f) atomicMax(p.peak + b, __float_as_uint(m));
-    }
+    block_peak_merge(e, red, p.peak + b);
 }
 
 // first / last kept frame of each utterance: vector atomic min / max of the frame index (first[] starts at UINT_MAX, last[] at -1).

@@ -741,6 +741,27 @@ class NativeModel:
         return {names[i].decode(): float(ms[i]) for i in range(max(n, 0))}
 
 
+def _wav_lens(wav, lens):
+    """What every waveform call of MelFrontEnd starts with: wav as a contiguous f32 [B, L] device tensor and lens as int32 [B] (every
+    row L by default) -> (wav, lens, B, L)."""
+    import torch
+    assert wav.is_cuda and wav.dim() == 2
+    wav = wav.contiguous().to(torch.float32)
+    B, L = wav.shape
+    ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
+    assert ln.shape == (B,)
+    return wav, ln, B, L
+
+
+def _out_rows(out, B: int, like, width):
+    """The `out` of a call: the caller's contiguous f32 [B, >= what the call needs] device tensor, or a new [B, width()] beside `like`."""
+    import torch
+    if out is None:
+        out = torch.empty(B, width(), device=like.device, dtype=torch.float32)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+    return out
+
+
 class MelFrontEnd:
     """extract_mel_spec on the GPU (reference modules/tokenizer.py:107-125): STFT as an implicit conv on the
     GEMM engine, magnitude, slaney mel filterbank, log(clamp(., 1e-5)).  Owns a bare handle (no weights)."""
@@ -788,15 +809,8 @@ class MelFrontEnd:
         (f32 [B, max L_out], out_lens int32 [B]) with L_out = ceil(n * L / o), zeros beyond out_lens[b]; samples beyond lens[b] are
         never read.  normalize: each utterance divided by its peak as well (:336).  out: a contiguous f32 [B, >= max L_out] device
         tensor to write into.  sr_in == audio.sample_rate is an error: there is nothing to resample."""
-        import torch
-        assert wav.is_cuda and wav.dim() == 2
-        wav = wav.contiguous().to(torch.float32)
-        B, L = wav.shape
-        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
-        assert ln.shape == (B,)
-        if out is None:
-            out = torch.empty(B, resample_query(sr_in, self.audio.sample_rate, int(ln.max()))[0], device=wav.device, dtype=torch.float32)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        wav, ln, B, L = _wav_lens(wav, lens)
+        out = _out_rows(out, B, wav, lambda: resample_query(sr_in, self.audio.sample_rate, int(ln.max()))[0])
         out_lens = np.zeros(B, np.int32)
         _check(self.lib.mt2_resample(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, int(sr_in), self.audio.sample_rate,
                                      MT2_RESAMPLE_NORMALIZE if normalize else 0, _ptr(out), out.shape[1], _iptr(out_lens)))
@@ -811,14 +825,8 @@ class MelFrontEnd:
         [B, >= max lens] device tensor to write into (not wav).  return_energy: a fourth result, the frame energies f32
         [B, 1 + max lens // 512] (device).  The call waits for the device once, for the bounds."""
         import torch
-        assert wav.is_cuda and wav.dim() == 2
-        wav = wav.contiguous().to(torch.float32)
-        B, L = wav.shape
-        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
-        assert ln.shape == (B,)
-        if out is None:
-            out = torch.empty(B, max(int(ln.max()), 1), device=wav.device, dtype=torch.float32)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        wav, ln, B, L = _wav_lens(wav, lens)
+        out = _out_rows(out, B, wav, lambda: max(int(ln.max()), 1))
         F = 1 + max(int(ln.max()), 0) // TRIM_HOP
         energy = torch.empty(B, F, device=wav.device, dtype=torch.float32) if return_energy else None
         bounds = np.zeros((B, 2), np.int32)
@@ -837,11 +845,7 @@ class MelFrontEnd:
         400 ms block (every 100 ms), -inf behind an utterance's own blocks.  Samples beyond lens[b] are never read.  The call only
         enqueues."""
         import torch
-        assert wav.is_cuda and wav.dim() == 2
-        wav = wav.contiguous().to(torch.float32)
-        B, L = wav.shape
-        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
-        assert ln.shape == (B,)
+        wav, ln, B, L = _wav_lens(wav, lens)
         sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
         stats = torch.empty(B, LOUDNESS_FIELDS, device=wav.device, dtype=torch.float64)
         mom, NB = None, 0
@@ -862,11 +866,7 @@ class MelFrontEnd:
         [B, max(1, blocks of the longest)] as `loudness` returns it.  return_short_term: also f64 [B, max(1, short-term blocks of the
         longest)], -inf behind an utterance's own blocks.  Samples beyond lens[b] are never read.  The call only enqueues."""
         import torch
-        assert wav.is_cuda and wav.dim() == 2
-        wav = wav.contiguous().to(torch.float32)
-        B, L = wav.shape
-        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
-        assert ln.shape == (B,)
+        wav, ln, B, L = _wav_lens(wav, lens)
         sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
         stats = torch.empty(B, EBU_FIELDS, device=wav.device, dtype=torch.float64)
         ns = max(int(ln.max()), 0) // max(sr // 10, 1)
@@ -893,11 +893,7 @@ class MelFrontEnd:
         [B, 8] of `loudness` for the INPUT, with g in the last field.  The gain is formed and read on the device: the call only
         enqueues, with no copy to the host and no wait."""
         import torch
-        assert wav.is_cuda and wav.dim() == 2
-        wav = wav.contiguous().to(torch.float32)
-        B, L = wav.shape
-        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
-        assert ln.shape == (B,)
+        wav, ln, B, L = _wav_lens(wav, lens)
         sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
         if out is None:
             out = torch.empty_like(wav)
@@ -923,22 +919,24 @@ class MelFrontEnd:
         return_cmnd f32 [B, T] (the normalised difference at the chosen lag; voiced iff < threshold), return_lag int32 [B, T],
         return_diff f32 [B, T, 257] (the difference function).  out: a contiguous f32 [B, >= T] device tensor to write f0 into (the
         extras then have its width).  The call only enqueues."""
+        return self._f0(None, wav, lens, fmin, fmax, threshold, hop, return_cmnd, return_lag, return_diff, out)
+
+    def _f0(self, costs, wav, lens, fmin, fmax, threshold, hop, return_cmnd, return_lag, return_diff, out):
+        """`f0` (costs None) and `f0_track` (costs = (octave_cost, jump_cost)): the two differ in the entry point alone."""
         import torch
-        assert wav.is_cuda and wav.dim() == 2
-        wav = wav.contiguous().to(torch.float32)
-        B, L = wav.shape
-        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
-        assert ln.shape == (B,)
+        wav, ln, B, L = _wav_lens(wav, lens)
         hop = self.audio.hop_length if hop is None else int(hop)
-        if out is None:
-            out = torch.empty(B, 1 + max(int(ln.max()), 0) // max(hop, 1), device=wav.device, dtype=torch.float32)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        out = _out_rows(out, B, wav, lambda: 1 + max(int(ln.max()), 0) // max(hop, 1))
         T = out.shape[1]
         cmnd = torch.empty(B, T, device=wav.device, dtype=torch.float32) if return_cmnd else None
         lag = torch.empty(B, T, device=wav.device, dtype=torch.int32) if return_lag else None
         diff = torch.empty(B, T, F0_MAX_LAG + 1, device=wav.device, dtype=torch.float32) if return_diff else None
-        _check(self.lib.mt2_f0_yin(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, self.audio.sample_rate, hop, float(fmin), float(fmax),
-                                   float(threshold), _ptr(out), _ptr(cmnd), _ptr(lag), T, _ptr(diff)))
+        head = (self.h, _stream(), _ptr(wav), _iptr(ln), L, B, self.audio.sample_rate, hop, float(fmin), float(fmax), float(threshold))
+        tail = (_ptr(out), _ptr(cmnd), _ptr(lag), T, _ptr(diff))
+        if costs is None:
+            _check(self.lib.mt2_f0_yin(*head, *tail))
+        else:
+            _check(self.lib.mt2_f0_track(*head, float(costs[0]), float(costs[1]), *tail))
         extras = tuple(x for x in (cmnd, lag, diff) if x is not None)
         return (out,) + extras if extras else out
 
@@ -951,25 +949,7 @@ class MelFrontEnd:
         harmonics.  A frame is voiced iff d' at the tracked lag < threshold.  Arguments, outputs and extras as MelFrontEnd.f0.  A
         non-finite sample may change frames anywhere in its utterance (the path is global), never another utterance's.  The call
         only enqueues."""
-        import torch
-        assert wav.is_cuda and wav.dim() == 2
-        wav = wav.contiguous().to(torch.float32)
-        B, L = wav.shape
-        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
-        assert ln.shape == (B,)
-        hop = self.audio.hop_length if hop is None else int(hop)
-        if out is None:
-            out = torch.empty(B, 1 + max(int(ln.max()), 0) // max(hop, 1), device=wav.device, dtype=torch.float32)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
-        T = out.shape[1]
-        cmnd = torch.empty(B, T, device=wav.device, dtype=torch.float32) if return_cmnd else None
-        lag = torch.empty(B, T, device=wav.device, dtype=torch.int32) if return_lag else None
-        diff = torch.empty(B, T, F0_MAX_LAG + 1, device=wav.device, dtype=torch.float32) if return_diff else None
-        _check(self.lib.mt2_f0_track(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, self.audio.sample_rate, hop, float(fmin), float(fmax),
-                                     float(threshold), float(octave_cost), float(jump_cost), _ptr(out), _ptr(cmnd), _ptr(lag), T,
-                                     _ptr(diff)))
-        extras = tuple(x for x in (cmnd, lag, diff) if x is not None)
-        return (out,) + extras if extras else out
+        return self._f0((octave_cost, jump_cost), wav, lens, fmin, fmax, threshold, hop, return_cmnd, return_lag, return_diff, out)
 
     def f0_stats(self, f0, frame_lens=None):
         """Pitch moments of f0 f32 [B, T] (device) over the voiced frames (f0 > 0) among the first frame_lens[b] of each row ->
@@ -991,16 +971,9 @@ class MelFrontEnd:
         the F0 frames, so energy[b, t], f0[b, t] and mel frame t coincide; zeros behind an utterance's own 1 + lens[b] // hop.
         Samples beyond lens[b] are never read.  hop defaults to the mel front-end's.  out: a contiguous f32 [B, >= T] device tensor
         to write into.  No reference counterpart; parity with librosa's rms is unpinned.  The call only enqueues."""
-        import torch
-        assert wav.is_cuda and wav.dim() == 2
-        wav = wav.contiguous().to(torch.float32)
-        B, L = wav.shape
-        ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
-        assert ln.shape == (B,)
+        wav, ln, B, L = _wav_lens(wav, lens)
         hop = self.audio.hop_length if hop is None else int(hop)
-        if out is None:
-            out = torch.empty(B, 1 + max(int(ln.max()), 0) // max(hop, 1), device=wav.device, dtype=torch.float32)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        out = _out_rows(out, B, wav, lambda: 1 + max(int(ln.max()), 0) // max(hop, 1))
         _check(self.lib.mt2_frame_energy(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, hop, _ptr(out), out.shape[1]))
         return out
 
@@ -1086,9 +1059,7 @@ class MelFrontEnd:
         packed = torch.zeros(B, T, S, device=spec.device, dtype=torch.float32)
         packed[..., :F] = spec.real
         packed[..., F:2 * F] = spec.imag
-        if out is None:
-            out = torch.empty(B, max((int(ln.max()) - 1) * self.audio.hop_length, 1), device=spec.device, dtype=torch.float32)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        out = _out_rows(out, B, spec, lambda: max((int(ln.max()) - 1) * self.audio.hop_length, 1))
         _check(self.lib.mt2_istft(self.h, _stream(), C.byref(self.ac), _ptr(packed), _iptr(ln), T, B, _ptr(out), out.shape[1]))
         return out
 
@@ -1121,9 +1092,7 @@ class MelFrontEnd:
         B, T, _ = mel.shape
         ln = self._frame_lens(mel_lens, B, T)
         sd = seed_array(seeds, B)
-        if out is None:
-            out = torch.empty(B, max((int(ln.max()) - 1) * self.audio.hop_length, 1), device=mel.device, dtype=torch.float32)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B
+        out = _out_rows(out, B, mel, lambda: max((int(ln.max()) - 1) * self.audio.hop_length, 1))
         resid = resid_out
         if resid is None and return_resid:
             resid = torch.empty(B, max(int(n_iter), 0) + 1, T, device=mel.device, dtype=torch.float32)

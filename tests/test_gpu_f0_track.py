@@ -238,6 +238,23 @@ def test_a_nan_sample_cannot_move_a_lag_out_of_range(hop):
     assert_is_the_restatement(o, 2, 62.5, 500.0, 0.15, V.OCTAVE_COST, V.JUMP_COST)
 
 
+def test_arena_high_water_is_the_querys_figure():
+    """B = 2 with lengths (4000, 2500) at hop 256: T = 16; the first call of a fresh handle takes what mt2_f0_track_query says"""
+    from megatts2_amd import runtime as rt
+    fe = rt.MelFrontEnd()
+    try:
+        assert fe.workspace_high_water() == 0
+        wav = torch.zeros(2, 4000, device="cuda", dtype=torch.float32)
+        wav[0].copy_(dev(signal(("tone", 220.5, 1, 4000))))
+        wav[1, :2500].copy_(dev(signal(("tone", 220.5, 1, 4000))[:2500]))
+        f0 = fe.f0_track(wav, lens=[4000, 2500], hop=256)
+        torch.cuda.synchronize()
+        assert f0.shape == (2, 16)
+        assert fe.workspace_high_water() == rt.f0_track_query(4000, 2)[4]
+    finally:
+        fe.close()
+
+
 # ---- 5. refusals ---------------------------------------------------------------------------------------------------------------------
 
 def test_device_call_rejects_before_launch():

@@ -42,6 +42,11 @@ def main() -> None:
     ap.add_argument("--true-peak-ceiling", type=float, metavar="DB",
                     help="with --output-lufs: cap the gain so that the true peak (oversampled to at least 192 kHz) stays at or below this many dBTP "
                          "(e.g. -1, what EBU R 128 delivery asks); not together with --peak-ceiling")
+    ap.add_argument("--limiter", action="store_true",
+                    help="with --output-lufs and --true-peak-ceiling: reach the loudness under the ceiling by a look-ahead limiter that turns down the "
+                         "crests alone, where one gain would land under the target; --report-ebu then prints what it did")
+    ap.add_argument("--limiter-window-ms", type=float, default=5.0, metavar="MS", help="with --limiter: how far the gain looks ahead and behind (default 5)")
+    ap.add_argument("--limiter-passes", type=int, default=2, metavar="P", help="with --limiter: passes that re-measure and correct the loudness, 1 to 4 (default 2)")
     ap.add_argument("--report-ebu", action="store_true",
                     help="print true peak in dBTP, loudness range (EBU Tech 3342) and maximum short-term and momentary loudness (measured on the "
                          "GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
@@ -66,7 +71,8 @@ def main() -> None:
     phones = [int(v) for v in a.phones.split(",")] if a.phones else None
     gl = {"n_iter": a.gl_iters} if a.vocoder == "griffin-lim" else None
     mel, lens, aux = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl, loudness_lufs=a.output_lufs,
-                         peak_ceiling=a.peak_ceiling, true_peak_ceiling_dbtp=a.true_peak_ceiling)
+                         peak_ceiling=a.peak_ceiling, true_peak_ceiling_dbtp=a.true_peak_ceiling,
+                         **({"limiter": M.Limiter(a.limiter_window_ms, a.limiter_passes)} if a.limiter else {}))
     wrote = gl is not None or tts.hifi_gan is not None
     print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
     if a.report_loudness:
@@ -99,6 +105,12 @@ def main() -> None:
                   f"loudness range {float(st['lra'][0]):.2f} LU over {int(st['short_term_blocks_over_both_gates'][0])} of "
                   f"{int(st['short_term_blocks'][0])} blocks of 3 s, maximum short-term {float(st['short_term_max'][0]):.2f} LUFS, maximum "
                   f"momentary {float(st['max_momentary_lufs'][0]):.2f} LUFS")
+        if a.limiter and wrote:
+            import math
+            ls = aux["limiter_stats"][0].cpu().numpy()
+            print(f"limiter on the generated audio: {ls[23]:.2f} LUFS reached (target {a.output_lufs:.2f}), maximum gain reduction "
+                  f"{-20 * math.log10(ls[19] * ls[22]) if ls[19] * ls[22] > 0 else float('inf'):.2f} dB, {100.0 * ls[20] / max(n, 1):.2f} % of the samples "
+                  f"limited (half window {int(ls[18])} samples, pre-gain {20 * math.log10(ls[7]) if ls[7] > 0 else float('-inf'):+.2f} dB)")
     if a.report_pitch:
         import glob
         from megatts2_amd import audio_io

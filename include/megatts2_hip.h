@@ -636,6 +636,65 @@ int mt2_loudness_normalize_tp(mt2_model* m, void* stream, const float* wav /*[B,
                               int sample_rate, double target_lufs, double ceiling_dbtp, float* out /*[B, L_max]*/,
                               double* stats /*[B, 18] or NULL*/);
 
+/* ---- True-peak look-ahead limiter (csrc/limiter.hip): a gain s[i] <= 1 per sample under which G x holds a true-peak ceiling, so that
+ * normalisation under a ceiling reaches its target loudness where the one gain of rule 5 above gives way.  Offline and symmetric (it
+ * looks as far ahead as behind);  no reference counterpart.  Parity with any outside limiter and audible quality on real speech are
+ * unpinned;  the kernels are held to the rule's own properties and to the float64 restatement tests/limiter_ref.py.  THE RULE, for one
+ * utterance x f32 [L] at sample_rate;  o, Z, h[p][k] and y are those of the true-peak rule:
+ *  1 Window.  H = floor(sample_rate window_ms / 1000 + 0.5), in double;  W = 2 H + 1.  w[k] = 0.5 - 0.5 cos(2 pi (k + 1) / (2 H + 2)),
+ *    k = 0 .. 2 H, in double, divided by their sum (added ascending) and rounded once to f32.  Default 5 ms: H = 80 at 16 kHz.
+ *  2 Envelope, once per call, from x itself.  e[i] = max over p of |y[i o + p]| for i in [-1, L) - the f32 fma chains of the true-peak
+ *    rule, the max taken with v > m from 0, so a NaN never wins and an Inf does.  E[i] = max(e[i - 1], e[i]) for i in [0, L): every
+ *    oversampled position in (i - 1, i + 1).  The ringing in front of i = -1 and behind L - 1 is left to step 6.
+ *  3 Need, per pass with pre-gain G (f32).  a = G E[i], one f32 product;  need[i] = c / a (one f32 division) if a > c, else 1;
+ *    c = (f32) 10^(ceiling_dbtp / 20);  need = 1 outside [0, L).
+ *  4 Hold.  m[i] = min of need over [i - H, i + H].
+ *  5 Smooth and clamp.  d[i] = sum_k w[k] (1 - m[i - H + k]), 1 - m one f32 subtraction, one f32 fma chain from 0 with k ascending;
+ *    s[i] = min(need[i], 1 - d[i]).  Hence s <= need always, and s = 1 exactly wherever need is 1 over [i - 2 H, i + 2 H].
+ *    out[i] = (x[i] G) s[i], two f32 products;  zeros in [L, L_max).
+ *  6 Trim.  s varies inside the interpolator's window, so the true peak TP' of out, measured by the true-peak rule, can differ from c
+ *    by a little.  t = 1 where TP' <= c, else (double) c / TP' rounded toward zero to f32;  out is scaled by t in place (one f32
+ *    product, none where t = 1).
+ *  7 Normalising form, P passes (1 .. 4, default 2).  G_1 = 10^((target_lufs - I(x)) / 20) rounded to f32.  Pass k runs 3-6 on x with
+ *    G_k and measures I_k of its output by the loudness rule;  for k < P, G_(k+1) = G_k 10^((target_lufs - I_k) / 20), formed in double
+ *    on the device and rounded once to f32 (G_k is kept where I_k or the product is not finite).  The output is pass P's.  An
+ *    utterance whose I(x) is not finite, or whose G_1 does not fit f32, is copied unchanged (G = s = t = 1), as in the loudness
+ *    rule.  Everything is enqueued: no copy to the host and no wait.
+ *  8 stats f64 [24] per utterance:  0-17 mt2_loudness_ebu's row of the INPUT, bit for bit, with field 7 the final G   18 H
+ *    19 min s (1 where no sample was limited)   20 samples with s < 1   21 TP' before the trim   22 t   23 I of the final output.
+ *    19-22 are the last pass's.
+ *  9 Optional device outputs:  gain f32 [B, L_max], s of the last pass, 1 in [L, L_max);  need f32 [B, L_max] likewise.
+ * 10 The max, the min and the count are order-free and every chain's order depends on the sample's index in its utterance alone, so a
+ *    ragged batch is bit-identical to its utterances alone, whatever the slot, L_max or B.  A sample at or beyond L is never read.
+ *    A non-finite sample changes its own utterance only.
+ * Refused, on the host before the first HIP call, every output as it was:  all that mt2_loudness_normalize_tp refuses;  a non-finite
+ * window_ms or pre_gain_db, H outside [1, 1024], a pre-gain that is not a positive finite f32, passes outside [1, 4];  gain, need or stats
+ * misaligned or overlapping anything (out may be wav itself).  `m` may be a bare handle;  scratch comes from its arena. */
+#define MT2_LIMITER_FIELDS 24
+#define MT2_LIMITER_TILE 1024 /* samples of one workgroup of both limiter kernels: tile t holds i in [1024 t, 1024 (t + 1)) */
+#define MT2_LIMITER_MAX_HALF_WINDOW 1024
+#define MT2_LIMITER_MAX_PASSES 4
+/* H, the tile of the limiter kernels and the arena bytes of a call with ONE utterance of L samples, whatever the passes;  host only, no
+ * HIP call (outputs may be NULL).  A call with B utterances, the longest of L samples, takes what mt2_ebu_query states and
+ * r(4 Wp) + 2 r(4 B Lp) + r(64 B) + r(12 B) + r(144 B) + r(64 B) bytes, Wp = W rounded up to 4, Lp = L rounded up to 4: the weights;  E
+ * and the output of a pass that is not the last;  the min, count, true-peak and peak words of four passes;  G, the copy flag and t;
+ * the meter's row;  a pass's loudness row. */
+int mt2_limiter_query(int sample_rate, long long L, double window_ms, int* half_window, int* tile, long long* workspace_bytes);
+/* the weights f32 [2 H + 1] of rule 1;  host only, no HIP call */
+int mt2_limiter_window(int sample_rate, double window_ms, float* w /*[2 H + 1]*/);
+/* One pass with a host-given gain G = (f32) 10^(pre_gain_db / 20):  wav f32 [B, L_max] (device), lens host int32 [B] -> out f32
+ * [B, L_max] (device; may be wav itself), optionally gain and need f32 [B, L_max] and stats f64 [B, 24] (device; fields 0-17 are the
+ * input's meter row, 23 is measured only with stats).  The call only enqueues. */
+int mt2_limit_true_peak(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                        int sample_rate, double pre_gain_db, double ceiling_dbtp, double window_ms, float* out /*[B, L_max]*/,
+                        float* gain /*[B, L_max] or NULL*/, float* need /*[B, L_max] or NULL*/, double* stats /*[B, 24] or NULL*/);
+/* Rule 7:  each utterance brought to target_lufs under the true-peak ceiling by `passes` passes of the limiter.  No copy to the host
+ * and no wait. */
+int mt2_loudness_normalize_limited(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max,
+                                   int B, int sample_rate, double target_lufs, double ceiling_dbtp, double window_ms, int passes,
+                                   float* out /*[B, L_max]*/, float* gain /*[B, L_max] or NULL*/, float* need /*[B, L_max] or NULL*/,
+                                   double* stats /*[B, 24] or NULL*/);
+
 /* ---- the whole of Megatts.forward's no_grad block (models/megatts2.py:353-368 [+370]) for a batch,
  * activations staying in the packed internal layout between stages.
  *   forced_dur   (host, optional) int32 [B, Np_max]: replaces the ADM's integer durations AFTER the ADM

@@ -964,6 +964,58 @@ int mt2_loudness_normalize_tp(mt2_model* m, void* stream, const float* wav, cons
     MT2_API_END
 }
 
+// True-peak look-ahead limiter (limiter.hip): the half window, the tile of its kernels and the arena bytes of a call with ONE utterance
+// of L samples, without a HIP call (outputs may be NULL)
+int mt2_limiter_query(int sample_rate, long long L, double window_ms, int* half_window, int* tile, long long* workspace_bytes) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
+    MT2_REQUIRE(L >= 1 && L <= INT_MAX - 8 * 19200, "L outside [1, 2^31 - 153600)");
+    const int H = limiter_half_window(sample_rate, window_ms);
+    MT2_REQUIRE(H >= 1, "window_ms must be finite with round(sample_rate window_ms / 1000) in [1, 1024]");
+    if (half_window) *half_window = H;
+    if (tile) *tile = MT2_LIMITER_TILE;
+    if (workspace_bytes) *workspace_bytes = limiter_arena_bytes(sample_rate, L, 1, H);
+    MT2_API_END
+}
+
+// the limiter's 2 H + 1 weights, without a HIP call
+int mt2_limiter_window(int sample_rate, double window_ms, float* w) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
+    const int H = limiter_half_window(sample_rate, window_ms);
+    MT2_REQUIRE(H >= 1, "window_ms must be finite with round(sample_rate window_ms / 1000) in [1, 1024]");
+    MT2_REQUIRE(w != nullptr, "null w");
+    limiter_window(H, w);
+    MT2_API_END
+}
+
+// one pass of the limiter with a host-given gain; every refusal is decided on the host before the first HIP call
+int mt2_limit_true_peak(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sample_rate,
+                        double pre_gain_db, double ceiling_dbtp, double window_ms, float* out, float* gain, float* need, double* stats) {
+    MT2_API_BEGIN
+    int H = 0;
+    const int mx = limiter_check(wav, lens, L_max, B, sample_rate, 0.0, ceiling_dbtp, window_ms, 1, out, gain, need, stats, &H);
+    MT2_REQUIRE(std::isfinite(pre_gain_db), "pre_gain_db must be finite");
+    const float G = (float)pow(10.0, pre_gain_db / 20.0);
+    MT2_REQUIRE(std::isfinite(G) && G > 0.0f, "the pre-gain is not a positive finite f32");
+    MT2_AUDIO_CALL(m, stream);
+    limiter_run(c, wav, lens, L_max, B, mx, sample_rate, false, G, 0.0, ceiling_dbtp, H, 1, out, gain, need, stats);
+    MT2_API_END
+}
+
+// each utterance brought to target_lufs under a true-peak ceiling by `passes` passes of the limiter, every gain formed and read on the
+// device; every refusal is decided on the host before the first HIP call
+int mt2_loudness_normalize_limited(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sample_rate,
+                                   double target_lufs, double ceiling_dbtp, double window_ms, int passes, float* out, float* gain,
+                                   float* need, double* stats) {
+    MT2_API_BEGIN
+    int H = 0;
+    const int mx = limiter_check(wav, lens, L_max, B, sample_rate, target_lufs, ceiling_dbtp, window_ms, passes, out, gain, need, stats, &H);
+    MT2_AUDIO_CALL(m, stream);
+    limiter_run(c, wav, lens, L_max, B, mx, sample_rate, true, 1.0f, target_lufs, ceiling_dbtp, H, passes, out, gain, need, stats);
+    MT2_API_END
+}
+
 // the STFT the mel front-end takes its magnitude of, for a ragged batch (the front half of mt2_mel_spectrogram, shared with it)
 int mt2_stft(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* wav, const int32_t* lens, int L_max, int B, float* spec,
              int T_max) {

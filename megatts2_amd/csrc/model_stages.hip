@@ -2522,6 +2522,132 @@ static void ebu_run(const Ctx& c, const float* wav, const int* lens, int L_max, 
     st.finish();
 }
 
+// ---- true-peak look-ahead limiter (limiter.hip) behind the EBU call's kernels: every refusal is decided here, on the host, before the
+// first HIP call.  -> max_b lens[b];  *H the half window
+static int limiter_check(const float* wav, const int* lens, int L_max, int B, int sample_rate, double target_lufs, double ceiling_dbtp,
+                         double window_ms, int passes, const float* out, const float* gain, const float* need, const double* stats, int* H) {
+    MT2_REQUIRE(out != nullptr, "null out");
+    const int mx = ebu_check(wav, lens, L_max, B, sample_rate, target_lufs, ceiling_dbtp, out, nullptr, nullptr, 0, nullptr, 0);
+    *H = limiter_half_window(sample_rate, window_ms);
+    MT2_REQUIRE(*H >= 1, "window_ms must be finite with round(sample_rate window_ms / 1000) in [1, 1024]");
+    MT2_REQUIRE(passes >= 1 && passes <= MT2_LIMITER_MAX_PASSES, "passes outside [1, 4]");
+    MT2_REQUIRE((((uintptr_t)gain | (uintptr_t)need) & 3) == 0 && ((uintptr_t)stats & 7) == 0, "misaligned buffers");
+    const size_t nw = sizeof(float) * (size_t)B * L_max, ns = sizeof(double) * MT2_LIMITER_FIELDS * (size_t)B;
+    MT2_REQUIRE(!outputs_overlap({{gain, nw}, {need, nw}, {stats, ns}}, {{wav, nw}, {out, nw}}), "overlapping buffers");
+    return mx;
+}
+// What a limiter call takes from the arena behind the EBU call's carve: the weights (a plan of their own), E, the output of a pass
+// that is not the last (carved whatever the passes, so that the query needs none), the words of four passes, G | copy flag | t, the
+// meter's row and a pass's loudness row
+struct LimWs { float *env, *tmp; unsigned* words; float* ctl; double *row18, *rowk; };
+template <class Ws> static LimWs limiter_carve(Ws& ws, IntPlan& ip, size_t B, size_t E_ld) {
+    LimWs w{};
+    ip.carve(ws);
+    w.env = ws.template get<float>(B * E_ld);
+    w.tmp = ws.template get<float>(B * E_ld);
+    w.words = ws.template get<unsigned>(4 * MT2_LIMITER_MAX_PASSES * B);
+    w.ctl = ws.template get<float>(3 * B);
+    w.row18 = ws.template get<double>(MT2_EBU_FIELDS * B);
+    w.rowk = ws.template get<double>(8 * B);
+    return w;
+}
+static long long limiter_arena_bytes(int sample_rate, long long max_len, int B, int H) {
+    IntPlan ip;
+    ip.add_fill((size_t)limiter_window_words(H), 0);
+    ArenaCount count;
+    limiter_carve(count, ip, B, (size_t)((max_len + 3) & ~3ll));
+    return loudness_arena_bytes(sample_rate, max_len, B, true) + (long long)count.bytes;
+}
+// enqueues only.  normalizing: G_1 from the input's loudness, `passes` passes;  else one pass with G_host.  The meter's six kernels run
+// as in ebu_run, into the arena's row;  then the envelope, and per pass the gain kernel, the true peak of its output, the trim,
+// loudness.hip's scale kernel on t and - where another pass or the stats need it - the four loudness kernels on the output.
+static void limiter_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, bool normalizing,
+                        float G_host, double target_lufs, double ceiling_dbtp, int H, int passes, float* out, float* gain, float* need,
+                        double* stats) {
+    EbuP e{};
+    e.o = true_peak_oversample(sample_rate);
+    std::vector<int> tbits((size_t)e.o * MT2_TP_TAPS);
+    {
+        std::vector<float> table(tbits.size());
+        true_peak_table(sample_rate, table.data());
+        std::memcpy(tbits.data(), table.data(), sizeof(float) * table.size());
+    }
+    std::vector<int> wbits((size_t)limiter_window_words(H), 0);
+    {
+        std::vector<float> win((size_t)2 * H + 1);
+        limiter_window(H, win.data());
+        std::memcpy(wbits.data(), win.data(), sizeof(float) * win.size());
+    }
+    LoudnessP p{};
+    Stages st(c.m, c.s);
+    const LoudChain ch = loudness_chain(c, st, p, wav, lens, L_max, B, max_len, sample_rate, &tbits);
+    IntPlan ipw;
+    const int o_w = ipw.add(wbits);
+    const int E_ld = (max_len + 3) & ~3;
+    const LimWs w = limiter_carve(c.ws, ipw, B, E_ld);
+    ipw.send(c.m.pinned(), c.s);
+    MT2_HIP(hipMemsetAsync(w.words, 0, sizeof(unsigned) * 4 * MT2_LIMITER_MAX_PASSES * B, c.s));
+    e.wav = wav; e.L_max = L_max; e.len = p.len; e.max_len = max_len; e.B = B; e.h = p.h;
+    e.table = ch.table;
+    e.tp = ch.w.words + 2 * B;
+    e.sums = p.sums; e.NS = p.NS; e.row8 = ch.w.row8;
+    e.NST = std::max(p.NS - 29, 0);
+    e.keys = ch.w.keys;
+    e.stats = w.row18;
+    MT2_HIP(launch_true_peak(e, c.s));
+    st.mark("ebu_true_peak");
+    MT2_HIP(launch_loudness_range(e, c.s));
+    st.mark("ebu_range");
+    LimiterP q{};
+    q.wav = wav; q.L_max = L_max; q.len = p.len; q.max_len = max_len; q.B = B; q.o = e.o; q.table = ch.table;
+    q.H = H; q.win = reinterpret_cast<const float*>(ipw.dev(o_w));
+    q.c = (float)pow(10.0, ceiling_dbtp / 20.0);
+    q.env = w.env; q.E_ld = E_ld;
+    q.G = w.ctl; q.bypass = reinterpret_cast<int*>(w.ctl + B); q.t = w.ctl + 2 * B;
+    q.normalizing = normalizing ? 1 : 0; q.G_host = G_host; q.target_lufs = target_lufs; q.row18 = w.row18;
+    MT2_HIP(launch_limiter_envelope(q, c.s));
+    MT2_HIP(launch_limiter_step(q, kLimStepInit, c.s));
+    st.mark("lim_envelope");
+    static const char* const kGainMark[] = {"lim_gain1", "lim_gain2", "lim_gain3", "lim_gain4"};
+    static const char* const kTrimMark[] = {"lim_trim1", "lim_trim2", "lim_trim3", "lim_trim4"};
+    static const char* const kMeasureMark[] = {"lim_measure1", "lim_measure2", "lim_measure3", "lim_measure4"};
+    for (int k = 0; k < passes; ++k) {
+        const bool last = k == passes - 1;
+        unsigned* const words = w.words + (size_t)4 * k * B;                  // min | count | true peak | peak
+        q.out = last ? out : w.tmp; q.out_ld = last ? L_max : E_ld;
+        q.gain = last ? gain : nullptr; q.need = last ? need : nullptr;
+        q.minkey = words; q.count = words + B; q.tp = words + 2 * B;
+        MT2_HIP(launch_limiter_gain(q, c.s));
+        st.mark(kGainMark[k]);
+        EbuP ek{};
+        ek.wav = q.out; ek.L_max = q.out_ld; ek.len = p.len; ek.max_len = max_len; ek.B = B; ek.o = e.o; ek.table = ch.table;
+        ek.tp = words + 2 * B;
+        MT2_HIP(launch_true_peak(ek, c.s));
+        MT2_HIP(launch_limiter_step(q, kLimStepTrim, c.s));
+        LoudnessP pk = p;
+        pk.wav = q.out; pk.L_max = q.out_ld; pk.out = q.out; pk.gain = q.t; pk.peak = words + 3 * B;
+        pk.stats = w.rowk; pk.momentary = nullptr; pk.NB_max = 0;
+        MT2_HIP(launch_loudness_scale(pk, c.s));
+        st.mark(kTrimMark[k]);
+        q.rowk = nullptr;
+        if (!last || stats) {
+            pk.gain = nullptr; pk.out = nullptr;                              // the measuring form of the four kernels
+            MT2_HIP(launch_loudness_filter(pk, c.s));
+            MT2_HIP(launch_loudness_carry(pk, c.s));
+            MT2_HIP(launch_loudness_sums(pk, c.s));
+            MT2_HIP(launch_loudness_gate(pk, c.s));
+            q.rowk = w.rowk;
+            if (!last && normalizing) MT2_HIP(launch_limiter_step(q, kLimStepNext, c.s));
+            st.mark(kMeasureMark[k]);
+        }
+    }
+    if (stats) {
+        q.stats = stats;
+        MT2_HIP(launch_limiter_step(q, kLimStepStats, c.s));
+    }
+    st.finish();
+}
+
 // The lengths of a DTW call, checked before anything else (host only)
 static void dtw_check_geometry(int Tx_max, int Ty_max, int D, int B) {
     MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");

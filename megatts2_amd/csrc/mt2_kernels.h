@@ -629,4 +629,36 @@ struct EbuP {
 hipError_t launch_true_peak(const EbuP& p, hipStream_t s);
 hipError_t launch_loudness_range(const EbuP& p, hipStream_t s);
 
+// ---- true-peak look-ahead limiter (limiter.hip; the rule is in its header and in megatts2_hip.h) -------------------------------------
+// host only, no HIP call: H = round(sample_rate window_ms / 1000), or -1 where the rule refuses the window; the 2 H + 1 weights
+int limiter_half_window(int sample_rate, double window_ms);
+void limiter_window(int H, float* w);
+__host__ __device__ constexpr int limiter_window_words(int H) { return (2 * H + 1 + 3) & ~3; }      // the weights as the gain kernel reads them: zeros behind
+// launch_limiter_envelope once a call, behind the upload of `table`; then per pass launch_limiter_step(kLimStepTrim) behind the true
+// peak of the pass's output, launch_limiter_step(kLimStepNext) behind its loudness row; kLimStepInit in front of the first pass and
+// kLimStepStats behind the last.  The words of a pass are zeroed on the stream in front of it.
+enum { kLimStepInit = 0, kLimStepTrim = 1, kLimStepNext = 2, kLimStepStats = 3 };
+struct LimiterP {
+    const float* wav; int L_max;              // [B, L_max]; samples at or beyond len[b] are never read
+    const int* len; int max_len, B;           // device [B]; max_b len[b]
+    int o; const float* table;                // true_peak_oversample; device [o][MT2_TP_TAPS]
+    int H; const float* win;                  // device [limiter_window_words(H)]: limiter_window, zeros behind
+    float c;                                  // (f32) 10^(ceiling_dbtp / 20)
+    float* env; int E_ld;                     // scratch [B, E_ld], E_ld >= max_len, a multiple of 4: E[i]
+    float* G; int* bypass; float* t;          // device [B] each: the pass's pre-gain; 1 = copied unchanged; the trim
+    float* out; int out_ld;                   // the pass's output [B, out_ld]; may be wav (out_ld == L_max then)
+    float* gain; float* need;                 // optional [B, out_ld]: s and need of this pass, 1 behind len[b]
+    unsigned* minkey; unsigned* count;        // [B] each, zeroed: the inverted key of min s; samples with s < 1
+    const unsigned* tp;                       // [B]: the true peak of the pass's output before the trim
+    // launch_limiter_step
+    int normalizing; float G_host;            // kLimStepInit: G from row18's I and target_lufs, or G_host
+    double target_lufs;
+    const double* row18;                      // [B, MT2_EBU_FIELDS] of the input as launch_loudness_range left it
+    const double* rowk;                       // [B, 8] of the pass's output as launch_loudness_gate left it (kLimStepNext; kLimStepStats: or nullptr)
+    double* stats;                            // [B, MT2_LIMITER_FIELDS] (kLimStepStats)
+};
+hipError_t launch_limiter_envelope(const LimiterP& p, hipStream_t s);
+hipError_t launch_limiter_gain(const LimiterP& p, hipStream_t s);
+hipError_t launch_limiter_step(const LimiterP& p, int step, hipStream_t s);
+
 }  // namespace mt2

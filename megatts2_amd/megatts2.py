@@ -21,7 +21,7 @@ import numpy as np
 from . import config as cfgmod
 from . import weights
 from .config import HIFIGAN_HOP_LENGTH, HIFIGAN_SR
-from .runtime import NativeError, NativeModel
+from .runtime import Limiter, NativeError, NativeModel  # noqa: F401  (Limiter: the `limiter=` argument of synthesize / forward)
 from .sampling import PLMSampling, seed_array
 
 
@@ -151,6 +151,28 @@ def measure_loudness(samples, sample_rate: Optional[int] = None, lens=None, ebu:
         return res
     st = _frontend().loudness(x, lens, sample_rate=sample_rate).cpu().numpy()
     return {k: st[:, i].copy() for i, k in enumerate(LOUDNESS_STATS)}
+
+
+LIMITER_STATS = ("half_window", "min_gain", "samples_limited", "true_peak_before_trim", "trim", "output_lufs")
+
+
+def limit_true_peak(samples, sample_rate: Optional[int] = None, lens=None, pre_gain_db: float = 0.0, ceiling_dbtp: float = -1.0,
+                    window_ms: float = 5.0):
+    """True-peak look-ahead limiter on a 1-D waveform or a [B, L] batch, on the GPU by the rule of csrc/limiter.hip
+    (MelFrontEnd.limit; offline and symmetric; parity with any outside limiter and audible quality on real speech unpinned): the audio
+    is scaled by 10^(pre_gain_db / 20) and its crests are turned down by a smooth gain so that the true peak stays at or under
+    ceiling_dbtp; audio further than 2 window_ms from any such crest keeps the plain gain exactly.  -> (out float32 numpy [B, L]
+    ([L] for a 1-D waveform), dict of float64 numpy arrays [B]: measure_loudness(ebu=True)'s entries for the INPUT, with `gain` the
+    linear pre-gain, and half_window (samples), min_gain, samples_limited, true_peak_before_trim, trim, output_lufs)."""
+    import torch
+    x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
+    flat = x.dim() == 1
+    x = (x.unsqueeze(0) if flat else x).to("cuda", torch.float32)
+    out, st = _frontend().limit(x, lens, pre_gain_db, ceiling_dbtp, window_ms, sample_rate=sample_rate, return_stats=True)
+    st = st.cpu().numpy()
+    res = {k: st[:, i].copy() for i, k in enumerate(LOUDNESS_STATS + EBU_STATS + LIMITER_STATS)}
+    out = out.cpu().numpy()
+    return (out[0] if flat else out), res
 
 
 PHONE_PROSODY = ("start", "frames", "voiced_frames", "mean_hz", "mean_semitones", "min_hz", "max_hz", "mean_energy")
@@ -554,7 +576,7 @@ class Megatts:
     def synthesize(self, phone_tokens, mels, phone_lens=None, mel_lens=None, forced_durations=None,
                    forced_codes=None, vocoder: bool = False, return_aux: bool = False, sampling=None, seeds=None,
                    griffin_lim=None, loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0,
-                   true_peak_ceiling_dbtp: Optional[float] = None):
+                   true_peak_ceiling_dbtp: Optional[float] = None, limiter=None):
         """phone_tokens int64 [B, Np], mels f32 [B, Tp, 80] -> (mel [B, Tm, 80], mel_lens) - the
         no_grad block of Megatts.forward (models/megatts2.py:353-368) for every utterance of the batch.
         `sampling` (sampling.PLMSampling; None = greedy) / `seeds` (int64 [B] or one int s -> s + b): sampled PLM codes.
@@ -567,9 +589,14 @@ class Megatts:
         (MelFrontEnd.loudness_normalize; `peak_ceiling` > 0 caps the gain so that the sample peak stays under it; an utterance under
         0.4 s or silent keeps its level).  `true_peak_ceiling_dbtp` (None = off; needs loudness_lufs, excludes peak_ceiling > 0):
         the gain is capped so that the TRUE peak stays at or under this many dBTP (e.g. -1.0), which the sample-peak ceiling cannot
-        promise - a 16 kHz signal has crests up to 3 dB over its samples."""
+        promise - a 16 kHz signal has crests up to 3 dB over its samples.  `limiter` (None = off, exactly the call without it; a
+        runtime.Limiter; needs true_peak_ceiling_dbtp): where that cap binds, one gain lands under loudness_lufs - with the
+        limiter the crests alone are turned down (the look-ahead limiter of csrc/limiter.hip) and the audio reaches loudness_lufs
+        under the same ceiling."""
         if true_peak_ceiling_dbtp is not None and loudness_lufs is None:
             raise ValueError("true_peak_ceiling_dbtp caps the gain of the loudness normalisation: it needs loudness_lufs")
+        if limiter is not None and true_peak_ceiling_dbtp is None:
+            raise ValueError("a limiter holds a true-peak ceiling: it needs true_peak_ceiling_dbtp (and loudness_lufs)")
         if loudness_lufs is not None:
             gl_on = not (griffin_lim is None or griffin_lim is False)
             if not gl_on and not (vocoder and return_aux):
@@ -579,6 +606,11 @@ class Megatts:
             hg = self.native.hg_cfg
             n = np.asarray(out_lens, np.int64)
             n = (n - 1) * HIFIGAN_HOP_LENGTH if gl_on else (n + 2 * int(getattr(hg, "inference_padding", 0))) * hg.hop
+            if limiter is not None:          # aux["limiter_stats"]: the f64 [B, 24] of MelFrontEnd.limit, on the device
+                _, aux["limiter_stats"] = _frontend().loudness_normalize(
+                    aux["wav"], np.maximum(n, 1).astype(np.int32), float(loudness_lufs), float(peak_ceiling), sample_rate=HIFIGAN_SR,
+                    out=aux["wav"], return_stats=True, true_peak_ceiling_dbtp=true_peak_ceiling_dbtp, limiter=limiter)
+                return mel, out_lens, aux
             _frontend().loudness_normalize(aux["wav"], np.maximum(n, 1).astype(np.int32), float(loudness_lufs), float(peak_ceiling),
                                            sample_rate=HIFIGAN_SR, out=aux["wav"], true_peak_ceiling_dbtp=true_peak_ceiling_dbtp)
             return mel, out_lens, aux
@@ -839,21 +871,29 @@ class Megatts:
     # EACH to that integrated loudness (BS.1770, MelFrontEnd.loudness_normalize; peak_ceiling > 0 caps the gain by the sample peak)
     # before they are concatenated and written, with either vocoder - the two halves of the file then sound equally loud.
     # true_peak_ceiling_dbtp (None = off; needs loudness_lufs): each half's gain is capped so that its true peak stays under this many dBTP.
+    # limiter (None = off; a runtime.Limiter; needs true_peak_ceiling_dbtp): each half reaches loudness_lufs under that ceiling, its
+    # crests turned down by the look-ahead limiter, where one gain would land under it.
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
                 phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None, vocoder=None,
-                loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0, true_peak_ceiling_dbtp: Optional[float] = None):
+                loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0, true_peak_ceiling_dbtp: Optional[float] = None,
+                limiter=None):
         import torch
         if true_peak_ceiling_dbtp is not None and loudness_lufs is None:
             raise ValueError("true_peak_ceiling_dbtp caps the gain of the loudness normalisation: it needs loudness_lufs")
+        if limiter is not None and true_peak_ceiling_dbtp is None:
+            raise ValueError("a limiter holds a true-peak ceiling: it needs true_peak_ceiling_dbtp (and loudness_lufs)")
         level = {} if loudness_lufs is None else {"loudness_lufs": float(loudness_lufs), "peak_ceiling": float(peak_ceiling)}
         if true_peak_ceiling_dbtp is not None:
             level["true_peak_ceiling_dbtp"] = float(true_peak_ceiling_dbtp)
+        if limiter is not None:
+            level["limiter"] = limiter
 
         def levelled(x):          # the vocoded prompt, a 1-D device tensor
             if loudness_lufs is None:
                 return x
             return _frontend().loudness_normalize(x.unsqueeze(0), None, float(loudness_lufs), float(peak_ceiling), sample_rate=HIFIGAN_SR,
-                                                  true_peak_ceiling_dbtp=true_peak_ceiling_dbtp)[0]
+                                                  true_peak_ceiling_dbtp=true_peak_ceiling_dbtp,
+                                                  **({} if limiter is None else {"limiter": limiter}))[0]
 
         if not (vocoder is None or vocoder == "griffin_lim" or isinstance(vocoder, dict)):
             raise ValueError(f"vocoder={vocoder!r}: None (HiFi-GAN when loaded) or 'griffin_lim'")

@@ -30,10 +30,23 @@ DTW_MAX_LEN, DTW_DIR_COLS = 4096, 16  # MT2_DTW_MAX_LEN, MT2_DTW_DIR_COLS
 PROSODY_FIELDS = 8                    # MT2_PROSODY_FIELDS
 LOUDNESS_FIELDS = 8                   # MT2_LOUDNESS_FIELDS
 EBU_FIELDS, TP_ZERO_CROSSINGS, TP_TAPS, TP_TILE = 18, 12, 24, 1024      # MT2_EBU_FIELDS, MT2_TP_ZERO_CROSSINGS, MT2_TP_TAPS, MT2_TP_TILE
+LIMITER_FIELDS, LIMITER_TILE, LIMITER_MAX_HALF_WINDOW, LIMITER_MAX_PASSES = 24, 1024, 1024, 4      # MT2_LIMITER_*
 
 
 class NativeError(RuntimeError):
     pass
+
+
+class Limiter:
+    """The settings of the true-peak look-ahead limiter (csrc/limiter.hip): the half window in milliseconds (the gain looks that far
+    ahead and behind; 5 ms is 80 samples at 16 kHz) and the passes of the normalising form (1 .. 4), each of which re-measures the
+    loudness of the limited audio and corrects the gain in front of the limiter."""
+
+    def __init__(self, window_ms: float = 5.0, passes: int = 2):
+        self.window_ms, self.passes = float(window_ms), int(passes)
+
+    def __repr__(self):
+        return f"Limiter(window_ms={self.window_ms}, passes={self.passes})"
 
 
 class MT2Config(C.Structure):
@@ -117,6 +130,10 @@ def load_library():
     lib.mt2_true_peak_table.argtypes = [C.c_int, C.c_void_p]
     lib.mt2_loudness_ebu.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_loudness_normalize_tp.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    lib.mt2_limiter_query.argtypes = [C.c_int, C.c_longlong, C.c_double] + [C.c_void_p] * 3
+    lib.mt2_limiter_window.argtypes = [C.c_int, C.c_double, C.c_void_p]
+    lib.mt2_limit_true_peak.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_double] * 3 + [C.c_void_p] * 4
+    lib.mt2_loudness_normalize_limited.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_double] * 3 + [C.c_int] + [C.c_void_p] * 4
     lib.mt2_workspace_fill.argtypes = [C.c_void_p, C.c_int]
     lib.mt2_workspace_peek.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     _LIB = lib
@@ -882,7 +899,8 @@ class MelFrontEnd:
         return res if len(res) > 1 else stats
 
     def loudness_normalize(self, wav, lens=None, target_lufs: float = -23.0, peak_ceiling: float = 0.0, sample_rate: Optional[int] = None,
-                           out=None, return_stats: bool = False, true_peak_ceiling_dbtp: Optional[float] = None):
+                           out=None, return_stats: bool = False, true_peak_ceiling_dbtp: Optional[float] = None,
+                           limiter: Optional[Limiter] = None):
         """Each utterance of a ragged batch brought to target_lufs by one gain g = 10^((target - I) / 20), I its integrated loudness
         (`loudness`): wav f32 [B, L] (device) -> out f32 [B, L] with out[b, :lens[b]] = wav[b, :lens[b]] * g_b (one f32 product) and
         zeros behind.  peak_ceiling > 0: g is capped so that the sample peak stays at or below it (the sample peak, not the true
@@ -891,16 +909,28 @@ class MelFrontEnd:
         with peak_ceiling > 0, and return_stats then gives the f64 [B, 18] of `loudness_ebu`.  An utterance whose loudness is not finite - under 0.4 s, silent, holding a non-finite sample - is copied unchanged
         (g = 1).  out: a contiguous f32 [B, L] device tensor to write into; it may be wav itself.  return_stats: also the f64
         [B, 8] of `loudness` for the INPUT, with g in the last field.  The gain is formed and read on the device: the call only
-        enqueues, with no copy to the host and no wait."""
+        enqueues, with no copy to the host and no wait.
+        limiter (None = off, exactly the call without it; needs true_peak_ceiling_dbtp): a `Limiter`.  One gain under a ceiling stops
+        at the utterance's largest crest and lands under the target; with the limiter the crests alone are turned down by the
+        look-ahead gain of csrc/limiter.hip (`limit`), the gain in front of it is corrected over limiter.passes passes until the
+        limited audio reads target_lufs, and the ceiling holds as before.  return_stats then gives the f64 [B, 24] of `limit`."""
         import torch
         wav, ln, B, L = _wav_lens(wav, lens)
         sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
+        if limiter is not None and true_peak_ceiling_dbtp is None:
+            raise ValueError("a limiter holds a true-peak ceiling: state true_peak_ceiling_dbtp")
         if out is None:
             out = torch.empty_like(wav)
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == wav.shape
         if true_peak_ceiling_dbtp is not None:
             if peak_ceiling > 0:
                 raise ValueError("peak_ceiling and true_peak_ceiling_dbtp exclude each other: state the ceiling one way")
+            if limiter is not None:
+                stats = torch.empty(B, LIMITER_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
+                _check(self.lib.mt2_loudness_normalize_limited(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs),
+                                                               float(true_peak_ceiling_dbtp), float(limiter.window_ms), int(limiter.passes),
+                                                               _ptr(out), None, None, _ptr(stats)))
+                return (out, stats) if return_stats else out
             stats = torch.empty(B, EBU_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
             _check(self.lib.mt2_loudness_normalize_tp(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs),
                                                       float(true_peak_ceiling_dbtp), _ptr(out), _ptr(stats)))
@@ -909,6 +939,32 @@ class MelFrontEnd:
         _check(self.lib.mt2_loudness_normalize(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs), float(peak_ceiling),
                                                _ptr(out), _ptr(stats)))
         return (out, stats) if return_stats else out
+
+    def limit(self, wav, lens=None, pre_gain_db: float = 0.0, ceiling_dbtp: float = -1.0, window_ms: float = 5.0,
+              sample_rate: Optional[int] = None, out=None, return_stats: bool = False, return_gain: bool = False, return_need: bool = False):
+        """True-peak look-ahead limiter, one pass (the rule of csrc/limiter.hip / include/megatts2_hip.h; offline and symmetric; parity
+        with any outside limiter and audible quality on real speech are unpinned): wav f32 [B, L] (device) -> out f32 [B, L] with
+        out[b, i] = wav[b, i] * G * s[b, i] * t_b, G = 10^(pre_gain_db / 20), s <= 1 the smoothed gain that keeps every oversampled
+        value of G wav at or under 10^(ceiling_dbtp / 20) - 1 exactly further than 2 window_ms from any crest over the ceiling - and
+        t_b <= 1 a last trim that makes the re-measured true peak hold the ceiling; zeros behind lens[b].  out: a contiguous f32
+        [B, L] device tensor to write into; it may be wav itself.  The extras follow out in this order, device tensors:
+        return_stats f64 [B, 24] (0-17 `loudness_ebu`'s row of the INPUT with G in field 7, 18 the half window in samples, 19 min s,
+        20 the samples with s < 1, 21 the true peak before the trim, 22 t, 23 the integrated loudness of out), return_gain f32 [B, L]
+        (s, 1 behind lens[b]), return_need f32 [B, L] (the gain each sample needs by itself).  Samples beyond lens[b] are never read.
+        The call only enqueues."""
+        import torch
+        wav, ln, B, L = _wav_lens(wav, lens)
+        sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
+        if out is None:
+            out = torch.empty_like(wav)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == wav.shape
+        stats = torch.empty(B, LIMITER_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
+        gain = torch.empty_like(wav) if return_gain else None
+        need = torch.empty_like(wav) if return_need else None
+        _check(self.lib.mt2_limit_true_peak(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(pre_gain_db), float(ceiling_dbtp),
+                                            float(window_ms), _ptr(out), _ptr(gain), _ptr(need), _ptr(stats)))
+        res = (out,) + tuple(x for x in (stats, gain, need) if x is not None)
+        return res if len(res) > 1 else out
 
     def f0(self, wav, lens=None, fmin: float = 62.5, fmax: float = 500.0, threshold: float = 0.15, hop: Optional[int] = None,
            return_cmnd: bool = False, return_lag: bool = False, return_diff: bool = False, out=None):
@@ -1753,6 +1809,23 @@ def ebu_query(sample_rate: int, L: int):
     o, taps, tile, nst, ws = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0)
     _check(load_library().mt2_ebu_query(int(sample_rate), int(L), C.byref(o), C.byref(taps), C.byref(tile), C.byref(nst), C.byref(ws)))
     return o.value, taps.value, tile.value, nst.value, ws.value
+
+
+def limiter_query(sample_rate: int, L: int, window_ms: float = 5.0):
+    """mt2_limiter_query (no device needed) -> (half_window, tile, workspace_bytes): H = round(sample_rate * window_ms / 1000), the
+    samples one workgroup of the limiter kernels takes (tile t holds i in [tile * t, tile * (t + 1))) and the arena bytes of a
+    MelFrontEnd.limit / loudness_normalize(limiter=) call with one utterance of L samples; NativeError where the rule refuses."""
+    h, tile, ws = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    _check(load_library().mt2_limiter_query(int(sample_rate), int(L), float(window_ms), C.byref(h), C.byref(tile), C.byref(ws)))
+    return h.value, tile.value, ws.value
+
+
+def limiter_window(sample_rate: int, window_ms: float = 5.0):
+    """mt2_limiter_window (no device needed) -> the 2 H + 1 smoothing weights of the limiter rule, float32; they add up to 1."""
+    H = limiter_query(sample_rate, 1, window_ms)[0]
+    w = np.zeros(2 * H + 1, np.float32)
+    _check(load_library().mt2_limiter_window(int(sample_rate), float(window_ms), w.ctypes.data_as(C.c_void_p)))
+    return w
 
 
 def true_peak_table(sample_rate: int):

@@ -24,7 +24,7 @@ LIB = os.path.join(LIBDIR, "libmegatts2_hip.so")
 UNITS = ["gemm_f32.hip", "gemm_x3h.hip", "gemm_dispatch.hip", "gemm_skinny.hip", "attention.hip", "rowops.hip", "sampling.hip", "resample.hip", "trim.hip", "dtw.hip", "griffinlim.hip", "f0.hip", "prosody.hip", "loudness.hip", "ebu.hip", "limiter.hip", "model_load.hip",
          "model_stages.hip"]
 AUDITED = ["gemm_f32.hip", "gemm_x3h.hip"]      # units whose device assembly is audited (inline-asm LDS reads in loops)
-DEPS = ["mt2_kernels.h", "mt2_block_reduce.h", "mt2_model.h", "gemm_common.h", "gemm_tiles.h", "x3h_planes.h", "x3h_window.h", "planes_store.h", "philox.h", "capi.inc", os.path.join("..", "..", "include", "megatts2_hip.h")]
+DEPS = ["mt2_kernels.h", "mt2_block_reduce.h", "mt2_model.h", "gemm_common.h", "gemm_tiles.h", "x3h_planes.h", "x3h_window.h", "planes_store.h", "philox.h", "true_peak_tile.h", "capi.inc", os.path.join("..", "..", "include", "megatts2_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 FLAGS += os.environ.get("MT2_EXTRA_HIPCC_FLAGS", "").split()      # e.g. -DMT2_PHASE_TIMING (tools/x6_phase_timing.py)
 # per unit: the fp16 split of gemm_x3h.hip wants scalar f32 VALU (v_mul_f32 + v_fma_mix_f32), not hipcc's SLP-packed v_pk_* forms

@@ -885,8 +885,7 @@ int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0, const int32_t
 // of the high-pass) and the arena bytes of a call with ONE utterance of L samples, without a HIP call (outputs may be NULL)
 int mt2_loudness_query(int sample_rate, long long L, int* sub_block, int* blocks, double* coeffs, long long* workspace_bytes) {
     MT2_API_BEGIN
-    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
-    MT2_REQUIRE(L >= 1 && L <= INT_MAX - 8 * 19200, "L outside [1, 2^31 - 153600)");
+    loudness_check_query(sample_rate, L);
     const int h = sample_rate / 10;
     if (sub_block) *sub_block = h;
     if (blocks) *blocks = (int)std::max(L / h - 3, 0ll);
@@ -900,9 +899,9 @@ int mt2_loudness(mt2_model* m, void* stream, const float* wav, const int32_t* le
                  double* momentary, int NB_max) {
     MT2_API_BEGIN
     MT2_REQUIRE(stats != nullptr, "null stats");
-    const int mx = loudness_check(wav, lens, L_max, B, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max);
+    const WavArgs a = loudness_check({wav, lens, L_max, B, 0, sample_rate}, 0.0, 0.0, nullptr, stats, momentary, NB_max);
     MT2_AUDIO_CALL(m, stream);
-    loudness_run(c, wav, lens, L_max, B, mx, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max);
+    loudness_run(c, a, 0.0, 0.0, nullptr, stats, momentary, NB_max);
     MT2_API_END
 }
 
@@ -911,9 +910,9 @@ int mt2_loudness_normalize(mt2_model* m, void* stream, const float* wav, const i
                            double target_lufs, double peak_ceiling, float* out, double* stats) {
     MT2_API_BEGIN
     MT2_REQUIRE(out != nullptr, "null out");
-    const int mx = loudness_check(wav, lens, L_max, B, sample_rate, target_lufs, peak_ceiling, out, stats, nullptr, 0);
+    const WavArgs a = loudness_check({wav, lens, L_max, B, 0, sample_rate}, target_lufs, peak_ceiling, out, stats, nullptr, 0);
     MT2_AUDIO_CALL(m, stream);
-    loudness_run(c, wav, lens, L_max, B, mx, sample_rate, target_lufs, peak_ceiling, out, stats, nullptr, 0);
+    loudness_run(c, a, target_lufs, peak_ceiling, out, stats, nullptr, 0);
     MT2_API_END
 }
 
@@ -921,8 +920,7 @@ int mt2_loudness_normalize(mt2_model* m, void* stream, const float* wav, const i
 // the arena bytes of a call with ONE utterance of L samples, without a HIP call (outputs may be NULL)
 int mt2_ebu_query(int sample_rate, long long L, int* oversample, int* taps, int* tile, int* short_term_blocks, long long* workspace_bytes) {
     MT2_API_BEGIN
-    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
-    MT2_REQUIRE(L >= 1 && L <= INT_MAX - 8 * 19200, "L outside [1, 2^31 - 153600)");
+    loudness_check_query(sample_rate, L);
     if (oversample) *oversample = true_peak_oversample(sample_rate);
     if (taps) *taps = MT2_TP_TAPS;
     if (tile) *tile = MT2_TP_TILE;
@@ -934,7 +932,7 @@ int mt2_ebu_query(int sample_rate, long long L, int* oversample, int* taps, int*
 // the true-peak interpolation table [o][24] of a rate, without a HIP call
 int mt2_true_peak_table(int sample_rate, float* table) {
     MT2_API_BEGIN
-    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
+    loudness_check_rate(sample_rate);
     MT2_REQUIRE(table != nullptr, "null table");
     true_peak_table(sample_rate, table);
     MT2_API_END
@@ -946,9 +944,9 @@ int mt2_loudness_ebu(mt2_model* m, void* stream, const float* wav, const int32_t
                      double* momentary, int NB_max, double* short_term, int NST_max) {
     MT2_API_BEGIN
     MT2_REQUIRE(stats != nullptr, "null stats");
-    const int mx = ebu_check(wav, lens, L_max, B, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max, short_term, NST_max);
+    const WavArgs a = ebu_check({wav, lens, L_max, B, 0, sample_rate}, 0.0, 0.0, nullptr, stats, momentary, NB_max, short_term, NST_max);
     MT2_AUDIO_CALL(m, stream);
-    ebu_run(c, wav, lens, L_max, B, mx, sample_rate, 0.0, 0.0, nullptr, stats, momentary, NB_max, short_term, NST_max);
+    ebu_run(c, a, 0.0, 0.0, nullptr, stats, momentary, NB_max, short_term, NST_max);
     MT2_API_END
 }
 
@@ -958,9 +956,9 @@ int mt2_loudness_normalize_tp(mt2_model* m, void* stream, const float* wav, cons
                               double target_lufs, double ceiling_dbtp, float* out, double* stats) {
     MT2_API_BEGIN
     MT2_REQUIRE(out != nullptr, "null out");
-    const int mx = ebu_check(wav, lens, L_max, B, sample_rate, target_lufs, ceiling_dbtp, out, stats, nullptr, 0, nullptr, 0);
+    const WavArgs a = ebu_check({wav, lens, L_max, B, 0, sample_rate}, target_lufs, ceiling_dbtp, out, stats, nullptr, 0, nullptr, 0);
     MT2_AUDIO_CALL(m, stream);
-    ebu_run(c, wav, lens, L_max, B, mx, sample_rate, target_lufs, ceiling_dbtp, out, stats, nullptr, 0, nullptr, 0);
+    ebu_run(c, a, target_lufs, ceiling_dbtp, out, stats, nullptr, 0, nullptr, 0);
     MT2_API_END
 }
 
@@ -968,10 +966,8 @@ int mt2_loudness_normalize_tp(mt2_model* m, void* stream, const float* wav, cons
 // of L samples, without a HIP call (outputs may be NULL)
 int mt2_limiter_query(int sample_rate, long long L, double window_ms, int* half_window, int* tile, long long* workspace_bytes) {
     MT2_API_BEGIN
-    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
-    MT2_REQUIRE(L >= 1 && L <= INT_MAX - 8 * 19200, "L outside [1, 2^31 - 153600)");
-    const int H = limiter_half_window(sample_rate, window_ms);
-    MT2_REQUIRE(H >= 1, "window_ms must be finite with round(sample_rate window_ms / 1000) in [1, 1024]");
+    loudness_check_query(sample_rate, L);
+    const int H = limiter_check_window(sample_rate, window_ms);
     if (half_window) *half_window = H;
     if (tile) *tile = MT2_LIMITER_TILE;
     if (workspace_bytes) *workspace_bytes = limiter_arena_bytes(sample_rate, L, 1, H);
@@ -981,9 +977,8 @@ int mt2_limiter_query(int sample_rate, long long L, double window_ms, int* half_
 // the limiter's 2 H + 1 weights, without a HIP call
 int mt2_limiter_window(int sample_rate, double window_ms, float* w) {
     MT2_API_BEGIN
-    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
-    const int H = limiter_half_window(sample_rate, window_ms);
-    MT2_REQUIRE(H >= 1, "window_ms must be finite with round(sample_rate window_ms / 1000) in [1, 1024]");
+    loudness_check_rate(sample_rate);
+    const int H = limiter_check_window(sample_rate, window_ms);
     MT2_REQUIRE(w != nullptr, "null w");
     limiter_window(H, w);
     MT2_API_END
@@ -994,12 +989,12 @@ int mt2_limit_true_peak(mt2_model* m, void* stream, const float* wav, const int3
                         double pre_gain_db, double ceiling_dbtp, double window_ms, float* out, float* gain, float* need, double* stats) {
     MT2_API_BEGIN
     int H = 0;
-    const int mx = limiter_check(wav, lens, L_max, B, sample_rate, 0.0, ceiling_dbtp, window_ms, 1, out, gain, need, stats, &H);
+    const WavArgs a = limiter_check({wav, lens, L_max, B, 0, sample_rate}, 0.0, ceiling_dbtp, window_ms, 1, out, gain, need, stats, &H);
     MT2_REQUIRE(std::isfinite(pre_gain_db), "pre_gain_db must be finite");
     const float G = (float)pow(10.0, pre_gain_db / 20.0);
     MT2_REQUIRE(std::isfinite(G) && G > 0.0f, "the pre-gain is not a positive finite f32");
     MT2_AUDIO_CALL(m, stream);
-    limiter_run(c, wav, lens, L_max, B, mx, sample_rate, false, G, 0.0, ceiling_dbtp, H, 1, out, gain, need, stats);
+    limiter_run(c, a, false, G, 0.0, ceiling_dbtp, H, 1, out, gain, need, stats);
     MT2_API_END
 }
 
@@ -1010,9 +1005,9 @@ int mt2_loudness_normalize_limited(mt2_model* m, void* stream, const float* wav,
                                    float* need, double* stats) {
     MT2_API_BEGIN
     int H = 0;
-    const int mx = limiter_check(wav, lens, L_max, B, sample_rate, target_lufs, ceiling_dbtp, window_ms, passes, out, gain, need, stats, &H);
+    const WavArgs a = limiter_check({wav, lens, L_max, B, 0, sample_rate}, target_lufs, ceiling_dbtp, window_ms, passes, out, gain, need, stats, &H);
     MT2_AUDIO_CALL(m, stream);
-    limiter_run(c, wav, lens, L_max, B, mx, sample_rate, true, 1.0f, target_lufs, ceiling_dbtp, H, passes, out, gain, need, stats);
+    limiter_run(c, a, true, 1.0f, target_lufs, ceiling_dbtp, H, passes, out, gain, need, stats);
     MT2_API_END
 }
 

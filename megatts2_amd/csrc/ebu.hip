@@ -12,9 +12,8 @@
 //   LRA = g[((n - 1) 95 + 50) / 100] - g[((n - 1) 10 + 50) / 100]
 //
 // Two kernels behind the four of the loudness call, which run unchanged and leave S[j] and their eight doubles in the arena:
-//   true_peak_kernel        grid (tiles, B): kTile positions i, their samples with a halo of Z on each side and the o x 24 table in
-//                           LDS; a thread runs every phase of its four positions; wave max by shuffles, one atomicMax per wave,
-//                           skipped where it cannot raise the word
+//   true_peak_kernel        grid (tiles, B): the interpolator's tile of true_peak_tile.h, four positions a thread; wave max by
+//                           shuffles, one atomicMax per wave, skipped where it cannot raise the word
 //   loudness_range_kernel   a workgroup per utterance: z3 (kept in the arena), the counts, Gamma_r and max s in the fixed order of the
 //                           gate kernel; the s over both gates as order-preserving 64-bit keys in the arena and the two order
 //                           statistics by an exact radix select (8 bits a pass); then the 18 doubles and, for the normalising call,
@@ -24,6 +23,7 @@
 #include "../../include/megatts2_hip.h"
 #include "mt2_block_reduce.h"
 #include "mt2_kernels.h"
+#include "true_peak_tile.h"
 
 #include <limits.h>
 #include <math.h>
@@ -33,10 +33,9 @@
 namespace mt2 {
 
 namespace {
-constexpr int kZ = MT2_TP_ZERO_CROSSINGS, kTaps = MT2_TP_TAPS, kTile = MT2_TP_TILE, kMaxOver = 24;
-constexpr int kTpThreads = 256, kPer = 4, kRangeThreads = 256;
+constexpr int kTile = MT2_TP_TILE, kRangeThreads = 256;
 constexpr double kBeta = 8.0, kPi = 3.14159265358979323846;
-static_assert(kTaps == 2 * kZ && kTile == kTpThreads * kPer && kPer == 4 && kTaps % 4 == 0, "true-peak geometry");
+static_assert(kTile == kTpTile, "the true-peak kernel's tile is the shared one");
 
 // I0 by its power series: the terms fall below 2^-53 of the sum within 40 steps for x <= 8
 double bessel_i0(double x) {
@@ -66,59 +65,33 @@ void true_peak_table(int sample_rate, float* table) {
         }
 }
 
-// positions i in [tile * kTile - Z, (tile + 1) * kTile - Z) of one utterance: xs[q] = x[i0 - Z + 1 + q] (0 outside [0, L)), so that the
-// window of position i0 + q, x[i - Z + 1 .. i + Z], is xs[q .. q + 2 Z).  Thread t takes the kPer consecutive positions from
-// q = kPer t: their windows are 27 words, read as seven aligned 16-byte vectors (consecutive lanes, consecutive vectors: no bank
-// conflict), and a phase's 24 coefficients, one address for the whole wave, are read once for the four chains.  The windows use
-// kTile + 2 Z - 1 words of xs; the last word only fills the seventh vector of the last thread.
+// positions i in [tile * kTile - Z, (tile + 1) * kTile - Z) of one utterance, by the tile of true_peak_tile.h: xs[q] = x[i0 - Z + 1 + q], so
+// that the window of position i0 + q, x[i - Z + 1 .. i + Z], is xs[q .. q + 2 Z).  Thread t takes the kPer positions from q = kPer t.
+// The windows use kTile + 2 Z - 1 words of xs; the last word only fills the seventh vector of the last thread.
 __global__ __launch_bounds__(kTpThreads) void true_peak_kernel(EbuP p) {
-    __shared__ __attribute__((aligned(16))) float xs[kTile + 2 * kZ];
-    __shared__ __attribute__((aligned(16))) float hs[kMaxOver * kTaps];
+    __shared__ __attribute__((aligned(16))) float xs[kTpXsWords];
+    __shared__ __attribute__((aligned(16))) float hs[kTpHsWords];
     const int b = blockIdx.y, L = p.len[b], t = threadIdx.x, o = p.o;
     const long long i0 = (long long)blockIdx.x * kTile - kZ;
     float pk = 0.0f;
     if (i0 < L) {                                                             // uniform over the workgroup
-        const float* __restrict__ x = p.wav + (long long)b * p.L_max;
-        for (int q = t; q < kTile + 2 * kZ; q += kTpThreads) {
-            const long long s = i0 - kZ + 1 + q;
-            xs[q] = s >= 0 && s < L ? x[s] : 0.0f;
-        }
-        for (int q = t; q < o * kTaps; q += kTpThreads) hs[q] = p.table[q];
-        __syncthreads();
+        tp_tile_load(xs, hs, p.wav + (long long)b * p.L_max, i0 - kZ + 1, L, p.table, o);
         const int q0 = t * kPer;
         const long long left = (long long)L - (i0 + q0);                     // positions of this thread in front of L
         if (left > 0) {
-            float w[kTaps + kPer];
+            const TpWindows<kPer> win(xs, q0);
 #pragma unroll
-            for (int k = 0; k < kTaps + kPer; k += 4) {
-                const float4 v4 = *reinterpret_cast<const float4*>(xs + q0 + k);
-                w[k] = v4.x; w[k + 1] = v4.y; w[k + 2] = v4.z; w[k + 3] = v4.w;
-            }
-#pragma unroll
-            for (int j = 0; j < kPer; ++j) {                                  // phase 0: the sample itself (0 in front of the signal)
-                const float v = fabsf(w[j + kZ - 1]);
+            for (int j = 0; j < kPer; ++j) {                                  // phase 0
+                const float v = win.sample(j);
                 if (j < left && v > pk) pk = v;
             }
 #pragma unroll 1
             for (int ph = 1; ph < o; ++ph) {
-                float h[kTaps];
+                float a[kPer];
+                win.phase(hs, ph, a);
 #pragma unroll
-                for (int k = 0; k < kTaps; k += 4) {
-                    const float4 v4 = *reinterpret_cast<const float4*>(hs + ph * kTaps + k);
-                    h[k] = v4.x; h[k + 1] = v4.y; h[k + 2] = v4.z; h[k + 3] = v4.w;
-                }
-                float acc[kPer];
-#pragma unroll
-                for (int j = 0; j < kPer; ++j) acc[j] = 0.0f;
-#pragma unroll
-                for (int k = 0; k < kTaps; ++k)
-#pragma unroll
-                    for (int j = 0; j < kPer; ++j) acc[j] = __fmaf_rn(h[k], w[k + j], acc[j]);      // each chain in ascending k
-#pragma unroll
-                for (int j = 0; j < kPer; ++j) {
-                    const float v = fabsf(acc[j]);
-                    if (j < left && v > pk) pk = v;                           // a NaN never wins, an Inf does
-                }
+                for (int j = 0; j < kPer; ++j)
+                    if (j < left && a[j] > pk) pk = a[j];                     // a NaN never wins, an Inf does
             }
         }
     }

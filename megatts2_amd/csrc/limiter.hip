@@ -11,9 +11,8 @@
 //   TP' = true peak of out (ebu.hip);  t = min(1, c / TP') toward zero;  out *= t (loudness.hip's scale kernel)
 //
 // Kernels:
-//   limiter_envelope_kernel  grid (tiles, B): the true-peak kernel's tile - kTile samples with a halo of Z in LDS, a phase's
-//                            coefficients read once for the chains of a thread - but five chains a thread, the positions
-//                            4 t - 1 .. 4 t + 3 of the tile, so that E of its four samples needs no neighbour; writes E to the arena
+//   limiter_envelope_kernel  grid (tiles, B): the interpolator's tile of true_peak_tile.h, but five positions a thread, 4 t - 1 ..
+//                            4 t + 3 of the tile, so that E of its four samples needs no neighbour; writes E to the arena
 //   limiter_gain_kernel      grid (tiles, B), once a pass: need on kTile samples with a halo of 2 H each side in LDS; m by log-step
 //                            doubling between two LDS buffers (min over 2^k, then two overlapping windows: an element of need, hence
 //                            exact); 1 - m in LDS; the Hann chains of a thread's four samples from 16-byte LDS reads (consecutive
@@ -26,6 +25,7 @@
 #include "../../include/megatts2_hip.h"
 #include "mt2_block_reduce.h"
 #include "mt2_kernels.h"
+#include "true_peak_tile.h"
 
 #include <limits.h>
 #include <math.h>
@@ -36,10 +36,9 @@
 namespace mt2 {
 
 namespace {
-constexpr int kZ = MT2_TP_ZERO_CROSSINGS, kTaps = MT2_TP_TAPS, kTile = MT2_LIMITER_TILE, kMaxOver = 24;
-constexpr int kThreads = 256, kPer = 4, kChains = kPer + 1, kMaxH = MT2_LIMITER_MAX_HALF_WINDOW;
+constexpr int kTile = MT2_LIMITER_TILE, kThreads = kTpThreads, kChains = kPer + 1, kMaxH = MT2_LIMITER_MAX_HALF_WINDOW;
 constexpr double kPi = 3.14159265358979323846;
-static_assert(kTaps == 2 * kZ && kTile == kThreads * kPer && kPer == 4 && kTaps % 4 == 0, "limiter geometry");
+static_assert(kTile == kTpTile && kTile == kThreads * kPer, "both limiter kernels work on the shared tile");
 
 // the words of one of the gain kernel's two LDS buffers: need over the tile and its halo, and room for the zeros behind 1 - m
 __host__ __device__ constexpr int gain_buffer_words(int H) { return (kTile + 4 * H + 8 + 3) & ~3; }
@@ -77,56 +76,32 @@ void limiter_window(int H, float* w) {
     for (int k = 0; k < W; ++k) w[k] = (float)(v[k] / sum);
 }
 
-// samples i in [tile * kTile, (tile + 1) * kTile) of one utterance: xs[q] = x[i0 - Z + q] (0 outside [0, L)), so that the window of
-// position i0 - 1 + q, x[i - Z + 1 .. i + Z], is xs[q .. q + 2 Z).  Thread t takes the five positions from q = 4 t: 28 words, seven
-// aligned 16-byte vectors.  e of a position at or beyond L is formed and dropped.
+// samples i in [tile * kTile, (tile + 1) * kTile) of one utterance, by the tile of true_peak_tile.h: xs[q] = x[i0 - Z + q], so that the
+// window of position i0 - 1 + q, x[i - Z + 1 .. i + Z], is xs[q .. q + 2 Z).  Thread t takes the five positions from q = 4 t, so that
+// E of its four samples needs no neighbour.  e of a position at or beyond L is formed and dropped.
 __global__ __launch_bounds__(kThreads) void limiter_envelope_kernel(LimiterP p) {
-    __shared__ __attribute__((aligned(16))) float xs[kTile + 2 * kZ];
-    __shared__ __attribute__((aligned(16))) float hs[kMaxOver * kTaps];
+    __shared__ __attribute__((aligned(16))) float xs[kTpXsWords];
+    __shared__ __attribute__((aligned(16))) float hs[kTpHsWords];
     const int b = blockIdx.y, L = p.len[b], t = threadIdx.x, o = p.o;
     const long long i0 = (long long)blockIdx.x * kTile;
     if (i0 >= L) return;                                                      // uniform over the workgroup
-    const float* __restrict__ x = p.wav + (long long)b * p.L_max;
-    for (int q = t; q < kTile + 2 * kZ; q += kThreads) {
-        const long long s = i0 - kZ + q;
-        xs[q] = s >= 0 && s < L ? x[s] : 0.0f;
-    }
-    for (int q = t; q < o * kTaps; q += kThreads) hs[q] = p.table[q];
-    __syncthreads();
+    tp_tile_load(xs, hs, p.wav + (long long)b * p.L_max, i0 - kZ, L, p.table, o);
     const int q0 = t * kPer;
     if (i0 + q0 >= L) return;
-    float w[kTaps + kPer];
-#pragma unroll
-    for (int k = 0; k < kTaps + kPer; k += 4) {
-        const float4 v4 = *reinterpret_cast<const float4*>(xs + q0 + k);
-        w[k] = v4.x; w[k + 1] = v4.y; w[k + 2] = v4.z; w[k + 3] = v4.w;
-    }
+    const TpWindows<kChains> win(xs, q0);
     float e[kChains];
 #pragma unroll
-    for (int j = 0; j < kChains; ++j) {                                       // phase 0: the sample itself (0 in front of the signal)
-        const float v = fabsf(w[j + kZ - 1]);
+    for (int j = 0; j < kChains; ++j) {                                       // phase 0
+        const float v = win.sample(j);
         e[j] = v > 0.0f ? v : 0.0f;
     }
 #pragma unroll 1
     for (int ph = 1; ph < o; ++ph) {
-        float h[kTaps];
+        float a[kChains];
+        win.phase(hs, ph, a);
 #pragma unroll
-        for (int k = 0; k < kTaps; k += 4) {
-            const float4 v4 = *reinterpret_cast<const float4*>(hs + ph * kTaps + k);
-            h[k] = v4.x; h[k + 1] = v4.y; h[k + 2] = v4.z; h[k + 3] = v4.w;
-        }
-        float acc[kChains];
-#pragma unroll
-        for (int j = 0; j < kChains; ++j) acc[j] = 0.0f;
-#pragma unroll
-        for (int k = 0; k < kTaps; ++k)
-#pragma unroll
-            for (int j = 0; j < kChains; ++j) acc[j] = __fmaf_rn(h[k], w[k + j], acc[j]);       // each chain in ascending k
-#pragma unroll
-        for (int j = 0; j < kChains; ++j) {
-            const float v = fabsf(acc[j]);
-            if (v > e[j]) e[j] = v;                                           // a NaN never wins, an Inf does
-        }
+        for (int j = 0; j < kChains; ++j)
+            if (a[j] > e[j]) e[j] = a[j];                                     // a NaN never wins, an Inf does
     }
     float E[kPer];
 #pragma unroll

@@ -2280,10 +2280,8 @@ static long long f0_track_arena_bytes(int B, long long T_max) {
 static void f0_track_run(const Ctx& c, const F0Args& a, float octave_cost, float jump_cost) {
     float lg[256];
     f0_track_table(a.lag_min, a.lag_max, lg);
-    std::vector<int> bits(256);
-    std::memcpy(bits.data(), lg, sizeof(lg));
     IntPlan ip;
-    const int o_len = ip.add(a.lens, a.B), o_lg = ip.add(bits);
+    const int o_len = ip.add(a.lens, a.B), o_lg = ip.add_bits(lg, 256);
     const F0TrackWs w = f0_track_carve(c.ws, ip, a.B, a.T_max);
     ip.send(c.m.pinned(), c.s);
     F0TrackP q{};
@@ -2379,22 +2377,31 @@ static void pitch_contour_run(const Ctx& c, const float* f0, const int* frame_le
 }
 
 // ---- integrated loudness and loudness normalisation (loudness.hip): every refusal is decided here, on the host, before the first HIP call
-// -> max_b lens[b].  out == nullptr: the measuring call
-static int loudness_check(const float* wav, const int* lens, int L_max, int B, int sample_rate, double target_lufs, double peak_ceiling,
-                          const float* out, const double* stats, const double* momentary, int NB_max) {
-    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
-    MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]");
+// the rule on the rate, for every function of the family, and with it the rule on the longest waveform, for its queries
+constexpr int kLoudMaxLen = INT_MAX - 8 * 19200;
+static void loudness_check_rate(int sample_rate) { MT2_REQUIRE(loudness_rate_ok(sample_rate), "sample_rate must be a multiple of 10 in [8000, 192000]"); }
+static void loudness_check_query(int sample_rate, long long L) {
+    loudness_check_rate(sample_rate);
+    MT2_REQUIRE(L >= 1 && L <= kLoudMaxLen, "L outside [1, 2^31 - 153600)");
+}
+// the waveform batch of a loudness, EBU or limiter call; its check hands it back with max_len = max_b lens[b] filled in
+struct WavArgs { const float* wav; const int* lens; int L_max, B, max_len, sample_rate; };
+// out == nullptr: the measuring call
+static WavArgs loudness_check(WavArgs a, double target_lufs, double peak_ceiling, const float* out, const double* stats, const double* momentary,
+                              int NB_max) {
+    MT2_REQUIRE(a.B >= 1 && a.B <= 65535, "B outside [1, 65535]");
+    loudness_check_rate(a.sample_rate);
     MT2_REQUIRE(std::isfinite(target_lufs) && std::isfinite(peak_ceiling), "target_lufs / peak_ceiling must be finite");
-    MT2_REQUIRE(wav != nullptr && lens != nullptr && L_max >= 1, "bad buffers");
-    MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)out) & 3) == 0 && (((uintptr_t)stats | (uintptr_t)momentary) & 7) == 0, "misaligned buffers");
-    const int mx = check_lens(lens, B, L_max, "waveform length outside [1, L_max]");
-    MT2_REQUIRE(mx <= INT_MAX - 8 * 19200, "waveform too long");
-    const int nb = std::max(mx / (sample_rate / 10) - 3, 0);
+    MT2_REQUIRE(a.wav != nullptr && a.lens != nullptr && a.L_max >= 1, "bad buffers");
+    MT2_REQUIRE((((uintptr_t)a.wav | (uintptr_t)out) & 3) == 0 && (((uintptr_t)stats | (uintptr_t)momentary) & 7) == 0, "misaligned buffers");
+    a.max_len = check_lens(a.lens, a.B, a.L_max, "waveform length outside [1, L_max]");
+    MT2_REQUIRE(a.max_len <= kLoudMaxLen, "waveform too long");
+    const int nb = std::max(a.max_len / (a.sample_rate / 10) - 3, 0);
     MT2_REQUIRE(momentary == nullptr || (NB_max >= 1 && NB_max >= nb), "NB_max smaller than the blocks of the longest utterance (or < 1)");
-    const size_t nw = sizeof(float) * (size_t)B * L_max, nst = sizeof(double) * 8 * (size_t)B, nm = sizeof(double) * (size_t)B * std::max(NB_max, 0);
-    MT2_REQUIRE(out == wav || !spans_overlap({out, nw}, {wav, nw}), "out overlaps wav without being wav");
-    MT2_REQUIRE(!outputs_overlap({{stats, nst}, {momentary, nm}}, {{wav, nw}, {out, nw}}), "overlapping buffers");
-    return mx;
+    const size_t nw = sizeof(float) * (size_t)a.B * a.L_max, nst = sizeof(double) * 8 * (size_t)a.B, nm = sizeof(double) * (size_t)a.B * std::max(NB_max, 0);
+    MT2_REQUIRE(out == a.wav || !spans_overlap({out, nw}, {a.wav, nw}), "out overlaps wav without being wav");
+    MT2_REQUIRE(!outputs_overlap({{stats, nst}, {momentary, nm}}, {{a.wav, nw}, {out, nw}}), "overlapping buffers");
+    return a;
 }
 // The arena of one loudness / EBU call, in carve order: the plan (the lengths, the carry matrix and, for EBU, the filter table), the
 // chunk states, S, the words (peak | gain, and EBU's true peak) and, for EBU alone, the loudness rows and z3 / the keys
@@ -2421,50 +2428,51 @@ static long long loudness_arena_bytes(int sample_rate, long long max_len, int B,
     loudness_carve(count, ip, B, (int)(max_len / (sample_rate / 10)), ebu);
     return (long long)count.bytes;
 }
+// the four kernels of the loudness rule on p;  st: where their marks go, or nullptr (a pass of the limiter measures under one mark)
+static void loudness_launches(const Ctx& c, const LoudnessP& p, Stages* st) {
+    MT2_HIP(launch_loudness_filter(p, c.s));
+    if (st) st->mark("loud_zero_state");
+    MT2_HIP(launch_loudness_carry(p, c.s));
+    if (st) st->mark("loud_carry");
+    MT2_HIP(launch_loudness_sums(p, c.s));
+    if (st) st->mark("loud_sums");
+    MT2_HIP(launch_loudness_gate(p, c.s));
+    if (st) st->mark("loud_gate");
+}
 // What the loudness and the EBU call share, up to and including the gate kernel and its mark.  The caller has set the gate's own
-// fields of p (targets, out, stats, momentary); the rest of p is filled here.  `tbits`: nullptr, or what the EBU call adds - its
-// filter table as the plan's third entry, the third word row, the loudness rows and the keys.  Its gate kernel only measures, into
-// the rows (ebu.hip forms the gain); the loudness call's forms the gain where there is an `out` to scale.
+// fields of p (targets, out, stats, momentary); the rest of p is filled here.  `table`: nullptr, or what the EBU call adds - its
+// filter table [o][24] as the plan's third entry, the third word row, the loudness rows and the keys.  Its gate kernel only measures,
+// into the rows (ebu.hip forms the gain); the loudness call's forms the gain where there is an `out` to scale.
 // -> the arena, and the table on the device
 struct LoudChain { LoudWs w; const float* table; };
-static LoudChain loudness_chain(const Ctx& c, Stages& st, LoudnessP& p, const float* wav, const int* lens, int L_max, int B, int max_len,
-                                int sample_rate, const std::vector<int>* tbits) {
-    p.h = sample_rate / 10;
-    loudness_coeffs(sample_rate, p.c);
-    if (c.m.loud_rate != sample_rate) {          // a function of the rate alone: kept by the handle
+static LoudChain loudness_chain(const Ctx& c, Stages& st, LoudnessP& p, const WavArgs& a, const std::vector<float>* table) {
+    p.h = a.sample_rate / 10;
+    loudness_coeffs(a.sample_rate, p.c);
+    if (c.m.loud_rate != a.sample_rate) {          // a function of the rate alone: kept by the handle
         loudness_carry_matrix(p.c, p.h, c.m.loud_M);
-        c.m.loud_rate = sample_rate;
+        c.m.loud_rate = a.sample_rate;
     }
-    std::vector<int> mbits(32);
-    std::memcpy(mbits.data(), c.m.loud_M, sizeof(c.m.loud_M));
     IntPlan ip;
-    const int o_len = ip.add(lens, B), o_m = ip.add(mbits), o_t = tbits ? ip.add(*tbits) : 0;
-    p.NS = max_len / p.h;
-    const LoudWs w = loudness_carve(c.ws, ip, B, p.NS, tbits != nullptr);
+    const int o_len = ip.add(a.lens, a.B), o_m = ip.add_bits(c.m.loud_M, 16), o_t = table ? ip.add_bits(table->data(), table->size()) : 0;
+    p.NS = a.max_len / p.h;
+    const LoudWs w = loudness_carve(c.ws, ip, a.B, p.NS, table != nullptr);
     ip.send(c.m.pinned(), c.s);
-    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.max_len = max_len; p.B = B; p.M = ip.dev(o_m);
+    p.wav = a.wav; p.L_max = a.L_max; p.len = ip.dev(o_len); p.max_len = a.max_len; p.B = a.B; p.M = ip.dev(o_m);
     p.state = w.state; p.sums = w.sums; p.peak = w.words;
-    if (tbits) p.stats = w.row8;
-    else if (p.out) p.gain = reinterpret_cast<float*>(w.words + B);
-    MT2_HIP(hipMemsetAsync(w.words, 0, sizeof(unsigned) * (tbits ? 3 : 1) * B, c.s));
+    if (table) p.stats = w.row8;
+    else if (p.out) p.gain = reinterpret_cast<float*>(w.words + a.B);
+    MT2_HIP(hipMemsetAsync(w.words, 0, sizeof(unsigned) * (table ? 3 : 1) * a.B, c.s));
     st.mark("start");
-    MT2_HIP(launch_loudness_filter(p, c.s));
-    st.mark("loud_zero_state");
-    MT2_HIP(launch_loudness_carry(p, c.s));
-    st.mark("loud_carry");
-    MT2_HIP(launch_loudness_sums(p, c.s));
-    st.mark("loud_sums");
-    MT2_HIP(launch_loudness_gate(p, c.s));
-    st.mark("loud_gate");
-    return {w, tbits ? reinterpret_cast<const float*>(ip.dev(o_t)) : nullptr};
+    loudness_launches(c, p, &st);
+    return {w, table ? reinterpret_cast<const float*>(ip.dev(o_t)) : nullptr};
 }
 // enqueues only: the lengths and the carry matrix travel in the call's one IntPlan upload; the gain is formed and read on the device
-static void loudness_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, double target_lufs,
-                         double peak_ceiling, float* out, double* stats, double* momentary, int NB_max) {
+static void loudness_run(const Ctx& c, const WavArgs& a, double target_lufs, double peak_ceiling, float* out, double* stats, double* momentary,
+                         int NB_max) {
     LoudnessP p{};
     p.target_lufs = target_lufs; p.peak_ceiling = peak_ceiling; p.out = out; p.stats = stats; p.momentary = momentary; p.NB_max = NB_max;
     Stages st(c.m, c.s);
-    (void)loudness_chain(c, st, p, wav, lens, L_max, B, max_len, sample_rate, nullptr);
+    (void)loudness_chain(c, st, p, a, nullptr);
     if (out) {
         MT2_HIP(launch_loudness_scale(p, c.s));
         st.mark("loud_scale");
@@ -2473,47 +2481,46 @@ static void loudness_run(const Ctx& c, const float* wav, const int* lens, int L_
 }
 
 // ---- EBU-mode metering (ebu.hip) behind the loudness kernels: every refusal is decided here, on the host, before the first HIP call
-// -> max_b lens[b].  out == nullptr: the measuring call
-static int ebu_check(const float* wav, const int* lens, int L_max, int B, int sample_rate, double target_lufs, double ceiling_dbtp,
-                     const float* out, const double* stats, const double* momentary, int NB_max, const double* short_term, int NST_max) {
-    const int mx = loudness_check(wav, lens, L_max, B, sample_rate, target_lufs, ceiling_dbtp, out, nullptr, momentary, NB_max);
+// out == nullptr: the measuring call
+static WavArgs ebu_check(WavArgs a, double target_lufs, double ceiling_dbtp, const float* out, const double* stats, const double* momentary,
+                         int NB_max, const double* short_term, int NST_max) {
+    a = loudness_check(a, target_lufs, ceiling_dbtp, out, nullptr, momentary, NB_max);
     MT2_REQUIRE((((uintptr_t)stats | (uintptr_t)short_term) & 7) == 0, "misaligned buffers");
-    const int nst = std::max(mx / (sample_rate / 10) - 29, 0);
+    const int nst = std::max(a.max_len / (a.sample_rate / 10) - 29, 0);
     MT2_REQUIRE(short_term == nullptr || (NST_max >= 1 && NST_max >= nst), "NST_max smaller than the short-term blocks of the longest utterance (or < 1)");
-    const size_t nw = sizeof(float) * (size_t)B * L_max, ns = sizeof(double) * MT2_EBU_FIELDS * (size_t)B,
-                 nm = sizeof(double) * (size_t)B * std::max(NB_max, 0), nt = sizeof(double) * (size_t)B * std::max(NST_max, 0);
-    MT2_REQUIRE(!outputs_overlap({{stats, ns}, {short_term, nt}}, {{wav, nw}, {out, nw}, {momentary, nm}}), "overlapping buffers");
-    return mx;
+    const size_t nw = sizeof(float) * (size_t)a.B * a.L_max, ns = sizeof(double) * MT2_EBU_FIELDS * (size_t)a.B,
+                 nm = sizeof(double) * (size_t)a.B * std::max(NB_max, 0), nt = sizeof(double) * (size_t)a.B * std::max(NST_max, 0);
+    MT2_REQUIRE(!outputs_overlap({{stats, ns}, {short_term, nt}}, {{a.wav, nw}, {out, nw}, {momentary, nm}}), "overlapping buffers");
+    return a;
 }
-// enqueues only: the lengths, the carry matrix and the filter table travel in the call's one IntPlan upload; the loudness kernels run
-// as in loudness_run and leave their row in the arena; the gain is formed and read on the device
-static void ebu_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, double target_lufs,
-                    double ceiling_dbtp, float* out, double* stats, double* momentary, int NB_max, double* short_term, int NST_max) {
-    EbuP e{};
-    e.o = true_peak_oversample(sample_rate);
-    std::vector<int> tbits((size_t)e.o * MT2_TP_TAPS);
-    {
-        std::vector<float> table(tbits.size());
-        true_peak_table(sample_rate, table.data());
-        std::memcpy(tbits.data(), table.data(), sizeof(float) * table.size());
-    }
-    LoudnessP p{};
-    p.momentary = momentary; p.NB_max = NB_max;
-    Stages st(c.m, c.s);
-    const LoudChain ch = loudness_chain(c, st, p, wav, lens, L_max, B, max_len, sample_rate, &tbits);
-    unsigned* const words = ch.w.words;                           // peak | gain | true peak
-    e.wav = wav; e.L_max = L_max; e.len = p.len; e.max_len = max_len; e.B = B; e.h = p.h;
-    e.table = ch.table;
-    e.tp = words + 2 * B;
-    e.sums = p.sums; e.NS = p.NS; e.row8 = ch.w.row8;
-    e.NST = std::max(p.NS - 29, 0);
-    e.keys = ch.w.keys;
-    e.gain = out ? reinterpret_cast<float*>(words + B) : nullptr;
-    e.target_lufs = target_lufs; e.ceiling_dbtp = ceiling_dbtp; e.stats = stats; e.short_term = short_term; e.NST_max = NST_max;
+// The EBU meter of ebu_run and limiter_run: the filter table, loudness_chain (one IntPlan upload; the loudness kernels leave their row
+// in the arena), then the true-peak and the range kernel.  The caller has set its own fields: of p as for loudness_chain, of e the
+// targets and the short-term output.  gain: whether the range kernel forms the gain word.  row18(): where the 18 doubles go - asked
+// behind loudness_chain, so that a caller can carve what it adds to the arena behind the meter's part.
+template <class Row> static void ebu_meter(const Ctx& c, Stages& st, const WavArgs& a, LoudnessP& p, EbuP& e, bool gain, Row&& row18) {
+    e.o = true_peak_oversample(a.sample_rate);
+    std::vector<float> table((size_t)e.o * MT2_TP_TAPS);
+    true_peak_table(a.sample_rate, table.data());
+    const LoudChain ch = loudness_chain(c, st, p, a, &table);
+    e.wav = a.wav; e.L_max = a.L_max; e.len = p.len; e.max_len = a.max_len; e.B = a.B; e.h = p.h;
+    e.table = ch.table; e.sums = p.sums; e.NS = p.NS; e.row8 = ch.w.row8; e.NST = std::max(p.NS - 29, 0); e.keys = ch.w.keys;
+    e.tp = ch.w.words + 2 * a.B;                                  // peak | gain | true peak
+    e.gain = gain ? reinterpret_cast<float*>(ch.w.words + a.B) : nullptr;
+    e.stats = row18();
     MT2_HIP(launch_true_peak(e, c.s));
     st.mark("ebu_true_peak");
     MT2_HIP(launch_loudness_range(e, c.s));
     st.mark("ebu_range");
+}
+// enqueues only; the gain is formed and read on the device
+static void ebu_run(const Ctx& c, const WavArgs& a, double target_lufs, double ceiling_dbtp, float* out, double* stats, double* momentary,
+                    int NB_max, double* short_term, int NST_max) {
+    LoudnessP p{};
+    p.momentary = momentary; p.NB_max = NB_max;
+    EbuP e{};
+    e.target_lufs = target_lufs; e.ceiling_dbtp = ceiling_dbtp; e.short_term = short_term; e.NST_max = NST_max;
+    Stages st(c.m, c.s);
+    ebu_meter(c, st, a, p, e, out != nullptr, [&] { return stats; });
     if (out) {
         p.gain = e.gain; p.out = out;
         MT2_HIP(launch_loudness_scale(p, c.s));
@@ -2523,18 +2530,22 @@ static void ebu_run(const Ctx& c, const float* wav, const int* lens, int L_max, 
 }
 
 // ---- true-peak look-ahead limiter (limiter.hip) behind the EBU call's kernels: every refusal is decided here, on the host, before the
-// first HIP call.  -> max_b lens[b];  *H the half window
-static int limiter_check(const float* wav, const int* lens, int L_max, int B, int sample_rate, double target_lufs, double ceiling_dbtp,
-                         double window_ms, int passes, const float* out, const float* gain, const float* need, const double* stats, int* H) {
+// first HIP call.  -> H, the half window
+static int limiter_check_window(int sample_rate, double window_ms) {
+    const int H = limiter_half_window(sample_rate, window_ms);
+    MT2_REQUIRE(H >= 1, "window_ms must be finite with round(sample_rate window_ms / 1000) in [1, 1024]");
+    return H;
+}
+static WavArgs limiter_check(WavArgs a, double target_lufs, double ceiling_dbtp, double window_ms, int passes, const float* out,
+                             const float* gain, const float* need, const double* stats, int* H) {
     MT2_REQUIRE(out != nullptr, "null out");
-    const int mx = ebu_check(wav, lens, L_max, B, sample_rate, target_lufs, ceiling_dbtp, out, nullptr, nullptr, 0, nullptr, 0);
-    *H = limiter_half_window(sample_rate, window_ms);
-    MT2_REQUIRE(*H >= 1, "window_ms must be finite with round(sample_rate window_ms / 1000) in [1, 1024]");
+    a = ebu_check(a, target_lufs, ceiling_dbtp, out, nullptr, nullptr, 0, nullptr, 0);
+    *H = limiter_check_window(a.sample_rate, window_ms);
     MT2_REQUIRE(passes >= 1 && passes <= MT2_LIMITER_MAX_PASSES, "passes outside [1, 4]");
     MT2_REQUIRE((((uintptr_t)gain | (uintptr_t)need) & 3) == 0 && ((uintptr_t)stats & 7) == 0, "misaligned buffers");
-    const size_t nw = sizeof(float) * (size_t)B * L_max, ns = sizeof(double) * MT2_LIMITER_FIELDS * (size_t)B;
-    MT2_REQUIRE(!outputs_overlap({{gain, nw}, {need, nw}, {stats, ns}}, {{wav, nw}, {out, nw}}), "overlapping buffers");
-    return mx;
+    const size_t nw = sizeof(float) * (size_t)a.B * a.L_max, ns = sizeof(double) * MT2_LIMITER_FIELDS * (size_t)a.B;
+    MT2_REQUIRE(!outputs_overlap({{gain, nw}, {need, nw}, {stats, ns}}, {{a.wav, nw}, {out, nw}}), "overlapping buffers");
+    return a;
 }
 // What a limiter call takes from the arena behind the EBU call's carve: the weights (a plan of their own), E, the output of a pass
 // that is not the last (carved whatever the passes, so that the query needs none), the words of four passes, G | copy flag | t, the
@@ -2558,48 +2569,28 @@ static long long limiter_arena_bytes(int sample_rate, long long max_len, int B, 
     limiter_carve(count, ip, B, (size_t)((max_len + 3) & ~3ll));
     return loudness_arena_bytes(sample_rate, max_len, B, true) + (long long)count.bytes;
 }
-// enqueues only.  normalizing: G_1 from the input's loudness, `passes` passes;  else one pass with G_host.  The meter's six kernels run
-// as in ebu_run, into the arena's row;  then the envelope, and per pass the gain kernel, the true peak of its output, the trim,
-// loudness.hip's scale kernel on t and - where another pass or the stats need it - the four loudness kernels on the output.
-static void limiter_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, bool normalizing,
-                        float G_host, double target_lufs, double ceiling_dbtp, int H, int passes, float* out, float* gain, float* need,
-                        double* stats) {
-    EbuP e{};
-    e.o = true_peak_oversample(sample_rate);
-    std::vector<int> tbits((size_t)e.o * MT2_TP_TAPS);
-    {
-        std::vector<float> table(tbits.size());
-        true_peak_table(sample_rate, table.data());
-        std::memcpy(tbits.data(), table.data(), sizeof(float) * table.size());
-    }
-    std::vector<int> wbits((size_t)limiter_window_words(H), 0);
-    {
-        std::vector<float> win((size_t)2 * H + 1);
-        limiter_window(H, win.data());
-        std::memcpy(wbits.data(), win.data(), sizeof(float) * win.size());
-    }
-    LoudnessP p{};
-    Stages st(c.m, c.s);
-    const LoudChain ch = loudness_chain(c, st, p, wav, lens, L_max, B, max_len, sample_rate, &tbits);
+// enqueues only.  normalizing: G_1 from the input's loudness, `passes` passes;  else one pass with G_host.  The meter runs as in ebu_run,
+// into the arena's row;  then the envelope, and per pass the gain kernel, the true peak of its output, the trim, loudness.hip's scale
+// kernel on t and - where another pass or the stats need it - the four loudness kernels on the output.
+static void limiter_run(const Ctx& c, const WavArgs& a, bool normalizing, float G_host, double target_lufs, double ceiling_dbtp, int H,
+                        int passes, float* out, float* gain, float* need, double* stats) {
+    const int B = a.B, max_len = a.max_len, E_ld = (max_len + 3) & ~3;
+    std::vector<float> win((size_t)2 * H + 1);
+    limiter_window(H, win.data());
     IntPlan ipw;
-    const int o_w = ipw.add(wbits);
-    const int E_ld = (max_len + 3) & ~3;
-    const LimWs w = limiter_carve(c.ws, ipw, B, E_ld);
-    ipw.send(c.m.pinned(), c.s);
-    MT2_HIP(hipMemsetAsync(w.words, 0, sizeof(unsigned) * 4 * MT2_LIMITER_MAX_PASSES * B, c.s));
-    e.wav = wav; e.L_max = L_max; e.len = p.len; e.max_len = max_len; e.B = B; e.h = p.h;
-    e.table = ch.table;
-    e.tp = ch.w.words + 2 * B;
-    e.sums = p.sums; e.NS = p.NS; e.row8 = ch.w.row8;
-    e.NST = std::max(p.NS - 29, 0);
-    e.keys = ch.w.keys;
-    e.stats = w.row18;
-    MT2_HIP(launch_true_peak(e, c.s));
-    st.mark("ebu_true_peak");
-    MT2_HIP(launch_loudness_range(e, c.s));
-    st.mark("ebu_range");
+    const int o_w = ipw.add_bits(win.data(), win.size(), (size_t)limiter_window_words(H));
+    LimWs w{};
+    LoudnessP p{};                                                            // the meter's, kept for the passes
+    EbuP e{};
+    Stages st(c.m, c.s);
+    ebu_meter(c, st, a, p, e, false, [&] {                                    // the limiter's part of the arena, behind the meter's
+        w = limiter_carve(c.ws, ipw, B, E_ld);
+        ipw.send(c.m.pinned(), c.s);
+        MT2_HIP(hipMemsetAsync(w.words, 0, sizeof(unsigned) * 4 * MT2_LIMITER_MAX_PASSES * B, c.s));
+        return w.row18;
+    });
     LimiterP q{};
-    q.wav = wav; q.L_max = L_max; q.len = p.len; q.max_len = max_len; q.B = B; q.o = e.o; q.table = ch.table;
+    q.wav = a.wav; q.L_max = a.L_max; q.len = p.len; q.max_len = max_len; q.B = B; q.o = e.o; q.table = e.table;
     q.H = H; q.win = reinterpret_cast<const float*>(ipw.dev(o_w));
     q.c = (float)pow(10.0, ceiling_dbtp / 20.0);
     q.env = w.env; q.E_ld = E_ld;
@@ -2614,13 +2605,13 @@ static void limiter_run(const Ctx& c, const float* wav, const int* lens, int L_m
     for (int k = 0; k < passes; ++k) {
         const bool last = k == passes - 1;
         unsigned* const words = w.words + (size_t)4 * k * B;                  // min | count | true peak | peak
-        q.out = last ? out : w.tmp; q.out_ld = last ? L_max : E_ld;
+        q.out = last ? out : w.tmp; q.out_ld = last ? a.L_max : E_ld;
         q.gain = last ? gain : nullptr; q.need = last ? need : nullptr;
         q.minkey = words; q.count = words + B; q.tp = words + 2 * B;
         MT2_HIP(launch_limiter_gain(q, c.s));
         st.mark(kGainMark[k]);
         EbuP ek{};
-        ek.wav = q.out; ek.L_max = q.out_ld; ek.len = p.len; ek.max_len = max_len; ek.B = B; ek.o = e.o; ek.table = ch.table;
+        ek.wav = q.out; ek.L_max = q.out_ld; ek.len = p.len; ek.max_len = max_len; ek.B = B; ek.o = e.o; ek.table = e.table;
         ek.tp = words + 2 * B;
         MT2_HIP(launch_true_peak(ek, c.s));
         MT2_HIP(launch_limiter_step(q, kLimStepTrim, c.s));
@@ -2632,10 +2623,7 @@ static void limiter_run(const Ctx& c, const float* wav, const int* lens, int L_m
         q.rowk = nullptr;
         if (!last || stats) {
             pk.gain = nullptr; pk.out = nullptr;                              // the measuring form of the four kernels
-            MT2_HIP(launch_loudness_filter(pk, c.s));
-            MT2_HIP(launch_loudness_carry(pk, c.s));
-            MT2_HIP(launch_loudness_sums(pk, c.s));
-            MT2_HIP(launch_loudness_gate(pk, c.s));
+            loudness_launches(c, pk, nullptr);
             q.rowk = w.rowk;
             if (!last && normalizing) MT2_HIP(launch_limiter_step(q, kLimStepNext, c.s));
             st.mark(kMeasureMark[k]);

@@ -4,6 +4,8 @@
 #include "../../include/megatts2_hip.h"
 #include "mt2_kernels.h"
 
+#include <algorithm>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -92,6 +94,12 @@ class IntPlan {
     int add(const int* v, size_t n);
     int add(const std::vector<int>& v) { return add(v.data(), v.size()); }
     int add_fill(size_t n, int value);
+    // a table of f32 or f64 as the words it is made of, zeros behind it up to `words` where that is more
+    template <class T> int add_bits(const T* v, size_t n, size_t words = 0) {
+        const int off = add_fill(std::max(n * sizeof(T) / sizeof(int), words), 0);
+        std::memcpy(h_.data() + off, v, n * sizeof(T));
+        return off;
+    }
     std::vector<int>& host() { return h_; }
     // the plan's place in the arena (or its bytes in an ArenaCount), then the copy into it: upload() is both
     template <class A> void carve(A& a) {

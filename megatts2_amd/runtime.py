@@ -779,6 +779,19 @@ def _out_rows(out, B: int, like, width):
     return out
 
 
+def _out_like(out, wav):
+    """The `out` of a call that keeps wav's shape: the caller's contiguous f32 [B, L] device tensor, which may be wav itself, or a new one."""
+    out = _out_rows(out, wav.shape[0], wav, lambda: wav.shape[1])
+    assert out.shape == wav.shape
+    return out
+
+
+def _loudness_blocks(ln, sr: int, momentary: bool, short_term: bool):
+    """(NB, NST), a loudness call's momentary and short-term output widths: the longest utterance's blocks, at least 1; 0 if not asked for."""
+    ns = max(int(ln.max()), 0) // max(sr // 10, 1)
+    return max(1, ns - 3) if momentary else 0, max(1, ns - 29) if short_term else 0
+
+
 class MelFrontEnd:
     """extract_mel_spec on the GPU (reference modules/tokenizer.py:107-125): STFT as an implicit conv on the
     GEMM engine, magnitude, slaney mel filterbank, log(clamp(., 1e-5)).  Owns a bare handle (no weights)."""
@@ -852,6 +865,9 @@ class MelFrontEnd:
         res = (out, bounds[:, 1] - bounds[:, 0], bounds)
         return res + (energy,) if return_energy else res
 
+    def _rate(self, sample_rate: Optional[int]) -> int:
+        return self.audio.sample_rate if sample_rate is None else int(sample_rate)
+
     def loudness(self, wav, lens=None, sample_rate: Optional[int] = None, return_momentary: bool = False):
         """Integrated loudness (ITU-R BS.1770-4, gated; what EBU R 128 builds on) of a ragged batch of mono utterances on the device, by
         the rule of csrc/loudness.hip / include/megatts2_hip.h; parity with pyloudnorm / libebur128 is unpinned; true peak and
@@ -863,12 +879,10 @@ class MelFrontEnd:
         enqueues."""
         import torch
         wav, ln, B, L = _wav_lens(wav, lens)
-        sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
+        sr = self._rate(sample_rate)
         stats = torch.empty(B, LOUDNESS_FIELDS, device=wav.device, dtype=torch.float64)
-        mom, NB = None, 0
-        if return_momentary:
-            NB = max(1, max(int(ln.max()), 0) // max(sr // 10, 1) - 3)
-            mom = torch.empty(B, NB, device=wav.device, dtype=torch.float64)
+        NB = _loudness_blocks(ln, sr, return_momentary, False)[0]
+        mom = torch.empty(B, NB, device=wav.device, dtype=torch.float64) if NB else None
         _check(self.lib.mt2_loudness(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, _ptr(stats), _ptr(mom), NB))
         return (stats, mom) if return_momentary else stats
 
@@ -884,16 +898,11 @@ class MelFrontEnd:
         longest)], -inf behind an utterance's own blocks.  Samples beyond lens[b] are never read.  The call only enqueues."""
         import torch
         wav, ln, B, L = _wav_lens(wav, lens)
-        sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
+        sr = self._rate(sample_rate)
         stats = torch.empty(B, EBU_FIELDS, device=wav.device, dtype=torch.float64)
-        ns = max(int(ln.max()), 0) // max(sr // 10, 1)
-        mom, NB, sht, NST = None, 0, None, 0
-        if return_momentary:
-            NB = max(1, ns - 3)
-            mom = torch.empty(B, NB, device=wav.device, dtype=torch.float64)
-        if return_short_term:
-            NST = max(1, ns - 29)
-            sht = torch.empty(B, NST, device=wav.device, dtype=torch.float64)
+        NB, NST = _loudness_blocks(ln, sr, return_momentary, return_short_term)
+        mom = torch.empty(B, NB, device=wav.device, dtype=torch.float64) if NB else None
+        sht = torch.empty(B, NST, device=wav.device, dtype=torch.float64) if NST else None
         _check(self.lib.mt2_loudness_ebu(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, _ptr(stats), _ptr(mom), NB, _ptr(sht), NST))
         res = (stats,) + ((mom,) if return_momentary else ()) + ((sht,) if return_short_term else ())
         return res if len(res) > 1 else stats
@@ -916,28 +925,22 @@ class MelFrontEnd:
         limited audio reads target_lufs, and the ceiling holds as before.  return_stats then gives the f64 [B, 24] of `limit`."""
         import torch
         wav, ln, B, L = _wav_lens(wav, lens)
-        sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
+        sr = self._rate(sample_rate)
         if limiter is not None and true_peak_ceiling_dbtp is None:
             raise ValueError("a limiter holds a true-peak ceiling: state true_peak_ceiling_dbtp")
-        if out is None:
-            out = torch.empty_like(wav)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == wav.shape
-        if true_peak_ceiling_dbtp is not None:
-            if peak_ceiling > 0:
-                raise ValueError("peak_ceiling and true_peak_ceiling_dbtp exclude each other: state the ceiling one way")
-            if limiter is not None:
-                stats = torch.empty(B, LIMITER_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
-                _check(self.lib.mt2_loudness_normalize_limited(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs),
-                                                               float(true_peak_ceiling_dbtp), float(limiter.window_ms), int(limiter.passes),
-                                                               _ptr(out), None, None, _ptr(stats)))
-                return (out, stats) if return_stats else out
-            stats = torch.empty(B, EBU_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
-            _check(self.lib.mt2_loudness_normalize_tp(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs),
-                                                      float(true_peak_ceiling_dbtp), _ptr(out), _ptr(stats)))
-            return (out, stats) if return_stats else out
-        stats = torch.empty(B, LOUDNESS_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
-        _check(self.lib.mt2_loudness_normalize(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs), float(peak_ceiling),
-                                               _ptr(out), _ptr(stats)))
+        out = _out_like(out, wav)
+        if true_peak_ceiling_dbtp is not None and peak_ceiling > 0:
+            raise ValueError("peak_ceiling and true_peak_ceiling_dbtp exclude each other: state the ceiling one way")
+        fields = LOUDNESS_FIELDS if true_peak_ceiling_dbtp is None else EBU_FIELDS if limiter is None else LIMITER_FIELDS
+        stats = torch.empty(B, fields, device=wav.device, dtype=torch.float64) if return_stats else None
+        head = (self.h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, float(target_lufs))
+        if true_peak_ceiling_dbtp is None:
+            _check(self.lib.mt2_loudness_normalize(*head, float(peak_ceiling), _ptr(out), _ptr(stats)))
+        elif limiter is None:
+            _check(self.lib.mt2_loudness_normalize_tp(*head, float(true_peak_ceiling_dbtp), _ptr(out), _ptr(stats)))
+        else:
+            _check(self.lib.mt2_loudness_normalize_limited(*head, float(true_peak_ceiling_dbtp), float(limiter.window_ms), int(limiter.passes),
+                                                           _ptr(out), None, None, _ptr(stats)))
         return (out, stats) if return_stats else out
 
     def limit(self, wav, lens=None, pre_gain_db: float = 0.0, ceiling_dbtp: float = -1.0, window_ms: float = 5.0,
@@ -954,10 +957,8 @@ class MelFrontEnd:
         The call only enqueues."""
         import torch
         wav, ln, B, L = _wav_lens(wav, lens)
-        sr = self.audio.sample_rate if sample_rate is None else int(sample_rate)
-        if out is None:
-            out = torch.empty_like(wav)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == wav.shape
+        sr = self._rate(sample_rate)
+        out = _out_like(out, wav)
         stats = torch.empty(B, LIMITER_FIELDS, device=wav.device, dtype=torch.float64) if return_stats else None
         gain = torch.empty_like(wav) if return_gain else None
         need = torch.empty_like(wav) if return_need else None

@@ -768,7 +768,8 @@ int mt2_synthesize_prompt_conditioned_sampled(mt2_model* m, void* stream, const 
  *                   1 LayerNorm kernels, 2 ff.0's epilogue -> ff.3, 4 attention -> out-projection), "up_fuse" (3: bit mask 1 | 2 = the MRF mean in front of the 64- | 128-channel
  *                   stride-2 upsampler fused into it), "pair_fuse" (3: bit mask
  *                   of the HiFi-GAN stages whose resblock conv pairs x + conv2(lrelu(conv1(lrelu(x)))) run as ONE launch, bit-identical
- *                   to the two launches - 1 the 32-channel stage, 2 the 64-channel stage, 4 the 128-channel stage);
+ *                   to the two launches - 1 the 32-channel stage, 2 the 64-channel stage, 4 the 128-channel stage), "ks_epi4" (1: the
+ *                   fp16-pipe K-split tiles finish with 16-byte loads and stores where the layout allows, bit-identical to 0);
  *   thresholds      "t_x3h_128" (72), "t_x6_256" (160), "t_x6_128" (72), "t_ks4" (256), "t_ks2" (640), "t32" (64), "t32x32" (160)
  *                   (tile counts at which the tile choice changes), "attn_x6_min" (192), "attn_lds_min" (640) (queries per sequence);
  *   measurement     "force_gemm_config" (-1), "stage_markers" (0), "ldr64" (0).
@@ -828,6 +829,8 @@ int mt2_x3h_group_planes(long long row_len, long long w_off, long long ldw, long
  * groups = 1 and the pointers moved by the strides.  W3 / Wh / wh_inv / rowbase / bias / R / valid / range_flag may be NULL;
  * a_planes = 1: X holds fp16 planes.  range_flag: device int32, |= 1 when an fp16-pipe launch converted an activation with
  * |a| >= 65504.  cfg_out (host, may be NULL): the configuration index the routing chose (-1: rejected before a choice).
+ * ks_epi4: the option of that name for this launch (0: the x3h K-split tiles keep their dword finish); epi4_out (host, may be NULL):
+ * 1 when the launch finished its tiles with 16-byte loads and stores.
  * struct_bytes = sizeof(mt2_gemm_desc) as the caller sees it: a mirror of the struct laid out differently is an error, not a launch. */
 typedef struct mt2_gemm_desc {
     int32_t struct_bytes;
@@ -846,6 +849,8 @@ typedef struct mt2_gemm_desc {
     int32_t force_cfg;
     int32_t* range_flag;
     int32_t* cfg_out;
+    int32_t ks_epi4;
+    int32_t* epi4_out;
 } mt2_gemm_desc;
 int mt2_op_gemm_grouped(void* stream, const mt2_gemm_desc* d);
 /* Range guard of the fp16-pipe kernels inside a model handle (option "x3h", default 15): waits for the handle's last call, then
@@ -1025,6 +1030,11 @@ const char* mt2_gemm_config_name(int idx);
  * 1024 C).  force_cfg / x3h: the options of the same names.  Returns 0. */
 int mt2_gemm_route(int M, int N, int K, int taps, int dil, int groups, int pro_act, int operands, int misaligned, int force_cfg,
                    int x3h, int* err, int* cfg, int* variant, long long* lds, int* planes);
+/* ... the same launch with the rows of C and R ld_pad floats further apart (ldc = ldr = N + ld_pad) and the option ks_epi4 as given;
+ * epi4 (may be NULL): 1 when an x3h K-split tile would finish the launch row-major with 16-byte loads and stores - N, ldc, ldr and, in
+ * grouped launches, the group strides multiples of 4, C / R / bias / wh_inv on 16 bytes - 0 for its dword finish or any other kernel. */
+int mt2_gemm_route_ex(int M, int N, int K, int taps, int dil, int groups, int pro_act, int operands, int misaligned, int force_cfg,
+                      int x3h, int ld_pad, int ks_epi4, int* err, int* cfg, int* variant, long long* lds, int* planes, int* epi4);
 /* test hook, no device needed: what launch_conv_pair (csrc/gemm_x3h.hip, conv_pair_route) would do with the resblock conv pair of C
  * channels, `taps` taps, first dilation `dil` over R rows - err: 0 it launches (or R <= 0: nothing to launch, grid 0), hipErrorNotSupported
  * (801) the two-launch form keeps the pair, hipErrorInvalidValue (1) bad arguments; lds: dynamic LDS bytes; grid / block: the launch;
@@ -1057,7 +1067,8 @@ int mt2_op_up_mrf(void* stream, const float* X0, const float* X1, const float* X
  * through `w_copies` copies of the weight matrix (> 1: weights are not L2-resident from the previous launch);
  * flags bit0: leaky-ReLU prologue, bit1: bias + residual + row-mask epilogue, bit2: clock probe - one wave of the
  * loader-wave x6 kernel reads s_memtime and s_memrealtime around its K loop; `sustained_ghz` (nullable) receives the
- * shader clock that launch ran at (0 when the configuration has no probe), bit3: no stderr report; average ms */
+ * shader clock that launch ran at (0 when the configuration has no probe), bit3: no stderr report, bit4: loader waves at the default
+ * issue priority, bit5: no fp16-pipe forms, bit6: the x3h K-split tiles' dword finish (option ks_epi4 = 0); average ms */
 int mt2_op_gemm_x3h_ln(void* stream, const float* X, int ldx, int Rx, int a_mul, int shift0, const float* W, const void* W3,
                        const void* Wh, const float* wh_inv, const float* bias, const float* R, int ldr, float* C, int ldc, int M, int N,
                        int K, int epi_act, int force_cfg, float* stat_out, int32_t* stat_nt, int32_t* stat_w, const float* ln_stat,

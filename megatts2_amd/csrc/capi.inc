@@ -378,6 +378,7 @@ static int* option_slot(mt2_model* m, const std::string& n) {
     if (n == "a_planes") return &m->opts.a_planes;
     if (n == "pair_fuse") return &m->opts.pair_fuse;
     if (n == "up_fuse") return &m->opts.up_fuse;
+    if (n == "ks_epi4") return &m->opts.ks_epi4;
     return nullptr;
 }
 static bool* option_flag(mt2_model* m, const std::string& n) {
@@ -1459,8 +1460,15 @@ const char* mt2_gemm_config_name(int idx) { return gemm_config_name(idx); }
 // (with ln_g / ln_b and pairs of 64 columns), 32 R, 64 rowbase, 128 a_planes, 256 c_planes.  Every pointer sits on 128 bytes except
 // those whose bit is set in `misaligned` (same bits; 512: X, 1024: C), which sit 4 bytes further.  variant: GemmVariant; planes: bit 0
 // gemm_takes_planes, bit 1 gemm_writes_planes for the same launch.
+// mt2_gemm_route_ex: the same launch with the rows of C and R ld_pad floats apart beyond N and the option ks_epi4 as given; *epi4 = 1
+// when an x3h K-split tile would finish it with 16-byte loads and stores (GemmRoute::ks_epi4).
 int mt2_gemm_route(int M, int N, int K, int taps, int dil, int groups, int pro_act, int operands, int misaligned, int force_cfg,
                    int x3h, int* err, int* cfg, int* variant, long long* lds, int* planes) {
+    return mt2_gemm_route_ex(M, N, K, taps, dil, groups, pro_act, operands, misaligned, force_cfg, x3h, 0, 1, err, cfg, variant, lds,
+                             planes, nullptr);
+}
+int mt2_gemm_route_ex(int M, int N, int K, int taps, int dil, int groups, int pro_act, int operands, int misaligned, int force_cfg,
+                      int x3h, int ld_pad, int ks_epi4, int* err, int* cfg, int* variant, long long* lds, int* planes, int* epi4) {
     alignas(128) static char dummy[12 * 128];
     const auto ptr = [&](int slot, int bit) { return (void*)(dummy + 128 * slot + ((misaligned & bit) ? 4 : 0)); };
     GemmP p{};
@@ -1478,10 +1486,15 @@ int mt2_gemm_route(int M, int N, int K, int taps, int dil, int groups, int pro_a
     if (operands & 64) p.rowbase = (const int*)ptr(11, 64);
     p.a_planes = (operands & 128) ? 1 : 0;
     p.c_planes = (operands & 256) ? 1 : 0;
+    p.ldc += ld_pad;
+    if (p.R) p.ldr += ld_pad;
+    p.strideC = (long long)M * p.ldc; p.strideR = (long long)M * p.ldc;
     EngineOpts o;
     o.force_cfg = force_cfg;
     o.x3h = x3h;
+    o.ks_epi4 = ks_epi4;
     const GemmRoute r = gemm_route(p, o);
+    if (epi4) *epi4 = r.ks_epi4;
     if (err) *err = (int)r.err;
     if (cfg) *cfg = r.cfg;
     if (variant) *variant = r.variant;
@@ -1629,6 +1642,7 @@ int mt2_op_gemm_x3h(void* stream, const float* X, int ldx, int Rx, int shift0, i
     p.ldc = ldc; p.M = M; p.N = N; p.K = taps * Cin; p.groups = 1; p.pro_act = pro_act; p.pro_slope = pro_slope; p.epi_act = epi_act;
     p.out_scale = 1.0f;
     EngineOpts o;
+    if (force_cfg >= 8000) { o.ks_epi4 = 0; force_cfg -= 8000; }        // tests: configuration + 8000 = the K-split tiles' dword finish (option ks_epi4 = 0)
     if (force_cfg >= 4000) { p.c_planes = 1; force_cfg -= 4000; }       // tests: configuration + 4000 = C receives fp16 planes (GemmP::c_planes)
     if (force_cfg >= 2000) { p.a_planes = 1; force_cfg -= 2000; }       // tests: configuration + 2000 = X holds fp16 planes (GemmP::a_planes)
     o.ldr64 = force_cfg >= 1000;            // tests: configuration + 1000 = the same launch with the loaders' 64-bit address form
@@ -1664,6 +1678,7 @@ int mt2_op_gemm_grouped(void* stream, const mt2_gemm_desc* d) {
     MT2_REQUIRE(d != nullptr, "null descriptor");
     MT2_REQUIRE(d->struct_bytes == (int32_t)sizeof(mt2_gemm_desc), "descriptor size mismatch");
     if (d->cfg_out) *d->cfg_out = -1;
+    if (d->epi4_out) *d->epi4_out = 0;
     GemmP p{};
     p.X = d->X; p.strideX = d->strideX; p.ldx = d->ldx; p.Rx = d->Rx;
     p.rowbase = d->rowbase; p.a_mul = d->a_mul; p.shift0 = d->shift0; p.taps = d->taps; p.dil = d->dil; p.Cin = d->Cin;
@@ -1679,7 +1694,10 @@ int mt2_op_gemm_grouped(void* stream, const mt2_gemm_desc* d) {
     EngineOpts o;            // per call: no state is shared with any handle or thread
     o.force_cfg = d->force_cfg;
     o.x3h_flag = d->range_flag;
-    if (d->cfg_out) *d->cfg_out = gemm_route(p, o).cfg;
+    o.ks_epi4 = d->ks_epi4;
+    const GemmRoute rt = gemm_route(p, o);
+    if (d->cfg_out) *d->cfg_out = rt.cfg;
+    if (d->epi4_out) *d->epi4_out = rt.err == hipSuccess ? rt.ks_epi4 : 0;
     MT2_HIP(launch_gemm(p, (hipStream_t)stream, &o));
     MT2_API_END
 }
@@ -1719,6 +1737,7 @@ static int op_gemm_ln_impl(void* stream, const float* X, int ldx, int Rx, int a_
     p.epi_act = epi_act; p.out_scale = 1.0f; p.stat_out = stat_out;
     if (ln_stat) { p.pro_act = 5; p.ln_stat = ln_stat; p.ln_nt = ln_nt; p.ln_w = ln_w; p.ln_g = ln_s; p.ln_eps = ln_eps; }
     EngineOpts o;
+    if (force_cfg >= 8000) { o.ks_epi4 = 0; force_cfg -= 8000; }        // tests: configuration + 8000 = the K-split tiles' dword finish (option ks_epi4 = 0)
     o.ldr64 = force_cfg >= 1000;
     o.force_cfg = force_cfg >= 1000 ? force_cfg - 1000 : force_cfg;
     const hipError_t e = launch_gemm(p, (hipStream_t)stream, &o);
@@ -2095,6 +2114,7 @@ int mt2_bench_gemm(void* stream, int M, int N, int K, int taps, int dil, int fla
     o.force_cfg = force_cfg;
     if (flags & 16) o.ldr_prio = 0;         // measurement: loader waves at the default issue priority
     if (flags & 32) o.x3h = 0;              // measurement: the automatic choice without the fp16-pipe forms
+    if (flags & 64) o.ks_epi4 = 0;          // measurement: the x3h K-split tiles' dword finish
     hipError_t e = launch_gemm(p, s, &o);   // warm-up
     hipEvent_t e0, e1;
     MT2_HIP(hipEventCreate(&e0));

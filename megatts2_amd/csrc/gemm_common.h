@@ -206,6 +206,100 @@ __device__ __forceinline__ void epilogue_pre(const GemmP& p, const float (&acc)[
     if constexpr (STAT) emit_row_pairs<NE>(p, sv, qv, mw, nw >> 5, 32.0f, lane, e0);      // one pair per 32-column wave tile
 }
 
+// The row-major form of the same epilogue (the x3h K-split tiles, option ks_epi4): the K-group reduction leaves the 32x32 tile in LDS
+// as a [row][col] image, so a wave can finish its 32 / KS rows with a lane owning FOUR CONSECUTIVE COLUMNS of a row - lane l: columns
+// nw + 4 (l & 7) .. + 3 of the rows rl + 8 v, v < NV (rl = the first row of the wave's share + (l >> 3)) - one 16-byte residual load,
+// one mask dword and one 16-byte store per row instead of four of each.  `active`: the 32x32 k8 tile finishes 4 rows per wave, its
+// lanes 32-63 own nothing.  Per element the arithmetic and its order are epilogue_pre's: C is bit-identical.  The caller (gemm_route)
+// admits the form only with N, ldc, ldr multiples of 4 and every operand base on 16 bytes.
+template <int NV> struct EpiPre4 { f32x4 r[NV]; int v[NV]; f32x4 b; };
+template <int NV>
+__device__ __forceinline__ void epi_prefetch4(const GemmP& p, EpiPre4<NV>& q, int g, int mw, int nw, int lane, int rl) {
+    // (unconditional loads from safe addresses, as in epi_prefetch)
+    const int n = nw + (lane & 7) * 4;
+    const bool nok = n < p.N;                             // N is a multiple of 4: the four columns are in or out together
+    const float* __restrict__ bias = p.bias ? p.bias + (long long)g * p.strideB + (nok ? n : 0) : g_zero16;
+    const float* __restrict__ R = p.R ? p.R + (long long)g * p.strideR + (nok ? n : 0) : g_zero16;
+    const long long ldr = p.R ? p.ldr : 0;
+    const int* __restrict__ vp = p.valid ? p.valid : g_one_i;
+    const int vs = p.valid ? 1 : 0;
+    q.b = *reinterpret_cast<const f32x4*>(bias);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        int m = mw + rl + 8 * v;
+        m = m < p.M ? m : 0;
+        q.r[v] = *reinterpret_cast<const f32x4*>(R + m * ldr);
+        q.v[v] = vp[m * vs];
+    }
+}
+// Sum of a row's 32 columns (x: this lane's four, the row's other columns in the 7 lanes that differ in lane bits 0-2) in the
+// ASSOCIATION of rows_sum32<NE> - pairs of columns that differ in bit NE / 2 first, then NE / 4 ... 1, then NE ... 16 (column bit 1 / 2:
+// inside the lane; 4 / 8 / 16: lane xor 1 / 2 / 4) - so that the pairs of emit_row_pairs come out bit-identical (f32 addition is
+// commutative: only the tree matters).  No contraction: rows_sum32 adds a lane-selected value to a shuffled one, never a product.
+template <int NE>
+__device__ __forceinline__ float row4_sum32(float x0, float x1, float x2, float x3) {
+#pragma clang fp contract(off)
+    static_assert(NE == 2 || NE == 4 || NE == 8, "K-split shares of 2, 4 or 8 accumulator elements");
+    float s;
+    if constexpr (NE == 8) {                              // column bits 4, 2, 1, 8, 16
+        x0 += __shfl_xor(x0, 1); x1 += __shfl_xor(x1, 1); x2 += __shfl_xor(x2, 1); x3 += __shfl_xor(x3, 1);
+        s = (x0 + x2) + (x1 + x3);
+        s += __shfl_xor(s, 2);
+        s += __shfl_xor(s, 4);
+    } else {
+        if constexpr (NE == 4) s = (x0 + x2) + (x1 + x3);  // 2, 1, 4, 8, 16
+        else s = (x0 + x1) + (x2 + x3);                    // 1, 2, 4, 8, 16
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        s += __shfl_xor(s, 4);
+    }
+    return s;
+}
+__device__ __forceinline__ float mul_uncontracted(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+// NE: the accumulator elements per lane of the dword form of the same tile (16 / KS) - the association of the pair sums
+template <int NV, int NE, bool STAT = false>
+__device__ __forceinline__ void epilogue_pre4(const GemmP& p, const f32x4 (&acc)[NV], const EpiPre4<NV>& q, int g, int mw, int nw,
+                                              int lane, int rl, bool active) {
+    float* __restrict__ C = p.C + (long long)g * p.strideC;
+    const int epi_act = p.epi_act;
+    const float epi_par = p.pro_slope;     // parameter of the epilogue activation (ACT_LOGCLAMP: the clip value)
+    const float out_scale = p.out_scale;
+    const bool hasR = p.R != nullptr;
+    const int n = nw + (lane & 7) * 4;
+    const bool nok = n < p.N;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int m = mw + rl + 8 * v;
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        if (active && nok && m < p.M) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float x = acc[v][c] + q.b[c];
+                x = act_rt(epi_act, x, epi_par) * out_scale;
+                if (hasR) x += q.r[v][c];
+                if (q.v[v] == 0) x = 0.0f;
+                o[c] = x;
+            }
+            *reinterpret_cast<f32x4*>(C + (long long)m * p.ldc + n) = o;
+        }
+        if constexpr (STAT) {                             // one pair per row and 32-column wave tile, of the FINAL values (0 outside M x N)
+            const float S = row4_sum32<NE>(o[0], o[1], o[2], o[3]);
+            const float Q = row4_sum32<NE>(mul_uncontracted(o[0], o[0]), mul_uncontracted(o[1], o[1]), mul_uncontracted(o[2], o[2]),
+                                           mul_uncontracted(o[3], o[3]));
+            if (active && (lane & 7) == 0 && m < p.M) {
+                const float mean = S / 32.0f;
+                float2 pr;
+                pr.x = mean;
+                pr.y = fmaxf(Q - S * mean, 0.0f);
+                *reinterpret_cast<float2*>(p.stat_out + ((long long)m * p.stat_nt + (nw >> 5)) * 2) = pr;
+            }
+        }
+    }
+}
+
 // The same for TM x TN tiles per wave (no K split): residual, row mask and bias of the whole wave tile are
 // requested before the K loop.  On the vocoder's residual convolutions the un-prefetched epilogue cost 11-25 %
 // of the launch (1 workgroup per CU: nothing else covers the residual read).

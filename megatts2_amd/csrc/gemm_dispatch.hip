@@ -300,7 +300,7 @@ static long long wh_gstride_of(const GemmP& p) { return p.groups > 1 && p.wh_gst
 
 GemmRoute gemm_route(const GemmP& p, const EngineOpts& o) {
     GemmRoute r{hipSuccess, -1, V_NONE, 0, 0, 0};
-    const auto fail = [&r](hipError_t e) { r.err = e; r.lds = 0; r.stat_nt = r.stat_w = 0; return r; };
+    const auto fail = [&r](hipError_t e) { r.err = e; r.lds = 0; r.stat_nt = r.stat_w = 0; r.ks_epi4 = 0; return r; };
     if (p.M <= 0 || p.N <= 0 || p.groups <= 0) return r;        // nothing to launch
     if ((p.Cin & 3) || (p.ldx & 3) || (p.ldw & 3) || p.K != p.taps * p.Cin) return fail(hipErrorInvalidValue);
     if (p.pro_act < 0 || p.pro_act > PRO_LNX) return fail(hipErrorInvalidValue);
@@ -370,6 +370,14 @@ GemmRoute gemm_route(const GemmP& p, const EngineOpts& o) {
         r.lds = c->lds + (size_t)c->win_qs * wrp * BK * sizeof(float);
     }
     if (!c->fn[r.variant]) return fail(hipErrorNotSupported);   // no variant for this prologue
+    // the x3h K-split tiles finish row-major on 16 bytes (gemm_x3h_ks_kernel, EPI4) where every access of that finish is aligned: columns
+    // in fours, rows and - in grouped launches - groups a multiple of four floats apart, every operand it reads as a float4 on 16 bytes
+    if (o.ks_epi4 && x3h && c->x6_ks && c->fn4[r.variant]) {
+        const auto on16 = [](const void* q) { return (((unsigned long long)q) & 15) == 0; };
+        const bool grp4 = p.groups == 1 || ((p.strideC | (p.R ? p.strideR : 0) | (p.bias ? p.strideB : 0) | p.wh_inv_stride) & 3) == 0;
+        r.ks_epi4 = ((p.N | p.ldc | (p.R ? p.ldr : 0)) & 3) == 0 && grp4 && on16(p.C) && on16(p.R) && on16(p.bias) && on16(p.wh_inv) &&
+                    (p.pro_act != PRO_LNX || on16(p.ln_g));
+    }
     return r;
 }
 
@@ -398,14 +406,14 @@ bool gemm_writes_planes(const GemmP& p_in, const EngineOpts& o) {
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per-DEVICE state of the code object: a "done" mask per (configuration,
 // variant) with one bit per device only saves the call; the benign race (two threads setting the same value) is harmless.
-static std::atomic<unsigned long long> g_attr_done[kNumCfgs][kGemmVariants];   // bit per device (dyn_lds_once)
+static std::atomic<unsigned long long> g_attr_done[kNumCfgs][2 * kGemmVariants];   // bit per device (dyn_lds_once); [kGemmVariants ..): TileCfg::fn4
 
 hipError_t launch_gemm(const GemmP& p_in, hipStream_t s, EngineOpts* opts) {
     static const EngineOpts kDefaults;
     const EngineOpts& o = opts ? *opts : kDefaults;
     const GemmRoute r = gemm_route(p_in, o);
     if (r.cfg < 0 && r.err == hipSuccess) return hipSuccess;    // nothing to launch
-    if (opts) { opts->last_stat_nt = r.stat_nt; opts->last_stat_w = r.stat_w; opts->last_sk_nw = 0; }
+    if (opts) { opts->last_stat_nt = r.stat_nt; opts->last_stat_w = r.stat_w; opts->last_sk_nw = 0; opts->last_ks_epi4 = r.ks_epi4; }
     if (r.err != hipSuccess) return r.err;
     GemmP p = p_in;
     if (!r.stat_nt) p.stat_out = nullptr;                       // the chosen kernel has no row-statistics epilogue for this launch
@@ -423,10 +431,10 @@ hipError_t launch_gemm(const GemmP& p_in, hipStream_t s, EngineOpts* opts) {
         p.x3h_flag = o.x3h_flag;
     }
     if (c->pipe == PIPE_X6 && p.w3_plane == 0) p.w3_plane = (long long)p.N * p.ldw;
-    const GemmKernel fn = c->fn[r.variant];
+    const GemmKernel fn = r.ks_epi4 ? c->fn4[r.variant] : c->fn[r.variant];
     // window configurations: the attribute covers the widest window (span <= 64)
     const size_t lds_attr = c->win_qs ? c->lds + (size_t)c->win_qs * ((c->bm + 64 + 7) & ~7) * BK * sizeof(float) : r.lds;
-    const hipError_t e = dyn_lds_once(g_attr_done[r.cfg][r.variant], reinterpret_cast<const void*>(fn), lds_attr);
+    const hipError_t e = dyn_lds_once(g_attr_done[r.cfg][r.variant + (r.ks_epi4 ? kGemmVariants : 0)], reinterpret_cast<const void*>(fn), lds_attr);
     if (e != hipSuccess) return e;
     const int tiles = ((p.M + c->bm - 1) / c->bm) * ((p.N + c->bn - 1) / c->bn);
     p.epi_t4 = 1;

@@ -56,6 +56,7 @@ struct TileCfg {
     int x6_ks = 0;            // > 0: K-split tile of the x6 / x3h pipes: linear layers with K a multiple of 32 * x6_ks
     int stat_w = 0;           // > 0: the tile has the row-statistics epilogue (GemmP::stat_out: one pair per stat_w columns) and
                               // the pair-fed algebraic-LayerNorm form (pro_act == PRO_LNX)
+    GemmKernel fn4[kGemmVariants] = {};   // x3h K-split tiles: the same kernels with the row-major 16-byte finish (GemmRoute::ks_epi4)
 };
 struct TileRows { const TileCfg* rows; int n; };
 TileRows gemm_f32_tile_rows();      // gemm_f32.hip

@@ -634,7 +634,13 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void gemm_x3h_ldr_kernel(Gem
 // the whole refill, one barrier per round; the partial tiles (acc_hi + 2^-11 acc_lo of each group) are summed through LDS in a
 // fixed order and each group finishes 16 / KS accumulator elements in the fused epilogue.  Per wave and k block: 3 MFMAs and one
 // 28-VALU split instead of 6 and 44.  Linear layers only (taps = 1, K a multiple of 32 KS).
-template <int BM, int BN, int WGM, int WGN, int KS, int NL, int NST, int PRO>
+// EPI4 (option ks_epi4, chosen by gemm_route where the layout allows 16-byte accesses): the partial tiles go to LDS as row-major
+// [32][32] images and group kg finishes ROWS 32 kg / KS .. of the tile, a lane owning four consecutive columns of a row (epilogue_pre4,
+// gemm_common.h): ds_read_b128, 16-byte residual loads and 16-byte stores instead of dwords.  Same sums in the same order: C and the
+// row-statistics pairs are bit-identical to the dword finish.  The unpadded image is free of bank conflicts both ways: a ds_write_b32
+// half-wave writes the 32 consecutive dwords of one row; the four 16-lane groups of a ds_read_b128 (lanes l >> 3 = row, l & 7 = 16-byte
+// slot of a 128-byte row) each cover the 16 slots of a 256-byte bank row once.
+template <int BM, int BN, int WGM, int WGN, int KS, int NL, int NST, int PRO, bool EPI4 = false>
 __global__ __launch_bounds__((WGM * WGN * KS + NL) * 64) void gemm_x3h_ks_kernel(GemmP p) {
     constexpr int NW = WGM * WGN;                         // waves of one K group
     constexpr int NWC = NW * KS;                          // compute waves
@@ -643,6 +649,8 @@ __global__ __launch_bounds__((WGM * WGN * KS + NL) * 64) void gemm_x3h_ks_kernel
     constexpr int LW = PT / NL;                           // pieces per loader wave and round
     constexpr int STAGE_A = BM * BK * 4, STAGE_B = PB * 1024, STAGE = STAGE_A + STAGE_B;   // bytes, one group's stage
     constexpr int EPG = 16 / KS;
+    constexpr int NV = EPG >= 4 ? EPG / 4 : 1;            // EPI4: float4 per lane (the k8 tile: one, in lanes 0-31 only)
+    static_assert(!EPI4 || KS > 1, "the row-major finish reads the K-group reduction's LDS images");
     static_assert(BM == 32 * WGM && BN == 32 * WGN, "one 32x32 tile per wave");
     static_assert(PT % NL == 0 && 16 % KS == 0 && NST >= 2 && (NST - 2) * LW < 64 && NWC + NL <= 16, "config");
     static_assert(KS * NST * STAGE >= NWC * 16 * 64 * 4 || KS == 1, "the K-group reduction reuses the ring");
@@ -754,15 +762,24 @@ __global__ __launch_bounds__((WGM * WGN * KS + NL) * 64) void gemm_x3h_ks_kernel
     // ---------------------------------------------------------------------- compute wave: K group kg, tile (wm, wn)
     const int kg = wave_all / NW, wave = wave_all % NW;
     const int wm = wave / WGN, wn = wave % WGN;
-    EpiPre<EPG> pre;
-    epi_prefetch<EPG>(p, pre, g, m0 + wm * 32, n0 + wn * 32, lane, kg * EPG);
+    EpiPre<EPI4 ? 1 : EPG> pre;
+    EpiPre4<NV> pre4;
     float inv_s;
-    {
+    f32x4 inv4, sn4;                                      // EPI4: inverse row scales and the LayerNorm correction's s of the lane's four columns
+    const bool lnx = PRO == PRO_LNX && p.pro_act == PRO_LNX;
+    const bool active4 = EPG >= 4 || lane < 32;
+    const int rl4 = active4 ? kg * 2 * EPG + (lane >> 3) : 0;      // EPI4: the lane's first row of the wave's 32 / KS rows
+    if constexpr (EPI4) {
+        epi_prefetch4<NV>(p, pre4, g, m0 + wm * 32, n0 + wn * 32, lane, rl4);
+        const int n = n0 + wn * 32 + (lane & 7) * 4;
+        inv4 = *reinterpret_cast<const f32x4*>(p.wh_inv + (long long)g * p.wh_inv_stride + (n < p.N ? n : 0));
+        sn4 = *reinterpret_cast<const f32x4*>(lnx ? p.ln_g + (n < p.N ? n : 0) : g_zero16);
+    } else {
+        epi_prefetch<EPG>(p, pre, g, m0 + wm * 32, n0 + wn * 32, lane, kg * EPG);
         const int n = n0 + wn * 32 + (lane & 31);
         inv_s = (p.wh_inv + (long long)g * p.wh_inv_stride)[n < p.N ? n : 0];
     }
     float ln_mu = 0.0f, ln_rs = 0.0f;
-    const bool lnx = PRO == PRO_LNX && p.pro_act == PRO_LNX;
     if (lnx) lnx_row_stats<2>(p, m0 + wm * 32 + (lane & 31), lane >> 5, 32, ln_mu, ln_rs);      // lanes l and l ^ 32 share a row
     f32x16 acc, acl;
 #pragma unroll
@@ -820,8 +837,9 @@ __global__ __launch_bounds__((WGM * WGN * KS + NL) * 64) void gemm_x3h_ks_kernel
         fetch(1, sa, sb);
         __builtin_amdgcn_sched_barrier(0);
         // (a form with the fragment pipeline running across the rounds - the cross-chunk form of gemm_x3h_ldr_kernel - measured EQUAL,
-        // +-2 %: these tiles are bound by the ingest, KS x 8..16 KiB per round at the 64 B/clk of a CU's LDS-DMA path = 512..1 024
-        // cycles against 384 of matrix work; profiles/r06_experiment_x3h_ks_cross_round.patch, r06_x3h_phase_timing_v4_*.txt)
+        // +-2 %; profiles/r06_experiment_x3h_ks_cross_round.patch.  The ingest - KS x 8..16 KiB per round at the 64 B/clk of a CU's LDS-DMA
+        // path = 512..1 024 cycles against 384 of matrix work - is not the bound: r06_x3h_phase_timing_v4_*.txt has this fetch -> split ->
+        // product chain at ~450 of a chunk's ~585 cycles with the loader waves idle at the barrier)
         // one tile per wave: a split does not fit in the shadow of its three MFMAs - split and multiply in turn, the other
         // waves of the SIMD (another K group) fill the gaps
         wait_block(0);
@@ -851,7 +869,36 @@ __global__ __launch_bounds__((WGM * WGN * KS + NL) * 64) void gemm_x3h_ks_kernel
     for (int e = 0; e < 16; ++e) acc[e] = __builtin_fmaf(acl[e], kX3hLoInv, acc[e]);
     // ---- sum the KS partial tiles through LDS (every DMA has been waited for; the barrier orders the last operand reads),
     // fixed order kg = 0..KS-1; group kg finishes elements e = kg*EPG .. kg*EPG+EPG-1
-    if constexpr (KS > 1) {
+    if constexpr (EPI4) {
+        __syncthreads();                                  // (the loader waves have left: the barrier counts live waves only)
+        float* img = smem + (kg * NW + wave) * 1024 + half * 128 + (lane & 31);      // [32 rows][32 columns] of this wave's partial tile
+#pragma unroll
+        for (int e = 0; e < 16; ++e) img[((e & 3) + 8 * (e >> 2)) * 32] = acc[e];
+        __syncthreads();
+        f32x4 out[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int g2 = 0; g2 < KS; ++g2) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(smem + (g2 * NW + wave) * 1024 + (rl4 + 8 * v) * 32 + (lane & 7) * 4);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) s[c] += t[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) out[v][c] = s[c] * inv4[c];
+        }
+        if (lnx) {                                        // rstd_r * (acc - mean_r * s_n); the bias operand is c
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const float rs = __shfl(ln_rs, rl4 + 8 * v), mu = __shfl(ln_mu, rl4 + 8 * v);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) out[v][c] = rs * (out[v][c] - mu * sn4[c]);
+            }
+        }
+        if (PRO == PRO_LNX && p.stat_out) epilogue_pre4<NV, EPG, PRO == PRO_LNX>(p, out, pre4, g, m0 + wm * 32, n0 + wn * 32, lane, rl4, active4);
+        else epilogue_pre4<NV, EPG>(p, out, pre4, g, m0 + wm * 32, n0 + wn * 32, lane, rl4, active4);
+    } else if constexpr (KS > 1) {
         __syncthreads();                                  // (the loader waves have left: the barrier counts live waves only)
         float* red = smem + ((kg * NW + wave) * 16) * 64 + lane;
 #pragma unroll
@@ -1924,7 +1971,10 @@ hipError_t launch_up_mrf(const UpMrfP& p_in, hipStream_t s, EngineOpts* opts) {
       "x3hks" #BM_ "x" #BN_ "_" #WM_ "x" #WN_ "_k" #KS_ "+" #NL_ "_s" #NST_,                                                \
       { gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_NONE>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_RELU>, \
         gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_LRELU>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_APL>, \
-        gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_LNX> }, PIPE_X3H, 0, KS_, 32 }
+        gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_LNX> }, PIPE_X3H, 0, KS_, 32,                            \
+      { gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_NONE, true>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_RELU, true>, \
+        gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, ACT_LRELU, true>, gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_APL, true>, \
+        gemm_x3h_ks_kernel<BM_, BN_, WM_, WN_, KS_, NL_, NST_, PRO_LNX, true> } }
 // window convolution: ring stage = 2 planes x BN x 64 B, in whole KiB per loader wave (WinGeom, x3h_window.h)
 #define MT2_X3H_WIN(IDX_, QS_, BM_, BN_, WM_, WN_, NST_, NL_)                                                               \
     { IDX_, BM_, BN_, WinGeom<QS_, BM_, BN_, WM_, WN_, NST_, NL_>::NT, WinGeom<QS_, BM_, BN_, WM_, WN_, NST_, NL_>::ring_bytes(), \

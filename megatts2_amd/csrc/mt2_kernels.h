@@ -127,6 +127,8 @@ struct EngineOpts {
                                  // the conv stacks (LnP::out_planes); bit 1: ff.0's epilogue stores relu(..) as planes for ff.3 (GemmP::c_planes);
                                  // bit 2: the attention kernels store their output as planes for the out-projection (AttnP::o_planes) -
                                  // bit-identical, measured neutral, off by default (profiles/r06_opts_ab_block4_planes_producers.txt)
+    int ks_epi4 = 1;             // x3h K-split tiles: finish the tile row-major with 16-byte residual loads and stores where gemm_route finds the
+                                 // layout fit (GemmRoute::ks_epi4); 0: the dword finish everywhere.  Bit-identical (profiles/ks_epilogue_ab.txt)
     bool ldr64 = false;          // tests / measurement: the x3h loaders' 64-bit global_load_lds form (what operands of 2 GiB or more get)
     int ldr_prio = 3;            // issue priority (s_setprio 0..3) of the loader waves (gemm_x6_ldr / gemm_x6_ks / conv_win_x6 kernels)
     int skinny_rows = 64;        // linear layers with at most this many rows (<= 64) run on the weight-streaming kernel of
@@ -144,6 +146,7 @@ struct EngineOpts {
     std::vector<TraceRec> trace;
     const char* last_cfg = "";   // name of the tile configuration the last launch used
     int last_stat_nt = 0, last_stat_w = 0;   // GemmP::stat_out of the last launch: pairs per row / columns per pair (0: none written)
+    int last_ks_epi4 = 0;        // GemmRoute::ks_epi4 of the last launch
     int last_sk_nw = 0;          // waves that split K in the last launch, if it ran on the tile-major weight-streaming kernel (else 0)
     int ln_pairs = 0;            // (the value in force for the stage that is running: ln_pairs_adm inside the ADM, 0 elsewhere)
     int ln_pairs_adm = 2;        // ADM layers with more than skinny_rows rows: the residual GEMMs (out-projection, ff.3) write row statistics
@@ -161,7 +164,9 @@ struct EngineOpts {
 // the error it returns (hipSuccess: it launches), the configuration index (gemm_config_name; 87..90: the <= 64-row kernels of
 // gemm_skinny.hip; -1: nothing to launch or rejected before a choice), the variant of that tile's kernel (GemmVariant, gemm_tiles.h),
 // the dynamic LDS bytes, and the row-statistics layout it writes (0: none - a stat_out the chosen kernel cannot serve is dropped)
-struct GemmRoute { hipError_t err; int cfg; int variant; size_t lds; int stat_nt, stat_w; };
+// ks_epi4: 1 - an x3h K-split tile finishes the launch with 16-byte loads and stores (EngineOpts::ks_epi4 and N, ldc, ldr, the group
+// strides in fours, C / R / bias / wh_inv / ln_g on 16 bytes); 0 - the dword finish of the same kernel, or another kernel altogether
+struct GemmRoute { hipError_t err; int cfg; int variant; size_t lds; int stat_nt, stat_w; int ks_epi4; };
 GemmRoute gemm_route(const GemmP& p, const EngineOpts& o);
 hipError_t launch_gemm(const GemmP& p, hipStream_t s, EngineOpts* o = nullptr);
 // The vocoder's resblock pair  Y = X + conv2(lrelu(conv1(lrelu(X))))  as ONE launch (conv_pair_x3h_kernel, gemm_x3h.hip): conv1 with

@@ -1605,6 +1605,8 @@ class MT2GemmDesc(C.Structure):
         ("force_cfg", C.c_int32),
         ("range_flag", C.c_void_p),
         ("cfg_out", C.POINTER(C.c_int32)),
+        ("ks_epi4", C.c_int32),
+        ("epi4_out", C.POINTER(C.c_int32)),
     ]
 
 
@@ -1640,12 +1642,13 @@ class GemmWeights:
 def op_gemm_grouped(X, wts, out, *, M, N, Cin, ldx, Rx, ldw, ldc, groups=1, strideX=0, strideW=0, strideC=0, w_off=0, taps=1, dil=1,
                     a_mul=1, shift0=0, rowbase=None, bias=None, strideB=0, R=None, strideR=0, ldr=0, valid=None, pro_act=ACT_NONE,
                     pro_slope=0.0, epi_act=ACT_NONE, out_scale=1.0, force_cfg=-1, x6=True, x3h=True, a_planes=0, wh_gstride=None,
-                    flag=None):
+                    flag=None, ks_epi4=1, want_epi4=False):
     """mt2_op_gemm_grouped: one launch of the engine with `groups` groups.  X / out / bias / R: device tensors whose data pointer is
     the operand of group 0 (a view into a larger buffer moves it); wts: GemmWeights, the launch's W starts w_off elements into it.
     x6 / x3h: attach the bf16 / fp16 planes - the fp16 strides come from x3h_group_planes, i.e. from the model's own rule (no planes
     when it says so); wh_gstride overrides its group stride (rejection tests).  flag: device int32 range-guard word.  Writes `out`
-    in place and returns the configuration index the routing chose."""
+    in place and returns the configuration index the routing chose.  ks_epi4: the option of that name for this launch; want_epi4: return
+    (configuration, 1 when the launch finished its tiles with 16-byte loads and stores) instead."""
     lib = load_library()
     d = MT2GemmDesc()
     d.struct_bytes = C.sizeof(MT2GemmDesc)
@@ -1671,10 +1674,11 @@ def op_gemm_grouped(X, wts, out, *, M, N, Cin, ldx, Rx, ldw, ldc, groups=1, stri
     d.pro_act, d.pro_slope, d.epi_act, d.out_scale = pro_act, pro_slope, epi_act, out_scale
     d.force_cfg = force_cfg
     d.range_flag = flag.data_ptr() if flag is not None else None
-    cfg = C.c_int32(-1)
+    cfg, epi4 = C.c_int32(-1), C.c_int32(0)
     d.cfg_out = C.pointer(cfg)
+    d.ks_epi4, d.epi4_out = ks_epi4, C.pointer(epi4)
     _check(lib.mt2_op_gemm_grouped(_stream(), C.byref(d)))
-    return cfg.value
+    return (cfg.value, epi4.value) if want_epi4 else cfg.value
 
 
 def op_attention(Q, K, V, q_start, q_len, kv_start, kv_len, H, D, scale, lds_min_qlen=-1, lds_waves=0, out=None, x6_min_qlen=-1):
@@ -1774,6 +1778,15 @@ def op_gemm_route(M, N, K, taps=1, dil=1, groups=1, pro_act=ACT_NONE, operands=0
     """mt2_gemm_route (no device needed) -> (hipError_t, config index, variant, LDS bytes, planes bits) of the launch launch_gemm would make."""
     out = [C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_int(0)]
     _check(load_library().mt2_gemm_route(M, N, K, taps, dil, groups, pro_act, operands, misaligned, force_cfg, x3h, *map(C.byref, out)))
+    return tuple(v.value for v in out)
+
+
+def op_gemm_route_ex(M, N, K, taps=1, dil=1, groups=1, pro_act=ACT_NONE, operands=0, misaligned=0, force_cfg=-1, x3h=15, ld_pad=0, ks_epi4=1):
+    """mt2_gemm_route_ex (no device needed): op_gemm_route with ldc = ldr = N + ld_pad and the option ks_epi4 -> its tuple + (1 when an
+    x3h K-split tile would finish the launch with 16-byte loads and stores,)."""
+    out = [C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_int(0), C.c_int(0)]
+    _check(load_library().mt2_gemm_route_ex(M, N, K, taps, dil, groups, pro_act, operands, misaligned, force_cfg, x3h, ld_pad, ks_epi4,
+                                            *map(C.byref, out)))
     return tuple(v.value for v in out)
 
 

@@ -52,6 +52,10 @@ def main() -> None:
                          "GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
     ap.add_argument("--report-loudness", action="store_true",
                     help="print integrated LUFS, sample peak in dBFS and block counts (measured on the GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
+    ap.add_argument("--reference-wav", metavar="PATH",
+                    help="a recording of the same sentence: print the mel-cepstral distortion (dB, along the DTW path of the cepstra), the largest "
+                         "cell, and F0 RMSE, register offset and voiced / unvoiced error along the same path, of the generated audio against it")
+    ap.add_argument("--mcd-order", type=int, default=13, metavar="K", help="with --reference-wav: cepstral coefficients c1 .. cK compared (default 13)")
     ap.add_argument("--text")
     ap.add_argument("--phones", help="comma separated phone token ids (bypasses the G2P)")
     ap.add_argument("--out", default="test.wav")
@@ -119,6 +123,18 @@ def main() -> None:
             y, sr = audio_io.read_wav(path)
             st = M.pitch_stats(M.extract_f0(y, sr, trim_db=trim_db, method=a.pitch_tracker))
             print(f"pitch of the {what} ({path}): " + ", ".join(f"{k} {float(v[0]):.4g}" for k, v in st.items()))
+    if a.reference_wav:
+        from megatts2_amd import audio_io
+        if not wrote:
+            print("no distortion against --reference-wav: no vocoder produced audio to compare (--vocoder griffin-lim needs no weights)")
+        else:              # the generated audio alone, as the vocoder left it on the device - not the written file (prompt in front)
+            n = (int(lens[0]) - 1) * C.HIFIGAN_HOP_LENGTH if gl is not None else (int(lens[0]) + 2 * tts.hifi_gan.cfg.inference_padding) * tts.hifi_gan.cfg.hop
+            y, sr = audio_io.read_wav(a.reference_wav)
+            st = M.compare_audio(aux["wav"][0, :n], y, (C.HIFIGAN_SR, sr), tracker=a.pitch_tracker, order=a.mcd_order, trim_db=a.trim_db)
+            print(f"generated audio against {a.reference_wav}: MCD {float(st['mcd_db'][0]):.3f} dB over {int(st['cells'][0])} DTW cells of c1 .. c{a.mcd_order} "
+                  f"(a DCT of the 80-bin log-mel: comparable with itself only), largest cell {float(st['max_db'][0]):.3f} dB; F0 RMSE "
+                  f"{float(st['f0_rmse_cents'][0]):.1f} cents and register offset {float(st['f0_offset_cents'][0]):+.1f} cents over "
+                  f"{int(st['voiced_cells'][0])} cells voiced on both sides, voiced / unvoiced error {100.0 * float(st['vuv_error'][0]):.2f} %")
     if a.report_prosody:
         import glob
         import math

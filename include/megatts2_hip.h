@@ -339,6 +339,61 @@ int mt2_align_durations(mt2_model* m, void* stream, const int32_t* hi, const int
                         const int32_t* syn_dur /*host*/, const int32_t* phone_lens /*host*/, int Np_max, int B,
                         int32_t* dur_out_host);
 
+/* ---- Mel-cepstral distortion along the DTW path (csrc/mcd.hip): how far one log-mel is from another of the same sentence, in dB, with
+ * the F0 error and the voicing error along the SAME path - the spectral leg beside the pitch, prosody, rhythm and level measures.  No
+ * counterpart in the reference.  This cepstrum is a DCT of an N-bin log-mel, NOT a mel-generalised cepstrum of a spectral envelope:
+ * parity with SPTK / WORLD or with the ESPnet / Coqui MCD scripts is unpinned (none is on hand and they differ among themselves), and
+ * the figures are comparable only with themselves.  The rule is our own, held to its float64 restatement tests/mcd_ref.py.  THE RULE,
+ * for one pair A f32 [Ta, N], B f32 [Tb, N] of natural-log mels (as mt2_mel_spectrogram writes them), optionally f0_a f32 [Ta] and f0_b
+ * f32 [Tb] frame-aligned to them;  N = n_mels in [2, 128], order K in [1, min(N - 1, MT2_MCD_MAX_ORDER)], 13 by convention:
+ *  1 Table.  tab[k-1][m] = cos(pi (m + 1/2) k / N) / N, k = 1 .. K, m = 0 .. N-1, in double, rounded once to f32.  Under this scaling
+ *    logmel[m] = c0 + 2 sum_k c_k cos(pi (m + 1/2) k / N), the convention under which (10 / ln 10) sqrt 2 turns cepstral differences
+ *    into the RMS dB difference of the K-term-smoothed spectra.  c0, the level, is left out: a gain change is not distortion.
+ *  2 Cepstrum.  c[t][k-1] = sum_m M[t][m] tab[k-1][m] in f32 as ONE fma chain over m ascending from 0; never split across lanes, no
+ *    atomics.
+ *  3 Warp.  The DTW rule above, unchanged, with X = the cepstra of A, Y = those of B, D = K: lo, hi, steps.  The path's cells are
+ *    (i, j), lo[j] <= i <= hi[j], j < Tb.
+ *  4 Per cell.  q = sum_k (ca[i][k] - cb[j][k])^2, exactly the DTW's cost chain;  dB(i, j) = (10 / ln 10) sqrt(2 (double) q) in double.
+ *  5 F0 along the path, only when both tracks are given.  A frame is voiced iff f0 > 0 (a NaN is not).  On a cell voiced on both
+ *    sides D = 1200 log2((double) f0_a[i] / (double) f0_b[j]) cents;  a cell voiced on exactly one side is a voicing error.
+ *  6 Sums, in double, in an order that depends on the frame index in the utterance alone: one workgroup of 256 threads per utterance,
+ *    thread t takes the columns j = t, t + 256, ... ascending and in a column i ascending, one add per term;  the 256 partial sums meet
+ *    in a fixed tree (stride 128 .. 1), the maximum likewise.  A ragged batch is bit-identical to its utterances alone, whatever the
+ *    slot and the padded lengths.
+ *  7 Row of MT2_MCD_FIELDS = 8 doubles:  0 cells (= steps)   1 MCD = mean of dB over the cells   2 largest cell dB   3 cells voiced
+ *    on both sides   4 sqrt(mean D^2) in cents over those (0 if field 3 is 0)   5 mean D in cents, signed: the register offset
+ *    6 cells voiced on exactly one side   7 field 6 / field 0.  Fields 3-7 are 0 without F0 tracks.
+ * A non-finite input cannot fault, write outside the outputs or change another utterance's row;  nothing more is promised for its own.
+ * Refused, on the host before the first HIP call, every output as it was - never a clamp:  B outside [1, 65535];  N or K outside their
+ * ranges;  a length outside [1, its max];  a max over MT2_DTW_MAX_LEN;  one F0 track without the other;  overlapping buffers.
+ * `m` may be a bare handle;  scratch comes from its arena;  the table is built and uploaded once per (N, K) and handle.  Every call only
+ * enqueues. */
+#define MT2_MCD_FIELDS 8
+#define MT2_MCD_MAX_ORDER 32
+/* the table f32 [order][n_mels] of rule 1;  host only, no HIP call */
+int mt2_mcd_table(int n_mels, int order, float* table /*host [order][n_mels]*/);
+/* Arena bytes of one mt2_mel_cepstral_distortion call of this geometry - exactly its high water;  host only, no HIP call.  With r(n) =
+ * max(256, n rounded up to 256):  r(4 (4 ceil(B / 4) + B))  both lengths  +  the skewed costs and the packed directions that
+ * mt2_dtw_query states for (Ta_max, Tb_max)  +  r(4 B Ta_max K) + r(4 B Tb_max K)  the cepstra  +  2 r(4 B Tb_max)  lo and hi
+ * +  2 r(4 B)  steps and total. */
+int mt2_mcd_query(int Ta_max, int Tb_max, int n_mels, int order, int B, long long* workspace_bytes);
+/* Rule 2 for a ragged batch:  mel f32 [B, T_max, n_mels] (device; rows at or beyond frame_lens[b] are never read), frame_lens host
+ * int32 [B] -> cep f32 [B, T_max, order] (device), zeros in the rows at or beyond frame_lens[b]. */
+int mt2_mel_cepstrum(mt2_model* m, void* stream, const float* mel /*[B, T_max, n_mels]*/, const int32_t* frame_lens /*host*/, int T_max,
+                     int B, int n_mels, int order, float* cep /*[B, T_max, order]*/);
+/* Rules 4-7 on a path the caller supplies:  ca f32 [B, Ta_max, order], cb f32 [B, Tb_max, order], lo, hi int32 [B, Tb_max] (device, as
+ * mt2_dtw_align leaves them;  whatever they hold, a column's run is cut to the rows [0, a_lens[b]) and only the columns below b_lens[b]
+ * are walked), f0_a f32 [B, Ta_max] and f0_b f32 [B, Tb_max] (device; both or neither) -> out f64 [B, 8] (device). */
+int mt2_path_distortion(mt2_model* m, void* stream, const float* ca, const int32_t* a_lens /*host*/, int Ta_max, const float* cb,
+                        const int32_t* b_lens /*host*/, int Tb_max, int order, int B, const int32_t* lo, const int32_t* hi,
+                        const float* f0_a /*or NULL*/, const float* f0_b /*or NULL*/, double* out /*f64 [B, 8]*/);
+/* The whole chain in one call on the arena: both cepstra, the DTW on them, the path reduction.  mel_a f32 [B, Ta_max, n_mels], mel_b f32
+ * [B, Tb_max, n_mels] (device) -> out f64 [B, 8] and, on request, the path lo, hi int32 [B, Tb_max] (device; -1 at or beyond b_lens[b]). */
+int mt2_mel_cepstral_distortion(mt2_model* m, void* stream, const float* mel_a, const int32_t* a_lens /*host*/, int Ta_max,
+                                const float* mel_b, const int32_t* b_lens /*host*/, int Tb_max, int n_mels, int order, int B,
+                                const float* f0_a /*or NULL*/, const float* f0_b /*or NULL*/, double* out /*f64 [B, 8]*/,
+                                int32_t* lo /*or NULL*/, int32_t* hi /*or NULL*/);
+
 /* ---- Griffin-Lim vocoder (csrc/griffinlim.hip): log-mel -> audio with no weights, the fallback behind mt2_hifigan (whose weights are a
  * third-party hub model) and a debugging aid - intelligible but buzzy, not a replacement.  No counterpart in the reference; parity with
  * librosa.griffinlim / torchaudio.transforms.GriffinLim is unpinned, the rule is our own, held to tests/griffinlim_ref.py.  With the

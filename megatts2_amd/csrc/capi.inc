@@ -1111,6 +1111,58 @@ int mt2_align_durations(mt2_model* m, void* stream, const int32_t* hi, const int
     MT2_API_END
 }
 
+// mel-cepstral distortion along the DTW path (mcd.hip): the table and the arena bytes of the whole chain, without a HIP call
+int mt2_mcd_table(int n_mels, int order, float* table) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(mcd_geometry_ok(n_mels, order), "n_mels outside [2, 128] or order outside [1, min(n_mels - 1, MT2_MCD_MAX_ORDER)]");
+    MT2_REQUIRE(table != nullptr, "null table");
+    mcd_table(n_mels, order, table);
+    MT2_API_END
+}
+
+int mt2_mcd_query(int Ta_max, int Tb_max, int n_mels, int order, int B, long long* workspace_bytes) {
+    MT2_API_BEGIN
+    mcd_check_order(n_mels, order, B);
+    mcd_check_max(Ta_max, "Ta_max outside [1, MT2_DTW_MAX_LEN]");
+    mcd_check_max(Tb_max, "Tb_max outside [1, MT2_DTW_MAX_LEN]");
+    if (workspace_bytes) *workspace_bytes = mcd_arena_bytes(Ta_max, Tb_max, order, B);
+    MT2_API_END
+}
+
+// every refusal of the three calls is decided on the host before the first HIP call
+int mt2_mel_cepstrum(mt2_model* m, void* stream, const float* mel, const int32_t* frame_lens, int T_max, int B, int n_mels, int order,
+                     float* cep) {
+    MT2_API_BEGIN
+    mel_cepstrum_check(mel, frame_lens, T_max, B, n_mels, order, cep);
+    MT2_AUDIO_CALL(m, stream);
+    mel_cepstrum_run(c, mel, frame_lens, T_max, B, n_mels, order, cep);
+    MT2_API_END
+}
+
+int mt2_path_distortion(mt2_model* m, void* stream, const float* ca, const int32_t* a_lens, int Ta_max, const float* cb,
+                        const int32_t* b_lens, int Tb_max, int order, int B, const int32_t* lo, const int32_t* hi, const float* f0_a,
+                        const float* f0_b, double* out) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(order >= 1 && order <= MT2_MCD_MAX_ORDER, "order outside [1, MT2_MCD_MAX_ORDER]");
+    MT2_REQUIRE(lo != nullptr && hi != nullptr, "null lo / hi");
+    mcd_check_pair(ca, a_lens, Ta_max, cb, b_lens, Tb_max, order, B, lo, hi, false, f0_a, f0_b, out);
+    MT2_AUDIO_CALL(m, stream);
+    path_distortion_run(c, ca, a_lens, Ta_max, cb, b_lens, Tb_max, order, B, lo, hi, f0_a, f0_b, out);
+    MT2_API_END
+}
+
+int mt2_mel_cepstral_distortion(mt2_model* m, void* stream, const float* mel_a, const int32_t* a_lens, int Ta_max, const float* mel_b,
+                                const int32_t* b_lens, int Tb_max, int n_mels, int order, int B, const float* f0_a, const float* f0_b,
+                                double* out, int32_t* lo, int32_t* hi) {
+    MT2_API_BEGIN
+    mcd_check_order(n_mels, order, B);
+    mcd_check_pair(mel_a, a_lens, Ta_max, mel_b, b_lens, Tb_max, n_mels, B, lo, hi, true, f0_a, f0_b, out);
+    MT2_AUDIO_CALL(m, stream);
+    mcd_run(c, mel_a, a_lens, Ta_max, mel_b, b_lens, Tb_max, n_mels, order, B, f0_a, f0_b, out, lo, hi);
+    MT2_API_END
+}
+
 // :361-368 [+370]  zq = vq.decode(p_codes) repeated x8, cat([tc_latent_expand, zq]), decoder, optional vocoder - the part of
 // Megatts.forward behind the PLM, shared by mt2_synthesize_batch and mt2_synthesize_prompt_conditioned.  xdec: [D.R, H + Dq]
 // rows whose first H columns already hold the length-regulated tc_latents.

@@ -2666,6 +2666,16 @@ static long long dtw_arena_bytes(int Tx_max, int Ty_max, int B) {
     return (long long)count.bytes;
 }
 
+// the three kernels of the DTW rule on p, each under its mark (dtw_run; mcd_run on the cepstra)
+static void dtw_launches(const Ctx& c, const DtwP& p, Stages& st) {
+    MT2_HIP(launch_dtw_cost(p, c.s));
+    st.mark("dtw_cost");
+    MT2_HIP(launch_dtw_accumulate(p, c.s));
+    st.mark("dtw_accumulate");
+    MT2_HIP(launch_dtw_backtrack(p, c.s));
+    st.mark("dtw_backtrack");
+}
+
 // DTW of X onto Y by the rule of dtw.hip: cost -> accumulate -> backtrack on the caller's stream, nothing else
 static void dtw_run(const Ctx& c, const float* X, const int* x_lens, int Tx_max, const float* Y, const int* y_lens, int Ty_max, int D,
                     int B, int* lo, int* hi, int* steps, float* total, float* cost, float* acc) {
@@ -2684,12 +2694,7 @@ static void dtw_run(const Ctx& c, const float* X, const int* x_lens, int Tx_max,
     p.acc = acc; p.lo = lo; p.hi = hi; p.steps = steps; p.total = total;
     Stages st(c.m, c.s);
     st.mark("start");
-    MT2_HIP(launch_dtw_cost(p, c.s));
-    st.mark("dtw_cost");
-    MT2_HIP(launch_dtw_accumulate(p, c.s));
-    st.mark("dtw_accumulate");
-    MT2_HIP(launch_dtw_backtrack(p, c.s));
-    st.mark("dtw_backtrack");
+    dtw_launches(c, p, st);
     st.finish();
 }
 
@@ -2730,6 +2735,126 @@ static void align_durations_run(const Ctx& c, const int* hi, const int* y_lens, 
         MT2_REQUIRE(tx == last + 1, "synthetic durations do not sum to the x length of the path (hi[Ty - 1] + 1)");
     }
     std::copy(st, st + (size_t)B * Np_max, dur_out_host);
+}
+
+// ---- mel-cepstral distortion along the DTW path (mcd.hip): every refusal is decided here, on the host, before the first HIP call
+static void mcd_check_order(int n_mels, int order, int B) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(mcd_geometry_ok(n_mels, order), "n_mels outside [2, 128] or order outside [1, min(n_mels - 1, MT2_MCD_MAX_ORDER)]");
+}
+static void mcd_check_max(int T_max, const char* msg) { MT2_REQUIRE(T_max >= 1 && T_max <= MT2_DTW_MAX_LEN, msg); }
+static void mel_cepstrum_check(const float* mel, const int* frame_lens, int T_max, int B, int n_mels, int order, const float* cep) {
+    mcd_check_order(n_mels, order, B);
+    mcd_check_max(T_max, "T_max outside [1, MT2_DTW_MAX_LEN]");
+    MT2_REQUIRE(mel != nullptr && frame_lens != nullptr && cep != nullptr, "bad buffers");
+    MT2_REQUIRE((((uintptr_t)mel | (uintptr_t)cep) & 3) == 0, "misaligned buffers");
+    check_lens(frame_lens, B, T_max, "frame count outside [1, T_max]");
+    const size_t nt = sizeof(float) * (size_t)B * T_max;
+    MT2_REQUIRE(!outputs_overlap({{cep, nt * order}}, {{mel, nt * n_mels}}), "overlapping buffers");
+}
+// the path reduction's arguments: the cepstra of width `order` (or, in the whole chain, the mels of width n_mels: `width`)
+static void mcd_check_pair(const float* a, const int* a_lens, int Ta_max, const float* b, const int* b_lens, int Tb_max, int width, int B,
+                           const int* lo, const int* hi, bool lo_hi_out, const float* f0_a, const float* f0_b, const double* out) {
+    mcd_check_max(Ta_max, "Ta_max outside [1, MT2_DTW_MAX_LEN]");
+    mcd_check_max(Tb_max, "Tb_max outside [1, MT2_DTW_MAX_LEN]");
+    MT2_REQUIRE(a != nullptr && b != nullptr && a_lens != nullptr && b_lens != nullptr && out != nullptr, "bad buffers");
+    MT2_REQUIRE((f0_a == nullptr) == (f0_b == nullptr), "one F0 track given without the other");
+    MT2_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)lo | (uintptr_t)hi | (uintptr_t)f0_a | (uintptr_t)f0_b) & 3) == 0 &&
+                    ((uintptr_t)out & 7) == 0, "misaligned buffers");
+    check_lens(a_lens, B, Ta_max, "a length outside [1, Ta_max]");
+    check_lens(b_lens, B, Tb_max, "b length outside [1, Tb_max]");
+    const size_t na = sizeof(float) * (size_t)B * Ta_max, nb = sizeof(float) * (size_t)B * Tb_max, no = sizeof(double) * MT2_MCD_FIELDS * (size_t)B;
+    if (lo_hi_out)
+        MT2_REQUIRE(!outputs_overlap({{out, no}, {lo, nb}, {hi, nb}}, {{a, na * width}, {b, nb * width}, {f0_a, na}, {f0_b, nb}}), "overlapping buffers");
+    else
+        MT2_REQUIRE(!outputs_overlap({{out, no}}, {{a, na * width}, {b, nb * width}, {lo, nb}, {hi, nb}, {f0_a, na}, {f0_b, nb}}), "overlapping buffers");
+}
+static const float* mcd_prepare(mt2_model& m, int n_mels, int order) {
+    float*& d = m.mcd_tables[{n_mels, order}];
+    if (d) return d;
+    std::vector<float> h((size_t)n_mels * order);
+    mcd_table(n_mels, order, h.data());
+    float* t = nullptr;
+    MT2_HIP(hipMalloc(reinterpret_cast<void**>(&t), h.size() * sizeof(float)));
+    m.dev_allocs.push_back(t);
+    MT2_HIP(hipMemcpy(t, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return d = t;
+}
+static void mcd_cepstrum_launch(const Ctx& c, const float* table, const float* mel, const int* len_dev, int T_max, int B, int n_mels, int order,
+                                float* cep) {
+    McdCepP p{};
+    p.mel = mel; p.T_max = T_max; p.N = n_mels; p.K = order; p.B = B; p.len = len_dev; p.table = table; p.cep = cep;
+    MT2_HIP(launch_mcd_cepstrum(p, c.s));
+}
+static void mel_cepstrum_run(const Ctx& c, const float* mel, const int* frame_lens, int T_max, int B, int n_mels, int order, float* cep) {
+    const float* table = mcd_prepare(c.m, n_mels, order);
+    IntPlan ip;
+    const int o_t = ip.add(frame_lens, B);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    mcd_cepstrum_launch(c, table, mel, ip.dev(o_t), T_max, B, n_mels, order, cep);
+}
+static void mcd_path_launch(const Ctx& c, const float* ca, const int* a_dev, int Ta_max, const float* cb, const int* b_dev, int Tb_max, int order,
+                            int B, const int* lo, const int* hi, const float* f0_a, const float* f0_b, double* out) {
+    McdPathP p{};
+    p.ca = ca; p.Ta_max = Ta_max; p.cb = cb; p.Tb_max = Tb_max; p.K = order; p.B = B; p.a_len = a_dev; p.b_len = b_dev;
+    p.lo = lo; p.hi = hi; p.f0_a = f0_a; p.f0_b = f0_b; p.out = out;
+    MT2_HIP(launch_mcd_path(p, c.s));
+}
+static void path_distortion_run(const Ctx& c, const float* ca, const int* a_lens, int Ta_max, const float* cb, const int* b_lens, int Tb_max,
+                                int order, int B, const int* lo, const int* hi, const float* f0_a, const float* f0_b, double* out) {
+    IntPlan ip;
+    const int o_a = ip.add(a_lens, B), o_b = ip.add(b_lens, B);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    mcd_path_launch(c, ca, ip.dev(o_a), Ta_max, cb, ip.dev(o_b), Tb_max, order, B, lo, hi, f0_a, f0_b, out);
+}
+// the arena of one mcd_run, in carve order: what a DTW of this geometry takes (the plan with both lengths, the skewed costs, the packed
+// directions), the two cepstra, the path (lo | hi) and the DTW's steps and total - taken whether or not the caller asks for lo / hi
+struct McdWs { DtwWs dtw; float *ca, *cb; int *lo, *hi, *steps; float* total; };
+template <class Ws> static McdWs mcd_carve(Ws& ws, IntPlan& ip, size_t Ta_max, int Tb_max, size_t order, size_t B) {
+    McdWs w{};
+    w.dtw = dtw_carve(ws, ip, Ta_max, Tb_max, B);
+    w.ca = ws.template get<float>(B * Ta_max * order);
+    w.cb = ws.template get<float>(B * Tb_max * order);
+    w.lo = ws.template get<int>(B * Tb_max);
+    w.hi = ws.template get<int>(B * Tb_max);
+    w.steps = ws.template get<int>(B);
+    w.total = ws.template get<float>(B);
+    return w;
+}
+static long long mcd_arena_bytes(int Ta_max, int Tb_max, int order, int B) {
+    IntPlan ip;
+    ip.add_fill(B, 0);
+    ip.add_fill(B, 0);
+    ArenaCount count;
+    mcd_carve(count, ip, Ta_max, Tb_max, order, B);
+    return (long long)count.bytes;
+}
+// the whole chain on the arena: two cepstra, the DTW of dtw.hip on them, the path reduction.  Enqueues only.
+static void mcd_run(const Ctx& c, const float* mel_a, const int* a_lens, int Ta_max, const float* mel_b, const int* b_lens, int Tb_max,
+                    int n_mels, int order, int B, const float* f0_a, const float* f0_b, double* out, int* lo, int* hi) {
+    const float* table = mcd_prepare(c.m, n_mels, order);
+    IntPlan ip;
+    const int o_a = ip.add(a_lens, B), o_b = ip.add(b_lens, B);
+    const McdWs w = mcd_carve(c.ws, ip, Ta_max, Tb_max, order, B);
+    ip.send(c.m.pinned(), c.s);
+    Stages st(c.m, c.s);
+    st.mark("start");
+    mcd_cepstrum_launch(c, table, mel_a, ip.dev(o_a), Ta_max, B, n_mels, order, w.ca);
+    mcd_cepstrum_launch(c, table, mel_b, ip.dev(o_b), Tb_max, B, n_mels, order, w.cb);
+    st.mark("mcd_cepstrum");
+    DtwP p{};
+    p.X = w.ca; p.Tx_max = Ta_max; p.Y = w.cb; p.Ty_max = Tb_max; p.D = order; p.B = B;
+    p.max_tx = *std::max_element(a_lens, a_lens + B); p.max_ty = *std::max_element(b_lens, b_lens + B);
+    p.x_len = ip.dev(o_a); p.y_len = ip.dev(o_b);
+    p.S_max = (Ta_max + 63) / 64; p.TS = (int)dtw_skew_steps(Tb_max); p.skew = w.dtw.skew;
+    p.DW = (int)dtw_dir_words(Tb_max); p.dirs = w.dtw.dirs;
+    p.lo = w.lo; p.hi = w.hi; p.steps = w.steps; p.total = w.total;
+    dtw_launches(c, p, st);
+    mcd_path_launch(c, w.ca, ip.dev(o_a), Ta_max, w.cb, ip.dev(o_b), Tb_max, order, B, w.lo, w.hi, f0_a, f0_b, out);
+    if (lo) MT2_HIP(hipMemcpyAsync(lo, w.lo, sizeof(int) * (size_t)B * Tb_max, hipMemcpyDeviceToDevice, c.s));
+    if (hi) MT2_HIP(hipMemcpyAsync(hi, w.hi, sizeof(int) * (size_t)B * Tb_max, hipMemcpyDeviceToDevice, c.s));
+    st.mark("mcd_path");
+    st.finish();
 }
 
 }  // namespace mt2

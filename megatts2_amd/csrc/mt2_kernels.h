@@ -501,6 +501,31 @@ struct AlignDurP {
 };
 hipError_t launch_dtw_durations(const AlignDurP& p, hipStream_t s);
 
+// ---- mel-cepstral distortion along a DTW path (mcd.hip; the rule is in its header and in megatts2_hip.h) ----------------------------
+// host only, no HIP call: n_mels in [2, 128] and order in [1, min(n_mels - 1, MT2_MCD_MAX_ORDER)];  tab[k-1][m] = cos(pi (m + 1/2) k / N) / N
+bool mcd_geometry_ok(int n_mels, int order);
+void mcd_table(int n_mels, int order, float* table);
+// cep[b, t, k-1] = sum_m mel[b, t, m] table[k-1][m], one f32 fma chain over m ascending; zeros for t in [len[b], T_max)
+struct McdCepP {
+    const float* mel; int T_max, N;           // [B, T_max, N]; rows at or beyond len[b] are never read
+    int K, B;
+    const int* len;                           // device [B]
+    const float* table;                       // device [K][N]: mcd_table
+    float* cep;                               // [B, T_max, K]
+};
+hipError_t launch_mcd_cepstrum(const McdCepP& p, hipStream_t s);
+// the path's row of MT2_MCD_FIELDS doubles, one workgroup per utterance
+struct McdPathP {
+    const float* ca; int Ta_max;              // [B, Ta_max, K]
+    const float* cb; int Tb_max;              // [B, Tb_max, K]
+    int K, B;
+    const int* a_len; const int* b_len;       // device [B]
+    const int* lo; const int* hi;             // [B, Tb_max], as launch_dtw_backtrack left them
+    const float* f0_a; const float* f0_b;     // optional [B, Ta_max], [B, Tb_max]: both or neither
+    double* out;                              // [B, MT2_MCD_FIELDS]
+};
+hipError_t launch_mcd_path(const McdPathP& p, hipStream_t s);
+
 // ---- Griffin-Lim vocoder (griffinlim.hip; the rule is in its header and in megatts2_hip.h) -------------------------------------------
 // Frames of a ragged batch are packed rows: utterance b owns rows row0[b] .. row0[b] + T[b] of S / R / Rprev ([rows, lds]: re(0..F-1) |
 // im(0..F-1) | zero pad, lds = 2F rounded up to 4), of A ([rows, lda]) and of the inverse-DFT GEMM's frames ([rows, N]).

@@ -248,6 +248,8 @@ struct mt2_model {
     double loud_M[16] = {};
     // resampler filter tables, tap-major, by reduced ratio (o, n) = (sr_in, sr_out) / gcd: built and uploaded on first use
     std::map<std::pair<int, int>, float*> rs_tables;
+    // mel-cepstrum tables (mcd.hip) by (n_mels, order): built and uploaded on first use
+    std::map<std::pair<int, int>, float*> mcd_tables;
 
     bool profiling = false;
     std::vector<std::string> stage_names;

@@ -253,6 +253,62 @@ def pitch_distance(f0_a, f0_b, lens_a=None, lens_b=None, center: bool = True) ->
     return res
 
 
+def _mcd_dict(row) -> Dict[str, np.ndarray]:
+    from .runtime import MCD_NAMES
+    row = row.cpu().numpy()
+    return {k: row[:, i].copy() for i, k in enumerate(MCD_NAMES)}
+
+
+def mel_cepstral_distortion(mel_a, mel_b, lens_a=None, lens_b=None, f0_a=None, f0_b=None, order: int = 13) -> Dict[str, np.ndarray]:
+    """Mel-cepstral distortion along the DTW path, on the GPU by the rule of csrc/mcd.hip (MelFrontEnd.mcd): mel_a [Ta, N] or
+    [B, Ta, N] against mel_b [Tb, N] or [B, Tb, N], natural-log mels, TIME-major (extract_mel_spec(...).transpose(-1, -2)) -> dict of
+    float64 numpy arrays [B]: cells (the path's length), mcd_db (the mean over the path of (10 / ln 10) sqrt(2 sum_k (c_k - c'_k)^2),
+    k = 1 .. order; the level c0 is left out, so a gain change reads 0), max_db, and with F0 tracks f0_a [Ta] / f0_b [Tb] (Hz, 0 =
+    unvoiced, frame-aligned to the mels as extract_f0 is to extract_mel_spec) along the SAME path: voiced_cells, f0_rmse_cents,
+    f0_offset_cents (mean of 1200 log2(f0_a / f0_b): the register offset), vuv_cells and vuv_error (cells voiced on exactly one side,
+    and their share).  The cepstrum is a DCT of the N-bin log-mel, not a mel-generalised cepstrum of a spectral envelope: the figures
+    are comparable with themselves only, parity with SPTK / WORLD / ESPnet / Coqui MCD is unpinned."""
+    import torch
+
+    def dev(a, dims):
+        a = a if hasattr(a, "is_cuda") else torch.as_tensor(np.asarray(a, np.float32))
+        return (a if a.dim() == dims else a.unsqueeze(0)).to("cuda", torch.float32)
+
+    fa = None if f0_a is None else dev(f0_a, 2)
+    fb = None if f0_b is None else dev(f0_b, 2)
+    return _mcd_dict(_frontend().mcd(dev(mel_a, 3), dev(mel_b, 3), lens_a, lens_b, fa, fb, order=order))
+
+
+def compare_audio(wav_a, wav_b, sample_rate: Optional[int] = None, tracker: str = "yin", order: int = 13,
+                  trim_db: Optional[float] = None) -> Dict[str, np.ndarray]:
+    """The objective distance of two recordings of one sentence (1-D waveforms, e.g. generated audio and a reference recording):
+    both are resampled from sample_rate (one rate, or a pair (rate_a, rate_b)) to 16 kHz where needed and optionally trimmed
+    (trim_db), their mels and F0 tracks
+    (tracker "yin" or "viterbi") are made by one front end, frame-aligned, and mel_cepstral_distortion compares a against b ->
+    its dict (arrays [1])."""
+    import torch
+    if tracker not in ("yin", "viterbi"):
+        raise ValueError("tracker must be 'yin' or 'viterbi'")
+    fe = _frontend()
+    mels, f0s = [], []
+    rates = tuple(sample_rate) if isinstance(sample_rate, (tuple, list)) else (sample_rate, sample_rate)
+    for w, sr in zip((wav_a, wav_b), rates):
+        x = w if hasattr(w, "is_cuda") else torch.as_tensor(np.asarray(w, np.float32))
+        assert x.dim() == 1, "compare_audio takes two 1-D waveforms"
+        x = x.unsqueeze(0).to("cuda", torch.float32)
+        if sr is not None and int(sr) != fe.audio.sample_rate:
+            x = fe.resample(x, int(sr))[0]
+        lens = None
+        if trim_db is not None:
+            x, lens, _ = fe.trim(x, top_db=trim_db)
+        mel = fe(x, lens)
+        f0 = (fe.f0 if tracker == "yin" else fe.f0_track)(x, lens)
+        T = mel.shape[1] if lens is None else 1 + int(lens[0]) // fe.audio.hop_length
+        mels.append(mel[:, :T])
+        f0s.append(f0[:, :T])
+    return _mcd_dict(fe.mcd(mels[0], mels[1], None, None, f0s[0], f0s[1], order=order))
+
+
 class LengthRegulator:
     """reference modules/mrte.py:34-60 (FastSpeech length regulator) as a device gather."""
 
@@ -668,7 +724,10 @@ class Megatts:
         on the prompt's own phones under the prompt's own timbre (greedy PLM, no vocoder: the ADM's durations and a synthetic mel);
         `dtw` of that mel onto `mels` (csrc/dtw.hip); `align_durations`, which gives real frame j to the phone that owns the
         synthetic frame hi[j].  Always greedy, so the alignment is deterministic.  return_aux: (durations, dict) with the synthetic
-        durations `syn_dur` (host int32 [B, Npp]), `syn_lens`, and the path's lo, hi, steps, total (device).  Both lengths of the
+        durations `syn_dur` (host int32 [B, Npp]), `syn_lens`, the path's lo, hi, steps, total (device), and `mcd`, the dict of
+        mel_cepstral_distortion for the re-synthesis against the real prompt along the warp of their cepstra (`mcd_lo`, `mcd_hi`,
+        device) - the one number that says whether the alignment is any good; the durations come from the 80-bin warp as
+        before, and without return_aux nothing of this runs.  Both lengths of the
         warp are capped at runtime.DTW_MAX_LEN = 4096 frames (MT2_DTW_MAX_LEN): a prompt longer than that, or a synthesis of it that
         comes out longer (the ADM may give a phone up to 128 frames - untrained durations on many phones), is refused with a
         NativeError from mt2_dtw_align, never clamped.  Alignment quality on real speech is unpinned: there is no aligner here to
@@ -685,6 +744,9 @@ class Megatts:
         if not return_aux:
             return dur
         path.update(syn_dur=syn_dur, syn_lens=syn_lens)
+        # how good the alignment is: the distortion of the re-synthesis against the real prompt along the warp of their cepstra
+        row, lo, hi = nat.mcd(syn[:, :max(int(syn_lens.max()), 1)], mels, syn_lens, ml, return_path=True)
+        path.update(mcd=_mcd_dict(row), mcd_lo=lo, mcd_hi=hi)
         return dur, path
 
     def synthesize_prompt_conditioned(self, phone_tokens, mels, prompt_phone_tokens, prompt_durations=None, phone_lens=None,

@@ -28,6 +28,8 @@ TRIM_FRAME, TRIM_HOP = 2048, 512      # MT2_TRIM_FRAME, MT2_TRIM_HOP
 F0_FRAME, F0_WINDOW, F0_MAX_LAG = 1024, 768, 256      # MT2_F0_FRAME, MT2_F0_WINDOW, MT2_F0_MAX_LAG
 DTW_MAX_LEN, DTW_DIR_COLS = 4096, 16  # MT2_DTW_MAX_LEN, MT2_DTW_DIR_COLS
 PROSODY_FIELDS = 8                    # MT2_PROSODY_FIELDS
+MCD_FIELDS, MCD_MAX_ORDER = 8, 32     # MT2_MCD_FIELDS, MT2_MCD_MAX_ORDER
+MCD_NAMES = ("cells", "mcd_db", "max_db", "voiced_cells", "f0_rmse_cents", "f0_offset_cents", "vuv_cells", "vuv_error")
 LOUDNESS_FIELDS = 8                   # MT2_LOUDNESS_FIELDS
 EBU_FIELDS, TP_ZERO_CROSSINGS, TP_TAPS, TP_TILE = 18, 12, 24, 1024      # MT2_EBU_FIELDS, MT2_TP_ZERO_CROSSINGS, MT2_TP_TAPS, MT2_TP_TILE
 LIMITER_FIELDS, LIMITER_TILE, LIMITER_MAX_HALF_WINDOW, LIMITER_MAX_PASSES = 24, 1024, 1024, 4      # MT2_LIMITER_*
@@ -110,6 +112,12 @@ def load_library():
     lib.mt2_dtw_query.argtypes = [C.c_int] * 4 + [C.c_void_p]
     lib.mt2_dtw_align.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
     lib.mt2_align_durations.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_mcd_table.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_mcd_query.argtypes = [C.c_int] * 5 + [C.c_void_p]
+    lib.mt2_mel_cepstrum.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]
+    lib.mt2_path_distortion.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+    lib.mt2_mel_cepstral_distortion.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+                                                + [C.c_void_p] * 5)
     lib.mt2_stft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_istft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_mel_to_linear.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
@@ -235,6 +243,80 @@ def _dtw(lib, h, X, Y, x_lens=None, y_lens=None, return_cost: bool = False, retu
     _check(lib.mt2_dtw_align(h, _stream(), _ptr(X), _iptr(xl), Tx, _ptr(Y), _iptr(yl), Ty, D, B, _ptr(out["lo"]), _ptr(out["hi"]),
                              _ptr(out["steps"]), _ptr(out["total"]), _ptr(out.get("cost")), _ptr(out.get("acc"))))
     return out
+
+
+def _rows_lens(x, lens, what: str):
+    """x f32 [B, T, W] on the device, lens int [B] or None (every row whole) -> (x contiguous f32, lens int32 [B])"""
+    import torch
+    assert x.is_cuda and x.dim() == 3, what
+    x = x.contiguous().to(torch.float32)
+    ln = np.full(x.shape[0], x.shape[1], np.int32) if lens is None else _i32(lens)
+    assert ln.shape == (x.shape[0],), what
+    return x, ln
+
+
+def _f0_pair(f0_a, f0_b, B: int, Ta: int, Tb: int):
+    import torch
+    if f0_a is None and f0_b is None:
+        return None, None
+    if f0_a is not None:
+        assert f0_a.is_cuda and tuple(f0_a.shape) == (B, Ta)
+        f0_a = f0_a.contiguous().to(torch.float32)
+    if f0_b is not None:      # one track without the other goes to the library, which refuses it
+        assert f0_b.is_cuda and tuple(f0_b.shape) == (B, Tb)
+        f0_b = f0_b.contiguous().to(torch.float32)
+    return f0_a, f0_b
+
+
+def _mel_cepstrum(lib, h, mel, frame_lens=None, order: int = 13):
+    """mt2_mel_cepstrum on the handle `h`: mel f32 [B, T, N] (natural-log mel, time-major, device) -> cep f32 [B, T, order] by the
+    rule of csrc/mcd.hip: c[t][k-1] = sum_m mel[t][m] cos(pi (m + 1/2) k / N) / N, one f32 fma chain; c0 is left out.  Rows at or beyond
+    frame_lens[b] are never read and give zeros.  The call only enqueues."""
+    import torch
+    mel, fl = _rows_lens(mel, frame_lens, "mel f32 [B, T, N]")
+    B, T, N = mel.shape
+    cep = torch.empty(B, T, int(order), device=mel.device, dtype=torch.float32)
+    _check(lib.mt2_mel_cepstrum(h, _stream(), _ptr(mel), _iptr(fl), T, B, N, int(order), _ptr(cep)))
+    return cep
+
+
+def _path_distortion(lib, h, ca, cb, lo, hi, a_lens=None, b_lens=None, f0_a=None, f0_b=None):
+    """mt2_path_distortion on the handle `h`: cepstra ca f32 [B, Ta, K], cb f32 [B, Tb, K] and a path lo, hi int32 [B, Tb] (device, as
+    `dtw` returns them) -> float64 [B, 8] (device): cells, MCD in dB, largest cell dB, cells voiced on both sides, F0 RMSE in cents,
+    mean F0 difference in cents, cells voiced on one side, that over the cells; the last five are 0 without f0_a f32 [B, Ta] and f0_b
+    f32 [B, Tb].  The call only enqueues."""
+    import torch
+    ca, al = _rows_lens(ca, a_lens, "ca f32 [B, Ta, K]")
+    cb, bl = _rows_lens(cb, b_lens, "cb f32 [B, Tb, K]")
+    B, Ta, K = ca.shape
+    Tb = cb.shape[1]
+    assert cb.shape[0] == B and cb.shape[2] == K
+    lo, hi = (t.to(ca.device, torch.int32).contiguous() for t in (lo, hi))
+    assert tuple(lo.shape) == (B, Tb) and tuple(hi.shape) == (B, Tb)
+    f0_a, f0_b = _f0_pair(f0_a, f0_b, B, Ta, Tb)
+    out = torch.empty(B, MCD_FIELDS, device=ca.device, dtype=torch.float64)
+    _check(lib.mt2_path_distortion(h, _stream(), _ptr(ca), _iptr(al), Ta, _ptr(cb), _iptr(bl), Tb, K, B, _ptr(lo), _ptr(hi), _ptr(f0_a),
+                                   _ptr(f0_b), _ptr(out)))
+    return out
+
+
+def _mcd(lib, h, mel_a, mel_b, a_lens=None, b_lens=None, f0_a=None, f0_b=None, order: int = 13, return_path: bool = False):
+    """mt2_mel_cepstral_distortion on the handle `h`: the cepstra of mel_a f32 [B, Ta, N] and mel_b f32 [B, Tb, N], the DTW of
+    csrc/dtw.hip on them and the path reduction, in one call -> float64 [B, 8] (device; the fields of `_path_distortion`), with
+    return_path (row, lo, hi), the path int32 [B, Tb].  The call only enqueues."""
+    import torch
+    mel_a, al = _rows_lens(mel_a, a_lens, "mel_a f32 [B, Ta, N]")
+    mel_b, bl = _rows_lens(mel_b, b_lens, "mel_b f32 [B, Tb, N]")
+    B, Ta, N = mel_a.shape
+    Tb = mel_b.shape[1]
+    assert mel_b.shape[0] == B and mel_b.shape[2] == N
+    f0_a, f0_b = _f0_pair(f0_a, f0_b, B, Ta, Tb)
+    out = torch.empty(B, MCD_FIELDS, device=mel_a.device, dtype=torch.float64)
+    lo = torch.empty(B, Tb, device=mel_a.device, dtype=torch.int32) if return_path else None
+    hi = torch.empty(B, Tb, device=mel_a.device, dtype=torch.int32) if return_path else None
+    _check(lib.mt2_mel_cepstral_distortion(h, _stream(), _ptr(mel_a), _iptr(al), Ta, _ptr(mel_b), _iptr(bl), Tb, N, int(order), B,
+                                           _ptr(f0_a), _ptr(f0_b), _ptr(out), _ptr(lo), _ptr(hi)))
+    return (out, lo, hi) if return_path else out
 
 
 def _workspace_fill(lib, h, byte: int) -> None:
@@ -642,6 +724,20 @@ class NativeModel:
         """Dynamic time warping of X f32 [B, Tx, D] onto Y f32 [B, Ty, D] (`_dtw`): dict of device tensors lo, hi, steps, total
         [, cost, acc]."""
         return _dtw(self.lib, self.h, X, Y, x_lens, y_lens, return_cost, return_acc)
+
+    # ---- mel-cepstral distortion along the DTW path (csrc/mcd.hip)
+    def mel_cepstrum(self, mel, frame_lens=None, order: int = 13):
+        """Mel cepstra c1 .. c_order of a log-mel f32 [B, T, N] (`_mel_cepstrum`) -> f32 [B, T, order] (device)."""
+        return _mel_cepstrum(self.lib, self.h, mel, frame_lens, order)
+
+    def path_distortion(self, ca, cb, lo, hi, a_lens=None, b_lens=None, f0_a=None, f0_b=None):
+        """The distortion row float64 [B, 8] of two cepstra along a given path (`_path_distortion`; the fields are MCD_NAMES)."""
+        return _path_distortion(self.lib, self.h, ca, cb, lo, hi, a_lens, b_lens, f0_a, f0_b)
+
+    def mcd(self, mel_a, mel_b, a_lens=None, b_lens=None, f0_a=None, f0_b=None, order: int = 13, return_path: bool = False):
+        """Mel-cepstral distortion of mel_a f32 [B, Ta, N] against mel_b f32 [B, Tb, N] along the DTW path of their cepstra, with the F0
+        error and the voicing error along the same path where both tracks are given (`_mcd`) -> float64 [B, 8] (device)."""
+        return _mcd(self.lib, self.h, mel_a, mel_b, a_lens, b_lens, f0_a, f0_b, order, return_path)
 
     def align_durations(self, hi, y_lens, syn_dur, phone_lens=None):
         """mt2_align_durations: the path's `hi` int32 [B, Ty] (device, from `dtw` with these y_lens) and the synthetic durations
@@ -1082,6 +1178,20 @@ class MelFrontEnd:
         """Dynamic time warping of X f32 [B, Tx, D] onto Y f32 [B, Ty, D] on the bare handle (`_dtw`, as NativeModel.dtw): e.g. the
         DTW mel distance `total` between two utterances of different length."""
         return _dtw(self.lib, self.h, X, Y, x_lens, y_lens, return_cost, return_acc)
+
+    # ---- mel-cepstral distortion along the DTW path (csrc/mcd.hip)
+    def mel_cepstrum(self, mel, frame_lens=None, order: int = 13):
+        """Mel cepstra c1 .. c_order of a log-mel f32 [B, T, N] (`_mel_cepstrum`) -> f32 [B, T, order] (device)."""
+        return _mel_cepstrum(self.lib, self.h, mel, frame_lens, order)
+
+    def path_distortion(self, ca, cb, lo, hi, a_lens=None, b_lens=None, f0_a=None, f0_b=None):
+        """The distortion row float64 [B, 8] of two cepstra along a given path (`_path_distortion`; the fields are MCD_NAMES)."""
+        return _path_distortion(self.lib, self.h, ca, cb, lo, hi, a_lens, b_lens, f0_a, f0_b)
+
+    def mcd(self, mel_a, mel_b, a_lens=None, b_lens=None, f0_a=None, f0_b=None, order: int = 13, return_path: bool = False):
+        """Mel-cepstral distortion of mel_a f32 [B, Ta, N] against mel_b f32 [B, Tb, N] along the DTW path of their cepstra, with the F0
+        error and the voicing error along the same path where both tracks are given (`_mcd`) -> float64 [B, 8] (device)."""
+        return _mcd(self.lib, self.h, mel_a, mel_b, a_lens, b_lens, f0_a, f0_b, order, return_path)
 
     # ---- Griffin-Lim vocoder (csrc/griffinlim.hip): the STFT, its inverse, mel -> linear and the iteration
     def _frame_lens(self, lens, B: int, T: int) -> np.ndarray:
@@ -1878,6 +1988,22 @@ def dtw_query(Tx_max: int, Ty_max: int, D: int = 80, B: int = 1) -> int:
     n = C.c_longlong(0)
     _check(load_library().mt2_dtw_query(int(Tx_max), int(Ty_max), int(D), int(B), C.byref(n)))
     return n.value
+
+
+def mcd_query(Ta_max: int, Tb_max: int, n_mels: int = 80, order: int = 13, B: int = 1) -> int:
+    """mt2_mcd_query (no device needed) -> the arena bytes of one `mcd` call of this geometry, which is exactly its high water: what
+    dtw_query states for the skewed costs and the packed directions, and with r(n) = n rounded up to 256, r(4 (4 ceil(B / 4) + B)) for
+    the lengths + r(4 B Ta K) + r(4 B Tb K) for the cepstra + 2 r(4 B Tb) for lo and hi + 2 r(4 B) for steps and total."""
+    n = C.c_longlong(0)
+    _check(load_library().mt2_mcd_query(int(Ta_max), int(Tb_max), int(n_mels), int(order), int(B), C.byref(n)))
+    return n.value
+
+
+def mcd_table(n_mels: int = 80, order: int = 13) -> np.ndarray:
+    """mt2_mcd_table (no device needed) -> the cepstrum table float32 [order, n_mels]: cos(pi (m + 1/2) k / n_mels) / n_mels, k = 1 .. order."""
+    table = np.zeros((max(int(order), 0), max(int(n_mels), 0)), np.float32)
+    _check(load_library().mt2_mcd_table(int(n_mels), int(order), table.ctypes.data_as(C.c_void_p)))
+    return table
 
 
 def griffin_lim_query(audio, mel_lens=None, T_max: Optional[int] = None, B: Optional[int] = None, n_iter: int = 32,

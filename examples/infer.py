@@ -52,6 +52,17 @@ def main() -> None:
                          "GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
     ap.add_argument("--report-loudness", action="store_true",
                     help="print integrated LUFS, sample peak in dBFS and block counts (measured on the GPU) of the first prompt and, when a vocoder produced audio, of the generated audio")
+    ap.add_argument("--denoise-prompt", action="store_true",
+                    help="suppress stationary noise (hiss, room tone, hum) in every prompt file on the GPU before its mel is taken: a per-bin "
+                         "quantile noise floor and a spectral gate; a STEADY tone is removed like hum")
+    ap.add_argument("--denoise-percentile", type=int, default=20, metavar="P",
+                    help="with --denoise-prompt: the percentile of a bin's power over time taken as its noise floor, 1 to 99 (default 20); "
+                         "speech present in a bin for more than 100 - P %% of the frames raises that bin's floor")
+    ap.add_argument("--denoise-strength", type=float, default=3.0, metavar="BETA", help="with --denoise-prompt: the over-subtraction factor (default 3)")
+    ap.add_argument("--denoise-floor-db", type=float, default=-20.0, metavar="DB", help="with --denoise-prompt: the least gain of a cell in dB, at most 0 (default -20)")
+    ap.add_argument("--report-noise", action="store_true",
+                    help="print, for each prompt file, the estimated noise power and SNR, the share of cells at the floor gain and the power "
+                         "reduction in dB (measured on the GPU; the prompts are denoised only with --denoise-prompt)")
     ap.add_argument("--reference-wav", metavar="PATH",
                     help="a recording of the same sentence: print the mel-cepstral distortion (dB, along the DTW path of the cepstra), the largest "
                          "cell, and F0 RMSE, register offset and voiced / unvoiced error along the same path, of the generated audio against it")
@@ -74,11 +85,24 @@ def main() -> None:
     tts.eval()
     phones = [int(v) for v in a.phones.split(",")] if a.phones else None
     gl = {"n_iter": a.gl_iters} if a.vocoder == "griffin-lim" else None
+    dn = M.Denoise(a.denoise_percentile, a.denoise_strength, 10.0 ** (a.denoise_floor_db / 20.0))
     mel, lens, aux = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl, loudness_lufs=a.output_lufs,
                          peak_ceiling=a.peak_ceiling, true_peak_ceiling_dbtp=a.true_peak_ceiling,
-                         **({"limiter": M.Limiter(a.limiter_window_ms, a.limiter_passes)} if a.limiter else {}))
+                         **({"limiter": M.Limiter(a.limiter_window_ms, a.limiter_passes)} if a.limiter else {}),
+                         **({"denoise": dn} if a.denoise_prompt else {}))
     wrote = gl is not None or tts.hifi_gan is not None
     print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
+    if a.report_noise:
+        import glob
+        from megatts2_amd import audio_io
+        paths = sorted(glob.glob(f"{a.wavs_dir}/*.wav"))
+        # with --denoise-prompt the figures of the suppression that ran; without it a measurement of the file, nothing is changed
+        rows = aux["prompt_noise"] if a.denoise_prompt else [{k: float(v[0]) for k, v in M.denoise_audio(*audio_io.read_wav(p), denoise=dn)[1].items()
+                                                               if k in M.DENOISE_NAMES} for p in paths]
+        for path, st in zip(paths, rows):
+            print(f"noise of the prompt {path}{' (suppressed)' if a.denoise_prompt else ' (measured only)'}: floor {st['noise_db']:.2f} dB, "
+                  f"estimated SNR {st['snr_db']:.2f} dB, {100 * st['floored_share']:.1f} % of the cells at the floor gain, power "
+                  f"{st['reduction_db']:.2f} dB, percentile {a.denoise_percentile} = rank {int(st['rank'])} of {int(st['frames'])} frames")
     if a.report_loudness:
         import glob
         import math

@@ -447,6 +447,80 @@ int mt2_griffin_lim_query(const mt2_audio_config* ac, const int32_t* mel_lens /*
 int mt2_griffin_lim(mt2_model* m, void* stream, const mt2_audio_config* ac, const float* mel, const int32_t* mel_lens /*host*/, int T_max,
                     int B, int n_iter, double momentum, const uint64_t* seeds /*host*/, float* wav, int L_max, float* resid /*or NULL*/);
 
+/* ---- Stationary-noise suppression for prompt audio (csrc/denoise.hip): a per-bin quantile noise floor and a spectral gate between
+ * mt2_stft and mt2_istft - hiss, room tone or mains hum under a prompt is otherwise copied into the generated speech.  No counterpart in
+ * the reference.  Parity with any outside denoiser (noisereduce, RNNoise, Audacity) is unpinned, and so is audible quality on real
+ * speech: the test signals are analytic and the weights synthetic.  The rule is our own, held to tests/denoise_ref.py.  Out of scope:
+ * non-stationary noise tracking, a streaming form, de-reverberation, multichannel.  THE RULE, for one utterance x[0 .. L) with the audio
+ * configuration's N = n_fft, h = hop, F = N / 2 + 1, Fp and S as above, T = 1 + L / h frames, and the parameters of mt2_denoise_config:
+ *  1 Spectrum.  S = mt2_stft(x), exactly that call on this utterance alone: in a batch the STFT GEMM is launched per utterance, so that
+ *    its tile is the one the utterance's own row count chooses.
+ *  2 Power.  P[t, f] = fmaf(im, im, re re) in f32, f < F.
+ *  3 Noise floor (quantile-based noise estimation, Stahl, Fischer and Bippus 2000: a bin is speech-free in at least `percentile` % of
+ *    the frames).  k = ((T - 1) percentile + 50) / 100 in integers (the rank rule of mt2_loudness_ebu);  q[f] = the value of rank k
+ *    (0-based, ascending) among P[0 .. T, f], selected exactly - P >= 0, so the f32 bit pattern orders as an unsigned integer, and a
+ *    radix select is order-free: no sum;  c = (float)(1 / -ln(1 - percentile / 100)), in double, rounded once;  Nf[f] = q[f] c, one f32
+ *    product.  c turns the quantile of an exponentially distributed periodogram bin into its mean: for white Gaussian noise of variance
+ *    s^2 the expectation is Nf[f] = s^2 sum w^2 for 0 < f < N / 2.
+ *  4 Gain.  g0[t, f] = P > 0 ? max(g_min, (P - beta Nf[f]) / P) : g_min - one f32 product, one subtraction, one true f32 division, one
+ *    max (a NaN quotient takes g_min).
+ *  5 Smoothing against musical noise, f32 sums in ascending order divided by the count of existing cells:  g1[t, f] = mean of g0[t, f']
+ *    over f' in [f - bf, f + bf] and [0, F);  g[t, f] = mean of g1[t', f] over t' in [t - bt, t + bt] and [0, T).  Pad columns F .. Fp-1
+ *    and frames at or beyond T never enter a mean and are never read.
+ *  6 Apply.  S'[t, f] = g S[t, f], real and imaginary part each one f32 product, pad columns as mt2_stft wrote them;  y = mt2_istft(S'),
+ *    exactly that call:  (T - 1) h = h (L / h) samples, zeros beyond - up to h - 1 tail samples are dropped, the Griffin-Lim convention.
+ *  7 Figures, a row of MT2_DENOISE_FIELDS = 8 doubles:  0 noise power 10 log10(sum_f Nf) in dB   1 estimated SNR
+ *    10 log10(max(sum P / T - sum Nf, DBL_MIN) / sum Nf)   2 the share of cells with g0 == g_min   3 the reduction
+ *    10 log10(sum g^2 P / sum P)   4 T   5 k   6 sum P / T   7 sum_f Nf.  Sums in double: a tile of 16 frames by 64 bins is summed by
+ *    256 threads, each its own cells in ascending order, then a fixed tree;  the tiles likewise - an order that depends on the cell's
+ *    index in its utterance alone.
+ * A sample and a figure depend on their utterance alone: a ragged batch is bit-identical to its utterances alone.  Non-finite input
+ * does not fault and promises nothing more.
+ * TWO CONSEQUENCES.  A STEADY tone is stationary and is removed like hum: the estimator cannot tell it from noise.  Speech present in a
+ * bin for more than 100 - percentile % of the frames raises that bin's floor (at percentile 50 a tone gated on half the time is
+ * attenuated, not cleaned).
+ * Refused, on the host, with nothing launched and every output as it was:  a parameter outside its range or not finite;  B outside
+ * [1, 65535];  for mt2_denoise a T_b outside what mt2_istft accepts (N / (2 h) + 2 <= T_b), for the other two a frame count outside
+ * [1, T_max];  a T_max over MT2_DENOISE_MAX_FRAMES;  Lout_max < (max T_b - 1) h;  `out` overlapping `wav`, any output overlapping an
+ * input (mt2_spectral_gain's spec_out may BE spec).  `m` may be a bare handle;  scratch comes from its arena;  every call only enqueues. */
+#define MT2_DENOISE_FIELDS 8
+#define MT2_DENOISE_MAX_FRAMES 16384
+typedef struct mt2_denoise_config {
+    int32_t percentile;        /* [1, 99];  20 */
+    float over_subtraction;    /* beta > 0, finite;  3.0 */
+    float floor_gain;          /* g_min in (0, 1];  0.1 = -20 dB */
+    int32_t smooth_bins;       /* bf in [0, 8];  1 */
+    int32_t smooth_frames;     /* bt in [0, 8];  1 */
+    int32_t reserved;          /* 0 */
+} mt2_denoise_config;
+/* Arena bytes of one mt2_denoise call (exactly its high water), its output length, and k and c for the longest utterance;  host only, no
+ * HIP call;  outputs may be NULL;  lens NULL: every L_b = L_max.  It refuses what mt2_denoise refuses for these arguments.  With r(n) =
+ * max(256, n rounded up to 256), q(n) = n rounded up to 4, taps = N / h, T_b = 1 + L_b / h, Fr = sum_b T_b, Rb = sum_b (T_b - 1 + taps),
+ * tiles = ceil(max T_b / 16) ceil(F / 64):
+ *   r(4 (2 q(Rb) + q(B) + 2 q(Fr) + q(B) + B))  the call's one upload of block and row maps and lengths
+ *   + r(4 Rb h) + r(4 Fr S) + r(4 Fr Fp) + r(4 B Fp) + r(24 B tiles) + r(4 Fr N)   blocks, spectrum, P, Nf, tile sums, frames
+ * L_out = (max_b T_b - 1) h. */
+int mt2_denoise_query(const mt2_audio_config* ac, const mt2_denoise_config* dc, const int32_t* lens /*host or NULL*/, int L_max, int B,
+                      long long* workspace_bytes, long long* L_out, int* rank, float* factor);
+/* Rules 2-3 on a spectrum the caller supplies:  spec f32 [B, T_max, S] in mt2_stft's layout (device; pad columns and frames at or beyond
+ * frame_lens[b] are never read), frame_lens host int32 [B] -> floor f32 [B, Fp] (device), zeros in the columns F .. Fp-1.  On a
+ * noise-only clip this is a noise profile that mt2_denoise and mt2_spectral_gain take instead of their own rule 3. */
+int mt2_noise_floor(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* spec,
+                    const int32_t* frame_lens /*host*/, int T_max, int B, float* floor /*[B, Fp]*/);
+/* Rules 2 and 4-6 on a spectrum and a floor the caller supplies -> gain f32 [B, T_max, Fp] (device or NULL;  zeros in the pad columns and
+ * in the frames at or beyond frame_lens[b]) and / or the gated spectrum spec_out f32 [B, T_max, S] (device or NULL;  it may be `spec`
+ * itself: then pad columns and frames at or beyond frame_lens[b] stay as they were, else they are zero).  At least one output. */
+int mt2_spectral_gain(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* spec,
+                      const int32_t* frame_lens /*host*/, int T_max, int B, const float* floor /*[B, Fp]*/, float* gain /*or NULL*/,
+                      float* spec_out /*or NULL*/);
+/* The whole rule:  wav f32 [B, L_max] (device; samples at or beyond lens[b] are never read), lens host int32 [B] -> out f32
+ * [B, Lout_max] (device):  (T_b - 1) h samples, zeros beyond.  floor_in (device f32 [B, Fp] or NULL): the caller's floor instead of
+ * rule 3.  floor_out (device f32 [B, Fp] or NULL): the floor that was used.  figures (device f64 [B, 8] or NULL).  Stage events
+ * (mt2_set_profiling): dn_stft, dn_floor, dn_gain, dn_istft. */
+int mt2_denoise(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* wav,
+                const int32_t* lens /*host*/, int L_max, int B, const float* floor_in /*or NULL*/, float* floor_out /*or NULL*/,
+                double* figures /*or NULL*/, float* out, int Lout_max);
+
 /* ---- F0 tracking by YIN (de Cheveigne & Kawahara 2002, steps 2-5; csrc/f0.hip) and the pitch moments of a track.  No reference
  * counterpart: the reference tree has no pitch tracker (it would take one from librosa or pyworld).  Parity with librosa.yin / pyin
  * is unpinned - neither is on hand - and quality on real speech is unpinned as well; the rule is our own statement and the tests

@@ -1163,6 +1163,62 @@ int mt2_mel_cepstral_distortion(mt2_model* m, void* stream, const float* mel_a, 
     MT2_API_END
 }
 
+// stationary-noise suppression (denoise.hip): the arena bytes of one mt2_denoise call, its output length and the rank and factor of the
+// longest utterance, without a HIP call
+int mt2_denoise_query(const mt2_audio_config* ac, const mt2_denoise_config* dc, const int32_t* lens, int L_max, int B,
+                      long long* workspace_bytes, long long* L_out, int* rank, float* factor) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(ac != nullptr, "null audio configuration");
+    const DnArgs a = denoise_check_config(dc);
+    std::vector<int> T;
+    const int T_cap = denoise_frames(*ac, lens, L_max, B, T);
+    if (workspace_bytes) *workspace_bytes = denoise_arena_bytes(*ac, T, T_cap);
+    if (L_out) *L_out = (long long)(T_cap - 1) * ac->hop_length;
+    if (rank) *rank = denoise_rank(T_cap, a.percentile);
+    if (factor) *factor = a.c;
+    MT2_API_END
+}
+
+// every refusal of the three calls is decided on the host before the first HIP call
+int mt2_noise_floor(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* spec,
+                    const int32_t* frame_lens, int T_max, int B, float* floor) {
+    MT2_API_BEGIN
+    const DnArgs a = denoise_check_config(dc);
+    const int T_cap = denoise_check_spec(ac, spec, frame_lens, T_max, B);
+    MT2_REQUIRE(floor != nullptr && ((uintptr_t)floor & 3) == 0, "bad floor");
+    const size_t F = ac->n_fft / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
+    MT2_REQUIRE(!outputs_overlap({{floor, sizeof(float) * B * Fp}}, {{spec, sizeof(float) * (size_t)B * T_max * lds}}), "overlapping buffers");
+    MT2_AUDIO_CALL(m, stream);
+    noise_floor_run(c, *ac, a, spec, frame_lens, T_max, B, T_cap, floor);
+    MT2_API_END
+}
+
+int mt2_spectral_gain(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* spec,
+                      const int32_t* frame_lens, int T_max, int B, const float* floor, float* gain, float* spec_out) {
+    MT2_API_BEGIN
+    const DnArgs a = denoise_check_config(dc);
+    const int T_cap = denoise_check_spec(ac, spec, frame_lens, T_max, B);
+    MT2_REQUIRE(floor != nullptr && (gain != nullptr || spec_out != nullptr), "null floor, or neither output asked for");
+    MT2_REQUIRE((((uintptr_t)floor | (uintptr_t)gain | (uintptr_t)spec_out) & 3) == 0, "misaligned buffers");
+    const size_t F = ac->n_fft / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
+    const size_t ns = sizeof(float) * (size_t)B * T_max * lds, ng = sizeof(float) * (size_t)B * T_max * Fp, nf = sizeof(float) * B * Fp;
+    MT2_REQUIRE(!outputs_overlap({{gain, ng}, {spec_out == spec ? nullptr : spec_out, ns}}, {{spec, ns}, {floor, nf}}), "overlapping buffers");
+    MT2_AUDIO_CALL(m, stream);
+    spectral_gain_run(c, *ac, a, spec, frame_lens, T_max, B, T_cap, floor, gain, spec_out);
+    MT2_API_END
+}
+
+int mt2_denoise(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* wav, const int32_t* lens,
+                int L_max, int B, const float* floor_in, float* floor_out, double* figures, float* out, int Lout_max) {
+    MT2_API_BEGIN
+    std::vector<int> T;
+    DnArgs a{};
+    const int T_cap = denoise_check(ac, dc, wav, lens, L_max, B, floor_in, floor_out, figures, out, Lout_max, T, a);
+    MT2_AUDIO_CALL(m, stream);
+    denoise_run(c, *ac, a, wav, lens, L_max, B, T, T_cap, floor_in, floor_out, figures, out, Lout_max);
+    MT2_API_END
+}
+
 // :361-368 [+370]  zq = vq.decode(p_codes) repeated x8, cat([tc_latent_expand, zq]), decoder, optional vocoder - the part of
 // Megatts.forward behind the PLM, shared by mt2_synthesize_batch and mt2_synthesize_prompt_conditioned.  xdec: [D.R, H + Dq]
 // rows whose first H columns already hold the length-regulated tc_latents.

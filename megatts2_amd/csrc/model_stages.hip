@@ -2857,6 +2857,165 @@ static void mcd_run(const Ctx& c, const float* mel_a, const int* a_lens, int Ta_
     st.finish();
 }
 
+// ---- stationary-noise suppression (denoise.hip) between the STFT of the front-end and the inverse STFT of griffinlim.hip: every
+// refusal is decided here, on the host, before the first HIP call
+struct DnArgs { int percentile, bf, bt; float beta, gmin, c; };
+static DnArgs denoise_check_config(const mt2_denoise_config* dc) {
+    MT2_REQUIRE(dc != nullptr, "null denoise configuration");
+    MT2_REQUIRE(dc->percentile >= 1 && dc->percentile <= 99, "percentile outside [1, 99]");
+    MT2_REQUIRE(std::isfinite(dc->over_subtraction) && dc->over_subtraction > 0.0f, "over_subtraction must be finite and > 0");
+    MT2_REQUIRE(std::isfinite(dc->floor_gain) && dc->floor_gain > 0.0f && dc->floor_gain <= 1.0f, "floor_gain outside (0, 1]");
+    MT2_REQUIRE(dc->smooth_bins >= 0 && dc->smooth_bins <= kDnMaxSmooth, "smooth_bins outside [0, 8]");
+    MT2_REQUIRE(dc->smooth_frames >= 0 && dc->smooth_frames <= kDnMaxSmooth, "smooth_frames outside [0, 8]");
+    MT2_REQUIRE(dc->reserved == 0, "mt2_denoise_config.reserved must be 0");
+    return {dc->percentile, dc->smooth_bins, dc->smooth_frames, dc->over_subtraction, dc->floor_gain, denoise_factor(dc->percentile)};
+}
+static void denoise_fill(DenoiseP& p, const DnArgs& a, const mt2_audio_config& ac, int B, int T_cap) {
+    p.F = ac.n_fft / 2 + 1; p.Fp = (p.F + 3) & ~3; p.lds = (2 * p.F + 3) & ~3; p.B = B; p.T_cap = T_cap;
+    p.percentile = a.percentile; p.bf = a.bf; p.bt = a.bt; p.beta = a.beta; p.gmin = a.gmin; p.c = a.c;
+}
+static size_t denoise_tiles(int T_cap, int F) { return (size_t)((T_cap + kDnTileT - 1) / kDnTileT) * ((F + kDnTileF - 1) / kDnTileF); }
+// the frame counts of a waveform batch, T_b = 1 + L_b / hop, each inside what the inverse STFT accepts; -> their max
+static int denoise_frames(const mt2_audio_config& ac, const int* lens, int L_max, int B, std::vector<int>& T) {
+    gl_check_config(ac);
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(L_max >= 1, "L_max < 1");
+    T.resize(B);
+    int T_cap = 0;
+    for (int b = 0; b < B; ++b) {
+        const int L = lens ? lens[b] : L_max;
+        MT2_REQUIRE(L >= 1 && L <= L_max, "waveform length outside [1, L_max]");
+        T[b] = 1 + L / ac.hop_length;
+        MT2_REQUIRE(T[b] >= gl_min_frames(ac), "a waveform shorter than (n_fft / (2 hop) + 1) hop samples: fewer frames than mt2_istft accepts");
+        T_cap = std::max(T_cap, T[b]);
+    }
+    MT2_REQUIRE(T_cap <= MT2_DENOISE_MAX_FRAMES, "more than MT2_DENOISE_MAX_FRAMES frames");
+    gl_check_lens(ac, T.data(), T_cap, B, (long long)(T_cap - 1) * ac.hop_length);
+    return T_cap;
+}
+// the arena of one denoise_run, in carve order: the plan, the reflect-padded blocks, the packed spectrum (gated in place), P, the
+// floor, the tile sums and the frames of the inverse STFT - taken whatever the optional arguments
+struct DnWs { float *xp, *spec, *P, *floor; double* part; float* frames; };
+template <class Ws> static DnWs denoise_carve(Ws& ws, IntPlan& ip, const mt2_audio_config& ac, size_t Fr, size_t Rb, size_t B, int T_cap) {
+    const size_t N = ac.n_fft, F = N / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
+    DnWs w{};
+    ip.carve(ws);
+    w.xp = ws.template get<float>(Rb * ac.hop_length);
+    w.spec = ws.template get<float>(Fr * lds);
+    w.P = ws.template get<float>(Fr * Fp);
+    w.floor = ws.template get<float>(B * Fp);
+    w.part = ws.template get<double>(B * denoise_tiles(T_cap, (int)F) * 3);
+    w.frames = ws.template get<float>(Fr * N);
+    return w;
+}
+static long long denoise_arena_bytes(const mt2_audio_config& ac, const std::vector<int>& T, int T_cap) {
+    const size_t B = T.size();
+    size_t Fr = 0, Rb = 0;
+    for (int t : T) { Fr += t; Rb += t - 1 + ac.n_fft / ac.hop_length; }
+    IntPlan ip;      // the entries of denoise_run's plan, by size
+    for (size_t n : {Rb, Rb, B, Fr, Fr, B, B}) ip.add_fill(n, 0);
+    ArenaCount count;
+    denoise_carve(count, ip, ac, Fr, Rb, B, T_cap);
+    return (long long)count.bytes;
+}
+// -> T_cap, with T filled
+static int denoise_check(const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* wav, const int* lens, int L_max, int B,
+                         const float* floor_in, const float* floor_out, const double* figures, const float* out, int Lout_max,
+                         std::vector<int>& T, DnArgs& a) {
+    MT2_REQUIRE(ac != nullptr, "null audio configuration");
+    a = denoise_check_config(dc);
+    MT2_REQUIRE(wav != nullptr && lens != nullptr && out != nullptr, "bad buffers");
+    const int T_cap = denoise_frames(*ac, lens, L_max, B, T);
+    MT2_REQUIRE((long long)Lout_max >= (long long)(T_cap - 1) * ac->hop_length, "Lout_max smaller than (max T - 1) * hop_length");
+    MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)out | (uintptr_t)floor_in | (uintptr_t)floor_out) & 3) == 0 && ((uintptr_t)figures & 7) == 0,
+                "misaligned buffers");
+    const size_t Fp = (size_t)((ac->n_fft / 2 + 1 + 3) & ~3);
+    const size_t nw = sizeof(float) * (size_t)B * L_max, no = sizeof(float) * (size_t)B * Lout_max, nf = sizeof(float) * (size_t)B * Fp,
+                 ng = sizeof(double) * MT2_DENOISE_FIELDS * (size_t)B;
+    MT2_REQUIRE(!outputs_overlap({{out, no}, {floor_out, nf}, {figures, ng}}, {{wav, nw}, {floor_in, nf}}), "overlapping buffers");
+    return T_cap;
+}
+// enqueues only.  The STFT GEMM runs per utterance, on the tile its own row count chooses - what mt2_stft runs for the utterance alone;
+// the inverse GEMM runs once on the fixed tile of mt2_istft.
+static void denoise_run(const Ctx& c, const mt2_audio_config& ac, const DnArgs& a, const float* wav, const int* lens, int L_max, int B,
+                        const std::vector<int>& T, int T_cap, const float* floor_in, float* floor_out, double* figures, float* out,
+                        int Lout_max) {
+    gl_prepare_istft(c.m, ac);
+    IntPlan ip;
+    const StftRows r = stft_plan(ip, ac, lens, L_max, B, T_cap);
+    std::vector<int> row0(B);
+    for (int b = 0, at = 0; b < B; at += T[b], ++b) row0[b] = at;
+    const int o_row0 = ip.add(row0), o_T = ip.add(T);
+    const DnWs w = denoise_carve(c.ws, ip, ac, r.Fr, r.Rb, B, T_cap);
+    ip.send(c.m.pinned(), c.s);
+    DenoiseP p{};
+    denoise_fill(p, a, ac, B, T_cap);
+    p.spec = w.spec; p.spec_out = w.spec; p.row0 = ip.dev(o_row0); p.T = ip.dev(o_T); p.P = w.P; p.floor_out = w.floor;
+    p.floor = floor_in ? floor_in : w.floor;
+    if (figures) { p.part = w.part; p.fig = figures; }
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(launch_reflect_pad_blocks(wav, L_max, ip.dev(r.o_b), ip.dev(r.o_t), ip.dev(r.o_len), ac.hop_length, ac.n_fft / 2, w.xp, r.Rb, c.s));
+    MT2_HIP(hipMemsetAsync(w.spec, 0, sizeof(float) * (size_t)r.Fr * p.lds, c.s));      // the pad columns meet zero basis columns
+    for (int b = 0; b < B; ++b)
+        stft_gemm(c, ac, w.xp, r.Rb, ip.dev(r.o_base) + row0[b], w.spec + (size_t)row0[b] * p.lds, T[b]);
+    st.mark("dn_stft");
+    MT2_HIP(launch_denoise_power(p, c.s));
+    if (!floor_in) MT2_HIP(launch_denoise_select(p, c.s));
+    if (floor_out) MT2_HIP(hipMemcpyAsync(floor_out, p.floor, sizeof(float) * (size_t)B * p.Fp, hipMemcpyDeviceToDevice, c.s));
+    st.mark("dn_floor");
+    MT2_HIP(launch_denoise_gain(p, c.s));
+    if (figures) MT2_HIP(launch_denoise_figures(p, c.s));
+    st.mark("dn_gain");
+    {
+        FixedTile ft(c.m.opts);
+        istft_gemm(c, ac, w.spec, w.frames, r.Fr);
+    }
+    MT2_HIP(launch_istft_ola_wav(w.frames, ac.n_fft, ac.hop_length, c.m.gl_w2, ip.dev(o_row0), ip.dev(o_T), out, Lout_max, B, c.s));
+    st.mark("dn_istft");
+    st.finish();
+}
+
+// the spectrum batch of mt2_noise_floor and mt2_spectral_gain: utterance b owns the rows b T_max .. + frame_lens[b];  -> max frame count
+static int denoise_check_spec(const mt2_audio_config* ac, const float* spec, const int* frame_lens, int T_max, int B) {
+    MT2_REQUIRE(ac != nullptr, "null audio configuration");
+    frontend_check(*ac);
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(T_max >= 1 && T_max <= MT2_DENOISE_MAX_FRAMES, "T_max outside [1, MT2_DENOISE_MAX_FRAMES]");
+    MT2_REQUIRE(spec != nullptr && frame_lens != nullptr && ((uintptr_t)spec & 3) == 0, "bad buffers");
+    MT2_REQUIRE((long long)B * T_max * (ac->n_fft + 4) <= INT_MAX, "batch too large for 32-bit row indices");
+    return check_lens(frame_lens, B, T_max, "a frame count outside [1, T_max]");
+}
+// the plan and P of both calls (their whole arena: the plan of 2 B words, then 4 B T_max Fp bytes), and the power kernel
+static DenoiseP denoise_spec_setup(const Ctx& c, const mt2_audio_config& ac, const DnArgs& a, const float* spec, const int* frame_lens,
+                                   int T_max, int B, int T_cap) {
+    IntPlan ip;
+    std::vector<int> row0(B);
+    for (int b = 0; b < B; ++b) row0[b] = b * T_max;
+    const int o_row0 = ip.add(row0), o_T = ip.add(frame_lens, B);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    DenoiseP p{};
+    denoise_fill(p, a, ac, B, T_cap);
+    p.spec = spec; p.row0 = ip.dev(o_row0); p.T = ip.dev(o_T);
+    p.P = c.ws.get<float>((size_t)B * T_max * p.Fp);
+    MT2_HIP(launch_denoise_power(p, c.s));
+    return p;
+}
+static void noise_floor_run(const Ctx& c, const mt2_audio_config& ac, const DnArgs& a, const float* spec, const int* frame_lens, int T_max,
+                            int B, int T_cap, float* floor) {
+    DenoiseP p = denoise_spec_setup(c, ac, a, spec, frame_lens, T_max, B, T_cap);
+    p.floor_out = floor;
+    MT2_HIP(launch_denoise_select(p, c.s));
+}
+static void spectral_gain_run(const Ctx& c, const mt2_audio_config& ac, const DnArgs& a, const float* spec, const int* frame_lens, int T_max,
+                              int B, int T_cap, const float* floor, float* gain, float* spec_out) {
+    DenoiseP p = denoise_spec_setup(c, ac, a, spec, frame_lens, T_max, B, T_cap);
+    p.floor = floor; p.gain_out = gain; p.gain_T = T_max; p.spec_out = spec_out;
+    if (gain) MT2_HIP(hipMemsetAsync(gain, 0, sizeof(float) * (size_t)B * T_max * p.Fp, c.s));
+    if (spec_out && spec_out != spec) MT2_HIP(hipMemsetAsync(spec_out, 0, sizeof(float) * (size_t)B * T_max * p.lds, c.s));
+    MT2_HIP(launch_denoise_gain(p, c.s));
+}
+
 }  // namespace mt2
 
 // the C ABI lives in capi.hip and includes this translation unit's helpers

@@ -526,6 +526,34 @@ struct McdPathP {
 };
 hipError_t launch_mcd_path(const McdPathP& p, hipStream_t s);
 
+// ---- stationary-noise suppression between the two STFT GEMMs (denoise.hip; the rule is in its header and in megatts2_hip.h) ----------
+// Utterance b owns the rows row0[b] .. row0[b] + T[b] of the spectrum ([rows, lds]: re(0..F-1) | im(0..F-1) | pad) and of P ([rows, Fp]);
+// a row at or beyond T[b] and a column at or beyond F is never read.
+constexpr int kDnSelBins = 16;                // adjacent bins a select workgroup takes: a 64-byte segment of every row of P
+constexpr int kDnTileT = 16, kDnTileF = 64;   // the gain kernel's tile of cells; its halo is at most kDnMaxSmooth on every side
+constexpr int kDnMaxSmooth = 8;
+// host only: c = (float)(1 / -ln(1 - percentile / 100)) and the rank k = ((T - 1) percentile + 50) / 100
+float denoise_factor(int percentile);
+inline int denoise_rank(int T, int percentile) { return (int)((((long long)T - 1) * percentile + 50) / 100); }
+struct DenoiseP {
+    const float* spec; int lds;               // the spectrum rows
+    float* spec_out;                          // the gated rows in the same row numbering (may be spec itself), or nullptr
+    const int* row0; const int* T;            // device [B]
+    int B, F, Fp, T_cap;                      // T_cap >= max_b T[b]: sizes the grids and the partial sums
+    float* P;                                 // [rows, Fp]: written by launch_denoise_power, read by the other two
+    float* floor_out;                         // launch_denoise_select: [B, Fp], zeros in the columns F .. Fp-1
+    const float* floor;                       // launch_denoise_gain / _figures: [B, Fp]
+    float* gain_out; int gain_T;              // optional [B, gain_T, Fp]: only the cells (t < T[b], f < F) are written
+    int percentile, bf, bt;
+    float c, beta, gmin;
+    double* part;                             // optional [B, tiles_t(T_cap), tiles_f, 3]: sum P, sum g^2 P and the floored cells of a tile
+    double* fig;                              // launch_denoise_figures: [B, MT2_DENOISE_FIELDS]
+};
+hipError_t launch_denoise_power(const DenoiseP& p, hipStream_t s);
+hipError_t launch_denoise_select(const DenoiseP& p, hipStream_t s);
+hipError_t launch_denoise_gain(const DenoiseP& p, hipStream_t s);
+hipError_t launch_denoise_figures(const DenoiseP& p, hipStream_t s);
+
 // ---- Griffin-Lim vocoder (griffinlim.hip; the rule is in its header and in megatts2_hip.h) -------------------------------------------
 // Frames of a ragged batch are packed rows: utterance b owns rows row0[b] .. row0[b] + T[b] of S / R / Rprev ([rows, lds]: re(0..F-1) |
 // im(0..F-1) | zero pad, lds = 2F rounded up to 4), of A ([rows, lda]) and of the inverse-DFT GEMM's frames ([rows, N]).

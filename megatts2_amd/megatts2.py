@@ -21,7 +21,7 @@ import numpy as np
 from . import config as cfgmod
 from . import weights
 from .config import HIFIGAN_HOP_LENGTH, HIFIGAN_SR
-from .runtime import Limiter, NativeError, NativeModel  # noqa: F401  (Limiter: the `limiter=` argument of synthesize / forward)
+from .runtime import DENOISE_NAMES, Denoise, Limiter, NativeError, NativeModel  # noqa: F401  (Limiter, Denoise: arguments of synthesize / forward)
 from .sampling import PLMSampling, seed_array
 
 
@@ -40,13 +40,15 @@ def _frontend():
     return _FRONTEND
 
 
-def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None):
+def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, denoise: Optional[Denoise] = None):
     """reference modules/tokenizer.py:107-125: 1-D waveform tensor (16 kHz) -> mel [80, T] (the reference
     returns channels first and `Megatts.forward` transposes it, models/megatts2.py:339).  Runs on the GPU
     (runtime.MelFrontEnd); a [B, L] input gives [B, 80, T].  sample_rate: the rate of `samples` when it is not
     16 kHz - they are resampled on the GPU first (MelFrontEnd.resample, not normalised).  trim_db: leading and
     trailing silence is cut off first (MelFrontEnd.trim, `librosa.effects.trim(y, top_db=trim_db)` of :337; a batch
-    is cut per row, T follows the longest row and the frames behind a shorter row's own are zero)."""
+    is cut per row, T follows the longest row and the frames behind a shorter row's own are zero).  denoise (None = off, exactly
+    the call without it): a `Denoise`; stationary noise is suppressed behind the resampling and in front of the trim
+    (MelFrontEnd.denoise, csrc/denoise.hip; the level is left as it comes out, up to hop - 1 tail samples are dropped)."""
     import torch
     fe = _frontend()
     x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
@@ -55,8 +57,10 @@ def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Option
     if sample_rate is not None and int(sample_rate) != fe.audio.sample_rate:
         x = fe.resample(x, int(sample_rate))[0]
     lens = None
+    if denoise is not None:
+        x, lens = fe.denoise(x, None, denoise)
     if trim_db is not None:
-        x, lens, _ = fe.trim(x, top_db=trim_db)
+        x, lens, _ = fe.trim(x, lens, top_db=trim_db)
     mel = fe(x, lens).transpose(1, 2)
     return mel if batched else mel[0]
 
@@ -151,6 +155,43 @@ def measure_loudness(samples, sample_rate: Optional[int] = None, lens=None, ebu:
         return res
     st = _frontend().loudness(x, lens, sample_rate=sample_rate).cpu().numpy()
     return {k: st[:, i].copy() for i, k in enumerate(LOUDNESS_STATS)}
+
+
+def denoise_audio(samples, sample_rate: Optional[int] = None, lens=None, denoise: Optional[Denoise] = None, noise=None):
+    """Stationary-noise suppression of a 1-D waveform or a [B, L] batch on the GPU, by the rule of csrc/denoise.hip (MelFrontEnd.denoise;
+    no reference counterpart; parity with noisereduce / RNNoise / Audacity and audible quality on real speech unpinned): a per-bin
+    noise floor - the `percentile`-th percentile of the power over time, turned into a mean - and a spectral gate between the STFT and
+    its inverse.  A steady tone is stationary and is removed like hum; speech present in a bin for more than 100 - percentile % of
+    the frames raises that bin's floor.  sample_rate: the rate of `samples` when it is not 16 kHz - they are resampled on the GPU first
+    (not normalised), and the result is at 16 kHz.  lens: the real samples of each row.  denoise: a `Denoise` (None: its defaults).
+    noise: a noise-only clip (1-D, or [B, L'] - one per row - at the same rate as `samples`) whose floor is used instead of each
+    utterance's own.  -> (out float32 numpy [B, hop * (L // hop)] ([.] for a 1-D waveform), dict: out_lens int32 [B], floor float32
+    [B, 513] and float64 [B] noise_db, snr_db, floored_share, reduction_db, frames, rank, mean_frame_power, noise_power)."""
+    import torch
+    fe = _frontend()
+    dn = denoise or Denoise()
+
+    def at_rate(a, ln):
+        a = a if hasattr(a, "is_cuda") else torch.as_tensor(np.asarray(a, np.float32))
+        a = (a.unsqueeze(0) if a.dim() == 1 else a).to("cuda", torch.float32)
+        if sample_rate is not None and int(sample_rate) != fe.audio.sample_rate:
+            return fe.resample(a, int(sample_rate), ln)
+        return a, ln
+
+    flat = (samples.dim() if hasattr(samples, "dim") else np.asarray(samples).ndim) == 1
+    x, ln = at_rate(samples, lens)
+    floor = None
+    if noise is not None:
+        nz, nl = at_rate(noise, None)
+        floor = fe.noise_floor(fe.stft(nz, nl), None if nl is None else 1 + np.asarray(nl) // fe.audio.hop_length, dn)
+        if floor.shape[0] == 1 and x.shape[0] > 1:
+            floor = floor.expand(x.shape[0], -1)
+    out, out_lens, used, fig = fe.denoise(x, ln, dn, noise_floor=floor, return_floor=True, return_figures=True)
+    fig = fig.cpu().numpy()
+    res = {k: fig[:, i].copy() for i, k in enumerate(DENOISE_NAMES)}
+    res["out_lens"], res["floor"] = out_lens, used.cpu().numpy()
+    out = out.cpu().numpy()
+    return (out[0] if flat else out), res
 
 
 LIMITER_STATS = ("half_window", "min_gain", "samples_limited", "true_peak_before_trim", "trim", "output_lufs")
@@ -935,10 +976,13 @@ class Megatts:
     # true_peak_ceiling_dbtp (None = off; needs loudness_lufs): each half's gain is capped so that its true peak stays under this many dBTP.
     # limiter (None = off; a runtime.Limiter; needs true_peak_ceiling_dbtp): each half reaches loudness_lufs under that ceiling, its
     # crests turned down by the look-ahead limiter, where one gain would land under it.
+    # denoise (None = off; a runtime.Denoise): every prompt file, 16 kHz ones too, goes through MelFrontEnd.from_audio(denoise=...):
+    # resample, peak-normalise, suppress stationary noise (csrc/denoise.hip), peak-normalise, trim.  aux["prompt_noise"] then holds
+    # one dict per prompt file with the figures of the suppression (DENOISE_NAMES).
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
                 phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None, vocoder=None,
                 loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0, true_peak_ceiling_dbtp: Optional[float] = None,
-                limiter=None):
+                limiter=None, denoise: Optional[Denoise] = None):
         import torch
         if true_peak_ceiling_dbtp is not None and loudness_lufs is None:
             raise ValueError("true_peak_ceiling_dbtp caps the gain of the loudness normalisation: it needs loudness_lufs")
@@ -964,8 +1008,17 @@ class Megatts:
         if not wavs:
             raise NativeError(f"no *.wav under {wavs_dir}")
 
+        prompt_noise = []
+
         def prompt_mel(w):
             y, sr = audio_io.read_wav(w)
+            if denoise is not None:
+                if sr != HIFIGAN_SR and not resample:
+                    raise ValueError(f"{w}: {sr} Hz, expected {HIFIGAN_SR} Hz (resample=False)")
+                mel, _, fig = _frontend().from_audio(torch.from_numpy(y).unsqueeze(0).cuda(), sr, trim_db=trim_db, denoise=denoise,
+                                                     return_noise=True)
+                prompt_noise.append(dict(zip(DENOISE_NAMES, fig[0].cpu().numpy().tolist())))
+                return mel[0]
             if sr == HIFIGAN_SR and trim_db is None:          # audio_io.load_audio's two steps
                 return extract_mel_spec(torch.from_numpy(audio_io.normalize(y))).transpose(0, 1)
             if sr != HIFIGAN_SR and not resample:
@@ -992,6 +1045,8 @@ class Megatts:
         if vocoder is not None:
             gl = vocoder if isinstance(vocoder, dict) else {}
             mel, mel_lens, aux = self.synthesize(phone_tokens, mels, return_aux=True, griffin_lim=gl or True, **level)
+            if denoise is not None:
+                aux["prompt_noise"] = prompt_noise
             if out_path:
                 prompt = levelled(self.vocode_griffin_lim(mels_prompt.unsqueeze(0).contiguous(), **gl)[0])
                 audio = torch.cat([prompt, aux["wav"][0, :(int(mel_lens[0]) - 1) * HIFIGAN_HOP_LENGTH]])
@@ -999,6 +1054,8 @@ class Megatts:
             return mel, mel_lens, aux
         mel, mel_lens, aux = self.synthesize(phone_tokens, mels, vocoder=self.hifi_gan is not None, return_aux=True,
                                              **(level if self.hifi_gan is not None else {}))
+        if denoise is not None:
+            aux["prompt_noise"] = prompt_noise
         if self.hifi_gan is not None and out_path:
             # :370-375  prompt audio (vocoded first prompt mel) followed by the generated audio; decode_batch output
             # includes the generator's inference padding on both sides, exactly as the reference concatenates it

@@ -8,6 +8,7 @@ device is missing, construction fails loudly.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 import os
 from typing import Dict, Optional, Sequence
@@ -49,6 +50,32 @@ class Limiter:
 
     def __repr__(self):
         return f"Limiter(window_ms={self.window_ms}, passes={self.passes})"
+
+
+@dataclasses.dataclass(frozen=True)
+class Denoise:
+    """The settings of the stationary-noise suppression (csrc/denoise.hip; the rule is in include/megatts2_hip.h): the per-bin noise
+    floor is the `percentile`-th percentile of the power over time (1 .. 99) times the factor that turns that quantile of an
+    exponential distribution into its mean; a cell keeps max(floor_gain, (P - over_subtraction * floor) / P) of its amplitude, averaged
+    over +-smooth_bins bins and +-smooth_frames frames (0 .. 8 each).  A steady tone is stationary and is removed like hum; speech
+    present in a bin for more than 100 - percentile % of the frames raises that bin's floor."""
+    percentile: int = 20
+    over_subtraction: float = 3.0
+    floor_gain: float = 0.1
+    smooth_bins: int = 1
+    smooth_frames: int = 1
+
+    def c_struct(self) -> "MT2DenoiseConfig":
+        return MT2DenoiseConfig(int(self.percentile), float(self.over_subtraction), float(self.floor_gain), int(self.smooth_bins),
+                                int(self.smooth_frames), 0)
+
+
+class MT2DenoiseConfig(C.Structure):
+    _fields_ = [("percentile", C.c_int32), ("over_subtraction", C.c_float), ("floor_gain", C.c_float), ("smooth_bins", C.c_int32),
+                ("smooth_frames", C.c_int32), ("reserved", C.c_int32)]
+
+
+DENOISE_NAMES = ("noise_db", "snr_db", "floored_share", "reduction_db", "frames", "rank", "mean_frame_power", "noise_power")
 
 
 class MT2Config(C.Structure):
@@ -118,6 +145,10 @@ def load_library():
     lib.mt2_path_distortion.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
     lib.mt2_mel_cepstral_distortion.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
                                                 + [C.c_void_p] * 5)
+    lib.mt2_denoise_query.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 4
+    lib.mt2_noise_floor.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_spectral_gain.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib.mt2_denoise.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int]
     lib.mt2_stft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_istft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_mel_to_linear.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
@@ -317,6 +348,107 @@ def _mcd(lib, h, mel_a, mel_b, a_lens=None, b_lens=None, f0_a=None, f0_b=None, o
     _check(lib.mt2_mel_cepstral_distortion(h, _stream(), _ptr(mel_a), _iptr(al), Ta, _ptr(mel_b), _iptr(bl), Tb, N, int(order), B,
                                            _ptr(f0_a), _ptr(f0_b), _ptr(out), _ptr(lo), _ptr(hi)))
     return (out, lo, hi) if return_path else out
+
+
+def _audio_struct(audio) -> MT2AudioConfig:
+    a = audio or cfgmod.AudioConfig()
+    return MT2AudioConfig(a.sample_rate, a.n_fft, a.hop_length, a.win_length, a.n_mels, a.f_min, a.f_max, a.clip)
+
+
+def _packed_spec(spec, F: int):
+    """A spectrum as mt2_stft lays it out: complex64 [B, T, F] -> a new f32 [B, T, S] = [re | im | zero pad];  f32 [B, T, S] as it is."""
+    import torch
+    S = (2 * F + 3) & ~3
+    assert spec.is_cuda and spec.dim() == 3
+    if spec.is_complex():
+        assert spec.shape[2] == F
+        packed = torch.zeros(spec.shape[0], spec.shape[1], S, device=spec.device, dtype=torch.float32)
+        packed[..., :F] = spec.real
+        packed[..., F:2 * F] = spec.imag
+        return packed
+    assert spec.dtype == torch.float32 and spec.shape[2] == S and spec.is_contiguous()
+    return spec
+
+
+def _noise_floor(lib, h, ac, spec, frame_lens=None, denoise: Optional[Denoise] = None):
+    """mt2_noise_floor on the handle `h`: a spectrum (complex64 [B, T, F], or f32 [B, T, S] in mt2_stft's layout; device) -> the noise
+    floor f32 [B, F] (device): per bin the `percentile`-th percentile of the power over the frames below frame_lens[b], selected
+    exactly, times the quantile-to-mean factor.  On a noise-only clip this is a noise profile for `denoise(..., noise_floor=)`."""
+    import torch
+    F = ac.n_fft // 2 + 1
+    packed = _packed_spec(spec, F)
+    B, T, _ = packed.shape
+    ln = np.full(B, T, np.int32) if frame_lens is None else _i32(frame_lens)
+    assert ln.shape == (B,)
+    dc = (denoise or Denoise()).c_struct()
+    floor = torch.empty(B, (F + 3) & ~3, device=packed.device, dtype=torch.float32)
+    _check(lib.mt2_noise_floor(h, _stream(), C.byref(ac), C.byref(dc), _ptr(packed), _iptr(ln), T, B, _ptr(floor)))
+    return floor[:, :F]
+
+
+def _floor_arg(floor, B: int, F: int):
+    """A caller's floor f32 [B, F] or [B, Fp] (device) as the contiguous [B, Fp] the library reads."""
+    import torch
+    Fp = (F + 3) & ~3
+    assert floor.is_cuda and floor.dim() == 2 and floor.shape[0] == B and floor.shape[1] in (F, Fp)
+    if floor.shape[1] == Fp and floor.is_contiguous() and floor.dtype == torch.float32:
+        return floor
+    full = torch.zeros(B, Fp, device=floor.device, dtype=torch.float32)
+    full[:, :floor.shape[1]] = floor
+    return full
+
+
+def _spectral_gain(lib, h, ac, spec, floor, frame_lens=None, denoise: Optional[Denoise] = None, return_gain: bool = True,
+                   apply: bool = False, in_place: bool = False):
+    """mt2_spectral_gain on the handle `h`: a spectrum (as `_noise_floor`) and a floor f32 [B, F] -> the smoothed gain f32 [B, T, F]
+    (zeros in frames at or beyond frame_lens[b]) and / or, with apply, the gated spectrum in the form the spectrum came in (in_place:
+    written over an f32 [B, T, S] spectrum itself).  -> gain, gated, or (gain, gated)."""
+    import torch
+    assert return_gain or apply
+    F = ac.n_fft // 2 + 1
+    packed = _packed_spec(spec, F)
+    B, T, S = packed.shape
+    ln = np.full(B, T, np.int32) if frame_lens is None else _i32(frame_lens)
+    assert ln.shape == (B,)
+    dc = (denoise or Denoise()).c_struct()
+    fl = _floor_arg(floor, B, F)
+    gain = torch.empty(B, T, (F + 3) & ~3, device=packed.device, dtype=torch.float32) if return_gain else None
+    gated = None
+    if apply:
+        assert not in_place or packed is spec, "in_place needs the f32 [B, T, S] layout"
+        gated = packed if in_place else torch.empty_like(packed)
+    _check(lib.mt2_spectral_gain(h, _stream(), C.byref(ac), C.byref(dc), _ptr(packed), _iptr(ln), T, B, _ptr(fl), _ptr(gain), _ptr(gated)))
+    if gated is not None and spec.is_complex():
+        gated = torch.complex(gated[..., :F], gated[..., F:2 * F])
+    res = tuple(x for x in (gain[..., :F] if gain is not None else None, gated) if x is not None)
+    return res[0] if len(res) == 1 else res
+
+
+def _denoise(lib, h, ac, wav, lens=None, denoise: Optional[Denoise] = None, noise_floor=None, return_floor: bool = False,
+             return_figures: bool = False, out=None):
+    """mt2_denoise on the handle `h`: wav f32 [B, L] (device) -> the denoised audio f32 [B, (T - 1) * hop] with T = 1 + max lens // hop,
+    utterance b holding hop * (lens[b] // hop) samples (up to hop - 1 tail samples are dropped, the Griffin-Lim convention) and zeros
+    beyond; samples at or beyond lens[b] are never read.  noise_floor: f32 [B, F] (device) to gate against instead of the utterance's
+    own quantile floor, e.g. `noise_floor` of a noise-only clip.  return_floor: also the floor that was used, f32 [B, F];
+    return_figures: also float64 [B, 8] (device; DENOISE_NAMES).  out: a contiguous f32 [B, >= (T - 1) * hop] device tensor to write
+    into (not wav).  -> (out, out_lens int32 [B][, floor][, figures]).  The call only enqueues."""
+    import torch
+    wav, ln, B, L = _wav_lens(wav, lens)
+    hop, F = ac.hop_length, ac.n_fft // 2 + 1
+    out_lens = (hop * (ln // hop)).astype(np.int32)
+    out = _out_rows(out, B, wav, lambda: max(int(out_lens.max()), 1))
+    dc = (denoise or Denoise()).c_struct()
+    fin = None if noise_floor is None else _floor_arg(noise_floor, B, F)
+    fout = torch.empty(B, (F + 3) & ~3, device=wav.device, dtype=torch.float32) if return_floor else None
+    fig = torch.empty(B, len(DENOISE_NAMES), device=wav.device, dtype=torch.float64) if return_figures else None
+    _check(lib.mt2_denoise(h, _stream(), C.byref(ac), C.byref(dc), _ptr(wav), _iptr(ln), L, B, _ptr(fin), _ptr(fout), _ptr(fig), _ptr(out),
+                           out.shape[1]))
+    res = (out, out_lens)
+    if return_floor:
+        res += (fout[:, :F],)
+    if return_figures:
+        res += (fig,)
+    return res
 
 
 def _workspace_fill(lib, h, byte: int) -> None:
@@ -738,6 +870,21 @@ class NativeModel:
         """Mel-cepstral distortion of mel_a f32 [B, Ta, N] against mel_b f32 [B, Tb, N] along the DTW path of their cepstra, with the F0
         error and the voicing error along the same path where both tracks are given (`_mcd`) -> float64 [B, 8] (device)."""
         return _mcd(self.lib, self.h, mel_a, mel_b, a_lens, b_lens, f0_a, f0_b, order, return_path)
+
+    # ---- stationary-noise suppression (csrc/denoise.hip) on the model's handle, as MelFrontEnd's;  audio: the AudioConfig (default 16 kHz)
+    def denoise(self, wav, lens=None, denoise: Optional[Denoise] = None, noise_floor=None, return_floor: bool = False,
+                return_figures: bool = False, out=None, audio=None):
+        """Denoised audio of wav f32 [B, L] (`_denoise`)."""
+        return _denoise(self.lib, self.h, _audio_struct(audio), wav, lens, denoise, noise_floor, return_floor, return_figures, out)
+
+    def noise_floor(self, spec, frame_lens=None, denoise: Optional[Denoise] = None, audio=None):
+        """The quantile noise floor f32 [B, F] of a spectrum (`_noise_floor`)."""
+        return _noise_floor(self.lib, self.h, _audio_struct(audio), spec, frame_lens, denoise)
+
+    def spectral_gain(self, spec, floor, frame_lens=None, denoise: Optional[Denoise] = None, return_gain: bool = True, apply: bool = False,
+                      in_place: bool = False, audio=None):
+        """The smoothed gain and / or the gated spectrum of a spectrum and a floor (`_spectral_gain`)."""
+        return _spectral_gain(self.lib, self.h, _audio_struct(audio), spec, floor, frame_lens, denoise, return_gain, apply, in_place)
 
     def align_durations(self, hi, y_lens, syn_dur, phone_lens=None):
         """mt2_align_durations: the path's `hi` int32 [B, Ty] (device, from `dtw` with these y_lens) and the synthetic durations
@@ -1193,6 +1340,22 @@ class MelFrontEnd:
         error and the voicing error along the same path where both tracks are given (`_mcd`) -> float64 [B, 8] (device)."""
         return _mcd(self.lib, self.h, mel_a, mel_b, a_lens, b_lens, f0_a, f0_b, order, return_path)
 
+    # ---- stationary-noise suppression (csrc/denoise.hip): quantile noise floor, spectral gate
+    def denoise(self, wav, lens=None, denoise: Optional[Denoise] = None, noise_floor=None, return_floor: bool = False,
+                return_figures: bool = False, out=None):
+        """Denoised audio of wav f32 [B, L] at audio.sample_rate (`_denoise`) -> (out f32 [B, hop * (max lens // hop)], out_lens
+        int32 [B][, floor f32 [B, F]][, figures float64 [B, 8]])."""
+        return _denoise(self.lib, self.h, self.ac, wav, lens, denoise, noise_floor, return_floor, return_figures, out)
+
+    def noise_floor(self, spec, frame_lens=None, denoise: Optional[Denoise] = None):
+        """The quantile noise floor f32 [B, F] of a spectrum, e.g. `stft` of a noise-only clip (`_noise_floor`)."""
+        return _noise_floor(self.lib, self.h, self.ac, spec, frame_lens, denoise)
+
+    def spectral_gain(self, spec, floor, frame_lens=None, denoise: Optional[Denoise] = None, return_gain: bool = True, apply: bool = False,
+                      in_place: bool = False):
+        """The smoothed gain f32 [B, T, F] and / or the gated spectrum of a spectrum and a floor (`_spectral_gain`)."""
+        return _spectral_gain(self.lib, self.h, self.ac, spec, floor, frame_lens, denoise, return_gain, apply, in_place)
+
     # ---- Griffin-Lim vocoder (csrc/griffinlim.hip): the STFT, its inverse, mel -> linear and the iteration
     def _frame_lens(self, lens, B: int, T: int) -> np.ndarray:
         ln = np.full(B, T, np.int32) if lens is None else _i32(lens)
@@ -1300,14 +1463,19 @@ class MelFrontEnd:
         _check(self.lib.mt2_model_memory(self.h, C.byref(w), C.byref(s)))
         return w.value, s.value
 
-    def from_audio(self, wav, sr_in: int, lens=None, trim_db: Optional[float] = None, return_bounds: bool = False):
+    def from_audio(self, wav, sr_in: int, lens=None, trim_db: Optional[float] = None, return_bounds: bool = False,
+                   denoise: Optional[Denoise] = None, return_noise: bool = False):
         """Prompt audio at any sample rate -> (mel [B, T, n_mels], mel_lens): resample to audio.sample_rate, peak-normalise and
         extract the mel (models/megatts2.py:335-336,339) with no host round trip.  Audio that already has that rate is only
         normalised, by the same kernels.  trim_db: leading / trailing silence is cut off between the normalisation and the mel
         (`trim`, :337 - the reference's order); None leaves the audio whole.  return_bounds: a third result, int32 [B, 2] = the
-        (start, end) of each utterance within its resampled audio."""
+        (start, end) of each utterance within its resampled audio.  denoise (None = off, exactly the call without it): a `Denoise`;
+        the normalised audio goes through `denoise` and is peak-normalised again before the trim, so that the trim's threshold and the
+        mel see the level a clean prompt would have; up to hop - 1 tail samples are dropped.  return_noise (needs denoise): a last
+        result, the figures float64 [B, 8] of the suppression (device; DENOISE_NAMES)."""
         import torch
         assert wav.is_cuda and wav.dim() == 2
+        assert denoise is not None or not return_noise
         wav = wav.contiguous().to(torch.float32)
         B, L = wav.shape
         if int(sr_in) == self.audio.sample_rate:
@@ -1316,12 +1484,20 @@ class MelFrontEnd:
             _check(self.lib.mt2_peak_normalize(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, _ptr(y)))
         else:
             y, ln = self.resample(wav, sr_in, lens, normalize=True)
+        figures = None
+        if denoise is not None:
+            d = self.denoise(y, ln, denoise, return_figures=return_noise)
+            y, ln = d[0], d[1]
+            figures = d[2] if return_noise else None
+            _check(self.lib.mt2_peak_normalize(self.h, _stream(), _ptr(y), _iptr(ln), y.shape[1], B, _ptr(y)))
         bounds = None
         if trim_db is not None:
             y, ln, bounds = self.trim(y, ln, trim_db)
         res = (self(y, ln), 1 + ln // self.audio.hop_length)
         if return_bounds:
             res += (np.stack([np.zeros_like(ln), ln], axis=1) if bounds is None else bounds,)
+        if return_noise:
+            res += (figures,)
         return res
 
 
@@ -2004,6 +2180,21 @@ def mcd_table(n_mels: int = 80, order: int = 13) -> np.ndarray:
     table = np.zeros((max(int(order), 0), max(int(n_mels), 0)), np.float32)
     _check(load_library().mt2_mcd_table(int(n_mels), int(order), table.ctypes.data_as(C.c_void_p)))
     return table
+
+
+def denoise_query(audio=None, lens=None, L_max: Optional[int] = None, B: Optional[int] = None, denoise: Optional[Denoise] = None):
+    """mt2_denoise_query (no device needed) -> (arena bytes, L_out, rank k, factor c) of one `denoise` call: lens int [B] (or L_max and
+    B: every utterance L_max samples).  The bytes are exactly the call's high water; L_out = hop * (max lens // hop); k and c are the
+    rank and the quantile-to-mean factor of the longest utterance.  It refuses what the call refuses."""
+    ac = _audio_struct(audio)
+    ln = None if lens is None else _i32(lens)
+    if ln is not None:
+        B, L_max = len(ln), int(ln.max()) if L_max is None else L_max
+    dc = (denoise or Denoise()).c_struct()
+    nbytes, lout, rank, c = C.c_longlong(0), C.c_longlong(0), C.c_int(0), C.c_float(0)
+    _check(load_library().mt2_denoise_query(C.byref(ac), C.byref(dc), _iptr(ln), int(L_max or 0), int(B or 0), C.byref(nbytes),
+                                            C.byref(lout), C.byref(rank), C.byref(c)))
+    return nbytes.value, lout.value, rank.value, c.value
 
 
 def griffin_lim_query(audio, mel_lens=None, T_max: Optional[int] = None, B: Optional[int] = None, n_iter: int = 32,

@@ -63,6 +63,16 @@ def main() -> None:
     ap.add_argument("--report-noise", action="store_true",
                     help="print, for each prompt file, the estimated noise power and SNR, the share of cells at the floor gain and the power "
                          "reduction in dB (measured on the GPU; the prompts are denoised only with --denoise-prompt)")
+    ap.add_argument("--dereverb-prompt", action="store_true",
+                    help="remove late reverberation from every prompt file on the GPU before its mel is taken (and before --denoise-prompt): "
+                         "weighted prediction error, a per-bin prediction filter; discrete reflections go, diffuse tails are helped only "
+                         "modestly, a STEADY tone is removed like a reflection")
+    ap.add_argument("--dereverb-taps", type=int, default=10, metavar="K", help="with --dereverb-prompt: the length of the prediction filter in frames, 1 to 16 (default 10)")
+    ap.add_argument("--dereverb-delay", type=int, default=3, metavar="D", help="with --dereverb-prompt: the frames skipped before the prediction, 1 to 8 (default 3)")
+    ap.add_argument("--dereverb-iterations", type=int, default=3, metavar="I", help="with --dereverb-prompt: variance / filter passes, 1 to 8 (default 3)")
+    ap.add_argument("--report-reverb", action="store_true",
+                    help="print, for each prompt file, the power the de-reverberation removes in dB and the bins filtered and passed through "
+                         "(measured on the GPU; the prompts are de-reverberated only with --dereverb-prompt)")
     ap.add_argument("--reference-wav", metavar="PATH",
                     help="a recording of the same sentence: print the mel-cepstral distortion (dB, along the DTW path of the cepstra), the largest "
                          "cell, and F0 RMSE, register offset and voiced / unvoiced error along the same path, of the generated audio against it")
@@ -86,12 +96,24 @@ def main() -> None:
     phones = [int(v) for v in a.phones.split(",")] if a.phones else None
     gl = {"n_iter": a.gl_iters} if a.vocoder == "griffin-lim" else None
     dn = M.Denoise(a.denoise_percentile, a.denoise_strength, 10.0 ** (a.denoise_floor_db / 20.0))
+    dr = M.Dereverb(delay=a.dereverb_delay, taps=a.dereverb_taps, iterations=a.dereverb_iterations)
     mel, lens, aux = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl, loudness_lufs=a.output_lufs,
                          peak_ceiling=a.peak_ceiling, true_peak_ceiling_dbtp=a.true_peak_ceiling,
                          **({"limiter": M.Limiter(a.limiter_window_ms, a.limiter_passes)} if a.limiter else {}),
-                         **({"denoise": dn} if a.denoise_prompt else {}))
+                         **({"denoise": dn} if a.denoise_prompt else {}), **({"dereverb": dr} if a.dereverb_prompt else {}))
     wrote = gl is not None or tts.hifi_gan is not None
     print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
+    if a.report_reverb:
+        import glob
+        from megatts2_amd import audio_io
+        paths = sorted(glob.glob(f"{a.wavs_dir}/*.wav"))
+        # with --dereverb-prompt the figures of the stage that ran; without it a measurement of the file, nothing is changed
+        rows = aux["prompt_reverb"] if a.dereverb_prompt else [{k: float(v[0]) for k, v in M.dereverb_audio(*audio_io.read_wav(p), dereverb=dr)[1].items()
+                                                                 if k in M.WPE_NAMES} for p in paths]
+        for path, st in zip(paths, rows):
+            print(f"reverberation of the prompt {path}{' (removed)' if a.dereverb_prompt else ' (measured only)'}: power {st['reduction_db']:.2f} dB, "
+                  f"{int(st['bins_filtered'])} bins filtered and {int(st['bins_passed'])} passed through over {int(st['frames'])} frames, largest tap "
+                  f"{st['max_tap']:.3f}")
     if a.report_noise:
         import glob
         from megatts2_amd import audio_io

@@ -451,7 +451,8 @@ int mt2_griffin_lim(mt2_model* m, void* stream, const mt2_audio_config* ac, cons
  * mt2_stft and mt2_istft - hiss, room tone or mains hum under a prompt is otherwise copied into the generated speech.  No counterpart in
  * the reference.  Parity with any outside denoiser (noisereduce, RNNoise, Audacity) is unpinned, and so is audible quality on real
  * speech: the test signals are analytic and the weights synthetic.  The rule is our own, held to tests/denoise_ref.py.  Out of scope:
- * non-stationary noise tracking, a streaming form, de-reverberation, multichannel.  THE RULE, for one utterance x[0 .. L) with the audio
+ * non-stationary noise tracking, a streaming form, multichannel; de-reverberation is a stage of its own, mt2_dereverb below, and runs in
+ * front of this one.  THE RULE, for one utterance x[0 .. L) with the audio
  * configuration's N = n_fft, h = hop, F = N / 2 + 1, Fp and S as above, T = 1 + L / h frames, and the parameters of mt2_denoise_config:
  *  1 Spectrum.  S = mt2_stft(x), exactly that call on this utterance alone: in a batch the STFT GEMM is launched per utterance, so that
  *    its tile is the one the utterance's own row count chooses.
@@ -520,6 +521,76 @@ int mt2_spectral_gain(mt2_model* m, void* stream, const mt2_audio_config* ac, co
 int mt2_denoise(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* wav,
                 const int32_t* lens /*host*/, int L_max, int B, const float* floor_in /*or NULL*/, float* floor_out /*or NULL*/,
                 double* figures /*or NULL*/, float* out, int Lout_max);
+
+/* ---- De-reverberation of prompt audio by weighted prediction error (csrc/wpe.hip): single-channel WPE (Nakatani et al. 2010; Yoshioka
+ * and Nakatani 2012) between mt2_stft and mt2_istft - the room of a phone or laptop recording is otherwise copied into the generated
+ * voice as hiss was.  It needs no weights.  No counterpart in the reference.  Parity with nara_wpe or any other implementation is
+ * unpinned, because none is on hand, and so is audible quality on real speech: the test signals are analytic.  The rule is our own, held
+ * to tests/wpe_ref.py.  Out of scope: multichannel WPE, a streaming (RLS) form, joint WPE and denoising, neural variance estimators.
+ * THE RULE, for one utterance and one bin f < F;  Y[t], t < T, is the bin's complex STFT column, read from the f32 spectrum and widened
+ * to double;  D, K, I, c, eps, load are the parameters of mt2_wpe_config;  all arithmetic is in double.
+ *  1 x_k[t] = Y[t - D - k] for k < K, 0 where the index is negative.  Set E = Y (E is the de-reverberated column).
+ *  2 Repeat I times:
+ *    2.1 P[t] = the mean of |E[t']|^2 over t' in [t - c, t + c] and [0, T), summed in ascending order and divided by the count.
+ *    2.2 lambda[t] = max(P[t], eps max_t P[t]) (fmax: a NaN never wins);  w[t] = 1 / lambda[t], one division.  If max P is 0 or not
+ *        finite the bin PASSES THROUGH (E = Y) and the loop ends.
+ *    2.3 R[j][k] = sum_t (x_j[t] w[t]) conj(x_k[t]),  p[j] = sum_t (x_j[t] w[t]) conj(Y[t]).  Order: lane l of 64 adds its frames l,
+ *        l + 64, ... in ascending order, then the 64 partial sums meet in the butterfly of strides 32, 16 .. 1 - an order that depends
+ *        on t and T alone.  No atomics.
+ *    2.4 R[j][j] += load tr(R) / K, tr(R) summed in ascending j.
+ *    2.5 Cholesky R = L L^H without pivoting, a column at a time, each entry R[i][j] minus its products in ascending order.  If a pivot
+ *        is <= 0 or not finite the bin passes through (E = Y) and the loop ends.
+ *    2.6 g = R^-1 p by the two triangular solves, then E[t] = Y[t] - sum_k conj(g[k]) x_k[t], k ascending.
+ *  3 Each part of E is rounded to f32 once.  A bin that passed through comes back bit for bit.
+ * mt2_dereverb is mt2_stft on each utterance alone (rule 1 of mt2_denoise, word for word), steps 1-3 per bin, then mt2_istft:  (T - 1) h
+ * samples, zeros beyond - up to h - 1 tail samples are dropped, as mt2_denoise does.  A clip too short to estimate K taps passes through
+ * unfiltered there:  T_b < D + 4 K gives E = Y for every bin (a 10-tap filter fitted on 4 - 14 frames damages clean audio by 4 - 10 dB).
+ * mt2_wpe_spectrum applies steps 1-3 at any T >= 1 (at T <= D every regressor is zero, the first pivot is 0 and every bin passes through).
+ * Figures, a row of MT2_WPE_FIELDS = 8 doubles:  0 sum |Y|^2   1 sum |E|^2 (of the f32 output)   2 10 log10([1] / [0])   3 T   4 bins
+ * filtered   5 bins passed through   6 max over f, k of |g|   7 the iterations completed by the bin that ran longest.  Sums: a bin's
+ * frames by 512 threads, each its own in ascending order, then a fixed tree;  the bins likewise by 256 threads (mt2_denoise's order).
+ * A sample, a filter and a figure depend on their utterance alone: a ragged batch is bit-identical to its utterances alone.  Non-finite
+ * input neither faults nor hangs - every loop has a fixed trip count - and promises nothing more.
+ * CONSEQUENCES.  Diffuse tails are helped only modestly (white noise under an exponential decay: late / early ratio -6.5 -> -9.6 dB at
+ * T60 0.6 s, -12.8 -> -13.8 dB at 0.3 s); discrete reflections are removed well.  A STEADY tone is predictable from its own past and is
+ * removed like a reflection.  Clean gated noise comes out slightly distorted (about -28 dB from itself).  Real speech is unpinned.
+ * Refused, on the host, with nothing launched and every output as it was:  a parameter outside its range or not finite;  B outside
+ * [1, 65535];  for mt2_dereverb a T_b outside what mt2_istft accepts (N / (2 h) + 2 <= T_b), for mt2_wpe_spectrum a frame count outside
+ * [1, T_max];  a T_max over MT2_WPE_MAX_FRAMES;  Lout_max < (max T_b - 1) h;  an output overlapping an input or another output
+ * (mt2_wpe_spectrum's spec_out may BE spec);  spectra not on 16 bytes.  `m` may be a bare handle;  scratch comes from its arena;  every
+ * call only enqueues. */
+#define MT2_WPE_FIELDS 8
+#define MT2_WPE_MAX_FRAMES MT2_DENOISE_MAX_FRAMES
+typedef struct mt2_wpe_config {
+    int32_t delay;             /* D in [1, 8];  3: frames skipped before the prediction - the direct sound and the window overlap */
+    int32_t taps;              /* K in [1, 16];  10 */
+    int32_t iterations;        /* I in [1, 8];  3 */
+    int32_t context;           /* c in [0, 4];  1: the variance is averaged over +-c frames */
+    double variance_floor;     /* eps in (0, 1];  1e-2, relative to the bin's largest variance */
+    double loading;            /* load in [0, 1e-2];  1e-8 */
+    int32_t reserved;          /* 0 */
+} mt2_wpe_config;
+/* Arena bytes of one mt2_dereverb call (exactly its high water) and its output length;  host only, no HIP call;  outputs may be NULL;
+ * lens NULL: every L_b = L_max.  It refuses what mt2_dereverb refuses for these arguments.  With r, q, taps, T_b, Fr, Rb as for
+ * mt2_denoise_query and C = sum_b F q(T_b) complex cells:
+ *   r(4 (2 q(Rb) + q(B) + 2 q(Fr) + 3 q(B) + B))  the call's one upload of block, row and column maps, lengths and pass-through flags
+ *   + r(4 Rb h) + r(4 Fr S) + 2 r(8 C) + r(40 B F) + r(4 Fr N)   blocks, spectrum, the columns of Y and of E, the bins' sums, frames
+ * L_out = (max_b T_b - 1) h. */
+int mt2_dereverb_query(const mt2_audio_config* ac, const mt2_wpe_config* wc, const int32_t* lens /*host or NULL*/, int L_max, int B,
+                       long long* workspace_bytes, long long* L_out);
+/* Steps 1-3 on a spectrum the caller supplies:  spec f32 [B, T_max, S] in mt2_stft's layout (device, on 16 bytes;  frames at or beyond
+ * frame_lens[b] are never read, pad columns never enter a result), frame_lens host int32 [B] -> spec_out f32 [B, T_max, S] (device;  it
+ * may be `spec` itself: then pad columns and frames at or beyond frame_lens[b] stay as they were, else they are zero).  filters (device
+ * f64 [B, Fp, K, 2] or NULL): g of every bin, re and im;  zeros for a bin that passed through and in the rows F .. Fp-1.  figures
+ * (device f64 [B, 8] or NULL).  Its arena: r(4 (3 q(B) + B)) + 2 r(8 C) + r(40 B F). */
+int mt2_wpe_spectrum(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_wpe_config* wc, const float* spec,
+                     const int32_t* frame_lens /*host*/, int T_max, int B, float* spec_out /*may be spec*/, double* filters /*or NULL*/,
+                     double* figures /*or NULL*/);
+/* The whole rule:  wav f32 [B, L_max] (device; samples at or beyond lens[b] are never read), lens host int32 [B] -> out f32
+ * [B, Lout_max] (device):  (T_b - 1) h samples, zeros beyond.  figures (device f64 [B, 8] or NULL).  Stage events (mt2_set_profiling):
+ * dr_stft, dr_wpe, dr_istft. */
+int mt2_dereverb(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_wpe_config* wc, const float* wav,
+                 const int32_t* lens /*host*/, int L_max, int B, double* figures /*or NULL*/, float* out, int Lout_max);
 
 /* ---- F0 tracking by YIN (de Cheveigne & Kawahara 2002, steps 2-5; csrc/f0.hip) and the pitch moments of a track.  No reference
  * counterpart: the reference tree has no pitch tracker (it would take one from librosa or pyworld).  Parity with librosa.yin / pyin

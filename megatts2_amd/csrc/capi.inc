@@ -1219,6 +1219,53 @@ int mt2_denoise(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt
     MT2_API_END
 }
 
+// de-reverberation by weighted prediction error (wpe.hip): the arena bytes of one mt2_dereverb call and its output length, without a HIP
+// call
+int mt2_dereverb_query(const mt2_audio_config* ac, const mt2_wpe_config* wc, const int32_t* lens, int L_max, int B, long long* workspace_bytes,
+                       long long* L_out) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(ac != nullptr, "null audio configuration");
+    wpe_check_config(wc);
+    std::vector<int> T;
+    const int T_cap = denoise_frames(*ac, lens, L_max, B, T);
+    if (workspace_bytes) *workspace_bytes = dereverb_arena_bytes(*ac, T);
+    if (L_out) *L_out = (long long)(T_cap - 1) * ac->hop_length;
+    MT2_API_END
+}
+
+// every refusal of the two calls is decided on the host before the first HIP call
+int mt2_wpe_spectrum(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_wpe_config* wc, const float* spec,
+                     const int32_t* frame_lens, int T_max, int B, float* spec_out, double* filters, double* figures) {
+    MT2_API_BEGIN
+    const WpeArgs a = wpe_check_config(wc);
+    const int T_cap = denoise_check_spec(ac, spec, frame_lens, T_max, B);
+    MT2_REQUIRE(spec_out != nullptr, "null spec_out");
+    MT2_REQUIRE((((uintptr_t)spec | (uintptr_t)spec_out) & 15) == 0 && ((((uintptr_t)filters | (uintptr_t)figures) & 7) == 0),
+                "misaligned buffers: the spectra on 16 bytes, the doubles on 8");
+    const size_t F = ac->n_fft / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
+    const size_t ns = sizeof(float) * (size_t)B * T_max * lds, nf = sizeof(double) * 2 * (size_t)B * Fp * a.taps,
+                 ng = sizeof(double) * MT2_WPE_FIELDS * (size_t)B;
+    MT2_REQUIRE(!outputs_overlap({{spec_out == spec ? nullptr : spec_out, ns}, {filters, nf}, {figures, ng}}, {{spec, ns}}), "overlapping buffers");
+    {
+        std::vector<int> c0;
+        wpe_columns(std::vector<int>(frame_lens, frame_lens + B), (int)F, c0);
+    }
+    MT2_AUDIO_CALL(m, stream);
+    wpe_spectrum_run(c, *ac, a, spec, frame_lens, T_max, B, T_cap, spec_out, filters, figures);
+    MT2_API_END
+}
+
+int mt2_dereverb(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_wpe_config* wc, const float* wav, const int32_t* lens,
+                 int L_max, int B, double* figures, float* out, int Lout_max) {
+    MT2_API_BEGIN
+    std::vector<int> T;
+    WpeArgs a{};
+    const int T_cap = dereverb_check(ac, wc, wav, lens, L_max, B, figures, out, Lout_max, T, a);
+    MT2_AUDIO_CALL(m, stream);
+    dereverb_run(c, *ac, a, wav, lens, L_max, B, T, T_cap, figures, out, Lout_max);
+    MT2_API_END
+}
+
 // :361-368 [+370]  zq = vq.decode(p_codes) repeated x8, cat([tc_latent_expand, zq]), decoder, optional vocoder - the part of
 // Megatts.forward behind the PLM, shared by mt2_synthesize_batch and mt2_synthesize_prompt_conditioned.  xdec: [D.R, H + Dq]
 // rows whose first H columns already hold the length-regulated tc_latents.

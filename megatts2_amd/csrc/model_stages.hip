@@ -3016,6 +3016,139 @@ static void spectral_gain_run(const Ctx& c, const mt2_audio_config& ac, const Dn
     MT2_HIP(launch_denoise_gain(p, c.s));
 }
 
+// ---- de-reverberation by weighted prediction error (wpe.hip) between the same two transforms: every refusal is decided here, on the
+// host, before the first HIP call
+struct WpeArgs { int delay, taps, iters, ctx; double eps, load; };
+static WpeArgs wpe_check_config(const mt2_wpe_config* wc) {
+    MT2_REQUIRE(wc != nullptr, "null dereverberation configuration");
+    MT2_REQUIRE(wc->delay >= 1 && wc->delay <= 8, "delay outside [1, 8]");
+    MT2_REQUIRE(wc->taps >= 1 && wc->taps <= kWpeMaxTaps, "taps outside [1, 16]");
+    MT2_REQUIRE(wc->iterations >= 1 && wc->iterations <= 8, "iterations outside [1, 8]");
+    MT2_REQUIRE(wc->context >= 0 && wc->context <= 4, "context outside [0, 4]");
+    MT2_REQUIRE(std::isfinite(wc->variance_floor) && wc->variance_floor > 0.0 && wc->variance_floor <= 1.0, "variance_floor outside (0, 1]");
+    MT2_REQUIRE(std::isfinite(wc->loading) && wc->loading >= 0.0 && wc->loading <= 1e-2, "loading outside [0, 1e-2]");
+    MT2_REQUIRE(wc->reserved == 0, "mt2_wpe_config.reserved must be 0");
+    return {wc->delay, wc->taps, wc->iterations, wc->context, wc->variance_floor, wc->loading};
+}
+// the bin-major columns of a batch: utterance b starts at c0[b] (in complex cells) and holds F columns of T_b rounded up to 4; -> cells
+static size_t wpe_columns(const std::vector<int>& T, int F, std::vector<int>& c0) {
+    size_t at = 0;
+    c0.resize(T.size());
+    for (size_t b = 0; b < T.size(); ++b) {
+        MT2_REQUIRE(at <= (size_t)INT_MAX, "batch too large for 32-bit column indices");
+        c0[b] = (int)at;
+        at += (size_t)F * ((T[b] + 3) & ~3);
+    }
+    MT2_REQUIRE(at <= (size_t)INT_MAX, "batch too large for 32-bit column indices");
+    return at;
+}
+static void wpe_fill(WpeP& p, const WpeArgs& a, const mt2_audio_config& ac, int B, int T_cap) {
+    p.F = ac.n_fft / 2 + 1; p.Fp = (p.F + 3) & ~3; p.lds = (2 * p.F + 3) & ~3; p.B = B; p.T_cap = T_cap;
+    p.delay = a.delay; p.taps = a.taps; p.iters = a.iters; p.ctx = a.ctx; p.eps = a.eps; p.load = a.load;
+}
+// transposition, the bins, the way back and the figures: the four launches of both calls
+static void wpe_launches(const Ctx& c, WpeP& p, double* filters, double* figures) {
+    p.filters = filters; p.fig = figures;
+    if (filters) MT2_HIP(hipMemsetAsync(filters, 0, sizeof(double) * 2 * (size_t)p.B * p.Fp * p.taps, c.s));      // the rows F .. Fp-1
+    MT2_HIP(launch_wpe_to_bins(p, c.s));
+    MT2_HIP(launch_wpe_bins(p, c.s));
+    MT2_HIP(launch_wpe_from_bins(p, c.s));
+    if (figures) MT2_HIP(launch_wpe_figures(p, c.s));
+}
+// the arena of one dereverb_run, in carve order: the plan, the reflect-padded blocks, the packed spectrum (filtered in place), the
+// columns of Y and of D, the bins' sums and the frames of the inverse STFT - taken whatever the optional arguments
+struct WpeWs { float *xp, *spec; float2 *cols, *cols_out; double* stat; float* frames; };
+template <class Ws> static WpeWs dereverb_carve(Ws& ws, IntPlan& ip, const mt2_audio_config& ac, size_t Fr, size_t Rb, size_t B, size_t cells) {
+    const size_t N = ac.n_fft, F = N / 2 + 1, lds = (2 * F + 3) & ~size_t(3);
+    WpeWs w{};
+    ip.carve(ws);
+    w.xp = ws.template get<float>(Rb * ac.hop_length);
+    w.spec = ws.template get<float>(Fr * lds);
+    w.cols = reinterpret_cast<float2*>(ws.template get<float>(2 * cells));
+    w.cols_out = reinterpret_cast<float2*>(ws.template get<float>(2 * cells));
+    w.stat = ws.template get<double>(B * F * kWpeStat);
+    w.frames = ws.template get<float>(Fr * N);
+    return w;
+}
+static long long dereverb_arena_bytes(const mt2_audio_config& ac, const std::vector<int>& T) {
+    const size_t B = T.size();
+    size_t Fr = 0, Rb = 0;
+    for (int t : T) { Fr += t; Rb += t - 1 + ac.n_fft / ac.hop_length; }
+    std::vector<int> c0;
+    const size_t cells = wpe_columns(T, ac.n_fft / 2 + 1, c0);
+    IntPlan ip;      // the entries of dereverb_run's plan, by size
+    for (size_t n : {Rb, Rb, B, Fr, Fr, B, B, B, B}) ip.add_fill(n, 0);
+    ArenaCount count;
+    dereverb_carve(count, ip, ac, Fr, Rb, B, cells);
+    return (long long)count.bytes;
+}
+// -> T_cap, with T filled
+static int dereverb_check(const mt2_audio_config* ac, const mt2_wpe_config* wc, const float* wav, const int* lens, int L_max, int B,
+                          const double* figures, const float* out, int Lout_max, std::vector<int>& T, WpeArgs& a) {
+    MT2_REQUIRE(ac != nullptr, "null audio configuration");
+    a = wpe_check_config(wc);
+    MT2_REQUIRE(wav != nullptr && lens != nullptr && out != nullptr, "bad buffers");
+    const int T_cap = denoise_frames(*ac, lens, L_max, B, T);
+    MT2_REQUIRE((long long)Lout_max >= (long long)(T_cap - 1) * ac->hop_length, "Lout_max smaller than (max T - 1) * hop_length");
+    MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)out) & 3) == 0 && ((uintptr_t)figures & 7) == 0, "misaligned buffers");
+    const size_t nw = sizeof(float) * (size_t)B * L_max, no = sizeof(float) * (size_t)B * Lout_max, ng = sizeof(double) * MT2_WPE_FIELDS * (size_t)B;
+    MT2_REQUIRE(!outputs_overlap({{out, no}, {figures, ng}}, {{wav, nw}}), "overlapping buffers");
+    return T_cap;
+}
+// enqueues only.  The STFT GEMM runs per utterance and the inverse one on the fixed tile, as in denoise_run.  An utterance of fewer than
+// delay + 4 taps frames is not filtered: its bins pass through.
+static void dereverb_run(const Ctx& c, const mt2_audio_config& ac, const WpeArgs& a, const float* wav, const int* lens, int L_max, int B,
+                         const std::vector<int>& T, int T_cap, double* figures, float* out, int Lout_max) {
+    gl_prepare_istft(c.m, ac);
+    IntPlan ip;
+    const StftRows r = stft_plan(ip, ac, lens, L_max, B, T_cap);
+    std::vector<int> row0(B), run(B), c0;
+    for (int b = 0, at = 0; b < B; at += T[b], ++b) { row0[b] = at; run[b] = T[b] >= a.delay + 4 * a.taps; }
+    const size_t cells = wpe_columns(T, ac.n_fft / 2 + 1, c0);
+    const int o_row0 = ip.add(row0), o_T = ip.add(T), o_c0 = ip.add(c0), o_run = ip.add(run);
+    const WpeWs w = dereverb_carve(c.ws, ip, ac, r.Fr, r.Rb, B, cells);
+    ip.send(c.m.pinned(), c.s);
+    WpeP p{};
+    wpe_fill(p, a, ac, B, T_cap);
+    p.spec = w.spec; p.spec_out = w.spec; p.row0 = ip.dev(o_row0); p.T = ip.dev(o_T); p.c0 = ip.dev(o_c0); p.run = ip.dev(o_run);
+    p.cols = w.cols; p.cols_out = w.cols_out; p.stat = w.stat;
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(launch_reflect_pad_blocks(wav, L_max, ip.dev(r.o_b), ip.dev(r.o_t), ip.dev(r.o_len), ac.hop_length, ac.n_fft / 2, w.xp, r.Rb, c.s));
+    MT2_HIP(hipMemsetAsync(w.spec, 0, sizeof(float) * (size_t)r.Fr * p.lds, c.s));      // the pad columns meet zero basis columns
+    for (int b = 0; b < B; ++b)
+        stft_gemm(c, ac, w.xp, r.Rb, ip.dev(r.o_base) + row0[b], w.spec + (size_t)row0[b] * p.lds, T[b]);
+    st.mark("dr_stft");
+    wpe_launches(c, p, nullptr, figures);
+    st.mark("dr_wpe");
+    {
+        FixedTile ft(c.m.opts);
+        istft_gemm(c, ac, w.spec, w.frames, r.Fr);
+    }
+    MT2_HIP(launch_istft_ola_wav(w.frames, ac.n_fft, ac.hop_length, c.m.gl_w2, ip.dev(o_row0), ip.dev(o_T), out, Lout_max, B, c.s));
+    st.mark("dr_istft");
+    st.finish();
+}
+// steps 1-3 on a caller's spectrum batch: utterance b owns the rows b T_max .. + frame_lens[b].  Its arena: the plan of 4 B words, the
+// columns of Y and of D, the bins' sums
+static void wpe_spectrum_run(const Ctx& c, const mt2_audio_config& ac, const WpeArgs& a, const float* spec, const int* frame_lens, int T_max,
+                             int B, int T_cap, float* spec_out, double* filters, double* figures) {
+    IntPlan ip;
+    std::vector<int> row0(B), T(frame_lens, frame_lens + B), run(B, 1), c0;
+    for (int b = 0; b < B; ++b) row0[b] = b * T_max;
+    const size_t cells = wpe_columns(T, ac.n_fft / 2 + 1, c0);
+    const int o_row0 = ip.add(row0), o_T = ip.add(T), o_c0 = ip.add(c0), o_run = ip.add(run);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    WpeP p{};
+    wpe_fill(p, a, ac, B, T_cap);
+    p.spec = spec; p.spec_out = spec_out; p.row0 = ip.dev(o_row0); p.T = ip.dev(o_T); p.c0 = ip.dev(o_c0); p.run = ip.dev(o_run);
+    p.cols = reinterpret_cast<float2*>(c.ws.get<float>(2 * cells));
+    p.cols_out = reinterpret_cast<float2*>(c.ws.get<float>(2 * cells));
+    p.stat = c.ws.get<double>((size_t)B * p.F * kWpeStat);
+    if (spec_out != spec) MT2_HIP(hipMemsetAsync(spec_out, 0, sizeof(float) * (size_t)B * T_max * p.lds, c.s));
+    wpe_launches(c, p, filters, figures);
+}
+
 }  // namespace mt2
 
 // the C ABI lives in capi.hip and includes this translation unit's helpers

@@ -554,6 +554,30 @@ hipError_t launch_denoise_select(const DenoiseP& p, hipStream_t s);
 hipError_t launch_denoise_gain(const DenoiseP& p, hipStream_t s);
 hipError_t launch_denoise_figures(const DenoiseP& p, hipStream_t s);
 
+// ---- de-reverberation by weighted prediction error between the two STFT GEMMs (wpe.hip; the rule is in its header and in megatts2_hip.h)
+// Utterance b owns the rows row0[b] .. row0[b] + T[b] of the spectrum ([rows, lds], as above) and the bin-major complex f32 columns
+// cols[c0[b] + f Tp .. + Tp], f < F, Tp = T[b] rounded up to 4 (c0 in float2 units, a multiple of 4); run[b] = 0: every bin of b passes through.
+constexpr int kWpeThreads = 512, kWpeMaxTaps = 16;
+constexpr int kWpeLdsFrames = 4096;           // the column sits in LDS beside its weights up to here: 16 bytes a frame, two workgroups a CU
+constexpr int kWpeStat = 5;                   // per bin: sum |Y|^2, sum |D|^2, filtered (1) or passed (0), max_k |g|, iterations completed
+size_t wpe_lds_bytes(int T_cap);              // host only: the dynamic LDS of launch_wpe_bins
+struct WpeP {
+    const float* spec; int lds;               // launch_wpe_to_bins: the spectrum rows (16-byte aligned)
+    float* spec_out;                          // launch_wpe_from_bins: the same row numbering; only the cells (t < T[b], f < F) are written
+    const int* row0; const int* T; const int* c0; const int* run;      // device [B]
+    int B, F, Fp, T_cap;                      // T_cap >= max_b T[b]: sizes the grids and the LDS
+    float2* cols; float2* cols_out;           // Y and D, bin-major; written whole (zeros in the frames T[b] .. Tp-1)
+    int delay, taps, iters, ctx;
+    double eps, load;
+    double* filters;                          // optional [B, Fp, taps, 2]: the rows f < F are written (zeros for a bin that passed through)
+    double* stat;                             // [B, F, kWpeStat]
+    double* fig;                              // launch_wpe_figures: [B, MT2_WPE_FIELDS]
+};
+hipError_t launch_wpe_to_bins(const WpeP& p, hipStream_t s);
+hipError_t launch_wpe_bins(const WpeP& p, hipStream_t s);
+hipError_t launch_wpe_from_bins(const WpeP& p, hipStream_t s);
+hipError_t launch_wpe_figures(const WpeP& p, hipStream_t s);
+
 // ---- Griffin-Lim vocoder (griffinlim.hip; the rule is in its header and in megatts2_hip.h) -------------------------------------------
 // Frames of a ragged batch are packed rows: utterance b owns rows row0[b] .. row0[b] + T[b] of S / R / Rprev ([rows, lds]: re(0..F-1) |
 // im(0..F-1) | zero pad, lds = 2F rounded up to 4), of A ([rows, lda]) and of the inverse-DFT GEMM's frames ([rows, N]).

@@ -21,7 +21,7 @@ import numpy as np
 from . import config as cfgmod
 from . import weights
 from .config import HIFIGAN_HOP_LENGTH, HIFIGAN_SR
-from .runtime import DENOISE_NAMES, Denoise, Limiter, NativeError, NativeModel  # noqa: F401  (Limiter, Denoise: arguments of synthesize / forward)
+from .runtime import DENOISE_NAMES, WPE_NAMES, Denoise, Dereverb, Limiter, NativeError, NativeModel  # noqa: F401  (Limiter, Denoise, Dereverb: arguments of synthesize / forward)
 from .sampling import PLMSampling, seed_array
 
 
@@ -40,7 +40,8 @@ def _frontend():
     return _FRONTEND
 
 
-def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, denoise: Optional[Denoise] = None):
+def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, denoise: Optional[Denoise] = None,
+                     dereverb: Optional[Dereverb] = None):
     """reference modules/tokenizer.py:107-125: 1-D waveform tensor (16 kHz) -> mel [80, T] (the reference
     returns channels first and `Megatts.forward` transposes it, models/megatts2.py:339).  Runs on the GPU
     (runtime.MelFrontEnd); a [B, L] input gives [B, 80, T].  sample_rate: the rate of `samples` when it is not
@@ -48,7 +49,9 @@ def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Option
     trailing silence is cut off first (MelFrontEnd.trim, `librosa.effects.trim(y, top_db=trim_db)` of :337; a batch
     is cut per row, T follows the longest row and the frames behind a shorter row's own are zero).  denoise (None = off, exactly
     the call without it): a `Denoise`; stationary noise is suppressed behind the resampling and in front of the trim
-    (MelFrontEnd.denoise, csrc/denoise.hip; the level is left as it comes out, up to hop - 1 tail samples are dropped)."""
+    (MelFrontEnd.denoise, csrc/denoise.hip; the level is left as it comes out, up to hop - 1 tail samples are dropped).  dereverb (None
+    = off, exactly the call without it): a `Dereverb`; late reverberation is removed by weighted prediction error behind the resampling
+    and in front of the denoiser (MelFrontEnd.dereverb, csrc/wpe.hip; likewise)."""
     import torch
     fe = _frontend()
     x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
@@ -57,8 +60,10 @@ def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Option
     if sample_rate is not None and int(sample_rate) != fe.audio.sample_rate:
         x = fe.resample(x, int(sample_rate))[0]
     lens = None
+    if dereverb is not None:
+        x, lens = fe.dereverb(x, None, dereverb)
     if denoise is not None:
-        x, lens = fe.denoise(x, None, denoise)
+        x, lens = fe.denoise(x, lens, denoise)
     if trim_db is not None:
         x, lens, _ = fe.trim(x, lens, top_db=trim_db)
     mel = fe(x, lens).transpose(1, 2)
@@ -190,6 +195,31 @@ def denoise_audio(samples, sample_rate: Optional[int] = None, lens=None, denoise
     fig = fig.cpu().numpy()
     res = {k: fig[:, i].copy() for i, k in enumerate(DENOISE_NAMES)}
     res["out_lens"], res["floor"] = out_lens, used.cpu().numpy()
+    out = out.cpu().numpy()
+    return (out[0] if flat else out), res
+
+
+def dereverb_audio(samples, sample_rate: Optional[int] = None, lens=None, dereverb: Optional[Dereverb] = None):
+    """De-reverberation of a 1-D waveform or a [B, L] batch on the GPU by weighted prediction error, the rule of csrc/wpe.hip
+    (MelFrontEnd.dereverb; no reference counterpart; parity with nara_wpe and audible quality on real speech unpinned): per bin a
+    prediction filter estimated from the recording itself removes what is predictable from the frames at least `delay` back.  Discrete
+    reflections go, diffuse tails are helped only modestly, and a steady tone is removed like a reflection.  sample_rate: the rate of
+    `samples` when it is not 16 kHz - they are resampled on the GPU first (not normalised), and the result is at 16 kHz.  lens: the real
+    samples of each row.  dereverb: a `Dereverb` (None: its defaults).  -> (out float32 numpy [B, hop * (L // hop)] ([.] for a 1-D
+    waveform), dict: out_lens int32 [B] and float64 [B] power_in, power_out, reduction_db, frames, bins_filtered, bins_passed, max_tap,
+    iterations)."""
+    import torch
+    fe = _frontend()
+    flat = (samples.dim() if hasattr(samples, "dim") else np.asarray(samples).ndim) == 1
+    x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
+    x = (x.unsqueeze(0) if x.dim() == 1 else x).to("cuda", torch.float32)
+    ln = lens
+    if sample_rate is not None and int(sample_rate) != fe.audio.sample_rate:
+        x, ln = fe.resample(x, int(sample_rate), ln)
+    out, out_lens, fig = fe.dereverb(x, ln, dereverb or Dereverb(), return_figures=True)
+    fig = fig.cpu().numpy()
+    res = {k: fig[:, i].copy() for i, k in enumerate(WPE_NAMES)}
+    res["out_lens"] = out_lens
     out = out.cpu().numpy()
     return (out[0] if flat else out), res
 
@@ -979,10 +1009,13 @@ class Megatts:
     # denoise (None = off; a runtime.Denoise): every prompt file, 16 kHz ones too, goes through MelFrontEnd.from_audio(denoise=...):
     # resample, peak-normalise, suppress stationary noise (csrc/denoise.hip), peak-normalise, trim.  aux["prompt_noise"] then holds
     # one dict per prompt file with the figures of the suppression (DENOISE_NAMES).
+    # dereverb (None = off; a runtime.Dereverb): likewise through from_audio(dereverb=...): resample, peak-normalise, remove late
+    # reverberation by weighted prediction error (csrc/wpe.hip), the denoiser behind it if asked for, peak-normalise, trim.
+    # aux["prompt_reverb"] then holds one dict per prompt file with the figures of the stage (WPE_NAMES).
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
                 phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None, vocoder=None,
                 loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0, true_peak_ceiling_dbtp: Optional[float] = None,
-                limiter=None, denoise: Optional[Denoise] = None):
+                limiter=None, denoise: Optional[Denoise] = None, dereverb: Optional[Dereverb] = None):
         import torch
         if true_peak_ceiling_dbtp is not None and loudness_lufs is None:
             raise ValueError("true_peak_ceiling_dbtp caps the gain of the loudness normalisation: it needs loudness_lufs")
@@ -1008,17 +1041,20 @@ class Megatts:
         if not wavs:
             raise NativeError(f"no *.wav under {wavs_dir}")
 
-        prompt_noise = []
+        prompt_noise, prompt_reverb = [], []
 
         def prompt_mel(w):
             y, sr = audio_io.read_wav(w)
-            if denoise is not None:
+            if denoise is not None or dereverb is not None:
                 if sr != HIFIGAN_SR and not resample:
                     raise ValueError(f"{w}: {sr} Hz, expected {HIFIGAN_SR} Hz (resample=False)")
-                mel, _, fig = _frontend().from_audio(torch.from_numpy(y).unsqueeze(0).cuda(), sr, trim_db=trim_db, denoise=denoise,
-                                                     return_noise=True)
-                prompt_noise.append(dict(zip(DENOISE_NAMES, fig[0].cpu().numpy().tolist())))
-                return mel[0]
+                res = _frontend().from_audio(torch.from_numpy(y).unsqueeze(0).cuda(), sr, trim_db=trim_db, denoise=denoise,
+                                             return_noise=denoise is not None, dereverb=dereverb, return_reverb=dereverb is not None)
+                if denoise is not None:
+                    prompt_noise.append(dict(zip(DENOISE_NAMES, res[2][0].cpu().numpy().tolist())))
+                if dereverb is not None:
+                    prompt_reverb.append(dict(zip(WPE_NAMES, res[-1][0].cpu().numpy().tolist())))
+                return res[0][0]
             if sr == HIFIGAN_SR and trim_db is None:          # audio_io.load_audio's two steps
                 return extract_mel_spec(torch.from_numpy(audio_io.normalize(y))).transpose(0, 1)
             if sr != HIFIGAN_SR and not resample:
@@ -1047,6 +1083,8 @@ class Megatts:
             mel, mel_lens, aux = self.synthesize(phone_tokens, mels, return_aux=True, griffin_lim=gl or True, **level)
             if denoise is not None:
                 aux["prompt_noise"] = prompt_noise
+            if dereverb is not None:
+                aux["prompt_reverb"] = prompt_reverb
             if out_path:
                 prompt = levelled(self.vocode_griffin_lim(mels_prompt.unsqueeze(0).contiguous(), **gl)[0])
                 audio = torch.cat([prompt, aux["wav"][0, :(int(mel_lens[0]) - 1) * HIFIGAN_HOP_LENGTH]])
@@ -1056,6 +1094,8 @@ class Megatts:
                                              **(level if self.hifi_gan is not None else {}))
         if denoise is not None:
             aux["prompt_noise"] = prompt_noise
+        if dereverb is not None:
+            aux["prompt_reverb"] = prompt_reverb
         if self.hifi_gan is not None and out_path:
             # :370-375  prompt audio (vocoded first prompt mel) followed by the generated audio; decode_batch output
             # includes the generator's inference padding on both sides, exactly as the reference concatenates it

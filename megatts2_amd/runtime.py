@@ -78,6 +78,34 @@ class MT2DenoiseConfig(C.Structure):
 DENOISE_NAMES = ("noise_db", "snr_db", "floored_share", "reduction_db", "frames", "rank", "mean_frame_power", "noise_power")
 
 
+@dataclasses.dataclass(frozen=True)
+class Dereverb:
+    """The settings of the de-reverberation by weighted prediction error (csrc/wpe.hip; the rule is in include/megatts2_hip.h): per bin a
+    filter of `taps` frames (1 .. 16) predicts the late reverberation from the frames at least `delay` (1 .. 8) back and is subtracted;
+    `iterations` (1 .. 8) passes alternate between the variance of the result, averaged over +-`context` frames (0 .. 4) and floored
+    at `variance_floor` (in (0, 1]) of the bin's largest, and the filter; `loading` (0 .. 1e-2) is the diagonal loading of the normal
+    equations.  Discrete reflections are removed well, diffuse tails only modestly; a steady tone is predictable from its own past and
+    is removed like a reflection."""
+    delay: int = 3
+    taps: int = 10
+    iterations: int = 3
+    context: int = 1
+    variance_floor: float = 1e-2
+    loading: float = 1e-8
+
+    def c_struct(self) -> "MT2WpeConfig":
+        return MT2WpeConfig(int(self.delay), int(self.taps), int(self.iterations), int(self.context), float(self.variance_floor),
+                            float(self.loading), 0)
+
+
+class MT2WpeConfig(C.Structure):
+    _fields_ = [("delay", C.c_int32), ("taps", C.c_int32), ("iterations", C.c_int32), ("context", C.c_int32),
+                ("variance_floor", C.c_double), ("loading", C.c_double), ("reserved", C.c_int32)]
+
+
+WPE_NAMES = ("power_in", "power_out", "reduction_db", "frames", "bins_filtered", "bins_passed", "max_tap", "iterations")
+
+
 class MT2Config(C.Structure):
     _fields_ = [
         ("mel_bins", C.c_int32), ("mrte_hidden", C.c_int32), ("mrte_kernel", C.c_int32), ("mrte_stride", C.c_int32),
@@ -149,6 +177,9 @@ def load_library():
     lib.mt2_noise_floor.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
     lib.mt2_spectral_gain.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 3
     lib.mt2_denoise.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int]
+    lib.mt2_dereverb_query.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 2
+    lib.mt2_wpe_spectrum.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib.mt2_dereverb.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int]
     lib.mt2_stft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_istft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_mel_to_linear.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
@@ -449,6 +480,54 @@ def _denoise(lib, h, ac, wav, lens=None, denoise: Optional[Denoise] = None, nois
     if return_figures:
         res += (fig,)
     return res
+
+
+def _wpe_spectrum(lib, h, ac, spec, frame_lens=None, dereverb: Optional[Dereverb] = None, return_filters: bool = False,
+                  return_figures: bool = False, in_place: bool = False):
+    """mt2_wpe_spectrum on the handle `h`: steps 1-3 of the weighted-prediction-error rule on a spectrum (complex64 [B, T, F], or f32
+    [B, T, S] in mt2_stft's layout; device), at any T >= 1 -> the de-reverberated spectrum in the form it came in (in_place: written
+    over an f32 [B, T, S] spectrum itself; pad columns and frames at or beyond frame_lens[b] then stay as they were, else they are
+    zero).  return_filters: also the prediction filters complex128 [B, F, K] (zeros for a bin that passed through); return_figures:
+    also float64 [B, 8] (device; WPE_NAMES).  -> spectrum, or (spectrum[, filters][, figures])."""
+    import torch
+    F = ac.n_fft // 2 + 1
+    packed = _packed_spec(spec, F)
+    B, T, S = packed.shape
+    ln = np.full(B, T, np.int32) if frame_lens is None else _i32(frame_lens)
+    assert ln.shape == (B,)
+    cfg = dereverb or Dereverb()
+    wc = cfg.c_struct()
+    assert not in_place or packed is spec, "in_place needs the f32 [B, T, S] layout"
+    out = packed if in_place else torch.empty_like(packed)
+    Fp = (F + 3) & ~3
+    filt = torch.empty(B, Fp, int(cfg.taps), 2, device=packed.device, dtype=torch.float64) if return_filters else None
+    fig = torch.empty(B, len(WPE_NAMES), device=packed.device, dtype=torch.float64) if return_figures else None
+    _check(lib.mt2_wpe_spectrum(h, _stream(), C.byref(ac), C.byref(wc), _ptr(packed), _iptr(ln), T, B, _ptr(out), _ptr(filt), _ptr(fig)))
+    if spec.is_complex():
+        out = torch.complex(out[..., :F], out[..., F:2 * F])
+    res = (out,)
+    if return_filters:
+        res += (torch.view_as_complex(filt[:, :F].contiguous()),)
+    if return_figures:
+        res += (fig,)
+    return res[0] if len(res) == 1 else res
+
+
+def _dereverb(lib, h, ac, wav, lens=None, dereverb: Optional[Dereverb] = None, return_figures: bool = False, out=None):
+    """mt2_dereverb on the handle `h`: wav f32 [B, L] (device) -> the de-reverberated audio f32 [B, (T - 1) * hop] with T = 1 + max lens
+    // hop, utterance b holding hop * (lens[b] // hop) samples (up to hop - 1 tail samples are dropped, as `_denoise` does) and zeros
+    beyond; samples at or beyond lens[b] are never read.  An utterance of fewer than delay + 4 * taps frames passes through the two
+    transforms unfiltered.  return_figures: also float64 [B, 8] (device; WPE_NAMES).  out: a contiguous f32 [B, >= (T - 1) * hop]
+    device tensor to write into (not wav).  -> (out, out_lens int32 [B][, figures]).  The call only enqueues."""
+    import torch
+    wav, ln, B, L = _wav_lens(wav, lens)
+    hop = ac.hop_length
+    out_lens = (hop * (ln // hop)).astype(np.int32)
+    out = _out_rows(out, B, wav, lambda: max(int(out_lens.max()), 1))
+    wc = (dereverb or Dereverb()).c_struct()
+    fig = torch.empty(B, len(WPE_NAMES), device=wav.device, dtype=torch.float64) if return_figures else None
+    _check(lib.mt2_dereverb(h, _stream(), C.byref(ac), C.byref(wc), _ptr(wav), _iptr(ln), L, B, _ptr(fig), _ptr(out), out.shape[1]))
+    return (out, out_lens, fig) if return_figures else (out, out_lens)
 
 
 def _workspace_fill(lib, h, byte: int) -> None:
@@ -885,6 +964,16 @@ class NativeModel:
                       in_place: bool = False, audio=None):
         """The smoothed gain and / or the gated spectrum of a spectrum and a floor (`_spectral_gain`)."""
         return _spectral_gain(self.lib, self.h, _audio_struct(audio), spec, floor, frame_lens, denoise, return_gain, apply, in_place)
+
+    # ---- de-reverberation by weighted prediction error (csrc/wpe.hip) on the model's handle, as MelFrontEnd's
+    def dereverb(self, wav, lens=None, dereverb: Optional[Dereverb] = None, return_figures: bool = False, out=None, audio=None):
+        """De-reverberated audio of wav f32 [B, L] (`_dereverb`)."""
+        return _dereverb(self.lib, self.h, _audio_struct(audio), wav, lens, dereverb, return_figures, out)
+
+    def wpe_spectrum(self, spec, frame_lens=None, dereverb: Optional[Dereverb] = None, return_filters: bool = False, in_place: bool = False,
+                     return_figures: bool = False, audio=None):
+        """Steps 1-3 of the rule on a spectrum (`_wpe_spectrum`)."""
+        return _wpe_spectrum(self.lib, self.h, _audio_struct(audio), spec, frame_lens, dereverb, return_filters, return_figures, in_place)
 
     def align_durations(self, hi, y_lens, syn_dur, phone_lens=None):
         """mt2_align_durations: the path's `hi` int32 [B, Ty] (device, from `dtw` with these y_lens) and the synthetic durations
@@ -1356,6 +1445,18 @@ class MelFrontEnd:
         """The smoothed gain f32 [B, T, F] and / or the gated spectrum of a spectrum and a floor (`_spectral_gain`)."""
         return _spectral_gain(self.lib, self.h, self.ac, spec, floor, frame_lens, denoise, return_gain, apply, in_place)
 
+    # ---- de-reverberation by weighted prediction error (csrc/wpe.hip): a per-bin prediction filter between the STFT and its inverse
+    def dereverb(self, wav, lens=None, dereverb: Optional[Dereverb] = None, return_figures: bool = False, out=None):
+        """De-reverberated audio of wav f32 [B, L] at audio.sample_rate (`_dereverb`) -> (out f32 [B, hop * (max lens // hop)], out_lens
+        int32 [B][, figures float64 [B, 8]])."""
+        return _dereverb(self.lib, self.h, self.ac, wav, lens, dereverb, return_figures, out)
+
+    def wpe_spectrum(self, spec, frame_lens=None, dereverb: Optional[Dereverb] = None, return_filters: bool = False, in_place: bool = False,
+                     return_figures: bool = False):
+        """Steps 1-3 of the rule on a spectrum, e.g. `stft` of a recording, at any T >= 1 (`_wpe_spectrum`) -> the spectrum[, the
+        filters complex128 [B, F, K]][, figures float64 [B, 8]]."""
+        return _wpe_spectrum(self.lib, self.h, self.ac, spec, frame_lens, dereverb, return_filters, return_figures, in_place)
+
     # ---- Griffin-Lim vocoder (csrc/griffinlim.hip): the STFT, its inverse, mel -> linear and the iteration
     def _frame_lens(self, lens, B: int, T: int) -> np.ndarray:
         ln = np.full(B, T, np.int32) if lens is None else _i32(lens)
@@ -1464,7 +1565,8 @@ class MelFrontEnd:
         return w.value, s.value
 
     def from_audio(self, wav, sr_in: int, lens=None, trim_db: Optional[float] = None, return_bounds: bool = False,
-                   denoise: Optional[Denoise] = None, return_noise: bool = False):
+                   denoise: Optional[Denoise] = None, return_noise: bool = False, dereverb: Optional[Dereverb] = None,
+                   return_reverb: bool = False):
         """Prompt audio at any sample rate -> (mel [B, T, n_mels], mel_lens): resample to audio.sample_rate, peak-normalise and
         extract the mel (models/megatts2.py:335-336,339) with no host round trip.  Audio that already has that rate is only
         normalised, by the same kernels.  trim_db: leading / trailing silence is cut off between the normalisation and the mel
@@ -1472,10 +1574,15 @@ class MelFrontEnd:
         (start, end) of each utterance within its resampled audio.  denoise (None = off, exactly the call without it): a `Denoise`;
         the normalised audio goes through `denoise` and is peak-normalised again before the trim, so that the trim's threshold and the
         mel see the level a clean prompt would have; up to hop - 1 tail samples are dropped.  return_noise (needs denoise): a last
-        result, the figures float64 [B, 8] of the suppression (device; DENOISE_NAMES)."""
+        result, the figures float64 [B, 8] of the suppression (device; DENOISE_NAMES).  dereverb (None = off, exactly the call
+        without it): a `Dereverb`; the normalised audio goes through `dereverb` in FRONT of the denoiser - WPE is a linear filter and
+        must see the recording before a non-linear gate breaks the linear relation it estimates - and is peak-normalised again once, behind
+        the last of the two stages (resample -> normalise -> dereverb -> denoise -> normalise -> trim);
+        return_reverb (needs dereverb): the very last result, its figures float64 [B, 8] (device; WPE_NAMES)."""
         import torch
         assert wav.is_cuda and wav.dim() == 2
         assert denoise is not None or not return_noise
+        assert dereverb is not None or not return_reverb
         wav = wav.contiguous().to(torch.float32)
         B, L = wav.shape
         if int(sr_in) == self.audio.sample_rate:
@@ -1484,6 +1591,13 @@ class MelFrontEnd:
             _check(self.lib.mt2_peak_normalize(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, _ptr(y)))
         else:
             y, ln = self.resample(wav, sr_in, lens, normalize=True)
+        reverb = None
+        if dereverb is not None:
+            d = self.dereverb(y, ln, dereverb, return_figures=return_reverb)
+            y, ln = d[0], d[1]
+            reverb = d[2] if return_reverb else None
+            if denoise is None:      # with the denoiser behind it, its own normalisation is the one in front of the trim
+                _check(self.lib.mt2_peak_normalize(self.h, _stream(), _ptr(y), _iptr(ln), y.shape[1], B, _ptr(y)))
         figures = None
         if denoise is not None:
             d = self.denoise(y, ln, denoise, return_figures=return_noise)
@@ -1498,6 +1612,8 @@ class MelFrontEnd:
             res += (np.stack([np.zeros_like(ln), ln], axis=1) if bounds is None else bounds,)
         if return_noise:
             res += (figures,)
+        if return_reverb:
+            res += (reverb,)
         return res
 
 
@@ -2195,6 +2311,21 @@ def denoise_query(audio=None, lens=None, L_max: Optional[int] = None, B: Optiona
     _check(load_library().mt2_denoise_query(C.byref(ac), C.byref(dc), _iptr(ln), int(L_max or 0), int(B or 0), C.byref(nbytes),
                                             C.byref(lout), C.byref(rank), C.byref(c)))
     return nbytes.value, lout.value, rank.value, c.value
+
+
+def dereverb_query(audio=None, lens=None, L_max: Optional[int] = None, B: Optional[int] = None, dereverb: Optional[Dereverb] = None):
+    """mt2_dereverb_query (no device needed) -> (arena bytes, L_out) of one `dereverb` call: lens int [B] (or L_max and B: every
+    utterance L_max samples).  The bytes are exactly the call's high water; L_out = hop * (max lens // hop).  It refuses what the call
+    refuses."""
+    ac = _audio_struct(audio)
+    ln = None if lens is None else _i32(lens)
+    if ln is not None:
+        B, L_max = len(ln), int(ln.max()) if L_max is None else L_max
+    wc = (dereverb or Dereverb()).c_struct()
+    nbytes, lout = C.c_longlong(0), C.c_longlong(0)
+    _check(load_library().mt2_dereverb_query(C.byref(ac), C.byref(wc), _iptr(ln), int(L_max or 0), int(B or 0), C.byref(nbytes),
+                                             C.byref(lout)))
+    return nbytes.value, lout.value
 
 
 def griffin_lim_query(audio, mel_lens=None, T_max: Optional[int] = None, B: Optional[int] = None, n_iter: int = 32,

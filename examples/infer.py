@@ -73,6 +73,16 @@ def main() -> None:
     ap.add_argument("--report-reverb", action="store_true",
                     help="print, for each prompt file, the power the de-reverberation removes in dB and the bins filtered and passed through "
                          "(measured on the GPU; the prompts are de-reverberated only with --dereverb-prompt)")
+    ap.add_argument("--declip-prompt", action="store_true",
+                    help="restore the clipped samples of every prompt file on the GPU, first of all and at the file's own sample rate (sparse "
+                         "restoration, A-SPADE): hard clipping with flat tops only - soft clipping, or clipping behind a resampler or a lossy "
+                         "codec, is not detected; the restoration is a sparse guess, not the original")
+    ap.add_argument("--declip-frame", type=int, default=1024, metavar="N", help="with --declip-prompt: the frame length, 256, 512, 1024 or 2048 samples (default 1024)")
+    ap.add_argument("--declip-tol", type=float, default=1e-3, metavar="X", help="with --declip-prompt / --report-clipping: samples within X of the extreme, relative, count as clipped (default 1e-3)")
+    ap.add_argument("--declip-eps", type=float, default=0.02, metavar="E", help="with --declip-prompt: a frame stops once its residual is under E of its norm (default 0.02)")
+    ap.add_argument("--report-clipping", action="store_true",
+                    help="print, for each prompt file, whether it is clipped, the two levels and the share of samples at them, and with "
+                         "--declip-prompt the iterations and the power change; alone it only detects (on the GPU) and warns")
     ap.add_argument("--reference-wav", metavar="PATH",
                     help="a recording of the same sentence: print the mel-cepstral distortion (dB, along the DTW path of the cepstra), the largest "
                          "cell, and F0 RMSE, register offset and voiced / unvoiced error along the same path, of the generated audio against it")
@@ -97,12 +107,31 @@ def main() -> None:
     gl = {"n_iter": a.gl_iters} if a.vocoder == "griffin-lim" else None
     dn = M.Denoise(a.denoise_percentile, a.denoise_strength, 10.0 ** (a.denoise_floor_db / 20.0))
     dr = M.Dereverb(delay=a.dereverb_delay, taps=a.dereverb_taps, iterations=a.dereverb_iterations)
+    dc = M.Declip(frame=a.declip_frame, tol=a.declip_tol, eps=a.declip_eps)
     mel, lens, aux = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl, loudness_lufs=a.output_lufs,
                          peak_ceiling=a.peak_ceiling, true_peak_ceiling_dbtp=a.true_peak_ceiling,
                          **({"limiter": M.Limiter(a.limiter_window_ms, a.limiter_passes)} if a.limiter else {}),
-                         **({"denoise": dn} if a.denoise_prompt else {}), **({"dereverb": dr} if a.dereverb_prompt else {}))
+                         **({"denoise": dn} if a.denoise_prompt else {}), **({"dereverb": dr} if a.dereverb_prompt else {}),
+                         **({"declip": dc} if a.declip_prompt else {}))
     wrote = gl is not None or tts.hifi_gan is not None
     print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
+    if a.report_clipping:
+        import glob
+        from megatts2_amd import audio_io
+        paths = sorted(glob.glob(f"{a.wavs_dir}/*.wav"))
+        # with --declip-prompt the figures of the stage that ran; without it detection alone on the file as it is, nothing is changed
+        rows = aux["prompt_clipping"] if a.declip_prompt else [{k: float(v[0]) for k, v in M.detect_clipping(audio_io.read_wav(p)[0], declip=dc).items()}
+                                                                 for p in paths]
+        for path, st in zip(paths, rows):
+            if not st["clipped"]:
+                print(f"clipping of the prompt {path}: none detected (extremes {st['lo']:.4f} and {st['hi']:.4f})")
+            elif a.declip_prompt:
+                print(f"clipping of the prompt {path} (restored): levels {st['lo']:.4f} and {st['hi']:.4f}, {100 * st['share']:.2f} % of the samples, "
+                      f"{int(st['frames_iterated'])} frames iterated, {st['mean_iterations']:.1f} iterations on average and {int(st['max_iterations'])} "
+                      f"at most, power {st['power_change_db']:+.2f} dB")
+            else:
+                print(f"WARNING: the prompt {path} is clipped: levels {st['lo']:.4f} and {st['hi']:.4f}, {100 * st['share']:.2f} % of the samples; its "
+                      f"distortion goes into the cloned voice (--declip-prompt restores it)")
     if a.report_reverb:
         import glob
         from megatts2_amd import audio_io

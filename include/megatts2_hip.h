@@ -592,6 +592,80 @@ int mt2_wpe_spectrum(mt2_model* m, void* stream, const mt2_audio_config* ac, con
 int mt2_dereverb(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_wpe_config* wc, const float* wav,
                  const int32_t* lens /*host*/, int L_max, int B, double* figures /*or NULL*/, float* out, int Lout_max);
 
+/* ---- Declipping of prompt audio by sparsity (csrc/declip.hip): A-SPADE (Kitic, Bertin and Gribonval 2015; the analysis variant in the
+ * declipping survey of Zaviska, Rajmic, Ozerov and Rencker 2021) - a prompt recorded too hot has flat tops, the mel front end sees their
+ * harmonic distortion and the timbre encoder reproduces it.  It needs no weights.  No counterpart in the reference.  Parity with any
+ * outside declipper is unpinned, because none is on hand, and so is audible quality on real speech: the test signals are analytic.  The
+ * rule is our own, held to tests/declip_ref.py.  It runs at the audio's OWN sample rate, in front of any resampling or normalisation:
+ * both turn flat tops into ripple that nothing can recognise as clipping.  Out of scope: redundant (zero-padded) frames, S-SPADE,
+ * social-sparsity shrinkage, soft-clip models, a streaming form, multichannel.
+ * THE RULE, for one utterance y[0 .. len) (f32) and the parameters of mt2_declip_config;  N = frame, hop = N / 4, K = N / 2 + 1.
+ *  1 Detection, every comparison in f32, the counts integers.  hi = max y, lo = min y (fmax / fmin: a NaN never wins);  with `level`
+ *    set hi = (f32)level, lo = -hi.  n_hi = #{y >= hi - tol |hi|} if hi > 0, else 0;  n_lo = #{y <= lo + tol |lo|} if lo < 0, else 0
+ *    (the product and the sum each rounded to f32, never fused).  A side is CLIPPED iff its count >= max(min_count, ceil(min_share len))
+ *    (the ceiling in double).  A sample is H (at or over the high threshold of a clipped high side), L (likewise low) or reliable.  An
+ *    utterance with no clipped side, or with a sample that is not finite, PASSES THROUGH bit for bit.
+ *  2 Frames.  The utterance is zero-padded by N - hop in front and up to a multiple of hop plus N - hop behind:  T = ceil(len / hop) + 3
+ *    frames, frame t holding the samples t hop - 3 hop + n, n < N, so that every sample lies in exactly four frames;  pad samples are
+ *    reliable zeros.  w[n] = sqrt(0.5 - 0.5 cos(2 pi n / N)) is the analysis and the synthesis window;  F = (double)y w.
+ *  3 Per frame, in double;  A is the N-point real DFT scaled by 1 / sqrt(N), on the half spectrum of K bins (inner bins count twice in
+ *    norms).  If |F| = 0, or the frame has no H or L sample, or NONE of the utterance's own samples in it is reliable (pads anchor
+ *    nothing: a stretch that is clipped throughout, a square wave, comes back as it is), x = F and the frame does not iterate.
+ *    Otherwise x = F, u = 0, k = step, and for i = 1 .. max_iter (0: every ceil(K / step)):
+ *      v = A x + u;  zb keeps every bin whose |v|^2 >= the min(k, K)-th largest |v|^2 of the half spectrum, exactly - ties at the
+ *      threshold are all kept, so the rule has no order dependence;  x = proj(A^H (zb - u)), where proj sets reliable samples to F and
+ *      takes max(., F) on H and min(., F) on L;  d = A x - zb;  stop if |d| <= eps |F|;  otherwise u += d, and if i mod every = 0 then
+ *      k += step.
+ *    The transform is the library's own real FFT (an N / 2 point complex radix-2 in LDS; tests/declip_ref.py restates its order);  |v|^2
+ *    is fma(re, re, im im);  norms are summed by 256 threads, each its bins t, t + 256, .. in ascending order, then a fixed tree.
+ *  4 Synthesis.  s = sum_t x_t w / sum_t w^2 over the sample's four frames in ascending order (the sum of w^2 is 2 in exact arithmetic;
+ *    the actual sum divides), rounded to f32 once.  A reliable sample is written as the INPUT'S OWN BITS, an H sample as max(s, y), an L
+ *    sample as min(s, y): consistency with the clipped recording is exact in f32.  The output can exceed the input's peak - that is the
+ *    point - and the caller normalises after.
+ * Figures, a row of MT2_DECLIP_FIELDS = 8 doubles:  0 clipped (0 / 1)   1 hi   2 lo   3 the share of samples that are H or L   4 frames
+ * iterated   5 mean iterations over those frames   6 the largest iteration count   7 10 log10(sum out^2 / sum y^2).  mt2_clip_detect
+ * fills 0-3 and leaves 4-7 zero;  so does mt2_declip for an utterance that passes through.  A non-finite utterance reads 0, NaN, NaN, 0 ...
+ * A sample, a frame and a figure depend on their utterance alone: a ragged batch is bit-identical to its utterances alone.  Every loop
+ * has a trip count fixed by N, len and max_iter: non-finite values can neither fault nor hang.
+ * CONSEQUENCES.  A STEADY full-scale tone has several per cent of its samples within tol of its peak and reads as clipped;  the true
+ * tone satisfies the constraints, but the result need not equal it.  SOFT clipping, and clipping followed by lossy coding or a
+ * resampler, has no flat tops and is not detected.  The restoration is a sparse guess, not the original: on the test signal it gains 1
+ * to 29 dB of SDR.  Real speech is unpinned.
+ * Refused, on the host, with nothing launched and every output as it was:  a parameter outside its range or not finite where a finite
+ * one is required;  B outside [1, 65535];  a length outside [1, L_max];  an utterance of more than MT2_DECLIP_MAX_FRAMES frames;
+ * Lout_max under the longest length;  iters with T_max under the most frames;  an output overlapping an input or another output - in
+ * place is NOT offered, the overlap kernel reads the input's bits.  `m` may be a bare handle;  scratch comes from its arena;  every call
+ * only enqueues (the first call of a frame length on a handle uploads its table of twiddles and window, in double, made on the host). */
+#define MT2_DECLIP_FIELDS 8
+#define MT2_DECLIP_MAX_FRAMES 16384      /* frames of one utterance: 256 MiB of frame scratch at N = 2048;  69 s at 16 kHz and N = 256 */
+typedef struct mt2_declip_config {
+    int32_t frame;             /* N in {256, 512, 1024, 2048};  1024 */
+    int32_t min_count;         /* >= 1;  4 */
+    int32_t step;              /* s in [1, N / 2 + 1];  1 */
+    int32_t every;             /* r in [1, 64];  1 */
+    int32_t max_iter;          /* 0 = r ceil((N / 2 + 1) / s), or >= 1 */
+    int32_t reserved;          /* 0 */
+    double tol;                /* in [0, 0.1];  1e-3, relative to the level */
+    double min_share;          /* in [0, 1];  1e-4 of the utterance's samples */
+    double level;              /* NaN = detect, or the clipping level, positive and finite */
+    double eps;                /* in (0, 1);  0.02 */
+} mt2_declip_config;
+/* Arena bytes of one mt2_declip call and of one mt2_clip_detect call (exactly their high water) and the frames of the longest utterance;
+ * host only, no HIP call;  outputs may be NULL;  lens NULL: every len_b = L_max.  It refuses what the calls refuse for these arguments.
+ * With r(x) = x rounded up to 256 bytes and R = sum_b T_b:  detection r(4 * 2 B) + r(32 B);  the whole call r(4 * 3 B) + r(32 B) + r(4 R)
+ * + r(8 R N) - the one upload of lengths, needs and first rows, the detection words, the iteration counts, the frames in double. */
+int mt2_declip_query(const mt2_declip_config* dc, const int32_t* lens /*host or NULL*/, int L_max, int B, long long* workspace_bytes,
+                     long long* detect_bytes, long long* T_max);
+/* Step 1 alone:  wav f32 [B, L_max] (device; samples at or beyond lens[b] are never read), lens host int32 [B] -> figures (device f64
+ * [B, 8]).  Nothing is restored. */
+int mt2_clip_detect(mt2_model* m, void* stream, const mt2_declip_config* dc, const float* wav, const int32_t* lens /*host*/, int L_max, int B,
+                    double* figures);
+/* The whole rule:  -> out f32 [B, Lout_max] (device; the samples j < lens[b] are written, the rest are left untouched).  figures (device
+ * f64 [B, 8] or NULL).  iters (device int32 [B, T_max] or NULL): the iterations of every frame, zero for a frame that did not iterate
+ * and beyond T_b.  Stage events (mt2_set_profiling): dc_detect, dc_frames, dc_overlap, dc_figures. */
+int mt2_declip(mt2_model* m, void* stream, const mt2_declip_config* dc, const float* wav, const int32_t* lens /*host*/, int L_max, int B,
+               float* out, int Lout_max, double* figures /*or NULL*/, int32_t* iters /*or NULL*/, int T_max);
+
 /* ---- F0 tracking by YIN (de Cheveigne & Kawahara 2002, steps 2-5; csrc/f0.hip) and the pitch moments of a track.  No reference
  * counterpart: the reference tree has no pitch tracker (it would take one from librosa or pyworld).  Parity with librosa.yin / pyin
  * is unpinned - neither is on hand - and quality on real speech is unpinned as well; the rule is our own statement and the tests

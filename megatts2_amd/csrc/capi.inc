@@ -1266,6 +1266,39 @@ int mt2_dereverb(mt2_model* m, void* stream, const mt2_audio_config* ac, const m
     MT2_API_END
 }
 
+// declipping by sparsity (declip.hip): the arena bytes of one mt2_declip and of one mt2_clip_detect call and the frames of the longest
+// utterance, without a HIP call
+int mt2_declip_query(const mt2_declip_config* dc, const int32_t* lens, int L_max, int B, long long* workspace_bytes, long long* detect_bytes,
+                     long long* T_max) {
+    MT2_API_BEGIN
+    const DcArgs a = declip_check_config(dc);
+    std::vector<int> len, T;
+    declip_frames(a, lens, L_max, B, len, T);
+    if (workspace_bytes) *workspace_bytes = declip_arena_bytes(a, T, true);
+    if (detect_bytes) *detect_bytes = declip_arena_bytes(a, T, false);
+    if (T_max) *T_max = *std::max_element(T.begin(), T.end());
+    MT2_API_END
+}
+
+// every refusal of the two calls is decided on the host before the first HIP call
+int mt2_clip_detect(mt2_model* m, void* stream, const mt2_declip_config* dc, const float* wav, const int32_t* lens, int L_max, int B,
+                    double* figures) {
+    MT2_API_BEGIN
+    const DcCall k = declip_check(dc, wav, lens, L_max, B, nullptr, 0, figures, nullptr, 0, false);
+    MT2_AUDIO_CALL(m, stream);
+    declip_run(c, k, wav, L_max, B, nullptr, 0, figures, nullptr, 0);
+    MT2_API_END
+}
+
+int mt2_declip(mt2_model* m, void* stream, const mt2_declip_config* dc, const float* wav, const int32_t* lens, int L_max, int B, float* out,
+               int Lout_max, double* figures, int32_t* iters, int T_max) {
+    MT2_API_BEGIN
+    const DcCall k = declip_check(dc, wav, lens, L_max, B, out, Lout_max, figures, iters, T_max, true);
+    MT2_AUDIO_CALL(m, stream);
+    declip_run(c, k, wav, L_max, B, out, Lout_max, figures, iters, T_max);
+    MT2_API_END
+}
+
 // :361-368 [+370]  zq = vq.decode(p_codes) repeated x8, cat([tc_latent_expand, zq]), decoder, optional vocoder - the part of
 // Megatts.forward behind the PLM, shared by mt2_synthesize_batch and mt2_synthesize_prompt_conditioned.  xdec: [D.R, H + Dq]
 // rows whose first H columns already hold the length-regulated tc_latents.

@@ -3149,6 +3149,137 @@ static void wpe_spectrum_run(const Ctx& c, const mt2_audio_config& ac, const Wpe
     wpe_launches(c, p, filters, figures);
 }
 
+// ---- declipping by sparsity (declip.hip), at the audio's own sample rate: every refusal is decided here, on the host, before the
+// first HIP call
+struct DcArgs { int N, min_count, step, every, max_iter; float tol, level; double min_share, eps; };
+static DcArgs declip_check_config(const mt2_declip_config* dc) {
+    MT2_REQUIRE(dc != nullptr, "null declipping configuration");
+    const int N = dc->frame;
+    MT2_REQUIRE(N == 256 || N == 512 || N == 1024 || N == 2048, "frame not one of 256, 512, 1024, 2048");
+    MT2_REQUIRE(std::isfinite(dc->tol) && dc->tol >= 0.0 && dc->tol <= 0.1, "tol outside [0, 0.1]");
+    MT2_REQUIRE(std::isfinite(dc->min_share) && dc->min_share >= 0.0 && dc->min_share <= 1.0, "min_share outside [0, 1]");
+    MT2_REQUIRE(dc->min_count >= 1, "min_count < 1");
+    MT2_REQUIRE(std::isnan(dc->level) || (std::isfinite(dc->level) && dc->level > 0.0 && std::isfinite((float)dc->level) && (float)dc->level > 0.0f),
+                "level neither NaN (detect) nor a positive finite f32 value");
+    MT2_REQUIRE(dc->step >= 1 && dc->step <= N / 2 + 1, "step outside [1, frame / 2 + 1]");
+    MT2_REQUIRE(dc->every >= 1 && dc->every <= 64, "every outside [1, 64]");
+    MT2_REQUIRE(std::isfinite(dc->eps) && dc->eps > 0.0 && dc->eps < 1.0, "eps outside (0, 1)");
+    MT2_REQUIRE(dc->max_iter >= 0, "max_iter < 0");
+    MT2_REQUIRE(dc->reserved == 0, "mt2_declip_config.reserved must be 0");
+    const int K = N / 2 + 1;
+    return {N, dc->min_count, dc->step, dc->every, dc->max_iter > 0 ? dc->max_iter : dc->every * ((K + dc->step - 1) / dc->step),
+            (float)dc->tol, std::isnan(dc->level) ? NAN : (float)dc->level, dc->min_share, dc->eps};
+}
+// the ragged lengths (lens NULL: every utterance L_max samples) -> the frames of each utterance; returns the longest length
+static int declip_frames(const DcArgs& a, const int* lens, int L_max, int B, std::vector<int>& len, std::vector<int>& T) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(L_max >= 1, "L_max < 1");
+    len.assign(B, L_max);
+    if (lens) len.assign(lens, lens + B);
+    const int mx = check_lens(len.data(), B, L_max, "waveform length outside [1, L_max]");
+    const int hop = a.N / 4;
+    T.resize(B);
+    for (int b = 0; b < B; ++b) {
+        const long long t = ((long long)len[b] + hop - 1) / hop + 3;
+        MT2_REQUIRE(t <= MT2_DECLIP_MAX_FRAMES, "more than MT2_DECLIP_MAX_FRAMES frames in an utterance");
+        T[b] = (int)t;
+    }
+    return mx;
+}
+// the arena of a call, in carve order: the plan, the detection words, then - for mt2_declip alone - the iteration counts and the frames
+struct DcWs { int* det; int* it; double* frames; };
+template <class Ws> static DcWs declip_carve(Ws& ws, IntPlan& ip, size_t B, size_t rows, size_t N, bool restore) {
+    DcWs w{};
+    ip.carve(ws);
+    w.det = ws.template get<int>(B * kDcDet);
+    if (restore) {
+        w.it = ws.template get<int>(rows);
+        w.frames = ws.template get<double>(rows * N);
+    }
+    return w;
+}
+static long long declip_arena_bytes(const DcArgs& a, const std::vector<int>& T, bool restore) {
+    size_t rows = 0;
+    for (int t : T) rows += t;
+    IntPlan ip;      // the entries of declip_run's plan, by size: lengths, needs and - to restore - first rows
+    for (int i = 0; i < (restore ? 3 : 2); ++i) ip.add_fill(T.size(), 0);
+    ArenaCount count;
+    declip_carve(count, ip, T.size(), rows, a.N, restore);
+    return (long long)count.bytes;
+}
+static const double* declip_prepare(mt2_model& m, int N) {
+    double*& d = m.dc_tables[N];
+    if (d) return d;
+    std::vector<double> h(dc_table_doubles(N));
+    dc_table(N, h.data());
+    double* t = nullptr;
+    MT2_HIP(hipMalloc(reinterpret_cast<void**>(&t), h.size() * sizeof(double)));
+    m.dev_allocs.push_back(t);
+    MT2_HIP(hipMemcpy(t, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    return d = t;
+}
+struct DcCall { DcArgs a; std::vector<int> len, T; int max_len, T_cap; };
+// -> the checked call; out NULL: mt2_clip_detect
+static DcCall declip_check(const mt2_declip_config* dc, const float* wav, const int* lens, int L_max, int B, const float* out, int Lout_max,
+                           const double* figures, const int32_t* iters, int T_max, bool restore) {
+    DcCall k{};
+    k.a = declip_check_config(dc);
+    MT2_REQUIRE(wav != nullptr && lens != nullptr, "bad buffers");
+    k.max_len = declip_frames(k.a, lens, L_max, B, k.len, k.T);
+    k.T_cap = *std::max_element(k.T.begin(), k.T.end());
+    MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)out | (uintptr_t)iters) & 3) == 0 && ((uintptr_t)figures & 7) == 0, "misaligned buffers");
+    const size_t nw = sizeof(float) * (size_t)B * L_max, ng = sizeof(double) * MT2_DECLIP_FIELDS * (size_t)B;
+    if (restore) {
+        MT2_REQUIRE(out != nullptr, "null out");
+        MT2_REQUIRE(Lout_max >= k.max_len, "Lout_max smaller than the longest utterance");
+        MT2_REQUIRE(iters == nullptr || T_max >= k.T_cap, "T_max smaller than ceil(max length / hop) + 3");
+        const size_t no = sizeof(float) * (size_t)B * Lout_max, ni = iters ? sizeof(int32_t) * (size_t)B * T_max : 0;
+        MT2_REQUIRE(!outputs_overlap({{out, no}, {figures, ng}, {iters, ni}}, {{wav, nw}}), "overlapping buffers (in place is not offered)");
+    } else {
+        MT2_REQUIRE(figures != nullptr, "null figures");
+        MT2_REQUIRE(!outputs_overlap({{figures, ng}}, {{wav, nw}}), "overlapping buffers");
+    }
+    return k;
+}
+// enqueues only (the table of a frame length is uploaded once per handle).  out NULL: detection and its figures alone
+static void declip_run(const Ctx& c, const DcCall& k, const float* wav, int L_max, int B, float* out, int Lout_max, double* figures,
+                       int32_t* iters, int T_max) {
+    const bool restore = out != nullptr;
+    const DcArgs& a = k.a;
+    std::vector<int> need(B), row0(B);
+    size_t rows = 0;
+    for (int b = 0; b < B; ++b) {
+        need[b] = (int)std::min<double>(std::max<double>(a.min_count, std::ceil(a.min_share * (double)k.len[b])), (double)INT_MAX);
+        row0[b] = (int)rows;
+        rows += k.T[b];
+    }
+    MT2_REQUIRE(rows <= (size_t)INT_MAX, "batch too large for 32-bit frame indices");
+    IntPlan ip;
+    const int o_len = ip.add(k.len), o_need = ip.add(need), o_row0 = restore ? ip.add(row0) : 0;
+    const DcWs w = declip_carve(c.ws, ip, B, rows, a.N, restore);
+    ip.send(c.m.pinned(), c.s);
+    DeclipP p{};
+    p.wav = wav; p.L_max = L_max; p.len = ip.dev(o_len); p.need = ip.dev(o_need); p.row0 = restore ? ip.dev(o_row0) : nullptr;
+    p.B = B; p.T_cap = k.T_cap; p.N = a.N; p.tol = a.tol; p.level = a.level; p.step = a.step; p.every = a.every; p.max_iter = a.max_iter;
+    p.eps = a.eps; p.det = w.det; p.frames = w.frames; p.it = w.it; p.iters_out = iters; p.T_max = T_max; p.out = out; p.Lout_max = Lout_max;
+    p.fig = figures;
+    if (restore) p.table = declip_prepare(c.m, a.N);
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(launch_dc_detect(p, c.s));
+    st.mark("dc_detect");
+    if (restore) {
+        if (iters) MT2_HIP(hipMemsetAsync(iters, 0, sizeof(int32_t) * (size_t)B * T_max, c.s));
+        MT2_HIP(launch_dc_frames(p, c.s));
+        st.mark("dc_frames");
+        MT2_HIP(launch_dc_overlap(p, k.max_len, c.s));
+        st.mark("dc_overlap");
+    }
+    if (figures) MT2_HIP(launch_dc_figures(p, c.s));
+    st.mark("dc_figures");
+    st.finish();
+}
+
 }  // namespace mt2
 
 // the C ABI lives in capi.hip and includes this translation unit's helpers

@@ -578,6 +578,31 @@ hipError_t launch_wpe_bins(const WpeP& p, hipStream_t s);
 hipError_t launch_wpe_from_bins(const WpeP& p, hipStream_t s);
 hipError_t launch_wpe_figures(const WpeP& p, hipStream_t s);
 
+// ---- declipping by sparsity, A-SPADE (declip.hip; the rule is in its header and in megatts2_hip.h)
+// Utterance b owns the frames row0[b] .. row0[b] + T_b of `frames` ([rows, N] doubles) and of `it` ([rows]), T_b = ceil(len[b] / hop) + 3,
+// hop = N / 4.  det: kDcDet words an utterance: the bits of hi and lo, n_hi, n_lo, side clipped high / low (0 / 1), non-finite, 0.
+constexpr int kDcThreads = 256, kDcDetThreads = 1024, kDcDet = 8;
+size_t dc_lds_bytes(int N);                   // host only: the dynamic LDS of launch_dc_frames
+size_t dc_table_doubles(int N);               // host only: the size of the table below
+void dc_table(int N, double* t);              // host only: the twiddles e^(-2 pi i k / N), k < N / 2, at their swizzled cells, then the window [N]
+struct DeclipP {
+    const float* wav; int L_max;              // [B, L_max]; samples at or beyond len[b] are never read
+    const int* len; const int* need; const int* row0;      // device [B]; need: the count from which a side is clipped
+    int B, T_cap;                             // T_cap >= max_b T_b: sizes the frame kernel's grid
+    int N; float tol, level;                  // level NaN: detect
+    int step, every, max_iter; double eps;
+    const double* table;                      // dc_table(N), device
+    int* det;                                 // [B, kDcDet]
+    double* frames; int* it;                  // written for the utterances with a clipped side only, and read for those only
+    int32_t* iters_out; int T_max;            // optional [B, T_max] (the caller zeroes it): the frames t < T_b of those utterances
+    float* out; int Lout_max;                 // launch_dc_overlap: the samples j < len[b]; launch_dc_figures: NULL = detection only
+    double* fig;                              // launch_dc_figures: [B, MT2_DECLIP_FIELDS]
+};
+hipError_t launch_dc_detect(const DeclipP& p, hipStream_t s);
+hipError_t launch_dc_frames(const DeclipP& p, hipStream_t s);
+hipError_t launch_dc_overlap(const DeclipP& p, int max_len, hipStream_t s);
+hipError_t launch_dc_figures(const DeclipP& p, hipStream_t s);
+
 // ---- Griffin-Lim vocoder (griffinlim.hip; the rule is in its header and in megatts2_hip.h) -------------------------------------------
 // Frames of a ragged batch are packed rows: utterance b owns rows row0[b] .. row0[b] + T[b] of S / R / Rprev ([rows, lds]: re(0..F-1) |
 // im(0..F-1) | zero pad, lds = 2F rounded up to 4), of A ([rows, lda]) and of the inverse-DFT GEMM's frames ([rows, N]).

@@ -250,6 +250,8 @@ struct mt2_model {
     std::map<std::pair<int, int>, float*> rs_tables;
     // mel-cepstrum tables (mcd.hip) by (n_mels, order): built and uploaded on first use
     std::map<std::pair<int, int>, float*> mcd_tables;
+    // declipping tables (declip.hip) by frame length N: twiddles and window in double, built and uploaded on first use
+    std::map<int, double*> dc_tables;
 
     bool profiling = false;
     std::vector<std::string> stage_names;

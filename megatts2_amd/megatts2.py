@@ -21,7 +21,7 @@ import numpy as np
 from . import config as cfgmod
 from . import weights
 from .config import HIFIGAN_HOP_LENGTH, HIFIGAN_SR
-from .runtime import DENOISE_NAMES, WPE_NAMES, Denoise, Dereverb, Limiter, NativeError, NativeModel  # noqa: F401  (Limiter, Denoise, Dereverb: arguments of synthesize / forward)
+from .runtime import DECLIP_NAMES, DENOISE_NAMES, WPE_NAMES, Declip, Denoise, Dereverb, Limiter, NativeError, NativeModel  # noqa: F401  (Limiter, Denoise, Dereverb, Declip: arguments of synthesize / forward)
 from .sampling import PLMSampling, seed_array
 
 
@@ -41,7 +41,7 @@ def _frontend():
 
 
 def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, denoise: Optional[Denoise] = None,
-                     dereverb: Optional[Dereverb] = None):
+                     dereverb: Optional[Dereverb] = None, declip: Optional[Declip] = None):
     """reference modules/tokenizer.py:107-125: 1-D waveform tensor (16 kHz) -> mel [80, T] (the reference
     returns channels first and `Megatts.forward` transposes it, models/megatts2.py:339).  Runs on the GPU
     (runtime.MelFrontEnd); a [B, L] input gives [B, 80, T].  sample_rate: the rate of `samples` when it is not
@@ -51,12 +51,16 @@ def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Option
     the call without it): a `Denoise`; stationary noise is suppressed behind the resampling and in front of the trim
     (MelFrontEnd.denoise, csrc/denoise.hip; the level is left as it comes out, up to hop - 1 tail samples are dropped).  dereverb (None
     = off, exactly the call without it): a `Dereverb`; late reverberation is removed by weighted prediction error behind the resampling
-    and in front of the denoiser (MelFrontEnd.dereverb, csrc/wpe.hip; likewise)."""
+    and in front of the denoiser (MelFrontEnd.dereverb, csrc/wpe.hip; likewise).  declip (None = off, exactly the call without it): a
+    `Declip`; clipped samples are restored first of all, at the samples' own rate and in front of the resampling, which would turn
+    the flat tops into ripple (MelFrontEnd.declip, csrc/declip.hip; the level is left as it comes out and can exceed the input's)."""
     import torch
     fe = _frontend()
     x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
     batched = x.dim() == 2
     x = (x if batched else x.unsqueeze(0)).to("cuda", torch.float32)
+    if declip is not None:
+        x = fe.declip(x, None, declip)
     if sample_rate is not None and int(sample_rate) != fe.audio.sample_rate:
         x = fe.resample(x, int(sample_rate))[0]
     lens = None
@@ -220,6 +224,39 @@ def dereverb_audio(samples, sample_rate: Optional[int] = None, lens=None, dereve
     fig = fig.cpu().numpy()
     res = {k: fig[:, i].copy() for i, k in enumerate(WPE_NAMES)}
     res["out_lens"] = out_lens
+    out = out.cpu().numpy()
+    return (out[0] if flat else out), res
+
+
+def detect_clipping(samples, lens=None, declip: Optional[Declip] = None):
+    """Clipping of a 1-D waveform or a [B, L] batch, detected on the GPU by step 1 of the rule of csrc/declip.hip (MelFrontEnd.clip_detect):
+    nothing is restored.  -> dict of float64 [B]: clipped (0 / 1), hi, lo, share (of the samples at the two levels)."""
+    import torch
+    x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
+    x = (x.unsqueeze(0) if x.dim() == 1 else x).to("cuda", torch.float32)
+    fig = _frontend().clip_detect(x, lens, declip or Declip()).cpu().numpy()
+    return {k: fig[:, i].copy() for i, k in enumerate(DECLIP_NAMES[:4])}
+
+
+def declip_audio(samples, lens=None, declip: Optional[Declip] = None):
+    """Declipping of a 1-D waveform or a [B, L] batch on the GPU by sparsity, the rule of csrc/declip.hip (MelFrontEnd.declip, A-SPADE;
+    no reference counterpart; parity with any outside declipper and audible quality on real speech unpinned).  The samples are taken at
+    their OWN rate - nothing is resampled, because a resampler turns flat tops into ripple that is no longer recognised - so there is no
+    sample_rate argument.  Samples within `tol` of the utterance's extremes count as clipped once there are enough of them; each frame
+    that holds some is re-estimated as the signal of sparsest spectrum that keeps the reliable samples and lies beyond the level on the
+    clipped ones.  An utterance that is not clipped comes back bit for bit; soft clipping is not detected; a steady full-scale tone
+    reads as clipped.  The output can exceed the input's peak: normalise after.  lens: the real samples of each row.  declip: a
+    `Declip` (None: its defaults).  -> (out float32 numpy [B, L] ([L] for a 1-D waveform), dict: iters int32 [B, T] and float64 [B]
+    clipped, hi, lo, share, frames_iterated, mean_iterations, max_iterations, power_change_db)."""
+    import torch
+    fe = _frontend()
+    flat = (samples.dim() if hasattr(samples, "dim") else np.asarray(samples).ndim) == 1
+    x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
+    x = (x.unsqueeze(0) if x.dim() == 1 else x).to("cuda", torch.float32)
+    out, fig, iters = fe.declip(x, lens, declip or Declip(), return_figures=True, return_iters=True)
+    fig = fig.cpu().numpy()
+    res = {k: fig[:, i].copy() for i, k in enumerate(DECLIP_NAMES)}
+    res["iters"] = iters.cpu().numpy()
     out = out.cpu().numpy()
     return (out[0] if flat else out), res
 
@@ -1012,10 +1049,13 @@ class Megatts:
     # dereverb (None = off; a runtime.Dereverb): likewise through from_audio(dereverb=...): resample, peak-normalise, remove late
     # reverberation by weighted prediction error (csrc/wpe.hip), the denoiser behind it if asked for, peak-normalise, trim.
     # aux["prompt_reverb"] then holds one dict per prompt file with the figures of the stage (WPE_NAMES).
+    # declip (None = off; a runtime.Declip): likewise through from_audio(declip=...), where it comes first of all, at the file's own
+    # sample rate (csrc/declip.hip): declip, resample, peak-normalise, ...  aux["prompt_clipping"] then holds one dict per prompt file
+    # with the figures of the stage (DECLIP_NAMES).
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
                 phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None, vocoder=None,
                 loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0, true_peak_ceiling_dbtp: Optional[float] = None,
-                limiter=None, denoise: Optional[Denoise] = None, dereverb: Optional[Dereverb] = None):
+                limiter=None, denoise: Optional[Denoise] = None, dereverb: Optional[Dereverb] = None, declip: Optional[Declip] = None):
         import torch
         if true_peak_ceiling_dbtp is not None and loudness_lufs is None:
             raise ValueError("true_peak_ceiling_dbtp caps the gain of the loudness normalisation: it needs loudness_lufs")
@@ -1041,19 +1081,22 @@ class Megatts:
         if not wavs:
             raise NativeError(f"no *.wav under {wavs_dir}")
 
-        prompt_noise, prompt_reverb = [], []
+        prompt_noise, prompt_reverb, prompt_clipping = [], [], []
 
         def prompt_mel(w):
             y, sr = audio_io.read_wav(w)
-            if denoise is not None or dereverb is not None:
+            if denoise is not None or dereverb is not None or declip is not None:
                 if sr != HIFIGAN_SR and not resample:
                     raise ValueError(f"{w}: {sr} Hz, expected {HIFIGAN_SR} Hz (resample=False)")
+                more = {} if declip is None else {"declip": declip, "return_clipping": True}      # absent: exactly the call of before
                 res = _frontend().from_audio(torch.from_numpy(y).unsqueeze(0).cuda(), sr, trim_db=trim_db, denoise=denoise,
-                                             return_noise=denoise is not None, dereverb=dereverb, return_reverb=dereverb is not None)
+                                             return_noise=denoise is not None, dereverb=dereverb, return_reverb=dereverb is not None, **more)
                 if denoise is not None:
                     prompt_noise.append(dict(zip(DENOISE_NAMES, res[2][0].cpu().numpy().tolist())))
                 if dereverb is not None:
-                    prompt_reverb.append(dict(zip(WPE_NAMES, res[-1][0].cpu().numpy().tolist())))
+                    prompt_reverb.append(dict(zip(WPE_NAMES, res[-2 if declip is not None else -1][0].cpu().numpy().tolist())))
+                if declip is not None:
+                    prompt_clipping.append(dict(zip(DECLIP_NAMES, res[-1][0].cpu().numpy().tolist())))
                 return res[0][0]
             if sr == HIFIGAN_SR and trim_db is None:          # audio_io.load_audio's two steps
                 return extract_mel_spec(torch.from_numpy(audio_io.normalize(y))).transpose(0, 1)
@@ -1085,6 +1128,8 @@ class Megatts:
                 aux["prompt_noise"] = prompt_noise
             if dereverb is not None:
                 aux["prompt_reverb"] = prompt_reverb
+            if declip is not None:
+                aux["prompt_clipping"] = prompt_clipping
             if out_path:
                 prompt = levelled(self.vocode_griffin_lim(mels_prompt.unsqueeze(0).contiguous(), **gl)[0])
                 audio = torch.cat([prompt, aux["wav"][0, :(int(mel_lens[0]) - 1) * HIFIGAN_HOP_LENGTH]])
@@ -1096,6 +1141,8 @@ class Megatts:
             aux["prompt_noise"] = prompt_noise
         if dereverb is not None:
             aux["prompt_reverb"] = prompt_reverb
+        if declip is not None:
+            aux["prompt_clipping"] = prompt_clipping
         if self.hifi_gan is not None and out_path:
             # :370-375  prompt audio (vocoded first prompt mel) followed by the generated audio; decode_batch output
             # includes the generator's inference padding on both sides, exactly as the reference concatenates it

@@ -106,6 +106,44 @@ class MT2WpeConfig(C.Structure):
 WPE_NAMES = ("power_in", "power_out", "reduction_db", "frames", "bins_filtered", "bins_passed", "max_tap", "iterations")
 
 
+@dataclasses.dataclass(frozen=True)
+class Declip:
+    """The settings of the declipping by sparsity (csrc/declip.hip, A-SPADE; the rule is in include/megatts2_hip.h): frames of `frame`
+    samples (256, 512, 1024 or 2048; the hop is a quarter).  A side of the waveform is clipped when at least max(`min_count`,
+    ceil(`min_share` * length)) samples lie within `tol` (0 .. 0.1, relative) of the utterance's extreme - or of `level`, when the
+    clipping level is known (NaN: detect).  Each frame with clipped samples is re-estimated as the signal whose spectrum is sparsest
+    while the reliable samples stay and the clipped ones lie beyond the level: the sparsity grows by `step` bins every `every`
+    iterations until the residual falls under `eps` of the frame's norm, or `max_iter` (0: every * ceil((frame / 2 + 1) / step)) is
+    reached.  Soft clipping, and clipping followed by a resampler or a lossy codec, has no flat tops and is not detected; a steady
+    full-scale tone reads as clipped."""
+    frame: int = 1024
+    tol: float = 1e-3
+    min_share: float = 1e-4
+    min_count: int = 4
+    level: float = float("nan")
+    step: int = 1
+    every: int = 1
+    eps: float = 0.02
+    max_iter: int = 0
+
+    def c_struct(self) -> "MT2DeclipConfig":
+        return MT2DeclipConfig(int(self.frame), int(self.min_count), int(self.step), int(self.every), int(self.max_iter), 0, float(self.tol),
+                               float(self.min_share), float(self.level), float(self.eps))
+
+    def frames(self, length: int) -> int:
+        """the frames of an utterance of `length` samples: ceil(length / hop) + 3"""
+        hop = int(self.frame) // 4
+        return -(-int(length) // hop) + 3
+
+
+class MT2DeclipConfig(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("min_count", C.c_int32), ("step", C.c_int32), ("every", C.c_int32), ("max_iter", C.c_int32),
+                ("reserved", C.c_int32), ("tol", C.c_double), ("min_share", C.c_double), ("level", C.c_double), ("eps", C.c_double)]
+
+
+DECLIP_NAMES = ("clipped", "hi", "lo", "share", "frames_iterated", "mean_iterations", "max_iterations", "power_change_db")
+
+
 class MT2Config(C.Structure):
     _fields_ = [
         ("mel_bins", C.c_int32), ("mrte_hidden", C.c_int32), ("mrte_kernel", C.c_int32), ("mrte_stride", C.c_int32),
@@ -180,6 +218,9 @@ def load_library():
     lib.mt2_dereverb_query.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 2
     lib.mt2_wpe_spectrum.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 3
     lib.mt2_dereverb.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int]
+    lib.mt2_declip_query.argtypes = [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib.mt2_clip_detect.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_declip.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     lib.mt2_stft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_istft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_mel_to_linear.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
@@ -528,6 +569,44 @@ def _dereverb(lib, h, ac, wav, lens=None, dereverb: Optional[Dereverb] = None, r
     fig = torch.empty(B, len(WPE_NAMES), device=wav.device, dtype=torch.float64) if return_figures else None
     _check(lib.mt2_dereverb(h, _stream(), C.byref(ac), C.byref(wc), _ptr(wav), _iptr(ln), L, B, _ptr(fig), _ptr(out), out.shape[1]))
     return (out, out_lens, fig) if return_figures else (out, out_lens)
+
+
+def _clip_detect(lib, h, wav, lens=None, declip: Optional[Declip] = None):
+    """mt2_clip_detect on the handle `h`: wav f32 [B, L] (device, at its own sample rate) -> figures float64 [B, 8] (device;
+    DECLIP_NAMES; the last four are zero: nothing is restored).  Samples at or beyond lens[b] are never read.  The call only enqueues."""
+    import torch
+    wav, ln, B, L = _wav_lens(wav, lens)
+    dc = (declip or Declip()).c_struct()
+    fig = torch.empty(B, len(DECLIP_NAMES), device=wav.device, dtype=torch.float64)
+    _check(lib.mt2_clip_detect(h, _stream(), C.byref(dc), _ptr(wav), _iptr(ln), L, B, _ptr(fig)))
+    return fig
+
+
+def _declip(lib, h, wav, lens=None, declip: Optional[Declip] = None, return_figures: bool = False, return_iters: bool = False, out=None):
+    """mt2_declip on the handle `h`: wav f32 [B, L] (device, at its own sample rate; nothing is resampled) -> the declipped audio f32
+    [B, L]: reliable samples keep their bits, a clipped sample moves outward or stays, an utterance that is not clipped (or holds a
+    non-finite sample) comes back bit for bit.  The output can exceed the input's peak; the caller normalises after.  Samples at or
+    beyond lens[b] are never read; in a new `out` they are the input's, in a caller's they are left untouched.  out: a contiguous f32
+    [B, >= max lens] device tensor to write into (NOT wav: in place is not offered).  return_figures: also float64 [B, 8] (device;
+    DECLIP_NAMES); return_iters: also int32 [B, T] (device), T = ceil(max lens / hop) + 3: the iterations of every frame.
+    -> out, or (out[, figures][, iters]).  The call only enqueues."""
+    import torch
+    wav, ln, B, L = _wav_lens(wav, lens)
+    cfg = declip or Declip()
+    dc = cfg.c_struct()
+    if out is None:
+        out = wav.clone()
+    out = _out_rows(out, B, wav, lambda: L)
+    fig = torch.empty(B, len(DECLIP_NAMES), device=wav.device, dtype=torch.float64) if return_figures else None
+    T = cfg.frames(int(ln.max())) if int(cfg.frame) >= 4 and len(ln) else 1
+    it = torch.empty(B, T, device=wav.device, dtype=torch.int32) if return_iters else None
+    _check(lib.mt2_declip(h, _stream(), C.byref(dc), _ptr(wav), _iptr(ln), L, B, _ptr(out), out.shape[1], _ptr(fig), _ptr(it), T))
+    res = (out,)
+    if return_figures:
+        res += (fig,)
+    if return_iters:
+        res += (it,)
+    return res[0] if len(res) == 1 else res
 
 
 def _workspace_fill(lib, h, byte: int) -> None:
@@ -964,6 +1043,15 @@ class NativeModel:
                       in_place: bool = False, audio=None):
         """The smoothed gain and / or the gated spectrum of a spectrum and a floor (`_spectral_gain`)."""
         return _spectral_gain(self.lib, self.h, _audio_struct(audio), spec, floor, frame_lens, denoise, return_gain, apply, in_place)
+
+    # ---- declipping by sparsity (csrc/declip.hip) on the model's handle, as MelFrontEnd's
+    def clip_detect(self, wav, lens=None, declip: Optional[Declip] = None):
+        """The clipping figures float64 [B, 8] of wav f32 [B, L] (`_clip_detect`)."""
+        return _clip_detect(self.lib, self.h, wav, lens, declip)
+
+    def declip(self, wav, lens=None, declip: Optional[Declip] = None, return_figures: bool = False, return_iters: bool = False, out=None):
+        """Declipped audio of wav f32 [B, L] (`_declip`)."""
+        return _declip(self.lib, self.h, wav, lens, declip, return_figures, return_iters, out)
 
     # ---- de-reverberation by weighted prediction error (csrc/wpe.hip) on the model's handle, as MelFrontEnd's
     def dereverb(self, wav, lens=None, dereverb: Optional[Dereverb] = None, return_figures: bool = False, out=None, audio=None):
@@ -1445,6 +1533,17 @@ class MelFrontEnd:
         """The smoothed gain f32 [B, T, F] and / or the gated spectrum of a spectrum and a floor (`_spectral_gain`)."""
         return _spectral_gain(self.lib, self.h, self.ac, spec, floor, frame_lens, denoise, return_gain, apply, in_place)
 
+    # ---- declipping by sparsity (csrc/declip.hip, A-SPADE): detection of flat tops and their restoration, at the audio's own rate
+    def clip_detect(self, wav, lens=None, declip: Optional[Declip] = None):
+        """The clipping figures float64 [B, 8] (device; DECLIP_NAMES) of wav f32 [B, L] at any sample rate (`_clip_detect`): clipped or
+        not, the two levels, the share of samples clipped; nothing is restored."""
+        return _clip_detect(self.lib, self.h, wav, lens, declip)
+
+    def declip(self, wav, lens=None, declip: Optional[Declip] = None, return_figures: bool = False, return_iters: bool = False, out=None):
+        """Declipped audio of wav f32 [B, L] at any sample rate (`_declip`) -> out f32 [B, L][, figures float64 [B, 8]][, iters int32
+        [B, T]]."""
+        return _declip(self.lib, self.h, wav, lens, declip, return_figures, return_iters, out)
+
     # ---- de-reverberation by weighted prediction error (csrc/wpe.hip): a per-bin prediction filter between the STFT and its inverse
     def dereverb(self, wav, lens=None, dereverb: Optional[Dereverb] = None, return_figures: bool = False, out=None):
         """De-reverberated audio of wav f32 [B, L] at audio.sample_rate (`_dereverb`) -> (out f32 [B, hop * (max lens // hop)], out_lens
@@ -1566,7 +1665,7 @@ class MelFrontEnd:
 
     def from_audio(self, wav, sr_in: int, lens=None, trim_db: Optional[float] = None, return_bounds: bool = False,
                    denoise: Optional[Denoise] = None, return_noise: bool = False, dereverb: Optional[Dereverb] = None,
-                   return_reverb: bool = False):
+                   return_reverb: bool = False, declip: Optional[Declip] = None, return_clipping: bool = False):
         """Prompt audio at any sample rate -> (mel [B, T, n_mels], mel_lens): resample to audio.sample_rate, peak-normalise and
         extract the mel (models/megatts2.py:335-336,339) with no host round trip.  Audio that already has that rate is only
         normalised, by the same kernels.  trim_db: leading / trailing silence is cut off between the normalisation and the mel
@@ -1578,13 +1677,21 @@ class MelFrontEnd:
         without it): a `Dereverb`; the normalised audio goes through `dereverb` in FRONT of the denoiser - WPE is a linear filter and
         must see the recording before a non-linear gate breaks the linear relation it estimates - and is peak-normalised again once, behind
         the last of the two stages (resample -> normalise -> dereverb -> denoise -> normalise -> trim);
-        return_reverb (needs dereverb): the very last result, its figures float64 [B, 8] (device; WPE_NAMES)."""
+        return_reverb (needs dereverb): a last result, its figures float64 [B, 8] (device; WPE_NAMES).  declip (None = off, exactly
+        the call without it): a `Declip`; clipped samples are restored FIRST, at sr_in - the resampler and the normalisation turn flat
+        tops into ripple that nothing can recognise as clipping (declip -> resample -> normalise -> dereverb -> denoise -> normalise ->
+        trim); return_clipping (needs declip): the very last result, its figures float64 [B, 8] (device; DECLIP_NAMES)."""
         import torch
         assert wav.is_cuda and wav.dim() == 2
         assert denoise is not None or not return_noise
         assert dereverb is not None or not return_reverb
+        assert declip is not None or not return_clipping
         wav = wav.contiguous().to(torch.float32)
         B, L = wav.shape
+        clipping = None
+        if declip is not None:
+            d = self.declip(wav, lens, declip, return_figures=return_clipping)
+            wav, clipping = (d[0], d[1]) if return_clipping else (d, None)
         if int(sr_in) == self.audio.sample_rate:
             ln = np.full(B, L, np.int32) if lens is None else _i32(lens)
             y = torch.empty_like(wav)
@@ -1614,6 +1721,8 @@ class MelFrontEnd:
             res += (figures,)
         if return_reverb:
             res += (reverb,)
+        if return_clipping:
+            res += (clipping,)
         return res
 
 
@@ -2326,6 +2435,19 @@ def dereverb_query(audio=None, lens=None, L_max: Optional[int] = None, B: Option
     _check(load_library().mt2_dereverb_query(C.byref(ac), C.byref(wc), _iptr(ln), int(L_max or 0), int(B or 0), C.byref(nbytes),
                                              C.byref(lout)))
     return nbytes.value, lout.value
+
+
+def declip_query(lens=None, L_max: Optional[int] = None, B: Optional[int] = None, declip: Optional[Declip] = None):
+    """mt2_declip_query (no device needed) -> (arena bytes of one `declip` call, arena bytes of one `clip_detect` call, T): lens int [B]
+    (or L_max and B: every utterance L_max samples).  The bytes are exactly the calls' high water; T = ceil(max lens / hop) + 3, the
+    width of `iters`.  It refuses what the calls refuse."""
+    ln = None if lens is None else _i32(lens)
+    if ln is not None:
+        B, L_max = len(ln), (int(ln.max()) if len(ln) else 0) if L_max is None else L_max
+    dc = (declip or Declip()).c_struct()
+    nbytes, dbytes, T = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _check(load_library().mt2_declip_query(C.byref(dc), _iptr(ln), int(L_max or 0), int(B or 0), C.byref(nbytes), C.byref(dbytes), C.byref(T)))
+    return nbytes.value, dbytes.value, T.value
 
 
 def griffin_lim_query(audio, mel_lens=None, T_max: Optional[int] = None, B: Optional[int] = None, n_iter: int = 32,

@@ -1059,7 +1059,8 @@ int mt2_griffin_lim_query(const mt2_audio_config* ac, const int32_t* mel_lens, i
     const long long L = (long long)(*std::max_element(T.begin(), T.end()) - 1) * ac->hop_length;
     gl_check_call(*ac, T.data(), T_max, B, n_iter, momentum, std::max(L, 0ll));
     (void)gl_pinv(*ac).size();      // the rank-deficient filterbank
-    if (workspace_bytes) *workspace_bytes = gl_arena_bytes(*ac, T.data(), B, want_resid != 0);
+    const long long rstride = want_resid ? (long long)(n_iter + 1) * T_max : 0;
+    if (workspace_bytes) *workspace_bytes = arena_bytes([&](ArenaCount& count, IntPlan& ip) { gl_layout(count, ip, *ac, T.data(), T_max, B, nullptr, rstride); });
     if (L_out) *L_out = L;
     MT2_API_END
 }
@@ -1171,8 +1172,8 @@ int mt2_denoise_query(const mt2_audio_config* ac, const mt2_denoise_config* dc, 
     MT2_REQUIRE(ac != nullptr, "null audio configuration");
     const DnArgs a = denoise_check_config(dc);
     std::vector<int> T;
-    const int T_cap = denoise_frames(*ac, lens, L_max, B, T);
-    if (workspace_bytes) *workspace_bytes = denoise_arena_bytes(*ac, T, T_cap);
+    const int T_cap = wave_frames(*ac, lens, L_max, B, T);
+    if (workspace_bytes) *workspace_bytes = arena_bytes([&](ArenaCount& count, IntPlan& ip) { denoise_layout(count, ip, SpecGeom(*ac), lens, T, T_cap); });
     if (L_out) *L_out = (long long)(T_cap - 1) * ac->hop_length;
     if (rank) *rank = denoise_rank(T_cap, a.percentile);
     if (factor) *factor = a.c;
@@ -1186,7 +1187,7 @@ int mt2_noise_floor(mt2_model* m, void* stream, const mt2_audio_config* ac, cons
     const DnArgs a = denoise_check_config(dc);
     const int T_cap = denoise_check_spec(ac, spec, frame_lens, T_max, B);
     MT2_REQUIRE(floor != nullptr && ((uintptr_t)floor & 3) == 0, "bad floor");
-    const size_t F = ac->n_fft / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
+    const size_t Fp = SpecGeom(*ac).Fp, lds = SpecGeom(*ac).lds;
     MT2_REQUIRE(!outputs_overlap({{floor, sizeof(float) * B * Fp}}, {{spec, sizeof(float) * (size_t)B * T_max * lds}}), "overlapping buffers");
     MT2_AUDIO_CALL(m, stream);
     noise_floor_run(c, *ac, a, spec, frame_lens, T_max, B, T_cap, floor);
@@ -1200,7 +1201,7 @@ int mt2_spectral_gain(mt2_model* m, void* stream, const mt2_audio_config* ac, co
     const int T_cap = denoise_check_spec(ac, spec, frame_lens, T_max, B);
     MT2_REQUIRE(floor != nullptr && (gain != nullptr || spec_out != nullptr), "null floor, or neither output asked for");
     MT2_REQUIRE((((uintptr_t)floor | (uintptr_t)gain | (uintptr_t)spec_out) & 3) == 0, "misaligned buffers");
-    const size_t F = ac->n_fft / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
+    const size_t Fp = SpecGeom(*ac).Fp, lds = SpecGeom(*ac).lds;
     const size_t ns = sizeof(float) * (size_t)B * T_max * lds, ng = sizeof(float) * (size_t)B * T_max * Fp, nf = sizeof(float) * B * Fp;
     MT2_REQUIRE(!outputs_overlap({{gain, ng}, {spec_out == spec ? nullptr : spec_out, ns}}, {{spec, ns}, {floor, nf}}), "overlapping buffers");
     MT2_AUDIO_CALL(m, stream);
@@ -1211,9 +1212,10 @@ int mt2_spectral_gain(mt2_model* m, void* stream, const mt2_audio_config* ac, co
 int mt2_denoise(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* wav, const int32_t* lens,
                 int L_max, int B, const float* floor_in, float* floor_out, double* figures, float* out, int Lout_max) {
     MT2_API_BEGIN
+    MT2_REQUIRE(ac != nullptr, "null audio configuration");
+    const DnArgs a = denoise_check_config(dc);
     std::vector<int> T;
-    DnArgs a{};
-    const int T_cap = denoise_check(ac, dc, wav, lens, L_max, B, floor_in, floor_out, figures, out, Lout_max, T, a);
+    const int T_cap = wave_check(*ac, wav, lens, L_max, B, floor_in, floor_out, figures, MT2_DENOISE_FIELDS, out, Lout_max, T);
     MT2_AUDIO_CALL(m, stream);
     denoise_run(c, *ac, a, wav, lens, L_max, B, T, T_cap, floor_in, floor_out, figures, out, Lout_max);
     MT2_API_END
@@ -1225,10 +1227,10 @@ int mt2_dereverb_query(const mt2_audio_config* ac, const mt2_wpe_config* wc, con
                        long long* L_out) {
     MT2_API_BEGIN
     MT2_REQUIRE(ac != nullptr, "null audio configuration");
-    wpe_check_config(wc);
+    const WpeArgs a = wpe_check_config(wc);
     std::vector<int> T;
-    const int T_cap = denoise_frames(*ac, lens, L_max, B, T);
-    if (workspace_bytes) *workspace_bytes = dereverb_arena_bytes(*ac, T);
+    const int T_cap = wave_frames(*ac, lens, L_max, B, T);
+    if (workspace_bytes) *workspace_bytes = arena_bytes([&](ArenaCount& count, IntPlan& ip) { dereverb_layout(count, ip, SpecGeom(*ac), a, lens, T, T_cap); });
     if (L_out) *L_out = (long long)(T_cap - 1) * ac->hop_length;
     MT2_API_END
 }
@@ -1242,7 +1244,7 @@ int mt2_wpe_spectrum(mt2_model* m, void* stream, const mt2_audio_config* ac, con
     MT2_REQUIRE(spec_out != nullptr, "null spec_out");
     MT2_REQUIRE((((uintptr_t)spec | (uintptr_t)spec_out) & 15) == 0 && ((((uintptr_t)filters | (uintptr_t)figures) & 7) == 0),
                 "misaligned buffers: the spectra on 16 bytes, the doubles on 8");
-    const size_t F = ac->n_fft / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
+    const size_t F = SpecGeom(*ac).F, Fp = SpecGeom(*ac).Fp, lds = SpecGeom(*ac).lds;
     const size_t ns = sizeof(float) * (size_t)B * T_max * lds, nf = sizeof(double) * 2 * (size_t)B * Fp * a.taps,
                  ng = sizeof(double) * MT2_WPE_FIELDS * (size_t)B;
     MT2_REQUIRE(!outputs_overlap({{spec_out == spec ? nullptr : spec_out, ns}, {filters, nf}, {figures, ng}}, {{spec, ns}}), "overlapping buffers");
@@ -1258,9 +1260,10 @@ int mt2_wpe_spectrum(mt2_model* m, void* stream, const mt2_audio_config* ac, con
 int mt2_dereverb(mt2_model* m, void* stream, const mt2_audio_config* ac, const mt2_wpe_config* wc, const float* wav, const int32_t* lens,
                  int L_max, int B, double* figures, float* out, int Lout_max) {
     MT2_API_BEGIN
+    MT2_REQUIRE(ac != nullptr, "null audio configuration");
+    const WpeArgs a = wpe_check_config(wc);
     std::vector<int> T;
-    WpeArgs a{};
-    const int T_cap = dereverb_check(ac, wc, wav, lens, L_max, B, figures, out, Lout_max, T, a);
+    const int T_cap = wave_check(*ac, wav, lens, L_max, B, nullptr, nullptr, figures, MT2_WPE_FIELDS, out, Lout_max, T);
     MT2_AUDIO_CALL(m, stream);
     dereverb_run(c, *ac, a, wav, lens, L_max, B, T, T_cap, figures, out, Lout_max);
     MT2_API_END

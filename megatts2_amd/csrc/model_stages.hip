@@ -1714,10 +1714,18 @@ static float* frontend_upload(mt2_model& m, const std::vector<float>& v) {
     m.dev_allocs.push_back(d);
     return d;
 }
+// The geometry of every spectral call, from its audio configuration: taps hop-sized blocks to a frame, pad reflected samples on either
+// side, F one-sided bins; a magnitude row has Fp floats and a spectrum row (re | im | zero pad) lds
+struct SpecGeom {
+    int N, hop, taps, pad, F, Fp, lds;
+    explicit SpecGeom(const mt2_audio_config& ac)
+        : N(ac.n_fft), hop(ac.hop_length), taps(hop > 0 ? N / hop : 0), pad(N / 2), F(N / 2 + 1), Fp((F + 3) & ~3), lds((2 * F + 3) & ~3) {}
+};
 static void frontend_prepare(mt2_model& m, const mt2_audio_config& ac) {
     if (m.fe_basis && std::memcmp(&m.fe_cfg, &ac, sizeof(ac)) == 0) return;
     frontend_check(ac);
-    const int N = ac.n_fft, F = N / 2 + 1, Fp = (F + 3) & ~3;
+    const SpecGeom g(ac);
+    const int N = g.N, F = g.F, Fp = g.Fp;
     const double PI = 3.14159265358979323846;
     const std::vector<double> win = frontend_window(ac);
     std::vector<float> basis((size_t)2 * F * N);
@@ -1734,78 +1742,95 @@ static void frontend_prepare(mt2_model& m, const mt2_audio_config& ac) {
     m.gl_ibasis = m.gl_w2 = m.gl_P = nullptr;      // the Griffin-Lim constants follow the configuration: rebuilt on their next use
 }
 
-// The packed rows of a ragged batch of waveforms in front of the STFT convolution: utterance b owns T_b - 1 + taps hop-sized blocks of
-// its reflect-padded signal and T_b = 1 + L_b / hop frame rows; frame t reads blocks t .. t + taps - 1
-struct StftRows { int Rb, Fr, o_b, o_t, o_len, o_base, o_map; };
-static StftRows stft_plan(IntPlan& ip, const mt2_audio_config& ac, const int* lens, int L_max, int B, int T_max) {
-    const int hop = ac.hop_length, taps = ac.n_fft / hop, pad = ac.n_fft / 2;
-    std::vector<int> blk_b, blk_t, rowbase, rowmap, len(lens, lens + B);
-    for (int b = 0; b < B; ++b) {
-        MT2_REQUIRE(lens[b] > pad && lens[b] <= L_max, "waveform shorter than n_fft/2 + 1 samples (reflect padding) or > L_max");
-        const int T = 1 + lens[b] / hop, row0 = (int)blk_b.size();
-        MT2_REQUIRE(T <= T_max, "T_max smaller than 1 + L / hop_length");
-        for (int t = 0; t < T - 1 + taps; ++t) { blk_b.push_back(b); blk_t.push_back(t); }
-        for (int t = 0; t < T; ++t) { rowbase.push_back(row0 + t); rowmap.push_back(b * T_max + t); }
+// The packed rows of a ragged batch in front of the STFT convolution and behind the inverse one: utterance b owns T_b - 1 + taps hop-sized
+// blocks of its reflect-padded signal and the T_b frame rows row0[b] .. ; frame t reads blocks t .. t + taps - 1.  Every call adds the
+// lists it needs to its own plan
+struct FrameRows {
+    std::vector<int> blk_b, blk_t, rowbase, map, row0;      // map[r] = b * T_max + t
+    int Rb = 0, Fr = 0;
+};
+// the bound every row list of a batch stays under, refused before the lists are built
+static void check_row_count(const SpecGeom& g, const int* T, int B) {
+    long long rows = 0;
+    for (int b = 0; b < B; ++b) rows += T[b] + g.taps;
+    MT2_REQUIRE(rows * (g.N + 4) <= INT_MAX, "batch too large for 32-bit row indices");
+}
+static FrameRows frame_rows(const SpecGeom& g, const int* T, int B, int T_max) {
+    check_row_count(g, T, B);
+    FrameRows r;
+    r.row0.resize(B);
+    for (int b = 0; b < B; ++b) { r.row0[b] = r.Fr; r.Fr += T[b]; r.Rb += T[b] - 1 + g.taps; }
+    r.blk_b.resize(r.Rb); r.blk_t.resize(r.Rb); r.rowbase.resize(r.Fr); r.map.resize(r.Fr);
+    for (int b = 0, blk = 0, row = 0; b < B; ++b) {
+        const int blk0 = blk;
+        for (int t = 0; t < T[b] - 1 + g.taps; ++t, ++blk) { r.blk_b[blk] = b; r.blk_t[blk] = t; }
+        for (int t = 0; t < T[b]; ++t, ++row) { r.rowbase[row] = blk0 + t; r.map[row] = b * T_max + t; }
     }
-    StftRows r{};
-    r.Rb = (int)blk_b.size(); r.Fr = (int)rowbase.size();
-    r.o_b = ip.add(blk_b); r.o_t = ip.add(blk_t); r.o_len = ip.add(len); r.o_base = ip.add(rowbase); r.o_map = ip.add(rowmap);
     return r;
+}
+// the frame counts of a batch of waveforms in front of the STFT: T_b = 1 + L_b / hop
+static std::vector<int> stft_frames(const SpecGeom& g, const int* lens, int L_max, int B, int T_max) {
+    std::vector<int> T(B);
+    for (int b = 0; b < B; ++b) {
+        MT2_REQUIRE(lens[b] > g.pad && lens[b] <= L_max, "waveform shorter than n_fft/2 + 1 samples (reflect padding) or > L_max");
+        T[b] = 1 + lens[b] / g.hop;
+        MT2_REQUIRE(T[b] <= T_max, "T_max smaller than 1 + L / hop_length");
+    }
+    return T;
 }
 // STFT = Conv1d over hop-sized blocks against the windowed DFT basis: spec[m] = [re(0..F-1) | im(0..F-1)] of frame m, row pitch 2F
 // rounded up to 4
-static void stft_gemm(const Ctx& c, const mt2_audio_config& ac, const float* xp, int Rb, const int* rowbase, float* spec, int Fr) {
-    const int F = c.m.fe_nfreq;
+static void stft_gemm(const Ctx& c, const SpecGeom& g, const float* xp, int Rb, const int* rowbase, float* spec, int Fr) {
     GemmP p{};
-    p.X = xp; p.ldx = ac.hop_length; p.Rx = Rb; p.rowbase = rowbase; p.taps = ac.n_fft / ac.hop_length; p.Cin = ac.hop_length;
-    p.W = c.m.fe_basis; p.C = spec; p.ldc = (2 * F + 3) & ~3; p.M = Fr; p.N = 2 * F;
+    p.X = xp; p.ldx = g.hop; p.Rx = Rb; p.rowbase = rowbase; p.taps = g.taps; p.Cin = g.hop;
+    p.W = c.m.fe_basis; p.C = spec; p.ldc = g.lds; p.M = Fr; p.N = 2 * g.F;
     gemm(c, p);
 }
-// the front half of the mel front-end: reflect padding into blocks, then the STFT convolution -> spec [Fr, lds]
-static float* stft_run(const Ctx& c, const mt2_audio_config& ac, const float* wav, int L_max, const IntPlan& ip, const StftRows& r) {
-    const int hop = ac.hop_length, pad = ac.n_fft / 2;
-    float* xp = c.ws.get<float>((size_t)r.Rb * hop);
-    MT2_HIP(launch_reflect_pad_blocks(wav, L_max, ip.dev(r.o_b), ip.dev(r.o_t), ip.dev(r.o_len), hop, pad, xp, r.Rb, c.s));
-    float* spec = c.ws.get<float>((size_t)r.Fr * ((2 * c.m.fe_nfreq + 3) & ~3));
-    stft_gemm(c, ac, xp, r.Rb, ip.dev(r.o_base), spec, r.Fr);
-    return spec;
+// the front half of the mel front-end: reflect padding into blocks, then one STFT convolution over the batch -> the packed spec [Fr, lds]
+// and, on the device, the place b * T_max + t of each of its rows
+struct StftOut { const float* spec; const int* map; int Fr; };
+static StftOut stft_run(const Ctx& c, const mt2_audio_config& ac, const float* wav, const int* lens, int L_max, int B, int T_max) {
+    frontend_prepare(c.m, ac);
+    const SpecGeom g(ac);
+    const std::vector<int> T = stft_frames(g, lens, L_max, B, T_max);
+    const FrameRows r = frame_rows(g, T.data(), B, T_max);
+    IntPlan ip;
+    const int o_b = ip.add(r.blk_b), o_t = ip.add(r.blk_t), o_len = ip.add(lens, B), o_base = ip.add(r.rowbase), o_map = ip.add(r.map);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    float* xp = c.ws.get<float>((size_t)r.Rb * g.hop);
+    MT2_HIP(launch_reflect_pad_blocks(wav, L_max, ip.dev(o_b), ip.dev(o_t), ip.dev(o_len), g.hop, g.pad, xp, r.Rb, c.s));
+    float* spec = c.ws.get<float>((size_t)r.Fr * g.lds);
+    stft_gemm(c, g, xp, r.Rb, ip.dev(o_base), spec, r.Fr);
+    return {spec, ip.dev(o_map), r.Fr};
 }
 
 static void mel_spectrogram_run(const Ctx& c, const mt2_audio_config& ac, const float* wav, const int* lens, int L_max,
                                 int B, float* mel, int T_max) {
     mt2_model& m = c.m;
-    frontend_prepare(m, ac);
-    const int F = m.fe_nfreq, Fp = m.fe_nfreq_pad;
-    IntPlan ip;
-    const StftRows r = stft_plan(ip, ac, lens, L_max, B, T_max);
-    ip.upload(c.ws, c.m.pinned(), c.s);
-    const float* spec = stft_run(c, ac, wav, L_max, ip, r);
-    const int lds = (2 * F + 3) & ~3, Fr = r.Fr;
-    float* mag = c.ws.get<float>((size_t)Fr * Fp);
-    MT2_HIP(launch_magnitude(spec, lds, F, mag, Fp, Fr, c.s));
+    const StftOut s = stft_run(c, ac, wav, lens, L_max, B, T_max);
+    const SpecGeom g(ac);
+    const int Fr = s.Fr;
+    float* mag = c.ws.get<float>((size_t)Fr * g.Fp);
+    MT2_HIP(launch_magnitude(s.spec, g.lds, g.F, mag, g.Fp, Fr, c.s));
     float* mrows = c.ws.get<float>((size_t)Fr * ac.n_mels);
     {   // MelScale + dynamic range compression
         GemmP p{};
-        p.X = mag; p.ldx = Fp; p.Rx = Fr; p.Cin = Fp; p.W = m.fe_fb; p.C = mrows; p.ldc = ac.n_mels; p.M = Fr;
+        p.X = mag; p.ldx = g.Fp; p.Rx = Fr; p.Cin = g.Fp; p.W = m.fe_fb; p.C = mrows; p.ldc = ac.n_mels; p.M = Fr;
         p.N = ac.n_mels; p.epi_act = ACT_LOGCLAMP; p.pro_slope = ac.clip;
         gemm(c, p);
     }
     MT2_HIP(hipMemsetAsync(mel, 0, sizeof(float) * (size_t)B * T_max * ac.n_mels, c.s));
-    MT2_HIP(launch_unpack_rows(mrows, ac.n_mels, ac.n_mels, T_max, 0, ip.dev(r.o_map), mel, Fr, c.s));
+    MT2_HIP(launch_unpack_rows(mrows, ac.n_mels, ac.n_mels, T_max, 0, s.map, mel, Fr, c.s));
 }
 
 // spec f32 [B, T_max, lds] (re | im | zero pad; zeros in frames at or beyond T_b) = the STFT the mel front-end takes its magnitude of
 static void stft_only_run(const Ctx& c, const mt2_audio_config& ac, const float* wav, const int* lens, int L_max, int B, float* spec_out,
                           int T_max) {
     MT2_REQUIRE(wav != nullptr && lens != nullptr && spec_out != nullptr, "bad buffers");
-    frontend_prepare(c.m, ac);
-    IntPlan ip;
-    const StftRows r = stft_plan(ip, ac, lens, L_max, B, T_max);
-    ip.upload(c.ws, c.m.pinned(), c.s);
-    const float* spec = stft_run(c, ac, wav, L_max, ip, r);
-    const int lds = (2 * c.m.fe_nfreq + 3) & ~3;
+    const StftOut s = stft_run(c, ac, wav, lens, L_max, B, T_max);
+    const int lds = SpecGeom(ac).lds;
     MT2_HIP(hipMemsetAsync(spec_out, 0, sizeof(float) * (size_t)B * T_max * lds, c.s));
-    MT2_HIP(launch_unpack_rows(spec, lds, lds, T_max, 0, ip.dev(r.o_map), spec_out, r.Fr, c.s));
+    MT2_HIP(launch_unpack_rows(s.spec, lds, lds, T_max, 0, s.map, spec_out, s.Fr, c.s));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1836,6 +1861,14 @@ static bool outputs_overlap(std::initializer_list<Span> outs, std::initializer_l
     return false;
 }
 
+// what a call's layout function (its plan and its carve, a template over the arena) takes from an arena: the byte query of that call
+template <class Layout> static long long arena_bytes(Layout layout) {
+    ArenaCount count;
+    IntPlan ip;
+    layout(count, ip);
+    return (long long)count.bytes;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Griffin-Lim vocoder (griffinlim.hip holds the rule): mel -> linear magnitude by the filterbank's pseudo-inverse, random phase, then
 // n_iter rounds of inverse STFT -> forward STFT -> phase update.  Four launches a round: the inverse-DFT GEMM, the overlap-add (which
@@ -1862,46 +1895,56 @@ static int gl_min_frames(const mt2_audio_config& ac) { return ac.n_fft / (2 * ac
 static void gl_check_lens(const mt2_audio_config& ac, const int* T, int T_max, int B, long long L_max) {
     MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
     MT2_REQUIRE(T != nullptr && T_max >= 1, "mel_lens is NULL or T_max < 1");
-    long long rows = 0;
     for (int b = 0; b < B; ++b) {
         MT2_REQUIRE(T[b] >= gl_min_frames(ac) && T[b] <= T_max, "a frame count outside [n_fft / (2 hop) + 2, T_max]");
         MT2_REQUIRE(L_max >= (long long)(T[b] - 1) * ac.hop_length, "L_max smaller than (max T - 1) * hop_length");
-        rows += T[b] + ac.n_fft / ac.hop_length;
     }
-    MT2_REQUIRE(rows * (ac.n_fft + 4) <= INT_MAX, "batch too large for 32-bit row indices");
+    check_row_count(SpecGeom(ac), T, B);
 }
 // the arena of one griffin_lim_run, in carve order (the closed form is in megatts2_hip.h): the plan, exp(M), A, S / R / Rprev, the
 // frames, the block buffer.  Fr frame rows and Rb hop blocks in the batch
-struct GlWs { float *E, *A, *S, *R, *Rprev, *frames, *xp; };
-template <class Ws> static GlWs gl_carve(Ws& ws, IntPlan& ip, const mt2_audio_config& ac, size_t Fr, size_t Rb) {
-    const size_t N = ac.n_fft, F = N / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
+// The plan is built here too, so that mt2_griffin_lim_query (over an ArenaCount, seeds NULL: zeros) and griffin_lim_run (over the arena)
+// cannot disagree.  rstride = (n_iter + 1) T_max when the residuals are asked for, else 0: no rmap
+struct GlWs {
+    FrameRows r;
+    int o_b, o_t, o_base, o_map, o_rb, o_rt, o_row0, o_T, o_seed, o_rmap;
+    float *E, *A, *S, *R, *Rprev, *frames, *xp;
+};
+template <class Ws> static GlWs gl_layout(Ws& ws, IntPlan& ip, const mt2_audio_config& ac, const int* T, int T_max, int B,
+                                          const uint64_t* seeds, long long rstride) {
+    const SpecGeom g(ac);
     GlWs w{};
+    w.r = frame_rows(g, T, B, T_max);
+    const size_t Fr = w.r.Fr;
+    std::vector<int> row_b(Fr), row_t(Fr), sd(2 * (size_t)B, 0);
+    for (int b = 0, r = 0; b < B; ++b)
+        for (int t = 0; t < T[b]; ++t, ++r) { row_b[r] = b; row_t[r] = t; }
+    for (int b = 0; seeds && b < B; ++b) { sd[2 * b] = (int)(uint32_t)(seeds[b] & 0xFFFFFFFFu); sd[2 * b + 1] = (int)(uint32_t)(seeds[b] >> 32); }
+    w.o_b = ip.add(w.r.blk_b); w.o_t = ip.add(w.r.blk_t); w.o_base = ip.add(w.r.rowbase); w.o_map = ip.add(w.r.map);
+    w.o_rb = ip.add(row_b); w.o_rt = ip.add(row_t); w.o_row0 = ip.add(w.r.row0); w.o_T = ip.add(T, B); w.o_seed = ip.add(sd);
+    w.o_rmap = -1;
+    if (rstride) {
+        std::vector<int> rmap(Fr);
+        for (size_t r = 0; r < Fr; ++r) rmap[r] = (int)(row_b[r] * rstride + row_t[r]);
+        w.o_rmap = ip.add(rmap);
+    }
     ip.carve(ws);
     w.E = ws.template get<float>(Fr * ac.n_mels);
-    w.A = ws.template get<float>(Fr * Fp);
-    w.S = ws.template get<float>(Fr * lds);
-    w.R = ws.template get<float>(Fr * lds);
-    w.Rprev = ws.template get<float>(Fr * lds);
-    w.frames = ws.template get<float>(Fr * N);
-    w.xp = ws.template get<float>(Rb * ac.hop_length);
+    w.A = ws.template get<float>(Fr * g.Fp);
+    w.S = ws.template get<float>(Fr * g.lds);
+    w.R = ws.template get<float>(Fr * g.lds);
+    w.Rprev = ws.template get<float>(Fr * g.lds);
+    w.frames = ws.template get<float>(Fr * g.N);
+    w.xp = ws.template get<float>((size_t)w.r.Rb * g.hop);
     return w;
-}
-static long long gl_arena_bytes(const mt2_audio_config& ac, const int* T, int B, bool resid) {
-    size_t Fr = 0, Rb = 0;
-    for (int b = 0; b < B; ++b) { Fr += T[b]; Rb += T[b] - 1 + ac.n_fft / ac.hop_length; }
-    IntPlan ip;      // the entries of griffin_lim_run's plan, by size
-    for (size_t n : {Rb, Rb, Fr, Fr, Fr, Fr, (size_t)B, (size_t)B, 2 * (size_t)B}) ip.add_fill(n, 0);
-    if (resid) ip.add_fill(Fr, 0);
-    ArenaCount count;
-    gl_carve(count, ip, ac, Fr, Rb);
-    return (long long)count.bytes;
 }
 
 // the inverse basis [N, lds] (window and the 1/N, 2/N Hermitian weights folded in, zero columns for the imaginary parts of bins 0 and
 // N/2 and for the pad) and the squared window: built in double on the first call that inverts an STFT, rounded once
 static void gl_prepare_istft(mt2_model& m, const mt2_audio_config& ac) {
     gl_check_config(ac);
-    const int N = ac.n_fft, F = N / 2 + 1, lds = (2 * F + 3) & ~3, hop = ac.hop_length, pad = N / 2;
+    const SpecGeom g(ac);
+    const int N = g.N, F = g.F, lds = g.lds, hop = g.hop, pad = g.pad;
     const bool same = m.fe_basis && std::memcmp(&m.fe_cfg, &ac, sizeof(ac)) == 0;
     if (same && m.gl_ibasis) return;
     const double PI = 3.14159265358979323846;
@@ -1927,7 +1970,7 @@ static void gl_prepare_istft(mt2_model& m, const mt2_audio_config& ac) {
 // P = fb^T (fb fb^T)^-1 [Fp, n_mels] (rows F .. Fp-1 zero) by Cholesky in double from the f32 filterbank; refused when the Gram matrix
 // is not positive definite (filters without a bin: n_fft too small for n_mels)
 static std::vector<float> gl_pinv(const mt2_audio_config& ac) {
-    const int F = ac.n_fft / 2 + 1, Fp = (F + 3) & ~3, J = ac.n_mels;
+    const int F = SpecGeom(ac).F, Fp = SpecGeom(ac).Fp, J = ac.n_mels;
     const std::vector<float> fb = frontend_filterbank(ac, F, Fp);
     std::vector<double> G((size_t)J * J, 0.0);
     double dmax = 0.0;
@@ -1976,29 +2019,20 @@ static void gl_prepare_pinv(mt2_model& m, const mt2_audio_config& ac) {
     m.gl_P = frontend_upload(m, P);
 }
 
-// frame rows of a ragged batch of spectra / mels: utterance b owns rows row0[b] .. + T[b] and T[b] - 1 + taps blocks
-struct GlRows {
-    std::vector<int> blk_b, blk_t, rowbase, map, row_b, row_t, row0;
-    int Rb = 0, Fr = 0;
-};
-static GlRows gl_rows(const mt2_audio_config& ac, const int* T, int B, int T_max) {
-    GlRows g;
-    const int taps = ac.n_fft / ac.hop_length;
-    for (int b = 0; b < B; ++b) {
-        const int blk0 = (int)g.blk_b.size();
-        g.row0.push_back((int)g.rowbase.size());
-        for (int t = 0; t < T[b] - 1 + taps; ++t) { g.blk_b.push_back(b); g.blk_t.push_back(t); }
-        for (int t = 0; t < T[b]; ++t) { g.rowbase.push_back(blk0 + t); g.map.push_back(b * T_max + t); g.row_b.push_back(b); g.row_t.push_back(t); }
-    }
-    g.Rb = (int)g.blk_b.size(); g.Fr = (int)g.rowbase.size();
-    return g;
-}
 // frames[Fr, N] = S[Fr, lds] x inverse basis
-static void istft_gemm(const Ctx& c, const mt2_audio_config& ac, const float* S, float* frames, int Fr) {
-    const int lds = (2 * c.m.fe_nfreq + 3) & ~3;
+static void istft_gemm(const Ctx& c, const SpecGeom& g, const float* S, float* frames, int Fr) {
     GemmP p{};
-    p.X = S; p.ldx = lds; p.Rx = Fr; p.Cin = lds; p.W = c.m.gl_ibasis; p.C = frames; p.ldc = ac.n_fft; p.M = Fr; p.N = ac.n_fft;
+    p.X = S; p.ldx = g.lds; p.Rx = Fr; p.Cin = g.lds; p.W = c.m.gl_ibasis; p.C = frames; p.ldc = g.N; p.M = Fr; p.N = g.N;
     gemm(c, p);
+}
+// the back half of every inverse STFT: packed rows S [Fr, lds] -> frames on the fixed tile, overlap-added into wav [B, L_max]
+static void istft_rows_to_wav(const Ctx& c, const SpecGeom& g, const float* S, float* frames, int Fr, const int* row0, const int* T,
+                              float* wav, int L_max, int B) {
+    {
+        FixedTile ft(c.m.opts);
+        istft_gemm(c, g, S, frames, Fr);
+    }
+    MT2_HIP(launch_istft_ola_wav(frames, g.N, g.hop, c.m.gl_w2, row0, T, wav, L_max, B, c.s));
 }
 
 // torch.istft(center=True, length = (T - 1) hop) of spec f32 [B, T_max, lds] (re | im | pad, as stft_only_run leaves it) -> wav [B, L_max]
@@ -2007,20 +2041,16 @@ static void istft_run(const Ctx& c, const mt2_audio_config& ac, const float* spe
     gl_check_lens(ac, T, T_max, B, L_max);
     MT2_REQUIRE(spec != nullptr && wav != nullptr, "bad buffers");
     gl_prepare_istft(c.m, ac);
-    const int N = ac.n_fft, F = c.m.fe_nfreq, lds = (2 * F + 3) & ~3;
-    const GlRows g = gl_rows(ac, T, B, T_max);
+    const SpecGeom g(ac);
+    const FrameRows r = frame_rows(g, T, B, T_max);
     IntPlan ip;
-    const int o_map = ip.add(g.map), o_row0 = ip.add(g.row0), o_T = ip.add(T, B);
+    const int o_map = ip.add(r.map), o_row0 = ip.add(r.row0), o_T = ip.add(T, B);
     ip.upload(c.ws, c.m.pinned(), c.s);
-    float* S = c.ws.get<float>((size_t)g.Fr * lds);
-    MT2_HIP(hipMemsetAsync(S, 0, sizeof(float) * (size_t)g.Fr * lds, c.s));      // the pad columns meet zero basis columns: 0 x garbage must not be NaN
-    MT2_HIP(launch_pack_rows(spec, lds, T_max, 0, ip.dev(o_map), S, lds, g.Fr, c.s));
-    float* frames = c.ws.get<float>((size_t)g.Fr * N);
-    {
-        FixedTile ft(c.m.opts);
-        istft_gemm(c, ac, S, frames, g.Fr);
-    }
-    MT2_HIP(launch_istft_ola_wav(frames, N, ac.hop_length, c.m.gl_w2, ip.dev(o_row0), ip.dev(o_T), wav, L_max, B, c.s));
+    float* S = c.ws.get<float>((size_t)r.Fr * g.lds);
+    MT2_HIP(hipMemsetAsync(S, 0, sizeof(float) * (size_t)r.Fr * g.lds, c.s));      // the pad columns meet zero basis columns: 0 x garbage must not be NaN
+    MT2_HIP(launch_pack_rows(spec, g.lds, T_max, 0, ip.dev(o_map), S, g.lds, r.Fr, c.s));
+    float* frames = c.ws.get<float>((size_t)r.Fr * g.N);
+    istft_rows_to_wav(c, g, S, frames, r.Fr, ip.dev(o_row0), ip.dev(o_T), wav, L_max, B);
 }
 
 // A f32 [B, T_max, Fp] = max(0, exp(mel) P^T), zeros in frames at or beyond T_b and in columns F .. Fp-1
@@ -2068,45 +2098,35 @@ static void griffin_lim_run(const Ctx& c, const mt2_audio_config& ac, const floa
     gl_prepare_pinv(c.m, ac);
     gl_prepare_istft(c.m, ac);
     mt2_model& m = c.m;
-    const int N = ac.n_fft, hop = ac.hop_length, F = m.fe_nfreq, Fp = m.fe_nfreq_pad, lds = (2 * F + 3) & ~3;
+    const SpecGeom g(ac);
+    const int N = g.N, hop = g.hop, F = g.F, Fp = g.Fp, lds = g.lds;
     const float cm = (float)(momentum / (1.0 + momentum));
-    const GlRows g = gl_rows(ac, T, B, T_max);
-    const int Fr = g.Fr, Rb = g.Rb;
-    std::vector<int> sd(2 * (size_t)B);
-    for (int b = 0; b < B; ++b) { sd[2 * b] = (int)(uint32_t)(seeds[b] & 0xFFFFFFFFu); sd[2 * b + 1] = (int)(uint32_t)(seeds[b] >> 32); }
+    if (resid) MT2_REQUIRE((long long)B * (n_iter + 1) * T_max <= INT_MAX, "resid too large for 32-bit indices");
     IntPlan ip;
-    const int o_b = ip.add(g.blk_b), o_t = ip.add(g.blk_t), o_base = ip.add(g.rowbase), o_map = ip.add(g.map), o_rb = ip.add(g.row_b),
-              o_rt = ip.add(g.row_t), o_row0 = ip.add(g.row0), o_T = ip.add(T, B), o_seed = ip.add(sd);
-    int o_rmap = -1;
-    if (resid) {
-        std::vector<int> rmap(Fr);
-        for (int r = 0; r < Fr; ++r) rmap[r] = g.row_b[r] * (n_iter + 1) * T_max + g.row_t[r];
-        MT2_REQUIRE((long long)B * (n_iter + 1) * T_max <= INT_MAX, "resid too large for 32-bit indices");
-        o_rmap = ip.add(rmap);
-    }
-    const GlWs w = gl_carve(c.ws, ip, ac, Fr, Rb);
+    const GlWs w = gl_layout(c.ws, ip, ac, T, T_max, B, seeds, resid ? (long long)(n_iter + 1) * T_max : 0);
+    const int Fr = w.r.Fr, Rb = w.r.Rb;
     ip.send(m.pinned(), c.s);
-    const int* rmap = resid ? ip.dev(o_rmap) : nullptr;
+    const int *blk_b = ip.dev(w.o_b), *blk_t = ip.dev(w.o_t), *base = ip.dev(w.o_base), *row0 = ip.dev(w.o_row0), *dT = ip.dev(w.o_T);
+    const int* rmap = resid ? ip.dev(w.o_rmap) : nullptr;
     Stages st(m, c.s);
     st.mark("start");
     if (resid) MT2_HIP(hipMemsetAsync(resid, 0, sizeof(float) * (size_t)B * (n_iter + 1) * T_max, c.s));
-    mel_to_linear_rows(c, ac, mel, ip.dev(o_map), w.E, w.A, Fr);
-    MT2_HIP(launch_gl_phase_init(w.A, Fp, ip.dev(o_rb), ip.dev(o_rt), reinterpret_cast<const uint32_t*>(ip.dev(o_seed)), w.S, lds, F, Fr, c.s));
+    mel_to_linear_rows(c, ac, mel, ip.dev(w.o_map), w.E, w.A, Fr);
+    MT2_HIP(launch_gl_phase_init(w.A, Fp, ip.dev(w.o_rb), ip.dev(w.o_rt), reinterpret_cast<const uint32_t*>(ip.dev(w.o_seed)), w.S, lds, F, Fr, c.s));
     if (n_iter > 0) MT2_HIP(hipMemsetAsync(w.Rprev, 0, sizeof(float) * (size_t)Fr * lds, c.s));
     st.mark("gl_setup");
     FixedTile ft(m.opts);
     for (int k = 0; k < n_iter; ++k) {
-        istft_gemm(c, ac, w.S, w.frames, Fr);
-        MT2_HIP(launch_istft_ola_blocks(w.frames, N, hop, m.gl_w2, ip.dev(o_b), ip.dev(o_t), ip.dev(o_row0), ip.dev(o_T), w.xp, Rb, c.s));
-        stft_gemm(c, ac, w.xp, Rb, ip.dev(o_base), w.R, Fr);
+        istft_gemm(c, g, w.S, w.frames, Fr);
+        MT2_HIP(launch_istft_ola_blocks(w.frames, N, hop, m.gl_w2, blk_b, blk_t, row0, dT, w.xp, Rb, c.s));
+        stft_gemm(c, g, w.xp, Rb, base, w.R, Fr);
         MT2_HIP(launch_gl_phase_update(w.R, w.Rprev, w.A, Fp, w.S, lds, F, cm, resid ? resid + (size_t)k * T_max : nullptr, rmap, Fr, 1, c.s));
     }
     st.mark("gl_iterations");
-    istft_gemm(c, ac, w.S, w.frames, Fr);
-    MT2_HIP(launch_istft_ola_wav(w.frames, N, hop, m.gl_w2, ip.dev(o_row0), ip.dev(o_T), wav, L_max, B, c.s));
+    istft_rows_to_wav(c, g, w.S, w.frames, Fr, row0, dT, wav, L_max, B);
     if (resid) {      // entry n_iter: one extra STFT of the output, paid only on request
-        MT2_HIP(launch_istft_ola_blocks(w.frames, N, hop, m.gl_w2, ip.dev(o_b), ip.dev(o_t), ip.dev(o_row0), ip.dev(o_T), w.xp, Rb, c.s));
-        stft_gemm(c, ac, w.xp, Rb, ip.dev(o_base), w.R, Fr);
+        MT2_HIP(launch_istft_ola_blocks(w.frames, N, hop, m.gl_w2, blk_b, blk_t, row0, dT, w.xp, Rb, c.s));
+        stft_gemm(c, g, w.xp, Rb, base, w.R, Fr);
         MT2_HIP(launch_gl_phase_update(w.R, nullptr, w.A, Fp, nullptr, lds, F, cm, resid + (size_t)n_iter * T_max, rmap, Fr, 0, c.s));
     }
     st.mark("gl_final");
@@ -2870,13 +2890,15 @@ static DnArgs denoise_check_config(const mt2_denoise_config* dc) {
     MT2_REQUIRE(dc->reserved == 0, "mt2_denoise_config.reserved must be 0");
     return {dc->percentile, dc->smooth_bins, dc->smooth_frames, dc->over_subtraction, dc->floor_gain, denoise_factor(dc->percentile)};
 }
-static void denoise_fill(DenoiseP& p, const DnArgs& a, const mt2_audio_config& ac, int B, int T_cap) {
-    p.F = ac.n_fft / 2 + 1; p.Fp = (p.F + 3) & ~3; p.lds = (2 * p.F + 3) & ~3; p.B = B; p.T_cap = T_cap;
+static void denoise_fill(DenoiseP& p, const DnArgs& a, const SpecGeom& g, int B, int T_cap) {
+    p.F = g.F; p.Fp = g.Fp; p.lds = g.lds; p.B = B; p.T_cap = T_cap;
     p.percentile = a.percentile; p.bf = a.bf; p.bt = a.bt; p.beta = a.beta; p.gmin = a.gmin; p.c = a.c;
 }
 static size_t denoise_tiles(int T_cap, int F) { return (size_t)((T_cap + kDnTileT - 1) / kDnTileT) * ((F + kDnTileF - 1) / kDnTileF); }
+
+// ---- the round trip of mt2_denoise and mt2_dereverb: waveforms -> STFT -> the call's own work on the packed spectrum -> inverse STFT
 // the frame counts of a waveform batch, T_b = 1 + L_b / hop, each inside what the inverse STFT accepts; -> their max
-static int denoise_frames(const mt2_audio_config& ac, const int* lens, int L_max, int B, std::vector<int>& T) {
+static int wave_frames(const mt2_audio_config& ac, const int* lens, int L_max, int B, std::vector<int>& T) {
     gl_check_config(ac);
     MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
     MT2_REQUIRE(L_max >= 1, "L_max < 1");
@@ -2893,87 +2915,96 @@ static int denoise_frames(const mt2_audio_config& ac, const int* lens, int L_max
     gl_check_lens(ac, T.data(), T_cap, B, (long long)(T_cap - 1) * ac.hop_length);
     return T_cap;
 }
-// the arena of one denoise_run, in carve order: the plan, the reflect-padded blocks, the packed spectrum (gated in place), P, the
-// floor, the tile sums and the frames of the inverse STFT - taken whatever the optional arguments
-struct DnWs { float *xp, *spec, *P, *floor; double* part; float* frames; };
-template <class Ws> static DnWs denoise_carve(Ws& ws, IntPlan& ip, const mt2_audio_config& ac, size_t Fr, size_t Rb, size_t B, int T_cap) {
-    const size_t N = ac.n_fft, F = N / 2 + 1, Fp = (F + 3) & ~size_t(3), lds = (2 * F + 3) & ~size_t(3);
-    DnWs w{};
-    ip.carve(ws);
-    w.xp = ws.template get<float>(Rb * ac.hop_length);
-    w.spec = ws.template get<float>(Fr * lds);
-    w.P = ws.template get<float>(Fr * Fp);
-    w.floor = ws.template get<float>(B * Fp);
-    w.part = ws.template get<double>(B * denoise_tiles(T_cap, (int)F) * 3);
-    w.frames = ws.template get<float>(Fr * N);
-    return w;
-}
-static long long denoise_arena_bytes(const mt2_audio_config& ac, const std::vector<int>& T, int T_cap) {
-    const size_t B = T.size();
-    size_t Fr = 0, Rb = 0;
-    for (int t : T) { Fr += t; Rb += t - 1 + ac.n_fft / ac.hop_length; }
-    IntPlan ip;      // the entries of denoise_run's plan, by size
-    for (size_t n : {Rb, Rb, B, Fr, Fr, B, B}) ip.add_fill(n, 0);
-    ArenaCount count;
-    denoise_carve(count, ip, ac, Fr, Rb, B, T_cap);
-    return (long long)count.bytes;
-}
-// -> T_cap, with T filled
-static int denoise_check(const mt2_audio_config* ac, const mt2_denoise_config* dc, const float* wav, const int* lens, int L_max, int B,
-                         const float* floor_in, const float* floor_out, const double* figures, const float* out, int Lout_max,
-                         std::vector<int>& T, DnArgs& a) {
-    MT2_REQUIRE(ac != nullptr, "null audio configuration");
-    a = denoise_check_config(dc);
+// what both calls refuse about their waveform batch, after their own configuration; a call without floors passes NULL for them, and
+// `fields` doubles an utterance of figures.  -> T_cap, with T filled
+static int wave_check(const mt2_audio_config& ac, const float* wav, const int* lens, int L_max, int B, const float* floor_in, const float* floor_out,
+                      const double* figures, int fields, const float* out, int Lout_max, std::vector<int>& T) {
     MT2_REQUIRE(wav != nullptr && lens != nullptr && out != nullptr, "bad buffers");
-    const int T_cap = denoise_frames(*ac, lens, L_max, B, T);
-    MT2_REQUIRE((long long)Lout_max >= (long long)(T_cap - 1) * ac->hop_length, "Lout_max smaller than (max T - 1) * hop_length");
+    const int T_cap = wave_frames(ac, lens, L_max, B, T);
+    MT2_REQUIRE((long long)Lout_max >= (long long)(T_cap - 1) * ac.hop_length, "Lout_max smaller than (max T - 1) * hop_length");
     MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)out | (uintptr_t)floor_in | (uintptr_t)floor_out) & 3) == 0 && ((uintptr_t)figures & 7) == 0,
                 "misaligned buffers");
-    const size_t Fp = (size_t)((ac->n_fft / 2 + 1 + 3) & ~3);
-    const size_t nw = sizeof(float) * (size_t)B * L_max, no = sizeof(float) * (size_t)B * Lout_max, nf = sizeof(float) * (size_t)B * Fp,
-                 ng = sizeof(double) * MT2_DENOISE_FIELDS * (size_t)B;
+    const size_t nw = sizeof(float) * (size_t)B * L_max, no = sizeof(float) * (size_t)B * Lout_max,
+                 nf = sizeof(float) * (size_t)B * SpecGeom(ac).Fp, ng = sizeof(double) * fields * (size_t)B;
     MT2_REQUIRE(!outputs_overlap({{out, no}, {floor_out, nf}, {figures, ng}}, {{wav, nw}, {floor_in, nf}}), "overlapping buffers");
     return T_cap;
 }
-// enqueues only.  The STFT GEMM runs per utterance, on the tile its own row count chooses - what mt2_stft runs for the utterance alone;
-// the inverse GEMM runs once on the fixed tile of mt2_istft.
+// The arena of a round trip, in carve order: the plan, the reflect-padded blocks, the packed spectrum (worked on in place), the call's
+// own buffers, the frames of the inverse STFT - taken whatever the optional arguments.  trip_plan adds the plan entries both calls have
+// (lens NULL, as in a query: zeros), the call adds its own behind them, and trip_carve places the plan and the buffers - over the arena
+// in the run and over an ArenaCount in the query, so the two cannot disagree
+struct Trip {
+    FrameRows r;
+    int o_b, o_t, o_len, o_base, o_map, o_row0, o_T;
+    float *xp, *spec, *frames;
+};
+static Trip trip_plan(IntPlan& ip, const SpecGeom& g, const int* lens, const std::vector<int>& T, int T_cap) {
+    Trip t{};
+    const int B = (int)T.size();
+    t.r = frame_rows(g, T.data(), B, T_cap);
+    t.o_b = ip.add(t.r.blk_b); t.o_t = ip.add(t.r.blk_t); t.o_len = lens ? ip.add(lens, B) : ip.add_fill(B, 0);
+    t.o_base = ip.add(t.r.rowbase); t.o_map = ip.add(t.r.map); t.o_row0 = ip.add(t.r.row0); t.o_T = ip.add(T);
+    return t;
+}
+template <class Ws, class Own> static void trip_carve(Ws& ws, IntPlan& ip, const SpecGeom& g, Trip& t, Own own) {
+    ip.carve(ws);
+    t.xp = ws.template get<float>((size_t)t.r.Rb * g.hop);
+    t.spec = ws.template get<float>((size_t)t.r.Fr * g.lds);
+    own();
+    t.frames = ws.template get<float>((size_t)t.r.Fr * g.N);
+}
+// enqueues only; `mid` works on t.spec in place and sets its own stage marks.  The STFT GEMM runs per utterance, on the tile its own row
+// count chooses - what mt2_stft runs for the utterance alone; the inverse GEMM runs once on the fixed tile of mt2_istft.
+template <class Mid> static void trip_run(const Ctx& c, const SpecGeom& g, IntPlan& ip, const Trip& t, const std::vector<int>& T, const float* wav,
+                                          int L_max, float* out, int Lout_max, const std::string& prefix, Mid mid) {
+    const int B = (int)T.size();
+    ip.send(c.m.pinned(), c.s);
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(launch_reflect_pad_blocks(wav, L_max, ip.dev(t.o_b), ip.dev(t.o_t), ip.dev(t.o_len), g.hop, g.pad, t.xp, t.r.Rb, c.s));
+    MT2_HIP(hipMemsetAsync(t.spec, 0, sizeof(float) * (size_t)t.r.Fr * g.lds, c.s));      // the pad columns meet zero basis columns
+    for (int b = 0; b < B; ++b)
+        stft_gemm(c, g, t.xp, t.r.Rb, ip.dev(t.o_base) + t.r.row0[b], t.spec + (size_t)t.r.row0[b] * g.lds, T[b]);
+    st.mark((prefix + "stft").c_str());
+    mid(st);
+    istft_rows_to_wav(c, g, t.spec, t.frames, t.r.Fr, ip.dev(t.o_row0), ip.dev(t.o_T), out, Lout_max, B);
+    st.mark((prefix + "istft").c_str());
+    st.finish();
+}
+
+// the buffers of denoise's own between the spectrum and the frames: P, the floor, the tile sums
+struct DnWs { Trip t; float *P, *floor; double* part; };
+template <class Ws> static DnWs denoise_layout(Ws& ws, IntPlan& ip, const SpecGeom& g, const int* lens, const std::vector<int>& T, int T_cap) {
+    DnWs w{};
+    w.t = trip_plan(ip, g, lens, T, T_cap);
+    trip_carve(ws, ip, g, w.t, [&] {
+        w.P = ws.template get<float>((size_t)w.t.r.Fr * g.Fp);
+        w.floor = ws.template get<float>(T.size() * g.Fp);
+        w.part = ws.template get<double>(T.size() * denoise_tiles(T_cap, g.F) * 3);
+    });
+    return w;
+}
 static void denoise_run(const Ctx& c, const mt2_audio_config& ac, const DnArgs& a, const float* wav, const int* lens, int L_max, int B,
                         const std::vector<int>& T, int T_cap, const float* floor_in, float* floor_out, double* figures, float* out,
                         int Lout_max) {
     gl_prepare_istft(c.m, ac);
+    const SpecGeom g(ac);
     IntPlan ip;
-    const StftRows r = stft_plan(ip, ac, lens, L_max, B, T_cap);
-    std::vector<int> row0(B);
-    for (int b = 0, at = 0; b < B; at += T[b], ++b) row0[b] = at;
-    const int o_row0 = ip.add(row0), o_T = ip.add(T);
-    const DnWs w = denoise_carve(c.ws, ip, ac, r.Fr, r.Rb, B, T_cap);
-    ip.send(c.m.pinned(), c.s);
+    const DnWs w = denoise_layout(c.ws, ip, g, lens, T, T_cap);
     DenoiseP p{};
-    denoise_fill(p, a, ac, B, T_cap);
-    p.spec = w.spec; p.spec_out = w.spec; p.row0 = ip.dev(o_row0); p.T = ip.dev(o_T); p.P = w.P; p.floor_out = w.floor;
+    denoise_fill(p, a, g, B, T_cap);
+    p.spec = w.t.spec; p.spec_out = w.t.spec; p.row0 = ip.dev(w.t.o_row0); p.T = ip.dev(w.t.o_T); p.P = w.P; p.floor_out = w.floor;
     p.floor = floor_in ? floor_in : w.floor;
     if (figures) { p.part = w.part; p.fig = figures; }
-    Stages st(c.m, c.s);
-    st.mark("start");
-    MT2_HIP(launch_reflect_pad_blocks(wav, L_max, ip.dev(r.o_b), ip.dev(r.o_t), ip.dev(r.o_len), ac.hop_length, ac.n_fft / 2, w.xp, r.Rb, c.s));
-    MT2_HIP(hipMemsetAsync(w.spec, 0, sizeof(float) * (size_t)r.Fr * p.lds, c.s));      // the pad columns meet zero basis columns
-    for (int b = 0; b < B; ++b)
-        stft_gemm(c, ac, w.xp, r.Rb, ip.dev(r.o_base) + row0[b], w.spec + (size_t)row0[b] * p.lds, T[b]);
-    st.mark("dn_stft");
-    MT2_HIP(launch_denoise_power(p, c.s));
-    if (!floor_in) MT2_HIP(launch_denoise_select(p, c.s));
-    if (floor_out) MT2_HIP(hipMemcpyAsync(floor_out, p.floor, sizeof(float) * (size_t)B * p.Fp, hipMemcpyDeviceToDevice, c.s));
-    st.mark("dn_floor");
-    MT2_HIP(launch_denoise_gain(p, c.s));
-    if (figures) MT2_HIP(launch_denoise_figures(p, c.s));
-    st.mark("dn_gain");
-    {
-        FixedTile ft(c.m.opts);
-        istft_gemm(c, ac, w.spec, w.frames, r.Fr);
-    }
-    MT2_HIP(launch_istft_ola_wav(w.frames, ac.n_fft, ac.hop_length, c.m.gl_w2, ip.dev(o_row0), ip.dev(o_T), out, Lout_max, B, c.s));
-    st.mark("dn_istft");
-    st.finish();
+    trip_run(c, g, ip, w.t, T, wav, L_max, out, Lout_max, "dn_", [&](Stages& st) {
+        MT2_HIP(launch_denoise_power(p, c.s));
+        if (!floor_in) MT2_HIP(launch_denoise_select(p, c.s));
+        if (floor_out) MT2_HIP(hipMemcpyAsync(floor_out, p.floor, sizeof(float) * (size_t)B * p.Fp, hipMemcpyDeviceToDevice, c.s));
+        st.mark("dn_floor");
+        MT2_HIP(launch_denoise_gain(p, c.s));
+        if (figures) MT2_HIP(launch_denoise_figures(p, c.s));
+        st.mark("dn_gain");
+    });
 }
 
 // the spectrum batch of mt2_noise_floor and mt2_spectral_gain: utterance b owns the rows b T_max .. + frame_lens[b];  -> max frame count
@@ -2986,17 +3017,23 @@ static int denoise_check_spec(const mt2_audio_config* ac, const float* spec, con
     MT2_REQUIRE((long long)B * T_max * (ac->n_fft + 4) <= INT_MAX, "batch too large for 32-bit row indices");
     return check_lens(frame_lens, B, T_max, "a frame count outside [1, T_max]");
 }
+// the first two plan entries of every call on a caller's spectrum batch [B, T_max, lds]: row0[b] = b T_max, then the frame counts
+struct SpecBatch { int o_row0, o_T; };
+static SpecBatch spec_batch_plan(IntPlan& ip, const int* frame_lens, int T_max, int B) {
+    std::vector<int> row0(B);
+    for (int b = 0; b < B; ++b) row0[b] = b * T_max;
+    const int o_row0 = ip.add(row0);
+    return {o_row0, ip.add(frame_lens, B)};
+}
 // the plan and P of both calls (their whole arena: the plan of 2 B words, then 4 B T_max Fp bytes), and the power kernel
 static DenoiseP denoise_spec_setup(const Ctx& c, const mt2_audio_config& ac, const DnArgs& a, const float* spec, const int* frame_lens,
                                    int T_max, int B, int T_cap) {
     IntPlan ip;
-    std::vector<int> row0(B);
-    for (int b = 0; b < B; ++b) row0[b] = b * T_max;
-    const int o_row0 = ip.add(row0), o_T = ip.add(frame_lens, B);
+    const SpecBatch sb = spec_batch_plan(ip, frame_lens, T_max, B);
     ip.upload(c.ws, c.m.pinned(), c.s);
     DenoiseP p{};
-    denoise_fill(p, a, ac, B, T_cap);
-    p.spec = spec; p.row0 = ip.dev(o_row0); p.T = ip.dev(o_T);
+    denoise_fill(p, a, SpecGeom(ac), B, T_cap);
+    p.spec = spec; p.row0 = ip.dev(sb.o_row0); p.T = ip.dev(sb.o_T);
     p.P = c.ws.get<float>((size_t)B * T_max * p.Fp);
     MT2_HIP(launch_denoise_power(p, c.s));
     return p;
@@ -3042,8 +3079,8 @@ static size_t wpe_columns(const std::vector<int>& T, int F, std::vector<int>& c0
     MT2_REQUIRE(at <= (size_t)INT_MAX, "batch too large for 32-bit column indices");
     return at;
 }
-static void wpe_fill(WpeP& p, const WpeArgs& a, const mt2_audio_config& ac, int B, int T_cap) {
-    p.F = ac.n_fft / 2 + 1; p.Fp = (p.F + 3) & ~3; p.lds = (2 * p.F + 3) & ~3; p.B = B; p.T_cap = T_cap;
+static void wpe_fill(WpeP& p, const WpeArgs& a, const SpecGeom& g, int B, int T_cap) {
+    p.F = g.F; p.Fp = g.Fp; p.lds = g.lds; p.B = B; p.T_cap = T_cap;
     p.delay = a.delay; p.taps = a.taps; p.iters = a.iters; p.ctx = a.ctx; p.eps = a.eps; p.load = a.load;
 }
 // transposition, the bins, the way back and the figures: the four launches of both calls
@@ -3055,93 +3092,52 @@ static void wpe_launches(const Ctx& c, WpeP& p, double* filters, double* figures
     MT2_HIP(launch_wpe_from_bins(p, c.s));
     if (figures) MT2_HIP(launch_wpe_figures(p, c.s));
 }
-// the arena of one dereverb_run, in carve order: the plan, the reflect-padded blocks, the packed spectrum (filtered in place), the
-// columns of Y and of D, the bins' sums and the frames of the inverse STFT - taken whatever the optional arguments
-struct WpeWs { float *xp, *spec; float2 *cols, *cols_out; double* stat; float* frames; };
-template <class Ws> static WpeWs dereverb_carve(Ws& ws, IntPlan& ip, const mt2_audio_config& ac, size_t Fr, size_t Rb, size_t B, size_t cells) {
-    const size_t N = ac.n_fft, F = N / 2 + 1, lds = (2 * F + 3) & ~size_t(3);
+// the plan entries of dereverb's own behind the round trip's (c0, run) and its buffers between the spectrum and the frames: the columns
+// of Y and of D, the bins' sums.  An utterance of fewer than delay + 4 taps frames is not filtered: its bins pass through.
+struct WpeWs { Trip t; int o_c0, o_run; float2 *cols, *cols_out; double* stat; };
+template <class Ws> static WpeWs dereverb_layout(Ws& ws, IntPlan& ip, const SpecGeom& g, const WpeArgs& a, const int* lens, const std::vector<int>& T,
+                                                 int T_cap) {
     WpeWs w{};
-    ip.carve(ws);
-    w.xp = ws.template get<float>(Rb * ac.hop_length);
-    w.spec = ws.template get<float>(Fr * lds);
-    w.cols = reinterpret_cast<float2*>(ws.template get<float>(2 * cells));
-    w.cols_out = reinterpret_cast<float2*>(ws.template get<float>(2 * cells));
-    w.stat = ws.template get<double>(B * F * kWpeStat);
-    w.frames = ws.template get<float>(Fr * N);
+    w.t = trip_plan(ip, g, lens, T, T_cap);
+    std::vector<int> run(T.size()), c0;
+    for (size_t b = 0; b < T.size(); ++b) run[b] = T[b] >= a.delay + 4 * a.taps;
+    const size_t cells = wpe_columns(T, g.F, c0);
+    w.o_c0 = ip.add(c0); w.o_run = ip.add(run);
+    trip_carve(ws, ip, g, w.t, [&] {
+        w.cols = reinterpret_cast<float2*>(ws.template get<float>(2 * cells));
+        w.cols_out = reinterpret_cast<float2*>(ws.template get<float>(2 * cells));
+        w.stat = ws.template get<double>(T.size() * g.F * kWpeStat);
+    });
     return w;
 }
-static long long dereverb_arena_bytes(const mt2_audio_config& ac, const std::vector<int>& T) {
-    const size_t B = T.size();
-    size_t Fr = 0, Rb = 0;
-    for (int t : T) { Fr += t; Rb += t - 1 + ac.n_fft / ac.hop_length; }
-    std::vector<int> c0;
-    const size_t cells = wpe_columns(T, ac.n_fft / 2 + 1, c0);
-    IntPlan ip;      // the entries of dereverb_run's plan, by size
-    for (size_t n : {Rb, Rb, B, Fr, Fr, B, B, B, B}) ip.add_fill(n, 0);
-    ArenaCount count;
-    dereverb_carve(count, ip, ac, Fr, Rb, B, cells);
-    return (long long)count.bytes;
-}
-// -> T_cap, with T filled
-static int dereverb_check(const mt2_audio_config* ac, const mt2_wpe_config* wc, const float* wav, const int* lens, int L_max, int B,
-                          const double* figures, const float* out, int Lout_max, std::vector<int>& T, WpeArgs& a) {
-    MT2_REQUIRE(ac != nullptr, "null audio configuration");
-    a = wpe_check_config(wc);
-    MT2_REQUIRE(wav != nullptr && lens != nullptr && out != nullptr, "bad buffers");
-    const int T_cap = denoise_frames(*ac, lens, L_max, B, T);
-    MT2_REQUIRE((long long)Lout_max >= (long long)(T_cap - 1) * ac->hop_length, "Lout_max smaller than (max T - 1) * hop_length");
-    MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)out) & 3) == 0 && ((uintptr_t)figures & 7) == 0, "misaligned buffers");
-    const size_t nw = sizeof(float) * (size_t)B * L_max, no = sizeof(float) * (size_t)B * Lout_max, ng = sizeof(double) * MT2_WPE_FIELDS * (size_t)B;
-    MT2_REQUIRE(!outputs_overlap({{out, no}, {figures, ng}}, {{wav, nw}}), "overlapping buffers");
-    return T_cap;
-}
-// enqueues only.  The STFT GEMM runs per utterance and the inverse one on the fixed tile, as in denoise_run.  An utterance of fewer than
-// delay + 4 taps frames is not filtered: its bins pass through.
 static void dereverb_run(const Ctx& c, const mt2_audio_config& ac, const WpeArgs& a, const float* wav, const int* lens, int L_max, int B,
                          const std::vector<int>& T, int T_cap, double* figures, float* out, int Lout_max) {
     gl_prepare_istft(c.m, ac);
+    const SpecGeom g(ac);
     IntPlan ip;
-    const StftRows r = stft_plan(ip, ac, lens, L_max, B, T_cap);
-    std::vector<int> row0(B), run(B), c0;
-    for (int b = 0, at = 0; b < B; at += T[b], ++b) { row0[b] = at; run[b] = T[b] >= a.delay + 4 * a.taps; }
-    const size_t cells = wpe_columns(T, ac.n_fft / 2 + 1, c0);
-    const int o_row0 = ip.add(row0), o_T = ip.add(T), o_c0 = ip.add(c0), o_run = ip.add(run);
-    const WpeWs w = dereverb_carve(c.ws, ip, ac, r.Fr, r.Rb, B, cells);
-    ip.send(c.m.pinned(), c.s);
+    const WpeWs w = dereverb_layout(c.ws, ip, g, a, lens, T, T_cap);
     WpeP p{};
-    wpe_fill(p, a, ac, B, T_cap);
-    p.spec = w.spec; p.spec_out = w.spec; p.row0 = ip.dev(o_row0); p.T = ip.dev(o_T); p.c0 = ip.dev(o_c0); p.run = ip.dev(o_run);
+    wpe_fill(p, a, g, B, T_cap);
+    p.spec = w.t.spec; p.spec_out = w.t.spec; p.row0 = ip.dev(w.t.o_row0); p.T = ip.dev(w.t.o_T); p.c0 = ip.dev(w.o_c0); p.run = ip.dev(w.o_run);
     p.cols = w.cols; p.cols_out = w.cols_out; p.stat = w.stat;
-    Stages st(c.m, c.s);
-    st.mark("start");
-    MT2_HIP(launch_reflect_pad_blocks(wav, L_max, ip.dev(r.o_b), ip.dev(r.o_t), ip.dev(r.o_len), ac.hop_length, ac.n_fft / 2, w.xp, r.Rb, c.s));
-    MT2_HIP(hipMemsetAsync(w.spec, 0, sizeof(float) * (size_t)r.Fr * p.lds, c.s));      // the pad columns meet zero basis columns
-    for (int b = 0; b < B; ++b)
-        stft_gemm(c, ac, w.xp, r.Rb, ip.dev(r.o_base) + row0[b], w.spec + (size_t)row0[b] * p.lds, T[b]);
-    st.mark("dr_stft");
-    wpe_launches(c, p, nullptr, figures);
-    st.mark("dr_wpe");
-    {
-        FixedTile ft(c.m.opts);
-        istft_gemm(c, ac, w.spec, w.frames, r.Fr);
-    }
-    MT2_HIP(launch_istft_ola_wav(w.frames, ac.n_fft, ac.hop_length, c.m.gl_w2, ip.dev(o_row0), ip.dev(o_T), out, Lout_max, B, c.s));
-    st.mark("dr_istft");
-    st.finish();
+    trip_run(c, g, ip, w.t, T, wav, L_max, out, Lout_max, "dr_", [&](Stages& st) {
+        wpe_launches(c, p, nullptr, figures);
+        st.mark("dr_wpe");
+    });
 }
 // steps 1-3 on a caller's spectrum batch: utterance b owns the rows b T_max .. + frame_lens[b].  Its arena: the plan of 4 B words, the
 // columns of Y and of D, the bins' sums
 static void wpe_spectrum_run(const Ctx& c, const mt2_audio_config& ac, const WpeArgs& a, const float* spec, const int* frame_lens, int T_max,
                              int B, int T_cap, float* spec_out, double* filters, double* figures) {
     IntPlan ip;
-    std::vector<int> row0(B), T(frame_lens, frame_lens + B), run(B, 1), c0;
-    for (int b = 0; b < B; ++b) row0[b] = b * T_max;
-    const size_t cells = wpe_columns(T, ac.n_fft / 2 + 1, c0);
-    const int o_row0 = ip.add(row0), o_T = ip.add(T), o_c0 = ip.add(c0), o_run = ip.add(run);
+    std::vector<int> run(B, 1), c0;
+    const SpecBatch sb = spec_batch_plan(ip, frame_lens, T_max, B);
+    const size_t cells = wpe_columns(std::vector<int>(frame_lens, frame_lens + B), SpecGeom(ac).F, c0);
+    const int o_c0 = ip.add(c0), o_run = ip.add(run);
     ip.upload(c.ws, c.m.pinned(), c.s);
     WpeP p{};
-    wpe_fill(p, a, ac, B, T_cap);
-    p.spec = spec; p.spec_out = spec_out; p.row0 = ip.dev(o_row0); p.T = ip.dev(o_T); p.c0 = ip.dev(o_c0); p.run = ip.dev(o_run);
+    wpe_fill(p, a, SpecGeom(ac), B, T_cap);
+    p.spec = spec; p.spec_out = spec_out; p.row0 = ip.dev(sb.o_row0); p.T = ip.dev(sb.o_T); p.c0 = ip.dev(o_c0); p.run = ip.dev(o_run);
     p.cols = reinterpret_cast<float2*>(c.ws.get<float>(2 * cells));
     p.cols_out = reinterpret_cast<float2*>(c.ws.get<float>(2 * cells));
     p.stat = c.ws.get<double>((size_t)B * p.F * kWpeStat);

@@ -181,7 +181,7 @@ def dataclass_fields(d):
 
 
 def carve(audio, lens):
-    """denoise_carve by hand: every piece rounded up to 256 bytes, never none"""
+    """denoise_layout by hand: every piece rounded up to 256 bytes, never none"""
     r = lambda n: max(256, (n + 255) // 256 * 256)
     q = lambda n: (n + 3) // 4 * 4
     N, h = audio.n_fft, audio.hop_length

@@ -218,6 +218,20 @@ def test_floor_gain_one_is_istft_of_stft(name, T):
     assert same(got.cpu().numpy(), want.cpu().numpy())
 
 
+@pytest.mark.parametrize("name, T", [("small", 65), ("prod", 45)])
+def test_the_call_is_the_composition_of_the_public_calls(name, T):
+    """one utterance, default configuration (the gate at work): mt2_denoise gives the bits of mt2_stft -> mt2_noise_floor ->
+    mt2_spectral_gain (apply) -> mt2_istft"""
+    fe = frontend(name)
+    x = dev(signal(name, T)[None])
+    spec = fe.stft(x)
+    want = fe.istft(fe.spectral_gain(spec, fe.noise_floor(spec), return_gain=False, apply=True))
+    got, lens = fe.denoise(x)
+    assert lens[0] == (T - 1) * audio(name).hop_length == want.shape[1]
+    assert same(got.cpu().numpy(), want.cpu().numpy())
+    assert not same(got.cpu().numpy(), fe.istft(spec).cpu().numpy())
+
+
 # ---- 4. the whole call against float64 --------------------------------------------------------------------------------------------------
 
 def rel_l2(a, b):

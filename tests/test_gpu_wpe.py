@@ -220,6 +220,20 @@ def test_a_hop_aligned_echo_is_removed_on_the_device(name, hops, L):
         assert len(d) == len(ref) and after <= ECHO[(name, hops, L)][1]
 
 
+@pytest.mark.parametrize("name, T", [("small", 65), ("prod", 45)])
+def test_the_call_is_the_composition_of_the_public_calls(name, T):
+    """one utterance of at least delay + 4 taps = 43 frames, default configuration (the filter at work): mt2_dereverb gives the bits of
+    mt2_stft -> mt2_wpe_spectrum -> mt2_istft"""
+    fe, a = frontend(name), audio(name)
+    x = dev(W.spectrum_signal(a, T, seed=31)[None])
+    spec = fe.stft(x)
+    want = fe.istft(fe.wpe_spectrum(spec))
+    got, lens = fe.dereverb(x)
+    assert lens[0] == (T - 1) * a.hop_length == want.shape[1]
+    assert same(got.cpu().numpy(), want.cpu().numpy())
+    assert not same(got.cpu().numpy(), fe.istft(spec).cpu().numpy())
+
+
 # ---- 3. batches and the write set --------------------------------------------------------------------------------------------------
 
 def wav_batch(xs, extra=5):

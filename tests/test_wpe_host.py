@@ -204,7 +204,7 @@ def test_exports_and_the_struct(rt):
 
 
 def carve(a, lens):
-    """dereverb_carve by hand: every piece rounded up to 256 bytes, never none"""
+    """dereverb_layout by hand: every piece rounded up to 256 bytes, never none"""
     r = lambda n: max(256, (n + 255) // 256 * 256)
     q = lambda n: (n + 3) // 4 * 4
     N, h = a.n_fft, a.hop_length

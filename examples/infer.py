@@ -83,6 +83,17 @@ def main() -> None:
     ap.add_argument("--report-clipping", action="store_true",
                     help="print, for each prompt file, whether it is clipped, the two levels and the share of samples at them, and with "
                          "--declip-prompt the iterations and the power change; alone it only detects (on the GPU) and warns")
+    ap.add_argument("--cut-prompt-pauses", action="store_true",
+                    help="cut the pauses out of every prompt file on the GPU, its ends included (speech segments by frame energy, in place of "
+                         "--trim-db): the threshold is relative to the loudest frame, so room tone above it reads as speech and nothing is cut; "
+                         "a breath is speech or pause by its level alone; no cross-fade")
+    ap.add_argument("--pause-db", type=float, default=40.0, metavar="DB", help="with --cut-prompt-pauses / --report-pauses: a frame is active above this many dB under the loudest frame (default 40)")
+    ap.add_argument("--min-pause-ms", type=float, default=320.0, metavar="MS", help="... pauses shorter than this stay (default 320)")
+    ap.add_argument("--min-speech-ms", type=float, default=96.0, metavar="MS", help="... runs of speech shorter than this are dropped (default 96)")
+    ap.add_argument("--pause-pad-ms", type=float, default=64.0, metavar="MS", help="... kept on both sides of every segment; under half of --min-pause-ms (default 64)")
+    ap.add_argument("--report-pauses", action="store_true",
+                    help="print, for each prompt file, its speech segments, the seconds of speech of the total, the longest pause and the "
+                         "speech / pause energy ratio in dB (measured on the GPU); alone it only reports, nothing is cut")
     ap.add_argument("--reference-wav", metavar="PATH",
                     help="a recording of the same sentence: print the mel-cepstral distortion (dB, along the DTW path of the cepstra), the largest "
                          "cell, and F0 RMSE, register offset and voiced / unvoiced error along the same path, of the generated audio against it")
@@ -108,13 +119,39 @@ def main() -> None:
     dn = M.Denoise(a.denoise_percentile, a.denoise_strength, 10.0 ** (a.denoise_floor_db / 20.0))
     dr = M.Dereverb(delay=a.dereverb_delay, taps=a.dereverb_taps, iterations=a.dereverb_iterations)
     dc = M.Declip(frame=a.declip_frame, tol=a.declip_tol, eps=a.declip_eps)
+    pa = M.Pauses(top_db=a.pause_db, min_pause_ms=a.min_pause_ms, min_speech_ms=a.min_speech_ms, pad_ms=a.pause_pad_ms)
     mel, lens, aux = tts(a.wavs_dir, a.text, phone_tokens=phones, out_path=a.out, trim_db=a.trim_db, vocoder=gl, loudness_lufs=a.output_lufs,
                          peak_ceiling=a.peak_ceiling, true_peak_ceiling_dbtp=a.true_peak_ceiling,
                          **({"limiter": M.Limiter(a.limiter_window_ms, a.limiter_passes)} if a.limiter else {}),
                          **({"denoise": dn} if a.denoise_prompt else {}), **({"dereverb": dr} if a.dereverb_prompt else {}),
-                         **({"declip": dc} if a.declip_prompt else {}))
+                         **({"declip": dc} if a.declip_prompt else {}), **({"cut_pauses": pa} if a.cut_prompt_pauses else {}))
     wrote = gl is not None or tts.hifi_gan is not None
     print(f"{int(lens[0])} mel frames -> {a.out if wrote else '(no vocoder loaded: mel only; --vocoder griffin-lim needs none)'}")
+    if a.report_pauses:
+        import glob
+        import math
+        from megatts2_amd import audio_io
+        paths = sorted(glob.glob(f"{a.wavs_dir}/*.wav"))
+        # with --cut-prompt-pauses the figures of the stage that ran (at 16 kHz, behind the other stages); without it a measurement of
+        # the file as it is, at its own rate, nothing is changed
+        rows = []
+        for i, path in enumerate(paths):
+            if a.cut_prompt_pauses:
+                rows.append((aux["prompt_pauses"][i], C.HIFIGAN_SR))
+            else:
+                y, sr = audio_io.read_wav(path)
+                st = M.speech_segments(y, sr, pauses=pa)
+                rows.append(({k: float(st[k if k != "segments" else "n_segments"][0]) for k in M.PAUSES_NAMES}, sr))
+        for path, (st, sr) in zip(paths, rows):
+            total = 512 * (st["frames"] - 1)            # to a frame
+            speech = st["kept_samples"] if st["segments"] > 0 else 0.0
+            ratio = (f"{10 * math.log10(st['kept_energy'] / st['dropped_energy']):.1f} dB" if st["kept_energy"] > 0 and st["dropped_energy"] > 0
+                     else "n/a (nothing on one side)")
+            if st["segments"] < 0:
+                print(f"pauses of the prompt {path}: no speech segment found at {a.pause_db:g} dB: the file is left whole")
+            else:
+                print(f"pauses of the prompt {path}{' (cut)' if a.cut_prompt_pauses else ''}: {int(st['segments'])} segments, {speech / sr:.2f} s of speech "
+                      f"of about {total / sr:.2f} s, longest pause {512 * st['longest_pause'] / sr:.2f} s, speech / pause energy {ratio}")
     if a.report_clipping:
         import glob
         from megatts2_amd import audio_io

@@ -666,6 +666,81 @@ int mt2_clip_detect(mt2_model* m, void* stream, const mt2_declip_config* dc, con
 int mt2_declip(mt2_model* m, void* stream, const mt2_declip_config* dc, const float* wav, const int32_t* lens /*host*/, int L_max, int B,
                float* out, int Lout_max, double* figures /*or NULL*/, int32_t* iters /*or NULL*/, int T_max);
 
+/* ---- speech segments of prompt audio by frame energy, and the cut that takes the pauses out (csrc/segments.hip).  mt2_trim_silence
+ * cuts the two ENDS; silence inside a prompt - the pause between two sentences, room tone, the gap between joined takes - still
+ * reaches the mel context and the prosody codes as if it were speech.  The reference relies on pre-cut data (prepare_ds.py).  The rule
+ * is our own, held to its restatement (tests/segments_ref.py); parity with librosa.effects.split, webrtcvad or any model-based VAD is
+ * unpinned, and so is quality on real speech.
+ *
+ * THE RULE.  The frames are the trim's, unchanged: s[j], F = 1 + L / 512, e[f] = ((s[f-2] + s[f-1]) + s[f]) + s[f+1], E = max_f e[f],
+ * c = (float)pow(10.0, -top_db / 10.0).  (The staged call takes any contour e[f] >= 0; there E = max(0, max_f e[f]).)
+ *  1 raw    a[f] = e[f] > E * c, one f32 product;  E < FLT_MIN: every frame is active (the trim's convention)
+ *  2 close  an inactive run that lies BETWEEN two active frames and is shorter than min_pause frames becomes active -> b.  Leading and
+ *           trailing inactive runs never do.
+ *  3 open   a run of b shorter than min_speech frames becomes inactive -> c
+ *  4 pad    d[f] = some g in [0, F) with |g - f| <= pad has c[g]
+ *  5        c empty ("nothing found"): d is all true - the utterance stays whole as one segment, and figure 3 says so by its sign
+ * Segment k is the k-th maximal run [f0, f1] of d: frames [f0, f1 + 1), samples [512 f0, min(L, 512 (f1 + 1))).  Because min_pause >
+ * 2 pad the runs of d are the runs of c widened by pad and clamped, one for one, with at least min_pause - 2 pad frames between two of
+ * them: no merge step exists.  An utterance has at most max(1,(F + min_pause) / (min_speech + min_pause)) segments (64-bit), which
+ * mt2_segments_query reports; a caller's S_max below it is refused, so nothing can overflow.  With min_pause >= F, pad = 0 and
+ * min_speech = 2 the one segment is mt2_trim_silence's (start, end) whenever the trim keeps at least two frames.
+ *
+ * THE CUT.  The kept frames - d with keep = 0 (speech), !d with keep = 1 (pauses: a noise-only clip) - are copied in ascending order,
+ * frame f to the offset 512 * (kept frames before f), every copy exact.  No cross-fade: a join lies in frames under the threshold and
+ * on a multiple of 512 samples, so on a mel-frame boundary (hop 256).  The output has 512 * (kept frames) samples, minus what the last
+ * frame lacks of 512 if it is kept (it owns [512 (F - 1), L)); with keep = 1 that may be 0.  Zeros follow up to Lout_max.
+ *
+ * Figures, a row of MT2_SEGMENTS_FIELDS = 8 doubles:  0 F   1 raw active frames   2 kept frames   3 segments, NEGATIVE (-1) when
+ * nothing was found and the utterance stayed whole   4 kept samples (the staged call: 512 * kept frames)   5 the longest pause between
+ * two segments in frames (0 with one segment)   6 mean e over the kept frames   7 mean e over the dropped ones (0 where there are
+ * none).  The sums of 6 and 7 are taken in double in a fixed order.
+ *
+ * A flag, a segment and a figure depend on their utterance alone: a ragged batch is bit-identical to its utterances alone.  Input
+ * must be finite; a non-finite sample cannot fault and gives segments inside [0, L], nothing more.
+ * Refused on the host, before the first HIP call, outputs untouched: top_db not finite or <= 0; min_speech < 2 (so every segment owns
+ * at least 512 samples, even when L % 512 == 0 and the last frame owns none); pad < 0; min_pause <= 2 pad; keep not 0 or 1; B outside
+ * [1, 65535]; a length outside [1, L_max]; max length > INT_MAX - 4 * 512; S_max below the bound; F_max or Lout_max too small; an
+ * output overlapping an input or another output.
+ * Limits: the threshold is relative to the LOUDEST frame - room tone above -top_db of the peak reads as speech and nothing is cut; a
+ * breath is speech or pause by its level alone; a weak consonant at a segment's edge is protected only by pad; mel frames that
+ * straddle a join see both sides.  Out of scope: a maximum segment length, a streaming form, multichannel, model-based VAD. */
+#define MT2_SEGMENTS_FIELDS 8
+#define MT2_SEGMENTS_CHUNK 256      /* frames the smoothing kernel takes at a time (tests put runs and gaps across its multiples) */
+typedef struct mt2_segments_config {
+    float top_db;              /* > 0, finite;  40 */
+    int32_t min_pause;         /* frames, > 2 pad;  10 = 320 ms at 16 kHz */
+    int32_t min_speech;        /* frames, >= 2;  3 = 96 ms */
+    int32_t pad;               /* frames, >= 0;  2 = 64 ms */
+    int32_t keep;              /* 0 speech, 1 pauses */
+} mt2_segments_config;
+/* Host only, no HIP call; outputs may be NULL; lens (samples) NULL: every len_b = L_max.  frames = 1 + max_b len_b / 512, factor = c,
+ * max_segments = the bound at `frames`, workspace_bytes = the arena high water of mt2_speech_segments and of mt2_cut_pauses exactly,
+ * whatever optional outputs they are given.  With r(x) = x rounded up to 256 bytes, W = frames, NB = ceil(max len / 512):
+ *   r(4 * 2 B) + r(4 W B) + r(4 W B) + 3 r(W B) + r(32 B)   [+ r(4 NB B) + r(4 B) + r(4 W B) in front of the energies of the audio calls]
+ * mt2_segment_frames takes the unbracketed part with r(4 B) for the plan and W = max_b frame_lens[b].  It refuses what the calls
+ * refuse for these arguments. */
+int mt2_segments_query(const mt2_segments_config* cfg, const int32_t* lens /*host or NULL*/, int L_max, int B, int* frames, float* factor,
+                       long long* max_segments, long long* workspace_bytes);
+/* The staged form, steps 1-5 on any energy contour (from mt2_frame_energy, for one): energy f32 [B, F_max] (device; entries at or
+ * beyond frame_lens[b] are never read), frame_lens host int32 [B] in [1, F_max], F_max <= INT_MAX / 512 -> flags (device u8 [B, F_max]
+ * or NULL: d; bytes at or beyond frame_lens[b] are left alone), segments (device int32 [B, S_max, 2] or NULL: FRAMES [f0, f1 + 1), -1
+ * behind counts[b]), counts (device int32 [B] or NULL), figures (device f64 [B, 8] or NULL).  The call only enqueues. */
+int mt2_segment_frames(mt2_model* m, void* stream, const mt2_segments_config* cfg, const float* energy /*[B, F_max]*/,
+                       const int32_t* frame_lens /*host*/, int F_max, int B, uint8_t* flags, int32_t* segments, int S_max, int32_t* counts,
+                       double* figures);
+/* wav f32 [B, L_max] (device; samples at or beyond lens[b] are never read) -> segments (device int32 [B, S_max, 2] or NULL: SAMPLES
+ * [start, end), -1 behind counts[b]), counts, figures as above; energy (device f32 [B, F_max] or NULL): e[f], zeros in [F_b, F_max).
+ * The call only enqueues. */
+int mt2_speech_segments(mt2_model* m, void* stream, const mt2_segments_config* cfg, const float* wav, const int32_t* lens /*host*/, int L_max,
+                        int B, int32_t* segments, int S_max, int32_t* counts, double* figures, float* energy, int F_max);
+/* The cut: -> out f32 [B, Lout_max] (device), Lout_max >= max_b lens[b] (the cut is not known before the call).  out_lens (host int32
+ * [B] or NULL): as with the trim's `bounds`, only a caller that asks for it pays for one copy to the host and ONE stream synchronise;
+ * otherwise the call only enqueues, and the copy kernel reads its offsets on the device.  segments (samples of the INPUT, whichever
+ * `keep`), counts, figures: as above, or NULL. */
+int mt2_cut_pauses(mt2_model* m, void* stream, const mt2_segments_config* cfg, const float* wav, const int32_t* lens /*host*/, int L_max, int B,
+                   float* out, int Lout_max, int32_t* out_lens /*host or NULL*/, int32_t* segments, int S_max, int32_t* counts, double* figures);
+
 /* ---- F0 tracking by YIN (de Cheveigne & Kawahara 2002, steps 2-5; csrc/f0.hip) and the pitch moments of a track.  No reference
  * counterpart: the reference tree has no pitch tracker (it would take one from librosa or pyworld).  Parity with librosa.yin / pyin
  * is unpinned - neither is on hand - and quality on real speech is unpinned as well; the rule is our own statement and the tests

@@ -107,6 +107,37 @@ def trim_alignment(phone_tokens, durations, start: int, end: int, hop: int = 256
     return tok[keep], kept[keep].astype(np.int32)
 
 
+def cut_alignment(phone_tokens, durations, segments, hop: int = 256):
+    """The phone alignment of a prompt whose pauses were cut out (runtime.MelFrontEnd.cut_pauses / from_audio(cut_pauses=...,
+    return_segments=True)): the multi-segment form of `trim_alignment` -> (phone_tokens', durations').  segments: [(start, end)] in
+    samples of the uncut audio, ascending and apart.  Segment k contributes the (end - start) // hop original mel frames from
+    start // hop on, and the last segment one more, so that the result sums to the cut prompt's 1 + L' // hop frames (every segment but
+    the last is a multiple of 512 samples long); each phone keeps the frames of its span that lie in those ranges, a phone left with
+    none is dropped.  With one segment this is exactly `trim_alignment`.  ValueError when a start is no multiple of hop, when the
+    segments are not ascending and apart, or when they reach beyond sum(durations)."""
+    tok, dur = np.asarray(phone_tokens).reshape(-1), np.asarray(durations).reshape(-1).astype(np.int64)
+    if tok.shape != dur.shape:
+        raise ValueError("phone_tokens and durations differ in length")
+    seg = np.asarray(segments, np.int64).reshape(-1, 2)
+    if seg.shape[0] == 0:
+        raise ValueError("no segment")
+    last = np.cumsum(dur)
+    kept = np.zeros_like(dur)
+    behind = 0
+    for k, (start, end) in enumerate(seg):
+        if start % hop != 0:
+            raise ValueError(f"start = {start} is not a multiple of the mel hop {hop}")
+        if not behind <= start <= end:
+            raise ValueError(f"bad segment [{start}, {end}) behind sample {behind}")
+        s, frames = start // hop, (end - start) // hop + (1 if k == seg.shape[0] - 1 else 0)
+        if s + frames > int(dur.sum()):
+            raise ValueError(f"the cut frames [{s}, {s + frames}) reach beyond the alignment's {int(dur.sum())} frames")
+        kept += np.clip(np.minimum(last, s + frames) - np.maximum(last - dur, s), 0, None)
+        behind = end
+    keep = kept > 0
+    return tok[keep], kept[keep].astype(np.int32)
+
+
 def write_wav(path: str, samples, sample_rate: int = 16000, encoding: str = "PCM_F") -> None:
     """samples: [L] or [channels, L] float array in [-1, 1].  encoding "PCM_F" (32-bit float, what
     torchaudio.save writes for float32 input) or "PCM_S16" (clipped, round-to-nearest)."""

@@ -1302,6 +1302,49 @@ int mt2_declip(mt2_model* m, void* stream, const mt2_declip_config* dc, const fl
     MT2_API_END
 }
 
+// speech segments by frame energy (segments.hip): the frames of the longest utterance, the f32 factor, the most segments one can have and
+// the arena bytes of one mt2_speech_segments / mt2_cut_pauses call, without a HIP call
+int mt2_segments_query(const mt2_segments_config* cfg, const int32_t* lens, int L_max, int B, int* frames, float* factor, long long* max_segments,
+                       long long* workspace_bytes) {
+    MT2_API_BEGIN
+    SgCall k{};
+    k.a = segments_check_config(cfg);
+    segments_lens(k, lens, L_max, B);
+    if (frames) *frames = k.max_F;
+    if (factor) *factor = k.a.factor;
+    if (max_segments) *max_segments = segments_bound(k.max_F, k.a.min_pause, k.a.min_speech);
+    if (workspace_bytes) *workspace_bytes = segments_arena_bytes((size_t)B, segments_blocks(k.max_len), (size_t)k.max_F, true);
+    MT2_API_END
+}
+
+// every refusal of the three calls is decided on the host before the first HIP call
+int mt2_segment_frames(mt2_model* m, void* stream, const mt2_segments_config* cfg, const float* energy, const int32_t* frame_lens, int F_max, int B,
+                       uint8_t* flags, int32_t* segments, int S_max, int32_t* counts, double* figures) {
+    MT2_API_BEGIN
+    const SgCall k = segment_frames_check(cfg, energy, frame_lens, F_max, B, flags, segments, S_max, counts, figures);
+    MT2_AUDIO_CALL(m, stream);
+    segment_frames_run(c, k, energy, F_max, B, flags, segments, S_max, counts, figures);
+    MT2_API_END
+}
+
+int mt2_speech_segments(mt2_model* m, void* stream, const mt2_segments_config* cfg, const float* wav, const int32_t* lens, int L_max, int B,
+                        int32_t* segments, int S_max, int32_t* counts, double* figures, float* energy, int F_max) {
+    MT2_API_BEGIN
+    const SgCall k = segments_check(cfg, wav, lens, L_max, B, nullptr, 0, false, segments, S_max, counts, figures, energy, F_max);
+    MT2_AUDIO_CALL(m, stream);
+    segments_run(c, k, wav, L_max, B, nullptr, 0, nullptr, segments, S_max, counts, figures, energy, F_max);
+    MT2_API_END
+}
+
+int mt2_cut_pauses(mt2_model* m, void* stream, const mt2_segments_config* cfg, const float* wav, const int32_t* lens, int L_max, int B, float* out,
+                   int Lout_max, int32_t* out_lens, int32_t* segments, int S_max, int32_t* counts, double* figures) {
+    MT2_API_BEGIN
+    const SgCall k = segments_check(cfg, wav, lens, L_max, B, out, Lout_max, true, segments, S_max, counts, figures, nullptr, 0);
+    MT2_AUDIO_CALL(m, stream);
+    segments_run(c, k, wav, L_max, B, out, Lout_max, out_lens, segments, S_max, counts, figures, nullptr, 0);
+    MT2_API_END
+}
+
 // :361-368 [+370]  zq = vq.decode(p_codes) repeated x8, cat([tc_latent_expand, zq]), decoder, optional vocoder - the part of
 // Megatts.forward behind the PLM, shared by mt2_synthesize_batch and mt2_synthesize_prompt_conditioned.  xdec: [D.R, H + Dq]
 // rows whose first H columns already hold the length-regulated tc_latents.

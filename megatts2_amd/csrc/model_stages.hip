@@ -3276,6 +3276,163 @@ static void declip_run(const Ctx& c, const DcCall& k, const float* wav, int L_ma
     st.finish();
 }
 
+// ---- speech segments by frame energy and the cut of the pauses (segments.hip): every refusal is decided here, on the host, before the
+// first HIP call
+struct SgArgs { float factor; int min_pause, min_speech, pad, keep; };
+static SgArgs segments_check_config(const mt2_segments_config* cfg) {
+    MT2_REQUIRE(cfg != nullptr, "null segments configuration");
+    MT2_REQUIRE(std::isfinite(cfg->top_db) && cfg->top_db > 0.0f, "top_db must be finite and > 0");
+    MT2_REQUIRE(cfg->min_speech >= 2, "min_speech < 2 frames");
+    MT2_REQUIRE(cfg->pad >= 0, "pad < 0");
+    MT2_REQUIRE((long long)cfg->min_pause > 2ll * cfg->pad, "min_pause <= 2 pad (padded segments could touch; no merge step exists)");
+    MT2_REQUIRE(cfg->keep == 0 || cfg->keep == 1, "keep neither 0 (speech) nor 1 (pauses)");
+    return {trim_factor(cfg->top_db), cfg->min_pause, cfg->min_speech, cfg->pad, cfg->keep};
+}
+// the checked geometry of a call: lengths in samples (empty for the staged form), frames, the longest of each
+struct SgCall { SgArgs a; std::vector<int> len, flen; int max_len, max_F; };
+// the ragged lengths in samples (lens NULL: every utterance L_max samples) -> their frames
+static void segments_lens(SgCall& k, const int* lens, int L_max, int B) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(L_max >= 1, "L_max < 1");
+    k.len.assign(B, L_max);
+    if (lens) k.len.assign(lens, lens + B);
+    k.max_len = check_lens(k.len.data(), B, L_max, "waveform length outside [1, L_max]");
+    MT2_REQUIRE(k.max_len <= INT_MAX - 4 * MT2_TRIM_HOP, "waveform longer than INT_MAX - 4 * 512 samples");
+    k.flen.resize(B);
+    for (int b = 0; b < B; ++b) k.flen[b] = trim_frames(k.len[b]);
+    k.max_F = trim_frames(k.max_len);
+}
+// the arena of a call, in carve order: the plan, for the audio calls the block sums, the peak words and the energies, then the
+// scratch of the smoothing kernel.  Optional outputs change nothing here, so the query holds for every form of a call
+struct SgWs { float* sums; unsigned* peak; float* energy; int* prv; int* dst; unsigned char* fb; unsigned char* fc; unsigned char* fd; int* words; };
+template <class Ws> static SgWs segments_carve(Ws& ws, IntPlan& ip, size_t B, size_t NB, size_t W, bool audio) {
+    SgWs w{};
+    ip.carve(ws);
+    if (audio) {
+        w.sums = ws.template get<float>(B * NB);
+        w.peak = ws.template get<unsigned>(B);
+        w.energy = ws.template get<float>(B * W);
+    }
+    w.prv = ws.template get<int>(B * W);
+    w.dst = ws.template get<int>(B * W);
+    w.fb = ws.template get<unsigned char>(B * W);
+    w.fc = ws.template get<unsigned char>(B * W);
+    w.fd = ws.template get<unsigned char>(B * W);
+    w.words = ws.template get<int>(B * kSegWords);
+    return w;
+}
+static long long segments_arena_bytes(size_t B, size_t NB, size_t W, bool audio) {
+    IntPlan ip;      // the entries of the call's plan, by size: frames and - for the audio calls - lengths
+    for (int i = 0; i < (audio ? 2 : 1); ++i) ip.add_fill(B, 0);
+    ArenaCount count;
+    segments_carve(count, ip, B, NB, W, audio);
+    return (long long)count.bytes;
+}
+static size_t segments_blocks(int max_len) { return ((size_t)max_len + MT2_TRIM_HOP - 1) / MT2_TRIM_HOP; }
+// what the three calls share of their checks, behind the configuration and the lengths
+static void segments_check_outputs(const SgCall& k, int B, const void* in, size_t n_in, const uint8_t* flags, int F_max, const int32_t* segments,
+                                   int S_max, const int32_t* counts, const double* figures, const float* energy, const float* out, size_t n_out) {
+    MT2_REQUIRE((((uintptr_t)in | (uintptr_t)segments | (uintptr_t)counts | (uintptr_t)energy | (uintptr_t)out) & 3) == 0 && ((uintptr_t)figures & 7) == 0,
+                "misaligned buffers");
+    MT2_REQUIRE(segments == nullptr || (long long)S_max >= segments_bound(k.max_F, k.a.min_pause, k.a.min_speech),
+                "S_max smaller than max(1, (F + min_pause) / (min_speech + min_pause)) (mt2_segments_query)");
+    MT2_REQUIRE((flags == nullptr && energy == nullptr) || F_max >= k.max_F, "F_max smaller than the frames of the longest utterance");
+    const size_t nf = flags ? (size_t)B * F_max : 0, ne = energy ? sizeof(float) * (size_t)B * F_max : 0;
+    const size_t ns = segments ? sizeof(int32_t) * 2 * (size_t)B * S_max : 0, nc = sizeof(int32_t) * (size_t)B;
+    const size_t ng = sizeof(double) * MT2_SEGMENTS_FIELDS * (size_t)B;
+    MT2_REQUIRE(!outputs_overlap({{flags, nf}, {segments, ns}, {counts, nc}, {figures, ng}, {energy, ne}, {out, n_out}}, {{in, n_in}}), "overlapping buffers");
+}
+// the smoothing launch of all three calls
+static SegP segments_params(const SgCall& k, const SgWs& w, const IntPlan& ip, int o_flen, const float* energy, int E_pitch, int B, int W,
+                            int32_t* segments, int S_max, int32_t* counts, double* figures) {
+    SegP p{};
+    p.energy = energy; p.E_pitch = E_pitch; p.flen = ip.dev(o_flen); p.max_F = k.max_F; p.B = B;
+    p.factor = k.a.factor; p.min_pause = k.a.min_pause; p.min_speech = k.a.min_speech; p.pad = k.a.pad; p.keep = k.a.keep;
+    p.prv = w.prv; p.dst = w.dst; p.fb = w.fb; p.fc = w.fc; p.fd = w.fd; p.W = W; p.words = w.words;
+    p.seg = segments; p.S_max = S_max; p.counts = counts; p.fig = figures;
+    return p;
+}
+
+static SgCall segment_frames_check(const mt2_segments_config* cfg, const float* energy, const int* frame_lens, int F_max, int B, const uint8_t* flags,
+                                   const int32_t* segments, int S_max, const int32_t* counts, const double* figures) {
+    SgCall k{};
+    k.a = segments_check_config(cfg);
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(energy != nullptr && frame_lens != nullptr, "bad buffers");
+    MT2_REQUIRE(F_max >= 1 && F_max <= INT_MAX / MT2_TRIM_HOP, "F_max outside [1, INT_MAX / 512]");
+    k.flen.assign(frame_lens, frame_lens + B);
+    k.max_F = check_lens(frame_lens, B, F_max, "frame count outside [1, F_max]");
+    segments_check_outputs(k, B, energy, sizeof(float) * (size_t)B * F_max, flags, F_max, segments, S_max, counts, figures, nullptr, nullptr, 0);
+    return k;
+}
+// enqueues only
+static void segment_frames_run(const Ctx& c, const SgCall& k, const float* energy, int F_max, int B, uint8_t* flags, int32_t* segments, int S_max,
+                               int32_t* counts, double* figures) {
+    IntPlan ip;
+    const int o_flen = ip.add(k.flen);
+    const SgWs w = segments_carve(c.ws, ip, B, 0, k.max_F, false);
+    ip.send(c.m.pinned(), c.s);
+    SegP p = segments_params(k, w, ip, o_flen, energy, F_max, B, k.max_F, segments, S_max, counts, figures);
+    p.flags = flags; p.D_pitch = F_max;
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(launch_segments(p, kSegSmooth, c.s));
+    st.mark("seg_smooth");
+    if (figures) MT2_HIP(launch_segments(p, kSegFigures, c.s));
+    st.mark("seg_figures");
+    st.finish();
+}
+
+// out NULL: mt2_speech_segments
+static SgCall segments_check(const mt2_segments_config* cfg, const float* wav, const int* lens, int L_max, int B, const float* out, int Lout_max,
+                             bool cut, const int32_t* segments, int S_max, const int32_t* counts, const double* figures, const float* energy,
+                             int F_max) {
+    SgCall k{};
+    k.a = segments_check_config(cfg);
+    MT2_REQUIRE(wav != nullptr && lens != nullptr, "bad buffers");
+    segments_lens(k, lens, L_max, B);
+    if (cut) {
+        MT2_REQUIRE(out != nullptr, "null out");
+        MT2_REQUIRE(Lout_max >= k.max_len, "Lout_max smaller than the longest utterance (the cut is not known before the call)");
+    }
+    segments_check_outputs(k, B, wav, sizeof(float) * (size_t)B * L_max, nullptr, F_max, segments, S_max, counts, figures, energy, out,
+                           cut ? sizeof(float) * (size_t)B * Lout_max : 0);
+    return k;
+}
+// enqueues only, unless out_lens asks for the one copy to the host and the one synchronise
+static void segments_run(const Ctx& c, const SgCall& k, const float* wav, int L_max, int B, float* out, int Lout_max, int32_t* out_lens,
+                         int32_t* segments, int S_max, int32_t* counts, double* figures, float* energy, int F_max) {
+    IntPlan ip;
+    const int o_flen = ip.add(k.flen), o_len = ip.add(k.len);
+    const int NB = (int)segments_blocks(k.max_len), W = k.max_F;
+    const SgWs w = segments_carve(c.ws, ip, B, NB, W, true);
+    ip.send(c.m.pinned(), c.s);
+    TrimP t{};
+    t.wav = wav; t.L_max = L_max; t.len = ip.dev(o_len); t.max_len = k.max_len; t.B = B; t.factor = k.a.factor;
+    t.sums = w.sums; t.NB = NB; t.peak = w.peak;
+    t.energy = energy ? energy : w.energy; t.F_max = energy ? F_max : W;
+    SegP p = segments_params(k, w, ip, o_flen, t.energy, t.F_max, B, W, segments, S_max, counts, figures);
+    p.len = t.len; p.wav = wav; p.L_max = L_max; p.out = out; p.Lout_max = Lout_max;
+    Stages st(c.m, c.s);
+    st.mark("start");
+    MT2_HIP(hipMemsetAsync(t.peak, 0, sizeof(unsigned) * B, c.s));
+    MT2_HIP(launch_trim_energy(t, c.s));
+    st.mark("seg_energy");
+    MT2_HIP(launch_segments(p, kSegSmooth, c.s));
+    st.mark("seg_smooth");
+    if (figures) MT2_HIP(launch_segments(p, kSegFigures, c.s));
+    st.mark("seg_figures");
+    if (out) MT2_HIP(launch_segments(p, kSegCopy, c.s));
+    st.mark("seg_copy");
+    st.finish();
+    if (out_lens) {
+        int* host = static_cast<int*>(c.m.pinned().alloc(sizeof(int) * kSegWords * B));      // handle-owned staging
+        MT2_HIP(hipMemcpyAsync(host, w.words, sizeof(int) * kSegWords * B, hipMemcpyDeviceToHost, c.s));
+        MT2_HIP(hipStreamSynchronize(c.s));
+        for (int b = 0; b < B; ++b) out_lens[b] = host[kSegWords * b + 5];
+    }
+}
+
 }  // namespace mt2
 
 // the C ABI lives in capi.hip and includes this translation unit's helpers

@@ -468,6 +468,30 @@ struct TrimP {
     float* energy; int F_max;                 // optional [B, F_max], F_max >= 1 + max_len / 512: e[f], zeros in [F_b, F_max)
 };
 hipError_t launch_trim(const TrimP& p, hipStream_t s);
+// the first two launches alone: sums, peak and - where asked for - energy; out, first and last are not looked at
+hipError_t launch_trim_energy(const TrimP& p, hipStream_t s);
+
+// ---- speech segments by frame energy and the cut that takes the pauses out (segments.hip; the rule is in its header) ------------
+// host only: the most segments an utterance of F frames can have, max(1, (F + min_pause) / (min_speech + min_pause)) in 64 bits
+long long segments_bound(long long F, int min_pause, int min_speech);
+constexpr int kSegWords = 8;      // per utterance: F, raw active, kept frames, +-segments, longest pause, kept samples, 0, 0
+// Up to three launches on one stream, picked by `what`: smoothing and enumeration (one workgroup per utterance) -> figures -> copy.
+enum { kSegSmooth = 1, kSegFigures = 2, kSegCopy = 4 };
+struct SegP {
+    const float* energy; int E_pitch;         // [B, E_pitch]: e[f] of each utterance, read for f < flen[b] only
+    const int* flen; int max_F, B;            // device [B]: frames; max_b flen[b]
+    const int* len;                           // device [B]: samples (segments in samples, cutting) or NULL (the staged form: frames)
+    float factor; int min_pause, min_speech, pad, keep;
+    int* prv; int* dst; unsigned char* fb; unsigned char* fc; unsigned char* fd; int W;      // scratch [B, W] each, W >= max_F
+    int* words;                               // scratch [B, kSegWords]
+    unsigned char* flags; int D_pitch;        // optional [B, D_pitch]: d, in place of fd (bytes at or beyond flen[b] are left alone)
+    int* seg; int S_max;                      // optional [B, S_max, 2], -1 behind the segments found; S_max >= segments_bound(max_F)
+    int* counts;                              // optional [B]
+    double* fig;                              // optional [B, MT2_SEGMENTS_FIELDS]
+    const float* wav; int L_max;              // cutting: [B, L_max]; samples at or beyond len[b] are never read
+    float* out; int Lout_max;                 // optional [B, Lout_max], Lout_max >= max_b len[b]
+};
+hipError_t launch_segments(const SegP& p, int what, hipStream_t s);
 
 // ---- dynamic time warping of a synthesised mel onto a real one (dtw.hip; the rule is in its header and in megatts2_hip.h) --------
 // host only, no HIP call: u32 words of packed directions per row

@@ -133,14 +133,27 @@ __global__ __launch_bounds__(kThreads) void trim_copy_kernel(TrimP p) {
     }
 }
 
-hipError_t launch_trim(const TrimP& p, hipStream_t s) {
-    if (p.B <= 0) return hipSuccess;
-    if (p.B > 65535 || p.max_len < 1 || p.max_len > p.L_max || p.Lout_max < p.max_len || p.NB < (p.max_len + kHop - 1) / kHop ||
-        (p.energy && p.F_max < 1 + p.max_len / kHop) || p.max_len > INT_MAX - 4 * kHop)
-        return hipErrorInvalidValue;
+static bool energy_args_ok(const TrimP& p) {
+    return p.B <= 65535 && p.max_len >= 1 && p.max_len <= p.L_max && p.NB >= (p.max_len + kHop - 1) / kHop &&
+           (!p.energy || p.F_max >= 1 + p.max_len / kHop) && p.max_len <= INT_MAX - 4 * kHop;
+}
+static void launch_energy_half(const TrimP& p, hipStream_t s) {
     const int frames = std::max(1 + p.max_len / kHop, p.energy ? p.F_max : 0);
     hipLaunchKernelGGL(trim_block_sums_kernel, dim3((p.NB + kTileBlocks - 1) / kTileBlocks, p.B), dim3(kThreads), 0, s, p);
     hipLaunchKernelGGL(trim_frame_energy_kernel, dim3((frames + kThreads - 1) / kThreads, p.B), dim3(kThreads), 0, s, p);
+}
+
+hipError_t launch_trim_energy(const TrimP& p, hipStream_t s) {
+    if (p.B <= 0) return hipSuccess;
+    if (!energy_args_ok(p)) return hipErrorInvalidValue;
+    launch_energy_half(p, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_trim(const TrimP& p, hipStream_t s) {
+    if (p.B <= 0) return hipSuccess;
+    if (!energy_args_ok(p) || p.Lout_max < p.max_len) return hipErrorInvalidValue;
+    launch_energy_half(p, s);
     hipLaunchKernelGGL(trim_keep_bounds_kernel, dim3((1 + p.max_len / kHop + kThreads - 1) / kThreads, p.B), dim3(kThreads), 0, s, p);
     const int gx = (int)std::min<long long>(((long long)p.Lout_max + kThreads * 16 - 1) / (kThreads * 16), 1024);
     hipLaunchKernelGGL(trim_copy_kernel, dim3(gx, p.B), dim3(kThreads), 0, s, p);

@@ -21,7 +21,7 @@ import numpy as np
 from . import config as cfgmod
 from . import weights
 from .config import HIFIGAN_HOP_LENGTH, HIFIGAN_SR
-from .runtime import DECLIP_NAMES, DENOISE_NAMES, WPE_NAMES, Declip, Denoise, Dereverb, Limiter, NativeError, NativeModel  # noqa: F401  (Limiter, Denoise, Dereverb, Declip: arguments of synthesize / forward)
+from .runtime import DECLIP_NAMES, DENOISE_NAMES, PAUSES_NAMES, WPE_NAMES, Declip, Denoise, Dereverb, Limiter, NativeError, NativeModel, Pauses  # noqa: F401  (Limiter, Denoise, Dereverb, Declip, Pauses: arguments of synthesize / forward)
 from .sampling import PLMSampling, seed_array
 
 
@@ -41,7 +41,7 @@ def _frontend():
 
 
 def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, denoise: Optional[Denoise] = None,
-                     dereverb: Optional[Dereverb] = None, declip: Optional[Declip] = None):
+                     dereverb: Optional[Dereverb] = None, declip: Optional[Declip] = None, cut_pauses: Optional[Pauses] = None):
     """reference modules/tokenizer.py:107-125: 1-D waveform tensor (16 kHz) -> mel [80, T] (the reference
     returns channels first and `Megatts.forward` transposes it, models/megatts2.py:339).  Runs on the GPU
     (runtime.MelFrontEnd); a [B, L] input gives [B, 80, T].  sample_rate: the rate of `samples` when it is not
@@ -53,8 +53,12 @@ def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Option
     = off, exactly the call without it): a `Dereverb`; late reverberation is removed by weighted prediction error behind the resampling
     and in front of the denoiser (MelFrontEnd.dereverb, csrc/wpe.hip; likewise).  declip (None = off, exactly the call without it): a
     `Declip`; clipped samples are restored first of all, at the samples' own rate and in front of the resampling, which would turn
-    the flat tops into ripple (MelFrontEnd.declip, csrc/declip.hip; the level is left as it comes out and can exceed the input's)."""
+    the flat tops into ripple (MelFrontEnd.declip, csrc/declip.hip; the level is left as it comes out and can exceed the input's).
+    cut_pauses (None = off, exactly the call without it): a `Pauses`; where the trim would run, the pauses inside the audio are cut out
+    as well as its ends (MelFrontEnd.cut_pauses, csrc/segments.hip), so it excludes trim_db (ValueError)."""
     import torch
+    if cut_pauses is not None and trim_db is not None:
+        raise ValueError("cut_pauses cuts the ends itself: it excludes trim_db")
     fe = _frontend()
     x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
     batched = x.dim() == 2
@@ -70,6 +74,8 @@ def extract_mel_spec(samples, sample_rate: Optional[int] = None, trim_db: Option
         x, lens = fe.denoise(x, lens, denoise)
     if trim_db is not None:
         x, lens, _ = fe.trim(x, lens, top_db=trim_db)
+    if cut_pauses is not None:
+        x, lens = fe.cut_pauses(x, lens, cut_pauses)
     mel = fe(x, lens).transpose(1, 2)
     return mel if batched else mel[0]
 
@@ -259,6 +265,64 @@ def declip_audio(samples, lens=None, declip: Optional[Declip] = None):
     res["iters"] = iters.cpu().numpy()
     out = out.cpu().numpy()
     return (out[0] if flat else out), res
+
+
+def _pause_input(samples, sample_rate):
+    import torch
+    x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
+    flat = x.dim() == 1
+    x = (x.unsqueeze(0) if flat else x).to("cuda", torch.float32)
+    return x, flat, _frontend().audio.sample_rate if sample_rate is None else int(sample_rate)
+
+
+def _segment_lists(seg, cnt):
+    """ONE copy to the host: the segment table and the counts side by side -> per utterance [(start, end)]"""
+    import torch
+    B = seg.shape[0]
+    t = torch.cat([seg.reshape(B, -1), cnt.reshape(B, 1)], dim=1).cpu().numpy()
+    return [[(int(t[b, 2 * k]), int(t[b, 2 * k + 1])) for k in range(int(t[b, -1]))] for b in range(B)]
+
+
+def speech_segments(samples, sample_rate: Optional[int] = None, lens=None, pauses: Optional[Pauses] = None):
+    """The speech segments of a 1-D waveform or a [B, L] batch, found on the GPU by frame energy - the rule of csrc/segments.hip
+    (MelFrontEnd.speech_segments; our own rule: parity with librosa.effects.split, webrtcvad or a model-based VAD and quality on real
+    speech are unpinned).  The samples are taken at their OWN rate (sample_rate, default 16 kHz): nothing is resampled, and the
+    durations of `pauses` (a `Pauses`; None: its defaults) become frames of 512 samples at that rate.  -> dict: segments, per utterance
+    a list of (start, end) in samples, and float64 [B] for each of PAUSES_NAMES (segments negative: nothing was found and the utterance
+    stayed whole)."""
+    x, _, sr = _pause_input(samples, sample_rate)
+    out = _frontend().speech_segments(x, lens, pauses, sample_rate=sr)
+    fig = out["figures"].cpu().numpy()
+    res = {k: fig[:, i].copy() for i, k in enumerate(PAUSES_NAMES)}
+    res["n_segments"] = res.pop("segments")
+    res["segments"] = _segment_lists(out["segments"], out["counts"])
+    return res
+
+
+def cut_pauses(samples, sample_rate: Optional[int] = None, lens=None, pauses: Optional[Pauses] = None, keep: str = "speech"):
+    """A 1-D waveform or a [B, L] batch with its pauses cut out on the GPU (MelFrontEnd.cut_pauses, csrc/segments.hip), at the samples'
+    own rate; keep="pauses" returns what is between the speech segments instead - a noise-only clip, e.g. for denoise_audio(noise=).
+    Every kept sample is an exact copy; there is no cross-fade, and every join is a multiple of 512 samples.  -> (out float32 numpy
+    [B, max out_lens] ([out_len] for a 1-D waveform), out_lens int32 [B], dict as `speech_segments`)."""
+    x, flat, sr = _pause_input(samples, sample_rate)
+    out, out_lens, seg, cnt, fig = _frontend().cut_pauses(x, lens, pauses, sample_rate=sr, keep=keep, return_segments=True, return_figures=True)
+    fig = fig.cpu().numpy()
+    res = {k: fig[:, i].copy() for i, k in enumerate(PAUSES_NAMES)}
+    res["n_segments"] = res.pop("segments")
+    res["segments"] = _segment_lists(seg, cnt)
+    out = out[:, :max(int(out_lens.max()), 0)].cpu().numpy()
+    return (out[0] if flat else out), out_lens, res
+
+
+def split_on_pauses(samples, sample_rate: Optional[int] = None, lens=None, pauses: Optional[Pauses] = None):
+    """A 1-D waveform or a [B, L] batch split at its pauses: per utterance a list of float32 numpy arrays, one per speech segment (the
+    segments of `speech_segments`; one copy of the segment table to the host, the slices are taken from the host samples)."""
+    x, flat, sr = _pause_input(samples, sample_rate)
+    out = _frontend().speech_segments(x, lens, pauses, sample_rate=sr)
+    segs = _segment_lists(out["segments"], out["counts"])
+    host = (samples.detach().cpu().numpy() if hasattr(samples, "detach") else np.asarray(samples, np.float32)).reshape(x.shape)
+    parts = [[host[b, s:e].copy() for s, e in segs[b]] for b in range(x.shape[0])]
+    return parts[0] if flat else parts
 
 
 LIMITER_STATS = ("half_window", "min_gain", "samples_limited", "true_peak_before_trim", "trim", "output_lufs")
@@ -1052,11 +1116,17 @@ class Megatts:
     # declip (None = off; a runtime.Declip): likewise through from_audio(declip=...), where it comes first of all, at the file's own
     # sample rate (csrc/declip.hip): declip, resample, peak-normalise, ...  aux["prompt_clipping"] then holds one dict per prompt file
     # with the figures of the stage (DECLIP_NAMES).
+    # cut_pauses (None = off; a runtime.Pauses): likewise through from_audio(cut_pauses=...), where it comes last, in the trim's place
+    # (csrc/segments.hip): the pauses inside every prompt file are cut out as well as its ends, so it excludes trim_db.
+    # aux["prompt_pauses"] then holds one dict per prompt file with the figures of the stage (PAUSES_NAMES).
     def forward(self, wavs_dir: str, text: Optional[str] = None, phone_tokens=None, out_path: Optional[str] = "test.wav",
                 phones: Optional[Sequence[str]] = None, resample: bool = True, trim_db: Optional[float] = None, vocoder=None,
                 loudness_lufs: Optional[float] = None, peak_ceiling: float = 0.0, true_peak_ceiling_dbtp: Optional[float] = None,
-                limiter=None, denoise: Optional[Denoise] = None, dereverb: Optional[Dereverb] = None, declip: Optional[Declip] = None):
+                limiter=None, denoise: Optional[Denoise] = None, dereverb: Optional[Dereverb] = None, declip: Optional[Declip] = None,
+                cut_pauses: Optional[Pauses] = None):
         import torch
+        if cut_pauses is not None and trim_db is not None:
+            raise ValueError("cut_pauses cuts the ends itself: it excludes trim_db")
         if true_peak_ceiling_dbtp is not None and loudness_lufs is None:
             raise ValueError("true_peak_ceiling_dbtp caps the gain of the loudness normalisation: it needs loudness_lufs")
         if limiter is not None and true_peak_ceiling_dbtp is None:
@@ -1081,22 +1151,23 @@ class Megatts:
         if not wavs:
             raise NativeError(f"no *.wav under {wavs_dir}")
 
-        prompt_noise, prompt_reverb, prompt_clipping = [], [], []
+        prompt_noise, prompt_reverb, prompt_clipping, prompt_pauses = [], [], [], []
 
         def prompt_mel(w):
             y, sr = audio_io.read_wav(w)
-            if denoise is not None or dereverb is not None or declip is not None:
+            if denoise is not None or dereverb is not None or declip is not None or cut_pauses is not None:
                 if sr != HIFIGAN_SR and not resample:
                     raise ValueError(f"{w}: {sr} Hz, expected {HIFIGAN_SR} Hz (resample=False)")
                 more = {} if declip is None else {"declip": declip, "return_clipping": True}      # absent: exactly the call of before
+                if cut_pauses is not None:
+                    more.update(cut_pauses=cut_pauses, return_pauses=True)
                 res = _frontend().from_audio(torch.from_numpy(y).unsqueeze(0).cuda(), sr, trim_db=trim_db, denoise=denoise,
                                              return_noise=denoise is not None, dereverb=dereverb, return_reverb=dereverb is not None, **more)
-                if denoise is not None:
-                    prompt_noise.append(dict(zip(DENOISE_NAMES, res[2][0].cpu().numpy().tolist())))
-                if dereverb is not None:
-                    prompt_reverb.append(dict(zip(WPE_NAMES, res[-2 if declip is not None else -1][0].cpu().numpy().tolist())))
-                if declip is not None:
-                    prompt_clipping.append(dict(zip(DECLIP_NAMES, res[-1][0].cpu().numpy().tolist())))
+                figures = list(res[2:])      # in from_audio's order: noise, reverb, clipping, pauses - those that were asked for
+                for on, names, sink in ((denoise, DENOISE_NAMES, prompt_noise), (dereverb, WPE_NAMES, prompt_reverb),
+                                        (declip, DECLIP_NAMES, prompt_clipping), (cut_pauses, PAUSES_NAMES, prompt_pauses)):
+                    if on is not None:
+                        sink.append(dict(zip(names, figures.pop(0)[0].cpu().numpy().tolist())))
                 return res[0][0]
             if sr == HIFIGAN_SR and trim_db is None:          # audio_io.load_audio's two steps
                 return extract_mel_spec(torch.from_numpy(audio_io.normalize(y))).transpose(0, 1)
@@ -1130,6 +1201,8 @@ class Megatts:
                 aux["prompt_reverb"] = prompt_reverb
             if declip is not None:
                 aux["prompt_clipping"] = prompt_clipping
+            if cut_pauses is not None:
+                aux["prompt_pauses"] = prompt_pauses
             if out_path:
                 prompt = levelled(self.vocode_griffin_lim(mels_prompt.unsqueeze(0).contiguous(), **gl)[0])
                 audio = torch.cat([prompt, aux["wav"][0, :(int(mel_lens[0]) - 1) * HIFIGAN_HOP_LENGTH]])
@@ -1143,6 +1216,8 @@ class Megatts:
             aux["prompt_reverb"] = prompt_reverb
         if declip is not None:
             aux["prompt_clipping"] = prompt_clipping
+        if cut_pauses is not None:
+            aux["prompt_pauses"] = prompt_pauses
         if self.hifi_gan is not None and out_path:
             # :370-375  prompt audio (vocoded first prompt mel) followed by the generated audio; decode_batch output
             # includes the generator's inference padding on both sides, exactly as the reference concatenates it

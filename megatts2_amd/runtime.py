@@ -144,6 +144,65 @@ class MT2DeclipConfig(C.Structure):
 DECLIP_NAMES = ("clipped", "hi", "lo", "share", "frames_iterated", "mean_iterations", "max_iterations", "power_change_db")
 
 
+class MT2SegmentsConfig(C.Structure):
+    _fields_ = [("top_db", C.c_float), ("min_pause", C.c_int32), ("min_speech", C.c_int32), ("pad", C.c_int32), ("keep", C.c_int32)]
+
+
+SEGMENTS_HOP = 512
+SEGMENTS_KEEP = {"speech": 0, "pauses": 1}
+PAUSES_NAMES = ("frames", "raw_active", "kept_frames", "segments", "kept_samples", "longest_pause", "kept_energy", "dropped_energy")
+
+
+def segments_config(top_db: float = 40.0, min_pause: int = 10, min_speech: int = 3, pad: int = 2, keep: str = "speech") -> MT2SegmentsConfig:
+    """The rule of csrc/segments.hip in FRAMES of 512 samples, checked as the library checks it (ValueError)."""
+    if keep not in SEGMENTS_KEEP:
+        raise ValueError('keep must be "speech" or "pauses"')
+    top_db, min_pause, min_speech, pad = float(top_db), int(min_pause), int(min_speech), int(pad)
+    if not (math.isfinite(top_db) and top_db > 0.0):
+        raise ValueError("top_db must be finite and > 0")
+    if min_speech < 2:
+        raise ValueError("min_speech < 2 frames")
+    if pad < 0:
+        raise ValueError("pad < 0")
+    if min_pause <= 2 * pad:
+        raise ValueError("min_pause <= 2 pad (padded segments could touch; no merge step exists)")
+    if max(min_pause, min_speech, pad) > 2 ** 31 - 1:
+        raise ValueError("a frame count beyond int32")
+    return MT2SegmentsConfig(top_db, min_pause, min_speech, pad, SEGMENTS_KEEP[keep])
+
+
+@dataclasses.dataclass(frozen=True)
+class Pauses:
+    """The settings of the speech segments by frame energy (csrc/segments.hip; the rule is in include/megatts2_hip.h): a frame of 2048
+    samples every 512 is active while its energy is above the loudest frame's * 10^(-`top_db` / 10); pauses between active frames
+    shorter than `min_pause_ms` are closed, runs shorter than `min_speech_ms` are dropped, and what is left is widened by `pad_ms` on
+    both sides.  Each duration becomes frames by round(ms * rate / 512000) at the rate of the audio it is applied to.  The threshold is
+    relative to the LOUDEST frame: room tone above -top_db of the peak reads as speech and nothing is cut; a breath is speech or pause
+    by its level alone; a weak consonant at a segment's edge is protected only by the pad."""
+    top_db: float = 40.0
+    min_pause_ms: float = 320.0
+    min_speech_ms: float = 96.0
+    pad_ms: float = 64.0
+
+    def frames(self, sample_rate: int):
+        """(min_pause, min_speech, pad) in frames at sample_rate"""
+        if int(sample_rate) < 1:
+            raise ValueError("sample_rate < 1")
+        return tuple(int(round(float(ms) * int(sample_rate) / (1000.0 * SEGMENTS_HOP))) for ms in (self.min_pause_ms, self.min_speech_ms, self.pad_ms))
+
+    def c_struct(self, sample_rate: int, keep: str = "speech") -> MT2SegmentsConfig:
+        for ms in (self.min_pause_ms, self.min_speech_ms, self.pad_ms):
+            if not math.isfinite(float(ms)):
+                raise ValueError("a duration that is not finite")
+        mp, ms, pad = self.frames(sample_rate)
+        return segments_config(self.top_db, mp, ms, pad, keep)
+
+
+def segments_bound(F: int, min_pause: int, min_speech: int) -> int:
+    """the most segments an utterance of F frames can have: max(1, (F + min_pause) // (min_speech + min_pause))"""
+    return max(1, (int(F) + int(min_pause)) // (int(min_speech) + int(min_pause)))
+
+
 class MT2Config(C.Structure):
     _fields_ = [
         ("mel_bins", C.c_int32), ("mrte_hidden", C.c_int32), ("mrte_kernel", C.c_int32), ("mrte_stride", C.c_int32),
@@ -221,6 +280,10 @@ def load_library():
     lib.mt2_declip_query.argtypes = [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 3
     lib.mt2_clip_detect.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
     lib.mt2_declip.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.mt2_segments_query.argtypes = [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 4
+    lib.mt2_segment_frames.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mt2_speech_segments.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int]
+    lib.mt2_cut_pauses.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.mt2_stft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_istft.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_mel_to_linear.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
@@ -607,6 +670,82 @@ def _declip(lib, h, wav, lens=None, declip: Optional[Declip] = None, return_figu
     if return_iters:
         res += (it,)
     return res[0] if len(res) == 1 else res
+
+
+def _segments_cfg(pauses, sample_rate: int, keep: str) -> MT2SegmentsConfig:
+    """a `Pauses` (durations, turned into frames at sample_rate), None (its defaults) or an MT2SegmentsConfig in frames (segments_config),
+    whose own `keep` then stands"""
+    if isinstance(pauses, MT2SegmentsConfig):
+        return pauses
+    return (pauses or Pauses()).c_struct(sample_rate, keep)
+
+
+def _segment_frames(lib, h, energy, frame_lens=None, pauses=None, sample_rate: int = 16000, keep: str = "speech"):
+    """mt2_segment_frames on the handle `h`, the staged form of the rule: energy f32 [B, F] (device; any contour >= 0, e.g. from
+    `frame_energy`), frame_lens int [B] (every row F by default) -> dict of device tensors: flags uint8 [B, F] (d; bytes at or beyond
+    frame_lens[b] are zero), segments int32 [B, S, 2] (FRAMES [f0, f1 + 1); -1 behind counts[b]; S = the bound of the rule), counts
+    int32 [B], figures float64 [B, 8] (PAUSES_NAMES).  The call only enqueues."""
+    import torch
+    assert energy.is_cuda and energy.dim() == 2
+    energy = energy.contiguous().to(torch.float32)
+    B, F = energy.shape
+    fl = np.full(B, F, np.int32) if frame_lens is None else _i32(frame_lens)
+    assert fl.shape == (B,)
+    cfg = _segments_cfg(pauses, sample_rate, keep)
+    S = segments_bound(int(fl.max()) if B else 1, cfg.min_pause, cfg.min_speech)
+    dev = energy.device
+    out = {"flags": torch.zeros(B, F, device=dev, dtype=torch.uint8), "segments": torch.empty(B, S, 2, device=dev, dtype=torch.int32),
+           "counts": torch.empty(B, device=dev, dtype=torch.int32), "figures": torch.empty(B, len(PAUSES_NAMES), device=dev, dtype=torch.float64)}
+    _check(lib.mt2_segment_frames(h, _stream(), C.byref(cfg), _ptr(energy), _iptr(fl), F, B, _ptr(out["flags"]), _ptr(out["segments"]), S,
+                                  _ptr(out["counts"]), _ptr(out["figures"])))
+    return out
+
+
+def _speech_segments(lib, h, wav, lens=None, pauses=None, sample_rate: int = 16000, keep: str = "speech", return_energy: bool = False):
+    """mt2_speech_segments on the handle `h`: wav f32 [B, L] (device, at sample_rate; nothing is resampled) -> dict of device tensors:
+    segments int32 [B, S, 2] (SAMPLES [start, end); -1 behind counts[b]), counts int32 [B], figures float64 [B, 8] (PAUSES_NAMES) and,
+    on request, energy f32 [B, 1 + max lens // 512].  Samples at or beyond lens[b] are never read.  The call only enqueues."""
+    import torch
+    wav, ln, B, L = _wav_lens(wav, lens)
+    cfg = _segments_cfg(pauses, sample_rate, keep)
+    F = 1 + max(int(ln.max()), 0) // SEGMENTS_HOP
+    S = segments_bound(F, cfg.min_pause, cfg.min_speech)
+    dev = wav.device
+    out = {"segments": torch.empty(B, S, 2, device=dev, dtype=torch.int32), "counts": torch.empty(B, device=dev, dtype=torch.int32),
+           "figures": torch.empty(B, len(PAUSES_NAMES), device=dev, dtype=torch.float64)}
+    if return_energy:
+        out["energy"] = torch.empty(B, F, device=dev, dtype=torch.float32)
+    _check(lib.mt2_speech_segments(h, _stream(), C.byref(cfg), _ptr(wav), _iptr(ln), L, B, _ptr(out["segments"]), S, _ptr(out["counts"]),
+                                   _ptr(out["figures"]), _ptr(out.get("energy")), F))
+    return out
+
+
+def _cut_pauses(lib, h, wav, lens=None, pauses=None, sample_rate: int = 16000, keep: str = "speech", out=None, return_segments: bool = False,
+                return_figures: bool = False):
+    """mt2_cut_pauses on the handle `h`: wav f32 [B, L] (device, at sample_rate) -> (out f32 [B, max lens], out_lens int32 [B]): the
+    kept frames of each utterance - its speech segments, or with keep = "pauses" everything else: a noise-only clip - moved together,
+    every sample an exact copy, zeros behind out_lens[b] (which may be 0 with keep = "pauses").  No cross-fade; every join is a multiple
+    of 512 samples.  out: a contiguous f32 [B, >= max lens] device tensor to write into (not wav).  return_segments: also segments
+    int32 [B, S, 2] (device; samples of the INPUT, -1 behind counts) and counts int32 [B] (device); return_figures: also float64 [B, 8]
+    (device; PAUSES_NAMES).  The call waits for the device once, for out_lens."""
+    import torch
+    wav, ln, B, L = _wav_lens(wav, lens)
+    cfg = _segments_cfg(pauses, sample_rate, keep)
+    out = _out_rows(out, B, wav, lambda: max(int(ln.max()), 1))
+    F = 1 + max(int(ln.max()), 0) // SEGMENTS_HOP
+    S = segments_bound(F, cfg.min_pause, cfg.min_speech)
+    seg = torch.empty(B, S, 2, device=wav.device, dtype=torch.int32) if return_segments else None
+    cnt = torch.empty(B, device=wav.device, dtype=torch.int32) if return_segments else None
+    fig = torch.empty(B, len(PAUSES_NAMES), device=wav.device, dtype=torch.float64) if return_figures else None
+    out_lens = np.zeros(B, np.int32)
+    _check(lib.mt2_cut_pauses(h, _stream(), C.byref(cfg), _ptr(wav), _iptr(ln), L, B, _ptr(out), out.shape[1], _iptr(out_lens), _ptr(seg), S,
+                              _ptr(cnt), _ptr(fig)))
+    res = (out, out_lens)
+    if return_segments:
+        res += (seg, cnt)
+    if return_figures:
+        res += (fig,)
+    return res
 
 
 def _workspace_fill(lib, h, byte: int) -> None:
@@ -1052,6 +1191,20 @@ class NativeModel:
     def declip(self, wav, lens=None, declip: Optional[Declip] = None, return_figures: bool = False, return_iters: bool = False, out=None):
         """Declipped audio of wav f32 [B, L] (`_declip`)."""
         return _declip(self.lib, self.h, wav, lens, declip, return_figures, return_iters, out)
+
+    # ---- speech segments by frame energy and the cut of the pauses (csrc/segments.hip) on the model's handle, as MelFrontEnd's
+    def segment_frames(self, energy, frame_lens=None, pauses=None, sample_rate: int = 16000, keep: str = "speech"):
+        """The staged form of the rule on any energy contour (`_segment_frames`)."""
+        return _segment_frames(self.lib, self.h, energy, frame_lens, pauses, sample_rate, keep)
+
+    def speech_segments(self, wav, lens=None, pauses=None, sample_rate: int = 16000, keep: str = "speech", return_energy: bool = False):
+        """The speech segments of wav f32 [B, L] in samples (`_speech_segments`)."""
+        return _speech_segments(self.lib, self.h, wav, lens, pauses, sample_rate, keep, return_energy)
+
+    def cut_pauses(self, wav, lens=None, pauses=None, sample_rate: int = 16000, keep: str = "speech", out=None, return_segments: bool = False,
+                   return_figures: bool = False):
+        """wav f32 [B, L] with its pauses (or with keep = "pauses" its speech) cut out (`_cut_pauses`)."""
+        return _cut_pauses(self.lib, self.h, wav, lens, pauses, sample_rate, keep, out, return_segments, return_figures)
 
     # ---- de-reverberation by weighted prediction error (csrc/wpe.hip) on the model's handle, as MelFrontEnd's
     def dereverb(self, wav, lens=None, dereverb: Optional[Dereverb] = None, return_figures: bool = False, out=None, audio=None):
@@ -1544,6 +1697,23 @@ class MelFrontEnd:
         [B, T]]."""
         return _declip(self.lib, self.h, wav, lens, declip, return_figures, return_iters, out)
 
+    # ---- speech segments by frame energy and the cut of the pauses (csrc/segments.hip), at the audio's own rate
+    def segment_frames(self, energy, frame_lens=None, pauses=None, sample_rate: Optional[int] = None, keep: str = "speech"):
+        """The staged form of the rule on any energy contour f32 [B, F] (`_segment_frames`) -> dict: flags, segments (frames), counts,
+        figures.  pauses: a `Pauses` (frames at sample_rate, default audio.sample_rate) or a `segments_config` in frames."""
+        return _segment_frames(self.lib, self.h, energy, frame_lens, pauses, self._rate(sample_rate), keep)
+
+    def speech_segments(self, wav, lens=None, pauses=None, sample_rate: Optional[int] = None, keep: str = "speech", return_energy: bool = False):
+        """The speech segments of wav f32 [B, L] at sample_rate (default audio.sample_rate) in samples (`_speech_segments`) -> dict:
+        segments int32 [B, S, 2], counts int32 [B], figures float64 [B, 8] (PAUSES_NAMES)[, energy]."""
+        return _speech_segments(self.lib, self.h, wav, lens, pauses, self._rate(sample_rate), keep, return_energy)
+
+    def cut_pauses(self, wav, lens=None, pauses=None, sample_rate: Optional[int] = None, keep: str = "speech", out=None,
+                   return_segments: bool = False, return_figures: bool = False):
+        """wav f32 [B, L] with its pauses - or with keep = "pauses" its speech - cut out (`_cut_pauses`) -> (out, out_lens int32 [B][,
+        segments, counts][, figures])."""
+        return _cut_pauses(self.lib, self.h, wav, lens, pauses, self._rate(sample_rate), keep, out, return_segments, return_figures)
+
     # ---- de-reverberation by weighted prediction error (csrc/wpe.hip): a per-bin prediction filter between the STFT and its inverse
     def dereverb(self, wav, lens=None, dereverb: Optional[Dereverb] = None, return_figures: bool = False, out=None):
         """De-reverberated audio of wav f32 [B, L] at audio.sample_rate (`_dereverb`) -> (out f32 [B, hop * (max lens // hop)], out_lens
@@ -1665,7 +1835,8 @@ class MelFrontEnd:
 
     def from_audio(self, wav, sr_in: int, lens=None, trim_db: Optional[float] = None, return_bounds: bool = False,
                    denoise: Optional[Denoise] = None, return_noise: bool = False, dereverb: Optional[Dereverb] = None,
-                   return_reverb: bool = False, declip: Optional[Declip] = None, return_clipping: bool = False):
+                   return_reverb: bool = False, declip: Optional[Declip] = None, return_clipping: bool = False,
+                   cut_pauses: Optional[Pauses] = None, return_segments: bool = False, return_pauses: bool = False):
         """Prompt audio at any sample rate -> (mel [B, T, n_mels], mel_lens): resample to audio.sample_rate, peak-normalise and
         extract the mel (models/megatts2.py:335-336,339) with no host round trip.  Audio that already has that rate is only
         normalised, by the same kernels.  trim_db: leading / trailing silence is cut off between the normalisation and the mel
@@ -1680,8 +1851,17 @@ class MelFrontEnd:
         return_reverb (needs dereverb): a last result, its figures float64 [B, 8] (device; WPE_NAMES).  declip (None = off, exactly
         the call without it): a `Declip`; clipped samples are restored FIRST, at sr_in - the resampler and the normalisation turn flat
         tops into ripple that nothing can recognise as clipping (declip -> resample -> normalise -> dereverb -> denoise -> normalise ->
-        trim); return_clipping (needs declip): the very last result, its figures float64 [B, 8] (device; DECLIP_NAMES)."""
+        trim); return_clipping (needs declip): a last result, its figures float64 [B, 8] (device; DECLIP_NAMES).  cut_pauses (None =
+        off, exactly the call without it): a `Pauses`; where the trim would run, behind the last normalisation, the pauses INSIDE the
+        audio are cut out as well as its ends (`cut_pauses`; the pad included), so it excludes trim_db and return_bounds (ValueError).
+        return_segments (needs cut_pauses): two more results, segments int32 [B, S, 2] (device; samples of the normalised audio, -1
+        behind counts) and counts int32 [B] (device); return_pauses (needs cut_pauses): the very last result, its figures float64
+        [B, 8] (device; PAUSES_NAMES)."""
         import torch
+        if cut_pauses is not None and (trim_db is not None or return_bounds):
+            raise ValueError("cut_pauses cuts the ends itself: it excludes trim_db and return_bounds")
+        if cut_pauses is None and (return_segments or return_pauses):
+            raise ValueError("return_segments and return_pauses need cut_pauses")
         assert wav.is_cuda and wav.dim() == 2
         assert denoise is not None or not return_noise
         assert dereverb is not None or not return_reverb
@@ -1714,6 +1894,10 @@ class MelFrontEnd:
         bounds = None
         if trim_db is not None:
             y, ln, bounds = self.trim(y, ln, trim_db)
+        cut = None
+        if cut_pauses is not None:
+            cut = self.cut_pauses(y, ln, cut_pauses, return_segments=return_segments, return_figures=return_pauses)
+            y, ln = cut[0], cut[1]
         res = (self(y, ln), 1 + ln // self.audio.hop_length)
         if return_bounds:
             res += (np.stack([np.zeros_like(ln), ln], axis=1) if bounds is None else bounds,)
@@ -1723,6 +1907,8 @@ class MelFrontEnd:
             res += (reverb,)
         if return_clipping:
             res += (clipping,)
+        if cut is not None:
+            res += cut[2:]
         return res
 
 
@@ -2435,6 +2621,20 @@ def dereverb_query(audio=None, lens=None, L_max: Optional[int] = None, B: Option
     _check(load_library().mt2_dereverb_query(C.byref(ac), C.byref(wc), _iptr(ln), int(L_max or 0), int(B or 0), C.byref(nbytes),
                                              C.byref(lout)))
     return nbytes.value, lout.value
+
+
+def segments_query(lens=None, L_max: Optional[int] = None, B: Optional[int] = None, pauses=None, sample_rate: int = 16000):
+    """mt2_segments_query (no device needed) -> (frames of the longest utterance, the f32 factor 10^(-top_db / 10), the most segments an
+    utterance can have - the S of `speech_segments` -, arena bytes of one `speech_segments` or `cut_pauses` call): lens int [B] in
+    samples, or every utterance L_max samples.  pauses: a `Pauses` at sample_rate, or a `segments_config` in frames."""
+    ln = None if lens is None else _i32(lens)
+    if ln is not None:
+        L_max = int(ln.max()) if L_max is None and ln.size else L_max
+        B = ln.size
+    cfg = _segments_cfg(pauses, sample_rate, "speech")
+    F, c, S, nbytes = C.c_int(0), C.c_float(0.0), C.c_longlong(0), C.c_longlong(0)
+    _check(load_library().mt2_segments_query(C.byref(cfg), _iptr(ln), int(L_max or 0), int(B or 0), C.byref(F), C.byref(c), C.byref(S), C.byref(nbytes)))
+    return F.value, c.value, S.value, nbytes.value
 
 
 def declip_query(lens=None, L_max: Optional[int] = None, B: Optional[int] = None, declip: Optional[Declip] = None):

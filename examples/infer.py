@@ -94,6 +94,13 @@ def main() -> None:
     ap.add_argument("--report-pauses", action="store_true",
                     help="print, for each prompt file, its speech segments, the seconds of speech of the total, the longest pause and the "
                          "speech / pause energy ratio in dB (measured on the GPU); alone it only reports, nothing is cut")
+    ap.add_argument("--report-formants", action="store_true",
+                    help="print, for the first prompt file and for the generated audio, the voiced frames used, the mean and sigma of F1 .. F4 "
+                         "and the vocal-tract length they imply (linear prediction on the GPU), then the length ratio and the formants' "
+                         "differences in per cent: whether the output has the prompt's vocal tract, whatever the text; alone it only reports")
+    ap.add_argument("--max-formant", type=float, default=5500.0, metavar="HZ",
+                    help="with --report-formants: the formant ceiling; the audio is analysed at twice this rate (5500 for a female voice, 5000 for a male one)")
+    ap.add_argument("--lpc-order", type=int, default=10, metavar="P", help="with --report-formants: the order of the all-pole fit, even, 2 to 32 (default 10)")
     ap.add_argument("--reference-wav", metavar="PATH",
                     help="a recording of the same sentence: print the mel-cepstral distortion (dB, along the DTW path of the cepstra), the largest "
                          "cell, and F0 RMSE, register offset and voiced / unvoiced error along the same path, of the generated audio against it")
@@ -247,6 +254,27 @@ def main() -> None:
                   f"(a DCT of the 80-bin log-mel: comparable with itself only), largest cell {float(st['max_db'][0]):.3f} dB; F0 RMSE "
                   f"{float(st['f0_rmse_cents'][0]):.1f} cents and register offset {float(st['f0_offset_cents'][0]):+.1f} cents over "
                   f"{int(st['voiced_cells'][0])} cells voiced on both sides, voiced / unvoiced error {100.0 * float(st['vuv_error'][0]):.2f} %")
+    if a.report_formants:
+        import glob
+        from megatts2_amd import audio_io
+        fm = M.Formants(max_formant_hz=a.max_formant, order=a.lpc_order)
+        path = sorted(glob.glob(f"{a.wavs_dir}/*.wav"))[0]
+        y, sr = audio_io.read_wav(path)
+        f0 = M.extract_f0(y, sr, method=a.pitch_tracker)
+        tr = M.extract_formants(y, sr, formants=fm)
+        n = min(int(f0.shape[0]), int(tr["count"].shape[0]))
+        report = [(f"first prompt ({path})", M.formant_stats(tr["freq"][:n], tr["count"][:n], f0[:n], [min(n, int(tr["frame_lens"][0]))]))]
+        if wrote:          # the generated audio alone, as the vocoder left it on the device - not the written file (prompt in front)
+            report.append(("generated audio", tts.output_formants(lens, aux, tracker=a.pitch_tracker, formants=fm)))
+        for what, st in report:
+            print(f"formants of the {what}: {int(st['frames'][0])} voiced frames with four candidates ({100 * float(st['share'][0]):.1f} %), " +
+                  ", ".join(f"F{k} {float(st[f'f{k}'][0]):.0f} +- {float(st[f'f{k}_sigma'][0]):.0f} Hz" for k in range(1, 5)) +
+                  f", dispersion {float(st['dispersion'][0]):.0f} Hz, vocal-tract length {float(st['vtl_cm'][0]):.2f} cm")
+        if len(report) == 2 and all(float(st["frames"][0]) > 0 for _, st in report):
+            p, g = report[0][1], report[1][1]
+            print(f"generated against the prompt: vocal-tract length ratio {float(g['vtl_cm'][0]) / float(p['vtl_cm'][0]):.3f}, " +
+                  ", ".join(f"F{k} {100 * (float(g[f'f{k}'][0]) / float(p[f'f{k}'][0]) - 1):+.1f} %" for k in range(1, 5)) +
+                  " (LPC by the autocorrelation method at order " + f"{a.lpc_order}, {a.max_formant:g} Hz ceiling; per-frame candidates, untracked)")
     if a.report_prosody:
         import glob
         import math

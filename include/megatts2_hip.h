@@ -869,6 +869,98 @@ int mt2_phone_prosody(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/
 int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/, const int32_t* frame_lens /*host*/, int T_max, int B,
                       int center, float* st /*[B, T_max]*/, int32_t* n_voiced /*[B]*/, int32_t* index /*or NULL*/);
 
+/* ---- Formant candidates by linear prediction (csrc/formants.hip; Markel & Gray 1976) and the formant figures of an utterance: the
+ * resonances of an all-pole fit of every frame, their means, the formant dispersion (Fitch 1997) and a vocal-tract length (the uniform
+ * tube closed at one end; Wakita 1977, Reby & McComb 2003) - a timbre measure that, unlike mt2_mel_cepstral_distortion, needs no
+ * recording of the same sentence.  No reference counterpart.  The fit is the AUTOCORRELATION method; parity with Praat (Burg's method,
+ * Gaussian window) is unpinned, and so is quality on real speech; the rule is our own statement, restated in tests/formant_ref.py,
+ * and the tests hold the kernel to it and to the poles of known all-pole filters.  Candidates are per frame: nothing tracks a formant
+ * across frames, so candidate q of one frame need not be candidate q of the next.
+ * THE RULE, for one utterance x f32 [L] at sample_rate, a hop, an even window W in [64, 1024] and an even order P in [2, 32], P < W:
+ *  1 frames  T = 1 + L / hop.  Frame t covers the samples i = s + j, s = hop t - W / 2, j = 0 .. W - 1.  A sample outside [0, L) is a
+ *            zero by its index and is never read.  At hop = the mel's and the mel's rate, frame t is centred like mel frame t.
+ *  2 pre-emphasis in double:  y[i] = x[i] - alpha * x[i - 1] (one product, one difference, each rounded), x[-1] = 0,
+ *            alpha = exp(-2 pi preemphasis_hz / sample_rate) made in double on the host.  preemphasis_hz = 0 is alpha = 0: off, y[i] =
+ *            x[i] and x[i - 1] is not read.  With alpha > 0 frame t reads x over [s - 1, s + W) within [0, L).
+ *  3 window  v[j] = y[s + j] * w[j], one product; 0 for a sample outside [0, L).  MT2_FORMANT_HANN: w[j] = 0.5 - 0.5 cos(2 pi (j + 0.5)
+ *            / W);  MT2_FORMANT_RECT: w[j] = 1.  The table is built in double on the host (mt2_formant_window) and kept in the handle
+ *            per (W, kind) as the resampler keeps its filters: the first call with a new pair uploads it, every later one only enqueues.
+ *  4 autocorrelation in double:  r[k] = sum_j v[j] v[j + k], k = 0 .. P, in this order: lane l of 64 runs ONE chain acc = fma(v[j],
+ *            v[j + k], acc) from 0 over j = l, l + 64, l + 128, ... while j + k < W;  the 64 partial sums meet in the xor butterfly
+ *            32, 16, 8, 4, 2, 1 (lane l adds lane l ^ o's value to its own).  Then r[0] = r[0] * (1 + 1e-9), one product.  The frame is
+ *            EMPTY unless r[0] > 1e-300 and r[0] is finite.
+ *  5 Levinson-Durbin in double, every operation rounded on its own, no fma:
+ *              e = r[0];  a[0] = 1
+ *              for m = 1 .. P:
+ *                acc = r[m];  for i = 1 .. m - 1 ascending:  acc = acc + (a[i] * r[m - i])
+ *                k = (-acc) / e;  the frame is empty unless |k| < 1
+ *                for i = 1 .. m - 1:  a'[i] = a[i] + (k * a[m - i]) (from the a of before this m);  a'[m] = k;  a = a'
+ *                e = e * (1 - (k * k));  the frame is empty unless e > 0 and e is finite
+ *            and empty if an a[i] is not finite.  lpc = a[0 .. P], err = the last e.
+ *  6 roots   of z^P + a[1] z^(P-1) + ... + a[P] by Aberth-Ehrlich iteration in double complex, not pinned to the bit.  Starts z_k =
+ *            0.9 exp(i (2 pi k / P + 0.4)), k = 0 .. P - 1.  One iteration, for every k from the z of before it:  p and p' at z_k by
+ *            Horner, q = p / p';  S = sum over j != k, j ascending, of 1 / (z_k - z_j);  w_k = q / (1 - q S);  z_k = z_k - w_k.  It stops
+ *            after the iteration whose max_k |w_k|^2 < 1e-26 (max_k |w_k| < 1e-13); iters = the iterations run.  The frame is empty
+ *            if a w_k is not finite or MT2_FORMANT_MAX_ITERS = 64 iterations do not get there.
+ *  7 candidates  of the roots with Im z > 0:  f = atan2(Im z, Re z) sample_rate / (2 pi),  bw = -(1/2) ln(|z|^2) sample_rate / pi.
+ *            Kept:  fmin_hz < f < sample_rate / 2 - fmin_hz  and  bw < max_bandwidth_hz.  Sorted ascending by f, a tie going to the
+ *            smaller root index.  count = min(kept, MT2_FORMANT_MAX = 5);  freq[t][q], bw[t][q] = candidate q rounded to f32 for q <
+ *            count, zeros behind.
+ * An EMPTY frame has count 0, freq and bw zeros, iters -1; of the optional outputs it keeps what its stages reached - autocorr always,
+ * lpc and err if step 5 went through - and has zeros in the others.  A frame in [T_b, T_max) has zeros everywhere, iters 0 as well.
+ * Nothing depends on the batch slot, L_max or T_max: a ragged batch is bit-identical to its utterances alone.  A non-finite sample
+ * cannot fault and cannot write outside the outputs; it empties the frames that read it (step 2) and changes no other frame's bits.
+ * Refused on the host (error, nothing launched, every output as it was): B < 1 or > 65535; lens[b] < 1 or > L_max; sample_rate < 1;
+ * hop outside [1, 1024]; window outside [64, 1024] or odd; order outside [2, 32] or odd; order >= window (which the two ranges as they stand already exclude: a guard); kind not one of the two;
+ * reserved not 0; a non-finite or negative preemphasis_hz, fmin_hz or max_bandwidth_hz; fmin_hz >= sample_rate / 4; T_max < 1 + max_b
+ * lens[b] / hop; a NULL or misaligned buffer; an output overlapping wav or another output.
+ * Limits: LPC on a voiced frame fits the harmonics as well as the envelope - a formant near a strong harmonic is drawn to it (F1 of a
+ * 700 Hz resonance under 110 Hz pulses reads about 764 Hz, by the 7th harmonic): a property of linear prediction, not of the kernel.
+ * Out of scope: Burg's method; tracking across frames (Viterbi over candidates); LPC-cepstral distortion; line spectral frequencies;
+ * nasal / anti-formant models; a streaming form; multichannel.
+ *
+ * THE FIGURES, mt2_formant_stats: over the frames t < frame_lens[b] with count[t] >= 4, and f0[t] > 0 where an F0 track is given, all
+ * in double, two passes, sums in the order of mt2_f0_stats (thread i of 256 sums the frames i, i + 256, ... ascending, the partial sums
+ * meet in a fixed tree):  n;  mu_k = sum freq[t][k - 1] / n and sigma_k = sqrt(sum (freq[t][k - 1] - mu_k)^2 / n) for k = 1 .. 4.  A row
+ * of MT2_FORMANT_STAT_FIELDS = 12 doubles:  0 n   1 n / T_b   2-5 mu_1 .. mu_4   6-9 sigma_1 .. sigma_4   10 the formant dispersion
+ * (mu_4 - mu_1) / 3   11 the vocal-tract length in cm, (35000 / 4) (1 / 4) sum_k (2 k - 1) / mu_k, evaluated as
+ * 2187.5 * (((1 / mu_1 + 3 / mu_2) + 5 / mu_3) + 7 / mu_4): 17.5 cm for 500 / 1500 / 2500 / 3500 Hz.  n = 0: all zeros. */
+#define MT2_FORMANT_MAX 5
+#define MT2_FORMANT_MAX_WINDOW 1024
+#define MT2_FORMANT_MAX_ORDER 32
+#define MT2_FORMANT_MAX_ITERS 64
+#define MT2_FORMANT_STAT_FIELDS 12
+#define MT2_FORMANT_HANN 0
+#define MT2_FORMANT_RECT 1
+typedef struct mt2_formant_config {
+    int32_t window;            /* W, samples: even, in [64, 1024];  550 = 50 ms at 11 kHz */
+    int32_t order;             /* P: even, in [2, 32], < window;  10 */
+    int32_t kind;              /* MT2_FORMANT_HANN or MT2_FORMANT_RECT */
+    int32_t reserved;          /* 0 */
+    double preemphasis_hz;     /* >= 0, finite; 0 = off;  50 */
+    double fmin_hz;            /* >= 0, finite, < sample_rate / 4;  50 */
+    double max_bandwidth_hz;   /* >= 0, finite;  500 */
+} mt2_formant_config;
+/* Host only, no HIP call; outputs may be NULL.  frames = 1 + L / hop;  workspace_bytes = the arena high water of one mt2_lpc_formants
+ * call exactly, whatever B and whatever optional outputs: 4 * 65535 rounded up to 256 - the lengths, in the room of the largest batch.
+ * Refuses what mt2_lpc_formants refuses of these arguments, and L outside [1, 2^31). */
+int mt2_formant_query(int sample_rate, int hop, int window, int order, long long L, int* frames, long long* workspace_bytes);
+/* Host only: the window of step 3, table[0 .. window) in double.  Refuses a window outside [64, 1024] or odd and an unknown kind. */
+int mt2_formant_window(int window, int kind, double* table /*host [window]*/);
+/* wav f32 [B, L_max] (device; samples at or beyond lens[b] are never read), lens host int32 [B] -> freq, bw f32 [B, T_max, 5] and count
+ * int32 [B, T_max] (device).  Optional (NULL to skip), device, 8-byte aligned where f64: lpc f64 [B, T_max, P + 1], err f64 [B, T_max],
+ * autocorr f64 [B, T_max, P + 1] (r[0] as scaled), roots f64 [B, T_max, P, 2] (re, im; in root-index order), iters int32 [B, T_max].
+ * ONE launch for the batch, a wave per frame; the call only enqueues.  `m` may be a bare handle. */
+int mt2_lpc_formants(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/, const int32_t* lens /*host*/, int L_max, int B,
+                     int sample_rate, int hop, const mt2_formant_config* cfg, float* freq /*[B, T_max, 5]*/, float* bw /*[B, T_max, 5]*/,
+                     int32_t* count /*[B, T_max]*/, int T_max, double* lpc /*or NULL*/, double* err /*or NULL*/, double* autocorr /*or NULL*/,
+                     double* roots /*or NULL*/, int32_t* iters /*or NULL*/);
+/* freq f32 [B, T_max, 5], count int32 [B, T_max], f0 f32 [B, T_max] or NULL (all device), frame_lens host int32 [B] in [1, T_max] ->
+ * stats f64 [B, 12] (device).  One launch, a workgroup per utterance; the call only enqueues.  Refused: B < 1 or > 65535; a frame count
+ * outside [1, T_max]; a NULL or misaligned buffer; stats overlapping an input. */
+int mt2_formant_stats(mt2_model* m, void* stream, const float* freq /*[B, T_max, 5]*/, const int32_t* count /*[B, T_max]*/,
+                      const float* f0 /*or NULL*/, const int32_t* frame_lens /*host*/, int T_max, int B, double* stats /*[B, 12]*/);
+
 /* ---- Integrated loudness and loudness normalisation (csrc/loudness.hip): ITU-R BS.1770-4 gated loudness, which EBU R 128 builds on, of
  * a ragged batch of mono utterances, and each utterance brought to a target loudness by one gain.  No reference counterpart (the
  * reference peak-normalises its prompts, models/megatts2.py:336, and leaves the output level alone).  Parity with pyloudnorm /

@@ -852,6 +852,50 @@ int mt2_f0_stats(mt2_model* m, void* stream, const float* f0, const int32_t* fra
     MT2_API_END
 }
 
+// formant candidates by linear prediction: the frame count and the arena bytes of the rule, without a HIP call
+int mt2_formant_query(int sample_rate, int hop, int window, int order, long long L, int* frames, long long* workspace_bytes) {
+    MT2_API_BEGIN
+    formant_check_rule(sample_rate, hop, window, order);
+    MT2_REQUIRE(L >= 1 && L <= INT_MAX, "L outside [1, 2^31)");
+    MT2_REQUIRE(1 + L / hop <= INT_MAX, "2^31 frames or more");
+    if (frames) *frames = (int)(1 + L / hop);
+    if (workspace_bytes) *workspace_bytes = formant_arena_bytes();
+    MT2_API_END
+}
+
+// the window the device applies, in double (host only: lets a test pin it without a GPU)
+int mt2_formant_window(int window, int kind, double* table) {
+    MT2_API_BEGIN
+    MT2_REQUIRE(window >= 64 && window <= MT2_FORMANT_MAX_WINDOW && window % 2 == 0, "window outside [64, 1024] or odd");
+    formant_check_kind(kind);
+    MT2_REQUIRE(table != nullptr, "null table");
+    formant_window_table(window, kind, table);
+    MT2_API_END
+}
+
+// formant candidates (and, optionally, every intermediate) of a ragged batch; every refusal is decided on the host before the first HIP call
+int mt2_lpc_formants(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int sample_rate, int hop,
+                     const mt2_formant_config* cfg, float* freq, float* bw, int32_t* count, int T_max, double* lpc, double* err,
+                     double* autocorr, double* roots, int32_t* iters) {
+    MT2_API_BEGIN
+    formant_check_config(sample_rate, hop, cfg);
+    const FormantOut o{freq, bw, count, T_max, lpc, err, autocorr, roots, iters};
+    const int mx = formant_check_call(wav, lens, L_max, B, hop, cfg->order, o);
+    MT2_AUDIO_CALL(m, stream);
+    formant_run(c, wav, lens, L_max, B, mx, sample_rate, hop, *cfg, o);
+    MT2_API_END
+}
+
+// the formant figures of candidate tracks over their frames with four candidates (voiced ones, where an F0 track is given)
+int mt2_formant_stats(mt2_model* m, void* stream, const float* freq, const int32_t* count, const float* f0, const int32_t* frame_lens,
+                      int T_max, int B, double* stats) {
+    MT2_API_BEGIN
+    formant_stats_check(freq, count, f0, frame_lens, T_max, B, stats);
+    MT2_AUDIO_CALL(m, stream);
+    formant_stats_run(c, freq, count, f0, frame_lens, T_max, B, stats);
+    MT2_API_END
+}
+
 // the energy contour on the F0 / mel frames (prosody.hip); every refusal is decided on the host before the first HIP call
 int mt2_frame_energy(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int hop, float* energy,
                      int T_max) {

@@ -2331,6 +2331,92 @@ static void f0_stats_run(const Ctx& c, const float* f0, const int* frame_lens, i
     MT2_HIP(launch_f0_stats(f0, ip.dev(o_len), T_max, B, stats, c.s));
 }
 
+// ---- formant candidates by linear prediction and the formant figures (formants.hip) -----------------------------------------------
+// The parameters of the rule that mt2_formant_query shares with the call, checked before anything else (host only)
+static void formant_check_rule(int sample_rate, int hop, int window, int order) {
+    MT2_REQUIRE(sample_rate >= 1, "sample_rate < 1");
+    MT2_REQUIRE(hop >= 1 && hop <= 1024, "hop outside [1, 1024]");
+    MT2_REQUIRE(window >= 64 && window <= MT2_FORMANT_MAX_WINDOW && window % 2 == 0, "window outside [64, 1024] or odd");
+    MT2_REQUIRE(order >= 2 && order <= MT2_FORMANT_MAX_ORDER && order % 2 == 0, "order outside [2, 32] or odd");
+    MT2_REQUIRE(order < window, "order >= window");
+}
+static void formant_check_kind(int kind) { MT2_REQUIRE(kind == MT2_FORMANT_HANN || kind == MT2_FORMANT_RECT, "unknown window kind"); }
+static void formant_check_config(int sample_rate, int hop, const mt2_formant_config* cfg) {
+    MT2_REQUIRE(cfg != nullptr, "null formant config");
+    formant_check_rule(sample_rate, hop, cfg->window, cfg->order);
+    formant_check_kind(cfg->kind);
+    MT2_REQUIRE(cfg->reserved == 0, "mt2_formant_config.reserved must be 0");
+    MT2_REQUIRE(std::isfinite(cfg->preemphasis_hz) && cfg->preemphasis_hz >= 0.0, "preemphasis_hz must be finite and >= 0");
+    MT2_REQUIRE(std::isfinite(cfg->fmin_hz) && cfg->fmin_hz >= 0.0, "fmin_hz must be finite and >= 0");
+    MT2_REQUIRE(std::isfinite(cfg->max_bandwidth_hz) && cfg->max_bandwidth_hz >= 0.0, "max_bandwidth_hz must be finite and >= 0");
+    MT2_REQUIRE(cfg->fmin_hz < (double)sample_rate / 4.0, "fmin_hz >= sample_rate / 4");
+}
+struct FormantOut { float* freq; float* bw; int32_t* count; int T_max; double* lpc; double* err; double* autocorr; double* roots; int32_t* iters; };
+// every refusal of mt2_lpc_formants beyond the config, decided on the host before the first HIP call; -> max_b lens[b]
+static int formant_check_call(const float* wav, const int* lens, int L_max, int B, int hop, int P, const FormantOut& o) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(wav != nullptr && lens != nullptr && o.freq != nullptr && o.bw != nullptr && o.count != nullptr && L_max >= 1, "bad buffers");
+    MT2_REQUIRE((((uintptr_t)wav | (uintptr_t)o.freq | (uintptr_t)o.bw | (uintptr_t)o.count | (uintptr_t)o.iters) & 3) == 0 &&
+                    (((uintptr_t)o.lpc | (uintptr_t)o.err | (uintptr_t)o.autocorr | (uintptr_t)o.roots) & 7) == 0,
+                "misaligned buffers");
+    const int mx = check_lens(lens, B, L_max, "waveform length outside [1, L_max]");
+    MT2_REQUIRE((long long)o.T_max >= 1ll + mx / hop, "T_max smaller than 1 + max length / hop");
+    const size_t nt = (size_t)B * o.T_max;
+    MT2_REQUIRE(!outputs_overlap({{o.freq, 4 * nt * MT2_FORMANT_MAX}, {o.bw, 4 * nt * MT2_FORMANT_MAX}, {o.count, 4 * nt}, {o.lpc, 8 * nt * (P + 1)},
+                                  {o.err, 8 * nt}, {o.autocorr, 8 * nt * (P + 1)}, {o.roots, 16 * nt * P}, {o.iters, 4 * nt}},
+                                 {{wav, sizeof(float) * (size_t)B * L_max}}),
+                "overlapping buffers");
+    return mx;
+}
+static const double* formant_prepare(mt2_model& m, int W, int kind) {
+    double*& d = m.fm_windows[{W, kind}];
+    if (d) return d;
+    std::vector<double> h(W);
+    formant_window_table(W, kind, h.data());
+    double* t = nullptr;
+    MT2_HIP(hipMalloc(reinterpret_cast<void**>(&t), h.size() * sizeof(double)));
+    m.dev_allocs.push_back(t);
+    MT2_HIP(hipMemcpy(t, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    return d = t;
+}
+// the arena of one mt2_lpc_formants call
+static long long formant_arena_bytes() { return (long long)arena_round(sizeof(int) * 65535); }
+// enqueues only (behind the first call with a new window, which uploads its table): the lengths travel in the call's one upload
+static void formant_run(const Ctx& c, const float* wav, const int* lens, int L_max, int B, int max_len, int sample_rate, int hop,
+                        const mt2_formant_config& cfg, const FormantOut& o) {
+    FormantP p{};
+    p.window = formant_prepare(c.m, cfg.window, cfg.kind);
+    // the arena of the call: the lengths, in the room of the largest batch whatever B - so that mt2_formant_query needs no B
+    int* st = static_cast<int*>(c.m.pinned().alloc(sizeof(int) * B));      // handle-owned staging
+    std::copy(lens, lens + B, st);
+    int* d_len = c.ws.get<int>(65535);
+    MT2_HIP(hipMemcpyAsync(d_len, st, sizeof(int) * B, hipMemcpyHostToDevice, c.s));
+    p.wav = wav; p.L_max = L_max; p.len = d_len; p.max_len = max_len; p.B = B;
+    p.sample_rate = sample_rate; p.hop = hop; p.W = cfg.window; p.P = cfg.order;
+    p.alpha = formant_alpha(cfg.preemphasis_hz, sample_rate); p.fmin = cfg.fmin_hz; p.max_bw = cfg.max_bandwidth_hz;
+    p.freq = o.freq; p.bw = o.bw; p.count = o.count; p.T_max = o.T_max;
+    p.lpc = o.lpc; p.err = o.err; p.autocorr = o.autocorr; p.roots = o.roots; p.iters = o.iters;
+    MT2_HIP(launch_formants(p, c.s));
+}
+static void formant_stats_check(const float* freq, const int32_t* count, const float* f0, const int* frame_lens, int T_max, int B,
+                                const double* stats) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(freq != nullptr && count != nullptr && frame_lens != nullptr && stats != nullptr && T_max >= 1, "bad buffers");
+    MT2_REQUIRE((((uintptr_t)freq | (uintptr_t)count | (uintptr_t)f0) & 3) == 0 && ((uintptr_t)stats & 7) == 0, "misaligned buffers");
+    check_lens(frame_lens, B, T_max, "frame count outside [1, T_max]");
+    const size_t nt = (size_t)B * T_max;
+    MT2_REQUIRE(!outputs_overlap({{stats, sizeof(double) * MT2_FORMANT_STAT_FIELDS * (size_t)B}},
+                                 {{freq, 4 * nt * MT2_FORMANT_MAX}, {count, 4 * nt}, {f0, 4 * nt}}),
+                "stats overlaps an input");
+}
+static void formant_stats_run(const Ctx& c, const float* freq, const int32_t* count, const float* f0, const int* frame_lens, int T_max, int B,
+                              double* stats) {
+    IntPlan ip;
+    const int o_len = ip.add(frame_lens, B);
+    ip.upload(c.ws, c.m.pinned(), c.s);
+    MT2_HIP(launch_formant_stats(freq, count, f0, ip.dev(o_len), T_max, B, stats, c.s));
+}
+
 // ---- per-phone prosody (prosody.hip): every refusal is decided here, on the host, before the first HIP call -------------------------
 // mt2_frame_energy; -> max_b lens[b]
 static int energy_check(const float* wav, const int* lens, int L_max, int B, int hop, const float* energy, int T_max) {

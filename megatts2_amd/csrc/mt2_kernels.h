@@ -678,6 +678,25 @@ hipError_t launch_f0_viterbi(const F0TrackP& p, hipStream_t s);       // p.dprim
 // stats[b, 0 .. 6) (double) = n, n / T_b, mean, sigma, skewness, excess kurtosis of f0[b, t] > 0 over t < frame_len[b]; a workgroup per utterance
 hipError_t launch_f0_stats(const float* f0, const int* frame_len, int T_max, int B, double* stats, hipStream_t s);
 
+// ---- formant candidates by linear prediction and the formant figures (formants.hip; the rule is in its header and in megatts2_hip.h) --
+// host only, no HIP call: the window table w[0 .. W) in double and the pre-emphasis coefficient exp(-2 pi hz / sample_rate) (0 for hz = 0)
+void formant_window_table(int W, int kind, double* table);
+double formant_alpha(double preemphasis_hz, int sample_rate);
+// One launch over (frames, utterances), a wave per frame; frames in [T_b, T_max) are written count 0, zeros, iters 0.
+struct FormantP {
+    const float* wav; int L_max;              // [B, L_max]; samples at or beyond len[b] are never read
+    const int* len; int max_len, B;           // device [B]; max_b len[b]
+    int sample_rate, hop, W, P;
+    const double* window;                     // device [W]: formant_window_table
+    double alpha, fmin, max_bw;
+    float* freq; float* bw; int* count; int T_max;      // [B, T_max, 5], [B, T_max, 5], [B, T_max]
+    double* lpc; double* err; double* autocorr; double* roots; int* iters;      // optional [B, T_max, P + 1], [B, T_max], [B, T_max, P + 1], [B, T_max, P, 2], [B, T_max]
+};
+hipError_t launch_formants(const FormantP& p, hipStream_t s);
+// stats[b, 0 .. 12) (double) over the frames t < frame_len[b] with count >= 4 (and f0 > 0 where f0 is given); a workgroup per utterance
+hipError_t launch_formant_stats(const float* freq, const int* count, const float* f0, const int* frame_len, int T_max, int B, double* stats,
+                                hipStream_t s);
+
 // ---- per-phone prosody (prosody.hip; the rules are in its header and in megatts2_hip.h) ---------------------------------------------
 // energy[b, t] = the mean square of the F0 frame t of utterance b (a wave per frame); frames in [T_b, T_max) are written 0
 struct EnergyP {

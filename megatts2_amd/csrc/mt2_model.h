@@ -252,6 +252,8 @@ struct mt2_model {
     std::map<std::pair<int, int>, float*> mcd_tables;
     // declipping tables (declip.hip) by frame length N: twiddles and window in double, built and uploaded on first use
     std::map<int, double*> dc_tables;
+    // formant windows (formants.hip) by (W, kind), in double: built and uploaded on first use
+    std::map<std::pair<int, int>, double*> fm_windows;
 
     bool profiling = false;
     std::vector<std::string> stage_names;

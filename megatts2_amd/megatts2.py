@@ -22,6 +22,7 @@ from . import config as cfgmod
 from . import weights
 from .config import HIFIGAN_HOP_LENGTH, HIFIGAN_SR
 from .runtime import DECLIP_NAMES, DENOISE_NAMES, PAUSES_NAMES, WPE_NAMES, Declip, Denoise, Dereverb, Limiter, NativeError, NativeModel, Pauses  # noqa: F401  (Limiter, Denoise, Dereverb, Declip, Pauses: arguments of synthesize / forward)
+from .runtime import FORMANT_STAT_NAMES, Formants, resample_query
 from .sampling import PLMSampling, seed_array
 
 
@@ -118,6 +119,66 @@ def pitch_stats(f0, frame_lens=None) -> Dict[str, np.ndarray]:
     x = (x if x.dim() == 2 else x.unsqueeze(0)).to("cuda", torch.float32)
     st = _frontend().f0_stats(x, frame_lens).cpu().numpy()
     return {k: st[:, i].copy() for i, k in enumerate(PITCH_STATS)}
+
+
+def extract_formants(samples, sample_rate: Optional[int] = None, lens=None, formants: Optional[Formants] = None):
+    """Formant candidates of a 1-D waveform (16 kHz, or at sample_rate) on the mel's frames: linear prediction on the GPU by the rule of
+    csrc/formants.hip (MelFrontEnd.formants; no reference counterpart, parity with Praat's Burg fit and quality on real speech
+    unpinned).  formants: a `Formants` (defaults: 5.5 kHz ceiling, order 10, 50 ms Hann, pre-emphasis from 50 Hz).  The audio is
+    resampled on the GPU to 2 * max_formant_hz (11 kHz: MelFrontEnd.resample's rule) - not at all when that is its own rate - and
+    analysed there with the hop hop_length * rate / 16000 (176), which must be a whole number of samples (ValueError otherwise, never
+    rounded), so that frame t is centred where mel frame t of the same audio at 16 kHz is.  -> dict: "freq", "bw" f32 [T, 5] in Hz,
+    "count" int32 [T] (device), T = 1 + L16 // hop_length for the L16 samples the audio has at 16 kHz - the mel's frame count, so
+    freq[t], extract_f0's f0[t] and mel frame t coincide (the resampled audio can hold one frame more, which is dropped: the three tensors are then views of the wider rows, not
+    contiguous); "frame_lens"
+    (host int32 [B]), "rate", "hop".  A [B, L] input (lens: the rows' lengths) gives [B, T, ...]; frames behind a row's own are zeros."""
+    import torch
+    fe = _frontend()
+    cfg = formants or Formants()
+    x = samples if hasattr(samples, "is_cuda") else torch.as_tensor(np.asarray(samples, np.float32))
+    batched = x.dim() == 2
+    x = (x if batched else x.unsqueeze(0)).to("cuda", torch.float32)
+    B, L = x.shape
+    sr_in = fe.audio.sample_rate if sample_rate is None else int(sample_rate)
+    ln = np.full(B, L, np.int32) if lens is None else np.asarray(lens, np.int32).reshape(-1)
+    rate = cfg.rate()
+    if (fe.audio.hop_length * rate) % fe.audio.sample_rate:
+        raise ValueError(f"the mel's hop of {fe.audio.hop_length} samples at {fe.audio.sample_rate} Hz is not a whole number of samples at {rate} Hz: "
+                         "choose max_formant_hz so that hop_length * 2 * max_formant_hz / 16000 is an integer (5500, 5000, 4000)")
+    hop = fe.audio.hop_length * rate // fe.audio.sample_rate
+    # the mel's frames: of the audio as it is at the mel's rate
+    l16 = ln if sr_in == fe.audio.sample_rate else np.asarray([resample_query(sr_in, fe.audio.sample_rate, int(n))[0] for n in ln], np.int64)
+    frame_lens = (1 + l16 // fe.audio.hop_length).astype(np.int32)
+    if sr_in != rate:
+        x, ln = fe.resample(x, sr_in, ln, sr_out=rate)
+    T = int(frame_lens.max())
+    # rows wide enough for both frame counts: the analysed audio can hold one frame more than the mel (L = 256 k - 1), and behind two
+    # different resamplings one less, which then is an empty frame
+    rows = max(T, 1 + int(np.max(ln)) // hop)
+    res = fe.formants(x, ln, cfg, hop=hop, sample_rate=rate, out=torch.empty(B, rows, 5, device=x.device, dtype=torch.float32))
+    out = {k: v[:, :T] for k, v in res.items()}
+    if not batched:
+        out = {k: v[0] for k, v in out.items()}
+    out.update(frame_lens=frame_lens, rate=rate, hop=hop)
+    return out
+
+
+def formant_stats(freq, count, f0=None, frame_lens=None) -> Dict[str, np.ndarray]:
+    """The per-utterance formant figures of candidate tracks freq [T, 5] / [B, T, 5] and count [T] / [B, T] (extract_formants') over
+    the frames with at least four candidates among the first frame_lens[b] - the voiced ones (f0 > 0) where an F0 track of the same
+    frames is given (MelFrontEnd.formant_stats: double sums on the GPU) -> dict of float64 numpy arrays [B] (FORMANT_STAT_NAMES): frames,
+    share, f1 .. f4 (means, Hz), f1_sigma .. f4_sigma, dispersion ((f4 - f1) / 3, Hz), vtl_cm (the length of a uniform tube closed at
+    one end with these means; 17.5 for 500 / 1500 / 2500 / 3500 Hz).  Without such a frame every entry is 0.  Two voices compare by
+    the ratio of their vtl_cm, whatever the text."""
+    import torch
+
+    def dev(a, dims, dtype):
+        if a is None:
+            return None
+        t = a if hasattr(a, "is_cuda") else torch.as_tensor(np.asarray(a))
+        return (t if t.dim() == dims else t.unsqueeze(0)).to("cuda", dtype).contiguous()
+    st = _frontend().formant_stats(dev(freq, 3, torch.float32), dev(count, 2, torch.int32), dev(f0, 2, torch.float32), frame_lens).cpu().numpy()
+    return {k: st[:, i].copy() for i, k in enumerate(FORMANT_STAT_NAMES)}
 
 
 def extract_energy(samples, sample_rate: Optional[int] = None, trim_db: Optional[float] = None, **kw):
@@ -887,6 +948,34 @@ class Megatts:
         energy = fe.energy(x, lens)
         return {"phones": phone_prosody(f0, dur, energy, phone_lens, ml), "durations": duration_stats(dur, phone_lens), "f0": f0,
                 "energy": energy, "frame_lens": ml}
+
+    def output_formants(self, mel_lens, aux, tracker: str = "yin", formants: Optional[Formants] = None):
+        """The formant figures of a synthesis call's own output: `mel_lens` and `aux` as `synthesize(..., return_aux=True)` returned
+        them with a vocoder on.  The inference padding is taken off as `output_prosody` takes it off; the audio is tracked for F0
+        (tracker "yin" or "viterbi") and analysed by `extract_formants` (formants: a `Formants`), and the figures are taken over the
+        voiced frames with four candidates among the first mel_lens[b] -> formant_stats' dict (FORMANT_STAT_NAMES, float64 [B]) with
+        "freq", "bw", "count", "f0" (device, [B, T, ...]) and "frame_lens" beside it.  `aux` is not altered."""
+        if tracker not in ("yin", "viterbi"):
+            raise ValueError("tracker must be 'yin' or 'viterbi'")
+        wav = aux.get("wav")
+        if wav is None:
+            raise ValueError("aux has no audio: synthesize with vocoder=True or griffin_lim=True")
+        fe = _frontend()
+        hop = fe.audio.hop_length
+        ml = np.asarray(mel_lens, np.int32).reshape(-1)
+        top = int(ml.max())
+        pad = int(getattr(self.hifi_gan.cfg, "inference_padding", 0)) if self.hifi_gan is not None else 0
+        if self.hifi_gan is not None and wav.shape[1] >= (top + 2 * pad) * hop:      # HiFi-GAN: (mel_lens + 2 pad) hop samples a row
+            x, lens = wav[:, pad * hop:(pad + top) * hop].contiguous(), ml * hop
+        else:                                                                         # Griffin-Lim: (mel_lens - 1) hop samples
+            x, lens = wav, (ml - 1) * hop
+        f0 = (fe.f0 if tracker == "yin" else fe.f0_track)(x, lens)
+        res = extract_formants(x, None, lens, formants)
+        T = min(f0.shape[1], res["count"].shape[1])
+        fl = np.minimum(np.minimum(ml, res["frame_lens"]), T).astype(np.int32)
+        out = formant_stats(res["freq"][:, :T], res["count"][:, :T], f0[:, :T], fl)
+        out.update(freq=res["freq"], bw=res["bw"], count=res["count"], f0=f0, frame_lens=fl)
+        return out
 
     def align_prompt(self, prompt_phone_tokens, mels, prompt_phone_lens=None, mel_lens=None, return_aux: bool = False):
         """The phone-level alignment of a prompt utterance to its own phones, made by the model itself - the `prompt_durations` of

@@ -144,6 +144,52 @@ class MT2DeclipConfig(C.Structure):
 DECLIP_NAMES = ("clipped", "hi", "lo", "share", "frames_iterated", "mean_iterations", "max_iterations", "power_change_db")
 
 
+class MT2FormantConfig(C.Structure):
+    _fields_ = [("window", C.c_int32), ("order", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32), ("preemphasis_hz", C.c_double),
+                ("fmin_hz", C.c_double), ("max_bandwidth_hz", C.c_double)]
+
+
+FORMANT_MAX, FORMANT_MAX_WINDOW, FORMANT_MAX_ORDER, FORMANT_MAX_ITERS, FORMANT_STAT_FIELDS = 5, 1024, 32, 64, 12      # MT2_FORMANT_*
+FORMANT_WINDOWS = {"hann": 0, "rect": 1}      # MT2_FORMANT_HANN, MT2_FORMANT_RECT
+FORMANT_STAT_NAMES = ("frames", "share", "f1", "f2", "f3", "f4", "f1_sigma", "f2_sigma", "f3_sigma", "f4_sigma", "dispersion", "vtl_cm")
+
+
+@dataclasses.dataclass(frozen=True)
+class Formants:
+    """The settings of the formant candidates by linear prediction (csrc/formants.hip; the rule is in include/megatts2_hip.h): the audio
+    is analysed at 2 * `max_formant_hz` (5500 for an adult female voice, 5000 for a male one, as Praat advises) in frames of `window_ms`
+    under a `window` ("hann" or "rect"), behind a pre-emphasis from `preemphasis_hz` up (0: off), by an all-pole fit of `order`
+    coefficients (even; two per expected formant and two to spare).  A root of the fit is a candidate when its frequency lies more than
+    `fmin_hz` inside (0, rate / 2) and its bandwidth under `max_bandwidth_hz`.  The fit is the autocorrelation method, not Praat's
+    Burg; on a voiced frame it is drawn to strong harmonics (a property of linear prediction)."""
+    max_formant_hz: float = 5500.0
+    order: int = 10
+    window_ms: float = 50.0
+    preemphasis_hz: float = 50.0
+    fmin_hz: float = 50.0
+    max_bandwidth_hz: float = 500.0
+    window: str = "hann"
+
+    def rate(self) -> int:
+        """the rate the audio is analysed at, 2 * max_formant_hz, which must be a whole number of Hz"""
+        r = 2.0 * float(self.max_formant_hz)
+        if not (math.isfinite(r) and r >= 1.0 and r == int(r)):
+            raise ValueError("2 * max_formant_hz must be a whole number of Hz, at least 1")
+        return int(r)
+
+    def window_samples(self, sample_rate: int) -> int:
+        """W at sample_rate: window_ms * sample_rate / 1000 rounded down to even"""
+        if not math.isfinite(float(self.window_ms)):
+            raise ValueError("window_ms is not finite")
+        return int(float(self.window_ms) * int(sample_rate) / 1000.0) // 2 * 2
+
+    def c_struct(self, sample_rate: int) -> MT2FormantConfig:
+        if self.window not in FORMANT_WINDOWS:
+            raise ValueError('window must be "hann" or "rect"')
+        return MT2FormantConfig(self.window_samples(sample_rate), int(self.order), FORMANT_WINDOWS[self.window], 0, float(self.preemphasis_hz),
+                                float(self.fmin_hz), float(self.max_bandwidth_hz))
+
+
 class MT2SegmentsConfig(C.Structure):
     _fields_ = [("top_db", C.c_float), ("min_pause", C.c_int32), ("min_speech", C.c_int32), ("pad", C.c_int32), ("keep", C.c_int32)]
 
@@ -294,6 +340,10 @@ def load_library():
     lib.mt2_f0_track_query.argtypes = [C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_longlong, C.c_int] + [C.c_void_p] * 5
     lib.mt2_f0_track.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 5 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
     lib.mt2_f0_stats.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_formant_query.argtypes = [C.c_int] * 4 + [C.c_longlong, C.c_void_p, C.c_void_p]
+    lib.mt2_formant_window.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_lpc_formants.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5
+    lib.mt2_formant_stats.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
     lib.mt2_frame_energy.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_phone_prosody.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.mt2_pitch_contour.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
@@ -746,6 +796,67 @@ def _cut_pauses(lib, h, wav, lens=None, pauses=None, sample_rate: int = 16000, k
     if return_figures:
         res += (fig,)
     return res
+
+
+def _formant_cfg(cfg, sample_rate: int) -> MT2FormantConfig:
+    """a `Formants` (its window in samples at sample_rate; max_formant_hz is extract_formants' affair), None (its defaults) or an
+    MT2FormantConfig as it stands"""
+    if isinstance(cfg, MT2FormantConfig):
+        return cfg
+    return (cfg or Formants()).c_struct(sample_rate)
+
+
+def _formants(lib, h, wav, lens=None, cfg=None, hop: int = 256, sample_rate: int = 16000, return_lpc: bool = False, return_err: bool = False,
+              return_autocorr: bool = False, return_roots: bool = False, return_iters: bool = False, out=None):
+    """mt2_lpc_formants on the handle `h`: wav f32 [B, L] (device, at sample_rate; nothing is resampled) -> dict of device tensors: freq
+    and bw f32 [B, T, 5] (Hz; the candidates of every frame in ascending frequency, zeros behind count), count int32 [B, T], with T =
+    1 + max lens // hop; frames behind an utterance's own 1 + lens[b] // hop hold zeros.  At the mel's hop and rate freq[b, t] belongs
+    to mel frame t.  On request lpc f64 [B, T, P + 1], err f64 [B, T], autocorr f64 [B, T, P + 1], roots complex128 [B, T, P] and iters
+    int32 [B, T] (-1: an empty frame).  out: a contiguous f32 [B, T', 5] (or [B, 5 T']) device tensor to write freq into, T' >= T; every
+    other output then has T' rows.  Samples at or beyond lens[b] are never read.  The call only enqueues (the first one with a new
+    window uploads its table)."""
+    import torch
+    wav, ln, B, L = _wav_lens(wav, lens)
+    hop, sr = int(hop), int(sample_rate)
+    c = _formant_cfg(cfg, sr)
+    if out is not None:
+        assert out.is_contiguous() and out.numel() % (B * FORMANT_MAX) == 0
+        out = out.view(B, -1)
+    freq = _out_rows(out, B, wav, lambda: FORMANT_MAX * (1 + max(int(ln.max()), 0) // max(hop, 1)))
+    T, P, dev = freq.shape[1] // FORMANT_MAX, int(c.order), wav.device
+    assert freq.shape[1] == T * FORMANT_MAX
+    res = {"freq": freq.view(B, T, FORMANT_MAX), "bw": torch.empty(B, T, FORMANT_MAX, device=dev, dtype=torch.float32),
+           "count": torch.empty(B, T, device=dev, dtype=torch.int32)}
+    if return_lpc:
+        res["lpc"] = torch.empty(B, T, P + 1, device=dev, dtype=torch.float64)
+    if return_err:
+        res["err"] = torch.empty(B, T, device=dev, dtype=torch.float64)
+    if return_autocorr:
+        res["autocorr"] = torch.empty(B, T, P + 1, device=dev, dtype=torch.float64)
+    roots = torch.empty(B, T, max(P, 0), 2, device=dev, dtype=torch.float64) if return_roots else None
+    if return_iters:
+        res["iters"] = torch.empty(B, T, device=dev, dtype=torch.int32)
+    _check(lib.mt2_lpc_formants(h, _stream(), _ptr(wav), _iptr(ln), L, B, sr, hop, C.byref(c), _ptr(res["freq"]), _ptr(res["bw"]),
+                                _ptr(res["count"]), T, _ptr(res.get("lpc")), _ptr(res.get("err")), _ptr(res.get("autocorr")), _ptr(roots),
+                                _ptr(res.get("iters"))))
+    if roots is not None:
+        res["roots"] = torch.view_as_complex(roots)
+    return res
+
+
+def _formant_stats(lib, h, freq, count, f0, ln):
+    """mt2_formant_stats on the handle `h`: freq f32 [B, T, 5], count int32 [B, T][, f0 f32 [B, T]] (device), ln int32 [B] -> float64
+    [B, 12] (device; FORMANT_STAT_NAMES)."""
+    import torch
+    assert freq.is_cuda and freq.dim() == 3 and freq.shape[2] == FORMANT_MAX and count.is_cuda and count.shape == freq.shape[:2]
+    freq, count = freq.contiguous().to(torch.float32), count.contiguous().to(torch.int32)
+    B, T = count.shape
+    if f0 is not None:
+        assert f0.is_cuda and f0.shape == count.shape
+        f0 = f0.contiguous().to(torch.float32)
+    stats = torch.empty(B, FORMANT_STAT_FIELDS, device=freq.device, dtype=torch.float64)
+    _check(lib.mt2_formant_stats(h, _stream(), _ptr(freq), _ptr(count), _ptr(f0), _iptr(ln), T, B, _ptr(stats)))
+    return stats
 
 
 def _workspace_fill(lib, h, byte: int) -> None:
@@ -1206,6 +1317,18 @@ class NativeModel:
         """wav f32 [B, L] with its pauses (or with keep = "pauses" its speech) cut out (`_cut_pauses`)."""
         return _cut_pauses(self.lib, self.h, wav, lens, pauses, sample_rate, keep, out, return_segments, return_figures)
 
+    # ---- formant candidates by linear prediction and the formant figures (csrc/formants.hip) on the model's handle, as MelFrontEnd's
+    def formants(self, wav, lens=None, cfg=None, hop: Optional[int] = None, sample_rate: Optional[int] = None, return_lpc: bool = False,
+                 return_err: bool = False, return_autocorr: bool = False, return_roots: bool = False, return_iters: bool = False, out=None):
+        """The formant candidates of wav f32 [B, L] at sample_rate (default 16000; hop default 256) (`_formants`) -> dict: freq, bw, count
+        [, lpc, err, autocorr, roots, iters]."""
+        return _formants(self.lib, self.h, wav, lens, cfg, 256 if hop is None else hop, 16000 if sample_rate is None else sample_rate,
+                         return_lpc, return_err, return_autocorr, return_roots, return_iters, out)
+
+    def formant_stats(self, freq, count, f0=None, frame_lens=None):
+        """The formant figures float64 [B, 12] (device; FORMANT_STAT_NAMES) of candidate tracks (`_formant_stats`)."""
+        return _formant_stats(self.lib, self.h, freq, count, f0, self._lens(frame_lens, count.shape[0], count.shape[1]))
+
     # ---- de-reverberation by weighted prediction error (csrc/wpe.hip) on the model's handle, as MelFrontEnd's
     def dereverb(self, wav, lens=None, dereverb: Optional[Dereverb] = None, return_figures: bool = False, out=None, audio=None):
         """De-reverberated audio of wav f32 [B, L] (`_dereverb`)."""
@@ -1406,16 +1529,18 @@ class MelFrontEnd:
         _check(self.lib.mt2_mel_spectrogram(self.h, _stream(), C.byref(self.ac), _ptr(wav), _iptr(ln), L, B, _ptr(mel), T))
         return mel
 
-    def resample(self, wav, sr_in: int, lens=None, normalize: bool = False, out=None):
+    def resample(self, wav, sr_in: int, lens=None, normalize: bool = False, out=None, sr_out: Optional[int] = None):
         """`librosa.load(wav, sr=audio.sample_rate)` of the reference (models/megatts2.py:335) for a ragged batch on the device, by the
         rule of csrc/resample.hip (parity with librosa's soxr filter is unpinned): wav f32 [B, L] (device) at sr_in ->
         (f32 [B, max L_out], out_lens int32 [B]) with L_out = ceil(n * L / o), zeros beyond out_lens[b]; samples beyond lens[b] are
         never read.  normalize: each utterance divided by its peak as well (:336).  out: a contiguous f32 [B, >= max L_out] device
-        tensor to write into.  sr_in == audio.sample_rate is an error: there is nothing to resample."""
+        tensor to write into.  sr_in == audio.sample_rate is an error: there is nothing to resample.  sr_out (None: audio.sample_rate):
+        another rate to resample to, by the same rule - the formant analysis runs at 11 kHz."""
         wav, ln, B, L = _wav_lens(wav, lens)
-        out = _out_rows(out, B, wav, lambda: resample_query(sr_in, self.audio.sample_rate, int(ln.max()))[0])
+        sr_out = self._rate(sr_out)
+        out = _out_rows(out, B, wav, lambda: resample_query(sr_in, sr_out, int(ln.max()))[0])
         out_lens = np.zeros(B, np.int32)
-        _check(self.lib.mt2_resample(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, int(sr_in), self.audio.sample_rate,
+        _check(self.lib.mt2_resample(self.h, _stream(), _ptr(wav), _iptr(ln), L, B, int(sr_in), sr_out,
                                      MT2_RESAMPLE_NORMALIZE if normalize else 0, _ptr(out), out.shape[1], _iptr(out_lens)))
         return out, out_lens
 
@@ -1593,6 +1718,30 @@ class MelFrontEnd:
         stats = torch.empty(B, 6, device=f0.device, dtype=torch.float64)
         _check(self.lib.mt2_f0_stats(self.h, _stream(), _ptr(f0), _iptr(ln), T, B, _ptr(stats)))
         return stats
+
+    # ---- formant candidates by linear prediction and the formant figures (csrc/formants.hip)
+    def formants(self, wav, lens=None, cfg=None, hop: Optional[int] = None, sample_rate: Optional[int] = None, return_lpc: bool = False,
+                 return_err: bool = False, return_autocorr: bool = False, return_roots: bool = False, return_iters: bool = False, out=None):
+        """Formant candidates of a ragged batch by linear prediction, the rule of csrc/formants.hip / include/megatts2_hip.h (no reference
+        counterpart; parity with Praat's Burg fit and quality on real speech are unpinned): wav f32 [B, L] (device) at sample_rate
+        (default audio.sample_rate; nothing is resampled - `megatts2.extract_formants` does that) -> dict of device tensors (`_formants`):
+        freq and bw f32 [B, T, 5] in Hz, the candidates of every frame in ascending frequency with zeros behind count int32 [B, T]; T = 1 +
+        max lens // hop, hop defaulting to the mel front-end's, so that at the mel's rate freq[b, t] belongs to mel frame t.  cfg: a
+        `Formants` (defaults: order 10, 50 ms Hann, pre-emphasis from 50 Hz) or an MT2FormantConfig in samples.  The extras on request:
+        lpc, err, autocorr (float64), roots (complex128 [B, T, order]), iters (int32; -1 marks an empty frame).  out: a contiguous f32
+        [B, T', 5] device tensor for freq, T' >= T.  Candidates are per frame; nothing tracks a formant across frames.  The call only
+        enqueues."""
+        return _formants(self.lib, self.h, wav, lens, cfg, self.audio.hop_length if hop is None else hop, self._rate(sample_rate), return_lpc,
+                         return_err, return_autocorr, return_roots, return_iters, out)
+
+    def formant_stats(self, freq, count, f0=None, frame_lens=None):
+        """The formant figures of candidate tracks freq f32 [B, T, 5], count int32 [B, T] (device, from `formants`) over the frames with
+        at least four candidates among the first frame_lens[b] - and, where an F0 track f0 f32 [B, T] of the same frames is given, the
+        voiced ones (f0 > 0) among them -> float64 [B, 12] (device; FORMANT_STAT_NAMES): frames used, their share, the means and sigmas
+        of F1 .. F4 in Hz, the formant dispersion (F4 - F1) / 3 of the means, and the vocal-tract length in cm of a uniform tube closed
+        at one end with these means (17.5 cm for 500 / 1500 / 2500 / 3500 Hz).  All zeros without such a frame.  Sums in double, two
+        passes.  The call only enqueues."""
+        return _formant_stats(self.lib, self.h, freq, count, f0, self._frame_lens(frame_lens, count.shape[0], count.shape[1]))
 
     # ---- per-phone prosody (csrc/prosody.hip)
     def energy(self, wav, lens=None, hop: Optional[int] = None, out=None):
@@ -2555,6 +2704,21 @@ def f0_query(L: int, sample_rate: int = 16000, hop: int = 256, fmin: float = 62.
     _check(load_library().mt2_f0_query(int(sample_rate), int(hop), float(fmin), float(fmax), int(L), C.byref(f), C.byref(lo), C.byref(hi),
                                        C.byref(ws)))
     return f.value, lo.value, hi.value, ws.value
+
+
+def formant_query(L: int, sample_rate: int = 11000, hop: int = 176, window: int = 550, order: int = 10):
+    """mt2_formant_query (no device needed) -> (frames, workspace_bytes): T = 1 + L // hop and the arena bytes of one `formants` call
+    (4 * 65535 rounded up to 256, whatever the batch); NativeError where the rule refuses."""
+    f, ws = C.c_int(0), C.c_longlong(0)
+    _check(load_library().mt2_formant_query(int(sample_rate), int(hop), int(window), int(order), int(L), C.byref(f), C.byref(ws)))
+    return f.value, ws.value
+
+
+def formant_window(window: int, kind: str = "hann") -> np.ndarray:
+    """mt2_formant_window (no device needed) -> float64 [window]: the table the device applies; NativeError where the rule refuses."""
+    w = np.empty(max(int(window), 1), np.float64)
+    _check(load_library().mt2_formant_window(int(window), FORMANT_WINDOWS.get(kind, -1), w.ctypes.data_as(C.c_void_p)))
+    return w
 
 
 def f0_track_query(L: int, B: int = 1, sample_rate: int = 16000, hop: int = 256, fmin: float = 62.5, fmax: float = 500.0,

@@ -101,6 +101,13 @@ def main() -> None:
     ap.add_argument("--max-formant", type=float, default=5500.0, metavar="HZ",
                     help="with --report-formants: the formant ceiling; the audio is analysed at twice this rate (5500 for a female voice, 5000 for a male one)")
     ap.add_argument("--lpc-order", type=int, default=10, metavar="P", help="with --report-formants: the order of the all-pole fit, even, 2 to 32 (default 10)")
+    ap.add_argument("--track-formants", action="store_true",
+                    help="with --report-formants: track the candidates across frames first (a Viterbi pass on the GPU: of every frame's candidates "
+                         "those on the cheapest smooth path), so that one spurious root does not shift every formant above it; also prints the "
+                         "share of frames where the tracked selection differs from the first K candidates")
+    ap.add_argument("--formant-tracks", type=int, default=4, metavar="K", help="with --track-formants: the number of tracks, 1 to 5 (default 4; the figures need 4)")
+    ap.add_argument("--formant-jump-cost", type=float, default=1.0, metavar="X",
+                    help="with --track-formants: the cost of a relative change of a track between frames (default 1; 0: every frame on its own)")
     ap.add_argument("--reference-wav", metavar="PATH",
                     help="a recording of the same sentence: print the mel-cepstral distortion (dB, along the DTW path of the cepstra), the largest "
                          "cell, and F0 RMSE, register offset and voiced / unvoiced error along the same path, of the generated audio against it")
@@ -261,20 +268,31 @@ def main() -> None:
         path = sorted(glob.glob(f"{a.wavs_dir}/*.wav"))[0]
         y, sr = audio_io.read_wav(path)
         f0 = M.extract_f0(y, sr, method=a.pitch_tracker)
-        tr = M.extract_formants(y, sr, formants=fm)
+        ft = M.FormantTrack(tracks=a.formant_tracks, jump_cost=a.formant_jump_cost) if a.track_formants else None
+        fk, ck = ("track_freq", "track_count") if ft else ("freq", "count")
+        tr = M.extract_formants(y, sr, formants=fm, track=ft)
         n = min(int(f0.shape[0]), int(tr["count"].shape[0]))
-        report = [(f"first prompt ({path})", M.formant_stats(tr["freq"][:n], tr["count"][:n], f0[:n], [min(n, int(tr["frame_lens"][0]))]))]
+        report = [(f"first prompt ({path})", M.formant_stats(tr[fk][:n], tr[ck][:n], f0[:n], [min(n, int(tr["frame_lens"][0]))]), tr)]
         if wrote:          # the generated audio alone, as the vocoder left it on the device - not the written file (prompt in front)
-            report.append(("generated audio", tts.output_formants(lens, aux, tracker=a.pitch_tracker, formants=fm)))
-        for what, st in report:
+            g = tts.output_formants(lens, aux, tracker=a.pitch_tracker, formants=fm, track=ft)
+            report.append(("generated audio", g, {k: v[0] for k, v in g.items() if k in ("sel", "track_count")}))
+        for what, st, _ in report:
             print(f"formants of the {what}: {int(st['frames'][0])} voiced frames with four candidates ({100 * float(st['share'][0]):.1f} %), " +
                   ", ".join(f"F{k} {float(st[f'f{k}'][0]):.0f} +- {float(st[f'f{k}_sigma'][0]):.0f} Hz" for k in range(1, 5)) +
                   f", dispersion {float(st['dispersion'][0]):.0f} Hz, vocal-tract length {float(st['vtl_cm'][0]):.2f} cm")
-        if len(report) == 2 and all(float(st["frames"][0]) > 0 for _, st in report):
+        if ft:
+            for what, _, t in report:
+                on = t["track_count"] > 0
+                first = list(range(a.formant_tracks))
+                moved = ((t["sel"][..., :a.formant_tracks] != t["sel"].new_tensor(first)).any(-1) & on).sum()
+                print(f"formant tracks of the {what}: {int(on.sum())} tracked frames, on {100 * float(moved) / max(int(on.sum()), 1):.1f} % of them "
+                      f"the {a.formant_tracks} tracks are not the first {a.formant_tracks} candidates (jump cost {a.formant_jump_cost:g})")
+        if len(report) == 2 and all(float(st["frames"][0]) > 0 for _, st, _ in report):
             p, g = report[0][1], report[1][1]
             print(f"generated against the prompt: vocal-tract length ratio {float(g['vtl_cm'][0]) / float(p['vtl_cm'][0]):.3f}, " +
                   ", ".join(f"F{k} {100 * (float(g[f'f{k}'][0]) / float(p[f'f{k}'][0]) - 1):+.1f} %" for k in range(1, 5)) +
-                  " (LPC by the autocorrelation method at order " + f"{a.lpc_order}, {a.max_formant:g} Hz ceiling; per-frame candidates, untracked)")
+                  " (LPC by the autocorrelation method at order " + f"{a.lpc_order}, {a.max_formant:g} Hz ceiling; per-frame candidates, " +
+                  ("tracked across frames)" if ft else "untracked)"))
     if a.report_prosody:
         import glob
         import math

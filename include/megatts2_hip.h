@@ -874,8 +874,8 @@ int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/
  * tube closed at one end; Wakita 1977, Reby & McComb 2003) - a timbre measure that, unlike mt2_mel_cepstral_distortion, needs no
  * recording of the same sentence.  No reference counterpart.  The fit is the AUTOCORRELATION method; parity with Praat (Burg's method,
  * Gaussian window) is unpinned, and so is quality on real speech; the rule is our own statement, restated in tests/formant_ref.py,
- * and the tests hold the kernel to it and to the poles of known all-pole filters.  Candidates are per frame: nothing tracks a formant
- * across frames, so candidate q of one frame need not be candidate q of the next.
+ * and the tests hold the kernel to it and to the poles of known all-pole filters.  Candidates are per frame: candidate q of one frame
+ * need not be candidate q of the next - mt2_formant_track (below) connects them.
  * THE RULE, for one utterance x f32 [L] at sample_rate, a hop, an even window W in [64, 1024] and an even order P in [2, 32], P < W:
  *  1 frames  T = 1 + L / hop.  Frame t covers the samples i = s + j, s = hop t - W / 2, j = 0 .. W - 1.  A sample outside [0, L) is a
  *            zero by its index and is never read.  At hop = the mel's and the mel's rate, frame t is centred like mel frame t.
@@ -916,7 +916,7 @@ int mt2_pitch_contour(mt2_model* m, void* stream, const float* f0 /*[B, T_max]*/
  * lens[b] / hop; a NULL or misaligned buffer; an output overlapping wav or another output.
  * Limits: LPC on a voiced frame fits the harmonics as well as the envelope - a formant near a strong harmonic is drawn to it (F1 of a
  * 700 Hz resonance under 110 Hz pulses reads about 764 Hz, by the 7th harmonic): a property of linear prediction, not of the kernel.
- * Out of scope: Burg's method; tracking across frames (Viterbi over candidates); LPC-cepstral distortion; line spectral frequencies;
+ * Out of scope: Burg's method; LPC-cepstral distortion; line spectral frequencies;
  * nasal / anti-formant models; a streaming form; multichannel.
  *
  * THE FIGURES, mt2_formant_stats: over the frames t < frame_lens[b] with count[t] >= 4, and f0[t] > 0 where an F0 track is given, all
@@ -960,6 +960,57 @@ int mt2_lpc_formants(mt2_model* m, void* stream, const float* wav /*[B, L_max]*/
  * outside [1, T_max]; a NULL or misaligned buffer; stats overlapping an input. */
 int mt2_formant_stats(mt2_model* m, void* stream, const float* freq /*[B, T_max, 5]*/, const int32_t* count /*[B, T_max]*/,
                       const float* f0 /*or NULL*/, const int32_t* frame_lens /*host*/, int T_max, int B, double* stats /*[B, 12]*/);
+
+/* ---- Formant tracks across frames (csrc/formant_track.hip): of the candidates of mt2_lpc_formants, the K per frame that form the cheapest
+ * smooth path through the utterance, by a Viterbi pass in the manner of Praat's "Formant: Track" (Xia & Espy-Wilson 2000) with a rule of
+ * our own.  No reference counterpart.  The outputs have the candidates' own layout, so mt2_formant_stats reads them unchanged: one spurious
+ * root no longer shifts every formant above it by one slot.  Parity with Praat's tracker is unpinned, and so is quality on real speech; the
+ * rule is restated in tests/formant_track_ref.py, and the tests hold the kernel to it to the bit and to the truth of a synthetic scene.
+ * THE RULE, for one utterance freq, bw f32 [T, 5], count int32 [T], K = tracks in [1, 5], ref_hz[0 .. K), freq_cost, bw_cost, jump_cost:
+ * everything in DOUBLE, every operation rounded on its own, no fma; the f32 inputs convert exactly; there is no transcendental function, so
+ * a numpy restatement reproduces every cost, and hence every decision, to the bit.
+ *  states    the C(5, K) strictly increasing K-tuples of candidate indices from {0 .. 4} in lexicographic order, at most
+ *            MT2_FORMANT_TRACK_STATES = 10.  State s assigns candidate st[s][q] to track q.  The table does not depend on the frame.
+ *  gap       n = min(count[t], 5).  Frame t is a GAP if n < K, or if among its first n candidates a freq is not finite or <= 0 or a bw is
+ *            not finite or < 0.  State s is valid in a non-gap frame iff st[s][K - 1] < n; state 0 always is.
+ *  local     of a valid state:  term_q = (freq_cost * (|f - ref_q| / 1000)) + (bw_cost * (b / f)) with f, b the candidate of track q;
+ *            o[t, s] = term_0 + term_1 + ..., q ascending, left to right.  An invalid state has o = +inf.
+ *  jump      between non-gap frames t - 1 and t:  u_q = (2 * |f' - f|) / (f' + f), f the candidate of track q under state j at t - 1
+ *            and f' under state k at t;  tr(j, k) = jump_cost * (u_0 + u_1 + ...), q ascending.
+ *  forward   t = 0 or frame t - 1 a gap:  delta[t, k] = o[t, k], psi[t, k] = 0.  Otherwise best = min_j (delta[t - 1, j] + tr(j, k)) over
+ *            the j with finite delta[t - 1, j], j ascending with a strict < from +inf (the smallest j wins a tie), psi[t, k] that j,
+ *            delta[t, k] = o[t, k] + best; an invalid k has delta = +inf, psi = 0.  Costs are not renormalised: in double the sums stay
+ *            exact enough for any clip the call accepts.  In a gap frame delta[t, k] = 0 for every k and psi[t, k] is the smallest j
+ *            attaining min delta[t - 1, .] (0 at t = 0): a gap cuts the utterance into segments that are tracked independently.
+ *  backward  k*[T - 1] = the smallest k attaining min delta[T - 1, .];  k*[t - 1] = psi[t, k*[t]].
+ *  outputs   a non-gap frame:  sel[t][q] = st[k*[t]][q] for q < K and -1 behind;  track_freq[t][q], track_bw[t][q] = the selected
+ *            candidate's freq and bw, copied bit for bit, zeros behind;  track_count[t] = K.  A gap frame, and a frame in [T_b, T_max):
+ *            sel all -1, track_freq and track_bw zeros, track_count 0.
+ * jump_cost = 0 makes the frames independent: each picks its own arg-min of o.  Nothing depends on the batch slot or T_max: a ragged
+ * batch is bit-identical to its utterances alone.  A non-finite input cannot fault and cannot write outside the outputs; it turns its frame
+ * into a gap, which may change the path elsewhere in the same utterance, as in mt2_f0_track.
+ * Refused on the host (error, nothing launched, every output as it was): B < 1 or > 65535; a frame_lens[b] outside [1, T_max]; tracks
+ * outside [1, 5]; reserved not 0; a non-finite or non-positive ref_hz among the first K; a non-finite or negative cost; a NULL or
+ * misaligned buffer (sel may be NULL); an output overlapping an input or another output.
+ * Out of scope: a track that may be absent in some frames (every non-gap frame carries all K); an unvoiced state; a streaming form. */
+#define MT2_FORMANT_TRACK_STATES 10
+typedef struct mt2_formant_track_config {   /* 72 bytes, no padding */
+    int32_t tracks;      /* K in [1, 5];  4 */
+    int32_t reserved;    /* 0 */
+    double ref_hz[5];    /* finite, > 0, the first K used;  550 1650 2750 3850 4950 */
+    double freq_cost, bw_cost, jump_cost;   /* finite, >= 0;  1 1 1 */
+} mt2_formant_track_config;
+/* Host only, no HIP call; outputs may be NULL.  states = C(5, tracks);  workspace_bytes = the arena high water of one mt2_formant_track
+ * call exactly: r(4 * 65535) + r(16 * B * T_max), r rounding up to 256 - the lengths in the room of the largest batch, then psi, 16 bytes
+ * a frame.  Refuses tracks outside [1, 5], B outside [1, 65535] and T_max outside [1, 2^31). */
+int mt2_formant_track_query(int tracks, long long T_max, int B, int* states, long long* workspace_bytes);
+/* freq, bw f32 [B, T_max, 5], count int32 [B, T_max] (device, as mt2_lpc_formants wrote them; frames at or beyond frame_lens[b] are never
+ * read), frame_lens host int32 [B] -> track_freq, track_bw f32 [B, T_max, 5], track_count int32 [B, T_max] and, unless NULL, sel int32
+ * [B, T_max, 5] (device).  ONE launch for the batch, a workgroup per utterance; the call only enqueues.  `m` may be a bare handle. */
+int mt2_formant_track(mt2_model* m, void* stream, const float* freq, const float* bw, const int32_t* count,
+                      const int32_t* frame_lens /*host*/, int T_max, int B, const mt2_formant_track_config* cfg,
+                      float* track_freq /*[B,T_max,5]*/, float* track_bw /*[B,T_max,5]*/, int32_t* track_count /*[B,T_max]*/,
+                      int32_t* sel /*[B,T_max,5] or NULL*/);
 
 /* ---- Integrated loudness and loudness normalisation (csrc/loudness.hip): ITU-R BS.1770-4 gated loudness, which EBU R 128 builds on, of
  * a ragged batch of mono utterances, and each utterance brought to a target loudness by one gain.  No reference counterpart (the

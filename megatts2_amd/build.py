@@ -21,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmegatts2_hip.so")
-UNITS = ["gemm_f32.hip", "gemm_x3h.hip", "gemm_dispatch.hip", "gemm_skinny.hip", "attention.hip", "rowops.hip", "sampling.hip", "resample.hip", "trim.hip", "segments.hip", "dtw.hip", "mcd.hip", "denoise.hip", "wpe.hip", "declip.hip", "griffinlim.hip", "f0.hip", "formants.hip", "prosody.hip", "loudness.hip", "ebu.hip", "limiter.hip", "model_load.hip",
+UNITS = ["gemm_f32.hip", "gemm_x3h.hip", "gemm_dispatch.hip", "gemm_skinny.hip", "attention.hip", "rowops.hip", "sampling.hip", "resample.hip", "trim.hip", "segments.hip", "dtw.hip", "mcd.hip", "denoise.hip", "wpe.hip", "declip.hip", "griffinlim.hip", "f0.hip", "formants.hip", "formant_track.hip", "prosody.hip", "loudness.hip", "ebu.hip", "limiter.hip", "model_load.hip",
          "model_stages.hip"]
 AUDITED = ["gemm_f32.hip", "gemm_x3h.hip"]      # units whose device assembly is audited (inline-asm LDS reads in loops)
 DEPS = ["mt2_kernels.h", "mt2_block_reduce.h", "mt2_model.h", "gemm_common.h", "gemm_tiles.h", "x3h_planes.h", "x3h_window.h", "planes_store.h", "philox.h", "true_peak_tile.h", "capi.inc", os.path.join("..", "..", "include", "megatts2_hip.h")]

@@ -896,6 +896,27 @@ int mt2_formant_stats(mt2_model* m, void* stream, const float* freq, const int32
     MT2_API_END
 }
 
+// formant tracks across frames: the states and the arena bytes of a call, without a HIP call
+int mt2_formant_track_query(int tracks, long long T_max, int B, int* states, long long* workspace_bytes) {
+    MT2_API_BEGIN
+    formant_track_check_shape(tracks, T_max, B);
+    if (states) *states = formant_track_states(tracks);
+    if (workspace_bytes) *workspace_bytes = formant_track_arena_bytes(B, T_max);
+    MT2_API_END
+}
+
+// the K candidates per frame on the cheapest smooth path (formant_track.hip); every refusal is decided on the host before the first HIP call
+int mt2_formant_track(mt2_model* m, void* stream, const float* freq, const float* bw, const int32_t* count, const int32_t* frame_lens, int T_max,
+                      int B, const mt2_formant_track_config* cfg, float* track_freq, float* track_bw, int32_t* track_count, int32_t* sel) {
+    MT2_API_BEGIN
+    formant_track_check_config(cfg);
+    const FormantTrackIO a{freq, bw, count, track_freq, track_bw, track_count, sel};
+    formant_track_check_call(a, frame_lens, T_max, B);
+    MT2_AUDIO_CALL(m, stream);
+    formant_track_run(c, a, frame_lens, T_max, B, *cfg);
+    MT2_API_END
+}
+
 // the energy contour on the F0 / mel frames (prosody.hip); every refusal is decided on the host before the first HIP call
 int mt2_frame_energy(mt2_model* m, void* stream, const float* wav, const int32_t* lens, int L_max, int B, int hop, float* energy,
                      int T_max) {

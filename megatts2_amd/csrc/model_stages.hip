@@ -2417,6 +2417,71 @@ static void formant_stats_run(const Ctx& c, const float* freq, const int32_t* co
     MT2_HIP(launch_formant_stats(freq, count, f0, ip.dev(o_len), T_max, B, stats, c.s));
 }
 
+// ---- formant tracks across frames (formant_track.hip): every refusal is decided here, on the host, before the first HIP call -------
+static_assert(sizeof(mt2_formant_track_config) == 72 && offsetof(mt2_formant_track_config, ref_hz) == 8 &&
+                  offsetof(mt2_formant_track_config, freq_cost) == 48 && offsetof(mt2_formant_track_config, jump_cost) == 64,
+              "runtime.MT2FormantTrackConfig mirrors this layout");
+static void formant_track_check_shape(int tracks, long long T_max, int B) {
+    MT2_REQUIRE(tracks >= 1 && tracks <= MT2_FORMANT_MAX, "tracks outside [1, 5]");
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(T_max >= 1 && T_max <= INT_MAX, "T_max outside [1, 2^31)");
+}
+static void formant_track_check_config(const mt2_formant_track_config* cfg) {
+    MT2_REQUIRE(cfg != nullptr, "null formant track config");
+    MT2_REQUIRE(cfg->tracks >= 1 && cfg->tracks <= MT2_FORMANT_MAX, "tracks outside [1, 5]");
+    MT2_REQUIRE(cfg->reserved == 0, "mt2_formant_track_config.reserved must be 0");
+    for (int q = 0; q < cfg->tracks; ++q) MT2_REQUIRE(std::isfinite(cfg->ref_hz[q]) && cfg->ref_hz[q] > 0.0, "ref_hz must be finite and > 0");
+    MT2_REQUIRE(std::isfinite(cfg->freq_cost) && cfg->freq_cost >= 0.0, "freq_cost must be finite and >= 0");
+    MT2_REQUIRE(std::isfinite(cfg->bw_cost) && cfg->bw_cost >= 0.0, "bw_cost must be finite and >= 0");
+    MT2_REQUIRE(std::isfinite(cfg->jump_cost) && cfg->jump_cost >= 0.0, "jump_cost must be finite and >= 0");
+}
+struct FormantTrackIO { const float* freq; const float* bw; const int32_t* count; float* tfreq; float* tbw; int32_t* tcount; int32_t* sel; };
+static void formant_track_check_call(const FormantTrackIO& a, const int* frame_lens, int T_max, int B) {
+    MT2_REQUIRE(B >= 1 && B <= 65535, "B outside [1, 65535]");
+    MT2_REQUIRE(a.freq != nullptr && a.bw != nullptr && a.count != nullptr && frame_lens != nullptr && a.tfreq != nullptr && a.tbw != nullptr &&
+                    a.tcount != nullptr && T_max >= 1,
+                "bad buffers");
+    MT2_REQUIRE((((uintptr_t)a.freq | (uintptr_t)a.bw | (uintptr_t)a.count | (uintptr_t)a.tfreq | (uintptr_t)a.tbw | (uintptr_t)a.tcount |
+                  (uintptr_t)a.sel) & 3) == 0,
+                "misaligned buffers");
+    check_lens(frame_lens, B, T_max, "frame count outside [1, T_max]");
+    const size_t nt = 4 * (size_t)B * T_max, n5 = nt * MT2_FORMANT_MAX;
+    MT2_REQUIRE(!outputs_overlap({{a.tfreq, n5}, {a.tbw, n5}, {a.tcount, nt}, {a.sel, n5}}, {{a.freq, n5}, {a.bw, n5}, {a.count, nt}}),
+                "overlapping buffers");
+}
+// the arena of one mt2_formant_track call, in carve order: the lengths in the room of the largest batch, psi
+struct FormantTrackWs { int* len; unsigned char* psi; };
+template <class Ws> static FormantTrackWs formant_track_carve(Ws& ws, size_t B, size_t T_max) {
+    FormantTrackWs w{};
+    w.len = ws.template get<int>(65535);
+    w.psi = ws.template get<unsigned char>(16 * B * T_max);
+    return w;
+}
+static long long formant_track_arena_bytes(int B, long long T_max) {
+    ArenaCount count;
+    formant_track_carve(count, B, T_max);
+    return (long long)count.bytes;
+}
+// enqueues only: the lengths travel in the call's one upload
+static void formant_track_run(const Ctx& c, const FormantTrackIO& a, const int* frame_lens, int T_max, int B, const mt2_formant_track_config& cfg) {
+    const FormantTrackWs w = formant_track_carve(c.ws, B, T_max);
+    int* st = static_cast<int*>(c.m.pinned().alloc(sizeof(int) * B));      // handle-owned staging
+    std::copy(frame_lens, frame_lens + B, st);
+    MT2_HIP(hipMemcpyAsync(w.len, st, sizeof(int) * B, hipMemcpyHostToDevice, c.s));
+    FormantTrackP p{};
+    p.freq = a.freq; p.bw = a.bw; p.count = a.count; p.len = w.len; p.T_max = T_max; p.B = B;
+    p.K = cfg.tracks; p.S = formant_track_states(cfg.tracks);
+    for (int q = 0; q < MT2_FORMANT_MAX; ++q) p.ref[q] = q < cfg.tracks ? cfg.ref_hz[q] : 0.0;
+    p.fc = cfg.freq_cost; p.bc = cfg.bw_cost; p.jc = cfg.jump_cost;
+    formant_track_table(cfg.tracks, p.st);
+    p.psi = w.psi; p.tfreq = a.tfreq; p.tbw = a.tbw; p.tcount = a.tcount; p.sel = a.sel;
+    Stages stg(c.m, c.s);
+    stg.mark("start");
+    MT2_HIP(launch_formant_track(p, c.s));
+    stg.mark("formant_track");
+    stg.finish();
+}
+
 // ---- per-phone prosody (prosody.hip): every refusal is decided here, on the host, before the first HIP call -------------------------
 // mt2_frame_energy; -> max_b lens[b]
 static int energy_check(const float* wav, const int* lens, int L_max, int B, int hop, const float* energy, int T_max) {

@@ -697,6 +697,21 @@ hipError_t launch_formants(const FormantP& p, hipStream_t s);
 hipError_t launch_formant_stats(const float* freq, const int* count, const float* f0, const int* frame_len, int T_max, int B, double* stats,
                                 hipStream_t s);
 
+// ---- formant tracks across frames: Viterbi over the candidates (formant_track.hip; the rule is in its header and in megatts2_hip.h) --
+// host only, no HIP call: C(5, K), and the increasing K-tuples of {0 .. 4} in lexicographic order, st[s][q] at st[5 s + q], zeros behind
+int formant_track_states(int K);
+void formant_track_table(int K, signed char* st /*[50]*/);
+// One launch, a workgroup (one wave) per utterance; frames in [len[b], T_max) are written zeros, count 0, sel -1.
+struct FormantTrackP {
+    const float* freq; const float* bw; const int* count;      // [B, T_max, 5], [B, T_max, 5], [B, T_max]
+    const int* len; int T_max, B, K, S;                         // device [B], each in [1, T_max]; S = formant_track_states(K)
+    double ref[5]; double fc, bc, jc;                           // ref_hz, freq_cost, bw_cost, jump_cost
+    signed char st[50];                                         // formant_track_table(K)
+    unsigned char* psi;                                         // scratch [B, T_max, 16], 16-byte aligned
+    float* tfreq; float* tbw; int* tcount; int* sel;            // [B, T_max, 5], [B, T_max, 5], [B, T_max], [B, T_max, 5] or null
+};
+hipError_t launch_formant_track(const FormantTrackP& p, hipStream_t s);
+
 // ---- per-phone prosody (prosody.hip; the rules are in its header and in megatts2_hip.h) ---------------------------------------------
 // energy[b, t] = the mean square of the F0 frame t of utterance b (a wave per frame); frames in [T_b, T_max) are written 0
 struct EnergyP {

@@ -22,7 +22,7 @@ from . import config as cfgmod
 from . import weights
 from .config import HIFIGAN_HOP_LENGTH, HIFIGAN_SR
 from .runtime import DECLIP_NAMES, DENOISE_NAMES, PAUSES_NAMES, WPE_NAMES, Declip, Denoise, Dereverb, Limiter, NativeError, NativeModel, Pauses  # noqa: F401  (Limiter, Denoise, Dereverb, Declip, Pauses: arguments of synthesize / forward)
-from .runtime import FORMANT_STAT_NAMES, Formants, resample_query
+from .runtime import FORMANT_STAT_NAMES, Formants, FormantTrack, resample_query
 from .sampling import PLMSampling, seed_array
 
 
@@ -121,7 +121,8 @@ def pitch_stats(f0, frame_lens=None) -> Dict[str, np.ndarray]:
     return {k: st[:, i].copy() for i, k in enumerate(PITCH_STATS)}
 
 
-def extract_formants(samples, sample_rate: Optional[int] = None, lens=None, formants: Optional[Formants] = None):
+def extract_formants(samples, sample_rate: Optional[int] = None, lens=None, formants: Optional[Formants] = None,
+                     track: Optional[FormantTrack] = None):
     """Formant candidates of a 1-D waveform (16 kHz, or at sample_rate) on the mel's frames: linear prediction on the GPU by the rule of
     csrc/formants.hip (MelFrontEnd.formants; no reference counterpart, parity with Praat's Burg fit and quality on real speech
     unpinned).  formants: a `Formants` (defaults: 5.5 kHz ceiling, order 10, 50 ms Hann, pre-emphasis from 50 Hz).  The audio is
@@ -131,7 +132,9 @@ def extract_formants(samples, sample_rate: Optional[int] = None, lens=None, form
     "count" int32 [T] (device), T = 1 + L16 // hop_length for the L16 samples the audio has at 16 kHz - the mel's frame count, so
     freq[t], extract_f0's f0[t] and mel frame t coincide (the resampled audio can hold one frame more, which is dropped: the three tensors are then views of the wider rows, not
     contiguous); "frame_lens"
-    (host int32 [B]), "rate", "hop".  A [B, L] input (lens: the rows' lengths) gives [B, T, ...]; frames behind a row's own are zeros."""
+    (host int32 [B]), "rate", "hop".  A [B, L] input (lens: the rows' lengths) gives [B, T, ...]; frames behind a row's own are zeros.
+    track: a `FormantTrack` adds "track_freq", "track_bw", "track_count" and "sel", `track_formants` of these candidates (ref_hz None at
+    this call's max_formant_hz); None (the default) is the call of before, nothing tracked."""
     import torch
     fe = _frontend()
     cfg = formants or Formants()
@@ -157,10 +160,32 @@ def extract_formants(samples, sample_rate: Optional[int] = None, lens=None, form
     rows = max(T, 1 + int(np.max(ln)) // hop)
     res = fe.formants(x, ln, cfg, hop=hop, sample_rate=rate, out=torch.empty(B, rows, 5, device=x.device, dtype=torch.float32))
     out = {k: v[:, :T] for k, v in res.items()}
+    if track is not None:
+        out.update(fe.formant_track(out["freq"], out["bw"], out["count"], frame_lens, track, cfg.max_formant_hz))
     if not batched:
         out = {k: v[0] for k, v in out.items()}
     out.update(frame_lens=frame_lens, rate=rate, hop=hop)
     return out
+
+
+def track_formants(freq, bw, count, frame_lens=None, track: Optional[FormantTrack] = None, max_formant_hz: float = 5500.0):
+    """Formant tracks across frames of candidate rows freq, bw [T, 5] / [B, T, 5] and count [T] / [B, T] (extract_formants'): of every
+    frame's candidates the `track.tracks` that form the cheapest smooth path through the utterance's first frame_lens[b] frames, by a
+    Viterbi pass on the GPU (MelFrontEnd.formant_track; the rule is in include/megatts2_hip.h; parity with Praat's tracker and quality on
+    real speech unpinned) -> dict of device tensors in the input's layout: "track_freq", "track_bw" f32 [.., T, 5] (track q in slot q,
+    zeros behind), "track_count" int32 [.., T] (tracks, or 0 in a frame without that many sound candidates) and "sel" int32 [.., T, 5]
+    (the candidate slot of every track, -1 behind).  formant_stats(track_freq, track_count) is the intended use: one spurious root no
+    longer moves every formant above it.  track: a `FormantTrack` (None: its defaults; ref_hz None at max_formant_hz)."""
+    import torch
+
+    batched = (freq.dim() if hasattr(freq, "dim") else np.asarray(freq).ndim) == 3
+
+    def dev(a, dims, dtype):
+        t = a if hasattr(a, "is_cuda") else torch.as_tensor(np.asarray(a))
+        return (t if t.dim() == dims else t.unsqueeze(0)).to("cuda", dtype).contiguous()
+    out = _frontend().formant_track(dev(freq, 3, torch.float32), dev(bw, 3, torch.float32), dev(count, 2, torch.int32), frame_lens, track,
+                                    max_formant_hz)
+    return out if batched else {k: v[0] for k, v in out.items()}
 
 
 def formant_stats(freq, count, f0=None, frame_lens=None) -> Dict[str, np.ndarray]:
@@ -949,12 +974,14 @@ class Megatts:
         return {"phones": phone_prosody(f0, dur, energy, phone_lens, ml), "durations": duration_stats(dur, phone_lens), "f0": f0,
                 "energy": energy, "frame_lens": ml}
 
-    def output_formants(self, mel_lens, aux, tracker: str = "yin", formants: Optional[Formants] = None):
+    def output_formants(self, mel_lens, aux, tracker: str = "yin", formants: Optional[Formants] = None, track: Optional[FormantTrack] = None):
         """The formant figures of a synthesis call's own output: `mel_lens` and `aux` as `synthesize(..., return_aux=True)` returned
         them with a vocoder on.  The inference padding is taken off as `output_prosody` takes it off; the audio is tracked for F0
         (tracker "yin" or "viterbi") and analysed by `extract_formants` (formants: a `Formants`), and the figures are taken over the
         voiced frames with four candidates among the first mel_lens[b] -> formant_stats' dict (FORMANT_STAT_NAMES, float64 [B]) with
-        "freq", "bw", "count", "f0" (device, [B, T, ...]) and "frame_lens" beside it.  `aux` is not altered."""
+        "freq", "bw", "count", "f0" (device, [B, T, ...]) and "frame_lens" beside it.  `aux` is not altered.  track: a `FormantTrack` has
+        the candidates tracked across frames first (`track_formants`) and the figures taken over track_freq / track_count, which are
+        returned too with track_bw and sel; None (the default) is the call of before."""
         if tracker not in ("yin", "viterbi"):
             raise ValueError("tracker must be 'yin' or 'viterbi'")
         wav = aux.get("wav")
@@ -970,11 +997,14 @@ class Megatts:
         else:                                                                         # Griffin-Lim: (mel_lens - 1) hop samples
             x, lens = wav, (ml - 1) * hop
         f0 = (fe.f0 if tracker == "yin" else fe.f0_track)(x, lens)
-        res = extract_formants(x, None, lens, formants)
+        res = extract_formants(x, None, lens, formants, track)
         T = min(f0.shape[1], res["count"].shape[1])
         fl = np.minimum(np.minimum(ml, res["frame_lens"]), T).astype(np.int32)
-        out = formant_stats(res["freq"][:, :T], res["count"][:, :T], f0[:, :T], fl)
+        fk, ck = ("freq", "count") if track is None else ("track_freq", "track_count")
+        out = formant_stats(res[fk][:, :T], res[ck][:, :T], f0[:, :T], fl)
         out.update(freq=res["freq"], bw=res["bw"], count=res["count"], f0=f0, frame_lens=fl)
+        if track is not None:
+            out.update({k: res[k] for k in ("track_freq", "track_bw", "track_count", "sel")})
         return out
 
     def align_prompt(self, prompt_phone_tokens, mels, prompt_phone_lens=None, mel_lens=None, return_aux: bool = False):

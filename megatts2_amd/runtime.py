@@ -190,6 +190,36 @@ class Formants:
                                 float(self.fmin_hz), float(self.max_bandwidth_hz))
 
 
+class MT2FormantTrackConfig(C.Structure):
+    _fields_ = [("tracks", C.c_int32), ("reserved", C.c_int32), ("ref_hz", C.c_double * 5), ("freq_cost", C.c_double), ("bw_cost", C.c_double),
+                ("jump_cost", C.c_double)]
+
+
+FORMANT_TRACK_STATES = 10      # MT2_FORMANT_TRACK_STATES
+
+
+@dataclasses.dataclass(frozen=True)
+class FormantTrack:
+    """The settings of the formant tracks across frames (csrc/formant_track.hip; the rule is in include/megatts2_hip.h): of the up to five
+    candidates of every frame, the `tracks` that form the cheapest smooth path through the utterance.  A candidate on track q costs
+    `freq_cost` per kHz it lies from `ref_hz[q]` plus `bw_cost` times its bandwidth over its frequency; a step between frames costs
+    `jump_cost` times the relative change of every track.  ref_hz None: (2 q + 1) * max_formant_hz / 10, the formants of a uniform tube
+    scaled to the ceiling - Praat's 550, 1650, 2750, ... at 5500 Hz.  In the manner of Praat's "Formant: Track" (Xia and Espy-Wilson
+    2000) with a rule of our own; parity with Praat is unpinned."""
+    tracks: int = 4
+    ref_hz: Optional[Sequence[float]] = None
+    freq_cost: float = 1.0
+    bw_cost: float = 1.0
+    jump_cost: float = 1.0
+
+    def c_struct(self, max_formant_hz: float = 5500.0) -> MT2FormantTrackConfig:
+        ref = [(2 * q + 1) * float(max_formant_hz) / 10.0 for q in range(FORMANT_MAX)] if self.ref_hz is None else [float(r) for r in self.ref_hz]
+        if len(ref) < min(max(int(self.tracks), 0), FORMANT_MAX):
+            raise ValueError("ref_hz is shorter than tracks")
+        ref = (ref + [0.0] * FORMANT_MAX)[:FORMANT_MAX]
+        return MT2FormantTrackConfig(int(self.tracks), 0, (C.c_double * 5)(*ref), float(self.freq_cost), float(self.bw_cost), float(self.jump_cost))
+
+
 class MT2SegmentsConfig(C.Structure):
     _fields_ = [("top_db", C.c_float), ("min_pause", C.c_int32), ("min_speech", C.c_int32), ("pad", C.c_int32), ("keep", C.c_int32)]
 
@@ -344,6 +374,8 @@ def load_library():
     lib.mt2_formant_window.argtypes = [C.c_int, C.c_int, C.c_void_p]
     lib.mt2_lpc_formants.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5
     lib.mt2_formant_stats.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
+    lib.mt2_formant_track_query.argtypes = [C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mt2_formant_track.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 5
     lib.mt2_frame_energy.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.mt2_phone_prosody.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.mt2_pitch_contour.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
@@ -859,6 +891,32 @@ def _formant_stats(lib, h, freq, count, f0, ln):
     return stats
 
 
+def _formant_track_cfg(track, max_formant_hz: float) -> MT2FormantTrackConfig:
+    """a `FormantTrack` (its ref_hz at max_formant_hz), None (its defaults) or an MT2FormantTrackConfig as it stands"""
+    if isinstance(track, MT2FormantTrackConfig):
+        return track
+    return (track or FormantTrack()).c_struct(max_formant_hz)
+
+
+def _formant_track(lib, h, freq, bw, count, ln, track=None, max_formant_hz: float = 5500.0, return_sel: bool = True):
+    """mt2_formant_track on the handle `h`: freq, bw f32 [B, T, 5], count int32 [B, T] (device, as `_formants` returned them), ln int32
+    [B] -> dict of device tensors: track_freq, track_bw f32 [B, T, 5], track_count int32 [B, T] - the candidates' own layout, so
+    `_formant_stats` reads them unchanged - and sel int32 [B, T, 5] (the candidate slot of every track, -1 behind; None when not asked
+    for).  A frame without `tracks` sound candidates, and every frame behind ln[b], has zeros, count 0 and sel -1.  The call only
+    enqueues."""
+    import torch
+    assert freq.is_cuda and freq.dim() == 3 and freq.shape[2] == FORMANT_MAX and bw.is_cuda and bw.shape == freq.shape
+    assert count.is_cuda and count.shape == freq.shape[:2]
+    freq, bw, count = freq.contiguous().to(torch.float32), bw.contiguous().to(torch.float32), count.contiguous().to(torch.int32)
+    B, T = count.shape
+    c = _formant_track_cfg(track, max_formant_hz)
+    res = {"track_freq": torch.empty_like(freq), "track_bw": torch.empty_like(bw), "track_count": torch.empty_like(count),
+           "sel": torch.empty(B, T, FORMANT_MAX, device=freq.device, dtype=torch.int32) if return_sel else None}
+    _check(lib.mt2_formant_track(h, _stream(), _ptr(freq), _ptr(bw), _ptr(count), _iptr(ln), T, B, C.byref(c), _ptr(res["track_freq"]),
+                                 _ptr(res["track_bw"]), _ptr(res["track_count"]), _ptr(res["sel"])))
+    return res
+
+
 def _workspace_fill(lib, h, byte: int) -> None:
     """mt2_workspace_fill (test hook): every byte of the handle's arena := byte, after the handle's pending call; waits."""
     _check(lib.mt2_workspace_fill(h, int(byte)))
@@ -1329,6 +1387,11 @@ class NativeModel:
         """The formant figures float64 [B, 12] (device; FORMANT_STAT_NAMES) of candidate tracks (`_formant_stats`)."""
         return _formant_stats(self.lib, self.h, freq, count, f0, self._lens(frame_lens, count.shape[0], count.shape[1]))
 
+    def formant_track(self, freq, bw, count, frame_lens=None, track=None, max_formant_hz: float = 5500.0, return_sel: bool = True):
+        """The formant tracks across frames of candidate rows (`_formant_track`) -> dict: track_freq, track_bw, track_count, sel."""
+        return _formant_track(self.lib, self.h, freq, bw, count, self._lens(frame_lens, count.shape[0], count.shape[1]), track, max_formant_hz,
+                              return_sel)
+
     # ---- de-reverberation by weighted prediction error (csrc/wpe.hip) on the model's handle, as MelFrontEnd's
     def dereverb(self, wav, lens=None, dereverb: Optional[Dereverb] = None, return_figures: bool = False, out=None, audio=None):
         """De-reverberated audio of wav f32 [B, L] (`_dereverb`)."""
@@ -1742,6 +1805,18 @@ class MelFrontEnd:
         at one end with these means (17.5 cm for 500 / 1500 / 2500 / 3500 Hz).  All zeros without such a frame.  Sums in double, two
         passes.  The call only enqueues."""
         return _formant_stats(self.lib, self.h, freq, count, f0, self._frame_lens(frame_lens, count.shape[0], count.shape[1]))
+
+    def formant_track(self, freq, bw, count, frame_lens=None, track=None, max_formant_hz: float = 5500.0, return_sel: bool = True):
+        """Formant tracks across frames, the rule of csrc/formant_track.hip / include/megatts2_hip.h (no reference counterpart; parity with
+        Praat's "Formant: Track" and quality on real speech are unpinned): of the candidates freq, bw f32 [B, T, 5], count int32 [B, T]
+        (device, from `formants`) the `track.tracks` per frame that form the cheapest smooth path through the first frame_lens[b] frames,
+        by a Viterbi pass on the GPU, a workgroup per utterance -> dict of device tensors (`_formant_track`): track_freq, track_bw f32
+        [B, T, 5] (track q in slot q, zeros behind), track_count int32 [B, T] (`tracks`, or 0 in a frame without that many sound
+        candidates: a gap, which cuts the path) and sel int32 [B, T, 5] (the candidate slot each track took, -1 behind).  `formant_stats`
+        reads track_freq and track_count as it reads freq and count.  track: a `FormantTrack` (defaults: four tracks, all costs 1; its
+        ref_hz None is taken at max_formant_hz) or an MT2FormantTrackConfig.  The call only enqueues."""
+        return _formant_track(self.lib, self.h, freq, bw, count, self._frame_lens(frame_lens, count.shape[0], count.shape[1]), track,
+                              max_formant_hz, return_sel)
 
     # ---- per-phone prosody (csrc/prosody.hip)
     def energy(self, wav, lens=None, hop: Optional[int] = None, out=None):
@@ -2712,6 +2787,14 @@ def formant_query(L: int, sample_rate: int = 11000, hop: int = 176, window: int 
     f, ws = C.c_int(0), C.c_longlong(0)
     _check(load_library().mt2_formant_query(int(sample_rate), int(hop), int(window), int(order), int(L), C.byref(f), C.byref(ws)))
     return f.value, ws.value
+
+
+def formant_track_query(tracks: int = 4, T_max: int = 1, B: int = 1):
+    """mt2_formant_track_query (no device needed) -> (states, workspace_bytes): C(5, tracks) and the arena bytes of one `formant_track`
+    call, r(4 * 65535) + r(16 * B * T_max) with r rounding up to 256; NativeError where the rule refuses."""
+    st, ws = C.c_int(0), C.c_longlong(0)
+    _check(load_library().mt2_formant_track_query(int(tracks), int(T_max), int(B), C.byref(st), C.byref(ws)))
+    return st.value, ws.value
 
 
 def formant_window(window: int, kind: str = "hann") -> np.ndarray:
